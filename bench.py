@@ -18,7 +18,14 @@ barrier, the max-over-ranks time and the trivial result-summary gather.
   --total-pairs T  strong scaling: T pairs per step in total, rank r takes shard_pairs(T, N, r)
                    ("pairs/s at G = 1, 2, 4, 8 on the same 512 pairs", BASELINE configs[3])
 
-Extra objects in the line:
+A plain run sets up, warms up, times the K steps, writes the outputs of the last timed launch sequence when --dump-outputs DIR is
+given, and prints the line: metric / value / unit / higher_is_better / dtype / ms_per_step, the configuration, and everything
+else null.  --dump-outputs DIR writes, as float32 / float64 .npy files: num_pts (the keypoint count of every image of the last
+timed launch sequence) and, for a fixed seeded sample of its pairs (sample_images), the records a caller receives (x, y, octave,
+response, size, angle, features, match, distance, match_x, match_y; all records of the sampled images concatenated in order).
+The inputs are seeded: the same arguments give the same inputs in every run.
+
+--full adds every other measurement and check (each still switched off by its --no-* option):
   "verified"      the CPU oracle runs on ALL distinct pairs of the batch (16 pairs = 32 images); every slot of the last download of
                   every pipeline context, and every pair of an untimed summary pass, is digested (sha256 over the record fields)
                   and must equal the oracle's digest of its seed; same for the integer FAST leg (exit code 3 on a mismatch)
@@ -179,6 +186,25 @@ def summarize_pairs(counts, pts, gids):
         p1, p2 = pts[2 * k, :n1], pts[2 * k + 1, :n2]
         out[k] = (g, (n1 << 32) | n2, int((p1["match"] >= 0).sum()), pair_digest(p1, p2))
     return out
+
+
+DUMP_PAIRS = 8              # pairs of the last timed launch sequence whose records --dump-outputs writes (16 x 10000 records < 64 MB)
+
+
+def dump_outputs(out_dir, counts, pts):
+    """--dump-outputs: num_pts of every image of the launch sequence, and the records of a fixed seeded sample of its pairs (both
+    images each, records [0, num_pts) concatenated in sample order), every field as float32 (exact: small ints, float fields, bytes)"""
+    os.makedirs(out_dir, exist_ok=True)
+    npairs = len(counts) // 2
+    sample = np.sort(np.random.default_rng(2024).permutation(npairs)[:DUMP_PAIRS])
+    imgs = np.stack([2 * sample, 2 * sample + 1], axis=1).reshape(-1)
+    recs = np.concatenate([pts[i, :counts[i]] for i in imgs])
+    arrays = {"num_pts": counts.astype(np.float64), "sample_images": imgs.astype(np.float64)}
+    for f in KP_FIELDS + MATCH_FIELDS:
+        arrays[f] = recs[f].astype(np.float32)
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def gather_pair_summaries(local, device, use_dist):
@@ -806,6 +832,11 @@ def main():
                     help="internal: two serial launch sequences and the gather pass, nothing else (what run_pmc_legs profiles under rocprofv3 --pmc)")
     ap.add_argument("--launch", action="store_true",
                     help="go through the rank launcher even for --gpus 1 (N > 1 without a launcher always does)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every other leg: upload-inclusive, FAST path, verification gather, roofline (+ rocprofv3 --pmc child "
+                         "runs), oracle verification, cpu_baseline, configs (each still skipped by its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed launch sequence to DIR/<name>.npy (float32 / float64, at most 64 MB)")
     args = ap.parse_args()
     if args.single_pair_leg:
         return single_pair_leg()
@@ -814,6 +845,10 @@ def main():
     if args.pmc_leg:
         args.steps, args.warmup, args.serial, args.no_pipeline = 1, 1, True, True
         args.no_cpu_baseline = args.no_roofline = args.no_configs = args.no_verify = args.no_upload = args.no_fast = True
+    elif not args.full:
+        # a plain run times the headline path and nothing else
+        args.no_cpu_baseline = args.no_roofline = args.no_configs = args.no_verify = args.no_upload = args.no_fast = True
+    gather_pass = args.full or args.pmc_leg           # (the PMC legs profile the gather pass too: their byte counts divide by it)
     if args.config == 2:
         args.width, args.height, args.octaves, args.upright = 3840, 2160, 5, True
         args.pairs = min(args.pairs, 32)
@@ -892,9 +927,11 @@ def main():
     u8_pairs = [synth.pair(w, h, 1 + i) for i in range(NDIST)]
     seed_of = lambda k: (lo + k) % NDIST                     # noqa: E731
     assert len(chunks) <= 1 or B % NDIST == 0 or B >= my_pairs
-    host = np.stack([synth.to_float(u8_pairs[seed_of(i // 2)][i % 2], p) for i in range(nimg)])
-    d_imgs = torch.from_numpy(host).cuda()
-    del host
+    # the 2 * NDIST distinct float images go up once and are replicated into the batch on the device (same bytes as a host-built batch)
+    d_distinct = torch.from_numpy(np.stack([synth.to_float(u8_pairs[s][i], p) for s in range(NDIST) for i in (0, 1)])).cuda()
+    slot_src = torch.tensor([2 * seed_of(i // 2) + i % 2 for i in range(nimg)], dtype=torch.long, device="cuda")
+    d_imgs = d_distinct.index_select(0, slot_src).contiguous()
+    del d_distinct, slot_src
 
     # One stream per context when two contexts are in flight: the other context's launch sequence is what fills the small octaves'
     # gaps then, and per-context octave streams only add event waits and contention for the runtime's four hardware queues
@@ -910,9 +947,18 @@ def main():
     pipe.run(step_jobs * args.steps)
     fence(use_dist)
     elapsed = max_over_ranks(time.perf_counter() - t0, dist_dev, use_dist)
+    # what the last launch sequence of the timed region delivered (the host buffers of the context that ran it)
+    last_k = (len(step_jobs) * args.steps - 1) % NCTX
+    last_counts, last_pts = pipe.results(last_k) if my_pairs and args.steps > 0 else (None, None)
+    last_npairs, last_count = pipe.last_pairs[last_k], None
+    if rank == 0 and last_counts is not None:
+        last_count = (int(last_counts[:2 * last_npairs].sum()),
+                      sum(int((last_pts[2 * k, :last_counts[2 * k]]["match"] >= 0).sum()) for k in range(last_npairs)), last_npairs)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, last_counts[:2 * last_npairs], last_pts[:2 * last_npairs])
     # the last download of EVERY context of the timed region (checked slot by slot against the oracle below)
     timed_digests, first_slots = [], None
-    for k in range(NCTX):
+    for k in range(NCTX) if not args.no_verify else ():
         if pipe.last_pairs[k]:
             ck, pk = pipe.results(k)
             timed_digests.append(slot_digests(ck, pk, pipe.last_pairs[k]))
@@ -988,7 +1034,7 @@ def main():
     # all-gathered (the path's only collective); rank 0 checks the table
     local_rows = []
     c0 = 0
-    for c in chunks if my_pairs else []:
+    for c in chunks if my_pairs and gather_pass else []:
         pipe.enqueue(0, d_imgs, c)
         pipe.download(0, c)
         ck, pk = pipe.results(0)
@@ -999,11 +1045,13 @@ def main():
             pk["features"][0, 0, 0] ^= 1
         local_rows.append(summarize_pairs(ck, pk, [lo + c0 + k for k in range(c)]))
         c0 += c
-    table = gather_pair_summaries(np.concatenate(local_rows) if local_rows else np.zeros((0, 4), np.int64), dist_dev, use_dist)
-    golden_tab = None
-    if os.path.exists(CHECKSUM_FILE) and args.octaves == 4 and not args.upright:
-        golden_tab = json.load(open(CHECKSUM_FILE)).get(f"{w}x{h}")
-    gather = check_pair_table(table, args.total_pairs if strong else world * B, golden_tab) if rank == 0 else None
+    table, gather = None, None
+    if gather_pass:
+        table = gather_pair_summaries(np.concatenate(local_rows) if local_rows else np.zeros((0, 4), np.int64), dist_dev, use_dist)
+        golden_tab = None
+        if os.path.exists(CHECKSUM_FILE) and args.octaves == 4 and not args.upright:
+            golden_tab = json.load(open(CHECKSUM_FILE)).get(f"{w}x{h}")
+        gather = check_pair_table(table, args.total_pairs if strong else world * B, golden_tab) if rank == 0 else None
 
     # ---- roofline leg: the same launch sequence strictly serially on one stream with per-launch HIP events
     # (per-kernel durations are only meaningful without overlap; the timed region overlaps the octaves on separate streams)
@@ -1159,6 +1207,8 @@ def main():
 
     if rank == 0:
         total_pairs = (args.total_pairs if strong else world * B) * args.steps
+        kp_count = ((gather["keypoints"], gather["matches"], gather["pairs"]) if gather else
+                    last_count if last_count is not None else (0, 0, 0))
         out = {
             "metric": f"pairs_per_sec_detect_describe_match_{h}p", "value": round(total_pairs / elapsed, 2),
             "unit": "pairs/s", "n_gpus": world, "rccl_ranks": dist.get_world_size() if use_dist and backend == "nccl" else 0,
@@ -1177,8 +1227,9 @@ def main():
                        "float_sequences_enqueued": nseq_total,
                        "octave_streams": "one stream per context" if pipe.serial else "concurrent", "step_pipeline": NCTX,
                        "sharding": "independent pairs per rank, no data-path collective", "rank0_gpu_numa_node": numa_node,
-                       "keypoints_per_image": round(gather["keypoints"] / max(1.0, 2.0 * gather["pairs"]), 1),
-                       "matches_per_pair": round(gather["matches"] / max(1.0, float(gather["pairs"])), 1)},
+                       # from the gathered table with --full, else from rank 0's last timed launch sequence
+                       "keypoints_per_image": round(kp_count[0] / max(1.0, 2.0 * kp_count[2]), 1),
+                       "matches_per_pair": round(kp_count[1] / max(1.0, float(kp_count[2])), 1)},
             "verified": verified, "gather": gather, "roofline": roof, "cpu_baseline": cpu, "configs": extra,
             "upload_inclusive_pairs_per_s": None if upload_rate is None else round(upload_rate, 1),
             "fast_path_pairs_per_s": None if fast_rate is None else round(fast_rate, 1),

@@ -2,6 +2,7 @@
 
   fed_tau.json            FED tau tables produced by the REFERENCE's own fed.cpp (oracle/_ref/libfedref.so,
                           compiled from /root/reference/fed.cpp), as uint32 bit patterns
+  fed_tau_random.npz      the same for 300 seeded random process times (both reordering flags)
   left_right_u8.npz       the reference's only bundled input images (data/left.pgm, right.pgm; 1280x960 P5)
                           as uint8 arrays -- data, not source
   left_right_oracle.npz   oracle result on them (demo parameters main.cpp:156-166): points + match fields
@@ -42,6 +43,21 @@ def fed_golden():
     json.dump(dict(source="reference fed.cpp via oracle/_ref/libfedref.so", cases=cases),
               open(os.path.join(OUT, "fed_tau.json"), "w"))
     print("fed_tau.json", len(cases), "cases")
+
+
+def fed_random_golden():
+    """the 300 seeded random process times of tests/test_oracle_cpu.py::test_fed_tau_matches_live_reference_build, through the
+    reference's fed.cpp: per reordering flag the tau tables concatenated (uint32 bit patterns) and their lengths"""
+    okz.build()
+    assert okz.ref_lib() is not None, "needs the reference's fed.cpp built into oracle/_ref"
+    ts = np.random.default_rng(5).uniform(0.01, 300.0, 300).astype(np.float32)
+    out = {"T": ts}
+    for reorder in (0, 1):
+        taus = [okz.ref_fed_tau(float(T), 1, 0.25, reorder) for T in ts]
+        out[f"tau_bits_{reorder}"] = np.concatenate(taus).view(np.uint32)
+        out[f"tau_len_{reorder}"] = np.array([len(t) for t in taus], np.int32)
+    np.savez_compressed(os.path.join(OUT, "fed_tau_random.npz"), **out)
+    print("fed_tau_random.npz", 2 * len(ts), "cases")
 
 
 def read_pgm(path):

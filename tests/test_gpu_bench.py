@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from conftest import ROOT
@@ -27,7 +28,7 @@ def run_bench(extra, env_extra=None, timeout=900):
 
 
 def test_bench_contract_verified_and_roofline():
-    out = run_bench(["--steps", "2", "--warmup", "1", "--pairs", "16", "--no-cpu-baseline", "--no-configs"])
+    out = run_bench(["--full", "--steps", "2", "--warmup", "1", "--pairs", "16", "--no-cpu-baseline", "--no-configs"])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
               "dtype", "data", "config", "roofline", "cpu_baseline", "verified", "gather"):
         assert k in out, k
@@ -61,16 +62,44 @@ def test_bench_contract_verified_and_roofline():
     assert abs(mm["matrix_TOPs"] - mm["matrix_ops"] / (mm["ms"] * 1e-3) / 1e12) <= 0.06 * mm["matrix_TOPs"] + 0.1
 
 
+def test_bench_plain_run_times_only_and_dumps_what_it_computed(tmp_path):
+    """a plain run is the headline alone (every other leg is behind --full); --dump-outputs writes the last timed launch sequence:
+    its sampled pairs, rebuilt into records, digest to the committed one-GPU table of their seeds"""
+    sys.path.insert(0, ROOT)
+    import bench
+    import akaze_hip as ah
+    out = run_bench(["--steps", "3", "--warmup", "1", "--pairs", "16", "--dump-outputs", str(tmp_path)])
+    assert out["steps"] == 3 and out["metric"] == "pairs_per_sec_detect_describe_match_1080p" and out["unit"] == "pairs/s"
+    assert out["higher_is_better"] is True and out["dtype"] == "f32"
+    assert out["value"] > 100 and abs(out["value"] - 16 * 3 / (out["ms_per_step"] * 3e-3)) / out["value"] < 0.01
+    for k in ("verified", "gather", "roofline", "cpu_baseline", "configs", "upload_inclusive_pairs_per_s", "fast_path_pairs_per_s"):
+        assert out[k] is None, k
+    assert out["config"]["keypoints_per_image"] > 0 and out["config"]["float_sequences_enqueued"] == 4
+    d = {f[:-4]: np.load(os.path.join(tmp_path, f)) for f in os.listdir(tmp_path)}
+    assert all(a.dtype in (np.float32, np.float64) for a in d.values()) and sum(a.nbytes for a in d.values()) <= 64 << 20
+    counts, imgs = d["num_pts"].astype(np.int64), d["sample_images"].astype(np.int64)
+    assert len(counts) == 32 and len(imgs) == 16 and np.all(imgs[1::2] == imgs[0::2] + 1)
+    golden = json.load(open(bench.CHECKSUM_FILE))["1920x1080"]
+    recs = np.zeros(int(counts[imgs].sum()), ah.POINT_DTYPE)
+    for f in bench.KP_FIELDS + bench.MATCH_FIELDS:
+        recs[f] = d[f].astype(recs[f].dtype)
+    off = np.concatenate([[0], np.cumsum(counts[imgs])])
+    for j in range(0, len(imgs), 2):
+        p1, p2 = recs[off[j]:off[j + 1]], recs[off[j + 1]:off[j + 2]]
+        want = golden[str((imgs[j] // 2) % bench.NDIST)]
+        assert [(len(p1) << 32) | len(p2), int((p1["match"] >= 0).sum()), bench.pair_digest(p1, p2)] == want, imgs[j] // 2
+
+
 def test_bench_rccl_path_with_one_rank_weak_and_strong():
     """barrier / all_reduce(MAX) / all_gather over RCCL on the MI355X (world size 1), in both scaling modes"""
     env = {"HAK_BENCH_FORCE_DIST": "1", "MASTER_PORT": "29611"}
-    weak = run_bench(["--steps", "2", "--warmup", "1", "--pairs", "16", "--no-cpu-baseline", "--no-configs", "--no-roofline", "--no-fast",
+    weak = run_bench(["--full", "--steps", "2", "--warmup", "1", "--pairs", "16", "--no-cpu-baseline", "--no-configs", "--no-roofline", "--no-fast",
                       "--no-upload"], env)
     assert weak["scaling"] == "weak" and weak["config"]["total_pairs_per_step"] == 16 and weak["verified"]["slots_equal"]
     assert weak["upload_inclusive_pairs_per_s"] is None and weak["fast_path_pairs_per_s"] is None
     env["MASTER_PORT"] = "29612"
     # configs[3]'s shape through its shorthand, with fewer pairs: 40 pairs of 1280x720 = launch sequences of 16 + 16 + 8
-    strong = run_bench(["--config", "3", "--steps", "2", "--warmup", "1", "--pairs", "16", "--total-pairs", "40",
+    strong = run_bench(["--full", "--config", "3", "--steps", "2", "--warmup", "1", "--pairs", "16", "--total-pairs", "40",
                         "--no-cpu-baseline", "--no-configs", "--no-roofline"], env)
     assert strong["scaling"] == "strong" and strong["config"]["total_pairs_per_step"] == 40
     assert strong["metric"].endswith("720p") and strong["config"]["pairs_per_launch_sequence"] == 16
@@ -84,7 +113,7 @@ def test_bench_rccl_path_with_one_rank_weak_and_strong():
 def test_bench_through_its_own_rank_launcher():
     """`--launch`: bench.py starts torch.distributed.run itself (the N > 1 path of a plain `python bench.py --gpus N`) with one
     rank; the child runs over RCCL and the parent relays its line"""
-    out = run_bench(["--gpus", "1", "--launch", "--steps", "2", "--warmup", "1", "--pairs", "16", "--no-cpu-baseline", "--no-configs",
+    out = run_bench(["--gpus", "1", "--launch", "--full", "--steps", "2", "--warmup", "1", "--pairs", "16", "--no-cpu-baseline", "--no-configs",
                      "--no-roofline", "--no-fast", "--no-upload"], {"MASTER_PORT": "29613", "HAK_BENCH_FORCE_DIST": "1"})
     assert out["n_gpus"] == 1 and out["rccl_ranks"] == 1 and out["verified"]["slots_equal"]
 
@@ -104,7 +133,7 @@ def _run_two_ranks(extra_env, port):
     env.update({"HAK_BENCH_DIST_BACKEND": "gloo"})
     env.update(extra_env)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--config", "3", "--total-pairs", "37", "--pairs", "16", "--steps", "2", "--warmup", "1",
+           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--config", "3", "--total-pairs", "37", "--pairs", "16", "--steps", "2", "--warmup", "1",
            "--no-cpu-baseline", "--no-configs", "--no-roofline"]
     return subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
 

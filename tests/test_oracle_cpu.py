@@ -27,13 +27,20 @@ def test_fed_tau_matches_reference_golden(okz):
 
 
 def test_fed_tau_matches_live_reference_build(okz):
-    if okz.ref_lib() is None:
-        pytest.skip("oracle/_ref/libfedref.so not present (reference checkout absent)")
+    """300 seeded random process times: the reference's fed.cpp tables are frozen in tests/golden/fed_tau_random.npz
+    (make_golden.py fed_random_golden); where oracle/_ref/libfedref.so is built, the live reference must give them too"""
+    g = np.load(os.path.join(GOLDEN, "fed_tau_random.npz"))
     rng = np.random.default_rng(5)
-    for T in rng.uniform(0.01, 300.0, 300).astype(np.float32):
-        for reorder in (0, 1):
-            a, b = okz.fed_tau(float(T), 1, 0.25, reorder), okz.ref_fed_tau(float(T), 1, 0.25, reorder)
-            assert np.array_equal(a.view(np.uint32), b.view(np.uint32))
+    ts = rng.uniform(0.01, 300.0, 300).astype(np.float32)
+    assert np.array_equal(ts.view(np.uint32), g["T"].view(np.uint32))
+    live = okz.ref_lib() is not None
+    for reorder in (0, 1):
+        bits, offs = g[f"tau_bits_{reorder}"], np.concatenate([[0], np.cumsum(g[f"tau_len_{reorder}"])])
+        for i, T in enumerate(ts):
+            want = bits[offs[i]:offs[i + 1]]
+            assert np.array_equal(okz.fed_tau(float(T), 1, 0.25, reorder).view(np.uint32), want), (float(T), reorder)
+            if live:
+                assert np.array_equal(okz.ref_fed_tau(float(T), 1, 0.25, reorder).view(np.uint32), want), (float(T), reorder)
 
 
 def test_fed_schedule_kats(okz):

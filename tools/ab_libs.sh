@@ -4,7 +4,7 @@
 export HAK_BENCH_PMC=0
 for i in 1 2; do for v in "$@"; do
   if [ "$v" = "-" ]; then unset HAK_LIB; else export HAK_LIB=$PWD/cuda-akaze_amd/$v; fi
-  python bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-configs --no-upload --no-fast --no-verify > /tmp/ab_v.json 2>/dev/null
+  python bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-configs --no-upload --no-fast --no-verify > /tmp/ab_v.json 2>/dev/null
   python -c "
 import json; d=json.load(open('/tmp/ab_v.json')); c={x['class']:x['ms'] for x in d['roofline']['classes']}
 print('$v', d['value'], c)"

@@ -3,9 +3,9 @@
 
 Usage (on the GPU box, two separate passes as MI355X_MICROARCH.md prescribes -- FETCH_SIZE and
 WRITE_SIZE do not fit one pass):
-    rocprofv3 --pmc FETCH_SIZE --output-format csv -d gpurun_out/pmcF -- python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-roofline
-    rocprofv3 --pmc WRITE_SIZE --output-format csv -d gpurun_out/pmcW -- python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-roofline
-    python tools/pmc_traffic.py gpurun_out/pmcF gpurun_out/pmcW profiles/r03_pmc_traffic gpurun_out/pmcF.log
+    rocprofv3 --pmc FETCH_SIZE --output-format csv -d prof/pmcF -- python3 bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-roofline
+    rocprofv3 --pmc WRITE_SIZE --output-format csv -d prof/pmcW -- python3 bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-roofline
+    python tools/pmc_traffic.py prof/pmcF prof/pmcW profiles/r03_pmc_traffic prof/pmcF.log
 (the 4th argument is the stdout of the FETCH_SIZE pass: pairs per launch sequence and the number of sequences come from its JSON line)
 
 Units / corrections (MI355X_MICROARCH.md, HBM): the counters are in KiB; on gfx950 FETCH_SIZE reports
