@@ -43,6 +43,9 @@ assert POINT_DTYPE.itemsize == 104
 MATCH_PAIR_DTYPE = np.dtype([("query", "<i4"), ("train", "<i4"), ("distance", "<i4"), ("second", "<i4"),
                              ("x1", "<f4"), ("y1", "<f4"), ("x2", "<f4"), ("y2", "<f4")])      # hak_match_pair
 assert MATCH_PAIR_DTYPE.itemsize == 32
+HOMOGRAPHY_DTYPE = np.dtype([("H", "<f4", (9,)), ("inliers", "<i4"), ("hypothesis", "<i4"), ("refined", "<i4"),
+                             ("n", "<i4")])                                                   # hak_homography
+assert HOMOGRAPHY_DTYPE.itemsize == 52
 
 
 class HakError(RuntimeError):
@@ -90,6 +93,8 @@ SYMBOLS = {
     "hak_match_batch": (C.c_int, [_vp, _vp, _vp, C.c_int]),
     "hak_match_knn2": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _ip, _vp]),
     "hak_match_knn2_batch": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp]),
+    "hak_find_homography": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_float, C.c_uint, C.c_int, _vp, _vp]),
+    "hak_find_homography_batch": (C.c_int, [_vp, _vp, C.c_long, _vp, C.c_int, C.c_int, C.c_float, C.c_uint, C.c_int, _vp, _vp]),
     "hak_points_alloc": (C.c_int, [C.POINTER(_vp), C.c_int]),
     "hak_points_free": (C.c_int, [_vp]),
     "hak_image_alloc": (C.c_int, [C.POINTER(_vp), C.c_int, C.c_int, _ip]),
@@ -466,3 +471,23 @@ def cuMatchKnn(result1, result2, ratio=(1, 1), cross_check=True, max_dist=0, aka
     check(lib.hak_match_knn2(ctx, result1.d_data, n1, result2.d_data, result2.num_pts, int(ratio[0]), int(ratio[1]),
                              int(cross_check), int(max_dist), hptr, d_out.data_ptr(), C.byref(cnt), h_out.ctypes.data))
     return h_out[:cnt.value].copy()
+
+
+def findHomography(matches, iterations=1024, threshold=3.0, seed=0, refine=True, akazer=None):
+    """RANSAC homography over a match list (hipakaze.h hak_find_homography), on the device.  `matches`: the MATCH_PAIR_DTYPE
+    array cuMatchKnn returns (host), or a device tensor of such records (then it is used in place).  Returns (record of
+    HOMOGRAPHY_DTYPE, inlier mask as a uint8 numpy array); record["H"].reshape(3, 3) maps (x1, y1, 1) to image 2."""
+    import torch
+    ctx = akazer.ctx if akazer is not None else None
+    if isinstance(matches, torch.Tensor):
+        d_m = matches.contiguous()
+        n = d_m.numel() * d_m.element_size() // MATCH_PAIR_DTYPE.itemsize
+    else:
+        host = np.ascontiguousarray(matches, MATCH_PAIR_DTYPE)
+        n = len(host)
+        d_m = torch.from_numpy(host.view(np.uint8).reshape(-1)).cuda() if n else torch.zeros(32, dtype=torch.uint8, device="cuda")
+    d_mask = torch.zeros(max(n, 1), dtype=torch.uint8, device="cuda")
+    out = np.zeros((), HOMOGRAPHY_DTYPE)
+    check(lib.hak_find_homography(ctx, d_m.data_ptr(), n, int(iterations), float(threshold), int(seed) & 0xFFFFFFFF, int(bool(refine)),
+                                  d_mask.data_ptr(), out.ctypes.data))
+    return out, d_mask[:n].cpu().numpy()

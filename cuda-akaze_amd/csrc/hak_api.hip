@@ -347,7 +347,8 @@ extern "C" void hak_destroy(hak_ctx* c)
     for (auto& p : c->prof)
         for (auto ev : p.ev) (void)hipEventDestroy(ev);
     hak_match_scratch_free(&c->msc);
-    void* bufs[] = {c->arena, c->maps, c->bitmap, c->rowcount, c->cand, c->state, c->d_num, c->dtab, c->knn, c->d_cnt, c->perm, c->pair_pts};
+    void* bufs[] = {c->arena, c->maps, c->bitmap, c->rowcount, c->cand, c->state, c->d_num, c->dtab, c->knn, c->d_cnt, c->perm, c->pair_pts,
+                    c->hom_slots, c->hom_rec};
     for (void* b : bufs) (void)hipFree(b);
     if (c->h_num) (void)hipHostFree(c->h_num);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -1159,6 +1160,74 @@ extern "C" int hak_match_knn2_batch(hak_ctx* c, hak_point* d_points, const int* 
       hak_launch_knn2_finish(c->stream, d_points, d_points + mp, d_num_pts, 0, 2 * mp, 2 * mp, npairs, fwd, cross_check ? rev : nullptr,
                              mp, ratio_num, ratio_den, cross_check ? 1 : 0, max_dist, d_out, mp, d_counts); }
     if (hipGetLastError() != hipSuccess) return fail("knn2 launch failed");
+    return 0;
+}
+
+// ----------------------------------------------------------- geometric verification: RANSAC homography (kernels_homography.hip)
+static int homography_args(int iterations, float threshold, int refine)
+{
+    if (iterations < 1 || iterations > 65536) return fail("iterations must be in 1 .. 65536");
+    if (!std::isfinite(threshold) || !(threshold > 0.f)) return fail("threshold must be finite and > 0");
+    if (refine != 0 && refine != 1) return fail("refine must be 0 or 1");
+    return 0;
+}
+
+// grow-only; a buffer being replaced may still be read by an earlier call on the context's stream (hipFree waits for the device)
+static int homography_scratch(hak_ctx* c, long slots)
+{
+    if (slots > c->hom_cap) {
+        if (c->hom_slots) HIP_TRY(hipFree(c->hom_slots));
+        c->hom_slots = nullptr;
+        c->hom_cap = 0;
+        HIP_TRY(hipMalloc((void**)&c->hom_slots, sizeof(unsigned long long) * (size_t)slots));
+        c->hom_cap = slots;
+    }
+    if (!c->hom_rec) HIP_TRY(hipMalloc((void**)&c->hom_rec, sizeof(hak_homography)));
+    return 0;
+}
+
+extern "C" int hak_find_homography(hak_ctx* c, const hak_match_pair* d_matches, int n, int iterations, float threshold,
+                                   unsigned seed, int refine, unsigned char* d_mask, hak_homography* h_out)
+{
+    if (!h_out || (!d_matches && n > 0)) return fail("null argument");
+    if (n < 0) return fail("n < 0");
+    if ((reinterpret_cast<uintptr_t>(d_matches) & 15) != 0) return fail("d_matches must be 16-byte aligned");
+    if (homography_args(iterations, threshold, refine)) return 1;
+    if (hak_device_count() == 0) return fail("no HIP device: libhipakaze has no CPU fallback");
+    const long slots = hak_homography_blocks(1, iterations, nullptr);
+    unsigned long long* d_slots = nullptr;
+    hak_homography* d_rec = nullptr;
+    if (c) {
+        if (homography_scratch(c, slots)) return 1;
+        d_slots = c->hom_slots;
+        d_rec = c->hom_rec;
+    } else {
+        HIP_TRY(hipMalloc((void**)&d_slots, sizeof(unsigned long long) * (size_t)slots));
+        if (hipMalloc((void**)&d_rec, sizeof(hak_homography)) != hipSuccess) { (void)hipFree(d_slots); return fail("hipMalloc"); }
+    }
+    hipStream_t st = c ? c->stream : nullptr;
+    order_after_null_stream(c, st);
+    hak_launch_homography(st, d_matches, n, nullptr, n, 1, iterations, threshold, seed, refine, d_slots, d_rec, d_mask, 0);
+    int rc = 0;
+    if (hipGetLastError() != hipSuccess) rc = fail("homography launch failed");
+    if (!rc && hipStreamSynchronize(st) != hipSuccess) rc = fail("hipStreamSynchronize(homography)");
+    if (!rc && hipMemcpy(h_out, d_rec, sizeof(hak_homography), hipMemcpyDeviceToHost) != hipSuccess) rc = fail("homography download");
+    if (!c) { (void)hipFree(d_slots); (void)hipFree(d_rec); }
+    return rc;
+}
+
+extern "C" int hak_find_homography_batch(hak_ctx* c, const hak_match_pair* d_matches, long stride, const int* d_counts, int npairs,
+                                         int iterations, float threshold, unsigned seed, int refine, hak_homography* d_out,
+                                         unsigned char* d_masks)
+{
+    if (!c || !d_matches || !d_counts || !d_out || npairs < 1 || stride < 1) return fail("bad argument");
+    if ((reinterpret_cast<uintptr_t>(d_matches) & 15) != 0) return fail("d_matches must be 16-byte aligned");
+    if (homography_args(iterations, threshold, refine)) return 1;
+    if (homography_scratch(c, (long)npairs * hak_homography_blocks(npairs, iterations, nullptr))) return 1;
+    order_after_null_stream(c, c->stream);
+    hak_launch_homography(c->stream, d_matches, stride, d_counts, 0, npairs, iterations, threshold, seed, refine, c->hom_slots, d_out,
+                          d_masks, stride);
+    if (hipGetLastError() != hipSuccess) return fail("homography launch failed");
     return 0;
 }
 

@@ -80,6 +80,9 @@ struct hak_ctx {
                                     // (hak_stream_pays), 2 always where covered (env HAK_FUSE_SF)
     int4* knn = nullptr;            // 2-NN scratch: fwd[batch/2][max_pts] | rev[batch/2][max_pts], allocated on first use
     int* d_cnt = nullptr;
+    unsigned long long* hom_slots = nullptr;  // RANSAC scratch: best key per (pair, score block), grown on demand
+    long hom_cap = 0;
+    hak_homography* hom_rec = nullptr;        // the record of hak_find_homography before its download
     hak_point* pair_pts = nullptr;  // [2][cfg.max_pts]: the contiguous pair layout hak_detect_and_compute_pair detects into and matches on
     HakMatchScratch msc;            // sliced searches of one big pair (hak_match / hak_match_knn2): grows on demand, on this context's device
     HakKnobs knobs;                 // kernel-selection knobs of THIS context (two contexts of a process may differ)

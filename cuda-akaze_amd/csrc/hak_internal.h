@@ -485,6 +485,13 @@ void hak_launch_knn2_finish(hipStream_t st, hak_point* pts1, const hak_point* pt
                             int ratio_den, int cross, int max_dist, hak_match_pair* out, long out_stride, int* out_count,
                             HakMatchScratch* scratch = nullptr);
 
+// RANSAC homography (kernels_homography.hip): score blocks per pair (and hypotheses per block through hp_out); the launcher
+// writes one uint64 slot per (pair, block) to `slots` (npairs * hak_homography_blocks(...) of them)
+int hak_homography_blocks(int npairs, int iterations, int* hp_out);
+void hak_launch_homography(hipStream_t st, const hak_match_pair* matches, long stride, const int* counts, int n_host, int npairs,
+                           int iterations, float threshold, unsigned seed, int refine, unsigned long long* slots,
+                           hak_homography* out, unsigned char* masks, long mask_stride);
+
 // A launcher that cannot do what it was asked (a precondition its caller should have checked) records the reason here instead
 // of aborting; enqueue_detect turns it into the call's error (hak_api.hip).  Thread-local, like hak_last_error().
 void hak_note_launch_error(const char* msg);

@@ -1,0 +1,370 @@
+// kernels_homography.hip -- RANSAC homography over the match lists of hak_match_knn2(_batch) (gfx950, wave64).
+//
+// The semantics are fixed in include/hipakaze.h (hak_find_homography) so that the numpy reference tests/homography_ref.py
+// agrees bit for bit: a counter-based sample generator (splitmix64 of seed, hypothesis and draw), a float64 closed-form solve
+// through two square-to-quad maps, float32 scoring in one fixed expression, and a float64 least-squares refit whose sums have
+// a fixed order (lane l of one wave takes matches i = l mod 64 in ascending i, then an xor butterfly over 32 .. 1).
+// The file is built with -ffp-contract=off: no FMA is formed, so every rounding is the one the reference makes.
+//
+// k_hom_score: grid (pair, hypothesis block), 256 threads.  A block owns `hp` hypotheses (16 .. 256, a power of two) and
+//   256 / hp match slices: thread t scores hypothesis t mod hp against the records j = t / hp (mod 256 / hp) of each chunk.
+//   Every thread draws and solves its hypothesis in registers; the pair's records stream through LDS in chunks of HG_CHUNK
+//   float4 {x1, y1, x2, y2}, read back with ds_read_b128 where the lanes of a wave share one address (hp >= 64) or four
+//   consecutive ones (hp = 16).  Each block writes its best key (inliers << 32 | ~h) to its own slot [pair][block]: no atomics
+//   and nothing to clear before a call.
+// k_hom_finish: one wave per pair: reduces the slots, re-derives the winner through the same device function, refits, re-scores,
+//   writes the mask and the record.
+#include "hak_internal.h"
+
+#define HG_CHUNK 1024            // records per LDS chunk: 16 KB, so that several blocks share a CU
+#define HG_THREADS 256
+
+__device__ __forceinline__ unsigned long long hg_mix64(unsigned long long z)
+{
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+// the last 16 bytes of a hak_match_pair; a record with a non-finite coordinate gets x1 = NaN, which fails every test below
+__device__ __forceinline__ float4 hg_load(const hak_match_pair* m, int i)
+{
+    float4 r = *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(m + i) + 16);
+    if (!(__builtin_isfinite(r.x) && __builtin_isfinite(r.y) && __builtin_isfinite(r.z) && __builtin_isfinite(r.w)))
+        r.x = __builtin_nanf("");
+    return r;
+}
+
+__device__ __forceinline__ int hg_count(const int* counts, int pair, int n_host, long stride)
+{
+    long n = counts ? counts[pair] : n_host;
+    return (int)(n < 0 ? 0 : (n > stride ? stride : n));
+}
+
+__device__ __forceinline__ bool hg_inlier(const float H[9], const float4 r, const float t2)
+{
+    const float wz = (H[6] * r.x + H[7] * r.y) + 1.0f;
+    const float u = (H[0] * r.x + H[1] * r.y) + H[2];
+    const float v = (H[3] * r.x + H[4] * r.y) + H[5];
+    const float ex = u - r.z * wz, ey = v - r.w * wz;
+    return wz > 0.0f && ex * ex + ey * ey < t2 * (wz * wz);
+}
+
+// the closed-form map of the unit square (0,0) (1,0) (1,1) (0,1) onto the quad x[0..3], y[0..3] (Heckbert), S[8] = 1
+__device__ __forceinline__ void hg_square_to_quad(const double x[4], const double y[4], double S[9])
+{
+    const double dx1 = x[1] - x[2], dx2 = x[3] - x[2], dx3 = ((x[0] - x[1]) + x[2]) - x[3];
+    const double dy1 = y[1] - y[2], dy2 = y[3] - y[2], dy3 = ((y[0] - y[1]) + y[2]) - y[3];
+    const double den = dx1 * dy2 - dx2 * dy1;
+    const double g = (dx3 * dy2 - dx2 * dy3) / den;
+    const double h = (dx1 * dy3 - dx3 * dy1) / den;
+    S[0] = (x[1] - x[0]) + g * x[1]; S[1] = (x[3] - x[0]) + h * x[3]; S[2] = x[0];
+    S[3] = (y[1] - y[0]) + g * y[1]; S[4] = (y[3] - y[0]) + h * y[3]; S[5] = y[0];
+    S[6] = g; S[7] = h; S[8] = 1.0;
+}
+
+__device__ __forceinline__ void hg_mul3(const double A[9], const double B[9], double C[9])
+{
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+        for (int j = 0; j < 3; j++) C[3 * i + j] = (A[3 * i] * B[j] + A[3 * i + 1] * B[3 + j]) + A[3 * i + 2] * B[6 + j];
+}
+
+// divide by [2][2] and round to float32 with H[8] = 1; false if [2][2] is 0 or anything is non-finite
+__device__ __forceinline__ bool hg_to_float(const double F[9], float H[9])
+{
+    const double d = F[8];
+    if (!(d != 0.0) || !__builtin_isfinite(d)) return false;
+    bool ok = true;
+#pragma unroll
+    for (int k = 0; k < 8; k++) { H[k] = (float)(F[k] / d); ok = ok && __builtin_isfinite(H[k]); }
+    H[8] = 1.0f;
+    return ok;
+}
+
+__device__ __forceinline__ double hg_cross(const double x[4], const double y[4], int a, int b, int c)
+{
+    return (x[b] - x[a]) * (y[c] - y[a]) - (y[b] - y[a]) * (x[c] - x[a]);
+}
+
+// hypothesis h of a pair with n matches: false when it is degenerate (no four distinct indices within 16 draws, a triple with
+// |cross| <= 1 px^2 or a flipped orientation in either image, a non-finite or singular solve)
+__device__ bool hg_hypothesis(const hak_match_pair* m, int n, unsigned seed, int h, float H[9])
+{
+    if (n < 4) return false;
+    int i0 = -1, i1 = -1, i2 = -1, i3 = -1, k = 0;
+#pragma unroll
+    for (int d = 0; d < 16; d++) {
+        if (k < 4) {
+            const unsigned long long r =
+                hg_mix64((unsigned long long)seed + (unsigned long long)(16 * (unsigned)h + d + 1) * 0x9E3779B97F4A7C15ull);
+            const int j = (int)(((r >> 32) * (unsigned long long)n) >> 32);
+            if (j != i0 && j != i1 && j != i2) {
+                if (k == 0) i0 = j; else if (k == 1) i1 = j; else if (k == 2) i2 = j; else i3 = j;
+                k++;
+            }
+        }
+    }
+    if (k < 4) return false;
+    const int idx[4] = {i0, i1, i2, i3};
+    double ax[4], ay[4], bx[4], by[4];
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+        const float4 r = hg_load(m, idx[q]);
+        ax[q] = r.x; ay[q] = r.y; bx[q] = r.z; by[q] = r.w;
+    }
+    const int T[4][3] = {{0, 1, 2}, {0, 1, 3}, {0, 2, 3}, {1, 2, 3}};
+#pragma unroll
+    for (int t = 0; t < 4; t++) {
+        const double c1 = hg_cross(ax, ay, T[t][0], T[t][1], T[t][2]);
+        const double c2 = hg_cross(bx, by, T[t][0], T[t][1], T[t][2]);
+        if (!(fabs(c1) > 1.0 && fabs(c2) > 1.0 && ((c1 > 0.0) == (c2 > 0.0)))) return false;   // (NaN fails)
+    }
+    double S1[9], S2[9], A[9], F[9];
+    hg_square_to_quad(ax, ay, S1);
+    hg_square_to_quad(bx, by, S2);
+    // adj(S1)
+    A[0] = S1[4] * S1[8] - S1[5] * S1[7]; A[1] = S1[2] * S1[7] - S1[1] * S1[8]; A[2] = S1[1] * S1[5] - S1[2] * S1[4];
+    A[3] = S1[5] * S1[6] - S1[3] * S1[8]; A[4] = S1[0] * S1[8] - S1[2] * S1[6]; A[5] = S1[2] * S1[3] - S1[0] * S1[5];
+    A[6] = S1[3] * S1[7] - S1[4] * S1[6]; A[7] = S1[1] * S1[6] - S1[0] * S1[7]; A[8] = S1[0] * S1[4] - S1[1] * S1[3];
+    hg_mul3(S2, A, F);
+    return hg_to_float(F, H);
+}
+
+__device__ __forceinline__ double hg_wsum(double v)
+{
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v = v + __shfl_xor(v, off);
+    return v;
+}
+__device__ __forceinline__ int hg_wsum(int v)
+{
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+
+// inliers of H over the pair (one wave, every lane returns the total)
+__device__ int hg_count_inliers(const hak_match_pair* m, int n, const float H[9], float t2)
+{
+    int c = 0;
+    for (int i = threadIdx.x; i < n; i += HAK_WAVE) c += hg_inlier(H, hg_load(m, i), t2) ? 1 : 0;
+    return hg_wsum(c);
+}
+
+// least-squares refit of H's inliers (one wave; every lane computes the same): Hartley normalisation, 8x8 normal equations
+// with h22 = 1, Gaussian elimination with partial pivoting, all in float64.  False when the system is singular or the result
+// is not finite.
+__device__ bool hg_refit(const hak_match_pair* m, int n, const float H[9], float t2, float R[9])
+{
+    const int l = threadIdx.x;
+    int cnt = 0;
+    double sx1 = 0.0, sy1 = 0.0, sx2 = 0.0, sy2 = 0.0;
+    for (int i = l; i < n; i += HAK_WAVE) {
+        const float4 r = hg_load(m, i);
+        if (!hg_inlier(H, r, t2)) continue;
+        cnt++;
+        sx1 = sx1 + (double)r.x; sy1 = sy1 + (double)r.y; sx2 = sx2 + (double)r.z; sy2 = sy2 + (double)r.w;
+    }
+    const double mm = (double)hg_wsum(cnt);
+    const double c1x = hg_wsum(sx1) / mm, c1y = hg_wsum(sy1) / mm, c2x = hg_wsum(sx2) / mm, c2y = hg_wsum(sy2) / mm;
+    double q1 = 0.0, q2 = 0.0;
+    for (int i = l; i < n; i += HAK_WAVE) {
+        const float4 r = hg_load(m, i);
+        if (!hg_inlier(H, r, t2)) continue;
+        const double dx1 = (double)r.x - c1x, dy1 = (double)r.y - c1y, dx2 = (double)r.z - c2x, dy2 = (double)r.w - c2y;
+        q1 = q1 + (dx1 * dx1 + dy1 * dy1);
+        q2 = q2 + (dx2 * dx2 + dy2 * dy2);
+    }
+    const double s1 = sqrt((2.0 * mm) / hg_wsum(q1)), s2 = sqrt((2.0 * mm) / hg_wsum(q2));
+    // rows a = [X, Y, 1, 0, 0, 0, -X U, -Y U] (target U), b = [0, 0, 0, X, Y, 1, -X V, -Y V] (target V); N = upper triangle of
+    // sum a^T a + b^T b, row-major; g = sum a U + b V
+    double N[36], g[8];
+#pragma unroll
+    for (int k = 0; k < 36; k++) N[k] = 0.0;
+#pragma unroll
+    for (int k = 0; k < 8; k++) g[k] = 0.0;
+    for (int i = l; i < n; i += HAK_WAVE) {
+        const float4 r = hg_load(m, i);
+        if (!hg_inlier(H, r, t2)) continue;
+        const double X = s1 * ((double)r.x - c1x), Y = s1 * ((double)r.y - c1y);
+        const double U = s2 * ((double)r.z - c2x), V = s2 * ((double)r.w - c2y);
+        const double a[8] = {X, Y, 1.0, 0.0, 0.0, 0.0, -(X * U), -(Y * U)};
+        const double b[8] = {0.0, 0.0, 0.0, X, Y, 1.0, -(X * V), -(Y * V)};
+        int k = 0;
+#pragma unroll
+        for (int p = 0; p < 8; p++)
+#pragma unroll
+            for (int q = p; q < 8; q++, k++) N[k] = N[k] + (a[p] * a[q] + b[p] * b[q]);
+#pragma unroll
+        for (int p = 0; p < 8; p++) g[p] = g[p] + (a[p] * U + b[p] * V);
+    }
+    double M[8][9];
+    {
+        int k = 0;
+#pragma unroll
+        for (int p = 0; p < 8; p++)
+#pragma unroll
+            for (int q = p; q < 8; q++, k++) { const double v = hg_wsum(N[k]); M[p][q] = v; M[q][p] = v; }
+#pragma unroll
+        for (int p = 0; p < 8; p++) M[p][8] = hg_wsum(g[p]);
+    }
+#pragma unroll
+    for (int c = 0; c < 8; c++) {
+        int piv = c;
+        double best = fabs(M[c][c]);
+#pragma unroll
+        for (int r = c + 1; r < 8; r++) {
+            const double v = fabs(M[r][c]);
+            if (v > best) { best = v; piv = r; }
+        }
+        if (!(best > 0.0) || !__builtin_isfinite(best)) return false;
+#pragma unroll
+        for (int r = c + 1; r < 8; r++)                             // (selects, no dynamic register indexing)
+            if (r == piv)
+#pragma unroll
+                for (int q = c; q < 9; q++) { const double t = M[c][q]; M[c][q] = M[r][q]; M[r][q] = t; }
+#pragma unroll
+        for (int r = c + 1; r < 8; r++) {
+            const double f = M[r][c] / M[c][c];
+#pragma unroll
+            for (int q = c + 1; q < 9; q++) M[r][q] = M[r][q] - f * M[c][q];
+        }
+    }
+    double Hn[9];
+#pragma unroll
+    for (int i = 7; i >= 0; i--) {
+        double acc = M[i][8];
+#pragma unroll
+        for (int j = i + 1; j < 8; j++) acc = acc - M[i][j] * Hn[j];
+        Hn[i] = acc / M[i][i];
+    }
+    Hn[8] = 1.0;
+    const double is2 = 1.0 / s2;
+    const double T1[9] = {s1, 0.0, -(s1 * c1x), 0.0, s1, -(s1 * c1y), 0.0, 0.0, 1.0};
+    const double T2i[9] = {is2, 0.0, c2x, 0.0, is2, c2y, 0.0, 0.0, 1.0};
+    double G[9], F[9];
+    hg_mul3(Hn, T1, G);
+    hg_mul3(T2i, G, F);
+    return hg_to_float(F, R);
+}
+
+__global__ __launch_bounds__(HG_THREADS) void k_hom_score(const hak_match_pair* __restrict__ base, long stride,
+                                                          const int* __restrict__ counts, int n_host, int iterations, int hp,
+                                                          float t2, unsigned seed, unsigned long long* __restrict__ slots)
+{
+    __shared__ float4 rec[HG_CHUNK];
+    __shared__ int part[HG_THREADS];
+    __shared__ unsigned long long wbest[HG_THREADS / HAK_WAVE];
+    const int pair = blockIdx.x, t = threadIdx.x;
+    const hak_match_pair* m = base + (long)pair * stride;
+    const int n = hg_count(counts, pair, n_host, stride);
+    const int h = blockIdx.y * hp + (t & (hp - 1));
+    const int slice = t / hp, nslice = HG_THREADS / hp;
+    float H[9];
+    const bool ok = h < iterations && hg_hypothesis(m, n, seed, h, H);
+    int cnt = 0;
+    for (int c0 = 0; c0 < n; c0 += HG_CHUNK) {
+        const int len = min(HG_CHUNK, n - c0);
+        __syncthreads();                                            // the previous chunk is consumed
+        for (int j = t; j < len; j += HG_THREADS) rec[j] = hg_load(m, c0 + j);
+        __syncthreads();
+        if (ok) {
+#pragma unroll 4
+            for (int j = slice; j < len; j += nslice) cnt += hg_inlier(H, rec[j], t2) ? 1 : 0;
+        }
+    }
+    part[t] = cnt;
+    __syncthreads();
+    unsigned long long key = 0;
+    if (t < hp) {
+        int s = 0;
+        for (int k = 0; k < nslice; k++) s += part[t + k * hp];
+        if (ok) key = ((unsigned long long)s << 32) | (unsigned)~h;
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const unsigned long long o = __shfl_xor(key, off);
+        key = o > key ? o : key;
+    }
+    if ((t & (HAK_WAVE - 1)) == 0) wbest[t / HAK_WAVE] = key;
+    __syncthreads();
+    if (t == 0) {
+        unsigned long long b = wbest[0];
+#pragma unroll
+        for (int w = 1; w < HG_THREADS / HAK_WAVE; w++) b = wbest[w] > b ? wbest[w] : b;
+        slots[(long)pair * gridDim.y + blockIdx.y] = b;
+    }
+}
+
+__global__ __launch_bounds__(HAK_WAVE) void k_hom_finish(const hak_match_pair* __restrict__ base, long stride,
+                                                         const int* __restrict__ counts, int n_host, int hblocks, float t2,
+                                                         unsigned seed, int refine, const unsigned long long* __restrict__ slots,
+                                                         hak_homography* __restrict__ out, unsigned char* __restrict__ masks,
+                                                         long mask_stride)
+{
+    const int pair = blockIdx.x, l = threadIdx.x;
+    const hak_match_pair* m = base + (long)pair * stride;
+    const int n = hg_count(counts, pair, n_host, stride);
+    unsigned long long key = 0;
+    for (int k = l; k < hblocks; k += HAK_WAVE) {
+        const unsigned long long v = slots[(long)pair * hblocks + k];
+        key = v > key ? v : key;
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const unsigned long long o = __shfl_xor(key, off);
+        key = o > key ? o : key;
+    }
+    float H[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f};
+    int inl = 0, hyp = -1, refined = 0;
+    if (key != 0) {
+        hyp = (int)~(unsigned)key;
+        inl = (int)(key >> 32);
+        hg_hypothesis(m, n, seed, hyp, H);                          // non-degenerate: its key was written by the same function
+        float R[9];
+        if (refine && inl >= 4 && hg_refit(m, n, H, t2, R)) {
+            const int c = hg_count_inliers(m, n, R, t2);
+            if (c >= inl) {
+#pragma unroll
+                for (int k = 0; k < 9; k++) H[k] = R[k];
+                inl = c;
+                refined = 1;
+            }
+        }
+    }
+    if (masks) {
+        unsigned char* mk = masks + (long)pair * mask_stride;
+        for (int i = l; i < n; i += HAK_WAVE) mk[i] = (hyp >= 0 && hg_inlier(H, hg_load(m, i), t2)) ? 1 : 0;
+    }
+    if (l == 0) {
+        hak_homography o;
+#pragma unroll
+        for (int k = 0; k < 9; k++) o.H[k] = H[k];
+        o.inliers = inl; o.hypothesis = hyp; o.refined = refined; o.n = n;
+        out[pair] = o;
+    }
+}
+
+// hypotheses per score block: the largest power of two in 16 .. 256 that still gives >= 64 blocks over all pairs (a single pair
+// with 1024 hypotheses: 64 blocks of 16; 256 pairs: 4 blocks of 256 per pair)
+int hak_homography_blocks(int npairs, int iterations, int* hp_out)
+{
+    int hp = 256;
+    while (hp > 16 && (long)npairs * ((iterations + hp - 1) / hp) < 64) hp >>= 1;
+    if (hp_out) *hp_out = hp;
+    return (iterations + hp - 1) / hp;
+}
+
+void hak_launch_homography(hipStream_t st, const hak_match_pair* matches, long stride, const int* counts, int n_host, int npairs,
+                           int iterations, float threshold, unsigned seed, int refine, unsigned long long* slots,
+                           hak_homography* out, unsigned char* masks, long mask_stride)
+{
+    int hp = 0;
+    const int hblocks = hak_homography_blocks(npairs, iterations, &hp);
+    const float t2 = threshold * threshold;
+    k_hom_score<<<dim3(npairs, hblocks), HG_THREADS, 0, st>>>(matches, stride, counts, n_host, iterations, hp, t2, seed, slots);
+    k_hom_finish<<<npairs, HAK_WAVE, 0, st>>>(matches, stride, counts, n_host, hblocks, t2, seed, refine, slots, out, masks,
+                                              mask_stride);
+}

@@ -75,6 +75,26 @@ namespace akaze
         return count;
     }
 
+    int cuFindHomography(const hak_match_pair* matches, int n, float H[9], unsigned char* inlier_mask, int iterations, float threshold,
+                         unsigned seed, bool refine)
+    {
+        if (n < 0 || (n > 0 && !matches) || !H) { fprintf(stderr, "hip-akaze: cuFindHomography: bad argument\n"); exit(-1); }
+        hak_match_pair* d_matches = nullptr;
+        unsigned char* d_mask = nullptr;
+        if (n > 0) {
+            if (hipMalloc((void**)&d_matches, sizeof(hak_match_pair) * (size_t)n) != hipSuccess) die("cuFindHomography alloc");
+            if (inlier_mask && hipMalloc((void**)&d_mask, (size_t)n) != hipSuccess) die("cuFindHomography alloc");
+            if (hak_memcpy_h2d(d_matches, matches, (long)(sizeof(hak_match_pair) * (size_t)n))) die("cuFindHomography upload");
+        }
+        hak_homography r;
+        if (hak_find_homography(NULL, d_matches, n, iterations, threshold, seed, refine ? 1 : 0, d_mask, &r)) die("cuFindHomography");
+        if (d_mask && hak_memcpy_d2h(inlier_mask, d_mask, n)) die("cuFindHomography download");
+        for (int k = 0; k < 9; k++) H[k] = r.H[k];
+        if (d_mask) (void)hipFree(d_mask);
+        if (d_matches) (void)hipFree(d_matches);
+        return r.inliers;
+    }
+
     Akazer::Akazer() { hak_default_config(&cfg); }
 
     Akazer::~Akazer() { hak_destroy(ctx); }                              // akaze.cpp:74-77

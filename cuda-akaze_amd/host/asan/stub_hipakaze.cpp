@@ -86,7 +86,22 @@ int hak_match_knn2(hak_ctx*, hak_point* p1, int n1, const hak_point* p2, int n2,
     *count = c;
     return 0;
 }
-// the two HIP runtime calls of cuMatchKnn
+int hak_memcpy_h2d(void* dst, const void* src, long bytes) { memcpy(dst, src, (size_t)bytes); return 0; }
+int hak_memcpy_d2h(void* dst, const void* src, long bytes) { memcpy(dst, src, (size_t)bytes); return 0; }
+// reads every record and writes every mask byte (an undersized caller buffer is an ASan error); "inliers" are the even indices
+int hak_find_homography(hak_ctx*, const hak_match_pair* d, int n, int iterations, float threshold, unsigned, int refine,
+                        unsigned char* mask, hak_homography* out)
+{
+    if (!out || (n > 0 && !d) || iterations < 1 || !(threshold > 0.f) || (refine != 0 && refine != 1)) { g_err = "bad argument"; return 1; }
+    *out = hak_homography{{1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f}, 0, n >= 4 ? 0 : -1, 0, n};
+    for (int i = 0; i < n; i++) {
+        const bool in = n >= 4 && d[i].x1 == d[i].x1 && i % 2 == 0;
+        out->inliers += in;
+        if (mask) mask[i] = in;
+    }
+    return 0;
+}
+// the HIP runtime calls of cuMatchKnn and cuFindHomography
 hipError_t hipMalloc(void** p, size_t n) { *p = malloc(n); return *p ? hipSuccess : hipErrorOutOfMemory; }
 hipError_t hipFree(void* p) { free(p); return hipSuccess; }
 }

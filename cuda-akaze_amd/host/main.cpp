@@ -2,7 +2,7 @@
 // reads two binary PGMs (or synthesises a pair), uploads them, runs detectAndCompute on both images
 // `nrepeats` times and cuMatch once, and prints the same five result lines.
 //
-//   hipakaze_demo [device] [left.pgm right.pgm] [nrepeats] [--dump file] [--api-checks] [--pair]
+//   hipakaze_demo [device] [left.pgm right.pgm] [nrepeats] [--dump file] [--api-checks] [--pair] [--homography]
 //
 // --dump file   writes the host-side results as raw 104-byte AkazePoint records:
 //               int32 n1, n2, then n1 + n2 records of the float path (image 1 after cuMatch),
@@ -11,6 +11,9 @@
 //               detectAndCompute x 2 (+ cuMatch after the loop); the printed counts and the dumped records are the same
 // --api-checks  additionally drives Akazer through the call patterns of akaze.cpp:101-150 that the demo loop does not:
 //               an AkazeData smaller and larger than the default capacity, and an image size other than init()'s.
+// --homography  after the 2-NN match, estimates the homography between the two images from its matches (cuFindHomography: RANSAC,
+//               1024 hypotheses, 3 px, seed 0, least-squares refit) and prints it; with --dump, appends at the very end of the file
+//               int32 n, int32 inliers, float32 H[9], the n 32-byte hak_match_pair records and the n inlier-mask bytes.
 #include "akaze.h"
 #include <cmath>
 #include <cstdlib>
@@ -83,13 +86,14 @@ int main(int argc, char** argv)
     }
     std::cout << "===== Registration by HIP-AKAZE (MI355X) =====" << std::endl;
     std::string dumpPath;
-    bool apiChecks = false, pairCalls = false;
+    bool apiChecks = false, pairCalls = false, homography = false;
     {   // strip the options; what is left are the reference demo's positional arguments (main.cpp:131-135)
         int n = 1;
         for (int i = 1; i < argc; i++) {
             if (!strcmp(argv[i], "--dump") && i + 1 < argc) dumpPath = argv[++i];
             else if (!strcmp(argv[i], "--api-checks")) apiChecks = true;
             else if (!strcmp(argv[i], "--pair")) pairCalls = true;
+            else if (!strcmp(argv[i], "--homography")) homography = true;
             else argv[n++] = argv[i];
         }
         argc = n;
@@ -169,6 +173,18 @@ int main(int argc, char** argv)
     int ngood = akaze::cuMatchKnn(akaze_data1, akaze_data2, good.data(), 4, 5, true);
     float t5 = timer.read();
     std::cout << "2-NN ratio 0.8 + cross-check matches: " << ngood << "  (" << t5 - t4 << " ms)" << std::endl;
+    float hom[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f};
+    std::vector<unsigned char> inlier(good.size(), 0);
+    int ninlier = 0;
+    if (homography) {
+        float t6 = timer.read();
+        ninlier = akaze::cuFindHomography(good.data(), ngood, hom, inlier.data());
+        float t7 = timer.read();
+        std::cout << "Homography (RANSAC 1024 x 3 px, refit): " << ninlier << " inliers of " << ngood << "  (" << t7 - t6 << " ms)"
+                  << std::endl;
+        for (int r = 0; r < 3; r++)
+            std::cout << "  [" << hom[3 * r] << ", " << hom[3 * r + 1] << ", " << hom[3 * r + 2] << "]" << std::endl;
+    }
 
     // ---- the reference's second demo (main.cpp:227-300): the integer FAST path on the uint8 images
     std::cout << "===== FAST (16.16 fixed-point) path =====" << std::endl;
@@ -226,6 +242,14 @@ int main(int argc, char** argv)
         CHECK(hipFree(crop));
         akaze::freeAkazeData(small);
         akaze::freeAkazeData(large);
+    }
+
+    if (homography && dump.is_open()) {
+        const int hdr[2] = {ngood, ninlier};
+        dump.write((const char*)hdr, sizeof(hdr));
+        dump.write((const char*)hom, sizeof(hom));
+        dump.write((const char*)good.data(), sizeof(hak_match_pair) * (size_t)ngood);
+        dump.write((const char*)inlier.data(), (size_t)ngood);
     }
 
     akaze::freeAkazeData(akaze_data1);

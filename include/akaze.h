@@ -20,6 +20,12 @@ namespace akaze
     int cuMatchKnn(AkazeData& result1, AkazeData& result2, hak_match_pair* matches, int ratio_num = 1, int ratio_den = 1,
                    bool cross_check = true);
 
+    // build-side addition: RANSAC homography over a host match list (e.g. cuMatchKnn's), on the device (hak_find_homography):
+    // writes H (row-major, H[8] = 1; identity when there is no model) and, when inlier_mask is not NULL, n bytes (1 = inlier of H);
+    // returns the inlier count
+    int cuFindHomography(const hak_match_pair* matches, int n, float H[9], unsigned char* inlier_mask = nullptr, int iterations = 1024,
+                         float threshold = 3.f, unsigned seed = 0, bool refine = true);
+
     class Akazer
     {
     public:

@@ -179,6 +179,45 @@ int hak_match_knn2_batch(hak_ctx* ctx, hak_point* d_points, const int* d_num_pts
                          int ratio_num, int ratio_den, int cross_check, int max_dist,
                          hak_match_pair* d_out, int* d_counts);
 
+/* ---- geometric verification of a match list: RANSAC homography (build-side addition, "registration" of main.cpp:130).
+ * A pure function of (matches, iterations, threshold, seed, refine); tests/homography_ref.py is its bit-exact numpy statement.
+ * Input: n hak_match_pair records, the device list of hak_match_knn2 (only x1, y1, x2, y2 are read; 16-byte aligned).
+ *   1. Hypothesis h (0 <= h < iterations, 1 <= iterations <= 65536) draws r_d = mix64(seed + (16 h + d + 1) * 0x9E3779B97F4A7C15)
+ *      (splitmix64, mod 2^64) for d = 0..15 and takes index ((r_d >> 32) * n) >> 32 unless already chosen, until it has four.
+ *      It is degenerate without four distinct indices (and always when n < 4).
+ *   2. float64, no FMA: for the triples 012, 013, 023, 123 of the four points in each image c = (b - a) x (c - a); the sample is
+ *      degenerate unless |c| > 1 px^2 everywhere and sign(c) agrees between the images (NaN fails).  H = S2 * adj(S1) with S the
+ *      square-to-quad maps of the two quads (Heckbert), divided by H[2][2]; degenerate if that is 0 or anything is non-finite
+ *      after rounding to float32; H[8] = 1.
+ *   3. float32, no FMA: wz = (h6 x1 + h7 y1) + 1, u = (h0 x1 + h1 y1) + h2, v = (h3 x1 + h4 y1) + h5, ex = u - x2 wz, ey = v - y2 wz;
+ *      inlier iff wz > 0 and ex ex + ey ey < t2 (wz wz), t2 = threshold * threshold (threshold finite, > 0).  A record with a
+ *      non-finite coordinate is never an inlier (nor part of a usable sample).
+ *   4. The non-degenerate hypothesis with the most inliers wins, ties to the smallest h.
+ *   5. refine = 1 and >= 4 inliers: float64 least squares over the winner's inliers (Hartley normalisation per image: centroid,
+ *      s = sqrt(2 m / sum r^2); 8x8 normal equations with h22 = 1 by Gaussian elimination with partial pivoting; sums in a fixed
+ *      order: lane l of a wave takes matches i = l mod 64 ascending, then an xor butterfly over 32, 16, .., 1), denormalised,
+ *      divided by [2][2], rounded to float32 and re-scored.  It replaces the sample's H iff it is finite, the system was
+ *      non-singular and its inlier count is >= the sample's.
+ * Output: hypothesis = -1 means no model (H = identity, inliers = 0).  The optional mask gets 1 for every inlier of the returned H,
+ * 0 otherwise (n bytes). */
+typedef struct hak_homography {
+    float H[9];              /* row-major, x2 ~ (H[0] x1 + H[1] y1 + H[2]) / (H[6] x1 + H[7] y1 + 1); H[8] = 1 */
+    int   inliers;           /* inliers of H */
+    int   hypothesis;        /* winning hypothesis, -1 = no model */
+    int   refined;           /* 1 when H is the least-squares refit */
+    int   n;                 /* matches considered */
+} hak_homography;
+/* one list, synchronous: d_matches (device, n records), d_mask (device, n bytes) or NULL, result to *h_out.  ctx may be NULL
+ * (default stream; the call allocates its own scratch). */
+int hak_find_homography(hak_ctx* ctx, const hak_match_pair* d_matches, int n, int iterations, float threshold, unsigned seed,
+                        int refine, unsigned char* d_mask, hak_homography* h_out);
+/* batched, asynchronous on the context's stream, in the layout of hak_match_knn2_batch's output: pair k's list at
+ * d_matches + k*stride, its count d_counts[k] read on the device and clamped to [0, stride]; record k to d_out[k] (device), mask
+ * of pair k to d_masks + k*stride (device) unless d_masks is NULL. */
+int hak_find_homography_batch(hak_ctx* ctx, const hak_match_pair* d_matches, long stride, const int* d_counts, int npairs,
+                              int iterations, float threshold, unsigned seed, int refine, hak_homography* d_out,
+                              unsigned char* d_masks);
+
 /* ---- memory helpers: initAkazeData/freeAkazeData (akaze.cpp:26-52) and the
  * image upload of main.cpp:172-188 */
 int hak_points_alloc(hak_point** d_points, int count);
