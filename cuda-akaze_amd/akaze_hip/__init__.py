@@ -84,6 +84,7 @@ SYMBOLS = {
     "hak_phase_event": (C.c_int, [_vp, C.POINTER(C.c_void_p)]),
     "hak_set_concurrency": (C.c_int, [_vp, C.c_int]),
     "hak_set_null_order": (C.c_int, [_vp, C.c_int]),
+    "hak_set_retain_best": (C.c_int, [_vp, C.c_int]),
     "hak_detect_and_compute": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _ip, _vp, C.c_int]),
     "hak_detect_and_compute_pair": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, C.c_int, _ip, _ip, _vp, _vp, C.c_int, C.c_int]),
     "hak_detect_and_compute_batch": (C.c_int, [_vp, _vp, C.c_long, C.c_int, C.c_int, _vp, _vp, C.c_int]),
@@ -294,12 +295,14 @@ class Akazer:
     def __init__(self):
         self._ctx = None
         self._cfg = default_config()
+        self._retain_best = False
         self.whp = (0, 0, 0)
 
     def init(self, whp0, noctaves=4, max_scale=4, per=0.7, kcontrast=0.03, soffset=1.6, reordering=True,
              derivative_factor=1.5, dthreshold=0.001, diffusivity=PM_G2, descriptor_pattern_size=10,
-             max_pts=10000, upright=False, batch=1):
+             max_pts=10000, upright=False, batch=1, retain_best=False):
         self.whp = tuple(whp0)
+        self._retain_best = bool(retain_best)
         self._cfg = default_config(
             noctaves=noctaves, max_scale=max_scale, per=per, kcontrast=kcontrast, soffset=soffset,
             reordering=int(reordering), derivative_factor=derivative_factor, dthreshold=dthreshold,
@@ -313,6 +316,15 @@ class Akazer:
         check(lib.hak_create(C.byref(self._cfg), w, h, C.byref(ctx)))
         self._ctx = ctx
         self._ctx_wh = (w, h)
+        if self._retain_best:
+            check(lib.hak_set_retain_best(ctx, 1))
+
+    def set_retain_best(self, on=True):
+        """hak_set_retain_best: an image with more survivors than its clamp keeps its strongest ones instead of the raster-order
+        prefix (hipakaze.h states the rule).  Remembered: a context re-created for another image size keeps the mode."""
+        self._retain_best = bool(on)
+        if self._ctx is not None:
+            check(lib.hak_set_retain_best(self._ctx, int(self._retain_best)))
 
     @property
     def ctx(self):

@@ -275,6 +275,9 @@ extern "C" int hak_create(const hak_config* cfg, int w, int h, hak_ctx** out)
     A((void**)&c->cand, sizeof(unsigned long long) * (size_t)c->cand_cap * B);
     A((void**)&c->perm, sizeof(int) * (size_t)c->cfg.max_pts * B);
     A((void**)&c->state, sizeof(HakImgState) * (size_t)B);
+    A((void**)&c->sel.st, sizeof(HakSelState) * (size_t)B);
+    A((void**)&c->sel.bins, sizeof(unsigned) * HAK_SEL_PASSES * HAK_SEL_BINS * (size_t)B);
+    A((void**)&c->sel.tie, sizeof(int) * (size_t)L.oct[0].h * B);
     A((void**)&c->d_num, sizeof(int) * (size_t)B);
     A((void**)&c->dtab, sizeof(HakTables));
     if (e == hipSuccess) e = hipHostMalloc((void**)&c->h_num, sizeof(int) * (size_t)B);
@@ -348,7 +351,7 @@ extern "C" void hak_destroy(hak_ctx* c)
         for (auto ev : p.ev) (void)hipEventDestroy(ev);
     hak_match_scratch_free(&c->msc);
     void* bufs[] = {c->arena, c->maps, c->bitmap, c->rowcount, c->cand, c->state, c->d_num, c->dtab, c->knn, c->d_cnt, c->perm, c->pair_pts,
-                    c->hom_slots, c->hom_rec};
+                    c->hom_slots, c->hom_rec, c->sel.st, c->sel.bins, c->sel.tie};
     for (void* b : bufs) (void)hipFree(b);
     if (c->h_num) (void)hipHostFree(c->h_num);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -374,6 +377,15 @@ extern "C" int hak_set_null_order(hak_ctx* c, int on)
 {
     if (!c) return fail("null context");
     c->null_order = on != 0;
+    return 0;
+}
+
+// (the flag is read when a call enqueues its sequence: it is part of the graph key, so a sequence captured in one mode is never
+// replayed in the other; the scratch exists from hak_create on, so turning it on allocates nothing)
+extern "C" int hak_set_retain_best(hak_ctx* c, int on)
+{
+    if (!c) return fail("null context");
+    c->retain_best = on != 0;
     return 0;
 }
 
@@ -472,6 +484,7 @@ static int enqueue_detect(hak_ctx* c, const float* d_images, long image_stride, 
     const long S = L.arena;
     HakBatch b{A, S, nimg, c->state, c->maps, L.oct[0].plane, c->bitmap, c->rowcount, c->cand, c->cand_cap, &c->knobs, c->perm, cfg.max_pts};
     b.cap0 = cap0; b.cap1 = cap1;
+    if (c->retain_best) b.sel = c->sel;
     c->last_fast = false;
     c->fed_launches = 0;
     c->fed_fused_bytes = 0;
@@ -755,6 +768,7 @@ static int enqueue_fast_detect(hak_ctx* c, const unsigned char* d_images, long i
     int* A = reinterpret_cast<int*>(c->arena);
     const long S = L.arena;
     HakBatch b{c->arena, S, nimg, c->state, c->maps, L.oct[0].plane, c->bitmap, c->rowcount, c->cand, c->cand_cap, &c->knobs, c->perm, cfg.max_pts};
+    if (c->retain_best) b.sel = c->sel;
     const int idthreshold = 65;                                                   // akaze.cpp:559
     c->last_fast = true;
     c->sync_stream = c->stream;
@@ -899,6 +913,7 @@ static int run_detect_inner(hak_ctx* c, const float* d_images, long image_stride
     memset(&key, 0, sizeof(key));
     key.img = d_images; key.stride = image_stride; key.pitch = pitch; key.nimg = nimg; key.pts = d_points;
     key.num = d_num_pts; key.desc = desc; key.max_pts = max_pts; key.conc = c->concurrent ? 1 : 0; key.st = c->stream; key.hpts = h_pinned; key.cap0 = cap0; key.cap1 = cap1;
+    key.retain = c->retain_best ? 1 : 0;
     int slot = -1, victim = 0;
     for (int i = 0; i < hak_ctx::NGRAPH; i++) {
         if (c->graph_exec[i] && memcmp(&key, &c->gkey[i], sizeof(key)) == 0) slot = i;

@@ -263,6 +263,22 @@ struct HakKnobs {
 };
 HakKnobs hak_knobs_from_env();    // defaults overridden by the HAK_* variables (hak_api.hip)
 
+// Per-image state and scratch of the strongest-N selection (kernels_select.hip), allocated by hak_create for cfg.batch images.
+// Every word a call reads is written earlier in the same call (k_sel_init, k_sel_rows): nothing is cleared outside the sequence.
+struct HakSelState {
+    int active;                                 // survivors > clamp: this image selects (else every select kernel leaves at once)
+    int need;                                   // keys still to keep among those whose leading digits equal `prefix`
+    unsigned prefix;                            // the digits of the C-th largest key picked so far; after the last pass: the key T
+    int pad;
+};
+#define HAK_SEL_BINS 2048                       // radix digits of 11, 11 and 10 bits: three passes over the 32-bit key
+#define HAK_SEL_PASSES 3
+struct HakSelScratch {
+    HakSelState* st = nullptr;                  // [nimg]
+    unsigned* bins = nullptr;                   // [nimg][HAK_SEL_PASSES][HAK_SEL_BINS] global digit histograms
+    int* tie = nullptr;                         // [nimg][h0] keys equal to T per row
+};
+
 struct HakBatch {
     float* base;                  // arena of image 0
     long stride;                  // floats between consecutive image arenas
@@ -280,6 +296,8 @@ struct HakBatch {
     // per-image clamps of a PAIR call (hak_detect_and_compute_pair: the two AkazeData capacities, akaze.cpp:246, 451); 0: every
     // image is clamped at the launch's max_pts, which is always the record stride between images
     int cap0 = 0, cap1 = 0;
+    // scratch of the strongest-N selection (kernels_select.hip, hak_set_retain_best); sel.st == nullptr: the raster-order clamp
+    HakSelScratch sel{};
 };
 
 // scale space (kernels_scalespace.hip)
@@ -422,6 +440,8 @@ void hak_launch_download_pair(hipStream_t st, const hak_point* src, const int* d
 void hak_launch_nms_emit(hipStream_t st, const HakBatch& b, const HakLayout& L, const HakTables* tab, int psz,
                          hak_point* points, int max_pts, int* num_out, int fast = 0, int refine = 1);
 void hak_launch_clear_maps(hipStream_t st, const HakBatch& b, const HakLayout& L);
+// strongest-N selection (kernels_select.hip): prunes the survivor bitmap and rewrites the row counts between k_nms_cand and k_row_scan
+void hak_launch_select(hipStream_t st, const HakBatch& b, const HakLayout& L, int max_pts, int cap0, int cap1, int fast);
 void hak_launch_seed_maps(hipStream_t st, const HakBatch& b, const HakLayout& L, const unsigned* d_resp_bits, const int* d_layer);
 
 // integer FAST path (kernels_fast.hip); planes are int32 in the same arena layout

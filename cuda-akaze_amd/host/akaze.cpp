@@ -101,6 +101,11 @@ namespace akaze
 
     void Akazer::setMaxPoints(int max_pts) { cfg.max_pts = max_pts; hak_destroy(ctx); ctx = nullptr; }
     void Akazer::setUpright(bool upright) { cfg.upright = upright ? 1 : 0; hak_destroy(ctx); ctx = nullptr; }
+    void Akazer::setRetainBest(bool on)
+    {
+        retain_best = on;
+        if (ctx && hak_set_retain_best(ctx, on ? 1 : 0)) die("setRetainBest");
+    }
 
     void Akazer::ensureContext(int w, int h)
     {
@@ -108,6 +113,7 @@ namespace akaze
         hak_destroy(ctx);
         ctx = nullptr;
         if (hak_create(&cfg, w, h, &ctx)) die("Akazer: hak_create");
+        if (retain_best && hak_set_retain_best(ctx, 1)) die("Akazer: hak_set_retain_best");
         ctx_w = w;
         ctx_h = h;
     }

@@ -8,7 +8,7 @@
 #include <cstring>
 #include <string>
 
-struct hak_ctx { hak_config cfg; int w, h; };
+struct hak_ctx { hak_config cfg; int w, h; int retain_best; };
 static std::string g_err;
 int g_live_ctx = 0, g_live_dev = 0, g_live_host = 0;          // leak accounting checked by the driver
 
@@ -24,11 +24,12 @@ void hak_default_config(hak_config* c)
 int hak_create(const hak_config* cfg, int w, int h, hak_ctx** out)
 {
     if (w < 80 || h < 80) { g_err = "image smaller than 80 px"; return 1; }
-    *out = new hak_ctx{*cfg, w, h};
+    *out = new hak_ctx{*cfg, w, h, 0};
     g_live_ctx++;
     return 0;
 }
 void hak_destroy(hak_ctx* c) { if (c) { g_live_ctx--; delete c; } }
+int hak_set_retain_best(hak_ctx* c, int on) { if (!c) { g_err = "null context"; return 1; } c->retain_best = on != 0; return 0; }
 int hak_host_alloc(void** p, long bytes) { *p = malloc((size_t)bytes); g_live_host += *p != nullptr; return *p ? 0 : 1; }
 int hak_host_free(void* p) { g_live_host--; free(p); return 0; }
 int hak_points_alloc(hak_point** d, int count) { *d = (hak_point*)malloc(sizeof(hak_point) * (size_t)count); g_live_dev++; return *d ? 0 : 1; }

@@ -2,7 +2,7 @@
 // reads two binary PGMs (or synthesises a pair), uploads them, runs detectAndCompute on both images
 // `nrepeats` times and cuMatch once, and prints the same five result lines.
 //
-//   hipakaze_demo [device] [left.pgm right.pgm] [nrepeats] [--dump file] [--api-checks] [--pair] [--homography]
+//   hipakaze_demo [device] [left.pgm right.pgm] [nrepeats] [--dump file] [--api-checks] [--pair] [--homography] [--retain-best N]
 //
 // --dump file   writes the host-side results as raw 104-byte AkazePoint records:
 //               int32 n1, n2, then n1 + n2 records of the float path (image 1 after cuMatch),
@@ -14,6 +14,8 @@
 // --homography  after the 2-NN match, estimates the homography between the two images from its matches (cuFindHomography: RANSAC,
 //               1024 hypotheses, 3 px, seed 0, least-squares refit) and prints it; with --dump, appends at the very end of the file
 //               int32 n, int32 inliers, float32 H[9], the n 32-byte hak_match_pair records and the n inlier-mask bytes.
+// --retain-best N  both AkazeData get capacity N (instead of 10000) and Akazer::setRetainBest(true): an image with more keypoints
+//               keeps its N strongest (hak_set_retain_best), in raster order, on the float and the FAST path alike
 #include "akaze.h"
 #include <cmath>
 #include <cstdlib>
@@ -87,6 +89,7 @@ int main(int argc, char** argv)
     std::cout << "===== Registration by HIP-AKAZE (MI355X) =====" << std::endl;
     std::string dumpPath;
     bool apiChecks = false, pairCalls = false, homography = false;
+    int retainBest = 0;
     {   // strip the options; what is left are the reference demo's positional arguments (main.cpp:131-135)
         int n = 1;
         for (int i = 1; i < argc; i++) {
@@ -94,6 +97,7 @@ int main(int argc, char** argv)
             else if (!strcmp(argv[i], "--api-checks")) apiChecks = true;
             else if (!strcmp(argv[i], "--pair")) pairCalls = true;
             else if (!strcmp(argv[i], "--homography")) homography = true;
+            else if (!strcmp(argv[i], "--retain-best") && i + 1 < argc) retainBest = std::atoi(argv[++i]);
             else argv[n++] = argv[i];
         }
         argc = n;
@@ -118,7 +122,7 @@ int main(int argc, char** argv)
     std::cout << "Image size = (" << w << "," << h << ")" << std::endl;
 
     // configuration: main.cpp:155-166
-    int max_npts = 10000, noctaves = 4, max_scale = 4;
+    int max_npts = retainBest > 0 ? retainBest : 10000, noctaves = 4, max_scale = 4;
     float per = 0.7f, kcontrast = 0.03f, soffset = 1.6f, derivative_factor = 1.5f, dthreshold = 0.001f;
     bool reordering = true;
     int diffusivity = 1, descriptor_pattern_size = 10;
@@ -142,6 +146,7 @@ int main(int argc, char** argv)
     std::unique_ptr<akaze::Akazer> detector(new akaze::Akazer);
     detector->init(whp1, noctaves, max_scale, per, kcontrast, soffset, reordering, derivative_factor, dthreshold, diffusivity,
                    descriptor_pattern_size);
+    if (retainBest > 0) detector->setRetainBest(true);
 
     float t1 = timer.read();
     for (int i = 0; i < nrepeats; i++) {

@@ -47,6 +47,9 @@ namespace akaze
                                   const bool desc = true, const bool match = true);
         void setMaxPoints(int max_pts);      // capacity the context is built for (default 10000, main.cpp:155)
         void setUpright(bool upright);       // MLDB-upright extension
+        // an AkazeData that overflows keeps its result.max_pts STRONGEST keypoints (in raster order) instead of the first ones in
+        // raster order (hak_set_retain_best); remembered across context re-creation.  Default off.
+        void setRetainBest(bool on);
         hak_ctx* context() { return ctx; }
 
     private:
@@ -54,6 +57,7 @@ namespace akaze
         int3 whp{0, 0, 0};
         hak_ctx* ctx = nullptr;      // owns the arena (the reference's omem; room for the two images of a pair call), freed in the destructor
         int ctx_w = 0, ctx_h = 0;
+        bool retain_best = false;
         void ensureContext(int w, int h);
     };
 }

@@ -105,6 +105,19 @@ int hak_set_concurrency(hak_ctx* ctx, int on);
  * before its fill has run: tools/probes/memset_order_probe.hip).  0: no such dependency (a caller that drives the context from its
  * own stream, hak_set_stream, or captures graphs while calling).  Env HAK_NULL_ORDER=0 presets 0. */
 int hak_set_null_order(hak_ctx* ctx, int on);
+/* 0 (default): an image with more NMS survivors than its clamp keeps the raster-order prefix of them (the reference's behaviour
+ * up to its arbitrary arrival order).  1: it keeps its N strongest, N = the clamp (a call's max_pts, a pair call's per-image cap,
+ * cfg.max_pts in a batch), selected on the device before emission; refinement, orientation, MLDB and the pair call's match then
+ * run on the kept set only.  The rule, per image with S survivors in raster order and clamp C:
+ *   S <= C: the output does not change, byte for byte.
+ *   S >  C: the C survivors ranking highest by (K(response word), then the smaller raster index y * w + x of the integer
+ *           full-resolution position before refinement) are kept and emitted in raster order -- a subsequence of the
+ *           unclamped output, every record byte-identical to the unclamped call's; num_pts = C.
+ *   K maps the 32-bit response word order-preservingly to unsigned: float path (bits u) u >> 31 ? ~u : u | 0x80000000;
+ *   FAST path (int32 response) u ^ 0x80000000.
+ * Covers every detect entry point of the context (hak_detect_and_compute, _batch, _pair, hak_fast_detect_and_compute, _batch)
+ * and the test ABI's hak_op_tail_finish; takes effect with the next call, allocates nothing and does not synchronise. */
+int hak_set_retain_best(hak_ctx* ctx, int on);
 
 /* ---- Akazer::detectAndCompute (akaze.h:29, akaze.cpp:101-150), one image,
  * synchronous.  d_image: device float32, pitch elements per row.  d_points:
