@@ -132,21 +132,6 @@ extern "C" void hak_compare_indices(int* idx1, int* idx2)
 
 static inline int align_up(int a, int b) { return (a + b - 1) / b * b; }
 
-HakKnobs hak_knobs_from_env()
-{
-    HakKnobs k;
-    if (const char* e = getenv("HAK_HESS_STREAM")) k.hess_stream = atoi(e);
-    if (const char* e = getenv("HAK_BASE_STREAM")) k.base_stream = atoi(e);
-    if (const char* e = getenv("HAK_BASE_HIST")) k.base_hist = atoi(e);
-    if (const char* e = getenv("HAK_HESS_CBUF")) { const int v = atoi(e); k.hess_cbuf = v < 1 ? 1 : (v > 256 ? 256 : v); }
-    if (const char* e = getenv("HAK_DESC_ORDER")) { const int v = atoi(e); k.desc_order = v < 0 ? 0 : (v > 255 ? 255 : v); }
-    if (const char* e = getenv("HAK_DESC_PLAN")) k.desc_plan = atoi(e);
-    if (const char* e = getenv("HAK_LEVEL_TILE")) k.level_tile = atoi(e);
-    if (const char* e = getenv("HAK_HESS_LP")) k.hess_lp = atoi(e);
-    if (const char* e = getenv("HAK_DESC_SORT")) k.desc_sort = atoi(e);
-    return k;
-}
-
 static int build_plan(hak_ctx* c, int w, int h)
 {
     const hak_config& cfg = c->cfg;
@@ -251,14 +236,10 @@ extern "C" int hak_create(const hak_config* cfg, int w, int h, hak_ctx** out)
     c->cfg = *cfg;
     if (c->cfg.batch < 1) c->cfg.batch = 1;
     if (c->cfg.max_pts < 1) c->cfg.max_pts = 1;
-    if (const char* e = getenv("HAK_FUSE_SF")) c->fuse_sf = atoi(e);
-    if (const char* e = getenv("HAK_FUSE_HEAD")) c->fuse_head = atoi(e);
-    if (const char* e = getenv("HAK_LEVEL_MIN_STEPS")) c->level_min_steps = atoi(e);
-    c->knobs = hak_knobs_from_env();
-    if (const char* e = getenv("HAK_FED_MAX_FUSE")) {
-        int v = atoi(e);
-        c->max_fuse = v < 1 ? 1 : (v > HAK_FED_MAX_FUSE ? HAK_FED_MAX_FUSE : v);
-    }
+    c->knobs = hak_knobs_from_env();                // the environment is read here and nowhere else
+    c->concurrent = c->knobs.serial == 0;
+    c->use_graph = c->knobs.graph != 0;
+    c->null_order = c->knobs.null_order != 0;
     if (build_plan(c, w, h)) { delete c; return 1; }
     const int B = c->cfg.batch;
     const HakLayout& L = c->L;
@@ -289,7 +270,6 @@ extern "C" int hak_create(const hak_config* cfg, int w, int h, hak_ctx** out)
     if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_tail_fork, hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_phase, hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_null, hipEventDisableTiming);
-    if (const char* s = getenv("HAK_NULL_ORDER")) c->null_order = atoi(s) != 0;
     if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_tail_join, hipEventDisableTiming);
     // ... and so must the survivor bitmap and the row counts (hak_launch_clear_maps restores all three)
     if (e == hipSuccess) e = hipMemset(c->bitmap, 0, sizeof(unsigned long long) * (size_t)L.oct[0].h * words * B);
@@ -297,24 +277,21 @@ extern "C" int hak_create(const hak_config* cfg, int w, int h, hak_ctx** out)
     // (hipMemset fills on the NULL stream and may return before the fill has run; the context's streams are non-blocking and would
     // not wait for it)
     if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-    if (const char* s = getenv("HAK_HESS_SIDE")) c->hess_side = atoi(s);
-    // (only when asked for, and behind the octave streams: the runtime deals a process's streams to its four hardware queues in
-    // creation order, so one more stream per context moves every later stream to another queue -- creating it unconditionally put
-    // the two pipeline contexts of the bench on ONE queue: 45.0 instead of 41-42 ms per step, single-image calls 1.12 instead of 0.94 ms)
     for (int o = 0; o < L.noct && e == hipSuccess; o++) {
         if (o > 0) e = hipStreamCreateWithFlags(&c->oct_stream[o], hipStreamNonBlocking);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_ready[o], hipEventDisableTiming);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_done[o], hipEventDisableTiming);
     }
-    if (c->hess_side && e == hipSuccess) {
+    // (only when asked for, and behind the octave streams: the runtime deals a process's streams to its four hardware queues in
+    // creation order, so one more stream per context moves every later stream to another queue -- creating it unconditionally put
+    // the two pipeline contexts of the bench on ONE queue: 45.0 instead of 41-42 ms per step, single-image calls 1.12 instead of 0.94 ms)
+    if (c->knobs.hess_side && e == hipSuccess) {
         e = hipStreamCreateWithFlags(&c->hess_stream, hipStreamNonBlocking);
         for (int s = 0; s < HAK_MAX_SCALES && e == hipSuccess; s++) {
             e = hipEventCreateWithFlags(&c->ev_hs[s], hipEventDisableTiming);
             if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_hd[s], hipEventDisableTiming);
         }
     }
-    if (const char* s = getenv("HAK_SERIAL")) c->concurrent = atoi(s) == 0;
-    if (const char* s = getenv("HAK_GRAPH")) { c->graph_mode = atoi(s); c->use_graph = c->graph_mode != 0; }
     if (e != hipSuccess) {
         fail(std::string("hak_create: ") + hipGetErrorString(e));
         hak_destroy(c);
@@ -456,7 +433,7 @@ static bool level_tile_pays(const hak_ctx* c, const HakOct& oc, int nimg)
     // (round 4, measured: taking the tile kernel for the latency-bound small octaves of a LARGE batch as well -- octave 3, or octaves
     // 2-3, of 512 images -- cuts the FED launches from 46 to 26 / 18 and costs 8-17 ms per sequence: its halo work, (T + 2n)^2 / T^2
     // of the useful work, is only worth paying where launches, not bytes or arithmetic, are the cost)
-    return c->fuse_sf != 2 && (long)oc.w * oc.h * nimg <= HAK_LEVEL_TILE_MAX_PX;
+    return c->knobs.fuse_sf != 2 && (long)oc.w * oc.h * nimg <= HAK_LEVEL_TILE_MAX_PX;
 }
 
 // Launch-bound sequences -- a single image: octave 0 small enough for k_level_tile -- are issued in SPINE order (enqueue_detect) and
@@ -466,8 +443,8 @@ static bool level_tile_pays(const hak_ctx* c, const HakOct& oc, int nimg)
 // kernels, the replayed per-octave order is the better one for it (profiles/r04_pair_timeline.txt).
 static bool spine_pays(const hak_ctx* c, int nimg)
 {
-    static const long max_px = [] { const char* e = getenv("HAK_SPINE_MAX_PX"); return e ? atol(e) : 0L; }();
-    if (max_px > 0 && c->knobs.level_tile == 1) return c->fuse_sf != 2 && (long)c->L.oct[0].w * c->L.oct[0].h * nimg <= max_px;
+    const long max_px = c->knobs.spine_max_px;
+    if (max_px > 0 && c->knobs.level_tile == 1) return c->knobs.fuse_sf != 2 && (long)c->L.oct[0].w * c->L.oct[0].h * nimg <= max_px;
     return level_tile_pays(c, c->L.oct[0], nimg);
 }
 
@@ -491,7 +468,7 @@ static int enqueue_detect(hak_ctx* c, const float* d_images, long image_stride, 
 
     bool hess_fused[HAK_MAX_OCTAVES * HAK_MAX_SCALES] = {};
     bool hess_lp[HAK_MAX_OCTAVES * HAK_MAX_SCALES] = {};     // the level's Hessian low-passes Lt(o,s-1) itself: `smooth` was not written
-    static const bool level_hess_on = [] { const char* e = getenv("HAK_LEVEL_HESS"); return !e || atoi(e) != 0; }();
+    const bool level_hess_on = c->knobs.level_hess != 0;
     // ---- part A of level (o, s): build Lt(o, s) and the sigma=1 low-pass `smooth` the level's Hessian reads (akaze.cpp:325-421)
     // smooth_alt != nullptr: the level's sigma=1 low-pass goes there instead of the octave's `smooth` plane (side-stream Hessians below)
     auto build_level = [&](int o, int s, hipStream_t st, float* smooth_alt = nullptr) {
@@ -512,7 +489,7 @@ static int enqueue_detect(hak_ctx* c, const float* d_images, long image_stride, 
         // octave heads (one launch instead of decimation + conductivity + FED groups) and every cycle long enough that the tile
         // kernel's halo work costs less than the launches it saves (by the size rule: n >= 8, i.e. octaves 2 and up of the demo
         // schedule; shorter cycles keep k_smooth_flow + k_fed_multi, which spend less GPU time per pixel)
-        if (level_tile_pays(c, oc, nimg) && (s == 0 || n >= c->level_min_steps || c->knobs.level_tile == 2)) {
+        if (level_tile_pays(c, oc, nimg) && (s == 0 || n >= c->knobs.level_min_steps || c->knobs.level_tile == 2)) {
             ProfScope ps(c, HAK_PROF_FED, st);
             // (the level's Hessian rides along when the cycle is long enough: hess_fused tells hessian_level below)
             const int nl = hak_launch_level_tile(st, s == 0 ? A + L.lt(o - 1, 0) : A + L.lt(o, s - 1), s == 0 ? L.oct[o - 1] : oc, s == 0, smooth, Lt, tmp, S,
@@ -523,12 +500,12 @@ static int enqueue_detect(hak_ctx* c, const float* d_images, long image_stride, 
             c->fed_fused_bytes += (s == 0 ? 1.0 * L.oct[o - 1].w * L.oct[o - 1].h : 4.0 * oc.w * oc.h) + 8.0 * oc.w * oc.h + (nl - 1) * 12.0 * oc.w * oc.h;
             return;
         }
-        const int G = hak_fed_groups(n, c->max_fuse, oc.w);     // launches of this FED cycle
+        const int G = hak_fed_groups(n, c->knobs.max_fuse, oc.w);     // launches of this FED cycle
         const float* fsrc;          // input of the first FED launch
         bool fused_first = false;
         if (s == 0) {                                                             // akaze.cpp:369-392
             // octave head: decimation + low-pass + conductivity + the first FED group in one streaming pass when covered
-            if (c->fuse_head && hak_stream_pays(c->fuse_sf, oc.w, oc.h, nimg)) {
+            if (c->knobs.fuse_head && hak_stream_pays(c->knobs.fuse_sf, oc.w, oc.h, nimg)) {
                 ProfScope ps(c, HAK_PROF_FED, st);
                 fused_first = hak_launch_fed_sf_head(st, A + L.lt(o - 1, 0), L.oct[o - 1], smooth, flow, (G % 2 == 1) ? Lt : tmp, S, oc,
                                                      nimg, c->taps1, cfg.diffusivity, lp.tau.data(), hak_fed_group_size(n, G, 0),
@@ -555,7 +532,7 @@ static int enqueue_detect(hak_ctx* c, const float* d_images, long image_stride, 
                 ProfScope ps(c, HAK_PROF_FLOW, st);
                 hak_launch_flow(st, smooth, flow, S, oc.w, oc.h, oc.p, nimg, cfg.diffusivity, c->state, o, 0.f);
             }
-        } else if (hak_stream_pays(c->fuse_sf, oc.w, oc.h, nimg) && cfg.diffusivity == HAK_PM_G2 && (oc.w & 3) == 0 && oc.w >= 16 &&
+        } else if (hak_stream_pays(c->knobs.fuse_sf, oc.w, oc.h, nimg) && cfg.diffusivity == HAK_PM_G2 && (oc.w & 3) == 0 && oc.w >= 16 &&
                    oc.h >= 8) {
             const int ns0 = hak_fed_group_size(n, G, 0);
             float* dst0 = (G % 2 == 1) ? Lt : tmp;
@@ -638,8 +615,7 @@ static int enqueue_detect(hak_ctx* c, const float* d_images, long image_stride, 
         // the others from the last to the first -- so the longest side chain (octave 0's) gets the last queue, the shortest the
         // first.  Pure placement: results and ordering are unaffected, and a runtime that places nodes differently merely ignores
         // the hint (HAK_GRAPH_PADS=0 switches it off).
-        static const bool pads_on = [] { const char* e = getenv("HAK_GRAPH_PADS"); return !e || atoi(e) != 0; }();
-        for (int o = 0; o < last && pads_on; o++)
+        for (int o = 0; o < last && c->knobs.graph_pads; o++)
             for (int k = 0; k < last - 1 - o && head_node[o] && cap_graph; k++) {
                 hipGraphNode_t pad = nullptr;
                 if (hipGraphAddEmptyNode(&pad, cap_graph, &head_node[o], 1) != hipSuccess) (void)hipGetLastError();
@@ -650,8 +626,7 @@ static int enqueue_detect(hak_ctx* c, const float* d_images, long image_stride, 
         // should start with GPU_MAX_HW_QUEUES=8 (the demo does) -- the library does not set it itself, because a
         // process that runs BATCHES loses 2 % (1080p) to 13 % (720p) with eight queues.  HAK_SIDE_STREAMS = n < noct-1 makes
         // octaves n-1 .. noct-2 share the last side stream by design (same time as the shared queue).
-        static const int nside_env = [] { const char* e = getenv("HAK_SIDE_STREAMS"); const int v = e ? atoi(e) : HAK_MAX_OCTAVES; return v < 1 ? 1 : v; }();
-        const int nside = nside_env < last ? nside_env : (last > 0 ? last : 1);
+        const int nside = c->knobs.side_streams < last ? c->knobs.side_streams : (last > 0 ? last : 1);
         auto side_of = [&](int o) { return c->oct_stream[1 + (o < nside ? o : nside - 1)]; };
         // the remaining work, one level per octave in turn, each octave's first node behind the wait for its head
         for (int s = 0; s < L.ms; s++)
@@ -679,11 +654,11 @@ static int enqueue_detect(hak_ctx* c, const float* d_images, long image_stride, 
         // queues alike; 6: 0.82): as with the spine order of round 4, a fifth chain of two-image kernels stretches the other four by
         // more than the critical chain shrinks -- the call is bound by the chip's throughput on these small kernels, not by the
         // order they are issued in.
-        bool side0 = c->hess_side != 0 && c->concurrent && L.noct > 1 && c->hess_stream && L.ms <= HAK_MAX_SCALES &&
+        bool side0 = c->knobs.hess_side != 0 && c->concurrent && L.noct > 1 && c->hess_stream && L.ms <= HAK_MAX_SCALES &&
                      !hak_stream_pays(c->knobs.hess_stream, L.oct[0].w, L.oct[0].h, nimg) && !level_tile_pays(c, L.oct[0], nimg) &&
-                     !hak_stream_pays(c->fuse_sf, L.oct[0].w, L.oct[0].h, nimg);
+                     !hak_stream_pays(c->knobs.fuse_sf, L.oct[0].w, L.oct[0].h, nimg);
         for (int s = 1; s < L.ms && side0; s++)
-            side0 = hak_fed_groups(c->plan[s].nsteps, c->max_fuse, L.oct[0].w) == 1 && c->plan[s].sigma_size <= 4;
+            side0 = hak_fed_groups(c->plan[s].nsteps, c->knobs.max_fuse, L.oct[0].w) == 1 && c->plan[s].sigma_size <= 4;
         hipStream_t st = main_st;
         for (int o = 0; o < L.noct; o++) {
             if (c->concurrent && o > 0) {                       // this octave's chain waits only for Lt(o-1,0)
@@ -737,10 +712,9 @@ static int enqueue_detect(hak_ctx* c, const float* d_images, long image_stride, 
     { ProfScope ps(c, HAK_PROF_NMS);                                              // akaze.cpp:449-455
       hak_launch_nms_emit(main_st, b, L, c->dtab, c->psz, d_points, max_pts, d_num_pts);
       // the clean-up for the next sequence needs only the candidate list: beside the descriptor kernels, not in front of them
-      static const bool tail_fork_on = [] { const char* e = getenv("HAK_TAIL_FORK"); return !e || atoi(e) != 0; }();
       // (batches: no gain beside 5 ms of descriptor kernels, A/B 5 640 vs 5 710 pairs/s; the pair call: the fork's two cross-stream
       // waits in the replayed graph cost more than the 5 us kernel they move aside, 0.571 vs 0.544 ms, round 5)
-      tail_fork = spine && tail_fork_on;
+      tail_fork = spine && c->knobs.tail_fork;
       if (tail_fork) {
           (void)hipEventRecord(c->ev_tail_fork, main_st);
           if (hipStreamWaitEvent(c->oct_stream[1], c->ev_tail_fork, 0) != hipSuccess) return fail("stream wait");
@@ -799,10 +773,9 @@ static int enqueue_fast_detect(hak_ctx* c, const unsigned char* d_images, long i
             const int n = lp.nsteps;
             if (level_tile_pays(c, oc, nimg)) {
                 bool hess_done = false;
-                static const bool level_hess_on = [] { const char* e = getenv("HAK_LEVEL_HESS"); return !e || atoi(e) != 0; }();
                 hakf_launch_level_tile(st, s == 0 ? A + L.lt(o - 1, 0) : A + L.lt(o, s - 1), s == 0 ? L.oct[o - 1] : oc, s == 0, smooth, Lt, tmp, S, oc,
                                        nimg, c->itaps1, cfg.diffusivity, lp.tau.data(), n, c->state, o,
-                                       level_hess_on ? A + L.dxy(o, s) : nullptr, lp.sigma_size, &b, &L, &c->htab, s, idthreshold, &hess_done);
+                                       c->knobs.level_hess ? A + L.dxy(o, s) : nullptr, lp.sigma_size, &b, &L, &c->htab, s, idthreshold, &hess_done);
                 if (!hess_done && !hakf_launch_hessian_level(st, smooth, A + L.dxy(o, s), flow, false, S, oc.w, oc.h, oc.p, nimg,
                                                lp.sigma_size, &b, &L, &c->htab, o, s, idthreshold)) {
                     hakf_launch_hessian(st, smooth, A + L.dxy(o, s), flow, S, oc.w, oc.h, oc.p, nimg, lp.sigma_size);
@@ -813,12 +786,12 @@ static int enqueue_fast_detect(hak_ctx* c, const unsigned char* d_images, long i
             // FED cycle in G fused launches (the float path's streaming kernel instantiated for int32) when the width
             // allows 16-byte rows, else one step per launch; ping-pong Lt <-> tmp so that the last launch lands in Lt
             const bool fused = (oc.w % 4) == 0;
-            const int G = fused ? hak_fed_groups(n, c->max_fuse, oc.w) : n;
+            const int G = fused ? hak_fed_groups(n, c->knobs.max_fuse, oc.w) : n;
             const int* src;
             bool fused_first = false;
             if (s == 0) {                                                         // akaze.cpp:640-662
                 int* first = (G % 2 == 0) ? Lt : tmp;
-                if (fused && c->fuse_head && hak_stream_pays(c->fuse_sf, oc.w, oc.h, nimg))
+                if (fused && c->knobs.fuse_head && hak_stream_pays(c->knobs.fuse_sf, oc.w, oc.h, nimg))
                     fused_first = hakf_launch_fed_sf_head(st, A + L.lt(o - 1, 0), L.oct[o - 1], smooth, flow, (G % 2 == 1) ? Lt : tmp, S, oc,
                                                           nimg, c->itaps1, cfg.diffusivity, lp.tau.data(), hak_fed_group_size(n, G, 0),
                                                           c->state, o, G > 1);
@@ -830,7 +803,7 @@ static int enqueue_fast_detect(hak_ctx* c, const unsigned char* d_images, long i
             } else {                                                              // akaze.cpp:664-695
                 src = A + L.lt(o, s - 1);
                 // low-pass + conductivity + first FED group in one streaming pass when covered, else low-pass + flow in one tile pass
-                if (fused && hak_stream_pays(c->fuse_sf, oc.w, oc.h, nimg))
+                if (fused && hak_stream_pays(c->knobs.fuse_sf, oc.w, oc.h, nimg))
                     fused_first = hakf_launch_fed_sf(st, src, smooth, flow, (G % 2 == 1) ? Lt : tmp, S, oc.w, oc.h, oc.p, nimg, c->itaps1,
                                                      cfg.diffusivity, lp.tau.data(), hak_fed_group_size(n, G, 0), c->state, o, G > 1);
                 if (!fused_first)
@@ -907,7 +880,7 @@ static int run_detect_inner(hak_ctx* c, const float* d_images, long image_stride
     // streams the host keeps ahead of the GPU, and the graph replay of ROCm 7.2 submits queue by queue in an order of its own
     // (measured on the C++ demo, ms per 1080p pair: eager 1.18, replay 1.31; HAK_GRAPH=2 forces the replay).
     const bool launch_bound = c->concurrent && c->L.noct > 1 && spine_pays(c, nimg);
-    if (!c->use_graph || c->prof_on || (launch_bound && c->graph_mode != 2))
+    if (!c->use_graph || c->prof_on || (launch_bound && c->knobs.graph != 2))
         return enqueue_detect(c, d_images, image_stride, pitch, nimg, d_points, d_num_pts, desc, max_pts, h_pinned, cap0, cap1);
     hak_ctx::GraphKey key;
     memset(&key, 0, sizeof(key));
@@ -980,7 +953,7 @@ extern "C" int hak_detect_and_compute(hak_ctx* c, const float* d_image, int pitc
     // count included: one synchronisation and the results are there.  A pageable one takes the reference's route
     // (akaze.cpp:134-139): count first, then a copy of the valid records.
     // HAK_TIMING=1: host-side split of the call (submission vs waiting), printed every 100 calls -- diagnosis only
-    static const bool timing = [] { const char* e = getenv("HAK_TIMING"); return e && atoi(e) != 0; }();
+    const bool timing = c->knobs.timing != 0;
     static double t_sub = 0, t_wait = 0; static int t_n = 0;
     const auto t0 = std::chrono::steady_clock::now();
     hak_point* h_pinned = host_pinned(h_points) ? h_points : nullptr;
@@ -1355,13 +1328,13 @@ extern "C" int hak_query_traffic(const hak_ctx* c, int npts_hint, hak_traffic* o
         for (int s = 0; s < L.ms; s++) {
             const LevelPlan& lp = c->plan[(size_t)o * L.ms + s];
             pxsteps += N * lp.nsteps;
-            launches += lp.nsteps ? hak_fed_groups(lp.nsteps, c->max_fuse, L.oct[o].w) : 0;
+            launches += lp.nsteps ? hak_fed_groups(lp.nsteps, c->knobs.max_fuse, L.oct[o].w) : 0;
             // sublevels whose low-pass (8 B/px) + conductivity (8 B/px) run inside the first FED launch (k_fed_sf), and octave
             // heads whose decimation + low-pass (4 N_{o-1} + 8 N_o) + conductivity (8 N_o) do
-            const bool covered = lp.nsteps && hak_stream_pays(c->fuse_sf, L.oct[o].w, L.oct[o].h, c->cfg.batch) &&
+            const bool covered = lp.nsteps && hak_stream_pays(c->knobs.fuse_sf, L.oct[o].w, L.oct[o].h, c->cfg.batch) &&
                                  c->cfg.diffusivity == HAK_PM_G2 && (L.oct[o].w & 3) == 0 && L.oct[o].w >= 16 && L.oct[o].h >= 8;
             if (covered && s > 0) folded += 16.0 * N;
-            if (covered && c->fuse_head && s == 0 && o > 0 && !(L.oct[o - 1].w & 1) && !(L.oct[o - 1].h & 1))
+            if (covered && c->knobs.fuse_head && s == 0 && o > 0 && !(L.oct[o - 1].w & 1) && !(L.oct[o - 1].h & 1))
                 folded += 4.0 * L.oct[o - 1].w * L.oct[o - 1].h + 16.0 * N;
             if (o == 0 && s == 0) all += 56.0 * N;                                // o0 prologue
             else if (s == 0) all += 4.0 * L.oct[o - 1].w * L.oct[o - 1].h + 8.0 * N + 8.0 * N + 24.0 * N + 4.0 * N;

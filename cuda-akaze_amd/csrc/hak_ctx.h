@@ -55,15 +55,13 @@ struct hak_ctx {
     // latency-bound small-octave launches overlap octave 0's heavy kernels
     hipStream_t oct_stream[HAK_MAX_OCTAVES] = {};      // [0] unused (= stream)
     hipEvent_t ev_ready[HAK_MAX_OCTAVES] = {}, ev_done[HAK_MAX_OCTAVES] = {};
-    // small launches (a pair, a handful of images): octave 0's Hessians leave its FED chain for a stream of their own (enqueue_detect)
+    // small launches (a pair, a handful of images): octave 0's Hessians leave its FED chain for a stream of their own (enqueue_detect);
+    // created only under HakKnobs::hess_side
     hipStream_t hess_stream = nullptr;
     hipEvent_t ev_hs[HAK_MAX_SCALES] = {}, ev_hd[HAK_MAX_SCALES] = {};   // level s's Hessian input ready / its Hessian done
-    int hess_side = 0;              // HAK_HESS_SIDE=1: on for launches in the tile-kernel regime.  Off by default: measured SLOWER (pair call
-                                    // 0.62 vs 0.57 ms) -- a fifth concurrent chain stretches the other four more than the shorter chain gains
-    bool concurrent = true;
+    bool concurrent = true;         // hak_set_concurrency; initially !HakKnobs::serial
     // the launch sequence has no host-side data dependence, so it is captured once per argument set and replayed
-    bool use_graph = true;          // env HAK_GRAPH=0 disables; profiling (event pairs) always runs eagerly
-    int graph_mode = 1;             // HAK_GRAPH: 0 never, 1 replay except for launch-bound single-image sequences, 2 always
+    bool use_graph = true;          // initially HakKnobs::graph != 0; cleared when a capture fails; profiling (event pairs) always runs eagerly
     struct GraphKey { const float* img; long stride; int pitch, nimg; hak_point* pts; int* num; int desc; int max_pts; int conc; hipStream_t st; hak_point* hpts; int cap0, cap1; int retain; };
     static constexpr int NGRAPH = 4;                    // e.g. the two images of a pair, alternating (main.cpp:201-205)
     hipGraphExec_t graph_exec[NGRAPH] = {};
@@ -73,11 +71,6 @@ struct hak_ctx {
     ProfClass prof[HAK_PROF_COUNT];
     int fed_launches = 0;
     double fed_fused_bytes = 0;     // compulsory HBM bytes per image of the FED launches as enqueued (read L [+ g], write L' [+ smooth, g])
-    int max_fuse = 4;               // FED steps fused per launch (env HAK_FED_MAX_FUSE, 1..6)
-    int fuse_head = 1;              // octave heads through the decimating k_fed_sf variant (env HAK_FUSE_HEAD=0 disables)
-    int level_min_steps = 8;        // shortest FED cycle that goes through k_level_tile under the size rule (env HAK_LEVEL_MIN_STEPS)
-    int fuse_sf = 1;                // low-pass + conductivity fused into the first FED launch of a sublevel: 0 never, 1 by size
-                                    // (hak_stream_pays), 2 always where covered (env HAK_FUSE_SF)
     int4* knn = nullptr;            // 2-NN scratch: fwd[batch/2][max_pts] | rev[batch/2][max_pts], allocated on first use
     int* d_cnt = nullptr;
     unsigned long long* hom_slots = nullptr;  // RANSAC scratch: best key per (pair, score block), grown on demand
@@ -85,11 +78,11 @@ struct hak_ctx {
     hak_homography* hom_rec = nullptr;        // the record of hak_find_homography before its download
     hak_point* pair_pts = nullptr;  // [2][cfg.max_pts]: the contiguous pair layout hak_detect_and_compute_pair detects into and matches on
     HakMatchScratch msc;            // sliced searches of one big pair (hak_match / hak_match_knn2): grows on demand, on this context's device
-    HakKnobs knobs;                 // kernel-selection knobs of THIS context (two contexts of a process may differ)
+    HakKnobs knobs;                 // the HAK_* variables as hak_create found them: THIS context's (two contexts of a process may differ)
     hipEvent_t ev_last = nullptr;   // recorded after the last enqueue on c->stream: hak_destroy waits for it (external streams)
     hipEvent_t ev_tail_fork = nullptr, ev_tail_join = nullptr;   // the map clean-up runs beside the descriptor kernels
     hipEvent_t ev_null = nullptr;   // recorded on the NULL stream at the start of a call: the context's stream waits for it (hak_set_null_order)
-    bool null_order = true;
+    bool null_order = true;         // hak_set_null_order; initially HakKnobs::null_order
     hipEvent_t ev_phase = nullptr;  // recorded in every detect sequence between the scale space and the keypoint stages (hak_phase_event)
     hipStream_t sync_stream = nullptr;                            // where the last detect sequence ends (c->stream unless it was left on the chain)
     bool last_fast = false;         // the arena holds the integer path's planes (hak_debug_plane)
@@ -110,7 +103,7 @@ struct ProfScope {
             // performance impact of those actions on the execution of following work").  Measured on one box in alternating runs the
             // difference is 0.3-0.4 % of the FED class (DESIGN.md 4 lesson 34: the leg's first sequence is what read 4 % high).
             // hak_prof_read synchronises the stream before it reads the events.
-            static const unsigned evflags = [] { const char* e = getenv("HAK_PROF_FENCE"); return e && atoi(e) ? 0u : (unsigned)hipEventDisableSystemFence; }();   // (=1: default events, for A/B)
+            const unsigned evflags = c->knobs.prof_fence ? 0u : (unsigned)hipEventDisableSystemFence;   // (HAK_PROF_FENCE=1: default events, for A/B)
             hipEvent_t a, b;
             (void)hipEventCreateWithFlags(&a, evflags); (void)hipEventCreateWithFlags(&b, evflags);
             p.ev.push_back(a); p.ev.push_back(b);

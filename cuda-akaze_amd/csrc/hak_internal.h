@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/hipakaze.h"
+#include "hak_knobs.h"
 
 #define HAK_NBINS 300        // akazed.cu:8
 #define HAK_WAVE 64
@@ -243,25 +244,7 @@ __host__ __device__ __forceinline__ float hak_expf(float x)
 // ---------------------------------------------------------------- launchers
 // (defined in the kernel files; all asynchronous on `st`; nimg = batch images,
 //  base = arena of image 0, stride = floats between image arenas)
-// Kernel-selection knobs of one context (hak_create reads them from the environment once; tests and A/B runs set them
-// there).  They never change results, only which of two bit-identical kernels runs.
-struct HakKnobs {
-    int hess_stream = 1;          // HAK_HESS_STREAM: register-streaming Hessian kernel 0 never / 1 by the size rule / 2 always where it applies
-    int base_stream = 1;          // HAK_BASE_STREAM: same for pass A of the octave-0 prologue
-    int base_hist = 0;            // HAK_BASE_HIST=1: the streaming prologue finds the (lattice) contrast maximum first and bins the gradient on the
-                                  // fly (no gradient plane, no histogram pass).  Off by default: half the bytes, 4 % SLOWER (the pass is bound by
-                                  // vector issue; kernels_base_stream.hip)
-    int hess_cbuf = 256;          // HAK_HESS_CBUF: staged candidates per block of the tile kernel (1..256; tests drive the overflow path)
-    int desc_order = 4;           // HAK_DESC_ORDER: image group size of the describe kernels' block order
-    int desc_plan = 1;            // HAK_DESC_PLAN: planned MLDB kernel (k_describe_runs) on / off
-    int desc_sort = 1;            // HAK_DESC_SORT: the keypoint kernels visit an image's keypoints level by level (raster order within a
-                                  // level) instead of in output order: 0 never / 1 in batches of 8 images and more / 2 always
-    int hess_lp = 0;              // HAK_HESS_LP=1: the streaming Hessian low-passes Lt(o,s-1) itself and k_fed_sf stops storing `smooth`.
-                                  // Off by default: measured 0.6 ms per 384 x 1080p SLOWER (FED -1.2 ms, Hessian +1.9 ms)
-    int level_tile = 1;           // HAK_LEVEL_TILE: one launch per sublevel out of LDS tiles (k_level_tile) 0 never / 1 for launches of at
-                                  // most HAK_LEVEL_TILE_MAX_PX pixels unless the streaming kernels are forced / 2 always
-};
-HakKnobs hak_knobs_from_env();    // defaults overridden by the HAK_* variables (hak_api.hip)
+// The HAK_* tuning variables (struct HakKnobs, per context; HakMatchKnobs, per call): hak_knobs.h
 
 // Per-image state and scratch of the strongest-N selection (kernels_select.hip), allocated by hak_create for cfg.batch images.
 // Every word a call reads is written earlier in the same call (k_sel_init, k_sel_rows): nothing is cleared outside the sequence.
@@ -290,7 +273,7 @@ struct HakBatch {
     int* rowcount;                // [nimg][h0]
     unsigned long long* cand;     // [nimg][cand_cap] extrema candidates: layer<<32 | y<<16 | x (full-res)
     long cand_cap;
-    const HakKnobs* knobs = nullptr;   // the owning context's; nullptr (stage operators): hak_knobs_from_env()
+    const HakKnobs* knobs = nullptr;   // the owning context's; nullptr (stage operators): read per call, hak_knobs_of()
     int* perm = nullptr;          // [nimg][perm_cap] visiting order of the keypoint kernels (k_desc_perm), or nullptr: output order
     int perm_cap = 0;
     // per-image clamps of a PAIR call (hak_detect_and_compute_pair: the two AkazeData capacities, akaze.cpp:246, 451); 0: every
@@ -299,6 +282,8 @@ struct HakBatch {
     // scratch of the strongest-N selection (kernels_select.hip, hak_set_retain_best); sel.st == nullptr: the raster-order clamp
     HakSelScratch sel{};
 };
+// the knobs a launcher works with: the owning context's, or (no context: b == nullptr or a stage operator's batch) the environment's now
+static inline HakKnobs hak_knobs_of(const HakBatch* b) { return (b && b->knobs) ? *b->knobs : hak_knobs_from_env(); }
 
 // scale space (kernels_scalespace.hip)
 void hak_launch_lowpass(hipStream_t st, const float* src, long src_stride, int src_pitch, float* dst, long dst_stride,
@@ -328,12 +313,12 @@ static inline bool hak_stream_pays(int mode, int w, int h, int nimg)
 // fill the chip.  1080 rows: 4 x 270, 2160: 8 x 270, 540: 4 x 135, 720: 4 x 180.  Measured on 256 x 1080p (FED / Hessian class,
 // ms): 9 segments of 128 rows, the ninth 56 rows tall in a block of its own (the rule this replaces): 9.70 / 9.14; 8 x 135:
 // 9.16 / 8.32; 4 x 270: 9.08 / 8.31; 12 x 90: 9.43 / 8.49; 16 x 68: 9.63 / 8.84.
-// Segments are halved only while the launch has fewer than 2048 waves (round 3; 4096 before; env HAK_STREAM_MIN_WAVES): at 384
+// Segments are halved only while the launch has fewer than 2048 waves (round 3; 4096 before; HAK_STREAM_MIN_WAVES, once per process): at 384
 // images octave 2 then keeps 4 x 68 rows and octave 3 gets 8 x 17 instead of 16 x 9 -- a 9-row segment spends half its rows
 // on warm-up.  FED class per 384 x 1080p images, A/B on one box: 8192: 13.68 ms, 4096: 13.18, 2048: 12.75-12.92, 1536: 12.78-12.85.
 static inline int hak_stream_rows(int h, long strips_times_images, int min_rows)
 {
-    static const long want = [] { const char* e = getenv("HAK_STREAM_MIN_WAVES"); const long v = e ? atol(e) : 2048; return v < 1 ? 1 : v; }();
+    const long want = hak_process_knobs().stream_min_waves;
     int nseg = 4 * ((h + 512) / 1024 > 1 ? (h + 512) / 1024 : 1);
     while (strips_times_images * nseg < want && (h + 2 * nseg - 1) / (2 * nseg) >= min_rows) nseg *= 2;
     const int ry = (h + nseg - 1) / nseg;
@@ -394,7 +379,6 @@ int hakf_launch_level_tile(hipStream_t st, const int* src, HakOct so, bool head,
                            int* dxy = nullptr, int step = 0, const HakBatch* b = nullptr, const HakLayout* L = nullptr,
                            const HakTables* htab = nullptr, int sub = 0, int idthreshold = 0, bool* hess_done = nullptr);
 // fused FED groups (kernels_fed.hip)
-#define HAK_FED_MAX_FUSE 4
 bool hakf_launch_base_level(hipStream_t st, const unsigned char* img, long img_stride, int sp, int* lt, int* grad_scratch, long stride,
                             int w, int h, int p, int nimg, const int* itaps1, const int* itaps_base, int R, HakImgState* state,
                             float per, int noct, const HakKnobs& knobs);

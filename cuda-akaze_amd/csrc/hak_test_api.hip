@@ -123,9 +123,7 @@ extern "C" int hak_op_nld_steps(const float* src, const float* flow, float* dst,
 {
     if (nsteps < 1) return fail("nsteps < 1");
     if (p % 4) return fail("pitch must be a multiple of 4");
-    int fuse = 4;
-    if (const char* e = getenv("HAK_FED_MAX_FUSE")) fuse = atoi(e);
-    const int G = hak_fed_groups(nsteps, fuse, w);
+    const int G = hak_fed_groups(nsteps, hak_knobs_from_env().max_fuse, w);
     const float* s = src;
     int done = 0;
     for (int g = 0; g < G; g++) {

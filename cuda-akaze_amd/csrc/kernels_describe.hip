@@ -626,7 +626,6 @@ __global__ __launch_bounds__(64) void k_describe(const V* __restrict__ base, lon
 // 4: 3.99, 8: 4.12, 16: 4.30, 32: 4.51, 256: 5.74 -- a few images side by side spread the gathers over more L2 channels, many
 // lose the L2 / Infinity-Cache sharing between neighbouring keypoints.  HakKnobs::desc_order / desc_plan, from HAK_DESC_ORDER /
 // HAK_DESC_PLAN (A/B runs and the alternatives test; results do not depend on either).
-static HakKnobs knobs_of(const HakBatch& b) { return b.knobs ? *b.knobs : hak_knobs_from_env(); }
 
 // Visiting order of the keypoint kernels: an image's keypoints come out of the NMS in raster order of the full-resolution map
 // with all levels mixed (the reference's order: the output keeps it), so consecutive blocks gather from sixteen different plane
@@ -698,7 +697,7 @@ void hak_launch_describe(hipStream_t st, const HakBatch& b, const HakLayout& L, 
     const int gx = max_pts < 4096 ? max_pts : 4096, gxo = max_pts < 1024 ? max_pts : 1024;
     const dim3 grido(gxo, b.nimg);
     dim3 grid(gx, b.nimg);
-    const HakKnobs kn = knobs_of(b);
+    const HakKnobs kn = hak_knobs_of(&b);
     const int order = kn.desc_order < 0 ? 0 : (kn.desc_order > 255 ? 255 : kn.desc_order);
     const int* perm = desc ? launch_perm(st, b, L, points, max_pts, kn) : nullptr;
     if (desc && !upright && orient) k_orient<float><<<grido, 64, 0, st>>>(b.base, b.stride, L, tab, b.state, points, max_pts, 1, 0, perm);
@@ -715,7 +714,7 @@ void hakf_launch_describe(hipStream_t st, const HakBatch& b, const HakLayout& L,
     const int gx = max_pts < 4096 ? max_pts : 4096, gxo = max_pts < 1024 ? max_pts : 1024;
     const dim3 grido(gxo, b.nimg);
     dim3 grid(gx, b.nimg);
-    const HakKnobs kn = knobs_of(b);
+    const HakKnobs kn = hak_knobs_of(&b);
     const int order = kn.desc_order < 0 ? 0 : (kn.desc_order > 255 ? 255 : kn.desc_order);
     const int* base = reinterpret_cast<const int*>(b.base);
     const int* perm = launch_perm(st, b, L, points, max_pts, kn);

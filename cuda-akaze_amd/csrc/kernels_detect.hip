@@ -393,6 +393,6 @@ void hak_launch_download_pair(hipStream_t st, const hak_point* src, const int* d
 {
     // blocks per image: the copy is a latency chain per thread (load, two stores, one of them over PCIe); 128 blocks instead of 8
     // take 7 us off the pair call (0.543 -> 0.536 ms; 16 / 32 / 64: 0.541 / 0.540 / 0.539)
-    static const int nb = [] { const char* e = getenv("HAK_DOWNLOAD_BLOCKS"); const int v = e ? atoi(e) : 128; return v < 1 ? 1 : v; }();
-    k_download_pair<<<dim3(nb, 2), 256, 0, st>>>(src, d_num, max_pts, dst, h_num);
+    // (HAK_DOWNLOAD_BLOCKS, once per process)
+    k_download_pair<<<dim3(hak_process_knobs().download_blocks, 2), 256, 0, st>>>(src, d_num, max_pts, dst, h_num);
 }

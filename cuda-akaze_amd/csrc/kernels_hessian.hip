@@ -332,7 +332,6 @@ static void deriv_factors(float& fac1, float& fac2) { hak_deriv_factors(&fac1, &
 
 // HakKnobs::hess_stream: 0 never / 1 by size / 2 always.  HakKnobs::hess_cbuf: staged candidates per block actually used
 // (1..HF_CBUF); HAK_HESS_CBUF shrinks it so that the tests can drive the overflow path of the staging buffer with ordinary images.
-static HakKnobs knobs_of(const HakBatch* b) { return (b && b->knobs) ? *b->knobs : hak_knobs_from_env(); }
 
 template <typename V, int S>
 static void launch_fused(hipStream_t st, const V* src, V* dxy, V* det, long stride,
@@ -374,7 +373,7 @@ bool hak_launch_hessian_level(hipStream_t st, const float* src, float* dxy, floa
                               const float* lp_taps)
 {
     // register-streaming kernel (kernels_hessian_stream.hip) when it covers the case; HAK_HESS_STREAM=0 forces the tile kernel
-    const HakKnobs kn = knobs_of(b);
+    const HakKnobs kn = hak_knobs_of(b);
     if (lp_taps || hak_stream_pays(kn.hess_stream, w, h, nimg)) {
         float f1, f2;
         deriv_factors(f1, f2);
@@ -408,7 +407,7 @@ bool hakf_launch_hessian_level(hipStream_t st, const int* src, int* dxy, int* de
                                int w, int h, int p, int nimg, int step,
                                const HakBatch* b, const HakLayout* L, const HakTables* htab, int octave, int sub, int idthreshold)
 {
-    const HakKnobs kn = knobs_of(b);
+    const HakKnobs kn = hak_knobs_of(b);
     if (hak_stream_pays(kn.hess_stream, w, h, nimg)) {
         float f1, f2;
         deriv_factors(f1, f2);

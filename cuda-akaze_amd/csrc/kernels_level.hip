@@ -342,7 +342,7 @@ __global__ __launch_bounds__(LV_NT) void k_level_tile(const V* __restrict__ src,
 template <typename V, bool HEAD, bool FIRST>
 void launch_level(hipStream_t st, const V* src, V* smooth, V* dst, long stride, HakOct so, int w, int h, int p, int nimg,
                   SfTaps<V> t, int diffusivity, const HakImgState* state, int octave, float fixed_ikc, const float* tau, int ns,
-                  const LvHess<V>& hs)
+                  const LvHess<V>& hs, int min_blocks)
 {
     LvFacs<V> fac;
     for (int k = 0; k < LV_MAX_STEPS; k++) {
@@ -359,7 +359,7 @@ void launch_level(hipStream_t st, const V* src, V* smooth, V* dst, long stride, 
     while (T > 8 && total(T) > LV_LDS_FLOATS) T -= 8;
     // ... but not so large that a small plane runs on a handful of CUs.  Smaller tiles mean more halo work in total (the planes are
     // (T + 2 ns + 6)^2): ~100 blocks keep a block short without multiplying the work of the octaves that run beside the critical chain
-    static const long min_blocks = [] { const char* e = getenv("HAK_LEVEL_MIN_BLOCKS"); const long v = e ? atol(e) : 96; return v < 1 ? 1 : v; }();
+    // (min_blocks: HakKnobs::level_min_blocks)
     while (T > 16 && (long)((w + T - 1) / T) * ((h + T - 1) / T) * nimg < min_blocks) T -= 8;
     const size_t lds = sizeof(V) * (size_t)total(T);
     // the 150 KB dynamic-LDS opt-in is a per-DEVICE attribute of the function: once per device and instantiation (contexts on
@@ -381,7 +381,7 @@ void launch_level(hipStream_t st, const V* src, V* smooth, V* dst, long stride, 
 template <typename V>
 int level_steps(hipStream_t st, const V* src, HakOct so, bool head, V* smooth, V* dst, V* tmp, long stride, HakOct dd, int nimg,
                 const V* taps, int diffusivity, const float* tau, int n, const HakImgState* state, int octave, float fixed_ikc,
-                const LvHess<V>& hs)
+                const LvHess<V>& hs, int min_blocks)
 {
     const SfTaps<V> t{taps[0], taps[1], taps[2]};
     const int G = (n + LV_MAX_STEPS - 1) / LV_MAX_STEPS;     // launches of this cycle (1 for every BASELINE configuration but 4K octave 4)
@@ -390,9 +390,9 @@ int level_steps(hipStream_t st, const V* src, HakOct so, bool head, V* smooth, V
     for (int g = 0; g < G; g++) {
         const int ns = hak_fed_group_size(n, G, g);
         V* out = ((G - g) % 2 == 1) ? dst : tmp;             // ping-pong so that the last launch lands in dst
-        if (g == 0 && head) launch_level<V, true, true>(st, cur, smooth, out, stride, so, dd.w, dd.h, dd.p, nimg, t, diffusivity, state, octave, fixed_ikc, tau, ns, hs);
-        else if (g == 0) launch_level<V, false, true>(st, cur, smooth, out, stride, dd, dd.w, dd.h, dd.p, nimg, t, diffusivity, state, octave, fixed_ikc, tau, ns, hs);
-        else launch_level<V, false, false>(st, cur, smooth, out, stride, dd, dd.w, dd.h, dd.p, nimg, t, diffusivity, state, octave, fixed_ikc, tau + done, ns, hs);
+        if (g == 0 && head) launch_level<V, true, true>(st, cur, smooth, out, stride, so, dd.w, dd.h, dd.p, nimg, t, diffusivity, state, octave, fixed_ikc, tau, ns, hs, min_blocks);
+        else if (g == 0) launch_level<V, false, true>(st, cur, smooth, out, stride, dd, dd.w, dd.h, dd.p, nimg, t, diffusivity, state, octave, fixed_ikc, tau, ns, hs, min_blocks);
+        else launch_level<V, false, false>(st, cur, smooth, out, stride, dd, dd.w, dd.h, dd.p, nimg, t, diffusivity, state, octave, fixed_ikc, tau + done, ns, hs, min_blocks);
         done += ns;
         cur = out;
     }
@@ -436,7 +436,7 @@ int hak_launch_level_tile(hipStream_t st, const float* src, HakOct so, bool head
     bool fused = false;
     const LvHess<float> hs = level_hess<float>(dxy, step, hak_fed_group_size(n, G, 0), b, L, htab, octave, sub, dthreshold, &fused);
     if (hess_done) *hess_done = fused;
-    return level_steps<float>(st, src, so, head, smooth, dst, tmp, stride, dd, nimg, taps, diffusivity, tau, n, state, octave, fixed_ikc, hs);
+    return level_steps<float>(st, src, so, head, smooth, dst, tmp, stride, dd, nimg, taps, diffusivity, tau, n, state, octave, fixed_ikc, hs, hak_knobs_of(b).level_min_blocks);
 }
 
 int hakf_launch_level_tile(hipStream_t st, const int* src, HakOct so, bool head, int* smooth, int* dst, int* tmp, long stride,
@@ -448,5 +448,5 @@ int hakf_launch_level_tile(hipStream_t st, const int* src, HakOct so, bool head,
     bool fused = false;
     const LvHess<int> hs = level_hess<int>(dxy, step, hak_fed_group_size(n, G, 0), b, L, htab, octave, sub, idthreshold, &fused);
     if (hess_done) *hess_done = fused;
-    return level_steps<int>(st, src, so, head, smooth, dst, tmp, stride, dd, nimg, itaps, diffusivity, tau, n, state, octave, 0.f, hs);
+    return level_steps<int>(st, src, so, head, smooth, dst, tmp, stride, dd, nimg, itaps, diffusivity, tau, n, state, octave, 0.f, hs, hak_knobs_of(b).level_min_blocks);
 }

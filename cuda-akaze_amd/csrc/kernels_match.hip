@@ -249,9 +249,6 @@ typedef float mm_v16f __attribute__((ext_vector_type(16)));
 #define MM_BASE 1024.0f
 #define MM_BASE_BITS 0x44800000u
 #define MM_QSTEP 0.0001220703125f        /* 2^-13 */
-#ifndef MM_QT_DEFAULT
-#define MM_QT_DEFAULT 1                  /* query tiles per wave (HAK_MATCH_QT overrides per call; 2 measured slower, see k_match_mfma) */
-#endif
 #define MM_MAX_ROWS (2047 * MM_BCH)     /* train rows one block pass can number (q < 2048): larger sets take the vector-pipe kernels */
 #define MM_ROW 36       // dwords per staged train row: [w0..w7 | w0..w7 >> 1 | w8..w15 | w8..w15 >> 1 | 4 of padding]: lane half h reads its
                         // 16 dwords at 16 h (no shift in the tile loop, where every VALU instruction counts); 144-byte rows make the
@@ -1007,10 +1004,9 @@ void hak_match_scratch_free(HakMatchScratch* sc)
 // slices of a big pair's train set for the matrix-core kernel: query blocks x slices ~ want_blocks, every slice a whole number of
 // 32-row tiles, none empty.  Two blocks per CU are resident (launch bounds, 2 x 72 KB of LDS): 512 blocks fill the chip once, and
 // 10k x 10k (79 query blocks) is fastest at 6 slices = 474 blocks for both searches (1-NN, ms per call at 4 5 6 7 8 10 13 slices:
-// 0.0541 0.0491 0.0462 0.0532 0.0504 0.0504 0.0510).  HAK_MATCH_SLICES overrides the count (tuning).
-static int mfma_slices(int gx, int n2, int* rows_per_slice, int want_blocks)
+// 0.0541 0.0491 0.0462 0.0532 0.0504 0.0504 0.0510).  env > 0 (HakMatchKnobs::slices) overrides the count (tuning).
+static int mfma_slices(int gx, int n2, int* rows_per_slice, int want_blocks, int env)
 {
-    static const int env = [] { const char* e = getenv("HAK_MATCH_SLICES"); return e ? atoi(e) : 0; }();
     const int tiles = (n2 + 31) / 32;
     if (tiles < 16) { *rows_per_slice = tiles * 32; return 1; }
     int slices = env > 0 ? env : (want_blocks + gx / 2) / gx;
@@ -1022,13 +1018,7 @@ static int mfma_slices(int gx, int n2, int* rows_per_slice, int want_blocks)
     return (tiles + tps - 1) / tps;
 }
 
-// query tiles per wave of k_match_mfma (HAK_MATCH_QT = 1 | 2, read per call like HAK_MATCH_VALU: A/B runs and the tests drive both)
-static int mm_query_tiles()
-{
-    const char* e = getenv("HAK_MATCH_QT");
-    const int v = e ? atoi(e) : MM_QT_DEFAULT;
-    return v == 1 ? 1 : 2;
-}
+// (qt: query tiles per wave of k_match_mfma, HakMatchKnobs::qt)
 template <bool KNN, typename... A>
 static void mm_launch(int qt, dim3 grid, hipStream_t st, A... a)
 {
@@ -1039,18 +1029,18 @@ static void mm_launch(int qt, dim3 grid, hipStream_t st, A... a)
 void hak_launch_knn2(hipStream_t st, const hak_point* ptsA, const hak_point* ptsB, const int* nA_dev, const int* nB_dev,
                      int nA_host, int nB_host, long strideA, long strideB, int npairs, int4* out, long out_stride, HakMatchScratch* sc)
 {
-    const char* env_valu = getenv("HAK_MATCH_VALU");               // (read per call, as in hak_launch_match)
+    const HakMatchKnobs mk = hak_match_knobs_from_env();           // (per call, as in hak_launch_match)
     // (with device-side counts nA_host / nB_host carry the CAPACITY of the sets)
-    if (!(env_valu && atoi(env_valu) != 0) && nB_host <= MM_MAX_ROWS) {
+    if (mk.valu == 0 && nB_host <= MM_MAX_ROWS) {
         // the matrix-core kernel with its 2-NN epilogue (the point records are only read: ptsA is not written)
-        const int qt = mm_query_tiles(), qpb = 128 * qt;
+        const int qt = mk.qt, qpb = 128 * qt;
         int gx = nA_dev ? (qt == 2 ? 43 : 83) : (nA_host + qpb - 1) / qpb;
         if (gx < 1) gx = 1;
         if (gx > 4096) gx = 4096;
         // one big pair with host-side counts whose query blocks alone cannot fill the chip: slice the train set
         if (sc && !nA_dev && npairs == 1 && gx < 384 && (long)gx * qpb >= nA_host) {
             int rps = 0;
-            const int slices = mfma_slices(gx, nB_host, &rps, qt == 2 ? 256 : 512);
+            const int slices = mfma_slices(gx, nB_host, &rps, qt == 2 ? 256 : 512, mk.slices);
             if (slices > 1 && hak_match_scratch_reserve(sc, st, 0, gx, (long)slices * gx * qpb, 0, 0)) {
                 mm_launch<true>(qt, dim3(gx, slices), st, const_cast<hak_point*>(ptsA), ptsB, (const int*)nullptr, (const int*)nullptr, nA_host, nB_host, 0L, 0L,
                                 2, rps, out, 0L, sc->ticket, sc->part, gx * qpb);
@@ -1090,9 +1080,9 @@ void hak_launch_match(hipStream_t st, hak_point* pts1, const hak_point* pts2, co
                       int n1_host, int n2_host, long pair_stride1, long pair_stride2, int npairs, HakMatchScratch* sc)
 {
     // k_match_mfma: a wave = 32 QT queries x the train set, four waves per block.  HAK_MATCH_VALU=1: the VALU / LDS kernel k_match
-    const char* env_valu = getenv("HAK_MATCH_VALU");               // (read per call: the tests run both kernels in one process)
-    const bool valu = (env_valu && atoi(env_valu) != 0) || n2_host > MM_MAX_ROWS;       // (device-side counts: n2_host = the capacity)
-    const int qt = mm_query_tiles(), qpb = 128 * qt;
+    const HakMatchKnobs mk = hak_match_knobs_from_env();           // (per call: the tests run both kernels in one process)
+    const bool valu = mk.valu != 0 || n2_host > MM_MAX_ROWS;       // (device-side counts: n2_host = the capacity)
+    const int qt = mk.qt, qpb = 128 * qt;
     const int nq = n1_dev ? 0 : n1_host;
     const bool two = n1_dev ? npairs >= 8 : (long)((nq + 2 * MQ - 1) / (2 * MQ)) * npairs >= 2048;    // (k_match only: queries per thread)
     const int qb = valu ? (two ? 2 * MQ : MQ) : qpb;                // queries per block
@@ -1110,7 +1100,7 @@ void hak_launch_match(hipStream_t st, hak_point* pts1, const hak_point* pts2, co
     if (sc && !n1_dev && npairs == 1 && (long)gx * qb >= nq) {
         if (!valu && gx < 384) {
             int rps = 0;
-            const int slices = mfma_slices(gx, n2_host, &rps, qt == 2 ? 256 : 512);
+            const int slices = mfma_slices(gx, n2_host, &rps, qt == 2 ? 256 : 512, mk.slices);
             if (slices > 1 && hak_match_scratch_reserve(sc, st, 0, gx, (long)slices * gx * qpb, 0, 0)) {
                 mm_launch<false>(qt, dim3(gx, slices), st, pts1, pts2, (const int*)nullptr, (const int*)nullptr, n1_host, n2_host, 0L, 0L, 2, rps,
                                  (int4*)nullptr, 0L, sc->ticket, sc->part, gx * qpb);

@@ -26,6 +26,19 @@ def test_header_symbols_are_exported(ah):
     assert not [n for n in exported if n.startswith(("hak_op_", "hak_debug_"))], "test entry points linked into libhipakaze.so"
 
 
+def test_environment_is_read_in_one_file_and_documented():
+    """the HAK_* tuning variables have one home: of the library's sources only one file calls getenv, and every variable it names
+    is described in INTEGRATION.md (a variable that grows beside the table, or without a word to the integrator, fails here)"""
+    csrc = os.path.join(ROOT, "cuda-akaze_amd", "csrc")
+    readers = sorted(f for f in os.listdir(csrc)
+                     if f.endswith((".hip", ".h", ".hpp", ".cpp", ".c")) and "getenv" in open(os.path.join(csrc, f)).read())
+    assert len(readers) == 1, readers
+    names = set(re.findall(r'"(HAK_[A-Z0-9_]+)"', open(os.path.join(csrc, readers[0])).read()))
+    assert len(names) >= 30, names
+    doc = set(re.findall(r"\bHAK_[A-Z0-9_]+\b", open(os.path.join(ROOT, "INTEGRATION.md")).read()))
+    assert names <= doc, sorted(names - doc)
+
+
 def test_test_abi_is_a_separate_library(ah):
     """include/hipakaze_test.h -> libhipakaze_test.so: every declared symbol exported there, the library links against the product
     library (it drives the product's launchers, it does not carry kernels of the launch sequence) and loads without a GPU"""

@@ -305,7 +305,12 @@ def test_two_contexts_keep_their_own_knobs(ah, torch, synth, monkeypatch):
     dets = []
     for env in ({"HAK_HESS_STREAM": "0", "HAK_FUSE_SF": "0", "HAK_BASE_STREAM": "0", "HAK_DESC_PLAN": "0", "HAK_LEVEL_TILE": "0"},
                 {"HAK_HESS_STREAM": "2", "HAK_FUSE_SF": "2", "HAK_BASE_STREAM": "2", "HAK_DESC_PLAN": "1", "HAK_LEVEL_TILE": "0"},
-                {"HAK_LEVEL_TILE": "2", "HAK_HESS_CBUF": "2"}):
+                {"HAK_LEVEL_TILE": "2", "HAK_HESS_CBUF": "2"},
+                # the single image takes the tile kernel and the spine order: the level's Hessian outside k_level_tile; one side
+                # stream and the map clean-up in front of the descriptor kernels; smaller tiles
+                {"HAK_LEVEL_TILE": "2", "HAK_LEVEL_HESS": "0"},
+                {"HAK_LEVEL_HESS": "1", "HAK_TAIL_FORK": "0", "HAK_SIDE_STREAMS": "1"},
+                {"HAK_TAIL_FORK": "1", "HAK_SIDE_STREAMS": "8", "HAK_LEVEL_MIN_BLOCKS": "400"}):
         for k, v in env.items():
             monkeypatch.setenv(k, v)
         d = ah.Akazer()
