@@ -351,17 +351,26 @@ __device__ __forceinline__ void hs_iter(HsState<V, S, LP>& T, const int t, const
             const V ul = wave_shr1(up.w), ur = wave_shl1(up.x);
             const V dl = wave_shr1(dn.w), dr = wave_shl1(dn.x);
             // strict maximum over the threshold and the 8 neighbours: v > max(all nine) -- four v_max3 and one compare per
-            // pixel instead of nine compares and their scalar mask chain (ordered compares: a NaN neighbour can only appear
-            // for non-finite input images)
+            // pixel instead of nine compares and their scalar mask chain.  The maximum drops a NaN operand, the reference's
+            // ordered compares (`*vp > *vp0 && ..`) do not: a pixel next to a NaN determinant is no extremum there, and NaN
+            // determinants (inf - inf) come from FINITE images already (isolated pixels of 1e19, a step to 3e38:
+            // tests/test_gpu_value_domain.py).  The maxima therefore only pre-select; rows with a candidate repeat the eight
+            // compares below.  Cost: 32 compares per wave and row that holds a candidate, nothing on the other rows
+            // (unmeasured).
             const V mx = hs_max3(hs_max3(thr, up.x, dn.x), hs_max3(vl, v.y, ul), hs_max3(up.y, dl, dn.y));
             const V my = hs_max3(hs_max3(thr, up.y, dn.y), hs_max3(v.x, v.z, up.x), hs_max3(up.z, dn.x, dn.z));
             const V mz = hs_max3(hs_max3(thr, up.z, dn.z), hs_max3(v.y, v.w, up.y), hs_max3(up.w, dn.y, dn.w));
             const V mw = hs_max3(hs_max3(thr, up.w, dn.w), hs_max3(v.z, vr, up.z), hs_max3(ur, dn.z, dr));
-            const bool hx = owns && (xok & 1u) && v.x > mx;
-            const bool hy = owns && (xok & 2u) && v.y > my;
-            const bool hz = owns && (xok & 4u) && v.z > mz;
-            const bool hw = owns && (xok & 8u) && v.w > mw;
+            bool hx = owns && (xok & 1u) && v.x > mx;
+            bool hy = owns && (xok & 2u) && v.y > my;
+            bool hz = owns && (xok & 4u) && v.z > mz;
+            bool hw = owns && (xok & 8u) && v.w > mw;
             if (__ballot(hx || hy || hz || hw) != 0ull) {
+                // akazed.cu:1361-1362 as written: false as soon as one neighbour is a NaN
+                hx = hx && v.x > up.x && v.x > dn.x && v.x > vl && v.x > v.y && v.x > ul && v.x > up.y && v.x > dl && v.x > dn.y;
+                hy = hy && v.y > up.y && v.y > dn.y && v.y > v.x && v.y > v.z && v.y > up.x && v.y > up.z && v.y > dn.x && v.y > dn.z;
+                hz = hz && v.z > up.z && v.z > dn.z && v.z > v.y && v.z > v.w && v.z > up.y && v.z > up.w && v.z > dn.y && v.z > dn.w;
+                hw = hw && v.w > up.w && v.w > dn.w && v.w > v.z && v.w > vr && v.w > up.z && v.w > ur && v.w > dn.z && v.w > dr;
                 if (T.cb.n > HS_CBUF - 128) hs_flush(T.cb, cold, lane);    // a row holds at most 128 strict 3x3 maxima per wave
                 const HsCold ca = *cold;                                   // one LDS read of the parked arguments per row with a hit
                 hs_emit(hx, v.x, x0, e, ca, lane, T.cb);

@@ -12,7 +12,8 @@ What a case draws (reference: main.cpp:156-166 for the parameter set, akaze.cpp:
   kernels   the library's own size rule, the streaming kernels forced on, or one launch per sublevel (k_level_tile)
   params    octaves 1-5, sublevels 2-5, per, dthreshold, soffset, derivative factor, all four diffusivities, pattern size, upright,
             max_pts small enough to clamp in a quarter of the cases
-  content   drawn scenes (tests/golden/make_golden.case_scene), optionally with uniform noise on top
+  content   drawn scenes (tests/golden/make_golden.case_scene), optionally with uniform noise on top; in four cases of nine the float legs
+            see them as full-mantissa float content instead of uint8 / 255 (tests/value_domain.py: hdr, x255, offset, dark)
   layout    the caller's images at pitch iAlignUp(w, 128) (main.cpp:174), dense, or at an odd pitch; 0 / 1 / 3 elements into their buffer;
             NaN (0xFF) everywhere outside the images
   legs      float batch -> 1-NN pair matching [-> 2-NN + ratio + cross-check] [-> the batch again on rolled images] [-> the pair call with a
@@ -113,13 +114,18 @@ def draw_more(c, rng, pick):
     # hak_download_batch into pinned / pageable host arrays
     c["ingest"] = bool(rng.random() < 0.3)
     c["download"] = pick((None, None, "pinned", "pageable"))
+    # float content (tests/value_domain.py): the float legs (batch, pair, single, again) take the scenes plus a smooth float term and
+    # full-mantissa noise, scaled / shifted; the FAST and ingest legs keep the uint8 scenes.  `dark` (x 1e-6) has no keypoints at any
+    # dthreshold drawn above (5e-4 .. 3e-3): its float legs compare empty sets, i.e. it only checks that such content yields none on
+    # any entry point -- the planes and keypoints of dark content are compared in tests/test_gpu_value_domain.py
+    c["float_content"] = pick((None, None, None, None, None, "hdr", "x255", "offset", "dark"))
     return c
 
 
 def describe(c):
     kw = ",".join(f"{k}={v}" for k, v in c["kw"].items())
     return (f"#{c['index']:<4d} {c['w']:4d}x{c['h']:<4d} B={c['B']:<2d} {c['mode']:<10s} max_pts={c['max_pts']:<5d} noise={c['noise']:<2d} "
-            f"{'fast ' if c['fast'] else ''}{'' if c['desc'] else 'nodesc '}{'knn2 ' if c['knn2'] else ''}{'again ' if c['again'] else ''}pitch{c['pitch_mode']}+{c['in_offset']} {'resize ' if c['resize'] else ''}{c['order'] + ' ' if c['order'] else ''}{'ingest ' if c['ingest'] else ''}{'dl-' + c['download'] + ' ' if c['download'] else ''}"
+            f"{'fast ' if c['fast'] else ''}{'' if c['desc'] else 'nodesc '}{'knn2 ' if c['knn2'] else ''}{'again ' if c['again'] else ''}pitch{c['pitch_mode']}+{c['in_offset']} {'resize ' if c['resize'] else ''}{c['order'] + ' ' if c['order'] else ''}{'ingest ' if c['ingest'] else ''}{'dl-' + c['download'] + ' ' if c['download'] else ''}{'content=' + c['float_content'] + ' ' if c.get('float_content') else ''}"
             f"{'pair(%.1f%s) ' % (c['pair'][0], ',pinned' if c['pair'][1] else '') if c['pair'] else ''}{kw}")
 
 
@@ -158,6 +164,13 @@ def run_case(ah, okz, torch, synth, mg, c):
             u = u + rng.integers(-c["noise"], c["noise"] + 1, u.shape)
         u8s.append(np.clip(u, 0, 255).astype(np.uint8))
     okw = {k: (int(v) if isinstance(v, bool) else v) for k, v in kw.items()}
+    fc = c.get("float_content")
+    if fc:
+        import value_domain as vd
+        tf = {"hdr": lambda b: b, "x255": lambda b: b * 255.0, "offset": lambda b: b - 0.5, "dark": lambda b: b * 1e-6}[fc]
+        planes = [vd.pitched(tf(vd.from_u8(u, c["scene_seed"] + i)).astype(np.float32), p) for i, u in enumerate(u8s)]
+    else:
+        planes = [synth.to_float(u, p) for u in u8s]
     fails, npts, nmatch = [], 0, 0
     saved = {k: os.environ.pop(k, None) for k in KNOBS}
     os.environ.update(MODES[c["mode"]])
@@ -168,7 +181,7 @@ def run_case(ah, okz, torch, synth, mg, c):
         d_pts = torch.zeros(B * mp * 104, dtype=torch.uint8, device="cuda")
         d_num = torch.zeros(B, dtype=torch.int32, device="cuda")
         # ---- float path: batch entry point, then pair matching on the device records
-        want = [okz.detect_and_compute(synth.to_float(u, p), w, okz.default_params(**okw), max_pts=mp, desc=c["desc"]).points for u in u8s]
+        want = [okz.detect_and_compute(f, w, okz.default_params(**okw), max_pts=mp, desc=c["desc"]).points for f in planes]
         pin = {0: p, 1: w, 2: w + 1, 3: w + 3}[c["pitch_mode"]]
         off = c["in_offset"]
 
@@ -177,7 +190,7 @@ def run_case(ah, okz, torch, synth, mg, c):
             hb = np.full(off + B * h * pin + 4, 0xFF if as_u8 else np.nan, np.uint8 if as_u8 else np.float32)
             for k, i in enumerate(order):
                 v = hb[off + k * h * pin: off + (k + 1) * h * pin].reshape(h, pin)
-                v[:, :w] = u8s[i % nd] if as_u8 else synth.to_float(u8s[i % nd], p)[:, :w]
+                v[:, :w] = u8s[i % nd] if as_u8 else planes[i % nd][:, :w]
             return torch.from_numpy(hb).cuda()
 
         stack = upload(range(B), False)
@@ -240,8 +253,9 @@ def run_case(ah, okz, torch, synth, mg, c):
             ah.check(ah.lib.hak_sync(det.ctx))
             nums3 = d_num.cpu().numpy()
             allp3 = d_pts.cpu().numpy().view(ah.POINT_DTYPE).reshape(B, mp)
+            want8 = want if not fc else [okz.detect_and_compute(synth.to_float(u, p), w, okz.default_params(**okw), max_pts=mp, desc=c["desc"]).points for u in u8s]
             for i in range(B):
-                fails += diff_points(f"device-side uint8 ingest, image {i}", allp3[i, :min(nums3[i], mp)], want[i % nd], fields)
+                fails += diff_points(f"device-side uint8 ingest, image {i}", allp3[i, :min(nums3[i], mp)], want8[i % nd], fields)
         # ---- 2-NN + ratio + cross-check on the same device records
         if B >= 2 and c["desc"] and c["knn2"] and small_sets and not fails:
             ratio, cross = c["knn2"]
@@ -284,7 +298,7 @@ def run_case(ah, okz, torch, synth, mg, c):
             ah.initAkazeData(r2, cap2, True, True, pinned=pinned)
             det.detectAndComputePair(img_ptr(0), img_ptr(1 % B), r1, r2, (w, h, pin), True, True)
             a = want[0].copy()
-            b = want[1 % nd] if cap2 >= len(want[1 % nd]) else okz.detect_and_compute(synth.to_float(u8s[1 % nd], p), w, okz.default_params(**okw), max_pts=cap2).points
+            b = want[1 % nd] if cap2 >= len(want[1 % nd]) else okz.detect_and_compute(planes[1 % nd], w, okz.default_params(**okw), max_pts=cap2).points
             okz.match(a, b)
             fails += diff_points("pair call image 1", r1.h_data[:r1.num_pts], a, FIELDS + MFIELDS)
             fails += diff_points("pair call image 2", r2.h_data[:r2.num_pts], b, FIELDS)
@@ -313,7 +327,7 @@ def run_case(ah, okz, torch, synth, mg, c):
         if c["resize"] and w - c["resize"][0] >= 134 and h - c["resize"][1] >= 80:
             w2, h2 = w - c["resize"][0], h - c["resize"][1]
             p2 = ah.iAlignUp(w2, 128)
-            crop = np.ascontiguousarray(synth.to_float(u8s[0], p)[:h2, :p2]) if p2 <= p else None
+            crop = np.ascontiguousarray(planes[0][:h2, :p2]) if p2 <= p else None
             if crop is not None:
                 crop[:, w2:] = 0
                 det.detectAndCompute(torch.from_numpy(crop).cuda().data_ptr(), data, (w2, h2, p2), c["desc"])
