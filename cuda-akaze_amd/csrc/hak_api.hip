@@ -1,9 +1,5 @@
-// hak_api.hip -- C ABI of libhipakaze: context, FED schedule, launch sequence.
-//
-// Host orchestration restates Akazer::detectAndCompute / detect
-// (akaze.cpp:101-150, 240-503) with every per-image scalar kept on the device
-// (kcontrast, point counts), one launch sequence per BATCH of images
-// (blockIdx.z = image) and no host synchronisation inside the sequence.
+// hak_api.hip -- C ABI of libhipakaze: context, FED schedule and the extern "C" entry points.  The launch sequence they enqueue
+// is hak_sequence.hip.
 #include "hak_internal.h"
 #include <chrono>
 #include <cmath>
@@ -18,8 +14,6 @@
 // ------------------------------------------------------------------ errors
 static thread_local std::string g_err;
 int hak_fail(const std::string& m) { g_err = m; return 1; }
-static thread_local const char* g_launch_err = nullptr;
-void hak_note_launch_error(const char* msg) { if (!g_launch_err) g_launch_err = msg; }
 
 extern "C" const char* hak_last_error(void) { return g_err.c_str(); }
 
@@ -366,22 +360,6 @@ extern "C" int hak_set_retain_best(hak_ctx* c, int on)
     return 0;
 }
 
-// The reference issues everything on stream 0 (akaze.cpp:101-150, 55-64): whatever its caller enqueued on the default stream before a call
-// -- a hipMemset of an output array, an asynchronous upload, a kernel of its own -- is finished when the call's first kernel starts.  A
-// context's streams are non-blocking; this makes the call's stream wait for the NULL stream's work enqueued so far (device-side: an event
-// record there, a wait here; nothing when the context runs on the NULL stream itself).  Never inside a stream capture: every caller sits
-// in front of run_detect_inner's capture.
-static void order_after_null_stream(hak_ctx* c, hipStream_t st)
-{
-    if (!c || !c->null_order || !c->ev_null || st == nullptr) return;
-    // (an idle NULL stream -- the reference's own call pattern with its blocking copies -- costs one query; the cross-queue dependency
-    // itself was measured at ~15 us per call: 0.54 -> 0.55 ms for the pair call when taken unconditionally)
-    const hipError_t q = hipStreamQuery(nullptr);
-    if (q == hipSuccess) return;
-    (void)hipGetLastError();
-    if (hipEventRecord(c->ev_null, nullptr) != hipSuccess || hipStreamWaitEvent(st, c->ev_null, 0) != hipSuccess) (void)hipGetLastError();
-}
-
 extern "C" int hak_phase_event(hak_ctx* c, void** ev)
 {
     if (!c || !ev) return fail("null argument");
@@ -403,436 +381,7 @@ extern "C" int hak_sync(hak_ctx* c)
     return 0;
 }
 
-// ------------------------------------------------------- the launch sequence
-// The key map must be all zero when a launch sequence starts; every sequence restores that itself (k_clear_cand_maps).  If a
-// call fails between writing the map and cleaning it up, the flag stays set and the next call clears the map in full -- eagerly
-// on the context's stream and never inside a stream capture, so a replayed graph cannot miss (or needlessly carry) the clear.
-void maps_guard_begin(hak_ctx* c)
-{
-    if (c->maps_dirty) {
-        const size_t h = c->L.oct[0].h, words = (c->L.oct[0].w + 63) / 64, B = c->cfg.batch;
-        (void)hipMemsetAsync(c->maps, 0, sizeof(unsigned long long) * (size_t)c->L.oct[0].plane * B, c->stream);
-        (void)hipMemsetAsync(c->bitmap, 0, sizeof(unsigned long long) * h * words * B, c->stream);
-        (void)hipMemsetAsync(c->rowcount, 0, sizeof(int) * h * B, c->stream);
-    }
-    c->maps_dirty = true;
-}
-int maps_guard_end(hak_ctx* c, int rc)
-{
-    if (!rc) c->maps_dirty = false;
-    // (on the stream the sequence ended on: a marker on the caller's idle stream would make the next call's idle test fail)
-    if (c->ev_last) (void)hipEventRecord(c->ev_last, c->sync_stream ? c->sync_stream : c->stream);
-    return rc;
-}
-
-// kernels_level.hip's one-launch sublevel: by the size rule unless a test forces the streaming kernels (fuse_sf == 2)
-static bool level_tile_pays(const hak_ctx* c, const HakOct& oc, int nimg)
-{
-    const int mode = c->knobs.level_tile;
-    if (mode != 1) return mode != 0;
-    // (round 4, measured: taking the tile kernel for the latency-bound small octaves of a LARGE batch as well -- octave 3, or octaves
-    // 2-3, of 512 images -- cuts the FED launches from 46 to 26 / 18 and costs 8-17 ms per sequence: its halo work, (T + 2n)^2 / T^2
-    // of the useful work, is only worth paying where launches, not bytes or arithmetic, are the cost)
-    return c->knobs.fuse_sf != 2 && (long)oc.w * oc.h * nimg <= HAK_LEVEL_TILE_MAX_PX;
-}
-
-// Launch-bound sequences -- a single image: octave 0 small enough for k_level_tile -- are issued in SPINE order (enqueue_detect) and
-// eagerly instead of as a replayed graph: their time is the longest dependency chain, not bytes.  Round 4 tried the same for a PAIR
-// (two to four images; HAK_SPINE_MAX_PX widens the rule): with four chains of two-image kernels in flight the kernels slow each other
-// down and the call got slower, 0.60 -> 0.635 ms (8 hardware queues) / 0.675 (4) -- a pair is bound by the GPU time of its small
-// kernels, the replayed per-octave order is the better one for it (profiles/r04_pair_timeline.txt).
-static bool spine_pays(const hak_ctx* c, int nimg)
-{
-    const long max_px = c->knobs.spine_max_px;
-    if (max_px > 0 && c->knobs.level_tile == 1) return c->knobs.fuse_sf != 2 && (long)c->L.oct[0].w * c->L.oct[0].h * nimg <= max_px;
-    return level_tile_pays(c, c->L.oct[0], nimg);
-}
-
-static int enqueue_detect(hak_ctx* c, const float* d_images, long image_stride, int pitch, int nimg,
-                          hak_point* d_points, int* d_num_pts, int desc, int max_pts, hak_point* h_points = nullptr, int cap0 = 0, int cap1 = 0)
-{
-    const hak_config& cfg = c->cfg;
-    const HakLayout& L = c->L;
-    // Octave o+1 depends only on Lt(o, 0) (the reference decimates from sublevel 0, akaze.cpp:371-375).
-    const bool spine = c->concurrent && L.noct > 1 && spine_pays(c, nimg);
-    const hipStream_t main_st = c->stream;
-    c->sync_stream = c->stream;
-    float* A = c->arena;
-    const long S = L.arena;
-    HakBatch b{A, S, nimg, c->state, c->maps, L.oct[0].plane, c->bitmap, c->rowcount, c->cand, c->cand_cap, &c->knobs, c->perm, cfg.max_pts};
-    b.cap0 = cap0; b.cap1 = cap1;
-    if (c->retain_best) b.sel = c->sel;
-    c->last_fast = false;
-    c->fed_launches = 0;
-    c->fed_fused_bytes = 0;
-
-    bool hess_fused[HAK_MAX_OCTAVES * HAK_MAX_SCALES] = {};
-    bool hess_lp[HAK_MAX_OCTAVES * HAK_MAX_SCALES] = {};     // the level's Hessian low-passes Lt(o,s-1) itself: `smooth` was not written
-    const bool level_hess_on = c->knobs.level_hess != 0;
-    // ---- part A of level (o, s): build Lt(o, s) and the sigma=1 low-pass `smooth` the level's Hessian reads (akaze.cpp:325-421)
-    // smooth_alt != nullptr: the level's sigma=1 low-pass goes there instead of the octave's `smooth` plane (side-stream Hessians below)
-    auto build_level = [&](int o, int s, hipStream_t st, float* smooth_alt = nullptr) {
-        const HakOct oc = L.oct[o];
-        float* smooth = smooth_alt ? smooth_alt : A + L.smooth_off[o];
-        float* flow = A + L.flow_off[o];
-        float* tmp = A + L.tmp_off[o];
-        const LevelPlan& lp = c->plan[(size_t)o * L.ms + s];
-        float* Lt = A + L.lt(o, s);
-        if (o == 0 && s == 0) {                                                   // akaze.cpp:325-332 in two passes over img
-            ProfScope ps(c, HAK_PROF_CONTRAST, st);
-            hak_launch_base_level(st, d_images, image_stride, pitch, Lt, tmp /* free until the FED cycle of (0,1) */, S, oc.w, oc.h, oc.p, nimg, c->taps1,
-                                  c->taps_base, c->base_R, c->state, cfg.per, L.noct, c->knobs);
-            return;
-        }
-        const int n = lp.nsteps;
-        // small launches (single images, small octaves of small batches): the whole sublevel in one launch out of LDS tiles --
-        // octave heads (one launch instead of decimation + conductivity + FED groups) and every cycle long enough that the tile
-        // kernel's halo work costs less than the launches it saves (by the size rule: n >= 8, i.e. octaves 2 and up of the demo
-        // schedule; shorter cycles keep k_smooth_flow + k_fed_multi, which spend less GPU time per pixel)
-        if (level_tile_pays(c, oc, nimg) && (s == 0 || n >= c->knobs.level_min_steps || c->knobs.level_tile == 2)) {
-            ProfScope ps(c, HAK_PROF_FED, st);
-            // (the level's Hessian rides along when the cycle is long enough: hess_fused tells hessian_level below)
-            const int nl = hak_launch_level_tile(st, s == 0 ? A + L.lt(o - 1, 0) : A + L.lt(o, s - 1), s == 0 ? L.oct[o - 1] : oc, s == 0, smooth, Lt, tmp, S,
-                                                 oc, nimg, c->taps1, cfg.diffusivity, lp.tau.data(), n, c->state, o, 0.f,
-                                                 level_hess_on ? A + L.dxy(o, s) : nullptr, lp.sigma_size, &b, &L, &c->htab, s, cfg.dthreshold,
-                                                 &hess_fused[o * HAK_MAX_SCALES + s]);
-            c->fed_launches += nl;
-            c->fed_fused_bytes += (s == 0 ? 1.0 * L.oct[o - 1].w * L.oct[o - 1].h : 4.0 * oc.w * oc.h) + 8.0 * oc.w * oc.h + (nl - 1) * 12.0 * oc.w * oc.h;
-            return;
-        }
-        const int G = hak_fed_groups(n, c->knobs.max_fuse, oc.w);     // launches of this FED cycle
-        const float* fsrc;          // input of the first FED launch
-        bool fused_first = false;
-        if (s == 0) {                                                             // akaze.cpp:369-392
-            // octave head: decimation + low-pass + conductivity + the first FED group in one streaming pass when covered
-            if (c->knobs.fuse_head && hak_stream_pays(c->knobs.fuse_sf, oc.w, oc.h, nimg)) {
-                ProfScope ps(c, HAK_PROF_FED, st);
-                fused_first = hak_launch_fed_sf_head(st, A + L.lt(o - 1, 0), L.oct[o - 1], smooth, flow, (G % 2 == 1) ? Lt : tmp, S, oc,
-                                                     nimg, c->taps1, cfg.diffusivity, lp.tau.data(), hak_fed_group_size(n, G, 0),
-                                                     c->state, o, G > 1);
-                if (fused_first) {
-                    c->fed_launches++;           // reads the even rows of Lt(o-1,0), writes smooth, L' (+ g for later launches)
-                    c->fed_fused_bytes += 2.0 * L.oct[o - 1].w * L.oct[o - 1].h + (G > 1 ? 12.0 : 8.0) * oc.w * oc.h;
-                }
-            }
-            // otherwise decimate Lt(o-1,0) so that the last of G ping-pong launches lands in Lt(o,0)
-            float* first = (G % 2 == 0) ? Lt : tmp;
-            if (!fused_first) {
-                ProfScope ps(c, HAK_PROF_DOWN, st);
-                hak_launch_down_smooth(st, A + L.lt(o - 1, 0), first, smooth, S, L.oct[o - 1], oc, nimg, c->taps1);
-            }
-            fsrc = first;
-        } else {                                                                  // akaze.cpp:393-421
-            fsrc = A + L.lt(o, s - 1);
-        }
-        // sublevels > 0: low-pass + conductivity + the first FED group in one streaming pass when the case is covered
-        // (PM_G2, 16-byte rows); the conductivity plane is written only if later groups of the cycle need it
-        if (s == 0) {
-            if (!fused_first) {
-                ProfScope ps(c, HAK_PROF_FLOW, st);
-                hak_launch_flow(st, smooth, flow, S, oc.w, oc.h, oc.p, nimg, cfg.diffusivity, c->state, o, 0.f);
-            }
-        } else if (hak_stream_pays(c->knobs.fuse_sf, oc.w, oc.h, nimg) && cfg.diffusivity == HAK_PM_G2 && (oc.w & 3) == 0 && oc.w >= 16 &&
-                   oc.h >= 8) {
-            const int ns0 = hak_fed_group_size(n, G, 0);
-            float* dst0 = (G % 2 == 1) ? Lt : tmp;
-            // the low-pass has one reader, the level's Hessian: when that runs as the streaming kernel it low-passes Lt(o,s-1)
-            // itself (LP variant) and the plane is not written at all
-            const bool lp_hess = c->knobs.hess_lp != 0 && hak_stream_pays(c->knobs.hess_stream, oc.w, oc.h, nimg) &&
-                                 hak_hessian_stream_covers(oc.w, oc.h, lp.sigma_size, true);
-            ProfScope ps(c, HAK_PROF_FED, st);
-            fused_first = hak_launch_fed_sf(st, fsrc, smooth, flow, dst0, S, oc.w, oc.h, oc.p, nimg, c->taps1, cfg.diffusivity,
-                                            lp.tau.data(), ns0, c->state, o, 0.f, G > 1, !lp_hess);
-            if (fused_first) {
-                hess_lp[o * HAK_MAX_SCALES + s] = lp_hess;
-                c->fed_launches++;               // reads L, writes L' (+ smooth unless the Hessian is LP, + g for later launches)
-                c->fed_fused_bytes += ((G > 1 ? 16.0 : 12.0) - (lp_hess ? 4.0 : 0.0)) * oc.w * oc.h;
-            }
-        }
-        if (s != 0 && !fused_first) {                                             // akaze.cpp:403-404 in one pass
-            ProfScope ps(c, HAK_PROF_LOWPASS, st);
-            hak_launch_smooth_flow(st, fsrc, smooth, flow, S, oc.w, oc.h, oc.p, nimg, c->taps1, cfg.diffusivity,
-                                   c->state, o, 0.f);
-        }
-        // the n explicit steps of the cycle in G fused launches, ping-pong Lt <-> tmp, ending in Lt
-        const float* src = fsrc;
-        int done = 0;
-        for (int g = 0; g < G; g++) {
-            const int ns = hak_fed_group_size(n, G, g);
-            float* dst = ((G - g) % 2 == 1) ? Lt : tmp;
-            if (!(g == 0 && fused_first)) {
-                ProfScope ps(c, HAK_PROF_FED, st);
-                hak_launch_fed_group(st, src, flow, dst, S, oc.w, oc.h, oc.p, nimg, lp.tau.data() + done, ns);
-                c->fed_launches++;
-                c->fed_fused_bytes += 12.0 * oc.w * oc.h;       // reads L and g, writes L'
-            }
-            done += ns;
-            src = dst;
-        }
-    };
-    // ---- part B of level (o, s): derivatives + determinant + extrema (akaze.cpp:354, 423, 431-433).  Level (0, 0) differentiates
-    // Lt itself, every other level the low-pass of its predecessor (D13).  (The determinant goes to HBM only in the dilation > 4
-    // fallback: `flow` is free at every call.)
-    auto hessian_level = [&](int o, int s, hipStream_t st, const float* smooth_alt = nullptr) {
-        if (hess_fused[o * HAK_MAX_SCALES + s]) return;              // done inside k_level_tile
-        const HakOct oc = L.oct[o];
-        const LevelPlan& lp = c->plan[(size_t)o * L.ms + s];
-        const bool lph = hess_lp[o * HAK_MAX_SCALES + s];
-        const float* hsrc = (o == 0 && s == 0) ? A + L.lt(0, 0) : lph ? A + L.lt(o, s - 1) : smooth_alt ? smooth_alt : A + L.smooth_off[o];
-        ProfScope ps(c, HAK_PROF_HESSIAN, st);
-        if (!hak_launch_hessian_level(st, hsrc, A + L.dxy(o, s), A + L.flow_off[o], false, S, oc.w, oc.h, oc.p, nimg,
-                                      lp.sigma_size, &b, &L, &c->htab, o, s, cfg.dthreshold, lph ? c->taps1 : nullptr))
-            hak_launch_extrema_level(st, b, L, c->dtab, o, s, cfg.dthreshold, L.flow_off[o]);
-    };
-
-    hak_launch_reset_state(main_st, c->state, nimg);   // (the key map is all zero here: hak_create / k_clear_cand_maps / maps_guard)
-
-    if (spine) {
-        // Launch-bound calls (a single image): the dependency chain base -> head(1) -> head(2) -> ... -> every sublevel of the
-        // last octave is the critical path, so it runs on ONE stream without cross-queue waits (each costs 15-35 us in a replayed
-        // graph, profiles/r03_single_*); what hangs off it -- the remaining sublevels and all Hessians of octaves 0 .. noct-2 --
-        // goes to side streams, one per octave.
-        const int last = L.noct - 1;
-        hipGraphNode_t head_node[HAK_MAX_OCTAVES] = {};
-        hipGraph_t cap_graph = nullptr;
-        for (int o = 0; o <= last; o++) {
-            build_level(o, 0, main_st);
-            if (o < last) {
-                (void)hipEventRecord(c->ev_ready[o], main_st);                    // Lt(o,0) + its low-pass ready: side stream o may start
-                // while capturing: remember the head's graph node (see below)
-                hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-                const hipGraphNode_t* deps = nullptr;
-                size_t ndeps = 0;
-                if (hipStreamGetCaptureInfo_v2(main_st, &cs, nullptr, &cap_graph, &deps, &ndeps) == hipSuccess &&
-                    cs == hipStreamCaptureStatusActive && ndeps == 1) head_node[o] = deps[0];
-                else (void)hipGetLastError();
-            }
-        }
-        // The graph executor deals a fork's branches to its queues by position: the first outgoing edge of a node stays on the
-        // node's queue, the k-th goes k-1 queues further (of four).  Every side stream forks from the spine as some head's SECOND
-        // edge, so all three would share one queue and run one after the other (measured: 440 us of side work in a row).  Empty
-        // nodes in front of a fork move its side branch further along.  The replay submits queue by queue -- the spine's first, then
-        // the others from the last to the first -- so the longest side chain (octave 0's) gets the last queue, the shortest the
-        // first.  Pure placement: results and ordering are unaffected, and a runtime that places nodes differently merely ignores
-        // the hint (HAK_GRAPH_PADS=0 switches it off).
-        for (int o = 0; o < last && c->knobs.graph_pads; o++)
-            for (int k = 0; k < last - 1 - o && head_node[o] && cap_graph; k++) {
-                hipGraphNode_t pad = nullptr;
-                if (hipGraphAddEmptyNode(&pad, cap_graph, &head_node[o], 1) != hipSuccess) (void)hipGetLastError();
-            }
-        // Side streams: one per remaining octave by default.  The chain + noct-1 side streams want noct hardware queues besides the
-        // null stream's; the runtime gives a process four (GPU_MAX_HW_QUEUES), so at four octaves two side chains share a queue and
-        // run one after the other (C++ demo: 1.08 instead of 0.91 ms per 1080p pair).  A process that makes single-image calls
-        // should start with GPU_MAX_HW_QUEUES=8 (the demo does) -- the library does not set it itself, because a
-        // process that runs BATCHES loses 2 % (1080p) to 13 % (720p) with eight queues.  HAK_SIDE_STREAMS = n < noct-1 makes
-        // octaves n-1 .. noct-2 share the last side stream by design (same time as the shared queue).
-        const int nside = c->knobs.side_streams < last ? c->knobs.side_streams : (last > 0 ? last : 1);
-        auto side_of = [&](int o) { return c->oct_stream[1 + (o < nside ? o : nside - 1)]; };
-        // the remaining work, one level per octave in turn, each octave's first node behind the wait for its head
-        for (int s = 0; s < L.ms; s++)
-            for (int k = 0; k <= last; k++) {
-                const int o = k == 0 ? last : k - 1;                              // the spine's own octave first
-                const hipStream_t st = o == last ? main_st : side_of(o);
-                if (s == 0 && o != last && hipStreamWaitEvent(st, c->ev_ready[o], 0) != hipSuccess) return fail("stream wait");
-                if (s > 0) build_level(o, s, st);
-                hessian_level(o, s, st);
-            }
-        for (int i = 0; i < nside && last > 0; i++) {
-            (void)hipEventRecord(c->ev_done[i + 1], c->oct_stream[i + 1]);
-            if (hipStreamWaitEvent(main_st, c->ev_done[i + 1], 0) != hipSuccess) return fail("stream join");
-        }
-    } else {
-        // each octave on its own stream, chained by events: the small octaves' launches are latency chains of a few hundred waves
-        // and hide under octave 0's chip-filling kernels
-        // Small launches in the tile-kernel regime (a pair, a handful of images): octave 0 is the longest chain, and a third of it
-        // are its four Hessians, which nothing in the scale space waits for.  They move to a stream of their own.  The only
-        // hazard is the `smooth` plane (level s's Hessian reads it, level s+1's low-pass overwrites it): the levels alternate
-        // between `smooth` and `tmp`, which is free in an octave whose FED cycles are single launches (G = 1: the cycle lands in
-        // Lt directly), so level s+1's low-pass only waits for the Hessian of level s-1.  profiles/r05_pair_serial_timeline.txt:
-        // 292 us of chain (alone) become 183 + the last Hessian.
-        // MEASURED, OFF BY DEFAULT (HAK_HESS_SIDE=1): the pair call gets SLOWER, 0.567-0.572 -> 0.620-0.623 ms (4 or 5 hardware
-        // queues alike; 6: 0.82): as with the spine order of round 4, a fifth chain of two-image kernels stretches the other four by
-        // more than the critical chain shrinks -- the call is bound by the chip's throughput on these small kernels, not by the
-        // order they are issued in.
-        bool side0 = c->knobs.hess_side != 0 && c->concurrent && L.noct > 1 && c->hess_stream && L.ms <= HAK_MAX_SCALES &&
-                     !hak_stream_pays(c->knobs.hess_stream, L.oct[0].w, L.oct[0].h, nimg) && !level_tile_pays(c, L.oct[0], nimg) &&
-                     !hak_stream_pays(c->knobs.fuse_sf, L.oct[0].w, L.oct[0].h, nimg);
-        for (int s = 1; s < L.ms && side0; s++)
-            side0 = hak_fed_groups(c->plan[s].nsteps, c->knobs.max_fuse, L.oct[0].w) == 1 && c->plan[s].sigma_size <= 4;
-        hipStream_t st = main_st;
-        for (int o = 0; o < L.noct; o++) {
-            if (c->concurrent && o > 0) {                       // this octave's chain waits only for Lt(o-1,0)
-                st = c->oct_stream[o];
-                if (hipStreamWaitEvent(st, c->ev_ready[o - 1], 0) != hipSuccess) return fail("stream wait");
-            }
-            for (int s = 0; s < L.ms; s++) {
-                if (o == 0 && side0) {
-                    float* sm = (s & 1) ? A + L.tmp_off[0] : A + L.smooth_off[0];
-                    // (level s's low-pass target was last read by the Hessian of level s - 2)
-                    if (s >= 2 && hipStreamWaitEvent(st, c->ev_hd[s - 2], 0) != hipSuccess) return fail("stream wait");
-                    build_level(0, s, st, sm);
-                    if (s == 0) (void)hipEventRecord(c->ev_ready[0], st);
-                    (void)hipEventRecord(c->ev_hs[s], st);
-                    if (hipStreamWaitEvent(c->hess_stream, c->ev_hs[s], 0) != hipSuccess) return fail("stream wait");
-                    hessian_level(0, s, c->hess_stream, sm);
-                    (void)hipEventRecord(c->ev_hd[s], c->hess_stream);
-                    continue;
-                }
-                build_level(o, s, st);
-                if (c->concurrent && s == 0) (void)hipEventRecord(c->ev_ready[o], st);   // Lt(o,0) final: octave o+1 may start
-                hessian_level(o, s, st);
-            }
-            if (c->concurrent && o > 0) (void)hipEventRecord(c->ev_done[o], st);
-        }
-        if (c->concurrent)
-            for (int o = 1; o < L.noct; o++)
-                if (hipStreamWaitEvent(main_st, c->ev_done[o], 0) != hipSuccess) return fail("stream join");
-        if (side0)                                              // (the stream runs in order: its last event covers all four)
-            if (hipStreamWaitEvent(main_st, c->ev_hd[L.ms - 1], 0) != hipSuccess) return fail("stream join");
-    }
-    // the scale space (bound by HBM stores) is done, the keypoint stages (bound by gathers and integer work) begin: a caller that
-    // runs two contexts lets the other one start its scale space here (hak_phase_event)
-    {
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        hipGraph_t g = nullptr;
-        const hipGraphNode_t* deps = nullptr;
-        size_t ndeps = 0;
-        if (hipStreamGetCaptureInfo_v2(main_st, &cs, nullptr, &g, &deps, &ndeps) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusNone; }
-        hipError_t pe;
-        if (cs == hipStreamCaptureStatusActive) {
-            // inside a capture a plain record would be a capture-internal dependency: the record becomes an event-record NODE behind
-            // the stream's current frontier, and the frontier moves to it
-            hipGraphNode_t node = nullptr;
-            pe = hipGraphAddEventRecordNode(&node, g, deps, ndeps, c->ev_phase);
-            if (pe == hipSuccess) pe = hipStreamUpdateCaptureDependencies(main_st, &node, 1, hipStreamSetCaptureDependencies);
-        } else pe = hipEventRecord(c->ev_phase, main_st);
-        if (pe != hipSuccess) { fprintf(stderr, "hipakaze: phase event record: %s\n", hipGetErrorString(pe)); (void)hipGetLastError(); }
-    }
-    bool tail_fork = false;
-    { ProfScope ps(c, HAK_PROF_NMS);                                              // akaze.cpp:449-455
-      hak_launch_nms_emit(main_st, b, L, c->dtab, c->psz, d_points, max_pts, d_num_pts);
-      // the clean-up for the next sequence needs only the candidate list: beside the descriptor kernels, not in front of them
-      // (batches: no gain beside 5 ms of descriptor kernels, A/B 5 640 vs 5 710 pairs/s; the pair call: the fork's two cross-stream
-      // waits in the replayed graph cost more than the 5 us kernel they move aside, 0.571 vs 0.544 ms, round 5)
-      tail_fork = spine && c->knobs.tail_fork;
-      if (tail_fork) {
-          (void)hipEventRecord(c->ev_tail_fork, main_st);
-          if (hipStreamWaitEvent(c->oct_stream[1], c->ev_tail_fork, 0) != hipSuccess) return fail("stream wait");
-          hak_launch_clear_maps(c->oct_stream[1], b, L);
-          (void)hipEventRecord(c->ev_tail_join, c->oct_stream[1]);
-      } else hak_launch_clear_maps(main_st, b, L); }
-    { ProfScope ps(c, HAK_PROF_DESCRIBE);                                         // akaze.cpp:124-131
-      hak_launch_describe(main_st, b, L, c->dtab, d_points, max_pts, cfg.descriptor_pattern_size, cfg.upright, desc, c->htab.dsc_plan_ok); }
-    if (h_points)                                                                 // pinned destination: records and count go out in the same sequence
-        hak_launch_download(main_st, d_points, d_num_pts, max_pts, nimg, h_points, c->h_num);
-    if (tail_fork && hipStreamWaitEvent(main_st, c->ev_tail_join, 0) != hipSuccess) return fail("stream join");
-    if (hipGetLastError() != hipSuccess) return fail("kernel launch failed");
-    if (g_launch_err) { const char* m = g_launch_err; g_launch_err = nullptr; return fail(m); }
-    return 0;
-}
-
-// ------------------------------------------------------- integer FAST path
-// Akazer::fastDetectAndCompute / fastDetect (akaze.cpp:153-201, 506-743): same orchestration on int32 planes.
-static int enqueue_fast_detect(hak_ctx* c, const unsigned char* d_images, long image_stride, int pitch, int nimg,
-                               hak_point* d_points, int* d_num_pts, int desc, int max_pts)
-{
-    const hak_config& cfg = c->cfg;
-    const HakLayout& L = c->L;
-    hipStream_t st = c->stream;
-    int* A = reinterpret_cast<int*>(c->arena);
-    const long S = L.arena;
-    HakBatch b{c->arena, S, nimg, c->state, c->maps, L.oct[0].plane, c->bitmap, c->rowcount, c->cand, c->cand_cap, &c->knobs, c->perm, cfg.max_pts};
-    if (c->retain_best) b.sel = c->sel;
-    const int idthreshold = 65;                                                   // akaze.cpp:559
-    c->last_fast = true;
-    c->sync_stream = c->stream;
-    hakf_launch_reset(st, c->state, nimg);              // (the key map is all zero here: hak_create / k_clear_cand_maps / maps_guard)
-    for (int o = 0; o < L.noct; o++) {
-        const HakOct oc = L.oct[o];
-        int* smooth = A + L.smooth_off[o];
-        int* flow = A + L.flow_off[o];
-        int* tmp = A + L.tmp_off[o];
-        for (int s = 0; s < L.ms; s++) {
-            const LevelPlan& lp = c->plan[(size_t)o * L.ms + s];
-            int* Lt = A + L.lt(o, s);
-            if (o == 0 && s == 0) {                                               // akaze.cpp:589-623
-                // one fused pass + a histogram pass over the gradient plane it leaves in det(0,0) (free until the Hessian below)
-                if (!hakf_launch_base_level(st, d_images, image_stride, pitch, Lt, tmp, S, oc.w, oc.h, oc.p, nimg, c->itaps1,
-                                            c->itaps_base, c->base_R, c->state, cfg.per, L.noct, c->knobs)) {
-                    hakf_launch_conv_u8(st, d_images, image_stride, pitch, smooth, S, oc.w, oc.h, oc.p, nimg, c->itaps1, 2);
-                    hakf_launch_contrast(st, smooth, S, oc.w, oc.h, oc.p, nimg, c->state, cfg.per, L.noct);
-                    hakf_launch_conv_u8(st, d_images, image_stride, pitch, Lt, S, oc.w, oc.h, oc.p, nimg, c->itaps_base, c->base_R);
-                }
-                if (!hakf_launch_hessian_level(st, Lt, A + L.dxy(o, s), flow, false, S, oc.w, oc.h, oc.p, nimg,
-                                               lp.sigma_size, &b, &L, &c->htab, o, s, idthreshold)) {
-                    hakf_launch_hessian(st, Lt, A + L.dxy(o, s), flow, S, oc.w, oc.h, oc.p, nimg, lp.sigma_size);
-                    hakf_launch_extrema(st, b, L, c->dtab, o, s, idthreshold, L.flow_off[o]);
-                }
-                continue;
-            }
-            const int n = lp.nsteps;
-            if (level_tile_pays(c, oc, nimg)) {
-                bool hess_done = false;
-                hakf_launch_level_tile(st, s == 0 ? A + L.lt(o - 1, 0) : A + L.lt(o, s - 1), s == 0 ? L.oct[o - 1] : oc, s == 0, smooth, Lt, tmp, S, oc,
-                                       nimg, c->itaps1, cfg.diffusivity, lp.tau.data(), n, c->state, o,
-                                       c->knobs.level_hess ? A + L.dxy(o, s) : nullptr, lp.sigma_size, &b, &L, &c->htab, s, idthreshold, &hess_done);
-                if (!hess_done && !hakf_launch_hessian_level(st, smooth, A + L.dxy(o, s), flow, false, S, oc.w, oc.h, oc.p, nimg,
-                                               lp.sigma_size, &b, &L, &c->htab, o, s, idthreshold)) {
-                    hakf_launch_hessian(st, smooth, A + L.dxy(o, s), flow, S, oc.w, oc.h, oc.p, nimg, lp.sigma_size);
-                    hakf_launch_extrema(st, b, L, c->dtab, o, s, idthreshold, L.flow_off[o]);
-                }
-                continue;
-            }
-            // FED cycle in G fused launches (the float path's streaming kernel instantiated for int32) when the width
-            // allows 16-byte rows, else one step per launch; ping-pong Lt <-> tmp so that the last launch lands in Lt
-            const bool fused = (oc.w % 4) == 0;
-            const int G = fused ? hak_fed_groups(n, c->knobs.max_fuse, oc.w) : n;
-            const int* src;
-            bool fused_first = false;
-            if (s == 0) {                                                         // akaze.cpp:640-662
-                int* first = (G % 2 == 0) ? Lt : tmp;
-                if (fused && c->knobs.fuse_head && hak_stream_pays(c->knobs.fuse_sf, oc.w, oc.h, nimg))
-                    fused_first = hakf_launch_fed_sf_head(st, A + L.lt(o - 1, 0), L.oct[o - 1], smooth, flow, (G % 2 == 1) ? Lt : tmp, S, oc,
-                                                          nimg, c->itaps1, cfg.diffusivity, lp.tau.data(), hak_fed_group_size(n, G, 0),
-                                                          c->state, o, G > 1);
-                if (!fused_first) {
-                    hakf_launch_down_smooth(st, A + L.lt(o - 1, 0), first, smooth, S, L.oct[o - 1], oc, nimg, c->itaps1);
-                    hakf_launch_flow(st, smooth, flow, S, oc.w, oc.h, oc.p, nimg, cfg.diffusivity, c->state, o);
-                }
-                src = first;
-            } else {                                                              // akaze.cpp:664-695
-                src = A + L.lt(o, s - 1);
-                // low-pass + conductivity + first FED group in one streaming pass when covered, else low-pass + flow in one tile pass
-                if (fused && hak_stream_pays(c->knobs.fuse_sf, oc.w, oc.h, nimg))
-                    fused_first = hakf_launch_fed_sf(st, src, smooth, flow, (G % 2 == 1) ? Lt : tmp, S, oc.w, oc.h, oc.p, nimg, c->itaps1,
-                                                     cfg.diffusivity, lp.tau.data(), hak_fed_group_size(n, G, 0), c->state, o, G > 1);
-                if (!fused_first)
-                    hakf_launch_smooth_flow(st, src, smooth, flow, S, oc.w, oc.h, oc.p, nimg, c->itaps1, cfg.diffusivity, c->state, o);
-            }
-            int done = 0;
-            for (int g = 0; g < G; g++) {
-                const int ns = fused ? hak_fed_group_size(n, G, g) : 1;
-                int* dst = ((G - g) % 2 == 1) ? Lt : tmp;
-                if (g == 0 && fused_first) { done += ns; src = dst; continue; }
-                if (fused) hakf_launch_fed_group(st, src, flow, dst, S, oc.w, oc.h, oc.p, nimg, lp.tau.data() + done, ns);
-                else hakf_launch_nld_step(st, src, flow, dst, S, oc.w, oc.h, oc.p, nimg, lp.tau[done]);
-                done += ns;
-                src = dst;
-            }
-            if (!hakf_launch_hessian_level(st, smooth, A + L.dxy(o, s), flow, false, S, oc.w, oc.h, oc.p, nimg,
-                                           lp.sigma_size, &b, &L, &c->htab, o, s, idthreshold)) {
-                hakf_launch_hessian(st, smooth, A + L.dxy(o, s), flow, S, oc.w, oc.h, oc.p, nimg, lp.sigma_size);
-                hakf_launch_extrema(st, b, L, c->dtab, o, s, idthreshold, L.flow_off[o]);
-            }
-        }
-    }
-    hak_launch_nms_emit(st, b, L, c->dtab, c->psz, d_points, max_pts, d_num_pts, 1);
-    hak_launch_clear_maps(st, b, L);
-    hakf_launch_describe(st, b, L, c->dtab, d_points, max_pts, cfg.descriptor_pattern_size, cfg.upright, desc, c->htab.dsc_plan_ok);
-    if (hipGetLastError() != hipSuccess) return fail("kernel launch failed");
-    return 0;
-}
-
+// ------------------------------------------------------- entry points of the detect sequences (hak_sequence.hip)
 extern "C" int hak_fast_detect_and_compute_batch(hak_ctx* c, const unsigned char* d_images, long image_stride, int pitch,
                                                  int nimg, hak_point* d_points, int* d_num_pts, int desc)
 {
@@ -858,63 +407,6 @@ extern "C" int hak_fast_detect_and_compute(hak_ctx* c, const unsigned char* d_im
     *num_pts = c->h_num[0];
     if (h_points && *num_pts > 0)
         HIP_TRY(hipMemcpy(h_points, d_points, sizeof(hak_point) * (size_t)*num_pts, hipMemcpyDeviceToHost));
-    return 0;
-}
-
-// enqueue one detect+describe sequence: replay the captured graph when the arguments repeat, else capture it
-static int run_detect_inner(hak_ctx* c, const float* d_images, long image_stride, int pitch, int nimg,
-                            hak_point* d_points, int* d_num_pts, int desc, int max_pts, hak_point* h_pinned, int cap0, int cap1);
-// h_pinned: device-visible host destination of the records (and c->h_num of the counts) written by the sequence itself, or NULL
-// max_pts: the record stride between images and their clamp; cap0 / cap1 > 0 (two images): smaller clamps per image
-static int run_detect(hak_ctx* c, const float* d_images, long image_stride, int pitch, int nimg,
-                      hak_point* d_points, int* d_num_pts, int desc, int max_pts, hak_point* h_pinned = nullptr, int cap0 = 0, int cap1 = 0)
-{
-    order_after_null_stream(c, c->stream);
-    maps_guard_begin(c);
-    return maps_guard_end(c, run_detect_inner(c, d_images, image_stride, pitch, nimg, d_points, d_num_pts, desc, max_pts, h_pinned, cap0, cap1));
-}
-static int run_detect_inner(hak_ctx* c, const float* d_images, long image_stride, int pitch, int nimg,
-                            hak_point* d_points, int* d_num_pts, int desc, int max_pts, hak_point* h_pinned, int cap0, int cap1)
-{
-    // A launch-bound sequence (single images: the spine order of enqueue_detect) is issued eagerly: with ~50 launches on four
-    // streams the host keeps ahead of the GPU, and the graph replay of ROCm 7.2 submits queue by queue in an order of its own
-    // (measured on the C++ demo, ms per 1080p pair: eager 1.18, replay 1.31; HAK_GRAPH=2 forces the replay).
-    const bool launch_bound = c->concurrent && c->L.noct > 1 && spine_pays(c, nimg);
-    if (!c->use_graph || c->prof_on || (launch_bound && c->knobs.graph != 2))
-        return enqueue_detect(c, d_images, image_stride, pitch, nimg, d_points, d_num_pts, desc, max_pts, h_pinned, cap0, cap1);
-    hak_ctx::GraphKey key;
-    memset(&key, 0, sizeof(key));
-    key.img = d_images; key.stride = image_stride; key.pitch = pitch; key.nimg = nimg; key.pts = d_points;
-    key.num = d_num_pts; key.desc = desc; key.max_pts = max_pts; key.conc = c->concurrent ? 1 : 0; key.st = c->stream; key.hpts = h_pinned; key.cap0 = cap0; key.cap1 = cap1;
-    key.retain = c->retain_best ? 1 : 0;
-    int slot = -1, victim = 0;
-    for (int i = 0; i < hak_ctx::NGRAPH; i++) {
-        if (c->graph_exec[i] && memcmp(&key, &c->gkey[i], sizeof(key)) == 0) slot = i;
-        if (c->graph_age[i] < c->graph_age[victim]) victim = i;
-    }
-    if (slot >= 0) {
-        c->graph_age[slot] = ++c->graph_clock;
-        if (hipGraphLaunch(c->graph_exec[slot], c->stream) != hipSuccess) return fail("hipGraphLaunch");
-        return 0;
-    }
-    slot = victim;                                              // least recently used (or empty) slot
-    if (c->graph_exec[slot]) { (void)hipGraphExecDestroy(c->graph_exec[slot]); c->graph_exec[slot] = nullptr; }
-    hipGraph_t graph = nullptr;
-    if (hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) {
-        (void)hipGetLastError();
-        c->use_graph = false;                                   // e.g. legacy default stream: fall back to eager launches
-        return enqueue_detect(c, d_images, image_stride, pitch, nimg, d_points, d_num_pts, desc, max_pts, h_pinned, cap0, cap1);
-    }
-    const int rc = enqueue_detect(c, d_images, image_stride, pitch, nimg, d_points, d_num_pts, desc, max_pts, h_pinned, cap0, cap1);
-    const hipError_t e = hipStreamEndCapture(c->stream, &graph);
-    if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-    if (e != hipSuccess || !graph) return fail(std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
-    const hipError_t ei = hipGraphInstantiate(&c->graph_exec[slot], graph, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(graph);
-    if (ei != hipSuccess) { c->graph_exec[slot] = nullptr; return fail(std::string("hipGraphInstantiate: ") + hipGetErrorString(ei)); }
-    c->gkey[slot] = key;
-    c->graph_age[slot] = ++c->graph_clock;
-    if (hipGraphLaunch(c->graph_exec[slot], c->stream) != hipSuccess) return fail("hipGraphLaunch");
     return 0;
 }
 
@@ -1331,10 +823,8 @@ extern "C" int hak_query_traffic(const hak_ctx* c, int npts_hint, hak_traffic* o
             launches += lp.nsteps ? hak_fed_groups(lp.nsteps, c->knobs.max_fuse, L.oct[o].w) : 0;
             // sublevels whose low-pass (8 B/px) + conductivity (8 B/px) run inside the first FED launch (k_fed_sf), and octave
             // heads whose decimation + low-pass (4 N_{o-1} + 8 N_o) + conductivity (8 N_o) do
-            const bool covered = lp.nsteps && hak_stream_pays(c->knobs.fuse_sf, L.oct[o].w, L.oct[o].h, c->cfg.batch) &&
-                                 c->cfg.diffusivity == HAK_PM_G2 && (L.oct[o].w & 3) == 0 && L.oct[o].w >= 16 && L.oct[o].h >= 8;
-            if (covered && s > 0) folded += 16.0 * N;
-            if (covered && c->knobs.fuse_head && s == 0 && o > 0 && !(L.oct[o - 1].w & 1) && !(L.oct[o - 1].h & 1))
+            if (s > 0 && hak_fed_sf_covers(c->knobs, c->cfg.diffusivity, L.oct[o], c->cfg.batch)) folded += 16.0 * N;
+            if (s == 0 && o > 0 && hak_fed_sf_covers(c->knobs, c->cfg.diffusivity, L.oct[o], c->cfg.batch, &L.oct[o - 1]))
                 folded += 4.0 * L.oct[o - 1].w * L.oct[o - 1].h + 16.0 * N;
             if (o == 0 && s == 0) all += 56.0 * N;                                // o0 prologue
             else if (s == 0) all += 4.0 * L.oct[o - 1].w * L.oct[o - 1].h + 8.0 * N + 8.0 * N + 24.0 * N + 4.0 * N;

@@ -116,6 +116,16 @@ struct ProfScope {
     ~ProfScope() { if (stop) (void)hipEventRecord(stop, s); }
 };
 
-// hak_api.hip: the key map must be all zero when a launch sequence starts; a failed call leaves the flag set (see there)
+// ------------------------------------------------------- the launch sequence (hak_sequence.hip)
+// the key map must be all zero when a launch sequence starts; a failed call leaves the flag set (see there)
 void maps_guard_begin(hak_ctx* c);
 int maps_guard_end(hak_ctx* c, int rc);
+// makes `st` wait for the NULL stream's work enqueued so far (hak_set_null_order); c == nullptr: nothing
+void order_after_null_stream(hak_ctx* c, hipStream_t st);
+// one float detect + describe sequence: replayed from the context's graph cache when the arguments repeat, else captured or eager
+// h_pinned: pinned host destination of records and counts (c->h_num), or NULL; max_pts: record stride between images and their clamp;
+// cap0 / cap1 > 0 (two images): smaller clamps per image
+int run_detect(hak_ctx* c, const float* d_images, long image_stride, int pitch, int nimg,
+               hak_point* d_points, int* d_num_pts, int desc, int max_pts, hak_point* h_pinned = nullptr, int cap0 = 0, int cap1 = 0);
+int enqueue_fast_detect(hak_ctx* c, const unsigned char* d_images, long image_stride, int pitch, int nimg,
+                        hak_point* d_points, int* d_num_pts, int desc, int max_pts);

@@ -294,7 +294,7 @@ void hak_launch_contrast(hipStream_t st, const float* smooth, long stride, int w
                          HakImgState* state, float per, int noct);
 void hak_launch_reset_state(hipStream_t st, HakImgState* state, int nimg);
 void hak_launch_flow(hipStream_t st, const float* src, float* dst, long stride, int w, int h, int p, int nimg,
-                     int diffusivity, const HakImgState* state, int octave, float fixed_ikc);
+                     int diffusivity, const HakImgState* state, int octave, float fixed_ikc = 0.f);
 // derivate + determinant of one level, with the level's extrema search fused in when b != nullptr
 // (kernels_hessian.hip); returns false when the caller still has to run hak_launch_extrema_level
 // The register-streaming kernels (k_hessian_stream, k_fed_sf) need a few thousand waves of >= 32 rows to fill the chip;
@@ -332,75 +332,84 @@ static inline bool hak_hessian_stream_covers(int w, int h, int step, bool lp)
 {
     return step >= 1 && step <= 4 && (w & 3) == 0 && w >= 16 && h >= 2 * step + 2 && (!lp || h >= 8);
 }
+// Launchers of both pipelines are overloaded on the element type: float (AKAZE) or int planes (FAST, 16.16 fixed point; taps as
+// (int)(tap * 65536 + 0.5f), integer thresholds), one template body next to the kernel.  fixed_ikc, lp_taps, store_smooth: float only.
 bool hak_launch_hessian_stream(hipStream_t st, const float* src, float* dxy, float* det, bool store_det, long stride,
                                int w, int h, int p, int nimg, int step, float fac1, float fac2,
                                const HakBatch* b, const HakLayout* L, const HakTables* htab, int octave, int sub, float dthreshold,
                                const float* lp_taps = nullptr);
-bool hakf_launch_hessian_stream(hipStream_t st, const int* src, int* dxy, int* det, bool store_det, long stride,
-                                int w, int h, int p, int nimg, int step, int fac1, int fac2,
-                                const HakBatch* b, const HakLayout* L, const HakTables* htab, int octave, int sub, int idthreshold);
-bool hakf_launch_hessian_level(hipStream_t st, const int* src, int* dxy, int* det, bool store_det, long stride,
-                               int w, int h, int p, int nimg, int step,
+bool hak_launch_hessian_stream(hipStream_t st, const int* src, int* dxy, int* det, bool store_det, long stride,
+                               int w, int h, int p, int nimg, int step, int fac1, int fac2,
                                const HakBatch* b, const HakLayout* L, const HakTables* htab, int octave, int sub, int idthreshold);
+// (dilation > 4: derivate + hessian, FAST: hakf_launch_hessian, fill `det`; the caller adds hak_launch_extrema_level)
 bool hak_launch_hessian_level(hipStream_t st, const float* src, float* dxy, float* det, bool store_det, long stride,
                               int w, int h, int p, int nimg, int step,
                               const HakBatch* b, const HakLayout* L, const HakTables* htab, int octave, int sub, float dthreshold,
                               const float* lp_taps = nullptr);
+bool hak_launch_hessian_level(hipStream_t st, const int* src, int* dxy, int* det, bool store_det, long stride,
+                              int w, int h, int p, int nimg, int step,
+                              const HakBatch* b, const HakLayout* L, const HakTables* htab, int octave, int sub, int idthreshold);
 // octave-0 prologue fused (kernels_base.hip): Lt(0,0) + contrast factors, sigma=1 plane never written
 // register-streaming pass A of the octave-0 prologue (kernels_base_stream.hip); false: not covered / does not pay
 bool hak_launch_base_stream(hipStream_t st, const float* img, long img_stride, int sp, float* lt, float* grad, long stride, int w, int h,
                             int p, int nimg, const float* taps1, const float* taps_base, int R, HakImgState* state, int mode);
-bool hakf_launch_base_stream(hipStream_t st, const unsigned char* img, long img_stride, int sp, int* lt, int* grad, long stride, int w,
-                             int h, int p, int nimg, const int* itaps1, const int* itaps_base, int R, HakImgState* state, int mode);
+bool hak_launch_base_stream(hipStream_t st, const unsigned char* img, long img_stride, int sp, int* lt, int* grad, long stride, int w,
+                            int h, int p, int nimg, const int* taps1, const int* taps_base, int R, HakImgState* state, int mode);
 bool hak_launch_base_level(hipStream_t st, const float* img, long img_stride, int sp, float* lt, float* grad_scratch, long stride,
                            int w, int h, int p, int nimg, const float* taps1, const float* taps_base, int R,
                            HakImgState* state, float per, int noct, const HakKnobs& knobs);
+// FAST (kernels_fast.hip): img is uint8; false: R not covered (caller: hakf_launch_conv_u8 x2 + hak_launch_contrast)
+bool hak_launch_base_level(hipStream_t st, const unsigned char* img, long img_stride, int sp, int* lt, int* grad_scratch, long stride,
+                           int w, int h, int p, int nimg, const int* taps1, const int* taps_base, int R, HakImgState* state,
+                           float per, int noct, const HakKnobs& knobs);
 // sigma=1 low-pass + conductivity fused (kernels_smoothflow.hip)
-void hakf_launch_smooth_flow(hipStream_t st, const int* src, int* smooth, int* flow, long stride,
-                             int w, int h, int p, int nimg, const int* itaps, int diffusivity,
-                             const HakImgState* state, int octave);
 void hak_launch_smooth_flow(hipStream_t st, const float* src, float* smooth, float* flow, long stride,
                             int w, int h, int p, int nimg, const float* taps, int diffusivity,
-                            const HakImgState* state, int octave, float fixed_ikc);
+                            const HakImgState* state, int octave, float fixed_ikc = 0.f);
+void hak_launch_smooth_flow(hipStream_t st, const int* src, int* smooth, int* flow, long stride,
+                            int w, int h, int p, int nimg, const int* taps, int diffusivity,
+                            const HakImgState* state, int octave);
 // one whole sublevel (low-pass | decimation, conductivity, every FED step) per launch out of LDS tiles, for launches too small
 // to fill the chip (kernels_level.hip).  Returns the number of launches (1 up to 36 steps).
 #define HAK_LEVEL_TILE_MAX_PX (1920L * 1088L)      // by-size rule: at most one 1080p plane's worth of pixels per launch
 // dxy / step / b / L / htab / sub / threshold: the level's Hessian inside the same launch where the cycle is long enough
 // (first launch has >= 2 * step steps); *hess_done tells the caller whether it still has to launch the Hessian kernel
-struct HakBatch;
 int hak_launch_level_tile(hipStream_t st, const float* src, HakOct so, bool head, float* smooth, float* dst, float* tmp, long stride,
                           HakOct dd, int nimg, const float* taps, int diffusivity, const float* tau, int n,
-                          const HakImgState* state, int octave, float fixed_ikc,
-                          float* dxy = nullptr, int step = 0, const HakBatch* b = nullptr, const HakLayout* L = nullptr,
-                          const HakTables* htab = nullptr, int sub = 0, float dthreshold = 0.f, bool* hess_done = nullptr);
-int hakf_launch_level_tile(hipStream_t st, const int* src, HakOct so, bool head, int* smooth, int* dst, int* tmp, long stride,
-                           HakOct dd, int nimg, const int* itaps, int diffusivity, const float* tau, int n,
-                           const HakImgState* state, int octave,
-                           int* dxy = nullptr, int step = 0, const HakBatch* b = nullptr, const HakLayout* L = nullptr,
-                           const HakTables* htab = nullptr, int sub = 0, int idthreshold = 0, bool* hess_done = nullptr);
-// fused FED groups (kernels_fed.hip)
-bool hakf_launch_base_level(hipStream_t st, const unsigned char* img, long img_stride, int sp, int* lt, int* grad_scratch, long stride,
-                            int w, int h, int p, int nimg, const int* itaps1, const int* itaps_base, int R, HakImgState* state,
-                            float per, int noct, const HakKnobs& knobs);
+                          const HakImgState* state, int octave, float* dxy = nullptr, int step = 0, const HakBatch* b = nullptr,
+                          const HakLayout* L = nullptr, const HakTables* htab = nullptr, int sub = 0, float dthreshold = 0.f,
+                          bool* hess_done = nullptr, float fixed_ikc = 0.f);
+int hak_launch_level_tile(hipStream_t st, const int* src, HakOct so, bool head, int* smooth, int* dst, int* tmp, long stride,
+                          HakOct dd, int nimg, const int* taps, int diffusivity, const float* tau, int n,
+                          const HakImgState* state, int octave, int* dxy = nullptr, int step = 0, const HakBatch* b = nullptr,
+                          const HakLayout* L = nullptr, const HakTables* htab = nullptr, int sub = 0, int idthreshold = 0, bool* hess_done = nullptr);
 int hak_launch_rcp_check(unsigned lo, unsigned hi, unsigned long long* d_bad);
+// the levels whose first FED launch is k_fed_sf: low-pass + conductivity + first FED group in one streaming pass (PM_G2, 16-byte rows);
+// so = geometry of Lt(o-1,0): an octave head, decimation included (even source extents).  The launchers keep their own guards.
+static inline bool hak_fed_sf_covers(const HakKnobs& kn, int diffusivity, const HakOct& dd, int nimg, const HakOct* so = nullptr)
+{
+    if (!hak_stream_pays(kn.fuse_sf, dd.w, dd.h, nimg) || diffusivity != HAK_PM_G2 || (dd.w & 3) != 0 || dd.w < 16 || dd.h < 8) return false;
+    return !so || (kn.fuse_head && !(so->w & 1) && !(so->h & 1));
+}
 bool hak_launch_fed_sf_head(hipStream_t st, const float* src, HakOct so, float* smooth, float* flow, float* dst, long stride,
                             HakOct dd, int nimg, const float* taps, int diffusivity, const float* tau, int ns,
                             const HakImgState* state, int octave, bool write_g);
-bool hakf_launch_fed_sf_head(hipStream_t st, const int* src, HakOct so, int* smooth, int* flow, int* dst, long stride,
-                             HakOct dd, int nimg, const int* itaps, int diffusivity, const float* tau, int ns,
-                             const HakImgState* state, int octave, bool write_g);
-bool hakf_launch_fed_sf(hipStream_t st, const int* src, int* smooth, int* flow, int* dst, long stride,
-                        int w, int h, int p, int nimg, const int* itaps, int diffusivity, const float* tau, int ns,
-                        const HakImgState* state, int octave, bool write_g);
+bool hak_launch_fed_sf_head(hipStream_t st, const int* src, HakOct so, int* smooth, int* flow, int* dst, long stride,
+                            HakOct dd, int nimg, const int* taps, int diffusivity, const float* tau, int ns,
+                            const HakImgState* state, int octave, bool write_g);
 // store_smooth = false: the low-pass is not written (its only reader, the level's Hessian, runs in the LP variant)
 bool hak_launch_fed_sf(hipStream_t st, const float* src, float* smooth, float* flow, float* dst, long stride,
                        int w, int h, int p, int nimg, const float* taps, int diffusivity, const float* tau, int ns,
-                       const HakImgState* state, int octave, float fixed_ikc, bool write_g, bool store_smooth = true);
-void hakf_launch_fed_group(hipStream_t st, const int* src, const int* flow, int* dst, long stride,
-                           int w, int h, int p, int nimg, const float* tau, int ns);
+                       const HakImgState* state, int octave, bool write_g, bool store_smooth = true, float fixed_ikc = 0.f);
+bool hak_launch_fed_sf(hipStream_t st, const int* src, int* smooth, int* flow, int* dst, long stride,
+                       int w, int h, int p, int nimg, const int* taps, int diffusivity, const float* tau, int ns,
+                       const HakImgState* state, int octave, bool write_g);
+// fused FED groups (kernels_fed.hip); w % 4 != 0: one step (tau[0]) per launch, k_fed_generic / kf_nld_step
 int hak_fed_groups(int n, int max_fuse, int w);
 int hak_fed_group_size(int n, int G, int g);
 void hak_launch_fed_group(hipStream_t st, const float* src, const float* flow, float* dst, long stride,
+                          int w, int h, int p, int nimg, const float* tau, int ns);
+void hak_launch_fed_group(hipStream_t st, const int* src, const int* flow, int* dst, long stride,
                           int w, int h, int p, int nimg, const float* tau, int ns);
 void hak_launch_derivate(hipStream_t st, const float* src, float* dxy, long stride,
                          int w, int h, int p, int nimg, int step);
@@ -428,22 +437,25 @@ void hak_launch_clear_maps(hipStream_t st, const HakBatch& b, const HakLayout& L
 void hak_launch_select(hipStream_t st, const HakBatch& b, const HakLayout& L, int max_pts, int cap0, int cap1, int fast);
 void hak_launch_seed_maps(hipStream_t st, const HakBatch& b, const HakLayout& L, const unsigned* d_resp_bits, const int* d_layer);
 
-// integer FAST path (kernels_fast.hip); planes are int32 in the same arena layout
+// integer FAST path (kernels_fast.hip); planes are int32 in the same arena layout.  Overloads of the launchers above ...
+void hak_launch_down_smooth(hipStream_t st, const int* src, int* dst, int* smooth, long stride, HakOct so, HakOct dd, int nimg,
+                            const int* taps);
+void hak_launch_contrast(hipStream_t st, const int* smooth, long stride, int w, int h, int p, int nimg, HakImgState* state,
+                         float per, int noct);
+void hak_launch_flow(hipStream_t st, const int* src, int* dst, long stride, int w, int h, int p, int nimg, int type,
+                     const HakImgState* state, int octave);
+// (no plane pointer ties this call to a pipeline: the TYPE of `threshold` alone selects kf_extrema on int32 planes -- pass a typed
+// variable, never a literal)
+void hak_launch_extrema_level(hipStream_t st, const HakBatch& b, const HakLayout& L, const HakTables* tab, int octave, int s, int threshold,
+                              long det_off);
+// ... and what has no float counterpart, or one with the same parameter types (reset, describe)
 void hakf_launch_reset(hipStream_t st, HakImgState* state, int nimg);
 void hakf_launch_conv_u8(hipStream_t st, const unsigned char* src, long src_stride, int sp, int* dst, long dst_stride,
                          int w, int h, int p, int nimg, const int* taps, int R);
 void hakf_launch_conv_int(hipStream_t st, const int* src, int* dst, long stride, int w, int h, int p, int nimg, const int* taps, int R);
-void hakf_launch_down_smooth(hipStream_t st, const int* src, int* dst, int* smooth, long stride, HakOct so, HakOct dd, int nimg,
-                             const int* taps);
-void hakf_launch_contrast(hipStream_t st, const int* smooth, long stride, int w, int h, int p, int nimg, HakImgState* state,
-                          float per, int noct);
-void hakf_launch_flow(hipStream_t st, const int* src, int* dst, long stride, int w, int h, int p, int nimg, int type,
-                      const HakImgState* state, int octave);
 void hakf_launch_nld_step(hipStream_t st, const int* src, const int* flow, int* dst, long stride, int w, int h, int p, int nimg, float tau);
-void hakf_launch_hessian(hipStream_t st, const int* src, int* dxy, int* det, long stride, int w, int h, int p, int nimg, int step);
+void hakf_launch_hessian(hipStream_t st, const int* src, int* dxy, int* det, long stride, int w, int h, int p, int nimg, int step);   // src -> dxy and det
 void hakf_launch_det(hipStream_t st, const int* dxy, int* det, long stride, int w, int h, int p, int nimg, int step);
-void hakf_launch_extrema(hipStream_t st, const HakBatch& b, const HakLayout& L, const HakTables* tab, int octave, int s, int threshold,
-                         long det_off);
 void hakf_launch_describe(hipStream_t st, const HakBatch& b, const HakLayout& L, const HakTables* tab, hak_point* points, int max_pts,
                           int patsize, int upright, int desc, int planned);
 
@@ -497,5 +509,5 @@ void hak_launch_homography(hipStream_t st, const hak_match_pair* matches, long s
                            hak_homography* out, unsigned char* masks, long mask_stride);
 
 // A launcher that cannot do what it was asked (a precondition its caller should have checked) records the reason here instead
-// of aborting; enqueue_detect turns it into the call's error (hak_api.hip).  Thread-local, like hak_last_error().
+// of aborting; enqueue_detect turns it into the call's error (hak_sequence.hip).  Thread-local, like hak_last_error().
 void hak_note_launch_error(const char* msg);

@@ -36,7 +36,7 @@ struct HakKnobs {
     int hess_side = 0;            // HAK_HESS_SIDE=1: octave 0's Hessians on a stream of their own for launches in the tile-kernel regime.  Off by
                                   // default: measured SLOWER (pair call 0.62 vs 0.57 ms) -- a fifth concurrent chain stretches the other four
                                   // more than the shorter chain gains
-    int spine_max_px = 0;         // HAK_SPINE_MAX_PX > 0: spine order for launches of at most this many octave-0 pixels (hak_api.hip, spine_pays)
+    int spine_max_px = 0;         // HAK_SPINE_MAX_PX > 0: spine order for launches of at most this many octave-0 pixels (hak_sequence.hip, spine_pays)
     int side_streams = HAK_MAX_OCTAVES;   // HAK_SIDE_STREAMS: side streams of the spine order (>= 1; more than there are octaves: one each)
     int graph_pads = 1;           // HAK_GRAPH_PADS=0: no empty nodes that steer the captured spine's side chains to queues of their own
     int tail_fork = 1;            // HAK_TAIL_FORK=0: the map clean-up of a spine sequence in front of the descriptor kernels, not beside them

@@ -428,8 +428,8 @@ bool hak_launch_base_stream(hipStream_t st, const float* img, long img_stride, i
 {
     return launch_base_stream<float>(st, img, img_stride, sp, lt, grad, stride, w, h, p, nimg, taps1, taps_base, R, state, mode);
 }
-bool hakf_launch_base_stream(hipStream_t st, const unsigned char* img, long img_stride, int sp, int* lt, int* grad, long stride, int w,
-                             int h, int p, int nimg, const int* itaps1, const int* itaps_base, int R, HakImgState* state, int mode)
+bool hak_launch_base_stream(hipStream_t st, const unsigned char* img, long img_stride, int sp, int* lt, int* grad, long stride, int w,
+                            int h, int p, int nimg, const int* taps1, const int* taps_base, int R, HakImgState* state, int mode)
 {
-    return launch_base_stream<int>(st, img, img_stride, sp, lt, grad, stride, w, h, p, nimg, itaps1, itaps_base, R, state, mode);
+    return launch_base_stream<int>(st, img, img_stride, sp, lt, grad, stride, w, h, p, nimg, taps1, taps_base, R, state, mode);
 }

@@ -102,8 +102,8 @@ __global__ __launch_bounds__(256) void kf_down_smooth(const int* __restrict__ sr
                      wmul(t.k[2], rowp[rr][c] + rowp[rr + 4][c])) >> 16;
     }
 }
-void hakf_launch_down_smooth(hipStream_t st, const int* src, int* dst, int* smooth, long stride, HakOct so, HakOct dd, int nimg,
-                             const int* taps)
+void hak_launch_down_smooth(hipStream_t st, const int* src, int* dst, int* smooth, long stride, HakOct so, HakOct dd, int nimg,
+                            const int* taps)
 {
     FkTaps t;
     for (int i = 0; i < 8; i++) t.k[i] = i <= 2 ? taps[i] : 0;
@@ -183,8 +183,8 @@ __global__ void kf_kcontrast(HakImgState* state, int npix, int extra0, float per
         st->ikc[o] = 1.f / (kc * kc);                                                            // akazed.cu:4215
     }
 }
-void hakf_launch_contrast(hipStream_t st, const int* smooth, long stride, int w, int h, int p, int nimg, HakImgState* state,
-                          float per, int noct)
+void hak_launch_contrast(hipStream_t st, const int* smooth, long stride, int w, int h, int p, int nimg, HakImgState* state,
+                         float per, int noct)
 {
     dim3 grid((w + FT_X - 1) / FT_X, (h + FT_Y - 1) / FT_Y, nimg);
     kf_grad_max<<<grid, 256, 0, st>>>(smooth, stride, w, h, p, state);
@@ -297,22 +297,22 @@ __global__ __launch_bounds__(256) void kf_grad_hist_plane(const int* __restrict_
 }
 
 // img (uint8) -> Lt(0,0), contrast factors; `grad_scratch` = a free int32 plane of the arena.  false: R not covered
-// (caller: hakf_launch_conv_u8 x2 + hakf_launch_contrast)
-bool hakf_launch_base_level(hipStream_t st, const unsigned char* img, long img_stride, int sp, int* lt, int* grad_scratch, long stride,
-                            int w, int h, int p, int nimg, const int* itaps1, const int* itaps_base, int R, HakImgState* state,
-                            float per, int noct, const HakKnobs& knobs)
+// (caller: hakf_launch_conv_u8 x2 + hak_launch_contrast)
+bool hak_launch_base_level(hipStream_t st, const unsigned char* img, long img_stride, int sp, int* lt, int* grad_scratch, long stride,
+                           int w, int h, int p, int nimg, const int* taps1, const int* taps_base, int R, HakImgState* state,
+                           float per, int noct, const HakKnobs& knobs)
 {
     if (R < 2 || R > 5) return false;
     FkTaps t1, tb;
-    for (int i = 0; i < 8; i++) { t1.k[i] = i <= 2 ? itaps1[i] : 0; tb.k[i] = i <= R ? itaps_base[i] : 0; }
+    for (int i = 0; i < 8; i++) { t1.k[i] = i <= 2 ? taps1[i] : 0; tb.k[i] = i <= R ? taps_base[i] : 0; }
     const int nbx = (w + FB_TX - 1) / FB_TX, nby = (h + FB_TY - 1) / FB_TY;
     const unsigned grid = hak_xcd_grid(nbx, nby, nimg);
     // the streaming form with the histogram inside (round 5): contrast maximum first, from the lattice points alone, then ONE pass
-    if (knobs.base_hist && hakf_launch_base_stream(st, img, img_stride, sp, lt, nullptr, stride, w, h, p, nimg, itaps1, itaps_base, R, state, knobs.base_stream)) {
+    if (knobs.base_hist && hak_launch_base_stream(st, img, img_stride, sp, lt, nullptr, stride, w, h, p, nimg, taps1, taps_base, R, state, knobs.base_stream)) {
         kf_kcontrast<<<nimg, 64, 0, st>>>(state, w * h, hak_hist_extra0(w, h), per, noct);
         return true;
     }
-    if (hakf_launch_base_stream(st, img, img_stride, sp, lt, grad_scratch, stride, w, h, p, nimg, itaps1, itaps_base, R, state, knobs.base_stream)) {
+    if (hak_launch_base_stream(st, img, img_stride, sp, lt, grad_scratch, stride, w, h, p, nimg, taps1, taps_base, R, state, knobs.base_stream)) {
         // pass A done by the streaming kernel
     } else
     switch (R) {
@@ -351,8 +351,8 @@ __global__ __launch_bounds__(256) void kf_flow(const int* __restrict__ src, int*
         d[(long)y * p + x] = (int)(g * 65536 + 0.5f);
     }
 }
-void hakf_launch_flow(hipStream_t st, const int* src, int* dst, long stride, int w, int h, int p, int nimg, int type,
-                      const HakImgState* state, int octave)
+void hak_launch_flow(hipStream_t st, const int* src, int* dst, long stride, int w, int h, int p, int nimg, int type,
+                     const HakImgState* state, int octave)
 {
     dim3 grid((w + FT_X - 1) / FT_X, (h + FT_Y - 1) / FT_Y, nimg);
     kf_flow<<<grid, 256, 0, st>>>(src, dst, stride, w, h, p, type, state, octave);
@@ -473,8 +473,8 @@ __global__ __launch_bounds__(256) void kf_extrema(const int* __restrict__ base, 
         }
     }
 }
-void hakf_launch_extrema(hipStream_t st, const HakBatch& b, const HakLayout& L, const HakTables* tab, int octave, int s, int threshold,
-                         long det_off)
+void hak_launch_extrema_level(hipStream_t st, const HakBatch& b, const HakLayout& L, const HakTables* tab, int octave, int s, int threshold,
+                              long det_off)
 {
     const HakOct oc = L.oct[octave];
     dim3 grid((oc.w + 63) / 64, (oc.h + 15) / 16, b.nimg);

@@ -256,35 +256,34 @@ int hak_fed_group_size(int n, int G, int g)
     return ns;
 }
 
-// ns fused steps src -> dst (dst != src), tau[0..ns); ns must be 1 when w % 4 != 0
-void hak_launch_fed_group(hipStream_t st, const float* src, const float* flow, float* dst, long stride,
-                          int w, int h, int p, int nimg, const float* tau, int ns)
+// ns fused steps src -> dst (dst != src), tau[0..ns); ns must be 1 when w % 4 != 0 (one step per launch: k_fed_generic, or the
+// FAST path's kf_nld_step of kernels_fast.hip).  int: fastakaze::hNldStep, akazed.cu:4231-4238, 16.16 steps
+template <typename V>
+static void launch_fed_group_t(hipStream_t st, const V* src, const V* flow, V* dst, long stride,
+                               int w, int h, int p, int nimg, const float* tau, int ns)
 {
     if (w % 4 != 0) {
-        const int gx = (w + 247) / 248;
-        int ry = 16;
-        while (ry > 2 && (long)gx * ((h + ry - 1) / ry) * nimg < 2048) ry >>= 1;
-        dim3 grid(gx, (h + 4 * ry - 1) / (4 * ry), nimg);
-        k_fed_generic<<<grid, 256, 0, st>>>(src, flow, dst, stride, w, h, p, 0.5f * tau[0], ry);
+        if constexpr (std::is_same<V, int>::value) hakf_launch_nld_step(st, src, flow, dst, stride, w, h, p, nimg, tau[0]);
+        else {
+            const int gx = (w + 247) / 248;
+            int ry = 16;
+            while (ry > 2 && (long)gx * ((h + ry - 1) / ry) * nimg < 2048) ry >>= 1;
+            dim3 grid(gx, (h + 4 * ry - 1) / (4 * ry), nimg);
+            k_fed_generic<<<grid, 256, 0, st>>>(src, flow, dst, stride, w, h, p, 0.5f * tau[0], ry);
+        }
         return;
     }
     switch (ns) {
-    case 1: launch_multi<float, 1>(st, src, flow, dst, stride, w, h, p, nimg, tau); break;
-    case 2: launch_multi<float, 2>(st, src, flow, dst, stride, w, h, p, nimg, tau); break;
-    case 3: launch_multi<float, 3>(st, src, flow, dst, stride, w, h, p, nimg, tau); break;
-    default: launch_multi<float, 4>(st, src, flow, dst, stride, w, h, p, nimg, tau); break;
+    case 1: launch_multi<V, 1>(st, src, flow, dst, stride, w, h, p, nimg, tau); break;
+    case 2: launch_multi<V, 2>(st, src, flow, dst, stride, w, h, p, nimg, tau); break;
+    case 3: launch_multi<V, 3>(st, src, flow, dst, stride, w, h, p, nimg, tau); break;
+    default: launch_multi<V, 4>(st, src, flow, dst, stride, w, h, p, nimg, tau); break;
     }
 }
 
-// integer FAST path (fastakaze::hNldStep, akazed.cu:4231-4238): ns fused 16.16 steps src -> dst; requires w % 4 == 0
-// (other widths: the one-step kf_nld_step of kernels_fast.hip)
-void hakf_launch_fed_group(hipStream_t st, const int* src, const int* flow, int* dst, long stride,
-                           int w, int h, int p, int nimg, const float* tau, int ns)
-{
-    switch (ns) {
-    case 1: launch_multi<int, 1>(st, src, flow, dst, stride, w, h, p, nimg, tau); break;
-    case 2: launch_multi<int, 2>(st, src, flow, dst, stride, w, h, p, nimg, tau); break;
-    case 3: launch_multi<int, 3>(st, src, flow, dst, stride, w, h, p, nimg, tau); break;
-    default: launch_multi<int, 4>(st, src, flow, dst, stride, w, h, p, nimg, tau); break;
-    }
-}
+void hak_launch_fed_group(hipStream_t st, const float* src, const float* flow, float* dst, long stride,
+                          int w, int h, int p, int nimg, const float* tau, int ns)
+{ launch_fed_group_t<float>(st, src, flow, dst, stride, w, h, p, nimg, tau, ns); }
+void hak_launch_fed_group(hipStream_t st, const int* src, const int* flow, int* dst, long stride,
+                          int w, int h, int p, int nimg, const float* tau, int ns)
+{ launch_fed_group_t<int>(st, src, flow, dst, stride, w, h, p, nimg, tau, ns); }

@@ -359,6 +359,20 @@ __global__ __launch_bounds__(256) void k_rcp_check(unsigned lo, unsigned hi, uns
     if (n) atomicAdd(bad, n);
 }
 
+// octave head (akaze.cpp:369-392): src = Lt(o-1,0) of the previous octave (so = its geometry); smooth = G1(decimated src) with
+// the source-extent mirror of hDownWithSmooth, g = PM_G2(smooth), dst = ns FED steps of the decimated plane.  The decimated
+// plane itself is never written.  Covered for even source extents only (odd ones mirror onto source pixels that are not on
+// the decimated lattice): otherwise returns false (caller: k_down_smooth + k_flow + k_fed_multi).
+// (the FAST path's fastakaze::gDownWithSmooth, akazed.cu:3143-3205, uses the same source-extent mirror)
+template <typename V>
+bool launch_fed_sf_head_t(hipStream_t st, const V* src, HakOct so, V* smooth, V* flow, V* dst, long stride, HakOct dd, int nimg,
+                          const V* taps, int diffusivity, const float* tau, int ns, const HakImgState* state, int octave, bool write_g)
+{
+    if ((so.w & 1) || (so.h & 1) || so.p < 2 * 8 || dd.w != so.w / 2 || dd.h != so.h / 2) return false;
+    return launch_fs_any<V>(st, src, smooth, flow, dst, stride, dd.w, dd.h, dd.p, nimg, SfTaps<V>{taps[0], taps[1], taps[2]},
+                            diffusivity, tau, ns, state, octave, 0.f, write_g, so.p, so.h);
+}
+
 }   // namespace
 
 // number of floats with bit patterns in [lo, hi) for which hak_rcp_newton(d) differs from the IEEE quotient 1.0f / d
@@ -372,40 +386,21 @@ int hak_launch_rcp_check(unsigned lo, unsigned hi, unsigned long long* d_bad)
 // Returns false when the case is not covered (caller: hak_launch_smooth_flow + hak_launch_fed_group).
 bool hak_launch_fed_sf(hipStream_t st, const float* src, float* smooth, float* flow, float* dst, long stride,
                        int w, int h, int p, int nimg, const float* taps, int diffusivity, const float* tau, int ns,
-                       const HakImgState* state, int octave, float fixed_ikc, bool write_g, bool store_smooth)
-{
-    return launch_fs_any<float>(st, src, store_smooth ? smooth : nullptr, flow, dst, stride, w, h, p, nimg, SfTaps<float>{taps[0], taps[1], taps[2]},
-                                diffusivity, tau, ns, state, octave, fixed_ikc, write_g);
-}
+                       const HakImgState* state, int octave, bool write_g, bool store_smooth, float fixed_ikc)
+{ return launch_fs_any<float>(st, src, store_smooth ? smooth : nullptr, flow, dst, stride, w, h, p, nimg, SfTaps<float>{taps[0], taps[1], taps[2]},
+                                diffusivity, tau, ns, state, octave, fixed_ikc, write_g); }
+// the integer FAST path's sublevel head (akaze.cpp:664-695): taps = (int)(tap * 65536 + 0.5f)
+bool hak_launch_fed_sf(hipStream_t st, const int* src, int* smooth, int* flow, int* dst, long stride,
+                       int w, int h, int p, int nimg, const int* taps, int diffusivity, const float* tau, int ns,
+                       const HakImgState* state, int octave, bool write_g)
+{ return launch_fs_any<int>(st, src, smooth, flow, dst, stride, w, h, p, nimg, SfTaps<int>{taps[0], taps[1], taps[2]},
+                              diffusivity, tau, ns, state, octave, 0.f, write_g); }
 
-// the integer FAST path's sublevel head (akaze.cpp:664-695): itaps = (int)(tap * 65536 + 0.5f)
-bool hakf_launch_fed_sf(hipStream_t st, const int* src, int* smooth, int* flow, int* dst, long stride,
-                        int w, int h, int p, int nimg, const int* itaps, int diffusivity, const float* tau, int ns,
-                        const HakImgState* state, int octave, bool write_g)
-{
-    return launch_fs_any<int>(st, src, smooth, flow, dst, stride, w, h, p, nimg, SfTaps<int>{itaps[0], itaps[1], itaps[2]},
-                              diffusivity, tau, ns, state, octave, 0.f, write_g);
-}
-
-// octave head (akaze.cpp:369-392): src = Lt(o-1,0) of the previous octave (so = its geometry); smooth = G1(decimated src) with
-// the source-extent mirror of hDownWithSmooth, g = PM_G2(smooth), dst = ns FED steps of the decimated plane.  The decimated
-// plane itself is never written.  Covered for even source extents only (odd ones mirror onto source pixels that are not on
-// the decimated lattice): otherwise returns false (caller: k_down_smooth + k_flow + k_fed_multi).
 bool hak_launch_fed_sf_head(hipStream_t st, const float* src, HakOct so, float* smooth, float* flow, float* dst, long stride,
                             HakOct dd, int nimg, const float* taps, int diffusivity, const float* tau, int ns,
                             const HakImgState* state, int octave, bool write_g)
-{
-    if ((so.w & 1) || (so.h & 1) || so.p < 2 * 8 || dd.w != so.w / 2 || dd.h != so.h / 2) return false;
-    return launch_fs_any<float>(st, src, smooth, flow, dst, stride, dd.w, dd.h, dd.p, nimg, SfTaps<float>{taps[0], taps[1], taps[2]},
-                                diffusivity, tau, ns, state, octave, 0.f, write_g, so.p, so.h);
-}
-
-// the FAST path's octave head (fastakaze::gDownWithSmooth akazed.cu:3143-3205 uses the same source-extent mirror)
-bool hakf_launch_fed_sf_head(hipStream_t st, const int* src, HakOct so, int* smooth, int* flow, int* dst, long stride,
-                             HakOct dd, int nimg, const int* itaps, int diffusivity, const float* tau, int ns,
-                             const HakImgState* state, int octave, bool write_g)
-{
-    if ((so.w & 1) || (so.h & 1) || so.p < 2 * 8 || dd.w != so.w / 2 || dd.h != so.h / 2) return false;
-    return launch_fs_any<int>(st, src, smooth, flow, dst, stride, dd.w, dd.h, dd.p, nimg, SfTaps<int>{itaps[0], itaps[1], itaps[2]},
-                              diffusivity, tau, ns, state, octave, 0.f, write_g, so.p, so.h);
-}
+{ return launch_fed_sf_head_t<float>(st, src, so, smooth, flow, dst, stride, dd, nimg, taps, diffusivity, tau, ns, state, octave, write_g); }
+bool hak_launch_fed_sf_head(hipStream_t st, const int* src, HakOct so, int* smooth, int* flow, int* dst, long stride,
+                            HakOct dd, int nimg, const int* taps, int diffusivity, const float* tau, int ns,
+                            const HakImgState* state, int octave, bool write_g)
+{ return launch_fed_sf_head_t<int>(st, src, so, smooth, flow, dst, stride, dd, nimg, taps, diffusivity, tau, ns, state, octave, write_g); }

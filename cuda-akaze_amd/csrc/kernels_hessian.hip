@@ -367,19 +367,26 @@ static HakExtremaArgs<V> extrema_args(const HakBatch* b, const HakLayout* L, con
 // derivate + determinant (+ extrema when b != nullptr) of one level.  Returns true when the
 // extrema were handled here; false means the caller must run the stand-alone extrema kernel on `det`.
 // The fused kernels write `det` only when store_det is set; the dilation > 4 fallback always fills it.
-bool hak_launch_hessian_level(hipStream_t st, const float* src, float* dxy, float* det, bool store_det, long stride,
-                              int w, int h, int p, int nimg, int step,
-                              const HakBatch* b, const HakLayout* L, const HakTables* htab, int octave, int sub, float dthreshold,
-                              const float* lp_taps)
+template <typename V>
+static bool launch_hessian_level_t(hipStream_t st, const V* src, V* dxy, V* det, bool store_det, long stride,
+                                   int w, int h, int p, int nimg, int step,
+                                   const HakBatch* b, const HakLayout* L, const HakTables* htab, int octave, int sub, V threshold,
+                                   const V* lp_taps)
 {
+    constexpr bool fast = std::is_same<V, int>::value;
     // register-streaming kernel (kernels_hessian_stream.hip) when it covers the case; HAK_HESS_STREAM=0 forces the tile kernel
     const HakKnobs kn = hak_knobs_of(b);
     if (lp_taps || hak_stream_pays(kn.hess_stream, w, h, nimg)) {
         float f1, f2;
         deriv_factors(f1, f2);
-        if (hak_launch_hessian_stream(st, src, dxy, det, store_det, stride, w, h, p, nimg, step, f1, f2, b, L, htab, octave, sub, dthreshold,
-                                      lp_taps))
-            return true;
+        bool streamed;
+        if constexpr (fast)                                                     // akazed.cu:4183-4184; no LP variant
+            streamed = hak_launch_hessian_stream(st, src, dxy, det, store_det, stride, w, h, p, nimg, step, (int)(f1 * 65536 + 0.5f),
+                                                 (int)(f2 * 65536 + 0.5f), b, L, htab, octave, sub, threshold);
+        else
+            streamed = hak_launch_hessian_stream(st, src, dxy, det, store_det, stride, w, h, p, nimg, step, f1, f2, b, L, htab, octave, sub,
+                                                 threshold, lp_taps);
+        if (streamed) return true;
     }
     if (lp_taps) {
         // the caller asked hak_hessian_stream_covers first, so this is not reached; should the two predicates ever drift apart the
@@ -387,41 +394,33 @@ bool hak_launch_hessian_level(hipStream_t st, const float* src, float* dxy, floa
         hak_note_launch_error("LP Hessian requested for a level the streaming kernel does not cover");
         return true;
     }
-    const HakExtremaArgs<float> ex = extrema_args<float>(b, L, htab, octave, sub, dthreshold);
-    float* od = store_det ? det : nullptr;
+    const HakExtremaArgs<V> ex = extrema_args<V>(b, L, htab, octave, sub, threshold);
+    V* od = store_det ? det : nullptr;
     switch (step) {
-    case 1: launch_fused<float, 1>(st, src, dxy, od, stride, w, h, p, nimg, ex, kn.hess_cbuf); return true;
-    case 2: launch_fused<float, 2>(st, src, dxy, od, stride, w, h, p, nimg, ex, kn.hess_cbuf); return true;
-    case 3: launch_fused<float, 3>(st, src, dxy, od, stride, w, h, p, nimg, ex, kn.hess_cbuf); return true;
-    case 4: launch_fused<float, 4>(st, src, dxy, od, stride, w, h, p, nimg, ex, kn.hess_cbuf); return true;
+    case 1: launch_fused<V, 1>(st, src, dxy, od, stride, w, h, p, nimg, ex, kn.hess_cbuf); return true;
+    case 2: launch_fused<V, 2>(st, src, dxy, od, stride, w, h, p, nimg, ex, kn.hess_cbuf); return true;
+    case 3: launch_fused<V, 3>(st, src, dxy, od, stride, w, h, p, nimg, ex, kn.hess_cbuf); return true;
+    case 4: launch_fused<V, 4>(st, src, dxy, od, stride, w, h, p, nimg, ex, kn.hess_cbuf); return true;
     default: break;
     }
-    hak_launch_derivate(st, src, dxy, stride, w, h, p, nimg, step);        // dilation > 4: two direct passes
-    hak_launch_hessian(st, dxy, det, stride, w, h, p, nimg, step);
+    // dilation > 4: direct passes, the determinant goes to `det`
+    if constexpr (fast) hakf_launch_hessian(st, src, dxy, det, stride, w, h, p, nimg, step);        // kf_derivate + kf_hessian
+    else {
+        hak_launch_derivate(st, src, dxy, stride, w, h, p, nimg, step);
+        hak_launch_hessian(st, dxy, det, stride, w, h, p, nimg, step);
+    }
     return false;
 }
 
+bool hak_launch_hessian_level(hipStream_t st, const float* src, float* dxy, float* det, bool store_det, long stride,
+                              int w, int h, int p, int nimg, int step,
+                              const HakBatch* b, const HakLayout* L, const HakTables* htab, int octave, int sub, float dthreshold,
+                              const float* lp_taps)
+{ return launch_hessian_level_t<float>(st, src, dxy, det, store_det, stride, w, h, p, nimg, step, b, L, htab, octave, sub, dthreshold, lp_taps); }
+
 // the integer FAST path's level (fastakaze::hHessianDeterminant + hCalcExtremaMap, akazed.cu:4175-4195, 4260-4285):
-// same kernel on int32 planes.  Returns false for dilation > 4 (caller: kf_derivate / kf_hessian / kf_extrema).
-bool hakf_launch_hessian_level(hipStream_t st, const int* src, int* dxy, int* det, bool store_det, long stride,
-                               int w, int h, int p, int nimg, int step,
-                               const HakBatch* b, const HakLayout* L, const HakTables* htab, int octave, int sub, int idthreshold)
-{
-    const HakKnobs kn = hak_knobs_of(b);
-    if (hak_stream_pays(kn.hess_stream, w, h, nimg)) {
-        float f1, f2;
-        deriv_factors(f1, f2);
-        if (hakf_launch_hessian_stream(st, src, dxy, det, store_det, stride, w, h, p, nimg, step, (int)(f1 * 65536 + 0.5f),
-                                       (int)(f2 * 65536 + 0.5f), b, L, htab, octave, sub, idthreshold))
-            return true;
-    }
-    const HakExtremaArgs<int> ex = extrema_args<int>(b, L, htab, octave, sub, idthreshold);
-    int* od = store_det ? det : nullptr;
-    switch (step) {
-    case 1: launch_fused<int, 1>(st, src, dxy, od, stride, w, h, p, nimg, ex, kn.hess_cbuf); return true;
-    case 2: launch_fused<int, 2>(st, src, dxy, od, stride, w, h, p, nimg, ex, kn.hess_cbuf); return true;
-    case 3: launch_fused<int, 3>(st, src, dxy, od, stride, w, h, p, nimg, ex, kn.hess_cbuf); return true;
-    case 4: launch_fused<int, 4>(st, src, dxy, od, stride, w, h, p, nimg, ex, kn.hess_cbuf); return true;
-    default: return false;
-    }
-}
+// same kernels on int32 planes
+bool hak_launch_hessian_level(hipStream_t st, const int* src, int* dxy, int* det, bool store_det, long stride,
+                              int w, int h, int p, int nimg, int step,
+                              const HakBatch* b, const HakLayout* L, const HakTables* htab, int octave, int sub, int idthreshold)
+{ return launch_hessian_level_t<int>(st, src, dxy, det, store_det, stride, w, h, p, nimg, step, b, L, htab, octave, sub, idthreshold, nullptr); }

@@ -562,9 +562,9 @@ bool hak_launch_hessian_stream(hipStream_t st, const float* src, float* dxy, flo
                                     lp_taps ? &kk : nullptr);
 }
 
-bool hakf_launch_hessian_stream(hipStream_t st, const int* src, int* dxy, int* det, bool store_det, long stride,
-                                int w, int h, int p, int nimg, int step, int fac1, int fac2,
-                                const HakBatch* b, const HakLayout* L, const HakTables* htab, int octave, int sub, int idthreshold)
+bool hak_launch_hessian_stream(hipStream_t st, const int* src, int* dxy, int* det, bool store_det, long stride,
+                               int w, int h, int p, int nimg, int step, int fac1, int fac2,
+                               const HakBatch* b, const HakLayout* L, const HakTables* htab, int octave, int sub, int idthreshold)
 {
     return launch_stream_any<int>(st, src, dxy, det, store_det, stride, w, h, p, nimg, step, fac1, fac2, b, L, htab, octave, sub, idthreshold,
                                   nullptr);

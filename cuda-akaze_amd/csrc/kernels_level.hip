@@ -420,6 +420,19 @@ LvHess<V> level_hess(V* dxy, int step, int first_ns, const HakBatch* b, const Ha
     return hs;
 }
 
+template <typename V>
+int launch_level_tile_t(hipStream_t st, const V* src, HakOct so, bool head, V* smooth, V* dst, V* tmp, long stride,
+                        HakOct dd, int nimg, const V* taps, int diffusivity, const float* tau, int n,
+                        const HakImgState* state, int octave, V* dxy, int step, const HakBatch* b, const HakLayout* L,
+                        const HakTables* htab, int sub, V threshold, bool* hess_done, float fixed_ikc)
+{
+    const int G = (n + LV_MAX_STEPS - 1) / LV_MAX_STEPS;
+    bool fused = false;
+    const LvHess<V> hs = level_hess<V>(dxy, step, hak_fed_group_size(n, G, 0), b, L, htab, octave, sub, threshold, &fused);
+    if (hess_done) *hess_done = fused;
+    return level_steps<V>(st, src, so, head, smooth, dst, tmp, stride, dd, nimg, taps, diffusivity, tau, n, state, octave, fixed_ikc, hs, hak_knobs_of(b).level_min_blocks);
+}
+
 } // namespace
 
 // One sublevel in ceil(n / 36) launches.  src: L(o, s-1), or (head) L(o-1, 0) with extents `so`.  dst receives L(o, s);
@@ -429,24 +442,12 @@ LvHess<V> level_hess(V* dxy, int step, int first_ns, const HakBatch* b, const Ha
 // Returns the number of launches.
 int hak_launch_level_tile(hipStream_t st, const float* src, HakOct so, bool head, float* smooth, float* dst, float* tmp, long stride,
                           HakOct dd, int nimg, const float* taps, int diffusivity, const float* tau, int n,
-                          const HakImgState* state, int octave, float fixed_ikc,
-                          float* dxy, int step, const HakBatch* b, const HakLayout* L, const HakTables* htab, int sub, float dthreshold, bool* hess_done)
-{
-    const int G = (n + LV_MAX_STEPS - 1) / LV_MAX_STEPS;
-    bool fused = false;
-    const LvHess<float> hs = level_hess<float>(dxy, step, hak_fed_group_size(n, G, 0), b, L, htab, octave, sub, dthreshold, &fused);
-    if (hess_done) *hess_done = fused;
-    return level_steps<float>(st, src, so, head, smooth, dst, tmp, stride, dd, nimg, taps, diffusivity, tau, n, state, octave, fixed_ikc, hs, hak_knobs_of(b).level_min_blocks);
-}
+                          const HakImgState* state, int octave, float* dxy, int step, const HakBatch* b, const HakLayout* L,
+                          const HakTables* htab, int sub, float dthreshold, bool* hess_done, float fixed_ikc)
+{ return launch_level_tile_t<float>(st, src, so, head, smooth, dst, tmp, stride, dd, nimg, taps, diffusivity, tau, n, state, octave, dxy, step, b, L, htab, sub, dthreshold, hess_done, fixed_ikc); }
 
-int hakf_launch_level_tile(hipStream_t st, const int* src, HakOct so, bool head, int* smooth, int* dst, int* tmp, long stride,
-                           HakOct dd, int nimg, const int* itaps, int diffusivity, const float* tau, int n,
-                           const HakImgState* state, int octave,
-                           int* dxy, int step, const HakBatch* b, const HakLayout* L, const HakTables* htab, int sub, int idthreshold, bool* hess_done)
-{
-    const int G = (n + LV_MAX_STEPS - 1) / LV_MAX_STEPS;
-    bool fused = false;
-    const LvHess<int> hs = level_hess<int>(dxy, step, hak_fed_group_size(n, G, 0), b, L, htab, octave, sub, idthreshold, &fused);
-    if (hess_done) *hess_done = fused;
-    return level_steps<int>(st, src, so, head, smooth, dst, tmp, stride, dd, nimg, itaps, diffusivity, tau, n, state, octave, 0.f, hs, hak_knobs_of(b).level_min_blocks);
-}
+int hak_launch_level_tile(hipStream_t st, const int* src, HakOct so, bool head, int* smooth, int* dst, int* tmp, long stride,
+                          HakOct dd, int nimg, const int* taps, int diffusivity, const float* tau, int n,
+                          const HakImgState* state, int octave, int* dxy, int step, const HakBatch* b, const HakLayout* L,
+                          const HakTables* htab, int sub, int idthreshold, bool* hess_done)
+{ return launch_level_tile_t<int>(st, src, so, head, smooth, dst, tmp, stride, dd, nimg, taps, diffusivity, tau, n, state, octave, dxy, step, b, L, htab, sub, idthreshold, hess_done, 0.f); }

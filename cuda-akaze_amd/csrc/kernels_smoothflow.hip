@@ -110,9 +110,10 @@ __global__ __launch_bounds__(256) void k_smooth_flow(const V* __restrict__ src, 
 }
 
 template <typename V>
-static void launch_sf(hipStream_t st, const V* src, V* smooth, V* flow, long stride, int w, int h, int p, int nimg,
-                      SfTaps<V> t, int diffusivity, const HakImgState* state, int octave, float fixed_ikc)
+static void launch_smooth_flow_t(hipStream_t st, const V* src, V* smooth, V* flow, long stride, int w, int h, int p, int nimg,
+                                 const V* taps, int diffusivity, const HakImgState* state, int octave, float fixed_ikc)
 {
+    const SfTaps<V> t{taps[0], taps[1], taps[2]};
     const int ntx = (w + SF_TX - 1) / SF_TX, nty = (h + SF_TY - 1) / SF_TY;
     int tpb = 8;
     while (tpb > 1 && (long)ntx * ((nty + tpb - 1) / tpb) * nimg < 4096) tpb >>= 1;
@@ -124,14 +125,10 @@ static void launch_sf(hipStream_t st, const V* src, V* smooth, V* flow, long str
 void hak_launch_smooth_flow(hipStream_t st, const float* src, float* smooth, float* flow, long stride,
                             int w, int h, int p, int nimg, const float* taps, int diffusivity,
                             const HakImgState* state, int octave, float fixed_ikc)
-{
-    launch_sf<float>(st, src, smooth, flow, stride, w, h, p, nimg, SfTaps<float>{taps[0], taps[1], taps[2]}, diffusivity, state, octave, fixed_ikc);
-}
+{ launch_smooth_flow_t<float>(st, src, smooth, flow, stride, w, h, p, nimg, taps, diffusivity, state, octave, fixed_ikc); }
 
-// integer FAST path: hLowPass(int, var 1) + hFlow (akaze.cpp:664-680) in one pass; itaps = (int)(tap * 65536 + 0.5f)
-void hakf_launch_smooth_flow(hipStream_t st, const int* src, int* smooth, int* flow, long stride,
-                             int w, int h, int p, int nimg, const int* itaps, int diffusivity,
-                             const HakImgState* state, int octave)
-{
-    launch_sf<int>(st, src, smooth, flow, stride, w, h, p, nimg, SfTaps<int>{itaps[0], itaps[1], itaps[2]}, diffusivity, state, octave, 0.f);
-}
+// integer FAST path: hLowPass(int, var 1) + hFlow (akaze.cpp:664-680) in one pass; taps = (int)(tap * 65536 + 0.5f)
+void hak_launch_smooth_flow(hipStream_t st, const int* src, int* smooth, int* flow, long stride,
+                            int w, int h, int p, int nimg, const int* taps, int diffusivity,
+                            const HakImgState* state, int octave)
+{ launch_smooth_flow_t<int>(st, src, smooth, flow, stride, w, h, p, nimg, taps, diffusivity, state, octave, 0.f); }

@@ -494,6 +494,57 @@ def test_strip_geometry_sweep_both_paths(ah, okz, torch, synth, w, h):
     det.close()
 
 
+@pytest.mark.parametrize("w,h", [(162, 164), (250, 170)], ids=lambda v: str(v))
+def test_odd_widths_outside_the_tile_kernel_both_paths(ah, okz, torch, synth, monkeypatch, w, h):
+    """widths with w % 4 != 0 through the STREAMING branch of the level sequence (HAK_LEVEL_TILE=0: under the default size rule a
+    single small image always takes k_level_tile, so the sweep's odd widths never get here): one FED step per launch --
+    k_fed_generic, FAST: kf_nld_step --, no k_fed_sf, and for 162 x 164 an octave 1 of odd extents (81 x 82), whose head cannot
+    take the decimating k_fed_sf either.  Every pixel of every plane and the whole records, exactly, against the oracles."""
+    monkeypatch.setenv("HAK_LEVEL_TILE", "0")
+    u8 = np.ascontiguousarray(_mg().case_scene(1280, 320, (7 * w + h) % 97)[:h, :w])
+    p = ah.iAlignUp(w, 128)
+    kw = dict(noctaves=2, max_scale=3)
+    det = ah.Akazer()
+    det.init((w, h, p), max_pts=3000, **kw)
+    assert [g[:2] for g in det.geometry()] == [(w, h), (w // 2, h // 2)]
+    data = ah.AkazeData()
+    ah.initAkazeData(data, 3000, True, True)
+
+    def check_planes(ref, as_int):
+        assert len(det.geometry()) == ref.noct
+        for o in range(ref.noct):
+            for s in range(kw["max_scale"]):
+                for kind, nm in ((0, "Lt"), (2, "Lx"), (3, "Ly"), (1, "det")):
+                    got = det.plane(kind, o, s)
+                    want = okz.plane(ref, kind, o, s)
+                    got = got.view(np.int32) if as_int else got.view(np.uint32)
+                    want = want if as_int else want.view(np.uint32)
+                    bad = np.argwhere(got != want)
+                    assert len(bad) == 0, f"{'FAST ' if as_int else ''}{nm}({o},{s}): {len(bad)} px differ, first at (y, x) = {tuple(bad[0])}"
+
+    img = torch.from_numpy(synth.to_float(u8, p)).cuda()
+    det.detectAndCompute(img.data_ptr(), data, (w, h, p), True)
+    r = okz.detect_and_compute(synth.to_float(u8, p), w, okz.default_params(**kw), max_pts=3000, keep_arena=True)
+    # the route this test exists for: the sequence counts the bytes of the FED launches it enqueued, and only one launch per step
+    # with nothing fused into it (read L and g, write L': 12 B/px) gives this sum -- k_level_tile or k_fed_sf would count otherwise
+    nsteps = det.schedule()["nsteps"].reshape(2, kw["max_scale"])
+    assert det.traffic().fed_fused_bytes == sum(12.0 * int(nsteps[o].sum()) * gw * gh for o, (gw, gh, _) in enumerate(det.geometry()))
+    check_planes(r, False)
+    assert data.num_pts == len(r.points), (data.num_pts, len(r.points))
+    if data.num_pts:
+        assert_points_equal(data.h_data[:data.num_pts], r.points)
+    pad = np.zeros((h, p), np.uint8)
+    pad[:, :w] = u8
+    det.fastDetectAndCompute(torch.from_numpy(pad).cuda().data_ptr(), data, (w, h, p), True)
+    rf = okz.fast_detect_and_compute(u8, okz.default_params(**kw), max_pts=3000, keep_arena=True)
+    check_planes(rf, True)
+    assert data.num_pts == len(rf.points), (data.num_pts, len(rf.points))
+    if data.num_pts:
+        assert_points_equal(data.h_data[:data.num_pts], rf.points)
+    ah.freeAkazeData(data)
+    det.close()
+
+
 def test_constant_image_vs_oracle_both_paths(ah, okz, torch, synth):
     """a constant image: hmax = 0, hfactor = inf, every histogram index 0 * inf = NaN -> bin 0 by the device cast (akazed.cu:924): no
     keypoints and the same contrast factor as the oracle, float and FAST; then a real image through the same context"""
