@@ -132,7 +132,7 @@ static int build_plan(hak_ctx* c, int w, int h)
     if (cfg.noctaves < 1 || cfg.noctaves > HAK_MAX_OCTAVES) return fail("noctaves out of range");
     if (cfg.max_scale < 1 || cfg.max_scale > HAK_MAX_SCALES) return fail("max_scale out of range");
     if (w < 80 || h < 80) return fail("image smaller than 80 px");
-    // candidate entries pack full-resolution coordinates as (y << 16) | x (kernels_detect.hip, kernels_hessian*.hip)
+    // candidate entries carry 16 bits per full-resolution coordinate (hak_cand_word, hak_internal.h)
     if (w > 65535 || h > 65535) return fail("image larger than 65535 px in one dimension");
     HakLayout& L = c->L;
     memset(&L, 0, sizeof(L));

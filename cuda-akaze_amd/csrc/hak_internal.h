@@ -148,6 +148,78 @@ __device__ __forceinline__ int hs_det(int dxx, int dyy, int dxy)
 }
 __device__ __forceinline__ unsigned hs_key_bits(float v) { return __float_as_uint(v); }     // positive floats order like their bits
 __device__ __forceinline__ unsigned hs_key_bits(int v) { return (unsigned)v; }              // positive ints
+__device__ __forceinline__ unsigned hs_key_bits(unsigned v) { return v; }                   // a response word as it is (k_seed_maps)
+
+// ---- the per-level extrema rule (gCalcExtremaMap akazed.cu:1334-1393, FAST 3476-3515), stated once for the five kernels that
+// apply it: k_hessian_stream, k_hessian_fused, k_level_tile and the two k_extrema<V>.  The border filter, the strict maximum,
+// the tie order of the key and the coordinate packing of the candidate word are defined here and nowhere else.
+// What a kernel needs to apply the rule to one level; filled on the host by hak_extrema_args (below HakBatch).
+template <typename V>
+struct HakExtremaArgs {
+    unsigned long long* maps;       // [nimg][map_stride]; nullptr: determinant only, no extrema
+    long map_stride;
+    unsigned long long* cand;       // [nimg][cand_cap]
+    long cand_cap;
+    HakImgState* state;
+    int p0;                         // pitch of the full-resolution map
+    int octave, layer;
+    int psz;                        // (int)borders[octave*ms]     akazed.cu:2572
+    float border;
+    V threshold;
+};
+// border filter of one axis (akazed.cu:1346-1353): coordinate i of an axis of n pixels
+__device__ __forceinline__ bool hak_ext_inside(int i, int n, int psz, float border)
+{
+    return i >= psz && i < n && (int)(i - border + 0.5f) - 1 >= 0 && (int)(i + border + 0.5f) + 1 < n;
+}
+// strict 3 x 3 maximum (akazed.cu:1361): eight ORDERED compares.  A maximum over the neighbours must never stand in for them: it
+// drops a NaN operand, while a NaN neighbour makes its compare -- and so the test -- false (NaN determinants, inf - inf, come
+// from finite images: tests/test_gpu_value_domain.py).  A maximum may pre-select (k_hessian_stream); these compares decide.
+template <typename V>
+__device__ __forceinline__ bool hak_ext_strict_max(V v, V up, V dn, V lf, V rt, V ul, V ur, V dl, V dr)
+{
+    return v > up && v > dn && v > lf && v > rt && v > ul && v > ur && v > dl && v > dr;
+}
+template <typename V>
+__device__ __forceinline__ bool hak_ext_strict_max(V v, const V* vp, int pitch)
+{
+    return hak_ext_strict_max(v, vp[-pitch], vp[pitch], vp[-1], vp[1], vp[-pitch - 1], vp[-pitch + 1], vp[pitch - 1], vp[pitch + 1]);
+}
+// key-map word: response bits << 32 | (0xFFFFFFFF - layer).  One atomicMax keeps the larger response and, on a tie, the lower
+// layer (the reference's sequential `response_map[oidx] < *vp`, akazed.cu:1368).
+template <typename V>
+__device__ __forceinline__ unsigned long long hak_ext_key(V v, int layer)
+{
+    return ((unsigned long long)hs_key_bits(v) << 32) | (0xFFFFFFFFu - (unsigned)layer);
+}
+__device__ __forceinline__ unsigned hak_key_word(unsigned long long k) { return (unsigned)(k >> 32); }       // response bits
+__device__ __forceinline__ float hak_key_resp(unsigned long long k) { return __uint_as_float(hak_key_word(k)); }
+__device__ __forceinline__ int hak_key_layer(unsigned long long k) { return (int)(0xFFFFFFFFu - (unsigned)k); }
+// candidate-list word: layer << 32 | y << 16 | x at full resolution -- 16 bits per coordinate (build_plan refuses larger images)
+__device__ __forceinline__ unsigned long long hak_cand_word(int layer, int fx, int fy)
+{
+    return ((unsigned long long)layer << 32) | ((unsigned)fy << 16) | (unsigned)fx;
+}
+__device__ __forceinline__ int hak_cand_layer(unsigned long long e) { return (int)(e >> 32); }
+__device__ __forceinline__ int hak_cand_x(unsigned long long e) { return (int)(e & 0xFFFFu); }
+__device__ __forceinline__ int hak_cand_y(unsigned long long e) { return (int)((e >> 16) & 0xFFFFu); }
+// one wave's hits of level pixels (x, y) -> the image's candidate list (one slot reservation per wave) and its key map.  Called
+// by all 64 lanes.  (k_hessian_stream and k_hessian_fused stage their candidates in LDS first, for the reasons given there.)
+template <typename V>
+__device__ __forceinline__ void hak_ext_append_wave(bool hit, V v, int x, int y, int img, int lane, const HakExtremaArgs<V>& ex)
+{
+    const unsigned long long m = __ballot(hit);
+    if (!m) return;
+    int cbase = 0;
+    if (lane == 0) cbase = atomicAdd(&ex.state[img].ncand, __popcll(m));
+    cbase = __builtin_amdgcn_readfirstlane(cbase);
+    if (hit) {
+        const int fx = x << ex.octave, fy = y << ex.octave;
+        atomicMax(&ex.maps[(long)img * ex.map_stride + (long)fy * ex.p0 + fx], hak_ext_key(v, ex.layer));
+        const long slot = cbase + __popcll(m & ((1ull << lane) - 1ull));
+        if (slot < ex.cand_cap) ex.cand[(long)img * ex.cand_cap + slot] = hak_cand_word(ex.layer, fx, fy);
+    }
+}
 
 // Hessian determinant of one level at (x, y), re-evaluated from the interleaved derivative plane with the expressions and
 // the reflect-101 index rule of the Hessian kernels (akazed.cu:1318-1330): bit-identical to the value those kernels
@@ -284,6 +356,20 @@ struct HakBatch {
 };
 // the knobs a launcher works with: the owning context's, or (no context: b == nullptr or a stage operator's batch) the environment's now
 static inline HakKnobs hak_knobs_of(const HakBatch* b) { return (b && b->knobs) ? *b->knobs : hak_knobs_from_env(); }
+// the extrema parameters of level (octave, sub) for every kernel that applies the rule; htab: the HOST copy of the tables.
+// b == nullptr: maps == nullptr, i.e. determinant only
+template <typename V>
+static inline HakExtremaArgs<V> hak_extrema_args(const HakBatch* b, const HakLayout* L, const HakTables* htab, int octave, int sub, V threshold)
+{
+    HakExtremaArgs<V> ex{};
+    if (b) {
+        const int layer = octave * L->ms + sub;
+        ex.maps = b->maps; ex.map_stride = b->map_stride; ex.cand = b->cand; ex.cand_cap = b->cand_cap;
+        ex.state = b->state; ex.p0 = L->oct[0].p; ex.octave = octave; ex.layer = layer;
+        ex.psz = (int)htab->borders[octave * L->ms]; ex.border = htab->borders[layer]; ex.threshold = threshold;
+    }
+    return ex;
+}
 
 // scale space (kernels_scalespace.hip)
 void hak_launch_lowpass(hipStream_t st, const float* src, long src_stride, int src_pitch, float* dst, long dst_stride,
@@ -423,8 +509,13 @@ void hak_launch_ingest_u8(hipStream_t st, const unsigned char* src, long src_str
                           int dp, int w, int h, int nimg);
 
 // detector tail (kernels_detect.hip)
-void hak_launch_extrema_level(hipStream_t st, const HakBatch& b, const HakLayout& L, const HakTables* tab, int octave,
+// stand-alone extrema of one level on the determinant plane at arena offset det_off (dilation > 4); htab: the host tables.
+// No plane pointer ties the call to a pipeline: the TYPE of the threshold alone selects k_extrema<float> or, on int32 planes,
+// k_extrema<int> -- pass a typed variable, never a literal
+void hak_launch_extrema_level(hipStream_t st, const HakBatch& b, const HakLayout& L, const HakTables* htab, int octave,
                               int s, float dthreshold, long det_off);
+void hak_launch_extrema_level(hipStream_t st, const HakBatch& b, const HakLayout& L, const HakTables* htab, int octave, int s, int threshold,
+                              long det_off);
 void hak_launch_download(hipStream_t st, const hak_point* d_points, const int* d_num, long max_pts, int nimg, hak_point* h_points,
                          int* h_num);
 // destinations of a pair call's records: device arrays, pinned host arrays (or NULL), capacity of each in records
@@ -444,10 +535,6 @@ void hak_launch_contrast(hipStream_t st, const int* smooth, long stride, int w, 
                          float per, int noct);
 void hak_launch_flow(hipStream_t st, const int* src, int* dst, long stride, int w, int h, int p, int nimg, int type,
                      const HakImgState* state, int octave);
-// (no plane pointer ties this call to a pipeline: the TYPE of `threshold` alone selects kf_extrema on int32 planes -- pass a typed
-// variable, never a literal)
-void hak_launch_extrema_level(hipStream_t st, const HakBatch& b, const HakLayout& L, const HakTables* tab, int octave, int s, int threshold,
-                              long det_off);
 // ... and what has no float counterpart, or one with the same parameter types (reset, describe)
 void hakf_launch_reset(hipStream_t st, HakImgState* state, int nimg);
 void hakf_launch_conv_u8(hipStream_t st, const unsigned char* src, long src_stride, int sp, int* dst, long dst_stride,

@@ -249,7 +249,7 @@ static void hessian_level(LevelArgs& a, int o, int s, hipStream_t st, const V* s
     else
         done = hak_launch_hessian_level(st, hsrc, A + L.dxy(o, s), A + L.flow_off[o], false, L.arena, oc.w, oc.h, oc.p, a.nimg, lp.sigma_size,
                                         &a.b, &L, &c->htab, o, s, thr, lph ? c->taps1 : nullptr);
-    if (!done) hak_launch_extrema_level(st, a.b, L, c->dtab, o, s, thr, L.flow_off[o]);
+    if (!done) hak_launch_extrema_level(st, a.b, L, &c->htab, o, s, thr, L.flow_off[o]);
 }
 
 static int enqueue_detect(hak_ctx* c, const float* d_images, long image_stride, int pitch, int nimg,

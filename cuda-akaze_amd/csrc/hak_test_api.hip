@@ -207,7 +207,7 @@ extern "C" int hak_op_tail_level(hak_ctx* c, int o, int s, const float* h_src)
     const int step = c->plan[(size_t)o * L.ms + s].sigma_size;
     if (!hak_launch_hessian_level(c->stream, smooth, A + L.dxy(o, s), A + L.flow_off[o], false, L.arena, oc.w, oc.h, oc.p, 1, step, &b, &L,
                                   &c->htab, o, s, c->cfg.dthreshold))
-        hak_launch_extrema_level(c->stream, b, L, c->dtab, o, s, c->cfg.dthreshold, L.flow_off[o]);
+        hak_launch_extrema_level(c->stream, b, L, &c->htab, o, s, c->cfg.dthreshold, L.flow_off[o]);
     if (hipGetLastError() != hipSuccess) return fail("tail level launch failed");
     HIP_TRY(hipStreamSynchronize(c->stream));
     return 0;
@@ -220,7 +220,7 @@ extern "C" int hak_op_tail_det_level(hak_ctx* c, int o, int s, const float* h_de
     const HakOct oc = L.oct[o];
     HIP_TRY(hipMemcpy2D(c->arena + L.flow_off[o], sizeof(float) * oc.p, h_det, sizeof(float) * oc.w, sizeof(float) * oc.w, oc.h,
                         hipMemcpyHostToDevice));
-    hak_launch_extrema_level(c->stream, tail_batch(c), L, c->dtab, o, s, c->cfg.dthreshold, L.flow_off[o]);
+    hak_launch_extrema_level(c->stream, tail_batch(c), L, &c->htab, o, s, c->cfg.dthreshold, L.flow_off[o]);
     if (hipGetLastError() != hipSuccess) return fail("extrema launch failed");
     HIP_TRY(hipStreamSynchronize(c->stream));
     return 0;

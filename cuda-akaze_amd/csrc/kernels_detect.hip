@@ -1,7 +1,7 @@
 // kernels_detect.hip -- Hessian-determinant extrema, cross-scale map, disc NMS,
 // deterministic compaction and sub-pixel refinement (gfx950, wave64).
 //
-//   hCalcExtremaMap/gCalcExtremaMap  akazed.cu:2563, 1334 -> k_extrema
+//   hCalcExtremaMap/gCalcExtremaMap  akazed.cu:2563, 1334 -> k_extrema<V> (float and FAST int planes)
 //   hNmsR/gNmsRNaive                 akazed.cu:2611, 1554 -> k_nms_mark, k_row_scan, k_emit
 //   hRefine/gRefine                  akazed.cu:2635, 1615 -> fused into k_emit
 //
@@ -12,55 +12,35 @@
 // updated with a single atomicMax: the larger response wins and, on a tie, the
 // lower layer (= the reference's sequential "strict <" order).  Survivors are
 // compacted in raster order: ballot -> bitmap + per-row counts -> scan -> emit.
+//
+// The extrema rule itself -- border filter (hak_ext_inside), strict maximum (hak_ext_strict_max), the key and its tie order
+// (hak_ext_key / hak_key_word, hak_key_resp, hak_key_layer), the candidate word and its coordinate packing (hak_cand_word /
+// hak_cand_layer, _x, _y) and the plain wave append (hak_ext_append_wave) -- is defined in hak_internal.h, for this file and
+// for the fused Hessian kernels alike.
 #include "hak_internal.h"
 
-__device__ __forceinline__ float key_resp(unsigned long long k) { return __uint_as_float((unsigned)(k >> 32)); }
-__device__ __forceinline__ int key_layer(unsigned long long k) { return (int)(0xFFFFFFFFu - (unsigned)k); }
-
 // ------------------------------------------------------------------ extrema
-// Stand-alone per-level extrema (used only when the dilation is too large for the fused
-// Hessian kernel, kernels_hessian.hip).  grid: (x tiles, y tiles, nimg)
-__global__ __launch_bounds__(256) void k_extrema(const float* __restrict__ base, long stride, unsigned long long* maps,
-                                                 long map_stride, unsigned long long* cand, long cand_cap,
-                                                 HakImgState* state, HakLayout L, const HakTables* __restrict__ tab,
-                                                 int octave, int s, float threshold, long det_off)
+// Stand-alone per-level extrema on a stored determinant plane (used only when the dilation is too large for the fused
+// Hessian kernels, kernels_hessian.hip): the rule of hak_internal.h, one wave per 64 x 1 pixels.  det: the plane of image 0.
+// grid: (x tiles, y tiles, nimg)
+template <typename V>
+__global__ __launch_bounds__(256) void k_extrema(const V* __restrict__ det, long stride, int w, int h, int p, HakExtremaArgs<V> ex)
 {
     const int img = blockIdx.z;
-    const HakOct oc = L.oct[octave];
-    const float* det = base + (long)img * stride + det_off;        // scratch plane filled by the unfused k_hessian
-    const int layer = octave * L.ms + s;
-    const float border = tab->borders[layer];
-    const int psz = (int)tab->borders[octave * L.ms];               // akazed.cu:2572
+    det += (long)img * stride;
     const int lane = threadIdx.x & 63;
     const int x = blockIdx.x * 64 + lane;
     const int y0 = blockIdx.y * 16 + (threadIdx.x >> 6);
-    // akazed.cu:1346-1353
-    const bool xok = x >= psz && x < oc.w && (int)(x - border + 0.5f) - 1 >= 0 && (int)(x + border + 0.5f) + 1 < oc.w;
+    const bool xok = hak_ext_inside(x, w, ex.psz, ex.border);
     for (int y = y0; y < blockIdx.y * 16 + 16; y += 4) {
         bool hit = false;
-        float v = 0.f;
-        if (xok && y >= psz && y < oc.h && (int)(y - border + 0.5f) - 1 >= 0 && (int)(y + border + 0.5f) + 1 < oc.h) {
-            const float* vp = det + (long)y * oc.p + x;
-            const float* vp0 = vp - oc.p;
-            const float* vp2 = vp + oc.p;
+        V v = 0;
+        if (xok && hak_ext_inside(y, h, ex.psz, ex.border)) {
+            const V* vp = det + (long)y * p + x;
             v = *vp;
-            hit = v > threshold && v > *vp0 && v > *vp2 && v > vp[-1] && v > vp[1] &&
-                  v > vp0[-1] && v > vp0[1] && v > vp2[-1] && v > vp2[1];
+            hit = v > ex.threshold && hak_ext_strict_max(v, vp, p);
         }
-        const unsigned long long m = __ballot(hit);
-        if (m) {
-            int cbase = 0;
-            if (lane == 0) cbase = atomicAdd(&state[img].ncand, __popcll(m));
-            cbase = __builtin_amdgcn_readfirstlane(cbase);
-            if (hit) {
-                const int fx = x << octave, fy = y << octave;
-                unsigned long long key = ((unsigned long long)__float_as_uint(v) << 32) | (0xFFFFFFFFu - (unsigned)layer);
-                atomicMax(&maps[(long)img * map_stride + (long)fy * L.oct[0].p + fx], key);
-                const long slot = cbase + __popcll(m & ((1ull << lane) - 1ull));
-                if (slot < cand_cap)
-                    cand[(long)img * cand_cap + slot] = ((unsigned long long)layer << 32) | ((unsigned)fy << 16) | (unsigned)fx;
-            }
-        }
+        hak_ext_append_wave(hit, v, x, y, img, lane, ex);
     }
 }
 
@@ -88,7 +68,7 @@ __global__ __launch_bounds__(256) void k_nms_cand(const unsigned long long* __re
         const long i = i0 + grp;
         bool live = i < n;
         const unsigned long long e = live ? cand[(long)img * cand_cap + i] : 0ull;
-        const int x = (int)(e & 0xFFFFu), y = (int)((e >> 16) & 0xFFFFu), layer = (int)(e >> 32);
+        const int x = hak_cand_x(e), y = hak_cand_y(e), layer = hak_cand_layer(e);
         live = live && x >= psz && x + psz < w && y >= psz && y + psz < h;
         const float fsz = live ? tab->sizes[layer] : 0.f;
         const int isz = (int)(fsz + 0.5f);
@@ -111,7 +91,7 @@ __global__ __launch_bounds__(256) void k_nms_cand(const unsigned long long* __re
                 const int col = dj - (int)(di == 0 && dj > 0);
                 rn[k] = in ? (reinterpret_cast<const unsigned*>(map + (long)(y + di) * p + x) + 1)[2 * col] : 0u;   // high words
             }
-            rc = (unsigned)(kc >> 32);              // response word: unsigned order == order of positive floats / ints
+            rc = hak_key_word(kc);                  // response word: unsigned order == order of positive floats / ints
 #pragma unroll
             for (int k = 0; k < 9; k++) {
                 const int di = k - 4;
@@ -119,7 +99,7 @@ __global__ __launch_bounds__(256) void k_nms_cand(const unsigned long long* __re
                 hit = hit || (in && (rn[k] > rc || (rn[k] == rc && di <= 0 && dj <= 0)));
             }
         } else {                                                    // any radius: row by row
-            rc = (unsigned)(kc >> 32);
+            rc = hak_key_word(kc);
             for (int di = -isz; di <= isz; di++) {
                 const unsigned* row = reinterpret_cast<const unsigned*>(map + (long)(y + di) * p + x) + 1;   // high words: row[2 * dj]
                 for (int dj = c - isz; dj <= isz; dj += 16) {
@@ -130,7 +110,7 @@ __global__ __launch_bounds__(256) void k_nms_cand(const unsigned long long* __re
                 }
             }
         }
-        live = live && key_layer(kc) == layer;                      // (else another level won this pixel)
+        live = live && hak_key_layer(kc) == layer;                      // (else another level won this pixel)
         const unsigned long long m = __ballot(hit);                 // (all lanes are back together here)
         const bool to_nms = ((m >> gsh) & 0xFFFFull) != 0ull;
         if (live && !to_nms && c == 0) {
@@ -197,14 +177,14 @@ __global__ __launch_bounds__(256) void k_emit(const float* __restrict__ base, lo
             if (idx < max_pts) {                        // (a pair call's smaller per-image clamp: the surplus records are never counted)
                 int x = (w0 + lane) * 64 + bit;
                 unsigned long long k = map[(long)y * p0 + x];
-                int layer = key_layer(k);
+                int layer = hak_key_layer(k);
                 // integer position; the sub-pixel refinement (akazed.cu:1615-1662) follows in k_refine, sixteen lanes per keypoint
                 const float px = (float)x, py = (float)y;
                 hak_point* pt = pts + idx;
                 pt->x = px;
                 pt->y = py;
                 pt->octave = layer;
-                pt->response = fast ? (float)(int)(k >> 32) : key_resp(k);   // D8
+                pt->response = fast ? (float)(int)hak_key_word(k) : hak_key_resp(k);   // D8
                 unsigned int* f32 = reinterpret_cast<unsigned int*>(pt->features);
 #pragma unroll
                 for (int q = 0; q < 16; q++) f32[q] = 0u;           // features + padding (written again by the describe kernel)
@@ -270,14 +250,22 @@ __global__ __launch_bounds__(256) void k_refine(const float* __restrict__ base, 
     }
 }
 
-void hak_launch_extrema_level(hipStream_t st, const HakBatch& b, const HakLayout& L, const HakTables* tab, int octave,
-                              int s, float dthreshold, long det_off)
+template <typename V>
+static void launch_extrema_level_t(hipStream_t st, const HakBatch& b, const HakLayout& L, const HakTables* htab, int octave, int s,
+                                   V threshold, long det_off)
 {
     const HakOct oc = L.oct[octave];
     dim3 grid((oc.w + 63) / 64, (oc.h + 15) / 16, b.nimg);
-    k_extrema<<<grid, 256, 0, st>>>(b.base, b.stride, b.maps, b.map_stride, b.cand, b.cand_cap, b.state, L, tab,
-                                    octave, s, dthreshold, det_off);
+    k_extrema<V><<<grid, 256, 0, st>>>(reinterpret_cast<const V*>(b.base) + det_off, b.stride, oc.w, oc.h, oc.p,
+                                       hak_extrema_args<V>(&b, &L, htab, octave, s, threshold));
 }
+void hak_launch_extrema_level(hipStream_t st, const HakBatch& b, const HakLayout& L, const HakTables* htab, int octave,
+                              int s, float dthreshold, long det_off)
+{ launch_extrema_level_t<float>(st, b, L, htab, octave, s, dthreshold, det_off); }
+// fastakaze::gCalcExtremaMap (akazed.cu:3476-3515): the same rule on int32 planes
+void hak_launch_extrema_level(hipStream_t st, const HakBatch& b, const HakLayout& L, const HakTables* htab, int octave, int s, int threshold,
+                              long det_off)
+{ launch_extrema_level_t<int>(st, b, L, htab, octave, s, threshold, det_off); }
 
 // The key map is sparse: only candidate pixels are ever written.  Instead of clearing the whole 8 B/px map before every
 // call (2.1 GB for a 128-image 1080p batch), every call zeroes the entries its own candidates touched once the keypoints
@@ -294,7 +282,7 @@ __global__ __launch_bounds__(256) void k_clear_cand_maps(unsigned long long* __r
     n = n < cand_cap ? n : cand_cap;
     for (long i = blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
         const unsigned long long e = cand[(long)img * cand_cap + i];
-        const int x = (int)(e & 0xFFFFu), y = (int)((e >> 16) & 0xFFFFu);
+        const int x = hak_cand_x(e), y = hak_cand_y(e);
         map[(long)y * p + x] = 0ull;
     }
     for (long i = blockIdx.x * 256 + threadIdx.x; i < bitmap_words; i += (long)gridDim.x * 256) bitmap[(long)img * bitmap_words + i] = 0ull;
@@ -310,9 +298,9 @@ __global__ __launch_bounds__(256) void k_seed_maps(const unsigned* __restrict__ 
     if (x >= w || y >= h) return;
     const int l = layer[(long)y * w + x];
     if (l < 0) return;
-    atomicMax(&map[(long)y * p + x], ((unsigned long long)resp_bits[(long)y * w + x] << 32) | (0xFFFFFFFFu - (unsigned)l));
+    atomicMax(&map[(long)y * p + x], hak_ext_key(resp_bits[(long)y * w + x], l));
     const long slot = atomicAdd(&state->ncand, 1);
-    if (slot < cand_cap) cand[slot] = ((unsigned long long)l << 32) | ((unsigned)y << 16) | (unsigned)x;
+    if (slot < cand_cap) cand[slot] = hak_cand_word(l, x, y);
 }
 
 void hak_launch_seed_maps(hipStream_t st, const HakBatch& b, const HakLayout& L, const unsigned* d_resp_bits, const int* d_layer)

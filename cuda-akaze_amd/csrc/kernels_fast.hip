@@ -435,51 +435,5 @@ void hakf_launch_det(hipStream_t st, const int* dxy, int* det, long stride, int 
     kf_hessian<<<grid, 256, 0, st>>>(dxy, det, stride, w, h, p, step, f1, f2);
 }
 
-// ---- akazed.cu:3476 gCalcExtremaMap (int): key = response << 32 | ~layer, candidates appended
-__global__ __launch_bounds__(256) void kf_extrema(const int* __restrict__ base, long stride, unsigned long long* maps, long map_stride,
-                                                  unsigned long long* cand, long cand_cap, HakImgState* state, HakLayout L,
-                                                  const HakTables* __restrict__ tab, int octave, int s, int threshold, long det_off)
-{
-    const int img = blockIdx.z;
-    const HakOct oc = L.oct[octave];
-    const int* det = base + (long)img * stride + det_off;
-    const int layer = octave * L.ms + s;
-    const float border = tab->borders[layer];
-    const int psz = (int)tab->borders[octave * L.ms];
-    const int lane = threadIdx.x & 63;
-    const int x = blockIdx.x * 64 + lane, y0 = blockIdx.y * 16 + (threadIdx.x >> 6);
-    const bool xok = x >= psz && x < oc.w && (int)(x - border + 0.5f) - 1 >= 0 && (int)(x + border + 0.5f) + 1 < oc.w;
-    for (int y = y0; y < blockIdx.y * 16 + 16; y += 4) {
-        bool hit = false;
-        int v = 0;
-        if (xok && y >= psz && y < oc.h && (int)(y - border + 0.5f) - 1 >= 0 && (int)(y + border + 0.5f) + 1 < oc.h) {
-            const int* vp = det + (long)y * oc.p + x;
-            v = *vp;
-            hit = v > threshold && v > vp[-oc.p] && v > vp[oc.p] && v > vp[-1] && v > vp[1] && v > vp[-oc.p - 1] &&
-                  v > vp[-oc.p + 1] && v > vp[oc.p - 1] && v > vp[oc.p + 1];
-        }
-        const unsigned long long m = __ballot(hit);
-        if (m) {
-            int cbase = 0;
-            if (lane == 0) cbase = atomicAdd(&state[img].ncand, __popcll(m));
-            cbase = __builtin_amdgcn_readfirstlane(cbase);
-            if (hit) {
-                const int fx = x << octave, fy = y << octave;
-                const unsigned long long key = ((unsigned long long)(unsigned)v << 32) | (0xFFFFFFFFu - (unsigned)layer);
-                atomicMax(&maps[(long)img * map_stride + (long)fy * L.oct[0].p + fx], key);
-                const long slot = cbase + __popcll(m & ((1ull << lane) - 1ull));
-                if (slot < cand_cap) cand[(long)img * cand_cap + slot] = ((unsigned long long)layer << 32) | ((unsigned)fy << 16) | (unsigned)fx;
-            }
-        }
-    }
-}
-void hak_launch_extrema_level(hipStream_t st, const HakBatch& b, const HakLayout& L, const HakTables* tab, int octave, int s, int threshold,
-                              long det_off)
-{
-    const HakOct oc = L.oct[octave];
-    dim3 grid((oc.w + 63) / 64, (oc.h + 15) / 16, b.nimg);
-    kf_extrema<<<grid, 256, 0, st>>>(reinterpret_cast<const int*>(b.base), b.stride, b.maps, b.map_stride, b.cand, b.cand_cap, b.state, L,
-                                     tab, octave, s, threshold, det_off);
-}
-
+// extrema (akazed.cu:3476 gCalcExtremaMap): k_extrema<int> in kernels_detect.hip
 // refine (akazed.cu:3600) + orientation (3649) + MLDB (3723): k_orient<int> / k_describe<int> in kernels_describe.hip

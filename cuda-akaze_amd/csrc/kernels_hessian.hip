@@ -72,20 +72,6 @@ __device__ __forceinline__ void hess_commit(const HessPrefetch<V, S>& P, V* sm, 
     }
 }
 
-template <typename V>
-struct HakExtremaArgs {
-    unsigned long long* maps;       // [nimg][map_stride]
-    long map_stride;
-    unsigned long long* cand;       // [nimg][cand_cap]
-    long cand_cap;
-    HakImgState* state;
-    int p0;                         // pitch of the full-resolution map
-    int octave, layer;
-    int psz;                        // (int)borders[octave*ms]     akazed.cu:2572
-    float border;
-    V threshold;
-};
-
 template <typename V, int S, bool INTERIOR>
 __device__ __forceinline__ void hessian_tile(V* __restrict__ oxy, V* __restrict__ od,
                                              int w, int h, int p, int x0, int y0, V fac1, V fac2,
@@ -221,8 +207,8 @@ __device__ __forceinline__ void hessian_tile(V* __restrict__ oxy, V* __restrict_
     }
     if (ex.maps == nullptr) return;                                 // (uniform) determinant only
     hak_lds_barrier();
-    // ---- extrema of this level on the output tile (akazed.cu:1346-1373)
-    const bool xok = x >= ex.psz && (int)(x - ex.border + 0.5f) - 1 >= 0 && (int)(x + ex.border + 0.5f) + 1 < w;
+    // ---- extrema of this level on the output tile (akazed.cu:1346-1373; the rule: hak_internal.h)
+    const bool xok = hak_ext_inside(x, w, ex.psz, ex.border);
     for (int rr = wv; rr < TY; rr += HF_NW) {
         const int y = y0 + rr;
         bool hit = false;
@@ -230,10 +216,7 @@ __device__ __forceinline__ void hessian_tile(V* __restrict__ oxy, V* __restrict_
         const V* vp = dt + (rr + HF_E) * EW + lane + HF_E;
         const V v = *vp;
         if (__ballot(v > ex.threshold) == 0ull) continue;
-        if (v > ex.threshold && xok && y >= ex.psz && (int)(y - ex.border + 0.5f) - 1 >= 0 && (int)(y + ex.border + 0.5f) + 1 < h) {
-            hit = v > vp[-EW] && v > vp[EW] && v > vp[-1] && v > vp[1] &&
-                  v > vp[-EW - 1] && v > vp[-EW + 1] && v > vp[EW - 1] && v > vp[EW + 1];
-        }
+        if (v > ex.threshold && xok && hak_ext_inside(y, h, ex.psz, ex.border)) hit = hak_ext_strict_max(v, vp, EW);
         const unsigned long long m = __ballot(hit);
         if (m) {
             // list slots: reserving them in the global counter needs an atomic WITH return, and waiting for it drains the
@@ -258,9 +241,8 @@ __device__ __forceinline__ void hessian_tile(V* __restrict__ oxy, V* __restrict_
             direct = __builtin_amdgcn_readfirstlane(direct);                  // wave-uniform
             if (hit) {
                 const int fx = x << ex.octave, fy = y << ex.octave;
-                const unsigned long long key = ((unsigned long long)hs_key_bits(v) << 32) | (0xFFFFFFFFu - (unsigned)ex.layer);
-                atomicMax(&ex.maps[(long)img * ex.map_stride + (long)fy * ex.p0 + fx], key);
-                const unsigned long long entry = ((unsigned long long)ex.layer << 32) | ((unsigned)fy << 16) | (unsigned)fx;
+                atomicMax(&ex.maps[(long)img * ex.map_stride + (long)fy * ex.p0 + fx], hak_ext_key(v, ex.layer));
+                const unsigned long long entry = hak_cand_word(ex.layer, fx, fy);
                 const long slot = base + __popcll(m & ((1ull << lane) - 1ull));
                 if (!direct) cbuf[slot] = entry;
                 else if (slot < ex.cand_cap) ex.cand[(long)img * ex.cand_cap + slot] = entry;
@@ -350,20 +332,6 @@ static void launch_fused(hipStream_t st, const V* src, V* dxy, V* det, long stri
     k_hessian_fused<V, S><<<hak_xcd_grid(ntx, nby, nimg), 64 * HF_NW, 0, st>>>(src, dxy, det, stride, w, h, p, v1, v2, tpb, ntx, nby, nimg, ex, cbuf_cap < 1 ? 1 : (cbuf_cap > HF_CBUF ? HF_CBUF : cbuf_cap));
 }
 
-template <typename V>
-static HakExtremaArgs<V> extrema_args(const HakBatch* b, const HakLayout* L, const HakTables* htab, int octave, int sub, V threshold)
-{
-    HakExtremaArgs<V> ex{};
-    if (b) {
-        const int layer = octave * L->ms + sub;
-        ex.maps = b->maps; ex.map_stride = b->map_stride; ex.cand = b->cand; ex.cand_cap = b->cand_cap;
-        ex.state = b->state; ex.p0 = L->oct[0].p; ex.octave = octave; ex.layer = layer;
-        ex.psz = (int)htab->borders[octave * L->ms]; ex.border = htab->borders[layer]; ex.threshold = threshold;
-    }
-    return ex;
-}
-
-
 // derivate + determinant (+ extrema when b != nullptr) of one level.  Returns true when the
 // extrema were handled here; false means the caller must run the stand-alone extrema kernel on `det`.
 // The fused kernels write `det` only when store_det is set; the dilation > 4 fallback always fills it.
@@ -394,7 +362,7 @@ static bool launch_hessian_level_t(hipStream_t st, const V* src, V* dxy, V* det,
         hak_note_launch_error("LP Hessian requested for a level the streaming kernel does not cover");
         return true;
     }
-    const HakExtremaArgs<V> ex = extrema_args<V>(b, L, htab, octave, sub, threshold);
+    const HakExtremaArgs<V> ex = hak_extrema_args<V>(b, L, htab, octave, sub, threshold);
     V* od = store_det ? det : nullptr;
     switch (step) {
     case 1: launch_fused<V, 1>(st, src, dxy, od, stride, w, h, p, nimg, ex, kn.hess_cbuf); return true;

@@ -131,9 +131,7 @@ template <typename V> struct HsArgs {
                                                     // HAK_BUF_OOB: the determinant is not stored (the hardware drops the store)
     int w, h, p;
     V fac1, fac2;
-    // extrema (maps == nullptr: determinant only)
-    unsigned long long* maps; unsigned long long* cand; long cand_cap; HakImgState* st;
-    int p0, octave, layer, psz; float border; V threshold;
+    HakExtremaArgs<V> ex;                           // extrema (maps == nullptr: determinant only)
 };
 
 // Arguments that only the (rare) candidate emission needs.  As kernel arguments they would sit in SGPRs for the whole row
@@ -177,10 +175,9 @@ __device__ __forceinline__ void hs_emit(const bool hit, const V v, const int x, 
         const int cnt = __popcll(m);
         if (hit) {
             const int fx = x << a.octave, fy = e << a.octave;
-            const unsigned long long key = ((unsigned long long)hs_key_bits(v) << 32) | (0xFFFFFFFFu - (unsigned)a.layer);
-            (void)__hip_atomic_fetch_max((hs_gu64p)a.maps + ((long)fy * a.p0 + fx), key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            cb.buf[cb.n + __popcll(m & ((1ull << lane) - 1ull))] =
-                ((unsigned long long)a.layer << 32) | ((unsigned)fy << 16) | (unsigned)fx;
+            (void)__hip_atomic_fetch_max((hs_gu64p)a.maps + ((long)fy * a.p0 + fx), hak_ext_key(v, a.layer), __ATOMIC_RELAXED,
+                                         __HIP_MEMORY_SCOPE_AGENT);
+            cb.buf[cb.n + __popcll(m & ((1ull << lane) - 1ull))] = hak_cand_word(a.layer, fx, fy);
         }
         cb.n += cnt;
     }
@@ -339,7 +336,7 @@ __device__ __forceinline__ void hs_iter(HsState<V, S, LP>& T, const int t, const
     // ---- extrema of row e = t - 2S - 1 (akazed.cu:1346-1373)
     {
         const int e = t - 2 * S - 1;
-        const V thr = a.threshold;
+        const V thr = a.ex.threshold;
         const V4 v = T.Dc;
         // threshold first: almost no pixel passes it, so the wave almost always skips the neighbourhood test.  [er0, er1) = the
         // rows of this segment that pass the reference's border test (akazed.cu:1351-1356), worked out once per strip; empty
@@ -367,10 +364,10 @@ __device__ __forceinline__ void hs_iter(HsState<V, S, LP>& T, const int t, const
             bool hw = owns && (xok & 8u) && v.w > mw;
             if (__ballot(hx || hy || hz || hw) != 0ull) {
                 // akazed.cu:1361-1362 as written: false as soon as one neighbour is a NaN
-                hx = hx && v.x > up.x && v.x > dn.x && v.x > vl && v.x > v.y && v.x > ul && v.x > up.y && v.x > dl && v.x > dn.y;
-                hy = hy && v.y > up.y && v.y > dn.y && v.y > v.x && v.y > v.z && v.y > up.x && v.y > up.z && v.y > dn.x && v.y > dn.z;
-                hz = hz && v.z > up.z && v.z > dn.z && v.z > v.y && v.z > v.w && v.z > up.y && v.z > up.w && v.z > dn.y && v.z > dn.w;
-                hw = hw && v.w > up.w && v.w > dn.w && v.w > v.z && v.w > vr && v.w > up.z && v.w > ur && v.w > dn.z && v.w > dr;
+                hx = hx && hak_ext_strict_max(v.x, up.x, dn.x, vl, v.y, ul, up.y, dl, dn.y);
+                hy = hy && hak_ext_strict_max(v.y, up.y, dn.y, v.x, v.z, up.x, up.z, dn.x, dn.z);
+                hz = hz && hak_ext_strict_max(v.z, up.z, dn.z, v.y, v.w, up.y, up.w, dn.y, dn.w);
+                hw = hw && hak_ext_strict_max(v.w, up.w, dn.w, v.z, vr, up.z, ur, dn.z, dr);
                 if (T.cb.n > HS_CBUF - 128) hs_flush(T.cb, cold, lane);    // a row holds at most 128 strict 3x3 maxima per wave
                 const HsCold ca = *cold;                                   // one LDS read of the parked arguments per row with a hit
                 hs_emit(hx, v.x, x0, e, ca, lane, T.cb);
@@ -407,14 +404,12 @@ __device__ __forceinline__ void hs_strip(const HsArgs<V>& a, const int x0, const
     // per-component x range of the extrema test (akazed.cu:1351-1356), constant along the strip
     unsigned xok = 0;
 #pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const int x = x0 + k;
-        if (x >= a.psz && (int)(x - a.border + 0.5f) - 1 >= 0 && (int)(x + a.border + 0.5f) + 1 < w) xok |= 1u << k;
-    }
+    for (int k = 0; k < 4; k++)
+        if (hak_ext_inside(x0 + k, w, a.ex.psz, a.ex.border)) xok |= 1u << k;
     // rows of this segment whose extrema are wanted: the reference's border test is monotone in the row, so it is a range
     int er0 = 0, er1 = 0;
-    if (a.maps != nullptr) {
-        auto row_ok = [&](int e) { return e >= a.psz && (int)(e - a.border + 0.5f) - 1 >= 0 && (int)(e + a.border + 0.5f) + 1 < h; };
+    if (a.ex.maps != nullptr) {
+        auto row_ok = [&](int e) { return hak_ext_inside(e, h, a.ex.psz, a.ex.border); };
         er0 = ybeg; er1 = yend;
         while (er0 < er1 && !row_ok(er0)) er0++;
         while (er1 > er0 && !row_ok(er1 - 1)) er1--;
@@ -458,12 +453,12 @@ __device__ __forceinline__ void hs_strip(const HsArgs<V>& a, const int x0, const
         else
             hs_group<V, S, XE, false, LP>(std::make_integer_sequence<int, G::R>{}, T, tb, a, xl, x0, ybeg, yend, owns, xok, lane, orsrc, ovoff, er0, er1, cold);
     }
-    if (a.maps != nullptr) hs_flush(T.cb, cold, lane);
+    if (a.ex.maps != nullptr) hs_flush(T.cb, cold, lane);
 }
 
 // grid: hak_xcd_grid(strips, segment groups of 4, images); wave wv of a block takes segment by*4 + wv
 template <typename V, int S, bool LP>
-__global__ __launch_bounds__(256, (HsGeo<S, LP>::MINW)) void k_hessian_stream(HsArgs<V> a, long stride, long map_stride, int ry, int nbx, int nby, int nimg)
+__global__ __launch_bounds__(256, (HsGeo<S, LP>::MINW)) void k_hessian_stream(HsArgs<V> a, long stride, int ry, int nbx, int nby, int nimg)
 {
     using G = HsGeo<S, LP>;
     __shared__ typename FedV<V>::V4 yring[4 * G::R * 64];                     // per-wave private Ly rings: no barrier ever needed
@@ -473,9 +468,11 @@ __global__ __launch_bounds__(256, (HsGeo<S, LP>::MINW)) void k_hessian_stream(Hs
     int bx, by, img;
     if (!hak_xcd_decode(nbx, nby, nimg, bx, by, img)) return;
     a.src += (long)img * stride; a.obase += (long)img * stride;
-    if (a.maps) {
-        if (threadIdx.x == 0)
-            cold = HsCold{a.maps + (long)img * map_stride, a.cand + (long)img * a.cand_cap, a.cand_cap, a.st + img, a.p0, a.octave, a.layer, 0};
+    if (a.ex.maps) {
+        if (threadIdx.x == 0) {
+            const HakExtremaArgs<V>& ex = a.ex;
+            cold = HsCold{ex.maps + (long)img * ex.map_stride, ex.cand + (long)img * ex.cand_cap, ex.cand_cap, ex.state + img, ex.p0, ex.octave, ex.layer, 0};
+        }
         __syncthreads();                                        // (block-uniform; the only barrier of the kernel)
     }
     const int lane = threadIdx.x & 63;
@@ -496,14 +493,14 @@ __global__ __launch_bounds__(256, (HsGeo<S, LP>::MINW)) void k_hessian_stream(Hs
 }
 
 template <typename V, int S, bool LP>
-void launch_stream(hipStream_t st, HsArgs<V> a, long stride, long map_stride, int nimg)
+void launch_stream(hipStream_t st, HsArgs<V> a, long stride, int nimg)
 {
     using G = HsGeo<S, LP>;
     const int gx = (a.w + G::XV - 1) / G::XV;
     // rows per wave: tall segments amortise the 4S+2 warm-up rows; shrink while the grid cannot fill the chip
     const int ry = hak_stream_rows(a.h, (long)gx * nimg, 16);
     const int gy = (a.h + 4 * ry - 1) / (4 * ry);
-    k_hessian_stream<V, S, LP><<<hak_xcd_grid(gx, gy, nimg), 256, 0, st>>>(a, stride, map_stride, ry, gx, gy, nimg);
+    k_hessian_stream<V, S, LP><<<hak_xcd_grid(gx, gy, nimg), 256, 0, st>>>(a, stride, ry, gx, gy, nimg);
 }
 
 
@@ -524,27 +521,21 @@ bool launch_stream_any(hipStream_t st, const V* src, V* dxy, V* det, bool store_
     a.obase = lo; a.off_dxy = (unsigned)((dxy - lo) * sizeof(V));
     a.off_det = store_det ? (unsigned)((det - lo) * sizeof(V)) : HAK_BUF_OOB;
     a.src = src; a.dxy = dxy; a.det = det; a.w = w; a.h = h; a.p = p; a.fac1 = fac1; a.fac2 = fac2;
-    long map_stride = 0;
-    if (b) {
-        const int layer = octave * L->ms + sub;
-        a.maps = b->maps; map_stride = b->map_stride; a.cand = b->cand; a.cand_cap = b->cand_cap; a.st = b->state;
-        a.p0 = L->oct[0].p; a.octave = octave; a.layer = layer;
-        a.psz = (int)htab->borders[octave * L->ms]; a.border = htab->borders[layer]; a.threshold = threshold;
-    }
+    a.ex = hak_extrema_args<V>(b, L, htab, octave, sub, threshold);
     if (lp) {
         switch (step) {
-        case 1: launch_stream<V, 1, true>(st, a, stride, map_stride, nimg); break;
-        case 2: launch_stream<V, 2, true>(st, a, stride, map_stride, nimg); break;
-        case 3: launch_stream<V, 3, true>(st, a, stride, map_stride, nimg); break;
-        default: launch_stream<V, 4, true>(st, a, stride, map_stride, nimg); break;
+        case 1: launch_stream<V, 1, true>(st, a, stride, nimg); break;
+        case 2: launch_stream<V, 2, true>(st, a, stride, nimg); break;
+        case 3: launch_stream<V, 3, true>(st, a, stride, nimg); break;
+        default: launch_stream<V, 4, true>(st, a, stride, nimg); break;
         }
         return true;
     }
     switch (step) {
-    case 1: launch_stream<V, 1, false>(st, a, stride, map_stride, nimg); break;
-    case 2: launch_stream<V, 2, false>(st, a, stride, map_stride, nimg); break;
-    case 3: launch_stream<V, 3, false>(st, a, stride, map_stride, nimg); break;
-    default: launch_stream<V, 4, false>(st, a, stride, map_stride, nimg); break;
+    case 1: launch_stream<V, 1, false>(st, a, stride, nimg); break;
+    case 2: launch_stream<V, 2, false>(st, a, stride, nimg); break;
+    case 3: launch_stream<V, 3, false>(st, a, stride, nimg); break;
+    default: launch_stream<V, 4, false>(st, a, stride, nimg); break;
     }
     return true;
 }

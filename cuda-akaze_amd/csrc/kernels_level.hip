@@ -33,12 +33,7 @@ template <typename V> struct LvHess {
     V* dxy;                         // the level's interleaved {Lx, Ly} plane of image 0
     V fac1, fac2;
     int S;                          // dilation (sigma_size)
-    unsigned long long* maps; long map_stride;
-    unsigned long long* cand; long cand_cap;
-    HakImgState* state;
-    int p0, octave, layer, psz;
-    float border;
-    V threshold;
+    HakExtremaArgs<V> ex;           // the level's extrema (hak_internal.h)
 };
 
 namespace {
@@ -106,7 +101,7 @@ __global__ __launch_bounds__(LV_NT) void k_level_tile(const V* __restrict__ src,
     V* B = A + EW * EH;                                      // row pass, then g
     V* C = B + EW * EH;                                      // smooth, then L pong
     // Hessian scratch behind the three planes: Lx, Ly on core +- (S + 1), the determinant on core +- 1
-    const bool hess = FIRST && hs.maps != nullptr;           // (uniform)
+    const bool hess = FIRST && hs.ex.maps != nullptr;        // (uniform)
     const int XW = T + 2 * (hs.S + 1), DW = T + 2;
     V* HX_ = C + EW * EH;
     V* HY_ = HX_ + XW * XW;
@@ -287,8 +282,7 @@ __global__ __launch_bounds__(LV_NT) void k_level_tile(const V* __restrict__ src,
         hak_lds_barrier();
         V* tmp = cur; cur = nxt; nxt = tmp;
         if (k == 1 && hess) {
-            // ---- extrema of the level on the core (gCalcExtremaMap akazed.cu:1346-1373): border filter, threshold, strict 3 x 3
-            // maximum; winners raise the full-resolution key map and join the image's candidate list (as k_extrema does)
+            // ---- extrema of the level on the core (gCalcExtremaMap akazed.cu:1346-1373; the rule: hak_internal.h)
             const int lane = tid & 63;
             for (int base = 0; base < T * T; base += LV_NT) {                         // (uniform trip count: ballots inside)
                 const int idx = base + tid;
@@ -296,28 +290,12 @@ __global__ __launch_bounds__(LV_NT) void k_level_tile(const V* __restrict__ src,
                 const int x = bx * T + c, y = by * T + r;
                 bool hit = false;
                 V v = V(0);
-                if (idx < T * T && x >= hs.psz && x < w && y >= hs.psz && y < h &&
-                    (int)(x - hs.border + 0.5f) - 1 >= 0 && (int)(x + hs.border + 0.5f) + 1 < w &&
-                    (int)(y - hs.border + 0.5f) - 1 >= 0 && (int)(y + hs.border + 0.5f) + 1 < h) {
+                if (idx < T * T && hak_ext_inside(x, w, hs.ex.psz, hs.ex.border) && hak_ext_inside(y, h, hs.ex.psz, hs.ex.border)) {
                     const V* vp = DT + (r + 1) * DW + c + 1;
                     v = *vp;
-                    hit = v > hs.threshold && v > vp[-DW] && v > vp[DW] && v > vp[-1] && v > vp[1] &&
-                          v > vp[-DW - 1] && v > vp[-DW + 1] && v > vp[DW - 1] && v > vp[DW + 1];
+                    hit = v > hs.ex.threshold && hak_ext_strict_max(v, vp, DW);
                 }
-                const unsigned long long m = __ballot(hit);
-                if (m) {
-                    int cbase = 0;
-                    if (lane == 0) cbase = atomicAdd(&hs.state[img].ncand, __popcll(m));
-                    cbase = __builtin_amdgcn_readfirstlane(cbase);
-                    if (hit) {
-                        const int fx = x << hs.octave, fy = y << hs.octave;
-                        const unsigned long long key = ((unsigned long long)hs_key_bits(v) << 32) | (0xFFFFFFFFu - (unsigned)hs.layer);
-                        atomicMax(&hs.maps[(long)img * hs.map_stride + (long)fy * hs.p0 + fx], key);
-                        const long slot = cbase + __popcll(m & ((1ull << lane) - 1ull));
-                        if (slot < hs.cand_cap)
-                            hs.cand[(long)img * hs.cand_cap + slot] = ((unsigned long long)hs.layer << 32) | ((unsigned)fy << 16) | (unsigned)fx;
-                    }
-                }
+                hak_ext_append_wave(hit, v, x, y, img, lane, hs.ex);
             }
         }
     }
@@ -352,7 +330,7 @@ void launch_level(hipStream_t st, const V* src, V* smooth, V* dst, long stride, 
     }
     // the largest tile (multiple of 8, at most 64) whose three planes fit the LDS budget
     const int HX = (ns + 5 + 3) & ~3;                      // (as in the kernel)
-    const bool hess = FIRST && hs.maps != nullptr;
+    const bool hess = FIRST && hs.ex.maps != nullptr;
     auto plane = [&](int t) { return (long)(t + 2 * HX) * (t + 2 * (ns + 3)); };
     auto total = [&](int t) { return 3L * plane(t) + (hess ? 2L * (t + 2 * hs.S + 2) * (t + 2 * hs.S + 2) + (long)(t + 2) * (t + 2) : 0L); };
     int T = 64;
@@ -412,11 +390,8 @@ LvHess<V> level_hess(V* dxy, int step, int first_ns, const HakBatch* b, const Ha
     hak_deriv_factors(&f1, &f2);
     if constexpr (std::is_same<V, float>::value) { hs.fac1 = f1; hs.fac2 = f2; }
     else { hs.fac1 = (int)(f1 * 65536 + 0.5f); hs.fac2 = (int)(f2 * 65536 + 0.5f); }     // akazed.cu:4183-4184
-    const int layer = octave * L->ms + sub;
     hs.dxy = dxy; hs.S = step;
-    hs.maps = b->maps; hs.map_stride = b->map_stride; hs.cand = b->cand; hs.cand_cap = b->cand_cap; hs.state = b->state;
-    hs.p0 = L->oct[0].p; hs.octave = octave; hs.layer = layer;
-    hs.psz = (int)htab->borders[octave * L->ms]; hs.border = htab->borders[layer]; hs.threshold = threshold;
+    hs.ex = hak_extrema_args<V>(b, L, htab, octave, sub, threshold);
     return hs;
 }
 

@@ -88,7 +88,7 @@ __global__ __launch_bounds__(256) void k_sel_hist(const unsigned long long* __re
         while (word) {
             const int bit = __ffsll((long long)word) - 1;
             word &= word - 1;
-            const unsigned k = sel_key((unsigned)(map[(long)y * p0 + x0 + bit] >> 32), fast);
+            const unsigned k = sel_key(hak_key_word(map[(long)y * p0 + x0 + bit]), fast);
             if (fshift == 32 || (k >> fshift) == prefix) atomicAdd(&hist[(k >> shift) & mask], 1u);
         }
     }
@@ -158,7 +158,7 @@ __global__ __launch_bounds__(256) void k_sel_rows(const unsigned long long* __re
                 while (word) {
                     const int bit = __ffsll((long long)word) - 1;
                     word &= word - 1;
-                    const unsigned k = sel_key((unsigned)(map[(long)y * p0 + (w0 + lane) * 64 + bit] >> 32), fast);
+                    const unsigned k = sel_key(hak_key_word(map[(long)y * p0 + (w0 + lane) * 64 + bit]), fast);
                     if (k < T) keep &= ~(1ull << bit);
                     gt += k > T;
                     eq += k == T;
@@ -219,7 +219,7 @@ __global__ __launch_bounds__(1024) void k_sel_ties(const unsigned long long* __r
             while (word) {
                 const int bit = __ffsll((long long)word) - 1;
                 word &= word - 1;
-                if (sel_key((unsigned)(map[(long)y * p0 + wi * 64 + bit] >> 32), fast) == T && seen++ >= keep) out &= ~(1ull << bit);
+                if (sel_key(hak_key_word(map[(long)y * p0 + wi * 64 + bit]), fast) == T && seen++ >= keep) out &= ~(1ull << bit);
             }
             if (out != orig) row[wi] = out;
         }

@@ -139,6 +139,25 @@ def extrema_fixture():
     return {0: d0, 1: d1}, sorted(exp, key=lambda t: (t[1], t[0]))
 
 
+# the ordered compares next to a NaN (akazed.cu:1360-1362: `*vp > threshold && *vp > *vp0 && ... `): every compare with a NaN
+# operand is false.  Sublevel 0 (sigma 2) accepts 29 <= x <= 170, 29 <= y <= 150 (above); its NMS disc has radius 2 (isz of
+# size 2.4), the three sites are 40 and more pixels apart.
+EXT_NAN_SITES = {"a": (60, 60), "b": (100, 90), "c": (140, 120)}
+
+
+def extrema_nan_fixture():
+    """-> (det (h, w) float32 of octave 0 / sublevel 0, expected [(x, y, layer, response)]): zero but for
+    (a) 1.0 whose right-hand neighbour is NaN -> `1.0 > NaN` is false (:1361): no extremum;
+    (b) NaN among zeros                        -> `NaN > threshold` is false (:1360); its neighbours hold 0 <= threshold;
+    (c) 1.0 among zeros                        -> the one extremum."""
+    det = np.zeros((EXT_H, EXT_W), np.float32)
+    (ax, ay), (bx, by), (cx, cy) = (EXT_NAN_SITES[k] for k in "abc")
+    det[ay, ax] = f32(1.0); det[ay, ax + 1] = np.nan
+    det[by, bx] = np.nan
+    det[cy, cx] = f32(1.0)
+    return det, [(cx, cy, 0, f32(1.0))]
+
+
 def blob_plane(w, h, centres, sigma=3.0):
     """sum of isotropic Gaussian blobs: the Hessian determinant of each has its strict 3 x 3 maximum at the (integer) centre"""
     yy, xx = np.mgrid[0:h, 0:w].astype(np.float64)

@@ -63,6 +63,19 @@ def test_extrema_border_filter_threshold_and_scatter(ah):
     det.close()
 
 
+def test_extrema_next_to_a_nan(ah):
+    """the stand-alone float extrema kernel in front of NaN determinants (the pipeline reaches it only for dilation > 4): the
+    sites are further apart than the NMS disc, so every candidate would come out as a keypoint -- exactly one does, site (c)"""
+    det = _akazer(ah, lf.EXT_W, lf.EXT_H, noctaves=1)
+    plane, exp = lf.extrema_nan_fixture()
+    det.tail_begin()
+    det.tail_det_level(0, 0, plane)
+    pts, total = det.tail_finish(refine=False)
+    assert total == len(exp) == 1
+    assert [(int(p["x"]), int(p["y"]), int(p["octave"]), p["response"]) for p in pts] == exp
+    det.close()
+
+
 @pytest.mark.parametrize("stream", ["2", "0"], ids=["streaming kernel", "tile kernel"])
 def test_extrema_border_filter_in_the_fused_hessian_kernels(ah, monkeypatch, stream):
     """the border rule inside k_hessian_stream / k_hessian_fused: blob images whose determinant peaks sit on and next to the

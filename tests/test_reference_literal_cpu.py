@@ -93,6 +93,16 @@ def test_extrema_border_filter_threshold_and_scatter(okz):
         assert size[y, x] == lf.SIZES[l % 4]                         # akazed.cu:1371 d_extrema_param[max_scale + curr_scale]
 
 
+def test_extrema_next_to_a_nan(okz):
+    """a NaN determinant is no extremum and neither is its neighbour: exactly one candidate, at site (c)"""
+    det, exp = lf.extrema_nan_fixture()
+    dets = np.zeros((4,) + det.shape, np.float32)
+    dets[0] = det
+    resp, size, layer = _run_extrema(okz, {0: dets})
+    ys, xs = np.nonzero(layer >= 0)
+    assert [(int(x), int(y), int(layer[y, x]), resp[y, x]) for y, x in zip(ys, xs)] == exp
+
+
 def test_extrema_fast_uses_the_same_rule(okz):
     """fastakaze::gCalcExtremaMap (akazed.cu:3476-3515) is the float kernel with int planes and threshold 65 (akaze.cpp:559)"""
     dets, exp = lf.extrema_fixture()
