@@ -85,6 +85,7 @@ SYMBOLS = {
     "hak_set_concurrency": (C.c_int, [_vp, C.c_int]),
     "hak_set_null_order": (C.c_int, [_vp, C.c_int]),
     "hak_set_retain_best": (C.c_int, [_vp, C.c_int]),
+    "hak_set_retain_grid": (C.c_int, [_vp, C.c_int]),
     "hak_detect_and_compute": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _ip, _vp, C.c_int]),
     "hak_detect_and_compute_pair": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, C.c_int, _ip, _ip, _vp, _vp, C.c_int, C.c_int]),
     "hak_detect_and_compute_batch": (C.c_int, [_vp, _vp, C.c_long, C.c_int, C.c_int, _vp, _vp, C.c_int]),
@@ -296,13 +297,15 @@ class Akazer:
         self._ctx = None
         self._cfg = default_config()
         self._retain_best = False
+        self._retain_grid = 0
         self.whp = (0, 0, 0)
 
     def init(self, whp0, noctaves=4, max_scale=4, per=0.7, kcontrast=0.03, soffset=1.6, reordering=True,
              derivative_factor=1.5, dthreshold=0.001, diffusivity=PM_G2, descriptor_pattern_size=10,
-             max_pts=10000, upright=False, batch=1, retain_best=False):
+             max_pts=10000, upright=False, batch=1, retain_best=False, retain_grid=0):
         self.whp = tuple(whp0)
         self._retain_best = bool(retain_best)
+        self._retain_grid = self._checked_grid(retain_grid)
         self._cfg = default_config(
             noctaves=noctaves, max_scale=max_scale, per=per, kcontrast=kcontrast, soffset=soffset,
             reordering=int(reordering), derivative_factor=derivative_factor, dthreshold=dthreshold,
@@ -318,6 +321,8 @@ class Akazer:
         self._ctx_wh = (w, h)
         if self._retain_best:
             check(lib.hak_set_retain_best(ctx, 1))
+        if self._retain_grid:
+            check(lib.hak_set_retain_grid(ctx, self._retain_grid))
 
     def set_retain_best(self, on=True):
         """hak_set_retain_best: an image with more survivors than its clamp keeps its strongest ones instead of the raster-order
@@ -325,6 +330,21 @@ class Akazer:
         self._retain_best = bool(on)
         if self._ctx is not None:
             check(lib.hak_set_retain_best(self._ctx, int(self._retain_best)))
+
+    @staticmethod
+    def _checked_grid(G):
+        G = int(G)
+        if G != 0 and not 8 <= G <= 128:
+            raise ValueError("retain_grid: the cell size must be 0 (off) or between 8 and 128")
+        return G
+
+    def set_retain_grid(self, G):
+        """hak_set_retain_grid: an image with more survivors than its clamp keeps the best of every G x G pixel cell (8 <= G <= 128;
+        0: off; hipakaze.h states the rule).  While on it decides the policy whatever set_retain_best says.  Remembered: a context
+        re-created for another image size keeps the mode."""
+        self._retain_grid = self._checked_grid(G)
+        if self._ctx is not None:
+            check(lib.hak_set_retain_grid(self._ctx, self._retain_grid))
 
     @property
     def ctx(self):

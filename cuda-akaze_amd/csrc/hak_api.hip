@@ -322,7 +322,7 @@ extern "C" void hak_destroy(hak_ctx* c)
         for (auto ev : p.ev) (void)hipEventDestroy(ev);
     hak_match_scratch_free(&c->msc);
     void* bufs[] = {c->arena, c->maps, c->bitmap, c->rowcount, c->cand, c->state, c->d_num, c->dtab, c->knn, c->d_cnt, c->perm, c->pair_pts,
-                    c->hom_slots, c->hom_rec, c->sel.st, c->sel.bins, c->sel.tie};
+                    c->hom_slots, c->hom_rec, c->sel.st, c->sel.bins, c->sel.tie, c->grid.st, c->grid.count, c->grid.comp};
     for (void* b : bufs) (void)hipFree(b);
     if (c->h_num) (void)hipHostFree(c->h_num);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -357,6 +357,30 @@ extern "C" int hak_set_retain_best(hak_ctx* c, int on)
 {
     if (!c) return fail("null context");
     c->retain_best = on != 0;
+    return 0;
+}
+
+// (read like hak_set_retain_best's flag and part of the graph key with it.  The scratch is sized for the smallest cell, so a later
+// change of G allocates nothing and a sequence captured earlier keeps valid pointers; it is allocated here, at the first G > 0)
+extern "C" int hak_set_retain_grid(hak_ctx* c, int G)
+{
+    if (!c) return fail("null context");
+    if (G != 0 && (G < HAK_GRID_MIN || G > HAK_GRID_MAX))
+        return fail("hak_set_retain_grid: the cell size must be 0 (off) or between " + std::to_string(HAK_GRID_MIN) + " and " + std::to_string(HAK_GRID_MAX));
+    if (G > 0 && !c->grid.st) {
+        const int B = c->cfg.batch;
+        HakGridScratch g;
+        g.cell_cap = (long)((c->L.oct[0].w + HAK_GRID_MIN - 1) / HAK_GRID_MIN) * ((c->L.oct[0].h + HAK_GRID_MIN - 1) / HAK_GRID_MIN);
+        hipError_t e = hipMalloc((void**)&g.st, sizeof(HakGridState) * (size_t)B);
+        if (e == hipSuccess) e = hipMalloc((void**)&g.count, sizeof(int) * (size_t)g.cell_cap * B);
+        if (e == hipSuccess) e = hipMalloc((void**)&g.comp, sizeof(unsigned long long) * (size_t)g.cell_cap * B);
+        if (e != hipSuccess) {
+            (void)hipFree(g.st); (void)hipFree(g.count); (void)hipFree(g.comp);
+            return fail(std::string("hak_set_retain_grid: ") + hipGetErrorString(e));
+        }
+        c->grid = g;
+    }
+    c->retain_grid = G;
     return 0;
 }
 

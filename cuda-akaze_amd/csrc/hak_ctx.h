@@ -89,6 +89,8 @@ struct hak_ctx {
     bool maps_dirty = false;        // a call failed between writing the key map and cleaning it up: clear it in full next time
     bool retain_best = false;       // hak_set_retain_best: an image over its clamp keeps its strongest survivors (kernels_select.hip)
     HakSelScratch sel;              // ... and their scratch, allocated with the context
+    int retain_grid = 0;            // hak_set_retain_grid: cell size G of the grid selection (kernels_grid_select.hip), 0 = off
+    HakGridScratch grid;            // ... and its scratch, allocated when the mode is first turned on (grid.G stays 0 here)
 };
 
 struct ProfScope {
@@ -115,6 +117,13 @@ struct ProfScope {
     }
     ~ProfScope() { if (stop) (void)hipEventRecord(stop, s); }
 };
+
+// the selection scratch a call's HakBatch carries: the grid mode replaces the strongest-N mode while it is on
+static inline void hak_batch_selection(const hak_ctx* c, HakBatch& b)
+{
+    if (c->retain_best) b.sel = c->sel;
+    if (c->retain_grid) { b.grid = c->grid; b.grid.G = c->retain_grid; }
+}
 
 // ------------------------------------------------------- the launch sequence (hak_sequence.hip)
 // the key map must be all zero when a launch sequence starts; a failed call leaves the flag set (see there)

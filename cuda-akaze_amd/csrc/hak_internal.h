@@ -334,6 +334,35 @@ struct HakSelScratch {
     int* tie = nullptr;                         // [nimg][h0] keys equal to T per row
 };
 
+// the order-preserving map of the 32-bit response word: float bits (negative values reversed below the positive ones) or int32
+__device__ __forceinline__ unsigned sel_key(unsigned u, int fast)
+{
+    return fast ? (u ^ 0x80000000u) : ((u >> 31) ? ~u : (u | 0x80000000u));
+}
+// the clamp of image img, exactly as k_row_scan computes it
+__device__ __forceinline__ int sel_cap(int img, int max_pts, int cap0, int cap1)
+{
+    return cap0 > 0 ? (img == 0 ? cap0 : cap1) : max_pts;
+}
+
+// Per-image state and scratch of the grid selection (kernels_grid_select.hip, hak_set_retain_grid), allocated at the first use of
+// the mode for cfg.batch images and the smallest cell size (HAK_GRID_MIN).  Every word a call reads is written earlier in the same call.
+#define HAK_GRID_MIN 8
+#define HAK_GRID_MAX 128
+struct HakGridState {
+    int active;                                 // survivors > clamp: this image selects (else every grid kernel leaves at once)
+    int cap;                                    // the image's clamp C
+    int q;                                      // the quota: every cell keeps its min(n_c, q) highest-ranked survivors
+    int rem;                                    // R = C - sum min(n_c, q): places for the rank-q candidates
+};
+struct HakGridScratch {
+    HakGridState* st = nullptr;                 // [nimg]
+    int* count = nullptr;                       // [nimg][cell_cap] n_c
+    unsigned long long* comp = nullptr;         // [nimg][cell_cap] the rank-q candidate of a cell with n_c > q: K << 32 | ~raster index
+    long cell_cap = 0;                          // cells per image at HAK_GRID_MIN
+    int G = 0;                                  // the cell size of this call; 0: the mode is off
+};
+
 struct HakBatch {
     float* base;                  // arena of image 0
     long stride;                  // floats between consecutive image arenas
@@ -353,6 +382,8 @@ struct HakBatch {
     int cap0 = 0, cap1 = 0;
     // scratch of the strongest-N selection (kernels_select.hip, hak_set_retain_best); sel.st == nullptr: the raster-order clamp
     HakSelScratch sel{};
+    // scratch of the grid selection (kernels_grid_select.hip, hak_set_retain_grid); grid.G > 0: it replaces both other policies
+    HakGridScratch grid{};
 };
 // the knobs a launcher works with: the owning context's, or (no context: b == nullptr or a stage operator's batch) the environment's now
 static inline HakKnobs hak_knobs_of(const HakBatch* b) { return (b && b->knobs) ? *b->knobs : hak_knobs_from_env(); }
@@ -526,6 +557,8 @@ void hak_launch_nms_emit(hipStream_t st, const HakBatch& b, const HakLayout& L, 
 void hak_launch_clear_maps(hipStream_t st, const HakBatch& b, const HakLayout& L);
 // strongest-N selection (kernels_select.hip): prunes the survivor bitmap and rewrites the row counts between k_nms_cand and k_row_scan
 void hak_launch_select(hipStream_t st, const HakBatch& b, const HakLayout& L, int max_pts, int cap0, int cap1, int fast);
+// grid selection (kernels_grid_select.hip): the same place and the same effect on bitmap and row counts, by the cell rule of hak_set_retain_grid
+void hak_launch_grid_select(hipStream_t st, const HakBatch& b, const HakLayout& L, int max_pts, int cap0, int cap1, int fast);
 void hak_launch_seed_maps(hipStream_t st, const HakBatch& b, const HakLayout& L, const unsigned* d_resp_bits, const int* d_layer);
 
 // integer FAST path (kernels_fast.hip); planes are int32 in the same arena layout.  Overloads of the launchers above ...

@@ -93,7 +93,7 @@ static LevelArgs level_args(hak_ctx* c, const void* images, long image_stride, i
     LevelArgs a{c, HakBatch{c->arena, L.arena, nimg, c->state, c->maps, L.oct[0].plane, c->bitmap, c->rowcount, c->cand, c->cand_cap, &c->knobs,
                             c->perm, c->cfg.max_pts},
                 images, image_stride, pitch, nimg, {}, {}};
-    if (c->retain_best) a.b.sel = c->sel;
+    hak_batch_selection(c, a.b);
     return a;
 }
 
@@ -454,7 +454,7 @@ static int run_detect_inner(hak_ctx* c, const float* d_images, long image_stride
     memset(&key, 0, sizeof(key));
     key.img = d_images; key.stride = image_stride; key.pitch = pitch; key.nimg = nimg; key.pts = d_points;
     key.num = d_num_pts; key.desc = desc; key.max_pts = max_pts; key.conc = c->concurrent ? 1 : 0; key.st = c->stream; key.hpts = h_pinned; key.cap0 = cap0; key.cap1 = cap1;
-    key.retain = c->retain_best ? 1 : 0;
+    key.retain = (c->retain_best ? 1 : 0) | (c->retain_grid << 1);     // (both selection modes: what hak_batch_selection reads)
     int slot = -1, victim = 0;
     for (int i = 0; i < hak_ctx::NGRAPH; i++) {
         if (c->graph_exec[i] && memcmp(&key, &c->gkey[i], sizeof(key)) == 0) slot = i;

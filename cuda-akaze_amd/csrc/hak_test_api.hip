@@ -154,7 +154,7 @@ extern "C" int hak_op_hessian(const float* s, float* lx, float* ly, float* det, 
 static HakBatch tail_batch(hak_ctx* c)
 {
     HakBatch b{c->arena, c->L.arena, 1, c->state, c->maps, c->L.oct[0].plane, c->bitmap, c->rowcount, c->cand, c->cand_cap, &c->knobs};
-    if (c->retain_best) b.sel = c->sel;                            // (hak_op_tail_finish selects like the detect entry points)
+    hak_batch_selection(c, b);                                      // (hak_op_tail_finish selects like the detect entry points)
     return b;
 }
 static int tail_level_ok(hak_ctx* c, int o, int s, const void* h)

@@ -318,7 +318,9 @@ void hak_launch_nms_emit(hipStream_t st, const HakBatch& b, const HakLayout& L, 
     dim3 g1(b.nimg >= 8 ? 128 : 256, b.nimg);
     k_nms_cand<<<g1, 256, 0, st>>>(b.maps, b.map_stride, b.cand, b.cand_cap, b.state, tab, psz, w, h, p,
                                    b.bitmap, words, b.rowcount);
-    if (b.sel.st)                                                   // hak_set_retain_best: an overflowing image keeps its strongest
+    if (b.grid.G > 0)                                               // hak_set_retain_grid: an overflowing image keeps the best of every cell
+        hak_launch_grid_select(st, b, L, max_pts, b.nimg == 2 ? b.cap0 : 0, b.cap1, fast);
+    else if (b.sel.st)                                              // hak_set_retain_best: an overflowing image keeps its strongest
         hak_launch_select(st, b, L, max_pts, b.nimg == 2 ? b.cap0 : 0, b.cap1, fast);
     k_row_scan<<<b.nimg, 256, 0, st>>>(b.rowcount, h, b.state, max_pts, b.nimg == 2 ? b.cap0 : 0, b.cap1, num_out);
     dim3 g3((h + 3) / 4, 1, b.nimg);

@@ -17,19 +17,7 @@
 namespace {
 constexpr int kShift[HAK_SEL_PASSES] = {21, 10, 0};
 constexpr int kWidth[HAK_SEL_PASSES] = {11, 11, 10};
-
-// the order-preserving map of the 32-bit response word: float bits (negative values reversed below the positive ones) or int32
-__device__ __forceinline__ unsigned sel_key(unsigned u, int fast)
-{
-    return fast ? (u ^ 0x80000000u) : ((u >> 31) ? ~u : (u | 0x80000000u));
-}
-
-// the clamp of image img, exactly as k_row_scan computes it
-__device__ __forceinline__ int sel_cap(int img, int max_pts, int cap0, int cap1)
-{
-    return cap0 > 0 ? (img == 0 ? cap0 : cap1) : max_pts;
-}
-}
+}                                               // (sel_key, sel_cap: hak_internal.h, shared with kernels_grid_select.hip)
 
 // survivors of the image vs its clamp; zeroes the image's digit histograms when it selects.  One block per image.
 __global__ __launch_bounds__(256) void k_sel_init(const int* __restrict__ rowcount, int h, int max_pts, int cap0, int cap1,

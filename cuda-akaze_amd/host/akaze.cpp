@@ -107,6 +107,13 @@ namespace akaze
         if (ctx && hak_set_retain_best(ctx, on ? 1 : 0)) die("setRetainBest");
     }
 
+    void Akazer::setRetainGrid(int G)
+    {
+        if (G != 0 && (G < 8 || G > 128)) die("setRetainGrid: the cell size must be 0 or between 8 and 128");
+        retain_grid = G;
+        if (ctx && hak_set_retain_grid(ctx, G)) die("setRetainGrid");
+    }
+
     void Akazer::ensureContext(int w, int h)
     {
         if (ctx && ctx_w == w && ctx_h == h) return;
@@ -114,6 +121,7 @@ namespace akaze
         ctx = nullptr;
         if (hak_create(&cfg, w, h, &ctx)) die("Akazer: hak_create");
         if (retain_best && hak_set_retain_best(ctx, 1)) die("Akazer: hak_set_retain_best");
+        if (retain_grid && hak_set_retain_grid(ctx, retain_grid)) die("Akazer: hak_set_retain_grid");
         ctx_w = w;
         ctx_h = h;
     }

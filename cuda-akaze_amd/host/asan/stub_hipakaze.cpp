@@ -8,7 +8,7 @@
 #include <cstring>
 #include <string>
 
-struct hak_ctx { hak_config cfg; int w, h; int retain_best; };
+struct hak_ctx { hak_config cfg; int w, h; int retain_best; int retain_grid; };
 static std::string g_err;
 int g_live_ctx = 0, g_live_dev = 0, g_live_host = 0;          // leak accounting checked by the driver
 
@@ -30,6 +30,13 @@ int hak_create(const hak_config* cfg, int w, int h, hak_ctx** out)
 }
 void hak_destroy(hak_ctx* c) { if (c) { g_live_ctx--; delete c; } }
 int hak_set_retain_best(hak_ctx* c, int on) { if (!c) { g_err = "null context"; return 1; } c->retain_best = on != 0; return 0; }
+int hak_set_retain_grid(hak_ctx* c, int G)
+{
+    if (!c) { g_err = "null context"; return 1; }
+    if (G != 0 && (G < 8 || G > 128)) { g_err = "cell size out of range"; return 1; }
+    c->retain_grid = G;
+    return 0;
+}
 int hak_host_alloc(void** p, long bytes) { *p = malloc((size_t)bytes); g_live_host += *p != nullptr; return *p ? 0 : 1; }
 int hak_host_free(void* p) { g_live_host--; free(p); return 0; }
 int hak_points_alloc(hak_point** d, int count) { *d = (hak_point*)malloc(sizeof(hak_point) * (size_t)count); g_live_dev++; return *d ? 0 : 1; }

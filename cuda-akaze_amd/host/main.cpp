@@ -3,6 +3,7 @@
 // `nrepeats` times and cuMatch once, and prints the same five result lines.
 //
 //   hipakaze_demo [device] [left.pgm right.pgm] [nrepeats] [--dump file] [--api-checks] [--pair] [--homography] [--retain-best N]
+//                 [--retain-grid G]
 //
 // --dump file   writes the host-side results as raw 104-byte AkazePoint records:
 //               int32 n1, n2, then n1 + n2 records of the float path (image 1 after cuMatch),
@@ -16,6 +17,8 @@
 //               int32 n, int32 inliers, float32 H[9], the n 32-byte hak_match_pair records and the n inlier-mask bytes.
 // --retain-best N  both AkazeData get capacity N (instead of 10000) and Akazer::setRetainBest(true): an image with more keypoints
 //               keeps its N strongest (hak_set_retain_best), in raster order, on the float and the FAST path alike
+// --retain-grid G  Akazer::setRetainGrid(G), G in 8..128: an image with more keypoints than the capacity (N of --retain-best, else
+//               10000) keeps the best of every G x G pixel cell (hak_set_retain_grid); with both options G decides the policy
 #include "akaze.h"
 #include <cmath>
 #include <cstdlib>
@@ -89,7 +92,7 @@ int main(int argc, char** argv)
     std::cout << "===== Registration by HIP-AKAZE (MI355X) =====" << std::endl;
     std::string dumpPath;
     bool apiChecks = false, pairCalls = false, homography = false;
-    int retainBest = 0;
+    int retainBest = 0, retainGrid = 0;
     {   // strip the options; what is left are the reference demo's positional arguments (main.cpp:131-135)
         int n = 1;
         for (int i = 1; i < argc; i++) {
@@ -98,6 +101,7 @@ int main(int argc, char** argv)
             else if (!strcmp(argv[i], "--pair")) pairCalls = true;
             else if (!strcmp(argv[i], "--homography")) homography = true;
             else if (!strcmp(argv[i], "--retain-best") && i + 1 < argc) retainBest = std::atoi(argv[++i]);
+            else if (!strcmp(argv[i], "--retain-grid") && i + 1 < argc) retainGrid = std::atoi(argv[++i]);
             else argv[n++] = argv[i];
         }
         argc = n;
@@ -147,6 +151,7 @@ int main(int argc, char** argv)
     detector->init(whp1, noctaves, max_scale, per, kcontrast, soffset, reordering, derivative_factor, dthreshold, diffusivity,
                    descriptor_pattern_size);
     if (retainBest > 0) detector->setRetainBest(true);
+    if (retainGrid > 0) detector->setRetainGrid(retainGrid);
 
     float t1 = timer.read();
     for (int i = 0; i < nrepeats; i++) {

@@ -50,6 +50,9 @@ namespace akaze
         // an AkazeData that overflows keeps its result.max_pts STRONGEST keypoints (in raster order) instead of the first ones in
         // raster order (hak_set_retain_best); remembered across context re-creation.  Default off.
         void setRetainBest(bool on);
+        // G in 8..128: an AkazeData that overflows keeps the best keypoints of every G x G pixel cell instead (hak_set_retain_grid;
+        // it then decides the policy whatever setRetainBest says); 0 (default): off.  Remembered across context re-creation.
+        void setRetainGrid(int G);
         hak_ctx* context() { return ctx; }
 
     private:
@@ -58,6 +61,7 @@ namespace akaze
         hak_ctx* ctx = nullptr;      // owns the arena (the reference's omem; room for the two images of a pair call), freed in the destructor
         int ctx_w = 0, ctx_h = 0;
         bool retain_best = false;
+        int retain_grid = 0;
         void ensureContext(int w, int h);
     };
 }

@@ -118,6 +118,25 @@ int hak_set_null_order(hak_ctx* ctx, int on);
  * Covers every detect entry point of the context (hak_detect_and_compute, _batch, _pair, hak_fast_detect_and_compute, _batch)
  * and the test ABI's hak_op_tail_finish; takes effect with the next call, allocates nothing and does not synchronise. */
 int hak_set_retain_best(hak_ctx* ctx, int on);
+/* G == 0 (default): off, the context behaves as above, hak_set_retain_best included.  8 <= G <= 128: an image with more NMS
+ * survivors than its clamp spreads the clamp over a grid of square cells of G pixels, so that every region keeps its best points;
+ * while it is on, this replaces both other policies, whatever hak_set_retain_best says.  Any other G: non-zero status and a
+ * message; a null context is refused without touching a device.  The rule, per image with S survivors and clamp C (as above):
+ *   S <= C: the output does not change, byte for byte.
+ *   S >  C: a survivor at the integer full-resolution position (x, y) before refinement lies in cell c = (y / G) * ncx + x / G,
+ *           ncx = ceil(w / G); n_c = survivors of cell c.  Inside a cell and between cells alike survivors rank by K(response
+ *           word) descending, then by the smaller raster index y * w + x (K: the map of hak_set_retain_best).
+ *           1. the quota q is the largest integer >= 0 with sum_c min(n_c, q) <= C;
+ *           2. every cell keeps its min(n_c, q) highest-ranked survivors;
+ *           3. R = C - sum_c min(n_c, q) places remain (R < number of cells with n_c > q);
+ *           4. the candidates for them are the rank-q survivors (0-based) of the cells with n_c > q, one per cell;
+ *           5. the R highest-ranked candidates are kept as well.
+ *           Every cell ends with min(n_c, q) or q + 1 keypoints, exactly C are kept and emitted in raster order -- a subsequence
+ *           of the unclamped output, every record byte-identical to the unclamped call's; num_pts = C.
+ * Refinement, orientation, MLDB and the pair call's match run on the kept set only.  Covers the entry points hak_set_retain_best
+ * covers; takes effect with the next call and does not synchronise; its scratch is allocated by the first call with G > 0 (never
+ * inside a call's launch sequence).  Statement: tests/retain_grid_ref.py; device code: csrc/kernels_grid_select.hip. */
+int hak_set_retain_grid(hak_ctx* ctx, int G);
 
 /* ---- Akazer::detectAndCompute (akaze.h:29, akaze.cpp:101-150), one image,
  * synchronous.  d_image: device float32, pitch elements per row.  d_points:
