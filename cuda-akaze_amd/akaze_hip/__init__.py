@@ -97,6 +97,8 @@ SYMBOLS = {
     "hak_match_knn2_batch": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp]),
     "hak_find_homography": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_float, C.c_uint, C.c_int, _vp, _vp]),
     "hak_find_homography_batch": (C.c_int, [_vp, _vp, C.c_long, _vp, C.c_int, C.c_int, C.c_float, C.c_uint, C.c_int, _vp, _vp]),
+    "hak_match_guided": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _fp, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _ip, _vp]),
+    "hak_match_guided_batch": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp]),
     "hak_points_alloc": (C.c_int, [C.POINTER(_vp), C.c_int]),
     "hak_points_free": (C.c_int, [_vp]),
     "hak_image_alloc": (C.c_int, [C.POINTER(_vp), C.c_int, C.c_int, _ip]),
@@ -502,6 +504,25 @@ def cuMatchKnn(result1, result2, ratio=(1, 1), cross_check=True, max_dist=0, aka
     hptr = result1.h_data.ctypes.data if result1.h_data is not None else None
     check(lib.hak_match_knn2(ctx, result1.d_data, n1, result2.d_data, result2.num_pts, int(ratio[0]), int(ratio[1]),
                              int(cross_check), int(max_dist), hptr, d_out.data_ptr(), C.byref(cnt), h_out.ctypes.data))
+    return h_out[:cnt.value].copy()
+
+
+def cuMatchGuided(result1, result2, H, radius=8.0, ratio=(4, 5), cross_check=True, max_dist=0, akazer=None):
+    """Guided matching (hipakaze.h hak_match_guided): re-matches result1 against result2 under the homography H (9 values, row-major,
+    e.g. findHomography's record["H"]): every query is searched only among the train points within `radius` pixels of where H sends
+    it; ratio test and cross-check inside that neighbourhood.  Updates result1 like cuMatch and returns the accepted matches
+    (MATCH_PAIR_DTYPE, ascending query index)."""
+    import torch
+    ctx = akazer.ctx if akazer is not None else None
+    n1 = result1.num_pts
+    h = np.ascontiguousarray(np.asarray(H, np.float32).reshape(9))
+    d_out = torch.zeros(max(n1, 1) * MATCH_PAIR_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+    h_out = np.zeros(max(n1, 1), MATCH_PAIR_DTYPE)
+    cnt = C.c_int(0)
+    hptr = result1.h_data.ctypes.data if result1.h_data is not None else None
+    check(lib.hak_match_guided(ctx, result1.d_data, n1, result2.d_data, result2.num_pts, h.ctypes.data_as(_fp), float(radius),
+                               int(ratio[0]), int(ratio[1]), int(cross_check), int(max_dist), hptr, d_out.data_ptr(), C.byref(cnt),
+                               h_out.ctypes.data))
     return h_out[:cnt.value].copy()
 
 

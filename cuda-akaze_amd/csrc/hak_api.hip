@@ -322,7 +322,7 @@ extern "C" void hak_destroy(hak_ctx* c)
         for (auto ev : p.ev) (void)hipEventDestroy(ev);
     hak_match_scratch_free(&c->msc);
     void* bufs[] = {c->arena, c->maps, c->bitmap, c->rowcount, c->cand, c->state, c->d_num, c->dtab, c->knn, c->d_cnt, c->perm, c->pair_pts,
-                    c->hom_slots, c->hom_rec, c->sel.st, c->sel.bins, c->sel.tie, c->grid.st, c->grid.count, c->grid.comp};
+                    c->hom_slots, c->hom_rec, c->sel.st, c->sel.bins, c->sel.tie, c->grid.st, c->grid.count, c->grid.comp, c->guided};
     for (void* b : bufs) (void)hipFree(b);
     if (c->h_num) (void)hipHostFree(c->h_num);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -732,6 +732,114 @@ extern "C" int hak_find_homography_batch(hak_ctx* c, const hak_match_pair* d_mat
     hak_launch_homography(c->stream, d_matches, stride, d_counts, 0, npairs, iterations, threshold, seed, refine, c->hom_slots, d_out,
                           d_masks, stride);
     if (hipGetLastError() != hipSuccess) return fail("homography launch failed");
+    return 0;
+}
+
+// ----------------------------------------------------------- guided matching (kernels_guided.hip; the rule: include/hipakaze.h)
+static int guided_args(float radius, int ratio_num, int ratio_den)
+{
+    if (!std::isfinite(radius) || !(radius > 0.f)) return fail("radius must be finite and > 0");
+    if (!std::isfinite(radius * radius)) return fail("radius * radius must be finite in float32");
+    if (ratio_num <= 0 || ratio_den <= 0) return fail("ratio must be a positive fraction");
+    return 0;
+}
+
+// grow-only, outside a launch sequence; a buffer being replaced may still be read by an earlier call on the context's stream
+// (hipFree waits for the device)
+static int guided_scratch(hak_ctx* c, size_t bytes)
+{
+    if (bytes <= c->guided_cap) return 0;
+    if (c->guided) HIP_TRY(hipFree(c->guided));
+    c->guided = nullptr;
+    c->guided_cap = 0;
+    HIP_TRY(hipMalloc(&c->guided, bytes));
+    c->guided_cap = bytes;
+    return 0;
+}
+
+extern "C" int hak_match_guided(hak_ctx* c, hak_point* d_pts1, int n1, const hak_point* d_pts2, int n2, const float* H, float radius,
+                                int ratio_num, int ratio_den, int cross_check, int max_dist, hak_point* h_pts1, hak_match_pair* d_out,
+                                int* count, hak_match_pair* h_out)
+{
+    if (!count) return fail("null argument");
+    if (n1 < 0 || n2 < 0) return fail("negative point count");
+    if ((!d_pts1 && n1 > 0) || (!d_pts2 && n2 > 0)) return fail("null point array");
+    if (!H) return fail("H is NULL");
+    for (int k = 0; k < 9; k++)
+        if (!std::isfinite(H[k])) return fail("H has a non-finite entry");
+    if (guided_args(radius, ratio_num, ratio_den)) return 1;
+    if (h_out && !d_out) return fail("h_out needs d_out");
+    if (n1 >= (1 << 20) || n2 >= (1 << 20)) return fail("more than 2^20 - 1 points");      // keys pack distance << 20 | index
+    *count = 0;
+    if (n1 == 0) return 0;
+    if (max_dist <= 0) max_dist = HAK_MAX_DIST;
+    if (hak_device_count() == 0) return fail("no HIP device: libhipakaze has no CPU fallback");
+    hipStream_t st = c ? c->stream : nullptr;
+    const long cap2 = n2 > 0 ? n2 : 1;
+    const size_t bytes = hak_guided_scratch_bytes(1, cap2);
+    void* buf = nullptr;
+    if (c) {
+        if (guided_scratch(c, bytes)) return 1;
+        buf = c->guided;
+    } else
+        HIP_TRY(hipMalloc(&buf, bytes));
+    HakMatchScratch* sc = c ? &c->msc : pool_acquire();
+    order_after_null_stream(c, st);
+    const int nb = (n1 + 1023) / 1024;
+    if (!hak_match_scratch_reserve(sc, st, 0, 0, 0, (long)n1 + cap2, nb)) {
+        if (!c) { pool_release(sc, false); (void)hipFree(buf); }
+        return fail("hak_match_guided: out of device memory for the search scratch");
+    }
+    int4* fwd = sc->knn;
+    int4* rev = sc->knn + n1;
+    *sc->h_cnt = -1;
+    {
+        ProfScope ps(c, HAK_PROF_MATCH);
+        hak_launch_guided(st, d_pts1, d_pts2, nullptr, nullptr, n1, n2, 0, 0, 1, nullptr, H, radius, cross_check ? 1 : 0,
+                          hak_guided_scratch_carve(buf, 1, cap2, rev, 0), fwd, 0);
+        hak_launch_knn2_finish(st, d_pts1, d_pts2, nullptr, n1, 0, 0, 1, fwd, cross_check ? rev : nullptr, 0, ratio_num, ratio_den,
+                               cross_check ? 1 : 0, max_dist, d_out, 0, sc->d_cnt, sc);
+    }
+    int rc = 0;
+    if (hipGetLastError() != hipSuccess) rc = fail("guided match launch failed");
+    if (!rc && hipStreamSynchronize(st) != hipSuccess) rc = fail("hipStreamSynchronize(guided match)");
+    // the multi-block finish leaves the count in the scratch's pinned word; the one-block finish only in device memory
+    if (!rc && *sc->h_cnt < 0 && hipMemcpy(sc->h_cnt, sc->d_cnt, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) rc = fail("count download");
+    if (!rc) *count = *sc->h_cnt;
+    if (!c) { pool_release(sc, rc == 0); (void)hipFree(buf); }
+    else if (rc) hak_match_scratch_free(sc);
+    if (!rc && h_out && *count > 0 &&
+        hipMemcpy(h_out, d_out, sizeof(hak_match_pair) * (size_t)*count, hipMemcpyDeviceToHost) != hipSuccess)
+        rc = fail("match list download");
+    if (!rc && h_pts1 &&                                                          // akaze.cpp:58-63
+        hipMemcpy2D(&h_pts1[0].match, sizeof(hak_point), &d_pts1[0].match, sizeof(hak_point), 16, n1, hipMemcpyDeviceToHost) != hipSuccess)
+        rc = fail("match field download");
+    return rc;
+}
+
+extern "C" int hak_match_guided_batch(hak_ctx* c, hak_point* d_points, const int* d_num_pts, int npairs, const hak_homography* d_H,
+                                      float radius, int ratio_num, int ratio_den, int cross_check, int max_dist, hak_match_pair* d_out,
+                                      int* d_counts)
+{
+    if (!c) return fail("hak_match_guided_batch needs a context");
+    if (!d_points || !d_num_pts || !d_H || !d_counts || npairs < 1) return fail("bad argument");
+    if (2 * npairs > c->cfg.batch + 1) return fail("npairs exceeds the context's batch capacity");
+    if (guided_args(radius, ratio_num, ratio_den)) return 1;
+    if (max_dist <= 0) max_dist = HAK_MAX_DIST;
+    const long mp = c->cfg.max_pts;
+    if (mp >= (1 << 20)) return fail("max_pts must stay below 2^20 for the matcher");   // keys pack distance << 20 | index
+    if (knn_scratch(c)) return 1;
+    const long npair_cap = (c->cfg.batch + 1) / 2;
+    if (guided_scratch(c, hak_guided_scratch_bytes(npair_cap, mp))) return 1;
+    order_after_null_stream(c, c->stream);
+    int4* fwd = c->knn;
+    int4* rev = c->knn + (size_t)npair_cap * mp;
+    { ProfScope ps(c, HAK_PROF_MATCH);
+      hak_launch_guided(c->stream, d_points, d_points + mp, d_num_pts, d_num_pts + 1, (int)mp, (int)mp, 2 * mp, 2 * mp, npairs, d_H, nullptr,
+                        radius, cross_check ? 1 : 0, hak_guided_scratch_carve(c->guided, npair_cap, mp, rev, mp), fwd, mp);
+      hak_launch_knn2_finish(c->stream, d_points, d_points + mp, d_num_pts, 0, 2 * mp, 2 * mp, npairs, fwd, cross_check ? rev : nullptr,
+                             mp, ratio_num, ratio_den, cross_check ? 1 : 0, max_dist, d_out, mp, d_counts); }
+    if (hipGetLastError() != hipSuccess) return fail("guided match launch failed");
     return 0;
 }
 

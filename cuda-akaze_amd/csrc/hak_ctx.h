@@ -76,6 +76,8 @@ struct hak_ctx {
     unsigned long long* hom_slots = nullptr;  // RANSAC scratch: best key per (pair, score block), grown on demand
     long hom_cap = 0;
     hak_homography* hom_rec = nullptr;        // the record of hak_find_homography before its download
+    void* guided = nullptr;         // guided-matching scratch (kernels_guided.hip): grown on demand, outside a launch sequence
+    size_t guided_cap = 0;
     hak_point* pair_pts = nullptr;  // [2][cfg.max_pts]: the contiguous pair layout hak_detect_and_compute_pair detects into and matches on
     HakMatchScratch msc;            // sliced searches of one big pair (hak_match / hak_match_knn2): grows on demand, on this context's device
     HakKnobs knobs;                 // the HAK_* variables as hak_create found them: THIS context's (two contexts of a process may differ)

@@ -621,6 +621,24 @@ void hak_launch_knn2_finish(hipStream_t st, hak_point* pts1, const hak_point* pt
                             int ratio_den, int cross, int max_dist, hak_match_pair* out, long out_stride, int* out_count,
                             HakMatchScratch* scratch = nullptr);
 
+// guided matching (kernels_guided.hip, hak_match_guided): the scratch of npairs pairs of at most pts_cap train points each.  Owned
+// by a context (grown outside a launch sequence) or allocated for the duration of a call without one; every word a call reads is
+// written earlier in the same call.
+struct HakGuidedScratch {
+    float2* xy = nullptr;                       // [npairs][pts_cap] train coordinates, sorted by cell
+    int* idx = nullptr;                         // [npairs][pts_cap] ... and their indices
+    int* off = nullptr;                         // [npairs][64 * 64 + 1] first list entry of every cell
+    int* grid = nullptr;                        // [npairs][8] the pair's grid: origin, 1 / cell side, cells per axis
+    long pts_cap = 0;
+    int4* rev = nullptr;                        // [npairs][rev_stride] reverse keys, then {rev(j), d, 512, 0} (the 2-NN scratch's reverse half)
+    long rev_stride = 0;
+};
+size_t hak_guided_scratch_bytes(long npairs, long pts_cap);
+HakGuidedScratch hak_guided_scratch_carve(void* base, long npairs, long pts_cap, int4* rev, long rev_stride);
+void hak_launch_guided(hipStream_t st, const hak_point* pts1, const hak_point* pts2, const int* n1_dev, const int* n2_dev, int n1_host,
+                       int n2_host, long stride1, long stride2, int npairs, const hak_homography* d_H, const float* h_H, float radius,
+                       int cross, const HakGuidedScratch& sc, int4* fwd, long fwd_stride);
+
 // RANSAC homography (kernels_homography.hip): score blocks per pair (and hypotheses per block through hp_out); the launcher
 // writes one uint64 slot per (pair, block) to `slots` (npairs * hak_homography_blocks(...) of them)
 int hak_homography_blocks(int npairs, int iterations, int* hp_out);

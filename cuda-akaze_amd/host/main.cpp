@@ -3,7 +3,7 @@
 // `nrepeats` times and cuMatch once, and prints the same five result lines.
 //
 //   hipakaze_demo [device] [left.pgm right.pgm] [nrepeats] [--dump file] [--api-checks] [--pair] [--homography] [--retain-best N]
-//                 [--retain-grid G]
+//                 [--retain-grid G] [--guided R]
 //
 // --dump file   writes the host-side results as raw 104-byte AkazePoint records:
 //               int32 n1, n2, then n1 + n2 records of the float path (image 1 after cuMatch),
@@ -15,6 +15,9 @@
 // --homography  after the 2-NN match, estimates the homography between the two images from its matches (cuFindHomography: RANSAC,
 //               1024 hypotheses, 3 px, seed 0, least-squares refit) and prints it; with --dump, appends at the very end of the file
 //               int32 n, int32 inliers, float32 H[9], the n 32-byte hak_match_pair records and the n inlier-mask bytes.
+// --guided R   implies --homography; after RANSAC re-matches the pair under that homography (cuMatchGuided: every keypoint of image 1
+//               is searched only within R pixels of where H sends it; ratio 4/5 + cross-check inside that neighbourhood), runs
+//               cuFindHomography again on the guided list and prints both match and inlier counts
 // --retain-best N  both AkazeData get capacity N (instead of 10000) and Akazer::setRetainBest(true): an image with more keypoints
 //               keeps its N strongest (hak_set_retain_best), in raster order, on the float and the FAST path alike
 // --retain-grid G  Akazer::setRetainGrid(G), G in 8..128: an image with more keypoints than the capacity (N of --retain-best, else
@@ -93,6 +96,7 @@ int main(int argc, char** argv)
     std::string dumpPath;
     bool apiChecks = false, pairCalls = false, homography = false;
     int retainBest = 0, retainGrid = 0;
+    float guided = 0.f;
     {   // strip the options; what is left are the reference demo's positional arguments (main.cpp:131-135)
         int n = 1;
         for (int i = 1; i < argc; i++) {
@@ -100,6 +104,7 @@ int main(int argc, char** argv)
             else if (!strcmp(argv[i], "--api-checks")) apiChecks = true;
             else if (!strcmp(argv[i], "--pair")) pairCalls = true;
             else if (!strcmp(argv[i], "--homography")) homography = true;
+            else if (!strcmp(argv[i], "--guided") && i + 1 < argc) { guided = (float)std::atof(argv[++i]); homography = true; }
             else if (!strcmp(argv[i], "--retain-best") && i + 1 < argc) retainBest = std::atoi(argv[++i]);
             else if (!strcmp(argv[i], "--retain-grid") && i + 1 < argc) retainGrid = std::atoi(argv[++i]);
             else argv[n++] = argv[i];
@@ -194,6 +199,18 @@ int main(int argc, char** argv)
                   << std::endl;
         for (int r = 0; r < 3; r++)
             std::cout << "  [" << hom[3 * r] << ", " << hom[3 * r + 1] << ", " << hom[3 * r + 2] << "]" << std::endl;
+    }
+    if (guided > 0.f) {
+        std::vector<hak_match_pair> gm(good.size());
+        float t8 = timer.read();
+        const int nguided = akaze::cuMatchGuided(akaze_data1, akaze_data2, hom, gm.data(), guided, 4, 5, true);
+        float t9 = timer.read();
+        std::cout << "Guided matches (radius " << guided << " px, ratio 0.8 + cross-check): " << nguided << " against " << ngood
+                  << " of the 2-NN match  (" << t9 - t8 << " ms)" << std::endl;
+        float hom2[9];
+        const int ninlier2 = akaze::cuFindHomography(gm.data(), nguided, hom2);
+        std::cout << "Homography of the guided matches: " << ninlier2 << " inliers of " << nguided << " against " << ninlier << " of "
+                  << ngood << std::endl;
     }
 
     // ---- the reference's second demo (main.cpp:227-300): the integer FAST path on the uint8 images

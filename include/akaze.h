@@ -26,6 +26,13 @@ namespace akaze
     int cuFindHomography(const hak_match_pair* matches, int n, float H[9], unsigned char* inlier_mask = nullptr, int iterations = 1024,
                          float threshold = 3.f, unsigned seed = 0, bool refine = true);
 
+    // build-side addition: guided matching (hak_match_guided) -- re-matches result1 against result2 under a homography H (row-major,
+    // (x1, y1, 1) -> image 2, e.g. cuFindHomography's): every keypoint of result1 is searched only among the keypoints of result2
+    // within `radius` pixels of where H sends it, ratio test and cross-check inside that neighbourhood.  Fills result1 like cuMatch
+    // and returns the accepted matches in query order (host array `matches`, capacity >= result1.num_pts; may be NULL to only count).
+    int cuMatchGuided(AkazeData& result1, AkazeData& result2, const float H[9], hak_match_pair* matches, float radius = 8.f,
+                      int ratio_num = 4, int ratio_den = 5, bool cross_check = true);
+
     class Akazer
     {
     public:

@@ -250,6 +250,41 @@ int hak_find_homography_batch(hak_ctx* ctx, const hak_match_pair* d_matches, lon
                               int iterations, float threshold, unsigned seed, int refine, hak_homography* d_out,
                               unsigned char* d_masks);
 
+/* ---- guided matching: re-match a pair under its estimated homography (build-side addition; the stage behind
+ * hak_find_homography).  The 2-NN search of hak_match_knn2 looks at the whole other image, so on repetitive texture its ratio
+ * test rejects correct matches that lose to a look-alike elsewhere; once H is known, each query is searched only among the train
+ * points near where H sends it.  A pure function of its arguments -- in particular it does not depend on how the implementation
+ * bins the points; tests/guided_match_ref.py is its bit-exact numpy statement.
+ *   Projection of query i, float32, no FMA, (x, y) = pts1[i].x, .y:
+ *      wz = (h6 x + h7 y) + h8, u = (h0 x + h1 y) + h2, v = (h3 x + h4 y) + h5, px = u / wz, py = v / wz (correctly rounded).
+ *   Gate G(i, j): wz > 0 and, with dx = x2_j - px, dy = y2_j - py, (dx dx) + (dy dy) < r2, r2 = radius * radius in float32.
+ *      Any NaN makes the comparison false: a record with a non-finite coordinate, or a non-finite projection, is in no gate.
+ *   Distance d(i, j): the Hamming distance of hak_match_knn2 (the 61 descriptor bytes).
+ *   Forward: J_i = { j : G(i, j) }; j1 = the member of J_i with the smallest d, ties to the smallest j; d1 = d(i, j1);
+ *      d2 = the smallest d over J_i \ {j1}, 512 when there is none.
+ *   Reverse: I_j = { i : G(i, j) } -- the same gate, no inverse projection; rev(j) = the member of I_j with the smallest d, ties to
+ *      the smallest i.
+ *   Accept query i iff J_i is not empty and d1 < max_dist and d1 * ratio_den < d2 * ratio_num (64-bit products)
+ *      and (cross_check == 0 or rev(j1) == i).
+ *   Outputs as hak_match_knn2: match / distance / match_x / match_y of an accepted query, -1 / -1 / -1.f / -1.f of a rejected one
+ *      (copied to h_pts1 when given); the accepted matches in ascending query order to d_out (capacity >= n1; may be NULL) with
+ *      second = d2; *count their number; h_out (needs d_out) receives the list as well.
+ * Synchronous; ctx may be NULL (default stream, scratch allocated for the call).  H: 9 floats on the HOST, row-major.
+ * max_dist <= 0 selects 96.  Refused with a non-zero status and a message before any device is touched: radius not finite or
+ * not > 0, radius * radius not finite in float32, H NULL or with a non-finite entry, a negative count, a ratio term <= 0, a NULL
+ * point array with a positive count.  Fewer than 2^20 points per side.  Device code: csrc/kernels_guided.hip. */
+int hak_match_guided(hak_ctx* ctx, hak_point* d_pts1, int n1, const hak_point* d_pts2, int n2,
+                     const float H[9] /* host */, float radius, int ratio_num, int ratio_den, int cross_check,
+                     int max_dist, hak_point* h_pts1, hak_match_pair* d_out, int* count, hak_match_pair* h_out);
+/* batched over the pairs of a detect batch, layouts and outputs as hak_match_knn2_batch; asynchronous on the context's stream.
+ * H of pair k is read ON THE DEVICE from d_H[k], the record hak_find_homography_batch wrote: the chain detect batch ->
+ * hak_match_knn2_batch -> hak_find_homography_batch -> hak_match_guided_batch needs no host synchronisation.  A pair whose
+ * record has hypothesis < 0 or a non-finite entry of H has no model: count 0, every query rejected.  A NULL context is refused. */
+int hak_match_guided_batch(hak_ctx* ctx, hak_point* d_points, const int* d_num_pts, int npairs,
+                           const hak_homography* d_H /* device, one per pair */, float radius,
+                           int ratio_num, int ratio_den, int cross_check, int max_dist,
+                           hak_match_pair* d_out, int* d_counts);
+
 /* ---- memory helpers: initAkazeData/freeAkazeData (akaze.cpp:26-52) and the
  * image upload of main.cpp:172-188 */
 int hak_points_alloc(hak_point** d_points, int count);
