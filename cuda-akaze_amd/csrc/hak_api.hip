@@ -515,6 +515,31 @@ void pool_release(HakMatchScratch* sc, bool ok)
 }
 }
 
+// the 16 match bytes (match, distance, match_x, match_y) of n1 device records -> the host records, as akaze.cpp:58-63
+static int download_match_fields(hak_point* h_pts1, const hak_point* d_pts1, int n1)
+{
+    HIP_TRY(hipMemcpy2D(&h_pts1[0].match, sizeof(hak_point), &d_pts1[0].match, sizeof(hak_point), 16, n1,
+                        hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// The tail of a single-pair call that returns a match list (hak_match_knn2, hak_match_guided), behind its synchronisation: the
+// count, the scratch back to its owner, the list and the match fields to the host.  rc: the call's state so far.
+static int match_list_tail(hak_ctx* c, HakMatchScratch* sc, int rc, hak_point* h_pts1, const hak_point* d_pts1, int n1,
+                           const hak_match_pair* d_out, int* count, hak_match_pair* h_out)
+{
+    // the multi-block finish leaves the count in the scratch's pinned word; the one-block finish only in device memory
+    if (!rc && *sc->h_cnt < 0 && hipMemcpy(sc->h_cnt, sc->d_cnt, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) rc = fail("count download");
+    if (!rc) *count = *sc->h_cnt;
+    if (!c) pool_release(sc, rc == 0);
+    else if (rc) hak_match_scratch_free(sc);
+    if (!rc && h_out && *count > 0 &&
+        hipMemcpy(h_out, d_out, sizeof(hak_match_pair) * (size_t)*count, hipMemcpyDeviceToHost) != hipSuccess)
+        rc = fail("match list download");
+    if (!rc && h_pts1 && download_match_fields(h_pts1, d_pts1, n1)) rc = fail("match field download");      // (names the step, as before)
+    return rc;
+}
+
 // One PAIR per call (include/hipakaze.h): both images through ONE launch sequence (the batch path with two images: every launch
 // covers both), the match appended, the records scattered to the caller's arrays by one more kernel, ONE synchronisation --
 // instead of the three synchronous calls of main.cpp:201-209 (43 + 43 + 1 launches, three waits).
@@ -527,7 +552,7 @@ extern "C" int hak_detect_and_compute_pair(hak_ctx* c, const float* d_image1, co
     if (max_pts1 < 1 || max_pts2 < 1) return fail("max_pts < 1");
     if (pitch < c->L.oct[0].w) return fail("pitch smaller than width");
     const long mp = c->cfg.max_pts;
-    if (mp >= (1 << 20)) return fail("max_pts must stay below 2^20 for the matcher");
+    if (!hak_mkey_fits(mp)) return fail("max_pts must stay below 2^20 for the matcher");
     if (!c->pair_pts) HIP_TRY(hipMalloc((void**)&c->pair_pts, sizeof(hak_point) * 2 * (size_t)mp));
     // each image keeps its own clamp, as in the three calls (setMaxNumPoints(result.max_pts), akaze.cpp:246, 451), bounded by the
     // context's max_pts -- the record stride of the pair buffer, which every kernel of the sequence and the matcher index with
@@ -557,7 +582,7 @@ extern "C" int hak_match(hak_ctx* c, hak_point* d_pts1, int n1, const hak_point*
     // ctx may be NULL (cuMatch is a free function in the reference): default stream, no profiling
     if (!d_pts1 || (!d_pts2 && n2 > 0)) return fail("null argument");
     if (n1 <= 0) return 0;
-    if (n2 >= (1 << 20)) return fail("more than 2^20 - 1 train points");         // k_match packs distance << 20 | index
+    if (!hak_mkey_fits(n2)) return fail("more than 2^20 - 1 train points");      // the packed key (hak_mkey, hak_internal.h)
     // one big pair takes the sliced search (kernels_match.hip), whose scratch belongs to the context (its device) or, without
     // one, comes from the per-device pool above for the duration of the call -- no process-wide buffer
     hipStream_t st = c ? c->stream : nullptr;
@@ -573,17 +598,14 @@ extern "C" int hak_match(hak_ctx* c, hak_point* d_pts1, int n1, const hak_point*
     if (!c) pool_release(sc, rc == 0);
     else if (rc) hak_match_scratch_free(sc);
     if (rc) return rc;
-    if (h_pts1)                                                                   // akaze.cpp:58-63
-        HIP_TRY(hipMemcpy2D(&h_pts1[0].match, sizeof(hak_point), &d_pts1[0].match, sizeof(hak_point), 16, n1,
-                            hipMemcpyDeviceToHost));
-    return 0;
+    return h_pts1 ? download_match_fields(h_pts1, d_pts1, n1) : 0;
 }
 
 extern "C" int hak_match_batch(hak_ctx* c, hak_point* d_points, const int* d_num_pts, int npairs)
 {
     if (!c || !d_points || !d_num_pts || npairs < 1) return fail("bad argument");
     const long mp = c->cfg.max_pts;
-    if (mp >= (1 << 20)) return fail("max_pts must stay below 2^20 for the matcher");   // k_match packs distance << 20 | index
+    if (!hak_mkey_fits(mp)) return fail("max_pts must stay below 2^20 for the matcher");
     order_after_null_stream(c, c->stream);
     { ProfScope ps(c, HAK_PROF_MATCH);
       hak_launch_match(c->stream, d_points, d_points + mp, d_num_pts, d_num_pts + 1, (int)mp, (int)mp, 2 * mp, 2 * mp, npairs, &c->msc); }
@@ -631,18 +653,7 @@ extern "C" int hak_match_knn2(hak_ctx* c, hak_point* d_pts1, int n1, const hak_p
     int rc = 0;
     if (hipGetLastError() != hipSuccess) rc = fail("knn2 launch failed");
     if (!rc && hipStreamSynchronize(st) != hipSuccess) rc = fail("sync");
-    // the multi-block finish leaves the count in the scratch's pinned word; the one-block finish only in device memory
-    if (!rc && *sc->h_cnt < 0 && hipMemcpy(sc->h_cnt, sc->d_cnt, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) rc = fail("count download");
-    if (!rc) *count = *sc->h_cnt;
-    if (!c) pool_release(sc, rc == 0);
-    else if (rc) hak_match_scratch_free(sc);
-    if (!rc && h_out && *count > 0 &&
-        hipMemcpy(h_out, d_out, sizeof(hak_match_pair) * (size_t)*count, hipMemcpyDeviceToHost) != hipSuccess)
-        rc = fail("match list download");
-    if (!rc && h_pts1 &&                                                          // akaze.cpp:58-63
-        hipMemcpy2D(&h_pts1[0].match, sizeof(hak_point), &d_pts1[0].match, sizeof(hak_point), 16, n1, hipMemcpyDeviceToHost) != hipSuccess)
-        rc = fail("match field download");
-    return rc;
+    return match_list_tail(c, sc, rc, h_pts1, d_pts1, n1, d_out, count, h_out);
 }
 
 extern "C" int hak_match_knn2_batch(hak_ctx* c, hak_point* d_points, const int* d_num_pts, int npairs, int ratio_num,
@@ -769,7 +780,7 @@ extern "C" int hak_match_guided(hak_ctx* c, hak_point* d_pts1, int n1, const hak
         if (!std::isfinite(H[k])) return fail("H has a non-finite entry");
     if (guided_args(radius, ratio_num, ratio_den)) return 1;
     if (h_out && !d_out) return fail("h_out needs d_out");
-    if (n1 >= (1 << 20) || n2 >= (1 << 20)) return fail("more than 2^20 - 1 points");      // keys pack distance << 20 | index
+    if (!hak_mkey_fits(n1) || !hak_mkey_fits(n2)) return fail("more than 2^20 - 1 points");
     *count = 0;
     if (n1 == 0) return 0;
     if (max_dist <= 0) max_dist = HAK_MAX_DIST;
@@ -803,17 +814,8 @@ extern "C" int hak_match_guided(hak_ctx* c, hak_point* d_pts1, int n1, const hak
     int rc = 0;
     if (hipGetLastError() != hipSuccess) rc = fail("guided match launch failed");
     if (!rc && hipStreamSynchronize(st) != hipSuccess) rc = fail("hipStreamSynchronize(guided match)");
-    // the multi-block finish leaves the count in the scratch's pinned word; the one-block finish only in device memory
-    if (!rc && *sc->h_cnt < 0 && hipMemcpy(sc->h_cnt, sc->d_cnt, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) rc = fail("count download");
-    if (!rc) *count = *sc->h_cnt;
-    if (!c) { pool_release(sc, rc == 0); (void)hipFree(buf); }
-    else if (rc) hak_match_scratch_free(sc);
-    if (!rc && h_out && *count > 0 &&
-        hipMemcpy(h_out, d_out, sizeof(hak_match_pair) * (size_t)*count, hipMemcpyDeviceToHost) != hipSuccess)
-        rc = fail("match list download");
-    if (!rc && h_pts1 &&                                                          // akaze.cpp:58-63
-        hipMemcpy2D(&h_pts1[0].match, sizeof(hak_point), &d_pts1[0].match, sizeof(hak_point), 16, n1, hipMemcpyDeviceToHost) != hipSuccess)
-        rc = fail("match field download");
+    rc = match_list_tail(c, sc, rc, h_pts1, d_pts1, n1, d_out, count, h_out);
+    if (!c) (void)hipFree(buf);
     return rc;
 }
 
@@ -827,7 +829,7 @@ extern "C" int hak_match_guided_batch(hak_ctx* c, hak_point* d_points, const int
     if (guided_args(radius, ratio_num, ratio_den)) return 1;
     if (max_dist <= 0) max_dist = HAK_MAX_DIST;
     const long mp = c->cfg.max_pts;
-    if (mp >= (1 << 20)) return fail("max_pts must stay below 2^20 for the matcher");   // keys pack distance << 20 | index
+    if (!hak_mkey_fits(mp)) return fail("max_pts must stay below 2^20 for the matcher");
     if (knn_scratch(c)) return 1;
     const long npair_cap = (c->cfg.batch + 1) / 2;
     if (guided_scratch(c, hak_guided_scratch_bytes(npair_cap, mp))) return 1;

@@ -591,12 +591,126 @@ int hak_launch_gather_probe(long bytes, int blocks, int per_lane, int iters, dou
 int hak_launch_stream_probe(int w, int h, int nimg, int nwrite, int warm, int iters, double* ms, double* bytes);
 int hak_launch_hess_probe(int w, int h, int nimg, int step, int iters, double* ms, double* bytes);
 
+// 1-D grids of looping blocks: at least one block, at most 4096
+static inline int hak_grid_x(int blocks) { return blocks < 1 ? 1 : blocks > 4096 ? 4096 : blocks; }
+
+// ---- the matcher's rules (cuMatch / gHammingMatch akazed.cu:2144-2223 and the 2-NN post-processing), stated once for
+// every kernel of kernels_match.hip and kernels_guided.hip: the packed key, the descriptor words, the record a search leaves and the
+// two accept rules with the fields they write are defined here and nowhere else.
+// packed key: Hamming distance << 20 | point index.  An unsigned minimum keeps the smallest distance and, among equal distances,
+// the smallest index -- the reference's "first strict minimum in ascending order" (akazed.cu:2176-2187).
+#define HAK_MKEY_BITS 20                        // index bits: a set holds fewer than 2^20 points
+#define HAK_MKEY_EMPTY 0xFFFFFFFFu              // no candidate
+static inline bool hak_mkey_fits(long n) { return n < (1L << HAK_MKEY_BITS); }      // the bound the entry points check
+__device__ __forceinline__ unsigned hak_mkey(unsigned dist, unsigned index) { return (dist << HAK_MKEY_BITS) | index; }
+__device__ __forceinline__ unsigned hak_mkey_dist(unsigned k) { return k >> HAK_MKEY_BITS; }
+__device__ __forceinline__ int hak_mkey_index(unsigned k) { return (int)(k & ((1u << HAK_MKEY_BITS) - 1u)); }
+// the two smallest keys of a stream: best <= sec after every update
+__device__ __forceinline__ void hak_mkey_two_smallest(unsigned& best, unsigned& sec, unsigned key)
+{
+    sec = min(sec, max(best, key));
+    best = min(best, key);
+}
+// descriptor as 16 dwords: exactly the 61 feature bytes (D9: the reference reads 3 bytes past them).  Features start at byte 24 of
+// the 104-byte record: 4-byte aligned; of the last dword byte 60 only -- bytes 61..63 are struct padding
+__device__ __forceinline__ void hak_desc_load(const hak_point* p, unsigned int d[16])
+{
+    const unsigned int* f = reinterpret_cast<const unsigned int*>(p->features);
+#pragma unroll
+    for (int i = 0; i < 15; i++) d[i] = f[i];
+    d[15] = f[15] & 0xFFu;
+}
+// v_bcnt_u32_b32 computes popcount(x) + acc in ONE instruction; left to itself the compiler takes sixteen plain popcounts
+// and rebuilds the sum as a tree of v_add3 (7 extra instructions per distance)
+__device__ __forceinline__ unsigned hak_bcnt_acc(unsigned x, unsigned acc)
+{
+    unsigned r;
+    asm("v_bcnt_u32_b32 %0, %1, %2" : "=v"(r) : "v"(x), "v"(acc));
+    return r;
+}
+// 2-NN result record of one query from its two smallest keys: {j1, d1, d2, 0}; 512 stands for a missing second neighbour (the
+// initial score of the reference's gMatch, akazed.cu:2028-2122), {-1, 512, 512, 0} for a query without a candidate
+#define HAK_KNN_NO_DIST 512
+__device__ __forceinline__ int4 hak_knn_none() { return make_int4(-1, HAK_KNN_NO_DIST, HAK_KNN_NO_DIST, 0); }
+__device__ __forceinline__ int4 hak_knn_record(unsigned k1, unsigned k2)
+{
+    if (k1 == HAK_MKEY_EMPTY) return hak_knn_none();
+    return make_int4(hak_mkey_index(k1), (int)hak_mkey_dist(k1), k2 == HAK_MKEY_EMPTY ? HAK_KNN_NO_DIST : (int)hak_mkey_dist(k2), 0);
+}
+// match fields of a query record (akaze.cpp:58-63 downloads these 16 bytes): accepted -> the train point, rejected -> -1
+__device__ __forceinline__ void hak_match_store(hak_point* p1, const hak_point* __restrict__ pts2, bool ok, int bi, int dist)
+{
+    if (ok) {
+        p1->match = bi;
+        p1->distance = dist;
+        p1->match_x = pts2[bi].x;
+        p1->match_y = pts2[bi].y;
+    } else {
+        p1->match = -1;
+        p1->distance = -1;
+        p1->match_x = -1.f;
+        p1->match_y = -1.f;
+    }
+}
+// accept rule of gHammingMatch (akazed.cu:2190-2223): the train set is split into 16 residue classes j mod 16, each keeps its
+// first strict minimum, and the match is accepted iff exactly ONE class attains the global minimum distance (akazed.cu:2206)
+// and that distance is < HAK_MAX_DIST (akazed.cu:2223).  kmin: the smallest key; attain: the classes that attain its distance.
+// (the clamp of the index never changes it: belt and braces for the gather)
+__device__ __forceinline__ void hak_match_decide(hak_point* p1, const hak_point* __restrict__ pts2, int n2, unsigned kmin, int attain)
+{
+    const int dmin = (int)hak_mkey_dist(kmin);
+    const bool ok = kmin != HAK_MKEY_EMPTY && attain == 1 && dmin < HAK_MAX_DIST;
+    hak_match_store(p1, pts2, ok, min(hak_mkey_index(kmin), max(n2 - 1, 0)), dmin);
+}
+// ... from a query's 16 class minima: distances only decide -- the rule compares class minima, not indices, and ties between
+// classes never matter for the result (they reject).  cls(t): the key of class t
+template <typename F>
+__device__ __forceinline__ void hak_match_decide_classes(hak_point* p1, const hak_point* __restrict__ pts2, int n2, F cls)
+{
+    unsigned kmin = cls(0);
+#pragma unroll
+    for (int t = 1; t < 16; t++)
+        if (hak_mkey_dist(cls(t)) < hak_mkey_dist(kmin)) kmin = cls(t);
+    int attain = 0;
+#pragma unroll
+    for (int t = 0; t < 16; t++) attain += hak_mkey_dist(cls(t)) == hak_mkey_dist(kmin) ? 1 : 0;
+    hak_match_decide(p1, pts2, n2, kmin, attain);
+}
+// ... from the slices' summaries {smallest key, mask of the classes that attain its distance}: one more summary into (K, M)
+__device__ __forceinline__ void hak_match_merge_slice(unsigned& K, unsigned& M, unsigned k2, unsigned m2)
+{
+    if (hak_mkey_dist(k2) < hak_mkey_dist(K)) M = m2;          // a smaller distance: its classes alone attain it
+    else if (hak_mkey_dist(k2) == hak_mkey_dist(K)) M |= m2;
+    K = min(K, k2);
+}
+// 2-NN accept rule of query i: a candidate, d1 < max_dist, the ratio test d1 / d2 < ratio_num / ratio_den and,
+// cross != 0, rev(j1) == i.  f: the query's search record ({-1, 512, 512, 0} past n1)
+__device__ __forceinline__ bool hak_knn2_rule(const int i, const int n1, const int4* __restrict__ fwd, const int4* __restrict__ rev,
+                                              const int ratio_num, const int ratio_den, const int cross, const int max_dist, int4& f)
+{
+    f = hak_knn_none();
+    if (i >= n1) return false;
+    f = fwd[i];
+    bool ok = f.x >= 0 && f.y < max_dist && (long)f.y * ratio_den < (long)f.z * ratio_num;
+    if (ok && cross) ok = rev[f.x].x == i;
+    return ok;
+}
+// the list entry of an accepted query
+__device__ __forceinline__ hak_match_pair hak_knn2_pair(int i, const int4 f, const hak_point* pts1, const hak_point* __restrict__ pts2)
+{
+    hak_match_pair r;
+    r.query = i; r.train = f.x; r.distance = f.y; r.second = f.z;
+    r.x1 = pts1[i].x; r.y1 = pts1[i].y; r.x2 = pts2[f.x].x; r.y2 = pts2[f.x].y;
+    return r;
+}
+
 // matcher (kernels_match.hip)
 // Scratch of the SLICED searches (one big pair through hak_match / hak_match_knn2, e.g. 10k x 10k: the train set is cut into
 // slices so that the query blocks x slices fill the chip).  Owned by a context or handed out by the per-device pool of
 // hak_api.hip (ctx == NULL: cuMatch is a free function in the reference); lives on one device, used by one call at a time.
-// Invariant between calls: every key is 0xFFFFFFFF and every ticket 0 -- the kernels restore that themselves (the block that
-// draws a query block's last ticket reads the merged keys with exchanges and resets the ticket), so no call starts with a memset.
+// Invariant between calls: every key is HAK_MKEY_EMPTY and every ticket 0 -- the kernels restore that themselves (k_match_finish
+// writes the empty key back over every key it reads; the block that draws a query block's last ticket resets the ticket; the
+// slices' summaries in `part` are plain stores with no initial state), so no call starts with a memset.
 struct HakMatchScratch {
     unsigned* keys = nullptr; long keys_cap = 0;        // [queries][16] class minima, merged with atomicMin          (1-NN)
     int* ticket = nullptr; long ticket_cap = 0;         // [query blocks of 128]

@@ -8,8 +8,8 @@
 //                    counters live in LDS -> histogram, exclusive scan, scatter of {index, x, y} into a list sorted by cell;
 //                    it also resets the pair's reverse keys
 //   k_guided_search  one query per thread: projection, the cells its gate can reach, the exact gate on every listed candidate,
-//                    16 x (v_xor, v_bcnt) per passer; the two smallest packed keys (d << 20 | j) give j1, d1, d2, and an
-//                    atomicMin of (d << 20 | i) on the train point's word gives rev(j) in the same pass
+//                    16 x (v_xor, v_bcnt) per passer; the two smallest packed keys (hak_mkey(d, j), hak_internal.h) give j1, d1, d2,
+//                    and an atomicMin of hak_mkey(d, i) on the train point's word gives rev(j) in the same pass
 //   k_guided_rev     reverse keys -> indices, the form k_knn2_finish reads
 // The accept rule and the compaction are the 2-NN matcher's own finish kernels (kernels_match.hip), unchanged.
 //
@@ -34,20 +34,6 @@
 #define GD_THREADS 1024          // k_guided_bin's block
 #define GD_BOX 1048576.f         // |coordinate| beyond 2^20 does not stretch the box (such points sit in border cells)
 
-// same descriptor words as the matcher's load_desc: the 61 feature bytes as aligned dwords, byte 60 alone of the last
-__device__ __forceinline__ void gd_load_desc(const hak_point* p, unsigned int d[16])
-{
-    const unsigned int* f = reinterpret_cast<const unsigned int*>(p->features);
-#pragma unroll
-    for (int i = 0; i < 15; i++) d[i] = f[i];
-    d[15] = f[15] & 0xFFu;
-}
-__device__ __forceinline__ unsigned gd_bcnt_acc(unsigned x, unsigned acc)
-{
-    unsigned r;
-    asm("v_bcnt_u32_b32 %0, %1, %2" : "=v"(r) : "v"(x), "v"(acc));
-    return r;
-}
 // non-decreasing in x for inv > 0; NaN lands in cell 0 (fmaxf drops it): listed there, and in no gate
 __device__ __forceinline__ int gd_cell(float x, float o, float inv, int n)
 {
@@ -85,7 +71,7 @@ __global__ __launch_bounds__(GD_THREADS) void k_guided_bin(const hak_point* __re
         if (fabsf(x) <= GD_BOX && fabsf(y) <= GD_BOX) {               // (false for NaN and inf)
             x0 = fminf(x0, x); x1 = fmaxf(x1, x); y0 = fminf(y0, y); y1 = fmaxf(y1, y);
         }
-        rev[j] = make_int4(-1, 512, 512, 0);                          // .x: the reverse key, 0xFFFFFFFF = no query gates this point
+        rev[j] = hak_knn_none();                                      // .x: the reverse key, HAK_MKEY_EMPTY = no query gates this point
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
@@ -182,11 +168,11 @@ __global__ __launch_bounds__(256) void k_guided_search(const hak_point* __restri
         const float u = (hr.H[0] * x + hr.H[1] * y) + hr.H[2];
         const float v = (hr.H[3] * x + hr.H[4] * y) + hr.H[5];
         const float px = u / wz, py = v / wz;
-        unsigned best = 0xFFFFFFFFu, second = 0xFFFFFFFFu;
+        unsigned best = HAK_MKEY_EMPTY, second = HAK_MKEY_EMPTY;
         // a non-finite projection is in no gate (every compare below would be false): it does not search
         if (model && wz > 0.f && fabsf(px) < INFINITY && fabsf(py) < INFINITY) {
             unsigned int qd[16];
-            gd_load_desc(pts1 + i, qd);
+            hak_desc_load(pts1 + i, qd);
             const int cx0 = gd_cell(px - rp, g.ox, g.inv, g.nx), cx1 = gd_cell(px + rp, g.ox, g.inv, g.nx);
             const int cy0 = gd_cell(py - rp, g.oy, g.inv, g.ny), cy1 = gd_cell(py + rp, g.oy, g.inv, g.ny);
             for (int cy = cy0; cy <= cy1; cy++) {
@@ -198,20 +184,17 @@ __global__ __launch_bounds__(256) void k_guided_search(const hak_point* __restri
                     if ((dx * dx) + (dy * dy) < r2) {                                  // the exact gate
                         const int j = idx[k];
                         unsigned int td[16];
-                        gd_load_desc(pts2 + j, td);
+                        hak_desc_load(pts2 + j, td);
                         unsigned d = 0;
 #pragma unroll
-                        for (int w = 0; w < 16; w++) d = gd_bcnt_acc(qd[w] ^ td[w], d);
-                        const unsigned key = (d << 20) | (unsigned)j;
-                        second = min(second, max(best, key));
-                        best = min(best, key);
-                        if (cross) atomicMin(reinterpret_cast<unsigned*>(&rev[j].x), (d << 20) | (unsigned)i);
+                        for (int w = 0; w < 16; w++) d = hak_bcnt_acc(qd[w] ^ td[w], d);
+                        hak_mkey_two_smallest(best, second, hak_mkey(d, (unsigned)j));
+                        if (cross) atomicMin(reinterpret_cast<unsigned*>(&rev[j].x), hak_mkey(d, (unsigned)i));
                     }
                 }
             }
         }
-        fwd[i] = best == 0xFFFFFFFFu ? make_int4(-1, 512, 512, 0)
-                                     : make_int4((int)(best & 0xFFFFFu), (int)(best >> 20), second == 0xFFFFFFFFu ? 512 : (int)(second >> 20), 0);
+        fwd[i] = hak_knn_record(best, second);
     }
 }
 
@@ -223,7 +206,7 @@ __global__ __launch_bounds__(256) void k_guided_rev(const int* __restrict__ n2_d
     int4* rev = sc.rev + (long)pair * sc.rev_stride;
     for (int j = blockIdx.x * 256 + threadIdx.x; j < n2; j += gridDim.x * 256) {
         const unsigned key = (unsigned)rev[j].x;
-        if (key != 0xFFFFFFFFu) rev[j] = make_int4((int)(key & 0xFFFFFu), (int)(key >> 20), 512, 0);
+        if (key != HAK_MKEY_EMPTY) rev[j] = hak_knn_record(key, HAK_MKEY_EMPTY);
     }
 }
 
@@ -258,15 +241,7 @@ void hak_launch_guided(hipStream_t st, const hak_point* pts1, const hak_point* p
     if (!d_H)
         for (int k = 0; k < 9; k++) hv.H[k] = h_H[k];
     k_guided_bin<<<npairs, GD_THREADS, 0, st>>>(pts2, n2_dev, n2_host, stride2, 2, rp, sc);
-    int gx = (n1_host + 255) / 256;
-    if (gx < 1) gx = 1;
-    if (gx > 4096) gx = 4096;
-    k_guided_search<<<dim3(gx, npairs), 256, 0, st>>>(pts1, pts2, n1_dev, n1_host, stride1, stride2, 2, d_H, hv, rp, r2, cross, sc, fwd,
-                                                      fwd_stride);
-    if (cross) {
-        int gr = (n2_host + 255) / 256;
-        if (gr < 1) gr = 1;
-        if (gr > 4096) gr = 4096;
-        k_guided_rev<<<dim3(gr, npairs), 256, 0, st>>>(n2_dev, n2_host, 2, sc);
-    }
+    k_guided_search<<<dim3(hak_grid_x((n1_host + 255) / 256), npairs), 256, 0, st>>>(pts1, pts2, n1_dev, n1_host, stride1, stride2, 2, d_H, hv,
+                                                                                      rp, r2, cross, sc, fwd, fwd_stride);
+    if (cross) k_guided_rev<<<dim3(hak_grid_x((n2_host + 255) / 256), npairs), 256, 0, st>>>(n2_dev, n2_host, 2, sc);
 }

@@ -10,10 +10,11 @@
 //
 // Two kernels with identical results: k_match_mfma (the default, below: Hamming distances as fp4 dot products on the matrix
 // cores) and k_match (HAK_MATCH_VALU=1: v_xor / v_bcnt on the vector pipe, kept for A/B runs and as the second reader of the
-// accept rule -- the tests run both).
+// accept rule -- the tests run both).  The packed key, the descriptor words, the accept rules and the fields they write are
+// stated once in hak_internal.h (hak_mkey_*, hak_desc_load, hak_match_*, hak_knn*).
 //
-// k_match mapping: a 256-thread block owns 32 queries x 16 residue classes.  Thread
-// (q, c) keeps the 64-byte descriptors of two queries in 32 VGPRs and walks class c with
+// k_match mapping: a 256-thread block owns 16 NQ queries x 16 residue classes (NQ = 1 or 2).  Thread
+// (q, c) keeps the 64-byte descriptors of its NQ queries in 16 NQ VGPRs and walks class c with
 // 16 x (v_xor, v_bcnt) per distance; the train descriptors are staged through LDS
 // in tiles of 128 (coalesced, once per block, the next tile's loads in flight during the compares) and read back with broadcast
 // ds_read_b128, each read serving two distances; classes are merged through LDS.
@@ -22,15 +23,6 @@
 
 #define MQ 16      // queries per block
 #define MC 16      // residue classes (X2 of akazed.cu:7)
-
-__device__ __forceinline__ void load_desc(const hak_point* p, unsigned int d[16])
-{
-    // features start at byte 24 of the 104-byte record: 4-byte aligned
-    const unsigned int* f = reinterpret_cast<const unsigned int*>(p->features);
-#pragma unroll
-    for (int i = 0; i < 15; i++) d[i] = f[i];
-    d[15] = f[15] & 0xFFu;                      // byte 60 only; bytes 61..63 are struct padding
-}
 
 #define MT 128     // train descriptors staged per LDS tile (16 per residue class)
 
@@ -59,26 +51,16 @@ __device__ __forceinline__ void put_train(const unsigned int (&pre)[MT / 16], un
     for (int k = 0; k < MT / 16; k++) wt[k * 64 + lane] = pre[k];
 }
 
-// v_bcnt_u32_b32 computes popcount(x) + acc in ONE instruction; left to itself the compiler takes sixteen plain popcounts
-// and rebuilds the sum as a tree of v_add3 (7 extra instructions per distance)
-__device__ __forceinline__ unsigned bcnt_acc(unsigned x, unsigned acc)
-{
-    unsigned r;
-    asm("v_bcnt_u32_b32 %0, %1, %2" : "=v"(r) : "v"(x), "v"(acc));
-    return r;
-}
-
-// key = (Hamming distance << 16) | (train index - j0) of one residue-class candidate, accumulated on top of `seed` = the
-// index part: 16 x (v_xor, v_bcnt) + one shift-or
+// packed key (hak_mkey) of one residue-class candidate, train index idx: 16 x (v_xor, v_bcnt) + one shift-or
 __device__ __forceinline__ unsigned hamming_key(const unsigned int (&q)[16], const uint4 t0, const uint4 t1, const uint4 t2,
                                                 const uint4 t3, const unsigned idx)
 {
-    unsigned d = bcnt_acc(q[0] ^ t0.x, 0u);
-    d = bcnt_acc(q[1] ^ t0.y, d); d = bcnt_acc(q[2] ^ t0.z, d); d = bcnt_acc(q[3] ^ t0.w, d);
-    d = bcnt_acc(q[4] ^ t1.x, d); d = bcnt_acc(q[5] ^ t1.y, d); d = bcnt_acc(q[6] ^ t1.z, d); d = bcnt_acc(q[7] ^ t1.w, d);
-    d = bcnt_acc(q[8] ^ t2.x, d); d = bcnt_acc(q[9] ^ t2.y, d); d = bcnt_acc(q[10] ^ t2.z, d); d = bcnt_acc(q[11] ^ t2.w, d);
-    d = bcnt_acc(q[12] ^ t3.x, d); d = bcnt_acc(q[13] ^ t3.y, d); d = bcnt_acc(q[14] ^ t3.z, d); d = bcnt_acc(q[15] ^ t3.w, d);
-    return (d << 20) | idx;
+    unsigned d = hak_bcnt_acc(q[0] ^ t0.x, 0u);
+    d = hak_bcnt_acc(q[1] ^ t0.y, d); d = hak_bcnt_acc(q[2] ^ t0.z, d); d = hak_bcnt_acc(q[3] ^ t0.w, d);
+    d = hak_bcnt_acc(q[4] ^ t1.x, d); d = hak_bcnt_acc(q[5] ^ t1.y, d); d = hak_bcnt_acc(q[6] ^ t1.z, d); d = hak_bcnt_acc(q[7] ^ t1.w, d);
+    d = hak_bcnt_acc(q[8] ^ t2.x, d); d = hak_bcnt_acc(q[9] ^ t2.y, d); d = hak_bcnt_acc(q[10] ^ t2.z, d); d = hak_bcnt_acc(q[11] ^ t2.w, d);
+    d = hak_bcnt_acc(q[12] ^ t3.x, d); d = hak_bcnt_acc(q[13] ^ t3.y, d); d = hak_bcnt_acc(q[14] ^ t3.z, d); d = hak_bcnt_acc(q[15] ^ t3.w, d);
+    return hak_mkey(d, idx);
 }
 
 // Mapping: a 256-thread block owns 16 * NQ queries x 16 residue classes; thread (q, c) keeps the descriptors of NQ queries
@@ -118,8 +100,8 @@ __global__ __launch_bounds__(256, 4) void k_match(hak_point* pts1_base, const ha
         for (int a = 0; a < NQ; a++) {
 #pragma unroll
             for (int k = 0; k < 16; k++) qd[a][k] = 0;
-            if (q0 + q + MQ * a < n1) load_desc(pts1 + q0 + q + MQ * a, qd[a]);
-            best[a] = 0xFFFFFFFFu;
+            if (q0 + q + MQ * a < n1) hak_desc_load(pts1 + q0 + q + MQ * a, qd[a]);
+            best[a] = HAK_MKEY_EMPTY;
         }
         unsigned int pre[MT / 16];
         if (jbeg < jend) fetch_train(pts2, jbeg, n2, pre, c, lane & 15);
@@ -152,7 +134,7 @@ __global__ __launch_bounds__(256, 4) void k_match(hak_point* pts1_base, const ha
         if (gkey) {                                                 // (uniform) sliced search: merge, k_match_finish decides
 #pragma unroll
             for (int a = 0; a < NQ; a++)
-                if (q0 + q + MQ * a < n1 && best[a] != 0xFFFFFFFFu) atomicMin(&gkey[(long)(q0 + q + MQ * a) * MC + c], best[a]);
+                if (q0 + q + MQ * a < n1 && best[a] != HAK_MKEY_EMPTY) atomicMin(&gkey[(long)(q0 + q + MQ * a) * MC + c], best[a]);
             continue;
         }
 #pragma unroll
@@ -160,29 +142,7 @@ __global__ __launch_bounds__(256, 4) void k_match(hak_point* pts1_base, const ha
         __syncthreads();
         if (c < NQ) {                                               // class-c threads finish queries q + 16 c
             const int qq = q + MQ * c, qi = q0 + qq;
-            if (qi < n1) {
-                // distances only (key >> 20): the accept rule compares class minima, not indices (akazed.cu:2190-2223)
-                int bc = 0;
-                for (int t = 1; t < MC; t++)
-                    if ((skey[t][qq] >> 20) < (skey[bc][qq] >> 20)) bc = t;
-                const unsigned kmin = skey[bc][qq];
-                const int dmin = (int)(kmin >> 20);
-                int nflag = 0;
-                for (int t = 0; t < MC; t++) nflag += (unsigned)dmin < (skey[t][qq] >> 20) ? 1 : 0;   // akazed.cu:2206
-                hak_point* p1 = pts1 + qi;
-                const int bi = (int)(kmin & 0xFFFFFu);
-                if (kmin != 0xFFFFFFFFu && nflag == MC - 1 && dmin < HAK_MAX_DIST) {  // akazed.cu:2223
-                    p1->match = bi;
-                    p1->distance = dmin;
-                    p1->match_x = pts2[bi].x;
-                    p1->match_y = pts2[bi].y;
-                } else {
-                    p1->match = -1;
-                    p1->distance = -1;
-                    p1->match_x = -1.f;
-                    p1->match_y = -1.f;
-                }
-            }
+            if (qi < n1) hak_match_decide_classes(pts1 + qi, pts2, n2, [&](int t) { return skey[t][qq]; });
         }
         __syncthreads();
     }
@@ -211,8 +171,8 @@ __global__ __launch_bounds__(256, 4) void k_match(hak_point* pts1_base, const ha
 // the minimum of packed keys exactly as in k_match.  A wave = 32 queries x the whole train set (or its slice); the four waves of a
 // block share the train descriptors through LDS.
 //
-// Rounds 4-5: the train set travels in CHUNKS of MM_CH descriptors (rows of 144 bytes: per lane half its 8 descriptor dwords and the
-// same shifted right by 1, padding -- conflict-free ds_read_b128), double-buffered: the 8-byte loads of chunk c+1 (MM_CH / 32 per
+// Rounds 4-5: the train set travels in CHUNKS of MM_BCH descriptors (rows of 144 bytes: per lane half its 8 descriptor dwords and the
+// same shifted right by 1, padding -- conflict-free ds_read_b128), double-buffered: the 8-byte loads of chunk c+1 (MM_BCH / 32 per
 // thread, all in flight at once; a lane fetching ITS descriptor row straight from the 104-byte records touches 32 lines per load
 // instruction and ran at a third of the matrix pipe's rate) are issued before the tiles of chunk c are multiplied and written to
 // the other buffer after them: ONE barrier and ONE exposed memory round trip per chunk.  Round 3 staged tile by tile (a barrier and
@@ -272,30 +232,15 @@ __device__ __forceinline__ mm_v4i mm_frag_b4(unsigned q)
     return f;
 }
 
-// accept rule of gHammingMatch on a query's 16 class minima (akazed.cu:2190-2223): distances only decide (key >> 20) -- the rule
-// compares class minima, not indices; ties between classes never matter for the result (nflag rejects them)
-__device__ __forceinline__ void mm_accept(hak_point* p1, const hak_point* __restrict__ pts2, const unsigned (&all)[16], const int n2)
+// the finishing block's loads: summaries of slices s0 .. s0 + 7 of one query (col = part + query) in flight together -- one memory
+// round trip instead of one per slice; slices past the grid read `fill`, the summary of an empty slice
+__device__ __forceinline__ void mm_load_parts(unsigned long long (&pv)[8], const uint2* col, int n1_pad, int s0, int ns, unsigned long long fill)
 {
-    unsigned kmin = all[0];
 #pragma unroll
-    for (int t = 1; t < 16; t++)
-        if ((all[t] >> 20) < (kmin >> 20)) kmin = all[t];
-    const int dmin = (int)(kmin >> 20);
-    int nflag = 0;
-#pragma unroll
-    for (int t = 0; t < 16; t++) nflag += (unsigned)dmin < (all[t] >> 20) ? 1 : 0;                        // akazed.cu:2206
-    const int bi = min((int)(kmin & 0xFFFFFu), max(n2 - 1, 0));           // (always the index itself: belt and braces for the gather below)
-    if (kmin != 0xFFFFFFFFu && nflag == MC - 1 && dmin < HAK_MAX_DIST) {                             // akazed.cu:2223
-        p1->match = bi;
-        p1->distance = dmin;
-        p1->match_x = pts2[bi].x;
-        p1->match_y = pts2[bi].y;
-    } else {
-        p1->match = -1;
-        p1->distance = -1;
-        p1->match_x = -1.f;
-        p1->match_y = -1.f;
-    }
+    for (int j = 0; j < 8; j++)
+        pv[j] = s0 + j < ns ? __hip_atomic_load(reinterpret_cast<const unsigned long long*>(col + (long)(s0 + j) * n1_pad), __ATOMIC_RELAXED,
+                                                __HIP_MEMORY_SCOPE_AGENT)
+                            : fill;
 }
 
 // Sliced search of one big pair (blockIdx.y = train slice, `ticket` != nullptr): a block merges what it found into scratch and
@@ -328,7 +273,7 @@ extern "C" int hak_debug_mm_blocks(unsigned long long* host) { return hipMemcpyF
 // operands out (v_accvgpr_read: 2 more vector instructions per MFMA, 5 in all again), and a lone wave cannot issue its vector
 // instructions beside its own dependent matrix chain the way a second wave does.  QT = 1 is the default; HAK_MATCH_QT=2 selects
 // the other instantiation (same results: the match tests run both).
-template <bool KNN, int MM_CH, int QT>
+template <bool KNN, int QT>
 __global__ __launch_bounds__(256, (QT == 2 ? 1 : 2)) void k_match_mfma(hak_point* __restrict__ pts1_base, const hak_point* __restrict__ pts2_base,
                                                        const int* __restrict__ n1_dev, const int* __restrict__ n2_dev,
                                                        int n1_host, int n2_host, long stride1, long stride2, int count_stride,
@@ -356,7 +301,7 @@ __global__ __launch_bounds__(256, (QT == 2 ? 1 : 2)) void k_match_mfma(hak_point
     }
     const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    __shared__ __attribute__((aligned(16))) unsigned int tile[2][MM_CH * MM_ROW];
+    __shared__ __attribute__((aligned(16))) unsigned int tile[2][MM_BCH * MM_ROW];
     __shared__ int s_last;
     // thread t fetches dwords 2 (t & 7), 2 (t & 7) + 1 of train descriptors j0 + (t >> 3) + 32 i, i < 6: one chunk, all six
     // loads in flight together; byte offsets in 32 bits from the (uniform) set base (n2 < 2^20 records, checked by the launcher)
@@ -372,25 +317,25 @@ __global__ __launch_bounds__(256, (QT == 2 ? 1 : 2)) void k_match_mfma(hak_point
         // distance (see the header: P through three spare k positions of the staged row, q through the C operand), so the whole
         // key epilogue of a tile is ONE unsigned minimum per element, shared between two tiles by v_min3_u32.
         const int nrows = max(jend - jbeg, 0);
-        const int NQ = nrows / MM_CH;                                                   // chunks of the main part (uniform)
+        const int NQ = nrows / MM_BCH;                                                   // chunks of the main part (uniform)
         const int E = 32 * NQ;                                                          // rows per sixth
-        const int jtail = jbeg + MM_CH * NQ;                                            // first row of the tail
+        const int jtail = jbeg + MM_BCH * NQ;                                            // first row of the tail
         // two chunks travel at a time: chunk q + 2 is requested when chunk q starts and written to LDS when chunk q + 1 starts (round 5:
         // with one chunk in flight the loop was a chain of exposed memory round trips).  pre[c & 1] holds chunk c; the chunk loop is
         // unrolled by two, so the index is static.
-        uint2 pre[2][MM_CH / 32];
+        uint2 pre[2][MM_BCH / 32];
         const int NC = NQ + (jtail < jend ? 1 : 0);                                     // chunks incl. the tail (uniform)
         // chunk c: a main chunk (every row exists) or, c == NQ, the tail (consecutive tiles, rows past jend do not exist)
         auto fetch = [&](int c, auto par) {
             constexpr int PAR = decltype(par)::value;
             if (c < NQ) {
 #pragma unroll
-                for (int i = 0; i < MM_CH / 32; i++)
+                for (int i = 0; i < MM_BCH / 32; i++)
                     pre[PAR][i] = *reinterpret_cast<const uint2*>(reinterpret_cast<const char*>(pts2) +
                                                                   ((unsigned)(jbeg + i * E + 32 * c) * (unsigned)sizeof(hak_point) + toff));
             } else {
 #pragma unroll
-                for (int i = 0; i < MM_CH / 32; i++) {
+                for (int i = 0; i < MM_BCH / 32; i++) {
                     uint2 v = make_uint2(0u, 0u);
                     if (jtail + (int)(threadIdx.x >> 3) + 32 * i < jend)
                         v = *reinterpret_cast<const uint2*>(reinterpret_cast<const char*>(pts2) +
@@ -419,7 +364,7 @@ __global__ __launch_bounds__(256, (QT == 2 ? 1 : 2)) void k_match_mfma(hak_point
             }
             unsigned pb = 0;
 #pragma unroll
-            for (int i = 0; i < 8; i++) pb = bcnt_acc(qd[i], pb);
+            for (int i = 0; i < 8; i++) pb = hak_bcnt_acc(qd[i], pb);
             pb += (unsigned)__shfl_xor((int)pb, 32);
 #pragma unroll
             for (int s = 0; s < 8; s++) B[t][s] = mm_frag_b4(qd[s]);
@@ -432,9 +377,9 @@ __global__ __launch_bounds__(256, (QT == 2 ? 1 : 2)) void k_match_mfma(hak_point
 #pragma unroll
         for (int t = 0; t < QT; t++) {
 #pragma unroll
-            for (int i = 0; i < 16; i++) best[t][i] = 0xFFFFFFFFu;
+            for (int i = 0; i < 16; i++) best[t][i] = HAK_MKEY_EMPTY;
 #pragma unroll
-            for (int i = 0; i < (KNN ? 16 : 1); i++) sec[t][i] = 0xFFFFFFFFu;
+            for (int i = 0; i < (KNN ? 16 : 1); i++) sec[t][i] = HAK_MKEY_EMPTY;
         }
         // the lane's 16 dwords of row r of tile K of chunk buffer BUF -> TD
 #define MM_READ(BUF, K, TD)                                                                                 \
@@ -452,8 +397,8 @@ __global__ __launch_bounds__(256, (QT == 2 ? 1 : 2)) void k_match_mfma(hak_point
             const unsigned ka = __float_as_uint(X[T][I]), kb = __float_as_uint(Y[T][I]);                    \
             if constexpr (KNN) {                                                                            \
                 const unsigned lo = min(ka, kb), hi = max(ka, kb);                                          \
-                sec[T][I] = min(min(sec[T][I], hi), max(best[T][I], lo));                                   \
-                best[T][I] = min(best[T][I], lo);                                                           \
+                sec[T][I] = min(sec[T][I], hi);                                                             \
+                hak_mkey_two_smallest(best[T][I], sec[T][I], lo);                                           \
                 asm volatile("" : "+v"(sec[T][I]));                                                         \
             } else best[T][I] = min(min(best[T][I], ka), kb);                                               \
             /* (the minimum is associative and the compiler knows it: left alone it keeps SIX accumulator sets alive and takes   \
@@ -484,7 +429,7 @@ __global__ __launch_bounds__(256, (QT == 2 ? 1 : 2)) void k_match_mfma(hak_point
             constexpr int PAR = decltype(par)::value;
             const bool tail = c >= NQ;
 #pragma unroll
-            for (int i = 0; i < MM_CH / 32; i++) {
+            for (int i = 0; i < MM_BCH / 32; i++) {
                 const unsigned P = tail ? 7u : (unsigned)i;
                 const unsigned pbits = ((P & 1u) << 8) | ((P & 2u) << 11) | ((P & 4u) << 14);
                 const uint2 v = make_uint2(pre[PAR][i].x, (threadIdx.x & 7) == 7 ? (pre[PAR][i].y & 0xFFu) | pbits : pre[PAR][i].y);
@@ -554,14 +499,9 @@ __global__ __launch_bounds__(256, (QT == 2 ? 1 : 2)) void k_match_mfma(hak_point
         // the tail: up to six consecutive tiles, tile k carries (P, q) = (7, k); rows past jend do not exist
         if (jtail < jend) {
             const int nt = (jend - jtail + 31) >> 5;
-            const unsigned int* tbase = tile[NQ & 1];
             for (int k = 0; k < nt; k++) {
                 unsigned int ta[16];
-                {
-                    const uint4* row = reinterpret_cast<const uint4*>(tbase + (32 * k + r) * MM_ROW + 16 * h);
-#pragma unroll
-                    for (int c = 0; c < 4; c++) { const uint4 v = row[c]; ta[4 * c] = v.x; ta[4 * c + 1] = v.y; ta[4 * c + 2] = v.z; ta[4 * c + 3] = v.w; }
-                }
+                MM_READ(NQ & 1, k, ta)
 #pragma unroll
                 for (int t = 0; t < QT; t++) {
 #pragma unroll
@@ -573,9 +513,9 @@ __global__ __launch_bounds__(256, (QT == 2 ? 1 : 2)) void k_match_mfma(hak_point
                 for (int t = 0; t < QT; t++) {
 #pragma unroll
                     for (int i = 0; i < 16; i++) {
-                        const unsigned key = jb + (i & 3) + 8 * (i >> 2) < jend ? __float_as_uint(X0[t][i]) : 0xFFFFFFFFu;
-                        if constexpr (KNN) sec[t][i] = min(sec[t][i], max(best[t][i], key));
-                        best[t][i] = min(best[t][i], key);
+                        const unsigned key = jb + (i & 3) + 8 * (i >> 2) < jend ? __float_as_uint(X0[t][i]) : HAK_MKEY_EMPTY;
+                        if constexpr (KNN) hak_mkey_two_smallest(best[t][i], sec[t][i], key);
+                        else best[t][i] = min(best[t][i], key);
                     }
                 }
             }
@@ -585,13 +525,13 @@ __global__ __launch_bounds__(256, (QT == 2 ? 1 : 2)) void k_match_mfma(hak_point
 #undef MM_PIPE
 #undef MM_EPI2
 #undef MM_READ
-        // decode: bits - bits(2^10) = d 2^14 + P 2^11 + q  ->  d << 20 | first row of the slot's lane half in that tile
+        // decode: bits - bits(2^10) = d 2^14 + P 2^11 + q  ->  the packed key of the first row of the slot's lane half in that tile
         auto decode = [&](unsigned k) -> unsigned {
-            if (k == 0xFFFFFFFFu) return k;
+            if (k == HAK_MKEY_EMPTY) return k;
             const unsigned u = k - MM_BASE_BITS;
             const unsigned P = (u >> 11) & 7u, q = u & 2047u;
             const unsigned row = (unsigned)jbeg + min(P, 6u) * (unsigned)E + 32u * q + 4u * (unsigned)h;
-            return ((u >> 14) << 20) + row;
+            return hak_mkey(u >> 14, 0u) + row;
         };
 #pragma unroll
         for (int t = 0; t < QT; t++) {
@@ -612,21 +552,20 @@ __global__ __launch_bounds__(256, (QT == 2 ? 1 : 2)) void k_match_mfma(hak_point
 #pragma unroll
                 for (int i = 0; i < 16; i++) {
                     const unsigned off = (unsigned)((i & 3) + 8 * (i >> 2));
-                    b1[i] = best[t][i] == 0xFFFFFFFFu ? best[t][i] : best[t][i] + off;
-                    b2[i] = sec[t][i] == 0xFFFFFFFFu ? sec[t][i] : sec[t][i] + off;
+                    b1[i] = best[t][i] == HAK_MKEY_EMPTY ? best[t][i] : best[t][i] + off;
+                    b2[i] = sec[t][i] == HAK_MKEY_EMPTY ? sec[t][i] : sec[t][i] + off;
                     b1[16 + i] = (unsigned)__shfl_xor((int)b1[i], 32);
                     b2[16 + i] = (unsigned)__shfl_xor((int)b2[i], 32);
                 }
                 unsigned m1 = b1[0];
 #pragma unroll
                 for (int i = 1; i < 32; i++) m1 = min(m1, b1[i]);
-                unsigned m2 = 0xFFFFFFFFu;                          // the keys are distinct (they carry the index): one slot holds m1
+                unsigned m2 = HAK_MKEY_EMPTY;                          // the keys are distinct (they carry the index): one slot holds m1
 #pragma unroll
                 for (int i = 0; i < 32; i++) m2 = min(m2, b1[i] == m1 ? b2[i] : b1[i]);
                 if (!sliced) {
                     if (h == 0 && qi < n1)
-                        out[qi] = m1 == 0xFFFFFFFFu ? make_int4(-1, 512, 512, 0)
-                                                    : make_int4((int)(m1 & 0xFFFFFu), (int)(m1 >> 20), m2 == 0xFFFFFFFFu ? 512 : (int)(m2 >> 20), 0);
+                        out[qi] = hak_knn_record(m1, m2);
                 } else if (h == 0) {
                     // sliced: this slice's two smallest keys of the query; the last block of the query block merges the slices:
                     // nearest = the smallest m1, second = the smallest of the other slices' m1 and the winning slice's m2
@@ -639,12 +578,12 @@ __global__ __launch_bounds__(256, (QT == 2 ? 1 : 2)) void k_match_mfma(hak_point
                 unsigned cls[8];
 #pragma unroll
                 for (int k = 0; k < 8; k++) {
-                    const unsigned lo = best[t][k] == 0xFFFFFFFFu ? best[t][k] : best[t][k] + (unsigned)((k & 3) + 8 * (k >> 2));
-                    const unsigned hi = best[t][k + 8] == 0xFFFFFFFFu ? best[t][k + 8] : best[t][k + 8] + (unsigned)((k & 3) + 8 * (k >> 2) + 16);
+                    const unsigned lo = best[t][k] == HAK_MKEY_EMPTY ? best[t][k] : best[t][k] + (unsigned)((k & 3) + 8 * (k >> 2));
+                    const unsigned hi = best[t][k + 8] == HAK_MKEY_EMPTY ? best[t][k + 8] : best[t][k + 8] + (unsigned)((k & 3) + 8 * (k >> 2) + 16);
                     cls[k] = min(lo, hi);
                 }
                 if (sliced) {                                       // (uniform)
-                    // What the accept rule needs of a slice is little: the smallest key (distance << 20 | index) and WHICH classes attain
+                    // What the accept rule needs of a slice is little: the smallest key and WHICH classes attain
                     // its distance -- the rule asks whether exactly one class attains the global minimum distance (akazed.cu:2206, 2223).
                     // Plain 8-byte stores; atomicMin on 16 class keys per query ran into the atomic units' throughput (2 M lane-atomics:
                     // 35-85 us for 10k x 10k).
@@ -654,17 +593,17 @@ __global__ __launch_bounds__(256, (QT == 2 ? 1 : 2)) void k_match_mfma(hak_point
                     const unsigned kmin = min(kloc, (unsigned)__shfl_xor((int)kloc, 32));
                     unsigned mloc = 0;
 #pragma unroll
-                    for (int k = 0; k < 8; k++) mloc |= (cls[k] >> 20) == (kmin >> 20) ? 1u << ((k & 3) + 8 * (k >> 2) + 4 * h) : 0u;
+                    for (int k = 0; k < 8; k++) mloc |= hak_mkey_dist(cls[k]) == hak_mkey_dist(kmin) ? 1u << ((k & 3) + 8 * (k >> 2) + 4 * h) : 0u;
                     const unsigned mask = mloc | (unsigned)__shfl_xor((int)mloc, 32);
                     if (h == 0)
                         __hip_atomic_store(reinterpret_cast<unsigned long long*>(part + (long)blockIdx.y * n1_pad + qi),
-                                           ((unsigned long long)(kmin == 0xFFFFFFFFu ? 0u : mask) << 32) | kmin, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                                           ((unsigned long long)(kmin == HAK_MKEY_EMPTY ? 0u : mask) << 32) | kmin, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 } else {
                     // the other half of the query's classes sits in lane ^ 32
                     unsigned all[16];
 #pragma unroll
                     for (int k = 0; k < 8; k++) { all[k] = cls[k]; all[8 + k] = (unsigned)__shfl_xor((int)cls[k], 32); }
-                    if (h == 0 && qi < n1) mm_accept(pts1 + qi, pts2, all, n2);
+                    if (h == 0 && qi < n1) hak_match_decide_classes(pts1 + qi, pts2, n2, [&](int t) { return all[t]; });
                 }
             }
         }
@@ -696,16 +635,12 @@ __global__ __launch_bounds__(256, (QT == 2 ? 1 : 2)) void k_match_mfma(hak_point
             if ((int)threadIdx.x < QPB && q < n1) {
                 // (eight slices' summaries in flight at a time: one memory round trip instead of one per slice -- the finishing
                 // blocks are the kernel's tail, round 5: they ended 4-8 us after the others)
+                const int ns = (int)gridDim.y;
+                unsigned long long pv[8];
                 if constexpr (KNN) {
-                    unsigned M1 = 0xFFFFFFFFu, M2 = 0xFFFFFFFFu;
-                    for (int s0 = 0; s0 < (int)gridDim.y; s0 += 8) {
-                        unsigned long long pv[8];
-#pragma unroll
-                        for (int j = 0; j < 8; j++)
-                            pv[j] = s0 + j < (int)gridDim.y
-                                        ? __hip_atomic_load(reinterpret_cast<const unsigned long long*>(part + (long)(s0 + j) * n1_pad + q),
-                                                            __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-                                        : 0xFFFFFFFFFFFFFFFFull;
+                    unsigned M1 = HAK_MKEY_EMPTY, M2 = HAK_MKEY_EMPTY;
+                    for (int s0 = 0; s0 < ns; s0 += 8) {
+                        mm_load_parts(pv, part + q, n1_pad, s0, ns, ~0ull);                                  // two empty keys
 #pragma unroll
                         for (int j = 0; j < 8; j++) {
                             const unsigned a1 = (unsigned)pv[j], a2 = (unsigned)(pv[j] >> 32);
@@ -715,34 +650,15 @@ __global__ __launch_bounds__(256, (QT == 2 ? 1 : 2)) void k_match_mfma(hak_point
                             M1 = lo;
                         }
                     }
-                    out[q] = M1 == 0xFFFFFFFFu ? make_int4(-1, 512, 512, 0)
-                                               : make_int4((int)(M1 & 0xFFFFFu), (int)(M1 >> 20), M2 == 0xFFFFFFFFu ? 512 : (int)(M2 >> 20), 0);
+                    out[q] = hak_knn_record(M1, M2);
                 } else {
-                    unsigned K = 0xFFFFFFFFu, M = 0u;
-                    for (int s0 = 0; s0 < (int)gridDim.y; s0 += 8) {
-                        unsigned long long pv[8];
+                    unsigned K = HAK_MKEY_EMPTY, M = 0u;
+                    for (int s0 = 0; s0 < ns; s0 += 8) {
+                        mm_load_parts(pv, part + q, n1_pad, s0, ns, (unsigned long long)HAK_MKEY_EMPTY);   // {empty key, no class}
 #pragma unroll
-                        for (int j = 0; j < 8; j++)
-                            pv[j] = s0 + j < (int)gridDim.y
-                                        ? __hip_atomic_load(reinterpret_cast<const unsigned long long*>(part + (long)(s0 + j) * n1_pad + q),
-                                                            __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-                                        : 0xFFFFFFFFull;
-#pragma unroll
-                        for (int j = 0; j < 8; j++) {
-                            const unsigned k2 = (unsigned)pv[j], m2 = (unsigned)(pv[j] >> 32);
-                            if ((k2 >> 20) < (K >> 20)) M = m2;      // a smaller distance: its classes alone attain it
-                            else if ((k2 >> 20) == (K >> 20)) M |= m2;
-                            K = min(K, k2);
-                        }
+                        for (int j = 0; j < 8; j++) hak_match_merge_slice(K, M, (unsigned)pv[j], (unsigned)(pv[j] >> 32));
                     }
-                    hak_point* p1 = pts1 + q;
-                    const int dmin = (int)(K >> 20);
-                    const int bi = min((int)(K & 0xFFFFFu), max(n2 - 1, 0));
-                    if (K != 0xFFFFFFFFu && __popc(M) == 1 && dmin < HAK_MAX_DIST) {                   // akazed.cu:2206, 2223
-                        p1->match = bi; p1->distance = dmin; p1->match_x = pts2[bi].x; p1->match_y = pts2[bi].y;
-                    } else {
-                        p1->match = -1; p1->distance = -1; p1->match_x = -1.f; p1->match_y = -1.f;
-                    }
+                    hak_match_decide(pts1 + q, pts2, n2, K, __popc(M));                              // akazed.cu:2206, 2223
                 }
             }
         }
@@ -752,7 +668,7 @@ __global__ __launch_bounds__(256, (QT == 2 ? 1 : 2)) void k_match_mfma(hak_point
 
 // accept rule of gHammingMatch (akazed.cu:2190-2223) on the merged class minima of the sliced search of the VALU kernel
 // (HAK_MATCH_VALU=1; k_match_mfma finishes inside its last block); one thread per query
-__global__ __launch_bounds__(256) void k_match_finish(hak_point* pts1, const hak_point* pts2, int n1, unsigned* __restrict__ gkey)
+__global__ __launch_bounds__(256) void k_match_finish(hak_point* pts1, const hak_point* pts2, int n1, int n2, unsigned* __restrict__ gkey)
 {
     const int qi = blockIdx.x * 256 + threadIdx.x;
     if (qi >= n1) return;
@@ -761,30 +677,9 @@ __global__ __launch_bounds__(256) void k_match_finish(hak_point* pts1, const hak
 #pragma unroll
     for (int t = 0; t < MC / 4; t++) {
         const uint4 v = k4[t]; k[4 * t] = v.x; k[4 * t + 1] = v.y; k[4 * t + 2] = v.z; k[4 * t + 3] = v.w;
-        k4[t] = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);     // the scratch goes back to its empty state (HakMatchScratch)
+        k4[t] = make_uint4(HAK_MKEY_EMPTY, HAK_MKEY_EMPTY, HAK_MKEY_EMPTY, HAK_MKEY_EMPTY);     // the scratch goes back to its empty state (HakMatchScratch)
     }
-    int bc = 0;
-#pragma unroll
-    for (int t = 1; t < MC; t++)
-        if ((k[t] >> 20) < (k[bc] >> 20)) bc = t;
-    const unsigned kmin = k[bc];
-    const int dmin = (int)(kmin >> 20);
-    int nflag = 0;
-#pragma unroll
-    for (int t = 0; t < MC; t++) nflag += (unsigned)dmin < (k[t] >> 20) ? 1 : 0;
-    hak_point* p1 = pts1 + qi;
-    const int bi = (int)(kmin & 0xFFFFFu);
-    if (kmin != 0xFFFFFFFFu && nflag == MC - 1 && dmin < HAK_MAX_DIST) {
-        p1->match = bi;
-        p1->distance = dmin;
-        p1->match_x = pts2[bi].x;
-        p1->match_y = pts2[bi].y;
-    } else {
-        p1->match = -1;
-        p1->distance = -1;
-        p1->match_x = -1.f;
-        p1->match_y = -1.f;
-    }
+    hak_match_decide_classes(pts1 + qi, pts2, n2, [&](int t) { return k[t]; });
 }
 
 // ------------------------------------------------------------------ match post-processing
@@ -808,12 +703,12 @@ __global__ __launch_bounds__(256) void k_knn2(const hak_point* ptsA_base, const 
     for (int q0 = blockIdx.x * MQ; q0 < nA; q0 += gridDim.x * MQ) {
         const int qi = q0 + q;
         unsigned int qd[16];
-        if (qi < nA) load_desc(A + qi, qd);
-        int best = 512, second = 512, besti = -1;
+        if (qi < nA) hak_desc_load(A + qi, qd);
+        int best = HAK_KNN_NO_DIST, second = HAK_KNN_NO_DIST, besti = -1;
         if (qi < nA)
             for (int j = c; j < nB; j += MC) {
                 unsigned int td[16];
-                load_desc(B + j, td);
+                hak_desc_load(B + j, td);
                 int dist = 0;
 #pragma unroll
                 for (int k = 0; k < 16; k += 2)
@@ -829,12 +724,12 @@ __global__ __launch_bounds__(256) void k_knn2(const hak_point* ptsA_base, const 
                 if (si1[t][q] < 0) continue;
                 if (bc < 0 || sd1[t][q] < sd1[bc][q] || (sd1[t][q] == sd1[bc][q] && si1[t][q] < si1[bc][q])) bc = t;
             }
-            int d2 = 512;
+            int d2 = HAK_KNN_NO_DIST;
             for (int t = 0; t < MC; t++) {
                 const int v = (t == bc) ? sd2[t][q] : sd1[t][q];
                 d2 = v < d2 ? v : d2;
             }
-            out[qi] = bc < 0 ? make_int4(-1, 512, 512, 0) : make_int4(si1[bc][q], sd1[bc][q], d2, 0);
+            out[qi] = bc < 0 ? hak_knn_none() : make_int4(si1[bc][q], sd1[bc][q], d2, 0);
         }
         __syncthreads();
     }
@@ -864,32 +759,15 @@ __global__ __launch_bounds__(1024) void k_knn2_finish(hak_point* pts1_base, cons
     __syncthreads();
     for (int i0 = 0; i0 < n1; i0 += 1024) {
         const int i = i0 + threadIdx.x;
-        bool ok = false;
-        int4 f = make_int4(-1, 512, 512, 0);
-        if (i < n1) {
-            f = fwd[i];
-            ok = f.x >= 0 && f.y < max_dist && (long)f.y * ratio_den < (long)f.z * ratio_num;
-            if (ok && cross) ok = rev[f.x].x == i;
-            hak_point* p1 = pts1 + i;
-            if (ok) {
-                p1->match = f.x; p1->distance = f.y;
-                p1->match_x = pts2[f.x].x; p1->match_y = pts2[f.x].y;
-            } else {
-                p1->match = -1; p1->distance = -1; p1->match_x = -1.f; p1->match_y = -1.f;
-            }
-        }
+        int4 f;
+        const bool ok = hak_knn2_rule(i, n1, fwd, rev, ratio_num, ratio_den, cross, max_dist, f);
+        if (i < n1) hak_match_store(pts1 + i, pts2, ok, f.x, f.y);
         const unsigned long long m = __ballot(ok);
         if (lane == 0) wsum[wv] = __popcll(m);
         __syncthreads();
         int before = sbase;
         for (int t = 0; t < wv; t++) before += wsum[t];
-        if (ok && out) {
-            const int pos = before + __popcll(m & ((1ull << lane) - 1ull));
-            hak_match_pair r;
-            r.query = i; r.train = f.x; r.distance = f.y; r.second = f.z;
-            r.x1 = pts1[i].x; r.y1 = pts1[i].y; r.x2 = pts2[f.x].x; r.y2 = pts2[f.x].y;
-            out[pos] = r;
-        }
+        if (ok && out) out[before + __popcll(m & ((1ull << lane) - 1ull))] = hak_knn2_pair(i, f, pts1, pts2);
         __syncthreads();
         if (threadIdx.x == 0) { int tot = 0; for (int t = 0; t < 16; t++) tot += wsum[t]; sbase += tot; }
         __syncthreads();
@@ -901,16 +779,6 @@ __global__ __launch_bounds__(1024) void k_knn2_finish(hak_point* pts1_base, cons
 // right for a batch of pairs, 35 us for 10k queries).  Pass A applies the rule, writes the match fields and counts the accepted
 // matches of its 1024 queries; pass B re-derives the rule's outcome, adds the counts of the blocks in front of it and writes the
 // match list in ascending query order.
-__device__ __forceinline__ bool knn2_rule(const int i, const int n1, const int4* __restrict__ fwd, const int4* __restrict__ rev,
-                                          const int ratio_num, const int ratio_den, const int cross, const int max_dist, int4& f)
-{
-    f = make_int4(-1, 512, 512, 0);
-    if (i >= n1) return false;
-    f = fwd[i];
-    bool ok = f.x >= 0 && f.y < max_dist && (long)f.y * ratio_den < (long)f.z * ratio_num;
-    if (ok && cross) ok = rev[f.x].x == i;
-    return ok;
-}
 __global__ __launch_bounds__(1024) void k_knn2_finish_a(hak_point* pts1, const hak_point* __restrict__ pts2, int n1,
                                                         const int4* __restrict__ fwd, const int4* __restrict__ rev, int ratio_num,
                                                         int ratio_den, int cross, int max_dist, int* __restrict__ blk)
@@ -918,12 +786,8 @@ __global__ __launch_bounds__(1024) void k_knn2_finish_a(hak_point* pts1, const h
     __shared__ int wsum[16];
     const int i = blockIdx.x * 1024 + threadIdx.x;
     int4 f;
-    const bool ok = knn2_rule(i, n1, fwd, rev, ratio_num, ratio_den, cross, max_dist, f);
-    if (i < n1) {
-        hak_point* p1 = pts1 + i;
-        if (ok) { p1->match = f.x; p1->distance = f.y; p1->match_x = pts2[f.x].x; p1->match_y = pts2[f.x].y; }
-        else { p1->match = -1; p1->distance = -1; p1->match_x = -1.f; p1->match_y = -1.f; }
-    }
+    const bool ok = hak_knn2_rule(i, n1, fwd, rev, ratio_num, ratio_den, cross, max_dist, f);
+    if (i < n1) hak_match_store(pts1 + i, pts2, ok, f.x, f.y);
     const unsigned long long m = __ballot(ok);
     if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = __popcll(m);
     __syncthreads();
@@ -939,7 +803,7 @@ __global__ __launch_bounds__(1024) void k_knn2_finish_b(const hak_point* __restr
     const int i = blockIdx.x * 1024 + threadIdx.x;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     int4 f;
-    const bool ok = knn2_rule(i, n1, fwd, rev, ratio_num, ratio_den, cross, max_dist, f);
+    const bool ok = hak_knn2_rule(i, n1, fwd, rev, ratio_num, ratio_den, cross, max_dist, f);
     const unsigned long long m = __ballot(ok);
     if (lane == 0) wsum[wv] = __popcll(m);
     if (wv == 0) {                                                  // accepted matches of all blocks in front of this one
@@ -952,12 +816,7 @@ __global__ __launch_bounds__(1024) void k_knn2_finish_b(const hak_point* __restr
     __syncthreads();
     int before = sbase;
     for (int t = 0; t < wv; t++) before += wsum[t];
-    if (ok && out) {
-        hak_match_pair r;
-        r.query = i; r.train = f.x; r.distance = f.y; r.second = f.z;
-        r.x1 = pts1[i].x; r.y1 = pts1[i].y; r.x2 = pts2[f.x].x; r.y2 = pts2[f.x].y;
-        out[before + __popcll(m & ((1ull << lane) - 1ull))] = r;
-    }
+    if (ok && out) out[before + __popcll(m & ((1ull << lane) - 1ull))] = hak_knn2_pair(i, f, pts1, pts2);
     if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) {
         int tot = sbase;
         for (int t = 0; t < 16; t++) tot += wsum[t];
@@ -1018,12 +877,23 @@ static int mfma_slices(int gx, int n2, int* rows_per_slice, int want_blocks, int
     return (tiles + tps - 1) / tps;
 }
 
+// One big pair with host-side counts whose query blocks alone cannot fill the chip: the slices of its train set for k_match_mfma,
+// their tickets and summaries reserved in `sc`; 1: the pair is not sliced (no scratch, the query blocks suffice or cover fewer than
+// nq queries, too few tiles, out of memory).  The same decision for both searches.
+static int mm_single_pair_slices(HakMatchScratch* sc, hipStream_t st, const HakMatchKnobs& mk, int gx, int nq, int n2, int* rows_per_slice)
+{
+    const int qpb = 128 * mk.qt;
+    if (!sc || gx >= 384 || (long)gx * qpb < nq) return 1;
+    const int slices = mfma_slices(gx, n2, rows_per_slice, mk.qt == 2 ? 256 : 512, mk.slices);
+    return slices > 1 && hak_match_scratch_reserve(sc, st, 0, gx, (long)slices * gx * qpb, 0, 0) ? slices : 1;
+}
+
 // (qt: query tiles per wave of k_match_mfma, HakMatchKnobs::qt)
 template <bool KNN, typename... A>
 static void mm_launch(int qt, dim3 grid, hipStream_t st, A... a)
 {
-    if (qt == 2) k_match_mfma<KNN, MM_BCH, 2><<<grid, 256, 0, st>>>(a...);
-    else k_match_mfma<KNN, MM_BCH, 1><<<grid, 256, 0, st>>>(a...);
+    if (qt == 2) k_match_mfma<KNN, 2><<<grid, 256, 0, st>>>(a...);
+    else k_match_mfma<KNN, 1><<<grid, 256, 0, st>>>(a...);
 }
 
 void hak_launch_knn2(hipStream_t st, const hak_point* ptsA, const hak_point* ptsB, const int* nA_dev, const int* nB_dev,
@@ -1034,26 +904,19 @@ void hak_launch_knn2(hipStream_t st, const hak_point* ptsA, const hak_point* pts
     if (mk.valu == 0 && nB_host <= MM_MAX_ROWS) {
         // the matrix-core kernel with its 2-NN epilogue (the point records are only read: ptsA is not written)
         const int qt = mk.qt, qpb = 128 * qt;
-        int gx = nA_dev ? (qt == 2 ? 43 : 83) : (nA_host + qpb - 1) / qpb;
-        if (gx < 1) gx = 1;
-        if (gx > 4096) gx = 4096;
-        // one big pair with host-side counts whose query blocks alone cannot fill the chip: slice the train set
-        if (sc && !nA_dev && npairs == 1 && gx < 384 && (long)gx * qpb >= nA_host) {
-            int rps = 0;
-            const int slices = mfma_slices(gx, nB_host, &rps, qt == 2 ? 256 : 512, mk.slices);
-            if (slices > 1 && hak_match_scratch_reserve(sc, st, 0, gx, (long)slices * gx * qpb, 0, 0)) {
-                mm_launch<true>(qt, dim3(gx, slices), st, const_cast<hak_point*>(ptsA), ptsB, (const int*)nullptr, (const int*)nullptr, nA_host, nB_host, 0L, 0L,
-                                2, rps, out, 0L, sc->ticket, sc->part, gx * qpb);
-                return;
-            }
+        const int gx = hak_grid_x(nA_dev ? (qt == 2 ? 43 : 83) : (nA_host + qpb - 1) / qpb);
+        int rps = 0;
+        const int slices = !nA_dev && npairs == 1 ? mm_single_pair_slices(sc, st, mk, gx, nA_host, nB_host, &rps) : 1;
+        if (slices > 1) {
+            mm_launch<true>(qt, dim3(gx, slices), st, const_cast<hak_point*>(ptsA), ptsB, (const int*)nullptr, (const int*)nullptr, nA_host, nB_host, 0L, 0L,
+                            2, rps, out, 0L, sc->ticket, sc->part, gx * qpb);
+            return;
         }
         mm_launch<true>(qt, dim3(gx, npairs), st, const_cast<hak_point*>(ptsA), ptsB, nA_dev, nB_dev, nA_host, nB_host, strideA, strideB,
                         2, 0, out, out_stride, (int*)nullptr, (uint2*)nullptr, 0);
         return;
     }
-    int gx = nA_dev ? 640 : (nA_host + MQ - 1) / MQ;
-    if (gx < 1) gx = 1;
-    if (gx > 4096) gx = 4096;
+    const int gx = hak_grid_x(nA_dev ? 640 : (nA_host + MQ - 1) / MQ);
     k_knn2<<<dim3(gx, npairs), 256, 0, st>>>(ptsA, ptsB, nA_dev, nB_dev, nA_host, nB_host, strideA, strideB, 2, out, out_stride);
 }
 
@@ -1089,23 +952,19 @@ void hak_launch_match(hipStream_t st, hak_point* pts1, const hak_point* pts2, co
     // device-side counts: k_match loops over the queries; k_match_mfma gets blocks for 10 240 queries (waves past n1 leave at once)
     // (83 / 43, not 80 / 40: blocks go to the eight XCDs by linear index mod 8, and with a multiple of 8 per pair the blocks of every
     // pair that find queries would land on the same XCDs pair after pair -- two XCDs with three of them, six with two: 1.33 x the mean)
-    int gx = n1_dev ? (valu ? (two ? 320 : 640) : (qt == 2 ? 43 : 83)) : (nq + qb - 1) / qb;
-    if (gx < 1) gx = 1;
-    if (gx > 4096) gx = 4096;
+    int gx = hak_grid_x(n1_dev ? (valu ? (two ? 320 : 640) : (qt == 2 ? 43 : 83)) : (nq + qb - 1) / qb);
     // with device-side counts n1_host carries the CAPACITY of a query set (the context's max_pts; 0: unknown).  The sliced path
     // below gives every query block its own ticket and partial-result rows, so its grid must cover the capacity -- the plain
     // kernel's blocks loop over the queries and need no such bound.
     const int cap_blocks = n1_dev && n1_host > 0 ? (n1_host + qpb - 1) / qpb : 0;
     // one pair with host-side counts whose query blocks alone cannot fill the chip: slice the train set as well
     if (sc && !n1_dev && npairs == 1 && (long)gx * qb >= nq) {
-        if (!valu && gx < 384) {
-            int rps = 0;
-            const int slices = mfma_slices(gx, n2_host, &rps, qt == 2 ? 256 : 512, mk.slices);
-            if (slices > 1 && hak_match_scratch_reserve(sc, st, 0, gx, (long)slices * gx * qpb, 0, 0)) {
-                mm_launch<false>(qt, dim3(gx, slices), st, pts1, pts2, (const int*)nullptr, (const int*)nullptr, n1_host, n2_host, 0L, 0L, 2, rps,
-                                 (int4*)nullptr, 0L, sc->ticket, sc->part, gx * qpb);
-                return;
-            }
+        int rps = 0;
+        const int mslices = valu ? 1 : mm_single_pair_slices(sc, st, mk, gx, nq, n2_host, &rps);
+        if (mslices > 1) {
+            mm_launch<false>(qt, dim3(gx, mslices), st, pts1, pts2, (const int*)nullptr, (const int*)nullptr, n1_host, n2_host, 0L, 0L, 2, rps,
+                             (int4*)nullptr, 0L, sc->ticket, sc->part, gx * qpb);
+            return;
         }
         const int tiles = (n2_host + MT - 1) / MT;
         if (valu && !two && gx < 2048 && tiles >= 4) {
@@ -1115,7 +974,7 @@ void hak_launch_match(hipStream_t st, hak_point* pts1, const hak_point* pts2, co
             slices = (tiles + tps - 1) / tps;
             if (slices > 1 && hak_match_scratch_reserve(sc, st, (long)n1_host * MC, 0, 0, 0, 0)) {
                 k_match<1><<<dim3(gx, slices), 256, 0, st>>>(pts1, pts2, nullptr, nullptr, n1_host, n2_host, 0, 0, 2, sc->keys, tps);
-                k_match_finish<<<(n1_host + 255) / 256, 256, 0, st>>>(pts1, pts2, n1_host, sc->keys);
+                k_match_finish<<<(n1_host + 255) / 256, 256, 0, st>>>(pts1, pts2, n1_host, n2_host, sc->keys);
                 return;
             }
         }

@@ -202,8 +202,7 @@ def test_mldb_cell_assignment(ah, monkeypatch, plan, case):
 
 
 # ------------------------------------------------------------------------------------------------ matcher
-@pytest.mark.parametrize("name,dists,exp", lf.MATCH_CASES, ids=[c[0] for c in lf.MATCH_CASES])
-def test_match_swap_reduce_and_flags(ah, name, dists, exp):
+def _match_case(ah, dists, exp):
     q, train = lf.match_descriptors(dists)
     d1, d2 = ah.AkazeData(), ah.AkazeData()
     ah.initAkazeData(d1, 4, True, True)
@@ -223,6 +222,21 @@ def test_match_swap_reduce_and_flags(ah, name, dists, exp):
     else:
         assert p["match_x"] == -1 and p["match_y"] == -1
     ah.freeAkazeData(d1); ah.freeAkazeData(d2)
+
+
+@pytest.mark.parametrize("name,dists,exp", lf.MATCH_CASES, ids=[c[0] for c in lf.MATCH_CASES])
+def test_match_swap_reduce_and_flags(ah, name, dists, exp):
+    _match_case(ah, dists, exp)
+
+
+@pytest.mark.parametrize("kernel", ["valu", "qt2"])
+@pytest.mark.parametrize("name,dists,exp", lf.MATCH_CASES, ids=[c[0] for c in lf.MATCH_CASES])
+def test_match_swap_reduce_and_flags_other_kernels(ah, monkeypatch, name, dists, exp, kernel):
+    """the same hand-derived cases through the other two readers of the accept rule (hak_match_decide, hak_internal.h): the
+    vector-pipe kernel and the 64-query-wave instantiation of the matrix-core one; the test above runs the default kernel"""
+    monkeypatch.setenv("HAK_MATCH_VALU", "1" if kernel == "valu" else "0")
+    monkeypatch.setenv("HAK_MATCH_QT", "2" if kernel == "qt2" else "1")
+    _match_case(ah, dists, exp)
 
 
 # ----------------------------------------------------------------------------------------- contrast factor
