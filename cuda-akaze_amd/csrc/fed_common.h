@@ -3,6 +3,7 @@
 #pragma once
 #include "hak_internal.h"
 #include <type_traits>
+#include <utility>
 
 // The same streaming kernel serves both pipelines: V = float (akaze) and V = int (fastakaze, 16.16 fixed point,
 // akazed.cu:3448-3470).  Integer arithmetic wraps (unsigned add / mul), so every regrouping used below for the float
@@ -114,50 +115,140 @@ __device__ __forceinline__ int4 hak_load_stream(const int4* p)
 
 constexpr int pmod(int a, int m) { return ((a % m) + m) % m; }
 
-// horizontal pair sums of one g row as seen by a lane: h[j] = g[x0+j-1] + g[x0+j], j = 1..4 (h4 needs the right lane's g.x)
-template <typename V> struct GHrow { V h1, h2, h3, h4; };
 __device__ __forceinline__ float vneg(float a) { return -a; }
 __device__ __forceinline__ int vneg(int a) { return (int)(0u - (unsigned)a); }
 
-// One output row (4 px per lane) of one FED level from shared flux products.
+// ---- the lane vector of the FED kernels: the W consecutive pixels of one row that a lane owns.  W = 4 (a wave's strip is 256 px
+// wide, 16 bytes per lane and row) or W = 2 (128 px, 8 bytes): every ring of the streaming kernels costs W registers per slot, so
+// the 2-px form keeps twice as many fused levels in the same register budget (kernels_fed.hip).  A wave moves 64 W contiguous
+// elements per row either way.
+template <typename V, int W> struct alignas(sizeof(V) * W) FedPx { V e[W]; };
+template <typename V, int W> __device__ __forceinline__ FedPx<V, W> px_fill(const V a)
+{
+    FedPx<V, W> r;
+#pragma unroll
+    for (int j = 0; j < W; j++) r.e[j] = a;
+    return r;
+}
+template <typename V, int W> __device__ __forceinline__ FedPx<V, W> px_add(const FedPx<V, W>& a, const FedPx<V, W>& b)
+{
+    FedPx<V, W> r;
+#pragma unroll
+    for (int j = 0; j < W; j++) r.e[j] = vadd(a.e[j], b.e[j]);
+    return r;
+}
+template <typename V, int W> __device__ __forceinline__ FedPx<V, W> px_neg(const FedPx<V, W>& a)
+{
+    FedPx<V, W> r;
+#pragma unroll
+    for (int j = 0; j < W; j++) r.e[j] = vneg(a.e[j]);
+    return r;
+}
+template <typename V, int W> __device__ __forceinline__ FedPx<V, W> px_sel(const bool c, const FedPx<V, W>& a, const FedPx<V, W>& b)
+{
+    FedPx<V, W> r;
+#pragma unroll
+    for (int j = 0; j < W; j++) r.e[j] = c ? a.e[j] : b.e[j];
+    return r;
+}
+// one row piece as ONE 16- or 8-byte access (p aligned to it).  HAK_NT_LOADS (A/B builds only) marks the load non-temporal.
+template <typename V, int W> __device__ __forceinline__ FedPx<V, W> px_load(const V* p)
+{
+    typedef V vec __attribute__((ext_vector_type(W)));
+#ifdef HAK_NT_LOADS
+    const vec t = __builtin_nontemporal_load(reinterpret_cast<const vec*>(p));
+#else
+    const vec t = *reinterpret_cast<const vec*>(p);
+#endif
+    FedPx<V, W> r;
+#pragma unroll
+    for (int j = 0; j < W; j++) r.e[j] = t[j];
+    return r;
+}
+template <typename V, int W> __device__ __forceinline__ void px_store_nt(V* p, const FedPx<V, W>& v)    // (see hak_store_nt)
+{
+    typedef V vec __attribute__((ext_vector_type(W)));
+    vec t;
+#pragma unroll
+    for (int j = 0; j < W; j++) t[j] = v.e[j];
+    __builtin_nontemporal_store(t, reinterpret_cast<vec*>(p));
+}
+__device__ __forceinline__ unsigned px_bits(float a) { return __float_as_uint(a); }
+__device__ __forceinline__ unsigned px_bits(int a) { return (unsigned)a; }
+template <typename V, int W> __device__ __forceinline__ void px_buf_store_nt(__amdgpu_buffer_rsrc_t r, unsigned voff, const FedPx<V, W>& v)
+{                                                                                                       // (see hak_buf_store_nt)
+    if constexpr (W == 4) {
+        const hak_v4u d = {px_bits(v.e[0]), px_bits(v.e[1]), px_bits(v.e[2]), px_bits(v.e[3])};
+        __builtin_amdgcn_raw_buffer_store_b128(d, r, voff, 0, 2);
+    } else {
+        static_assert(W == 2, "a lane owns 4 or 2 pixels");
+        typedef unsigned v2u __attribute__((ext_vector_type(2)));
+        const v2u d = {px_bits(v.e[0]), px_bits(v.e[1])};
+        __builtin_amdgcn_raw_buffer_store_b64(d, r, voff, 0, 2);
+    }
+}
+
+// horizontal pair sums of one g row as seen by a lane: h[j] = g[x0+j] + g[x0+j+1], j = 0..W-1 (the last needs the right lane's g[0])
+template <typename V, int W> struct GHrow { V h[W]; };
+template <typename V, int W> __device__ __forceinline__ GHrow<V, W> fed_gh(const FedPx<V, W>& g)
+{
+    const V gr = wave_shl1(g.e[0]);
+    GHrow<V, W> r;
+#pragma unroll
+    for (int j = 0; j < W; j++) r.h[j] = vadd(g.e[j], j + 1 < W ? g.e[(j + 1) % W] : gr);
+    return r;
+}
+
+// One output row (W px per lane) of one FED level from shared flux products.
 //   horizontal: P[j] = (g[x0+j-1] + g[x0+j]) * (L[x0+j] - L[x0+j-1]);  term_E(x) = P[x+1], term_W(x) = -P[x] exactly, so
-//               (tE + tW) = P[j+1] - P[j] bit for bit.  P[0] is the left lane's P[4] -- the same two operands in the same
+//               (tE + tW) = P[j+1] - P[j] bit for bit.  P[0] is the left lane's P[W] -- the same two operands in the same
 //               order -- and arrives by ONE wave shift instead of being recomputed (shift + subtract + multiply).
 //   vertical:   Q[r] = (g[r] + g[r+1]) * (L[r+1] - L[r]);  term_S(r) = Q[r], term_N(r) = -Q[r-1] exactly (IEEE addition
 //               commutes, negating a factor negates the product), so  ((tE + tW) + tS) + tN = ((P[j+1] - P[j]) + Qn) - Qp.
 //               Each Q row is formed once and serves the row above and the row below it.
-// Reflect-101 (akazed.cu:1251-1254): x == 0: tW = tE -> P[0] := -P[1];  x == w-1: tE = tW -> P[4] := -P[3];  the callers
+// Reflect-101 (akazed.cu:1251-1254): x == 0: tW = tE -> P[0] := -P[1];  x == w-1: tE = tW -> P[W] := -P[W-1];  the callers
 // do the same in y: row 0: Qp := -Qn, row h-1: Qn := -Qp.  Same value and same rounding as the reference expression
 //   (f+fE)(LE-L) + (f+fW)(LW-L) + (f+fS)(LS-L) + (f+fN)(LN-L)  then  fma(stepfac, sum, L)    (akazed.cu:1259-1263)
 // for both element types (integer arithmetic wraps, so the regroupings are exact there too).
-template <bool XEDGE, typename V, typename V4>
-__device__ __forceinline__ V4 fed_row(const V4 Lc, const GHrow<V>& gh, const V4 Qn, const V4 Qp, int x0, int w, V stepfac)
+template <bool XEDGE, typename V, int W>
+__device__ __forceinline__ FedPx<V, W> fed_row(const FedPx<V, W>& Lc, const GHrow<V, W>& gh, const FedPx<V, W>& Qn, const FedPx<V, W>& Qp,
+                                               int x0, int w, V stepfac)
 {
-    const V Lr = wave_shl1(Lc.x);
-    const V d1 = vsub(Lc.y, Lc.x), d2 = vsub(Lc.z, Lc.y), d3 = vsub(Lc.w, Lc.z), d4 = vsub(Lr, Lc.w);
-    const V P1 = vmul(gh.h1, d1), P2 = vmul(gh.h2, d2), P3 = vmul(gh.h3, d3);
-    V P4 = vmul(gh.h4, d4);
-    if (XEDGE) P4 = x0 + 3 == w - 1 ? vneg(P3) : P4;         // borderAdd(x,1,w) = w-2 (w % 4 == 0: x == w-1 is the last component)
-    V P0 = wave_shr1(P4);                                   // (executes with every lane active: not inside the select)
-    if (XEDGE) P0 = x0 == 0 ? vneg(P1) : P0;                // abs(x-1) = 1
-    V4 o;
-    o.x = vstep(stepfac, vsub(vadd(vsub(P1, P0), Qn.x), Qp.x), Lc.x);
-    o.y = vstep(stepfac, vsub(vadd(vsub(P2, P1), Qn.y), Qp.y), Lc.y);
-    o.z = vstep(stepfac, vsub(vadd(vsub(P3, P2), Qn.z), Qp.z), Lc.z);
-    o.w = vstep(stepfac, vsub(vadd(vsub(P4, P3), Qn.w), Qp.w), Lc.w);
+    const V Lr = wave_shl1(Lc.e[0]);
+    V P[W + 1];
+#pragma unroll
+    for (int j = 1; j <= W; j++) P[j] = vmul(gh.h[j - 1], vsub(j < W ? Lc.e[j % W] : Lr, Lc.e[j - 1]));
+    if (XEDGE) P[W] = x0 + W - 1 == w - 1 ? vneg(P[W - 1]) : P[W];   // borderAdd(x,1,w) = w-2 (w % 4 == 0: x == w-1 is a lane's last pixel)
+    P[0] = wave_shr1(P[W]);                                 // (executes with every lane active: not inside the select)
+    if (XEDGE) P[0] = x0 == 0 ? vneg(P[1]) : P[0];          // abs(x-1) = 1
+    FedPx<V, W> o;
+#pragma unroll
+    for (int j = 0; j < W; j++) o.e[j] = vstep(stepfac, vsub(vadd(vsub(P[j + 1], P[j]), Qn.e[j]), Qp.e[j]), Lc.e[j]);
     return o;
 }
 // Q[r] of one level: gv = g[r] + g[r+1], Ln = row r+1, Lc = row r
-template <typename V, typename V4>
-__device__ __forceinline__ V4 fed_q(const V4 gv, const V4 Ln, const V4 Lc)
+template <typename V, int W>
+__device__ __forceinline__ FedPx<V, W> fed_q(const FedPx<V, W>& gv, const FedPx<V, W>& Ln, const FedPx<V, W>& Lc)
 {
-    return mk4(vmul(gv.x, vsub(Ln.x, Lc.x)), vmul(gv.y, vsub(Ln.y, Lc.y)), vmul(gv.z, vsub(Ln.z, Lc.z)), vmul(gv.w, vsub(Ln.w, Lc.w)));
+    FedPx<V, W> r;
+#pragma unroll
+    for (int j = 0; j < W; j++) r.e[j] = vmul(gv.e[j], vsub(Ln.e[j], Lc.e[j]));
+    return r;
 }
-template <typename V4> __device__ __forceinline__ V4 vneg4(const V4 a) { return mk4(vneg(a.x), vneg(a.y), vneg(a.z), vneg(a.w)); }
+// the float4 / int4 select of the other streaming kernels (kernels_hessian_stream.hip)
 template <typename V4> __device__ __forceinline__ V4 vsel4(const bool c, const V4 a, const V4 b)
 {
     return mk4(c ? a.x : b.x, c ? a.y : b.y, c ? a.z : b.z, c ? a.w : b.w);
 }
+
+// ---- FED steps per launch (hak_fed_groups / hak_fed_group_size state how a cycle is cut): a group of at most HAK_FED_WIDE_STEPS
+// steps runs on 4-px lanes, a longer one (up to HAK_FED_MAX_FUSE) on 2-px lanes
+constexpr int HAK_FED_WIDE_STEPS = 4;
+constexpr int fed_lane_px(int ns) { return ns <= HAK_FED_WIDE_STEPS ? 4 : 2; }
+// ring geometry of a launch that fuses NS levels: the g-sum rings need NS + 1 slots, and every ring size (2 L / Q rows per level,
+// the prefetch distance 3, the 6- and 3-row rings of kernels_fedsf.hip) divides the number of rows one unrolled loop body handles
+constexpr int fed_gsum_slots(int ns) { return ns + 1 <= 6 ? 6 : 9; }
+constexpr int fed_unroll(int ns) { return ns + 1 <= 6 ? 6 : 18; }
 
 
 // ---- sigma=1 low-pass taps and the conductivity, per element type (kernels_smoothflow.hip, kernels_fedsf.hip).

@@ -954,7 +954,7 @@ extern "C" int hak_query_traffic(const hak_ctx* c, int npts_hint, hak_traffic* o
         for (int s = 0; s < L.ms; s++) {
             const LevelPlan& lp = c->plan[(size_t)o * L.ms + s];
             pxsteps += N * lp.nsteps;
-            launches += lp.nsteps ? hak_fed_groups(lp.nsteps, c->knobs.max_fuse, L.oct[o].w) : 0;
+            launches += lp.nsteps ? hak_fed_groups(lp.nsteps, c->knobs.max_fuse, L.oct[o].w, hak_fed_wide_only(o, L.oct[o].w)) : 0;
             // sublevels whose low-pass (8 B/px) + conductivity (8 B/px) run inside the first FED launch (k_fed_sf), and octave
             // heads whose decimation + low-pass (4 N_{o-1} + 8 N_o) + conductivity (8 N_o) do
             if (s > 0 && hak_fed_sf_covers(c->knobs, c->cfg.diffusivity, L.oct[o], c->cfg.batch)) folded += 16.0 * N;

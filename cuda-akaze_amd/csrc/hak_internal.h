@@ -522,7 +522,8 @@ bool hak_launch_fed_sf(hipStream_t st, const int* src, int* smooth, int* flow, i
                        int w, int h, int p, int nimg, const int* taps, int diffusivity, const float* tau, int ns,
                        const HakImgState* state, int octave, bool write_g);
 // fused FED groups (kernels_fed.hip); w % 4 != 0: one step (tau[0]) per launch, k_fed_generic / kf_nld_step
-int hak_fed_groups(int n, int max_fuse, int w);
+int hak_fed_groups(int n, int max_fuse, int w, bool wide_only);
+bool hak_fed_wide_only(int octave, int w);
 int hak_fed_group_size(int n, int G, int g);
 void hak_launch_fed_group(hipStream_t st, const float* src, const float* flow, float* dst, long stride,
                           int w, int h, int p, int nimg, const float* tau, int ns);

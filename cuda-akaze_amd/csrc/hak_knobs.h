@@ -4,7 +4,8 @@
 #pragma once
 #include "../../include/hipakaze.h"
 
-#define HAK_FED_MAX_FUSE 4        // most FED steps one launch fuses (kernels_fed.hip)
+#define HAK_FED_MAX_FUSE 8        // most FED steps one launch fuses: 4 on 4-px lanes, 8 on 2-px lanes, whose rings cost half the
+                                  // registers per fused step (kernels_fed.hip)
 
 // PER CONTEXT: hak_create reads them once, into hak_ctx::knobs (two contexts of a process may differ; tests and A/B runs set the
 // variables before they create a context).  The launchers get them through the context, its HakBatch or a const HakKnobs&.
@@ -30,7 +31,8 @@ struct HakKnobs {
     int fuse_sf = 1;              // HAK_FUSE_SF: low-pass + conductivity fused into the first FED launch of a sublevel: 0 never, 1 by size
                                   // (hak_stream_pays), 2 always where covered
     int fuse_head = 1;            // HAK_FUSE_HEAD=0: octave heads not through the decimating k_fed_sf variant
-    int max_fuse = 4;             // HAK_FED_MAX_FUSE: FED steps fused per launch (1..HAK_FED_MAX_FUSE)
+    int max_fuse = 8;             // HAK_FED_MAX_FUSE: FED steps fused per launch (1..HAK_FED_MAX_FUSE).  Above 4 a cycle takes the deeper 2-px
+                                  // groups where they save launches (hak_fed_groups); 1, 2 and 4 give the 4-px sequence
     int hist_min_blocks = 256;    // HAK_HIST_MIN_BLOCKS: the prologue's histogram pass halves its rows per block below this many blocks (>= 1)
     int hist_rpb_max = 8;         // HAK_HIST_RPB_MAX: ... starting from this many rows per block (>= 1)
     int hess_side = 0;            // HAK_HESS_SIDE=1: octave 0's Hessians on a stream of their own for launches in the tile-kernel regime.  Off by

@@ -159,7 +159,8 @@ static void build_level(LevelArgs& a, int o, int s, hipStream_t st, V* smooth_al
     }
     // the FED cycle in G fused launches, ping-pong Lt <-> tmp so that the last one lands in Lt (widths that do not allow 16-byte
     // rows: G = n, one step per launch)
-    const int G = hak_fed_groups(n, kn.max_fuse, oc.w);
+    // FAST keeps the 4-px groups: the deeper 2-px kernels are built and measured for the float sequence only
+    const int G = hak_fed_groups(n, is_fast<V> && kn.max_fuse > 4 ? 4 : kn.max_fuse, oc.w, hak_fed_wide_only(o, oc.w));
     const int ns0 = hak_fed_group_size(n, G, 0);
     V* dst0 = (G % 2 == 1) ? Lt : tmp;
     const V* fsrc;              // input of the first FED launch
@@ -342,7 +343,7 @@ static int enqueue_detect(hak_ctx* c, const float* d_images, long image_stride, 
                      !hak_stream_pays(c->knobs.hess_stream, L.oct[0].w, L.oct[0].h, nimg) && !level_tile_pays(c, L.oct[0], nimg) &&
                      !hak_stream_pays(c->knobs.fuse_sf, L.oct[0].w, L.oct[0].h, nimg);
         for (int s = 1; s < L.ms && side0; s++)
-            side0 = hak_fed_groups(c->plan[s].nsteps, c->knobs.max_fuse, L.oct[0].w) == 1 && c->plan[s].sigma_size <= 4;
+            side0 = hak_fed_groups(c->plan[s].nsteps, c->knobs.max_fuse, L.oct[0].w, true) == 1 && c->plan[s].sigma_size <= 4;
         hipStream_t st = main_st;
         for (int o = 0; o < L.noct; o++) {
             if (c->concurrent && o > 0) {                       // this octave's chain waits only for Lt(o-1,0)

@@ -123,7 +123,7 @@ extern "C" int hak_op_nld_steps(const float* src, const float* flow, float* dst,
 {
     if (nsteps < 1) return fail("nsteps < 1");
     if (p % 4) return fail("pitch must be a multiple of 4");
-    const int G = hak_fed_groups(nsteps, hak_knobs_from_env().max_fuse, w);
+    const int G = hak_fed_groups(nsteps, hak_knobs_from_env().max_fuse, w, false);
     const float* s = src;
     int done = 0;
     for (int g = 0; g < G; g++) {
@@ -135,6 +135,71 @@ extern "C" int hak_op_nld_steps(const float* src, const float* flow, float* dst,
     }
     HIP_TRY(hipDeviceSynchronize());
     return 0;
+}
+
+// hak_op_nld_steps on a batch: image i's planes lie `stride` elements behind image i-1's
+extern "C" int hak_op_nld_steps_batch(const float* src, const float* flow, float* dst, float* tmp, long stride, int w, int h, int p,
+                                      int nimg, const float* tau, int nsteps)
+{
+    if (nsteps < 1 || nimg < 1) return fail("nsteps < 1 or nimg < 1");
+    if (p % 4 || stride % 4) return fail("pitch and stride must be multiples of 4");
+    const int G = hak_fed_groups(nsteps, hak_knobs_from_env().max_fuse, w, false);
+    const float* s = src;
+    int done = 0;
+    for (int g = 0; g < G; g++) {
+        const int ns = hak_fed_group_size(nsteps, G, g);
+        float* d = ((G - g) % 2 == 1) ? dst : tmp;
+        hak_launch_fed_group(nullptr, s, flow, d, stride, w, h, p, nimg, tau + done, ns);
+        done += ns;
+        s = d;
+    }
+    HIP_TRY(hipDeviceSynchronize());
+    return 0;
+}
+
+// One whole FED cycle of a sublevel the way the launch sequence runs it on large batches: k_fed_sf (sigma=1 low-pass + PM_G2
+// conductivity + the first group of steps; head != 0: the decimating octave-head form, src = the sw x sh source plane of pitch sp)
+// followed by the remaining groups through k_fed_multi.  All planes of image i lie `stride` elements behind image i-1's;
+// kcontrast: one contrast factor per image.  Fails when k_fed_sf does not cover the case (no other kernel is substituted).
+extern "C" int hak_op_fed_cycle(const float* src, int head, int sw, int sh, int sp, float* smooth, float* flow, float* dst, float* tmp,
+                                long stride, int w, int h, int p, int nimg, const float* kcontrast, const float* tau, int nsteps)
+{
+    if (nsteps < 1 || nimg < 1 || !kcontrast) return fail("nsteps < 1, nimg < 1 or no contrast factors");
+    if (p % 4 || stride % 4) return fail("pitch and stride must be multiples of 4");
+    std::vector<HakImgState> hs((size_t)nimg);
+    for (int i = 0; i < nimg; i++) {
+        hs[i] = HakImgState{};
+        hs[i].kcontrast[0] = kcontrast[i];
+        hs[i].ikc[0] = 1.f / (kcontrast[i] * kcontrast[i]);                       // akazed.cu:2493
+    }
+    HakImgState* state = nullptr;
+    HIP_TRY(hipMalloc((void**)&state, sizeof(HakImgState) * (size_t)nimg));
+    int rc = 0;
+    if (hipMemcpy(state, hs.data(), sizeof(HakImgState) * (size_t)nimg, hipMemcpyHostToDevice) != hipSuccess) rc = fail("state upload");
+    float taps[8];
+    hak_gauss_taps(1.f, 2, taps);
+    const int G = hak_fed_groups(nsteps, hak_knobs_from_env().max_fuse, w, false);
+    const int ns0 = hak_fed_group_size(nsteps, G, 0);
+    float* dst0 = (G % 2 == 1) ? dst : tmp;
+    if (!rc) {
+        const bool ok = head ? hak_launch_fed_sf_head(nullptr, src, HakOct{sw, sh, sp, (long)sh * sp}, smooth, flow, dst0, stride,
+                                                      HakOct{w, h, p, (long)h * p}, nimg, taps, HAK_PM_G2, tau, ns0, state, 0, G > 1)
+                             : hak_launch_fed_sf(nullptr, src, smooth, flow, dst0, stride, w, h, p, nimg, taps, HAK_PM_G2, tau, ns0, state, 0,
+                                                 G > 1);
+        if (!ok) rc = fail("hak_op_fed_cycle: k_fed_sf does not cover this case");
+    }
+    const float* s = dst0;
+    int done = ns0;
+    for (int g = 1; g < G && !rc; g++) {
+        const int ns = hak_fed_group_size(nsteps, G, g);
+        float* d = ((G - g) % 2 == 1) ? dst : tmp;
+        hak_launch_fed_group(nullptr, s, flow, d, stride, w, h, p, nimg, tau + done, ns);
+        done += ns;
+        s = d;
+    }
+    if (hipDeviceSynchronize() != hipSuccess && !rc) rc = fail("hak_op_fed_cycle: kernel");
+    (void)hipFree(state);
+    return rc;
 }
 
 extern "C" int hak_op_hessian(const float* s, float* lx, float* ly, float* det, int w, int h, int p, int step)

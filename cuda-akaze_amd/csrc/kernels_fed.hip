@@ -4,13 +4,23 @@
 //   loop over tau[k]        akaze.cpp:381-391, 408-420
 //
 // The conductivity g is fixed for all steps of a sublevel (akaze.cpp:379, 404), so the n steps of a
-// FED cycle are pipelined in time.  A wave owns a 256-px-wide strip (one float4 per lane, 1 KiB
-// contiguous per row) and streams down the rows.  For each fused level k < NS it keeps a 3-row
+// FED cycle are pipelined in time.  A wave owns a strip of 64 W pixels -- W = 4 px per lane (256 px,
+// 1 KiB contiguous per row) for launches of up to 4 steps, W = 2 (128 px, 512 B) for 5..8 steps, see
+// below -- and streams down the rows.  For each fused level k < NS it keeps a 3-row
 // register window; when input row t arrives, level k produces row t-k from level k-1's window, so
 // L and g are read from HBM once and L' written once per NS steps (12 B/px per launch instead of
 // 12 B/px per step).  East/west neighbours come from the adjacent lane with one DPP wave shift;
 // no LDS, no barriers.  The strip's outer HX columns and the NS warm-up rows above/below a strip are
-// recomputed by the neighbouring wave (halo): efficiency (256-2HX)/256 x RY/(RY+2NS).
+// recomputed by the neighbouring wave (halo): efficiency (64W-2HX)/64W x RY/(RY+2NS).
+//
+// Steps per launch (HAK_FED_MAX_FUSE = 8).  What limits NS is registers: every fused level keeps two L rows
+// and two Q rows, and the g-sum rings have NS + 1 slots, all W registers per lane each.  On 4-px lanes NS = 4
+// is the last count that keeps three waves per SIMD (146 VGPRs; NS = 5 needed 220-250).  On 2-px lanes each
+// ring costs half, so NS = 8 costs less than NS = 4 did (113 VGPRs, four waves per SIMD).  The price is the
+// halo share -- (128 - 2*8)/128 = 87.5 % of the lanes store, against 97 % -- and one wave shift per two pixels
+// instead of per four; it buys one launch (12 B/px of L, g and L' traffic) per 8 steps instead of per 4.
+// hak_fed_groups / hak_fed_wide_only below state when a cycle takes the deep groups: octaves 1 and up, where
+// cycles are 5-24 steps long, while the narrow strips still fill their lanes; octave 0 keeps the 4-px launches.
 //
 // The kernel is VALU-issue-bound (rocprof: 4 waves/SIMD x 26 % VALU-active), so the inner loop is
 // written for instruction count:
@@ -22,7 +32,7 @@
 //     neighbour's P[4] (one wave shift); vertically Q = (g[y]+g[y+1]) * (L[y+1]-L[y]) gives term_S(y) = Q,
 //     term_N(y+1) = -Q, so a level keeps ONE L row and ONE Q row between iterations: 8.5 VALU per pixel and step
 //     instead of the 16 of the per-pixel expression;
-//   * the register windows rotate statically (loop unrolled by 6 with compile-time slots) instead
+//   * the register windows rotate statically (loop unrolled by 6, or 18 for NS > 5, with compile-time slots) instead
 //     of being shifted with v_mov;
 //   * border selects (reflect-101) are applied where a row / column IS a border, not per pixel.
 //
@@ -41,15 +51,17 @@
 
 template <typename V, int NS>
 struct FedState {
-    using V4 = typename FedV<V>::V4;
-    static constexpr int GS = 6;        // slots of the g-sum rings (needs NS + 1 <= GS; divides the unroll factor)
-    V4 Lw[NS][2];                       // level j (0 = input): its two newest rows, slot = (row - origin) mod 2
-    V4 Qw[NS][2];                       // vertical flux products of level j: Q[r] at slot (r - origin) mod 2
-    GHrow<V> GH[GS];                    // ring: horizontal sums of g row r        at slot (r - origin) mod GS
-    V4 GV[GS];                          // ring: g[r] + g[r+1]                     at slot (r - origin) mod GS
-    V4 gprev;                           // g row t-1
-    static constexpr int PD = NS <= HAK_FM_PD_MAXNS ? HAK_FM_PD : 3;        // prefetch distance in rows (divides the unroll factor 6)
-    V4 Lq[PD], Gq[PD];                  // software prefetch ring: rows t .. t+PD-1 in flight
+    static constexpr int W = fed_lane_px(NS);       // pixels per lane (fed_common.h)
+    using Px = FedPx<V, W>;
+    static constexpr int GS = fed_gsum_slots(NS);   // slots of the g-sum rings (needs NS + 1 <= GS; divides the unroll factor)
+    static constexpr int UF = fed_unroll(NS);       // rows per unrolled loop body
+    Px Lw[NS][2];                       // level j (0 = input): its two newest rows, slot = (row - origin) mod 2
+    Px Qw[NS][2];                       // vertical flux products of level j: Q[r] at slot (r - origin) mod 2
+    GHrow<V, W> GH[GS];                 // ring: horizontal sums of g row r        at slot (r - origin) mod GS
+    Px GV[GS];                          // ring: g[r] + g[r+1]                     at slot (r - origin) mod GS
+    Px gprev;                           // g row t-1
+    static constexpr int PD = NS <= HAK_FM_PD_MAXNS ? HAK_FM_PD : 3;        // prefetch distance in rows (divides the unroll factor)
+    Px Lq[PD], Gq[PD];                  // software prefetch ring: rows t .. t+PD-1 in flight
 };
 
 // One row-iteration.  Everything is computed unconditionally: a level-k row outside the range this
@@ -63,42 +75,50 @@ __device__ __forceinline__ void fed_iter(FedState<V, NS>& S, const int t, const 
                                          const int x0, const int w, const int h,
                                          const int ybeg, const int yend, const bool owns, const FedFacs<V, NS>& fac)
 {
-    using V4 = typename FedV<V>::V4;
-    constexpr int GS = FedState<V, NS>::GS;
+    constexpr int W = FedState<V, NS>::W, GS = FedState<V, NS>::GS;
+    using Px = FedPx<V, W>;
     // ---- level 0: input row t arrives (prefetched); request row t+PD (clamped: rows past the image are never used)
     {
         constexpr int PD = FedState<V, NS>::PD;
-        const V4 g = S.Gq[pmod(U, PD)];
+        const Px g = S.Gq[pmod(U, PD)];
         S.Lw[0][pmod(U, 2)] = S.Lq[pmod(U, PD)];
         // bytes in flight, not issue rate, bound this kernel (one row ahead = 2 KB per wave < latency x bandwidth):
         // keep PD rows of L and g outstanding per wave
         const long nrow = (long)min(t + PD, h - 1) * p + xl;
-        S.Lq[pmod(U, PD)] = hak_load_stream(reinterpret_cast<const V4*>(L + nrow));
-        S.Gq[pmod(U, PD)] = hak_load_stream(reinterpret_cast<const V4*>(G + nrow));
-        const V gr = wave_shl1(g.x);
-        S.GH[pmod(U, GS)] = GHrow<V>{vadd(g.x, g.y), vadd(g.y, g.z), vadd(g.z, g.w), vadd(g.w, gr)};
-        S.GV[pmod(U - 1, GS)] = mk4(vadd(S.gprev.x, g.x), vadd(S.gprev.y, g.y), vadd(S.gprev.z, g.z), vadd(S.gprev.w, g.w));
+        S.Lq[pmod(U, PD)] = px_load<V, W>(L + nrow);
+        S.Gq[pmod(U, PD)] = px_load<V, W>(G + nrow);
+        S.GH[pmod(U, GS)] = fed_gh(g);
+        S.GV[pmod(U - 1, GS)] = px_add(S.gprev, g);
         S.gprev = g;
     }
     // ---- levels 1..NS: level k produces row rho = t-k from level k-1's rows rho, rho+1 and its flux rows Q[rho-1], Q[rho]
 #pragma unroll
     for (int k = 1; k <= NS; k++) {
         const int rho = t - k;
-        const V4 Lc = S.Lw[k - 1][pmod(U - k, 2)];                              // row rho   of level k-1
-        V4 Qn = fed_q<V, V4>(S.GV[pmod(U - k, GS)], S.Lw[k - 1][pmod(U - k + 1, 2)], Lc);    // Q[rho] (row rho+1 is this iteration's)
-        V4 Qp = S.Qw[k - 1][pmod(U - k - 1, 2)];                                // Q[rho-1]
+        const Px Lc = S.Lw[k - 1][pmod(U - k, 2)];                              // row rho   of level k-1
+        Px Qn = fed_q(S.GV[pmod(U - k, GS)], S.Lw[k - 1][pmod(U - k + 1, 2)], Lc);    // Q[rho] (row rho+1 is this iteration's)
+        Px Qp = S.Qw[k - 1][pmod(U - k - 1, 2)];                                // Q[rho-1]
         if (YEDGE) {                                        // (selects on values: a branch here keeps the rings out of registers)
-            Qp = vsel4(rho == 0, vneg4(Qn), Qp);            // abs(y-1) = 1
-            Qn = vsel4(rho == h - 1, vneg4(Qp), Qn);        // borderAdd(y,1,h) = h-2
+            Qp = px_sel(rho == 0, px_neg(Qn), Qp);          // abs(y-1) = 1
+            Qn = px_sel(rho == h - 1, px_neg(Qp), Qn);      // borderAdd(y,1,h) = h-2
         }
         S.Qw[k - 1][pmod(U - k, 2)] = Qn;
-        const V4 out = fed_row<XE, V, V4>(Lc, S.GH[pmod(U - k, GS)], Qn, Qp, x0, w, fac.f[k - 1]);
+        const Px out = fed_row<XE>(Lc, S.GH[pmod(U - k, GS)], Qn, Qp, x0, w, fac.f[k - 1]);
         if (k < NS) {
             S.Lw[k < NS ? k : 0][pmod(U - k, 2)] = out;
         } else if (rho >= ybeg && rho < yend && owns) {
-            hak_store_nt(reinterpret_cast<V4*>(D + (long)rho * p + x0), out);
+            px_store_nt(D + (long)rho * p + x0, out);
         }
     }
+}
+// the UF row-iterations of one unrolled loop body: ring slots are compile-time constants (U = row - origin mod UF)
+template <typename V, int NS, bool YEDGE, bool XE, int... U>
+__device__ __forceinline__ void fed_body(std::integer_sequence<int, U...>, FedState<V, NS>& S, const int tb, const V* __restrict__ L,
+                                         const V* __restrict__ G, V* __restrict__ D, const int p, const int xl, const int x0,
+                                         const int w, const int h, const int ybeg, const int yend, const bool owns,
+                                         const FedFacs<V, NS>& fac)
+{
+    (fed_iter<V, NS, U, YEDGE, XE>(S, tb + U, L, G, D, p, xl, x0, w, h, ybeg, yend, owns, fac), ...);
 }
 
 // requires w % 4 == 0 (true for every octave of BASELINE's configs); other widths: k_fed_generic
@@ -107,52 +127,48 @@ __device__ __forceinline__ void fed_strip(const V* __restrict__ L, const V* __re
                                           V* __restrict__ D, int w, int h, int p, const FedFacs<V, NS>& fac,
                                           int x0, int ybeg, int yend, bool owns)
 {
-    using V4 = typename FedV<V>::V4;
-    const int xl = min(max(x0, 0), p - 4);                  // keep every lane's loads inside the plane
+    using St = FedState<V, NS>;
+    constexpr int W = St::W, UF = St::UF;
+    const int xl = min(max(x0, 0), p - W);                  // keep every lane's loads inside the plane
     const int t0 = max(0, ybeg - NS);                       // first input row; level k is exact from row t0 + k (or 0)
     const int tend = min(yend - 1, h - 1) + NS;             // iteration that emits the strip's last output row
-    FedState<V, NS> S;
-    const V z = 0;
+    St S;
+    const FedPx<V, W> z = px_fill<V, W>(0);
 #pragma unroll
-    for (int k = 0; k < NS; k++) S.Lw[k][0] = S.Lw[k][1] = S.Qw[k][0] = S.Qw[k][1] = mk4(z, z, z, z);
+    for (int k = 0; k < NS; k++) S.Lw[k][0] = S.Lw[k][1] = S.Qw[k][0] = S.Qw[k][1] = z;
 #pragma unroll
-    for (int i = 0; i < FedState<V, NS>::GS; i++) {
-        S.GH[i] = GHrow<V>{z, z, z, z};
-        S.GV[i] = mk4(z, z, z, z);
+    for (int i = 0; i < St::GS; i++) {
+#pragma unroll
+        for (int j = 0; j < W; j++) S.GH[i].h[j] = 0;
+        S.GV[i] = z;
     }
-    S.gprev = mk4(z, z, z, z);
+    S.gprev = z;
 #pragma unroll
-    for (int i = 0; i < FedState<V, NS>::PD; i++) {
+    for (int i = 0; i < St::PD; i++) {
         const long row = (long)min(t0 + i, h - 1) * p + xl;
-        S.Lq[i] = hak_load_stream(reinterpret_cast<const V4*>(L + row));
-        S.Gq[i] = hak_load_stream(reinterpret_cast<const V4*>(G + row));
+        S.Lq[i] = px_load<V, W>(L + row);
+        S.Gq[i] = px_load<V, W>(G + row);
     }
-    for (int tb = t0; tb <= tend; tb += 6) {                // ring slot = (row - t0) mod 2 / mod 6: static per unrolled body
+    for (int tb = t0; tb <= tend; tb += UF) {               // ring slot = (row - t0) mod ring size: static per unrolled body
         // the reflect rule can only fire while some level is at row 0 (t <= NS) or at row h-1
-        if (tb <= NS || tb + 5 >= h) {
-            fed_iter<V, NS, 0, true, XE>(S, tb + 0, L, G, D, p, xl, x0, w, h, ybeg, yend, owns, fac);
-            fed_iter<V, NS, 1, true, XE>(S, tb + 1, L, G, D, p, xl, x0, w, h, ybeg, yend, owns, fac);
-            fed_iter<V, NS, 2, true, XE>(S, tb + 2, L, G, D, p, xl, x0, w, h, ybeg, yend, owns, fac);
-            fed_iter<V, NS, 3, true, XE>(S, tb + 3, L, G, D, p, xl, x0, w, h, ybeg, yend, owns, fac);
-            fed_iter<V, NS, 4, true, XE>(S, tb + 4, L, G, D, p, xl, x0, w, h, ybeg, yend, owns, fac);
-            fed_iter<V, NS, 5, true, XE>(S, tb + 5, L, G, D, p, xl, x0, w, h, ybeg, yend, owns, fac);
-        } else {
-            fed_iter<V, NS, 0, false, XE>(S, tb + 0, L, G, D, p, xl, x0, w, h, ybeg, yend, owns, fac);
-            fed_iter<V, NS, 1, false, XE>(S, tb + 1, L, G, D, p, xl, x0, w, h, ybeg, yend, owns, fac);
-            fed_iter<V, NS, 2, false, XE>(S, tb + 2, L, G, D, p, xl, x0, w, h, ybeg, yend, owns, fac);
-            fed_iter<V, NS, 3, false, XE>(S, tb + 3, L, G, D, p, xl, x0, w, h, ybeg, yend, owns, fac);
-            fed_iter<V, NS, 4, false, XE>(S, tb + 4, L, G, D, p, xl, x0, w, h, ybeg, yend, owns, fac);
-            fed_iter<V, NS, 5, false, XE>(S, tb + 5, L, G, D, p, xl, x0, w, h, ybeg, yend, owns, fac);
-        }
+        if (tb <= NS || tb + UF - 1 >= h)
+            fed_body<V, NS, true, XE>(std::make_integer_sequence<int, UF>{}, S, tb, L, G, D, p, xl, x0, w, h, ybeg, yend, owns, fac);
+        else
+            fed_body<V, NS, false, XE>(std::make_integer_sequence<int, UF>{}, S, tb, L, G, D, p, xl, x0, w, h, ybeg, yend, owns, fac);
     }
 }
+
+// x halo of a launch that fuses ns levels: >= ns, a multiple of 4 (the lanes' 16- or 8-byte alignment); stored strip width
+constexpr int fed_hx(int ns) { return (ns + 3) & ~3; }
+constexpr int fed_xv(int ns) { return 64 * fed_lane_px(ns) - 2 * fed_hx(ns); }
 
 // grid: hak_xcd_grid(strips, strip-row groups, images); a block's four waves take four consecutive row segments
 template <typename V, int NS>
 __global__ __launch_bounds__(256) void k_fed_multi(const V* __restrict__ src, const V* __restrict__ flow,
                                                    V* __restrict__ dst, long stride, int w, int h, int p,
-                                                   FedFacs<V, NS> fac, int ry, int xv, int hx, int nbx, int nby, int nimg)
+                                                   FedFacs<V, NS> fac, int ry, int nbx, int nby, int nimg)
 {
+    constexpr int W = fed_lane_px(NS), hx = fed_hx(NS), xv = fed_xv(NS);
     int bx, by, img;
     if (!hak_xcd_decode(nbx, nby, nimg, bx, by, img)) return;
     const V* L = src + (long)img * stride;
@@ -160,11 +176,11 @@ __global__ __launch_bounds__(256) void k_fed_multi(const V* __restrict__ src, co
     V* D = dst + (long)img * stride;
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);     // wave-uniform -> row bookkeeping in SGPRs
-    const int x0 = bx * xv - hx + 4 * lane;                 // first pixel of this lane (may lie outside the image)
+    const int x0 = bx * xv - hx + W * lane;                 // first pixel of this lane (may lie outside the image)
     const int ybeg = (by * 4 + wv) * ry;
     if (ybeg >= h) return;                                  // wave-uniform
     const int yend = min(ybeg + ry, h);
-    const bool owns = 4 * lane >= hx && 4 * lane < hx + xv && x0 < w && x0 >= 0;
+    const bool owns = W * lane >= hx && W * lane < hx + xv && x0 < w && x0 >= 0;
     if (bx == 0 || (bx + 1) * xv + hx >= w) fed_strip<V, NS, true>(L, G, D, w, h, p, fac, x0, ybeg, yend, owns);
     else fed_strip<V, NS, false>(L, G, D, w, h, p, fac, x0, ybeg, yend, owns);
 }
@@ -231,21 +247,36 @@ static void launch_multi(hipStream_t st, const V* src, const V* flow, V* dst, lo
         if constexpr (std::is_same<V, float>::value) fac.f[k] = 0.5f * tau[k];      // akazed.cu:2515
         else fac.f[k] = (int)(0.5f * tau[k] * 65536 + 0.5f);                        // akazed.cu:4235
     }
-    const int hx = 4;                                               // x halo >= NS, multiple of 4 (16-byte alignment)
-    const int xv = 256 - 2 * hx;
+    constexpr int xv = fed_xv(NS);
     const int gx = (w + xv - 1) / xv;
     // rows per wave: tall strips amortise the 2*NS warm-up rows; shrink while the grid cannot fill the chip
     const int ry = hak_stream_rows(h, (long)gx * nimg, 8);
     const int gy = (h + 4 * ry - 1) / (4 * ry);
-    k_fed_multi<V, NS><<<hak_xcd_grid(gx, gy, nimg), 256, 0, st>>>(src, flow, dst, stride, w, h, p, fac, ry, xv, hx, gx, gy, nimg);
+    k_fed_multi<V, NS><<<hak_xcd_grid(gx, gy, nimg), 256, 0, st>>>(src, flow, dst, stride, w, h, p, fac, ry, gx, gy, nimg);
 }
 
-// launches needed for n steps at width w when at most max_fuse steps are fused per launch
-int hak_fed_groups(int n, int max_fuse, int w)
+// Launches needed for n steps at width w when at most max_fuse steps are fused per launch.  THE RULE for cutting a cycle:
+// groups of at most HAK_FED_WIDE_STEPS steps (4-px lanes) unless deeper groups (up to max_fuse <= HAK_FED_MAX_FUSE steps, 2-px
+// lanes) need FEWER launches for this cycle and the caller does not ask for wide groups only (hak_fed_wide_only: the launch
+// sequence's planes where the 2-px strip does not pay).  hak_fed_group_size balances the steps over the launches, and each launch
+// takes the lane width its own step count asks for (fed_lane_px), so max_fuse <= 4 gives the 4-px sequence unchanged.
+int hak_fed_groups(int n, int max_fuse, int w, bool wide_only)
 {
     if (max_fuse < 1 || w % 4 != 0) max_fuse = 1;                   // odd widths: one step per launch
     if (max_fuse > HAK_FED_MAX_FUSE) max_fuse = HAK_FED_MAX_FUSE;
-    return (n + max_fuse - 1) / max_fuse;
+    const int wide = max_fuse < HAK_FED_WIDE_STEPS ? max_fuse : HAK_FED_WIDE_STEPS;
+    const int Gw = (n + wide - 1) / wide, Gd = (n + max_fuse - 1) / max_fuse;
+    return !wide_only && Gd < Gw ? Gd : Gw;
+}
+// Planes of the launch sequence that keep the 4-px groups whatever the cycle length: octave 0 (cycles of at most 4 steps at the
+// demo schedule, launches at copy speed), and widths at which the 128-px strips (112 stored columns) would keep fewer than 3/4 of
+// their lanes on image columns -- the deep launches are bound by vector issue, which grows with the lanes, not by bytes.  Measured
+// on 512 x 1080p (profiles/fed_deep_launch_table.txt): w = 960 (83 % of the lanes) 5.30 -> 3.97 ms, w = 480 (75 %) 2.21 -> 2.01 ms,
+// w = 240 (62 %) 1.06 -> 1.30 ms.
+bool hak_fed_wide_only(int octave, int w)
+{
+    const int strips = (w + fed_xv(HAK_FED_MAX_FUSE) - 1) / fed_xv(HAK_FED_MAX_FUSE);
+    return octave == 0 || 4L * w < 3L * strips * 64 * fed_lane_px(HAK_FED_MAX_FUSE);
 }
 
 // steps of group g when n steps are split into G balanced groups (sizes differ by at most one)
@@ -277,7 +308,19 @@ static void launch_fed_group_t(hipStream_t st, const V* src, const V* flow, V* d
     case 1: launch_multi<V, 1>(st, src, flow, dst, stride, w, h, p, nimg, tau); break;
     case 2: launch_multi<V, 2>(st, src, flow, dst, stride, w, h, p, nimg, tau); break;
     case 3: launch_multi<V, 3>(st, src, flow, dst, stride, w, h, p, nimg, tau); break;
-    default: launch_multi<V, 4>(st, src, flow, dst, stride, w, h, p, nimg, tau); break;
+    case 4: launch_multi<V, 4>(st, src, flow, dst, stride, w, h, p, nimg, tau); break;
+    default:
+        // more than HAK_FED_WIDE_STEPS steps: the 2-px strip.  The integer FAST sequence keeps the 4-px rule (hak_sequence.hip caps its
+        // max_fuse), so these instantiations exist for float only.
+        if constexpr (std::is_same<V, float>::value) {
+            switch (ns) {
+            case 5: launch_multi<V, 5>(st, src, flow, dst, stride, w, h, p, nimg, tau); break;
+            case 6: launch_multi<V, 6>(st, src, flow, dst, stride, w, h, p, nimg, tau); break;
+            case 7: launch_multi<V, 7>(st, src, flow, dst, stride, w, h, p, nimg, tau); break;
+            default: launch_multi<V, 8>(st, src, flow, dst, stride, w, h, p, nimg, tau); break;
+            }
+        } else launch_multi<V, 4>(st, src, flow, dst, stride, w, h, p, nimg, tau);
+        break;
     }
 }
 

@@ -5,7 +5,7 @@
 //   hNldStep x NS (Lt(o,s-1), flow -> ...)        akaze.cpp:408-420, akazed.cu:2509, 1241
 //
 // The unfused sequence moves 12 B/px in k_smooth_flow (read L, write smooth, write g) and 12 B/px in the first
-// k_fed_multi launch (read L, read g, write L').  Here a wave streams down its 256-px strip exactly like
+// k_fed_multi launch (read L, read g, write L').  Here a wave streams down its strip exactly like
 // k_fed_multi, but the only input is L: when row t arrives,
 //     row pass  rp(t)      of the separable Gaussian (x neighbours at +-1, +-2 by DPP wave shifts),
 //     smooth    row t-2    = column pass over rp(t-4 .. t)            -> HBM (the Hessian kernel reads it),
@@ -14,7 +14,8 @@
 //     FED level k          produces row t-3-k from level k-1 (as in kernels_fed.hip, delayed by three rows),
 // so the pass reads 4 B/px and writes 8 (or 12) B/px instead of 24.  Rings (static slots, loop unrolled by 6):
 // L 6 rows, rp 6 rows, smooth 3 rows (+ its two x-neighbour columns), the g-sum rings and per-level windows of
-// the FED kernel.  No LDS, no barriers.
+// the FED kernel.  No LDS, no barriers.  NS = 5..8 (float only) run on 2-px lanes like k_fed_multi's deep groups (kernels_fed.hip):
+// 135-145 VGPRs, three waves per SIMD, x halo 2 + 1 + NS rounded up to 8 or 12 of a 128-px strip; the unrolled body then covers 18 rows.
 //
 // Bit-exactness: every stage evaluates the reference expression in the reference order (Gaussian: c*k0, then
 // += k1*(l1+r1), then += k2*(l2+r2), akazed.cu:227-239 / 283-288; Scharr / conductivity akazed.cu:1088-1106).
@@ -39,32 +40,40 @@ namespace {
 
 template <typename V, int NS>
 struct FsState {
-    using V4 = typename FedV<V>::V4;
-    static constexpr int GS = 6;
-    static constexpr int PD = NS <= HAK_FS_PD_MAXNS ? HAK_FS_PD : 3;     // input rows in flight (divides the unroll factor 6)
-    V4 Lr[6];                           // L rows t-5 .. t                      slot = iteration mod 6
-    V4 Rp[6];                           // row-pass rows t-5 .. t
-    V4 Sm[3];                           // smooth rows a-2 .. a (a = t-2)       slot = iteration mod 3
-    V SmL[3], SmR[3];                   // smooth at columns x0-1 and x0+4 of those rows
-    V4 Lw[NS][2];                       // FED level k >= 1: its two newest rows ([0] unused: level 0 reads Lr)
-    V4 Qw[NS][2];                       // vertical flux products of level j (fed_common.h fed_row), slot = row mod 2
-    GHrow<V> GH[GS];
-    V4 GV[GS];
-    V4 gprev;
-    V4 Lq[PD];                          // prefetch ring
+    static constexpr int W = fed_lane_px(NS);       // pixels per lane (fed_common.h)
+    using Px = FedPx<V, W>;
+    static constexpr int GS = fed_gsum_slots(NS);
+    static constexpr int UF = fed_unroll(NS);       // rows per unrolled loop body (a multiple of every ring size below)
+    static constexpr int PD = NS <= HAK_FS_PD_MAXNS ? HAK_FS_PD : 3;     // input rows in flight (divides the unroll factor)
+    Px Lr[6];                           // L rows t-5 .. t                      slot = iteration mod 6
+    Px Rp[6];                           // row-pass rows t-5 .. t
+    Px Sm[3];                           // smooth rows a-2 .. a (a = t-2)       slot = iteration mod 3
+    V SmL[3], SmR[3];                   // smooth at columns x0-1 and x0+W of those rows
+    Px Lw[NS][2];                       // FED level k >= 1: its two newest rows ([0] unused: level 0 reads Lr)
+    Px Qw[NS][2];                       // vertical flux products of level j (fed_common.h fed_row), slot = row mod 2
+    GHrow<V, W> GH[GS];
+    Px GV[GS];
+    Px gprev;
+    Px Lq[PD];                          // prefetch ring
 };
 
-// row `row` of the kernel's input L, columns xl .. xl+3.  DEC = false: L is the plane itself.  DEC = true (octave head,
-// hDownWithSmooth akazed.cu:449-511): L is Lt(o-1,0) and the input is its 2x decimation, L(x, y) = src(2x, 2y); the two
+// row `row` of the kernel's input L, columns xl .. xl+W-1.  DEC = false: L is the plane itself.  DEC = true (octave head,
+// hDownWithSmooth akazed.cu:449-511): L is Lt(o-1,0) and the input is its 2x decimation, L(x, y) = src(2x, 2y); the
 // 16-byte loads are never copied, the even components are simply the registers the consumers read.
-template <bool DEC, typename V, typename V4>
-__device__ __forceinline__ V4 fs_fetch(const V* __restrict__ L, const int row, const int lp, const int xl, const int sh)
+template <bool DEC, typename V, int W>
+__device__ __forceinline__ FedPx<V, W> fs_fetch(const V* __restrict__ L, const int row, const int lp, const int xl, const int sh)
 {
-    if constexpr (!DEC) return hak_load_stream(reinterpret_cast<const V4*>(L + (long)row * lp + xl));
+    if constexpr (!DEC) return px_load<V, W>(L + (long)row * lp + xl);
     else {
-        const V* r = L + (long)min(2 * row, sh - 1) * lp + min(2 * xl, lp - 8);
-        const V4 a = hak_load_stream(reinterpret_cast<const V4*>(r)), b = hak_load_stream(reinterpret_cast<const V4*>(r + 4));
-        return mk4(a.x, a.z, b.x, b.z);
+        const V* r = L + (long)min(2 * row, sh - 1) * lp + min(2 * xl, lp - 2 * W);
+        FedPx<V, W> o;
+#pragma unroll
+        for (int i = 0; i < W / 2; i++) {
+            const FedPx<V, 4> a = px_load<V, 4>(r + 4 * i);
+            o.e[2 * i] = a.e[0];
+            o.e[2 * i + 1] = a.e[2];
+        }
+        return o;
     }
 }
 
@@ -74,79 +83,73 @@ struct FsOut { __amdgpu_buffer_rsrc_t r; unsigned smo, go; };
 
 // lp / sh: pitch and row count of the plane L points to (= p, h unless DEC)
 template <typename V, int NS, int U, bool YEDGE, bool XE, bool WRITE_G, bool DEC, bool WRITE_SM>
-__device__ __forceinline__ void fs_iter(FsState<V, NS>& S, const int t, const V* __restrict__ L, V* __restrict__ SMO,
-                                        V* __restrict__ GO, V* __restrict__ D, const int p, const int xl,
-                                        const int x0, const int w, const int h, const int ybeg, const int yend,
+__device__ __forceinline__ void fs_iter(FsState<V, NS>& S, const int t, const V* __restrict__ L, V* __restrict__ D, const int p,
+                                        const int xl, const int x0, const int w, const int h, const int ybeg, const int yend,
                                         const bool owns, const FedFacs<V, NS>& fac, const SfTaps<V> kk, const float ikc,
                                         const int lp, const int sh, const FsOut& O)
 {
-    using V4 = typename FedV<V>::V4;
-    constexpr int GS = FsState<V, NS>::GS, PD = FsState<V, NS>::PD;
-    const bool le = x0 == 0, re = x0 + 3 == w - 1;
+    constexpr int W = FsState<V, NS>::W, GS = FsState<V, NS>::GS, PD = FsState<V, NS>::PD;
+    using Px = FedPx<V, W>;
+    const bool le = x0 == 0, re = x0 + W - 1 == w - 1;
     // ---- L row t arrives; request row t + PD (clamped: rows past the image are never used)
     {
-        const V4 Lc = S.Lq[pmod(U, PD)];
+        const Px Lc = S.Lq[pmod(U, PD)];
         S.Lr[pmod(U, 6)] = Lc;
-        S.Lq[pmod(U, PD)] = fs_fetch<DEC, V, V4>(L, min(t + PD, h - 1), lp, xl, sh);
+        S.Lq[pmod(U, PD)] = fs_fetch<DEC, V, W>(L, min(t + PD, h - 1), lp, xl, sh);
     }
     // ---- row pass of the Gaussian on row t (akazed.cu:227-239)
     {
-        const V4 c = S.Lr[pmod(U, 6)];
-        const V sl1 = wave_shr1(c.w), sl2 = wave_shr1(c.z), sr1 = wave_shl1(c.x), sr2 = wave_shl1(c.y);
-        V4 l1 = mk4(sl1, c.x, c.y, c.z), l2 = mk4(sl2, sl1, c.x, c.y);
-        V4 r1 = mk4(c.y, c.z, c.w, sr1), r2 = mk4(c.z, c.w, sr1, sr2);
+        const Px c = S.Lr[pmod(U, 6)];
+        V a[W + 4];                                         // columns x0-2 .. x0+W+1: the neighbour lanes' pixels by wave shifts
+        a[0] = wave_shr1(c.e[W - 2]); a[1] = wave_shr1(c.e[W - 1]);
+#pragma unroll
+        for (int j = 0; j < W; j++) a[2 + j] = c.e[j];
+        a[W + 2] = wave_shl1(c.e[0]); a[W + 3] = wave_shl1(c.e[1]);
         if (XE) {
-            l1.x = le ? c.y : l1.x;                         // column -1 -> 1
-            l2.x = le ? c.z : l2.x;                         // column -2 -> 2
-            l2.y = le ? c.y : l2.y;                         // column -1 -> 1
+            a[1] = le ? a[3] : a[1];                        // column -1 -> 1
+            a[0] = le ? a[4] : a[0];                        // column -2 -> 2
             if constexpr (!DEC) {
-                r1.w = re ? c.z : r1.w;                     // column w   -> w-2
-                r2.z = re ? c.z : r2.z;                     // column w   -> w-2
-                r2.w = re ? c.y : r2.w;                     // column w+1 -> w-3
+                a[W + 2] = re ? a[W] : a[W + 2];            // column w   -> w-2
+                a[W + 3] = re ? a[W - 1] : a[W + 3];        // column w+1 -> w-3
             } else {
                 // octave head: the mirror is taken on the SOURCE extents (akazed.cu:466, 477-494); with an even source
                 // width that is column w -> w-1, w+1 -> w-2 on the decimated lattice
-                r1.w = re ? c.w : r1.w;
-                r2.z = re ? c.w : r2.z;
-                r2.w = re ? c.z : r2.w;
+                a[W + 2] = re ? a[W + 1] : a[W + 2];
+                a[W + 3] = re ? a[W] : a[W + 3];
             }
         }
-        V4 rp;
-        rp.x = sf_conv(c.x, l1.x, r1.x, l2.x, r2.x, kk);
-        rp.y = sf_conv(c.y, l1.y, r1.y, l2.y, r2.y, kk);
-        rp.z = sf_conv(c.z, l1.z, r1.z, l2.z, r2.z, kk);
-        rp.w = sf_conv(c.w, l1.w, r1.w, l2.w, r2.w, kk);
+        Px rp;
+#pragma unroll
+        for (int j = 0; j < W; j++) rp.e[j] = sf_conv(a[j + 2], a[j + 1], a[j + 3], a[j], a[j + 4], kk);
         S.Rp[pmod(U, 6)] = rp;
         if (YEDGE) {
             // selects on values, not conditional stores: two adjacent `if (t == ..) ring[slot] = rp` are merged by the optimiser
             // into ONE store through a pointer phi, which keeps the whole ring in scratch memory
-            S.Rp[pmod(U - 2, 6)] = vsel4(t == 1, rp, S.Rp[pmod(U - 2, 6)]);          // row -1 := row 1
-            S.Rp[pmod(U - 4, 6)] = vsel4(t == 2, rp, S.Rp[pmod(U - 4, 6)]);          // row -2 := row 2
+            S.Rp[pmod(U - 2, 6)] = px_sel(t == 1, rp, S.Rp[pmod(U - 2, 6)]);          // row -1 := row 1
+            S.Rp[pmod(U - 4, 6)] = px_sel(t == 2, rp, S.Rp[pmod(U - 4, 6)]);          // row -2 := row 2
             if constexpr (!DEC) {
-                S.Rp[pmod(U, 6)] = vsel4(t == h, S.Rp[pmod(U - 2, 6)], S.Rp[pmod(U, 6)]);        // row h   := row h-2
-                S.Rp[pmod(U, 6)] = vsel4(t == h + 1, S.Rp[pmod(U - 4, 6)], S.Rp[pmod(U, 6)]);    // row h+1 := row h-3
-            } else {                                                                 // source-extent mirror, even source height
-                S.Rp[pmod(U, 6)] = vsel4(t == h, S.Rp[pmod(U - 1, 6)], S.Rp[pmod(U, 6)]);        // row h   := row h-1
-                S.Rp[pmod(U, 6)] = vsel4(t == h + 1, S.Rp[pmod(U - 3, 6)], S.Rp[pmod(U, 6)]);    // row h+1 := row h-2
+                S.Rp[pmod(U, 6)] = px_sel(t == h, S.Rp[pmod(U - 2, 6)], S.Rp[pmod(U, 6)]);        // row h   := row h-2
+                S.Rp[pmod(U, 6)] = px_sel(t == h + 1, S.Rp[pmod(U - 4, 6)], S.Rp[pmod(U, 6)]);    // row h+1 := row h-3
+            } else {                                                                  // source-extent mirror, even source height
+                S.Rp[pmod(U, 6)] = px_sel(t == h, S.Rp[pmod(U - 1, 6)], S.Rp[pmod(U, 6)]);        // row h   := row h-1
+                S.Rp[pmod(U, 6)] = px_sel(t == h + 1, S.Rp[pmod(U - 3, 6)], S.Rp[pmod(U, 6)]);    // row h+1 := row h-2
             }
         }
     }
     // ---- column pass -> smooth row a = t - 2 (akazed.cu:283-288)
     {
         const int a = t - 2;
-        const V4 c = S.Rp[pmod(U - 2, 6)], u1 = S.Rp[pmod(U - 3, 6)], d1 = S.Rp[pmod(U - 1, 6)];
-        const V4 u2 = S.Rp[pmod(U - 4, 6)], d2 = S.Rp[pmod(U, 6)];
-        V4 sm;
-        sm.x = sf_conv(c.x, u1.x, d1.x, u2.x, d2.x, kk);
-        sm.y = sf_conv(c.y, u1.y, d1.y, u2.y, d2.y, kk);
-        sm.z = sf_conv(c.z, u1.z, d1.z, u2.z, d2.z, kk);
-        sm.w = sf_conv(c.w, u1.w, d1.w, u2.w, d2.w, kk);
+        const Px c = S.Rp[pmod(U - 2, 6)], u1 = S.Rp[pmod(U - 3, 6)], d1 = S.Rp[pmod(U - 1, 6)];
+        const Px u2 = S.Rp[pmod(U - 4, 6)], d2 = S.Rp[pmod(U, 6)];
+        Px sm;
+#pragma unroll
+        for (int j = 0; j < W; j++) sm.e[j] = sf_conv(c.e[j], u1.e[j], d1.e[j], u2.e[j], d2.e[j], kk);
         if constexpr (WRITE_SM)
-            hak_buf_store_nt(O.r, O.smo + (a >= ybeg && a < yend ? (unsigned)(a * p) * (unsigned)sizeof(V) : HAK_BUF_OOB), sm);
-        V sl = wave_shr1(sm.w), sr = wave_shl1(sm.x);
+            px_buf_store_nt(O.r, O.smo + (a >= ybeg && a < yend ? (unsigned)(a * p) * (unsigned)sizeof(V) : HAK_BUF_OOB), sm);
+        V sl = wave_shr1(sm.e[W - 1]), sr = wave_shl1(sm.e[0]);
         if (XE) {
-            sl = le ? sm.y : sl;                            // abs(x-1) = 1
-            sr = re ? sm.z : sr;                            // borderAdd(x,1,w) = w-2
+            sl = le ? sm.e[1] : sl;                         // abs(x-1) = 1
+            sr = re ? sm.e[W - 2] : sr;                     // borderAdd(x,1,w) = w-2
         }
         S.Sm[pmod(U, 3)] = sm; S.SmL[pmod(U, 3)] = sl; S.SmR[pmod(U, 3)] = sr;
         if (YEDGE && a == 1) { S.Sm[pmod(U - 2, 3)] = sm; S.SmL[pmod(U - 2, 3)] = sl; S.SmR[pmod(U - 2, 3)] = sr; }
@@ -157,36 +160,39 @@ __device__ __forceinline__ void fs_iter(FsState<V, NS>& S, const int t, const V*
     // ---- conductivity row b = t - 3 (akazed.cu:1088-1098, PM_G2) and the FED rings' level-0 bookkeeping for that row
     const int tf = t - 3;                                   // the FED part runs three rows behind the input
     {
-        const V4 su = S.Sm[pmod(U - 2, 3)], sc = S.Sm[pmod(U - 1, 3)], sd = S.Sm[pmod(U, 3)];
-        const V uL = S.SmL[pmod(U - 2, 3)], uR = S.SmR[pmod(U - 2, 3)];
-        const V cL = S.SmL[pmod(U - 1, 3)], cR = S.SmR[pmod(U - 1, 3)];
-        const V dL = S.SmL[pmod(U, 3)], dR = S.SmR[pmod(U, 3)];
-        V4 g;
-        float4 den;                                         // 1 + dif2 of the four pixels
-#define FS_G(k, ul, uc, ur, cl, cr, ll, lc, lr)                                             \
-        {                                                                                   \
-            const V dx = 10 * ((cr) - (cl)) + 3 * ((ur) + (lr) - (ul) - (ll));              \
-            const V dy = 10 * ((lc) - (uc)) + 3 * ((ll) + (lr) - (ul) - (ur));              \
-            den.k = 1.f + sf_dif2(dx, dy, ikc);                                             \
+        // smooth rows b-1, b, b+1 at columns x0-1 .. x0+W
+        V su[W + 2], sc[W + 2], sd[W + 2];
+        su[0] = S.SmL[pmod(U - 2, 3)]; su[W + 1] = S.SmR[pmod(U - 2, 3)];
+        sc[0] = S.SmL[pmod(U - 1, 3)]; sc[W + 1] = S.SmR[pmod(U - 1, 3)];
+        sd[0] = S.SmL[pmod(U, 3)]; sd[W + 1] = S.SmR[pmod(U, 3)];
+#pragma unroll
+        for (int j = 0; j < W; j++) {
+            su[j + 1] = S.Sm[pmod(U - 2, 3)].e[j];
+            sc[j + 1] = S.Sm[pmod(U - 1, 3)].e[j];
+            sd[j + 1] = S.Sm[pmod(U, 3)].e[j];
         }
-        FS_G(x, uL, su.x, su.y, cL, sc.y, dL, sd.x, sd.y)
-        FS_G(y, su.x, su.y, su.z, sc.x, sc.z, sd.x, sd.y, sd.z)
-        FS_G(z, su.y, su.z, su.w, sc.y, sc.w, sd.y, sd.z, sd.w)
-        FS_G(w, su.z, su.w, uR, sc.z, cR, sd.z, sd.w, dR)
-#undef FS_G
+        float den[W];                                       // 1 + dif2 of the lane's pixels
+        bool fast = true;
+#pragma unroll
+        for (int j = 0; j < W; j++) {
+            const V dx = 10 * (sc[j + 2] - sc[j]) + 3 * (su[j + 2] + sd[j + 2] - su[j] - sd[j]);
+            const V dy = 10 * (sd[j + 1] - su[j + 1]) + 3 * (sd[j] + sd[j + 2] - su[j] - su[j + 2]);
+            den[j] = 1.f + sf_dif2(dx, dy, ikc);
+            fast = fast && den[j] < 0x1p64f;
+        }
         // g = 1 / den: the 3-instruction reciprocal is bit-identical to the IEEE division on [1, 2^64) (fed_common.h); a wave
         // with any value outside that range (NaN / inf from a degenerate contrast factor) takes the division for all lanes
-        const bool fast = den.x < 0x1p64f && den.y < 0x1p64f && den.z < 0x1p64f && den.w < 0x1p64f;
+        Px g;
         if (__ballot(!fast) == 0ull) {
-            g = mk4(sf_g_as<V>(hak_rcp_newton(den.x)), sf_g_as<V>(hak_rcp_newton(den.y)), sf_g_as<V>(hak_rcp_newton(den.z)),
-                    sf_g_as<V>(hak_rcp_newton(den.w)));
+#pragma unroll
+            for (int j = 0; j < W; j++) g.e[j] = sf_g_as<V>(hak_rcp_newton(den[j]));
         } else {
-            g = mk4(sf_g_as<V>(1.f / den.x), sf_g_as<V>(1.f / den.y), sf_g_as<V>(1.f / den.z), sf_g_as<V>(1.f / den.w));
+#pragma unroll
+            for (int j = 0; j < W; j++) g.e[j] = sf_g_as<V>(1.f / den[j]);
         }
-        if (WRITE_G) hak_buf_store_nt(O.r, O.go + (tf >= ybeg && tf < yend ? (unsigned)(tf * p) * (unsigned)sizeof(V) : HAK_BUF_OOB), g);
-        const V gr = wave_shl1(g.x);
-        S.GH[pmod(U, GS)] = GHrow<V>{vadd(g.x, g.y), vadd(g.y, g.z), vadd(g.z, g.w), vadd(g.w, gr)};
-        S.GV[pmod(U - 1, GS)] = mk4(vadd(S.gprev.x, g.x), vadd(S.gprev.y, g.y), vadd(S.gprev.z, g.z), vadd(S.gprev.w, g.w));
+        if (WRITE_G) px_buf_store_nt(O.r, O.go + (tf >= ybeg && tf < yend ? (unsigned)(tf * p) * (unsigned)sizeof(V) : HAK_BUF_OOB), g);
+        S.GH[pmod(U, GS)] = fed_gh(g);
+        S.GV[pmod(U - 1, GS)] = px_add(S.gprev, g);
         S.gprev = g;
     }
     // ---- FED levels 1..NS: level k produces row rho = tf-k from level k-1's rows rho, rho+1 and its flux rows Q[rho-1], Q[rho]
@@ -195,23 +201,32 @@ __device__ __forceinline__ void fs_iter(FsState<V, NS>& S, const int t, const V*
     for (int k = 1; k <= NS; k++) {
         const int rho = tf - k;
         // level 0 = the L ring (row tf-j lives in slot U-3-j); levels >= 1 = their two newest rows
-        const V4 Lc = k == 1 ? S.Lr[pmod(U - 3 - 1, 6)] : S.Lw[k - 1][pmod(U - k, 2)];
-        const V4 Ls = k == 1 ? S.Lr[pmod(U - 3, 6)] : S.Lw[k - 1][pmod(U - k + 1, 2)];
-        V4 Qn = fed_q<V, V4>(S.GV[pmod(U - k, GS)], Ls, Lc);
-        V4 Qp = S.Qw[k - 1][pmod(U - k - 1, 2)];
+        const Px Lc = k == 1 ? S.Lr[pmod(U - 3 - 1, 6)] : S.Lw[k - 1][pmod(U - k, 2)];
+        const Px Ls = k == 1 ? S.Lr[pmod(U - 3, 6)] : S.Lw[k - 1][pmod(U - k + 1, 2)];
+        Px Qn = fed_q(S.GV[pmod(U - k, GS)], Ls, Lc);
+        Px Qp = S.Qw[k - 1][pmod(U - k - 1, 2)];
         if (YEDGE) {                                        // (selects on values: a branch here keeps the rings out of registers)
-            Qp = vsel4(rho == 0, vneg4(Qn), Qp);            // abs(y-1) = 1
-            Qn = vsel4(rho == h - 1, vneg4(Qp), Qn);        // borderAdd(y,1,h) = h-2
+            Qp = px_sel(rho == 0, px_neg(Qn), Qp);          // abs(y-1) = 1
+            Qn = px_sel(rho == h - 1, px_neg(Qp), Qn);      // borderAdd(y,1,h) = h-2
         }
         S.Qw[k - 1][pmod(U - k, 2)] = Qn;
-        const V4 out = fed_row<XE, V, V4>(Lc, S.GH[pmod(U - k, GS)], Qn, Qp, x0, w, fac.f[k - 1]);
+        const Px out = fed_row<XE>(Lc, S.GH[pmod(U - k, GS)], Qn, Qp, x0, w, fac.f[k - 1]);
         if (k < NS) {
             S.Lw[k < NS ? k : 0][pmod(U - k, 2)] = out;
         } else if (rho >= ybeg && rho < yend && owns) {
             // kept conditional: an unconditional store means evaluating the last level for every row, which costs ~100 VGPRs
-            hak_store_nt(reinterpret_cast<V4*>(D + (long)rho * p + x0), out);
+            px_store_nt(D + (long)rho * p + x0, out);
         }
     }
+}
+// the UF row-iterations of one unrolled loop body: ring slots are compile-time constants (U = row - origin mod UF)
+template <typename V, int NS, bool YEDGE, bool XE, bool WRITE_G, bool DEC, bool WRITE_SM, int... U>
+__device__ __forceinline__ void fs_body(std::integer_sequence<int, U...>, FsState<V, NS>& S, const int tb, const V* __restrict__ L,
+                                        V* __restrict__ D, const int p, const int xl, const int x0, const int w, const int h,
+                                        const int ybeg, const int yend, const bool owns, const FedFacs<V, NS>& fac,
+                                        const SfTaps<V> kk, const float ikc, const int lp, const int sh, const FsOut& O)
+{
+    (fs_iter<V, NS, U, YEDGE, XE, WRITE_G, DEC, WRITE_SM>(S, tb + U, L, D, p, xl, x0, w, h, ybeg, yend, owns, fac, kk, ikc, lp, sh, O), ...);
 }
 
 template <typename V, int NS, bool XE, bool WRITE_G, bool DEC, bool WRITE_SM>
@@ -221,8 +236,9 @@ __device__ __forceinline__ void fs_strip(const V* __restrict__ L, V* __restrict_
                                          const int lp, const int sh)
 {
     // WRITE_SM = false (SMO == nullptr): the low-pass has no reader -- the level's Hessian low-passes Lt itself -- and is not stored
-    using V4 = typename FedV<V>::V4;
-    const int xl = min(max(x0, 0), p - 4);                  // keep every lane's loads inside the plane
+    using St = FsState<V, NS>;
+    constexpr int W = St::W, UF = St::UF;
+    const int xl = min(max(x0, 0), p - W);                  // keep every lane's loads inside the plane
     FsOut O;
     {
         V* lo = SMO ? SMO : GO;
@@ -234,46 +250,37 @@ __device__ __forceinline__ void fs_strip(const V* __restrict__ L, V* __restrict_
     }
     const int t0 = max(0, ybeg - NS - 4);                   // rp from t0, smooth from t0+2, g from t0+3, level k from t0+3+k
     const int tend = min(yend - 1, h - 1) + NS + 3;         // iteration that emits the strip's last L' row
-    FsState<V, NS> S;
+    St S;
     const V z = 0;
-    const V4 z4 = mk4(z, z, z, z);
+    const FedPx<V, W> zp = px_fill<V, W>(z);
 #pragma unroll
-    for (int i = 0; i < 6; i++) { S.Lr[i] = z4; S.Rp[i] = z4; }
+    for (int i = 0; i < 6; i++) { S.Lr[i] = zp; S.Rp[i] = zp; }
 #pragma unroll
-    for (int i = 0; i < 3; i++) { S.Sm[i] = z4; S.SmL[i] = z; S.SmR[i] = z; }
+    for (int i = 0; i < 3; i++) { S.Sm[i] = zp; S.SmL[i] = z; S.SmR[i] = z; }
 #pragma unroll
-    for (int k = 0; k < NS; k++) S.Lw[k][0] = S.Lw[k][1] = S.Qw[k][0] = S.Qw[k][1] = z4;
+    for (int k = 0; k < NS; k++) S.Lw[k][0] = S.Lw[k][1] = S.Qw[k][0] = S.Qw[k][1] = zp;
 #pragma unroll
-    for (int i = 0; i < FsState<V, NS>::GS; i++) {
-        S.GH[i] = GHrow<V>{z, z, z, z};
-        S.GV[i] = z4;
+    for (int i = 0; i < St::GS; i++) {
+#pragma unroll
+        for (int j = 0; j < W; j++) S.GH[i].h[j] = z;
+        S.GV[i] = zp;
     }
-    S.gprev = z4;
+    S.gprev = zp;
 #pragma unroll
-    for (int i = 0; i < FsState<V, NS>::PD; i++)
-        S.Lq[i] = fs_fetch<DEC, V, V4>(L, min(t0 + i, h - 1), lp, xl, sh);
-    for (int tb = t0; tb <= tend; tb += 6) {
+    for (int i = 0; i < St::PD; i++)
+        S.Lq[i] = fs_fetch<DEC, V, W>(L, min(t0 + i, h - 1), lp, xl, sh);
+    for (int tb = t0; tb <= tend; tb += UF) {
         // reflect injections fire while some stage is at rows 1..2 (t <= NS + 4) or at the virtual rows past h-1
-        if (tb <= NS + 4 || tb + 5 >= h) {
-            fs_iter<V, NS, 0, true, XE, WRITE_G, DEC, WRITE_SM>(S, tb + 0, L, SMO, GO, D, p, xl, x0, w, h, ybeg, yend, owns, fac, kk, ikc, lp, sh, O);
-            fs_iter<V, NS, 1, true, XE, WRITE_G, DEC, WRITE_SM>(S, tb + 1, L, SMO, GO, D, p, xl, x0, w, h, ybeg, yend, owns, fac, kk, ikc, lp, sh, O);
-            fs_iter<V, NS, 2, true, XE, WRITE_G, DEC, WRITE_SM>(S, tb + 2, L, SMO, GO, D, p, xl, x0, w, h, ybeg, yend, owns, fac, kk, ikc, lp, sh, O);
-            fs_iter<V, NS, 3, true, XE, WRITE_G, DEC, WRITE_SM>(S, tb + 3, L, SMO, GO, D, p, xl, x0, w, h, ybeg, yend, owns, fac, kk, ikc, lp, sh, O);
-            fs_iter<V, NS, 4, true, XE, WRITE_G, DEC, WRITE_SM>(S, tb + 4, L, SMO, GO, D, p, xl, x0, w, h, ybeg, yend, owns, fac, kk, ikc, lp, sh, O);
-            fs_iter<V, NS, 5, true, XE, WRITE_G, DEC, WRITE_SM>(S, tb + 5, L, SMO, GO, D, p, xl, x0, w, h, ybeg, yend, owns, fac, kk, ikc, lp, sh, O);
-        } else {
-            fs_iter<V, NS, 0, false, XE, WRITE_G, DEC, WRITE_SM>(S, tb + 0, L, SMO, GO, D, p, xl, x0, w, h, ybeg, yend, owns, fac, kk, ikc, lp, sh, O);
-            fs_iter<V, NS, 1, false, XE, WRITE_G, DEC, WRITE_SM>(S, tb + 1, L, SMO, GO, D, p, xl, x0, w, h, ybeg, yend, owns, fac, kk, ikc, lp, sh, O);
-            fs_iter<V, NS, 2, false, XE, WRITE_G, DEC, WRITE_SM>(S, tb + 2, L, SMO, GO, D, p, xl, x0, w, h, ybeg, yend, owns, fac, kk, ikc, lp, sh, O);
-            fs_iter<V, NS, 3, false, XE, WRITE_G, DEC, WRITE_SM>(S, tb + 3, L, SMO, GO, D, p, xl, x0, w, h, ybeg, yend, owns, fac, kk, ikc, lp, sh, O);
-            fs_iter<V, NS, 4, false, XE, WRITE_G, DEC, WRITE_SM>(S, tb + 4, L, SMO, GO, D, p, xl, x0, w, h, ybeg, yend, owns, fac, kk, ikc, lp, sh, O);
-            fs_iter<V, NS, 5, false, XE, WRITE_G, DEC, WRITE_SM>(S, tb + 5, L, SMO, GO, D, p, xl, x0, w, h, ybeg, yend, owns, fac, kk, ikc, lp, sh, O);
-        }
+        if (tb <= NS + 4 || tb + UF - 1 >= h)
+            fs_body<V, NS, true, XE, WRITE_G, DEC, WRITE_SM>(std::make_integer_sequence<int, UF>{}, S, tb, L, D, p, xl, x0, w, h, ybeg, yend, owns, fac, kk, ikc, lp, sh, O);
+        else
+            fs_body<V, NS, false, XE, WRITE_G, DEC, WRITE_SM>(std::make_integer_sequence<int, UF>{}, S, tb, L, D, p, xl, x0, w, h, ybeg, yend, owns, fac, kk, ikc, lp, sh, O);
     }
 }
 
-constexpr int FS_HX = 8;                                    // x halo: 2 (Gaussian) + 1 (Scharr) + NS (FED) <= 7, multiple of 4
-constexpr int FS_XV = 256 - 2 * FS_HX;
+// x halo: 2 (Gaussian) + 1 (Scharr) + NS (FED), a multiple of 4, at least 8; stored strip width
+constexpr int fs_hx(int ns) { return ns + 3 <= 8 ? 8 : (ns + 3 + 3) & ~3; }
+constexpr int fs_xv(int ns) { return 64 * fed_lane_px(ns) - 2 * fs_hx(ns); }
 
 // grid: hak_xcd_grid(strips, strip-row groups, images); a block's four waves take four consecutive row segments
 template <typename V, int NS, bool WRITE_G, bool DEC, bool WRITE_SM>
@@ -282,6 +289,7 @@ __global__ __launch_bounds__(256) void k_fed_sf(const V* __restrict__ src, V* __
                                                 FedFacs<V, NS> fac, SfTaps<V> kk, const HakImgState* __restrict__ state, int octave,
                                                 float fixed_ikc, int ry, int nbx, int nby, int nimg, int lp, int sh)
 {
+    constexpr int W = fed_lane_px(NS), HX = fs_hx(NS), XV = fs_xv(NS);
     int bx, by, img;
     if (!hak_xcd_decode(nbx, nby, nimg, bx, by, img)) return;
     const V* L = src + (long)img * stride;
@@ -291,12 +299,12 @@ __global__ __launch_bounds__(256) void k_fed_sf(const V* __restrict__ src, V* __
     const float ikc = state ? state[img].ikc[octave] : fixed_ikc;
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int x0 = bx * FS_XV - FS_HX + 4 * lane;           // first pixel of this lane (may lie outside the image)
+    const int x0 = bx * XV - HX + W * lane;                 // first pixel of this lane (may lie outside the image)
     const int ybeg = (by * 4 + wv) * ry;
     if (ybeg >= h) return;                                  // wave-uniform
     const int yend = min(ybeg + ry, h);
-    const bool owns = 4 * lane >= FS_HX && 4 * lane < FS_HX + FS_XV && x0 < w && x0 >= 0;
-    if (bx == 0 || (bx + 1) * FS_XV + FS_HX >= w) fs_strip<V, NS, true, WRITE_G, DEC, WRITE_SM>(L, SMO, GO, D, w, h, p, fac, kk, ikc, x0, ybeg, yend, owns, lp, sh);
+    const bool owns = W * lane >= HX && W * lane < HX + XV && x0 < w && x0 >= 0;
+    if (bx == 0 || (bx + 1) * XV + HX >= w) fs_strip<V, NS, true, WRITE_G, DEC, WRITE_SM>(L, SMO, GO, D, w, h, p, fac, kk, ikc, x0, ybeg, yend, owns, lp, sh);
     else fs_strip<V, NS, false, WRITE_G, DEC, WRITE_SM>(L, SMO, GO, D, w, h, p, fac, kk, ikc, x0, ybeg, yend, owns, lp, sh);
 }
 
@@ -311,7 +319,8 @@ void launch_fs(hipStream_t st, const V* src, V* smooth, V* flow, V* dst, long st
         if constexpr (std::is_same<V, float>::value) fac.f[k] = 0.5f * tau[k];      // akazed.cu:2515
         else fac.f[k] = (int)(0.5f * tau[k] * 65536 + 0.5f);                        // akazed.cu:4235
     }
-    const int gx = (w + FS_XV - 1) / FS_XV;
+    constexpr int XV = fs_xv(NS);
+    const int gx = (w + XV - 1) / XV;
     // rows per wave: tall segments amortise the NS+4 warm-up rows; shrink while the grid cannot fill the chip
     const int ry = hak_stream_rows(h, (long)gx * nimg, 8);
     const int gy = (h + 4 * ry - 1) / (4 * ry);
@@ -335,7 +344,9 @@ bool launch_fs_any(hipStream_t st, const V* src, V* smooth, V* flow, V* dst, lon
                    SfTaps<V> kk, int diffusivity, const float* tau, int ns, const HakImgState* state, int octave, float fixed_ikc,
                    bool write_g, int sp = 0, int sh = 0)
 {
-    if (diffusivity != HAK_PM_G2 || (w & 3) || w < 16 || h < 8 || ns < 1 || ns > 4) return false;
+    // (the integer FAST sequence keeps the 4-px rule: hak_sequence.hip caps its max_fuse, and no deeper int kernel is built)
+    constexpr int max_ns = std::is_same<V, float>::value ? HAK_FED_MAX_FUSE : HAK_FED_WIDE_STEPS;
+    if (diffusivity != HAK_PM_G2 || (w & 3) || w < 16 || h < 8 || ns < 1 || ns > max_ns) return false;
     if (!smooth && (sp > 0 || !std::is_same<V, float>::value)) return false;       // not stored: float sublevels only
     // smooth and g are addressed as 32-bit byte offsets from the lower of them: plane offset + plane size < the marker
     if ((write_g && smooth ? (flow < smooth ? smooth - flow : flow - smooth) : 0L) + (long)h * p >= (long)HAK_BUF_OOB / (long)sizeof(V)) return false;
@@ -343,7 +354,17 @@ bool launch_fs_any(hipStream_t st, const V* src, V* smooth, V* flow, V* dst, lon
     case 1: launch_fs<V, 1>(st, src, smooth, flow, dst, stride, w, h, p, nimg, kk, tau, state, octave, fixed_ikc, write_g, sp, sh); break;
     case 2: launch_fs<V, 2>(st, src, smooth, flow, dst, stride, w, h, p, nimg, kk, tau, state, octave, fixed_ikc, write_g, sp, sh); break;
     case 3: launch_fs<V, 3>(st, src, smooth, flow, dst, stride, w, h, p, nimg, kk, tau, state, octave, fixed_ikc, write_g, sp, sh); break;
-    default: launch_fs<V, 4>(st, src, smooth, flow, dst, stride, w, h, p, nimg, kk, tau, state, octave, fixed_ikc, write_g, sp, sh); break;
+    case 4: launch_fs<V, 4>(st, src, smooth, flow, dst, stride, w, h, p, nimg, kk, tau, state, octave, fixed_ikc, write_g, sp, sh); break;
+    default:
+        if constexpr (std::is_same<V, float>::value) {
+            switch (ns) {
+            case 5: launch_fs<V, 5>(st, src, smooth, flow, dst, stride, w, h, p, nimg, kk, tau, state, octave, fixed_ikc, write_g, sp, sh); break;
+            case 6: launch_fs<V, 6>(st, src, smooth, flow, dst, stride, w, h, p, nimg, kk, tau, state, octave, fixed_ikc, write_g, sp, sh); break;
+            case 7: launch_fs<V, 7>(st, src, smooth, flow, dst, stride, w, h, p, nimg, kk, tau, state, octave, fixed_ikc, write_g, sp, sh); break;
+            default: launch_fs<V, 8>(st, src, smooth, flow, dst, stride, w, h, p, nimg, kk, tau, state, octave, fixed_ikc, write_g, sp, sh); break;
+            }
+        }
+        break;
     }
     return true;
 }

@@ -32,6 +32,15 @@ int hak_op_kcontrast(const float* d_smooth, int w, int h, int p, float per, floa
 int hak_op_flow(const float* d_src, float* d_dst, int w, int h, int p, int diffusivity, float kcontrast); /* hFlow 2487 */
 int hak_op_nld_steps(const float* d_src, const float* d_flow, float* d_dst, float* d_tmp,
                      int w, int h, int p, const float* tau, int nsteps);                                  /* hNldStep 2509, n steps */
+/* hak_op_nld_steps on a batch: image i's planes lie `stride` elements behind image i-1's */
+int hak_op_nld_steps_batch(const float* d_src, const float* d_flow, float* d_dst, float* d_tmp, long stride,
+                           int w, int h, int p, int nimg, const float* tau, int nsteps);
+/* one whole FED cycle as the launch sequence runs it on large batches: hLowPass(var 1) + hFlow(PM_G2) + the first group of steps
+ * in one launch (head != 0: hDownWithSmooth of the sw x sh source plane first, akaze.cpp:369-392), then the remaining groups.
+ * d_smooth and d_dst receive the low-pass and L after nsteps steps; kcontrast: one factor per image (host).  Fails when the
+ * fused kernel does not cover the case. */
+int hak_op_fed_cycle(const float* d_src, int head, int sw, int sh, int sp, float* d_smooth, float* d_flow, float* d_dst, float* d_tmp,
+                     long stride, int w, int h, int p, int nimg, const float* kcontrast, const float* tau, int nsteps);
 /* self-check of the conductivity's fast reciprocal (csrc/fed_common.h hak_rcp_newton): counts the floats with bit patterns
  * in [lo_bits, hi_bits) whose 3-instruction reciprocal differs from the IEEE quotient 1.0f / d.  Must be 0 on [1, 2^64). */
 int hak_op_rcp_check(unsigned lo_bits, unsigned hi_bits, unsigned long long* mismatches);
