@@ -46,6 +46,9 @@ assert MATCH_PAIR_DTYPE.itemsize == 32
 HOMOGRAPHY_DTYPE = np.dtype([("H", "<f4", (9,)), ("inliers", "<i4"), ("hypothesis", "<i4"), ("refined", "<i4"),
                              ("n", "<i4")])                                                   # hak_homography
 assert HOMOGRAPHY_DTYPE.itemsize == 52
+FUNDAMENTAL_DTYPE = np.dtype([("F", "<f4", (9,)), ("inliers", "<i4"), ("hypothesis", "<i4"), ("root", "<i4"),
+                              ("n", "<i4")])                                                  # hak_fundamental
+assert FUNDAMENTAL_DTYPE.itemsize == 52
 
 
 class HakError(RuntimeError):
@@ -97,6 +100,8 @@ SYMBOLS = {
     "hak_match_knn2_batch": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp]),
     "hak_find_homography": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_float, C.c_uint, C.c_int, _vp, _vp]),
     "hak_find_homography_batch": (C.c_int, [_vp, _vp, C.c_long, _vp, C.c_int, C.c_int, C.c_float, C.c_uint, C.c_int, _vp, _vp]),
+    "hak_find_fundamental": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_float, C.c_uint, _vp, _vp]),
+    "hak_find_fundamental_batch": (C.c_int, [_vp, _vp, C.c_long, _vp, C.c_int, C.c_int, C.c_float, C.c_uint, _vp, _vp]),
     "hak_match_guided": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _fp, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _ip, _vp]),
     "hak_match_guided_batch": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp]),
     "hak_points_alloc": (C.c_int, [C.POINTER(_vp), C.c_int]),
@@ -546,4 +551,24 @@ def findHomography(matches, iterations=1024, threshold=3.0, seed=0, refine=True,
     out = np.zeros((), HOMOGRAPHY_DTYPE)
     check(lib.hak_find_homography(ctx, d_m.data_ptr(), n, int(iterations), float(threshold), int(seed) & 0xFFFFFFFF, int(bool(refine)),
                                   d_mask.data_ptr(), out.ctypes.data))
+    return out, d_mask[:n].cpu().numpy()
+
+
+def findFundamental(matches, iterations=1024, threshold=1.0, seed=0, akazer=None):
+    """RANSAC fundamental matrix over a match list (hipakaze.h hak_find_fundamental), on the device.  `matches` as findHomography's.
+    Returns (record of FUNDAMENTAL_DTYPE, inlier mask as a uint8 numpy array); F = record["F"].reshape(3, 3) satisfies
+    (x2, y2, 1) F (x1, y1, 1)^T = 0 for the inliers.  The seven-point model of the winning sample: there is no refit."""
+    import torch
+    ctx = akazer.ctx if akazer is not None else None
+    if isinstance(matches, torch.Tensor):
+        d_m = matches.contiguous()
+        n = d_m.numel() * d_m.element_size() // MATCH_PAIR_DTYPE.itemsize
+    else:
+        host = np.ascontiguousarray(matches, MATCH_PAIR_DTYPE)
+        n = len(host)
+        d_m = torch.from_numpy(host.view(np.uint8).reshape(-1)).cuda() if n else torch.zeros(32, dtype=torch.uint8, device="cuda")
+    d_mask = torch.zeros(max(n, 1), dtype=torch.uint8, device="cuda")
+    out = np.zeros((), FUNDAMENTAL_DTYPE)
+    check(lib.hak_find_fundamental(ctx, d_m.data_ptr(), n, int(iterations), float(threshold), int(seed) & 0xFFFFFFFF,
+                                   d_mask.data_ptr(), out.ctypes.data))
     return out, d_mask[:n].cpu().numpy()

@@ -7,6 +7,8 @@ pair(w, h, seed)   -> (img1, img2): img2 = img1 warped by a fixed small homograp
                      (3 deg rotation, 1.05 scale, 20 px shift), bilinear.
 to_float(u8)       -> float32 in [0,1] exactly as main.cpp:149 (convertTo(CV_32FC1, 1.0/255.0)).
 random_descriptors -> AkazePoint arrays for the 10k x 10k matcher config.
+two_view_matches(n_in, n_out, seed) -> (records, inlier flags, F_true): matches of a 3-D point cloud seen by two pinhole
+                     cameras with a known relative pose, plus uniformly random outlier records.
 """
 import numpy as np
 
@@ -110,3 +112,48 @@ def random_descriptors(n, seed, dtype, planted_from=None, nplanted=0, maxflip=40
                 f[i, b >> 3] ^= np.uint8(1 << (b & 7))
         pts["features"][dst] = f
     return pts
+
+
+def two_view_matches(n_in, n_out, seed, w=1920, h=1080, focal=1500.0, noise=0.0, depth=(4.0, 12.0)):
+    """Matches of a two-view scene for the fundamental-matrix tests and the timing tool, pure numpy.
+
+    n_in 3-D points, uniformly random in the first camera's frustum at depths `depth`, are projected into two pinhole cameras
+    (focal length `focal` px, principal point at the image centre) with a fixed relative pose (a rotation of a few degrees about
+    all three axes and a baseline that is mostly sideways); only points that fall inside both w x h images are kept.  `noise` px of
+    Gaussian noise is added to both projections.  n_out outlier records have both ends uniformly random in the image.  The
+    records are shuffled.
+    -> (records (n_in + n_out, 4) float32 {x1, y1, x2, y2}, inlier flags (n_in + n_out,) bool,
+        F_true (3, 3) float64 with (x2 y2 1) F (x1 y1 1)^T = 0, Frobenius norm 1)"""
+    rng = np.random.default_rng(seed)
+    K = np.array([[focal, 0.0, w / 2.0], [0.0, focal, h / 2.0], [0.0, 0.0, 1.0]])
+    ax, ay, az = np.deg2rad([2.0, -5.0, 1.5])
+    Rx = np.array([[1, 0, 0], [0, np.cos(ax), -np.sin(ax)], [0, np.sin(ax), np.cos(ax)]])
+    Ry = np.array([[np.cos(ay), 0, np.sin(ay)], [0, 1, 0], [-np.sin(ay), 0, np.cos(ay)]])
+    Rz = np.array([[np.cos(az), -np.sin(az), 0], [np.sin(az), np.cos(az), 0], [0, 0, 1]])
+    R = Rz @ Ry @ Rx
+    t = np.array([-1.0, 0.05, 0.1])
+    p1 = np.zeros((0, 2))
+    p2 = np.zeros((0, 2))
+    while len(p1) < n_in:                                              # rejection: keep the points both cameras see
+        m = 2 * n_in + 16
+        z = rng.uniform(depth[0], depth[1], m)
+        px = np.stack([rng.uniform(0, w, m), rng.uniform(0, h, m), np.ones(m)], axis=1)
+        X = (np.linalg.solve(K, px.T) * z).T                            # camera-1 coordinates
+        X2 = X @ R.T + t
+        q = X2 @ K.T
+        q = q[:, :2] / q[:, 2:]
+        keep = (X2[:, 2] > 0.5) & (q[:, 0] >= 0) & (q[:, 0] < w) & (q[:, 1] >= 0) & (q[:, 1] < h)
+        p1 = np.concatenate([p1, px[keep, :2]])
+        p2 = np.concatenate([p2, q[keep]])
+    p1, p2 = p1[:n_in], p2[:n_in]
+    if noise > 0.0:
+        p1 = p1 + rng.normal(0.0, noise, p1.shape)
+        p2 = p2 + rng.normal(0.0, noise, p2.shape)
+    o = np.stack([rng.uniform(0, w, n_out), rng.uniform(0, h, n_out), rng.uniform(0, w, n_out), rng.uniform(0, h, n_out)], axis=1)
+    recs = np.concatenate([np.concatenate([p1, p2], axis=1), o]).astype(np.float32)
+    flags = np.concatenate([np.ones(n_in, bool), np.zeros(n_out, bool)])
+    perm = rng.permutation(n_in + n_out)
+    tx = np.array([[0.0, -t[2], t[1]], [t[2], 0.0, -t[0]], [-t[1], t[0], 0.0]])
+    Ki = np.linalg.inv(K)
+    F = Ki.T @ tx @ R @ Ki
+    return recs[perm], flags[perm], F / np.linalg.norm(F)

@@ -322,7 +322,7 @@ extern "C" void hak_destroy(hak_ctx* c)
         for (auto ev : p.ev) (void)hipEventDestroy(ev);
     hak_match_scratch_free(&c->msc);
     void* bufs[] = {c->arena, c->maps, c->bitmap, c->rowcount, c->cand, c->state, c->d_num, c->dtab, c->knn, c->d_cnt, c->perm, c->pair_pts,
-                    c->hom_slots, c->hom_rec, c->sel.st, c->sel.bins, c->sel.tie, c->grid.st, c->grid.count, c->grid.comp, c->guided};
+                    c->hom_slots, c->hom_rec, c->fund_models, c->fund_rec, c->sel.st, c->sel.bins, c->sel.tie, c->grid.st, c->grid.count, c->grid.comp, c->guided};
     for (void* b : bufs) (void)hipFree(b);
     if (c->h_num) (void)hipHostFree(c->h_num);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -743,6 +743,75 @@ extern "C" int hak_find_homography_batch(hak_ctx* c, const hak_match_pair* d_mat
     hak_launch_homography(c->stream, d_matches, stride, d_counts, 0, npairs, iterations, threshold, seed, refine, c->hom_slots, d_out,
                           d_masks, stride);
     if (hipGetLastError() != hipSuccess) return fail("homography launch failed");
+    return 0;
+}
+
+// ----------------------------------------------------------- RANSAC fundamental matrix (kernels_fundamental.hip)
+// grow-only, outside a launch sequence, as homography_scratch (whose slots it shares)
+static int fundamental_scratch(hak_ctx* c, long slots, long words)
+{
+    if (homography_scratch(c, slots)) return 1;
+    if (words > c->fund_cap) {
+        if (c->fund_models) HIP_TRY(hipFree(c->fund_models));
+        c->fund_models = nullptr;
+        c->fund_cap = 0;
+        HIP_TRY(hipMalloc((void**)&c->fund_models, sizeof(unsigned) * (size_t)words));
+        c->fund_cap = words;
+    }
+    if (!c->fund_rec) HIP_TRY(hipMalloc((void**)&c->fund_rec, sizeof(hak_fundamental)));
+    return 0;
+}
+
+extern "C" int hak_find_fundamental(hak_ctx* c, const hak_match_pair* d_matches, int n, int iterations, float threshold,
+                                    unsigned seed, unsigned char* d_mask, hak_fundamental* h_out)
+{
+    if (!h_out || (!d_matches && n > 0)) return fail("null argument");
+    if (n < 0) return fail("n < 0");
+    if ((reinterpret_cast<uintptr_t>(d_matches) & 15) != 0) return fail("d_matches must be 16-byte aligned");
+    if (homography_args(iterations, threshold, 0)) return 1;
+    if (hak_device_count() == 0) return fail("no HIP device: libhipakaze has no CPU fallback");
+    const long slots = hak_homography_blocks(1, iterations, nullptr), words = hak_fundamental_words(1, iterations);
+    unsigned long long* d_slots = nullptr;
+    unsigned* d_models = nullptr;
+    hak_fundamental* d_rec = nullptr;
+    if (c) {
+        if (fundamental_scratch(c, slots, words)) return 1;
+        d_slots = c->hom_slots;
+        d_models = c->fund_models;
+        d_rec = c->fund_rec;
+    } else {
+        // one allocation: slots | record (64 bytes) | models
+        char* p = nullptr;
+        HIP_TRY(hipMalloc((void**)&p, sizeof(unsigned long long) * (size_t)slots + 64 + sizeof(unsigned) * (size_t)words));
+        d_slots = reinterpret_cast<unsigned long long*>(p);
+        d_rec = reinterpret_cast<hak_fundamental*>(p + sizeof(unsigned long long) * (size_t)slots);
+        d_models = reinterpret_cast<unsigned*>(p + sizeof(unsigned long long) * (size_t)slots + 64);
+    }
+    hipStream_t st = c ? c->stream : nullptr;
+    order_after_null_stream(c, st);
+    hak_launch_fundamental(st, d_matches, n, nullptr, n, 1, iterations, threshold, seed, d_models, d_slots, d_rec, d_mask, 0);
+    int rc = 0;
+    if (hipGetLastError() != hipSuccess) rc = fail("fundamental launch failed");
+    if (!rc && hipStreamSynchronize(st) != hipSuccess) rc = fail("hipStreamSynchronize(fundamental)");
+    if (!rc && hipMemcpy(h_out, d_rec, sizeof(hak_fundamental), hipMemcpyDeviceToHost) != hipSuccess) rc = fail("fundamental download");
+    if (!c) (void)hipFree(d_slots);
+    return rc;
+}
+
+extern "C" int hak_find_fundamental_batch(hak_ctx* c, const hak_match_pair* d_matches, long stride, const int* d_counts, int npairs,
+                                          int iterations, float threshold, unsigned seed, hak_fundamental* d_out,
+                                          unsigned char* d_masks)
+{
+    if (!c || !d_matches || !d_counts || !d_out || npairs < 1 || stride < 1) return fail("bad argument");
+    if ((reinterpret_cast<uintptr_t>(d_matches) & 15) != 0) return fail("d_matches must be 16-byte aligned");
+    if (homography_args(iterations, threshold, 0)) return 1;
+    if (fundamental_scratch(c, (long)npairs * hak_homography_blocks(npairs, iterations, nullptr),
+                            hak_fundamental_words(npairs, iterations)))
+        return 1;
+    order_after_null_stream(c, c->stream);
+    hak_launch_fundamental(c->stream, d_matches, stride, d_counts, 0, npairs, iterations, threshold, seed, c->fund_models,
+                           c->hom_slots, d_out, d_masks, stride);
+    if (hipGetLastError() != hipSuccess) return fail("fundamental launch failed");
     return 0;
 }
 

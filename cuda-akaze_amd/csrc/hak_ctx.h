@@ -76,6 +76,9 @@ struct hak_ctx {
     unsigned long long* hom_slots = nullptr;  // RANSAC scratch: best key per (pair, score block), grown on demand
     long hom_cap = 0;
     hak_homography* hom_rec = nullptr;        // the record of hak_find_homography before its download
+    unsigned* fund_models = nullptr;          // hak_find_fundamental scratch: 28 words per (pair, hypothesis), grown on demand
+    long fund_cap = 0;                        // (its slots are hom_slots: both run on the context's stream)
+    hak_fundamental* fund_rec = nullptr;      // the record of hak_find_fundamental before its download
     void* guided = nullptr;         // guided-matching scratch (kernels_guided.hip): grown on demand, outside a launch sequence
     size_t guided_cap = 0;
     hak_point* pair_pts = nullptr;  // [2][cfg.max_pts]: the contiguous pair layout hak_detect_and_compute_pair detects into and matches on

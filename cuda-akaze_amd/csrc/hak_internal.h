@@ -761,6 +761,13 @@ void hak_launch_homography(hipStream_t st, const hak_match_pair* matches, long s
                            int iterations, float threshold, unsigned seed, int refine, unsigned long long* slots,
                            hak_homography* out, unsigned char* masks, long mask_stride);
 
+// RANSAC fundamental matrix (kernels_fundamental.hip): the score blocks are hak_homography_blocks'; `models` is scratch of
+// hak_fundamental_words(npairs, iterations) 32-bit words (28 per hypothesis), `slots` as above
+long hak_fundamental_words(int npairs, int iterations);
+void hak_launch_fundamental(hipStream_t st, const hak_match_pair* matches, long stride, const int* counts, int n_host, int npairs,
+                            int iterations, float threshold, unsigned seed, unsigned* models, unsigned long long* slots,
+                            hak_fundamental* out, unsigned char* masks, long mask_stride);
+
 // A launcher that cannot do what it was asked (a precondition its caller should have checked) records the reason here instead
 // of aborting; enqueue_detect turns it into the call's error (hak_sequence.hip).  Thread-local, like hak_last_error().
 void hak_note_launch_error(const char* msg);

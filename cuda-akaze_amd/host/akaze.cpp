@@ -109,6 +109,26 @@ namespace akaze
         return r.inliers;
     }
 
+    int cuFindFundamental(const hak_match_pair* matches, int n, float F[9], unsigned char* inlier_mask, int iterations, float threshold,
+                          unsigned seed)
+    {
+        if (n < 0 || (n > 0 && !matches) || !F) { fprintf(stderr, "hip-akaze: cuFindFundamental: bad argument\n"); exit(-1); }
+        hak_match_pair* d_matches = nullptr;
+        unsigned char* d_mask = nullptr;
+        if (n > 0) {
+            if (hipMalloc((void**)&d_matches, sizeof(hak_match_pair) * (size_t)n) != hipSuccess) die("cuFindFundamental alloc");
+            if (inlier_mask && hipMalloc((void**)&d_mask, (size_t)n) != hipSuccess) die("cuFindFundamental alloc");
+            if (hak_memcpy_h2d(d_matches, matches, (long)(sizeof(hak_match_pair) * (size_t)n))) die("cuFindFundamental upload");
+        }
+        hak_fundamental r;
+        if (hak_find_fundamental(NULL, d_matches, n, iterations, threshold, seed, d_mask, &r)) die("cuFindFundamental");
+        if (d_mask && hak_memcpy_d2h(inlier_mask, d_mask, n)) die("cuFindFundamental download");
+        for (int k = 0; k < 9; k++) F[k] = r.F[k];
+        if (d_mask) (void)hipFree(d_mask);
+        if (d_matches) (void)hipFree(d_matches);
+        return r.inliers;
+    }
+
     Akazer::Akazer() { hak_default_config(&cfg); }
 
     Akazer::~Akazer() { hak_destroy(ctx); }                              // akaze.cpp:74-77

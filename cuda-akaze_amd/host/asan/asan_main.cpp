@@ -45,6 +45,16 @@ int main()
         std::vector<hak_match_pair> pairs(d1.num_pts);
         REQUIRE(cuMatchKnn(d1, d2, pairs.data()) == (d1.num_pts + 1) / 2 && pairs[1].query == 2);
         REQUIRE(cuMatchKnn(d1, d2, NULL) == (d1.num_pts + 1) / 2);
+        {                                                           // RANSAC over the host list: exact-size buffers
+            const int np = (d1.num_pts + 1) / 2;
+            std::vector<unsigned char> mask(np);
+            float H[9], F[9];
+            REQUIRE(cuFindHomography(pairs.data(), np, H, mask.data()) == (np + 1) / 2 && mask[2] == 1 && mask[1] == 0);
+            REQUIRE(cuFindFundamental(pairs.data(), np, F, mask.data()) == (np + 2) / 3 && mask[3] == 1 && mask[1] == 0 && F[7] == 1.f);
+            REQUIRE(cuFindFundamental(pairs.data(), np, F) == (np + 2) / 3);
+            REQUIRE(cuFindFundamental(pairs.data(), 6, F, mask.data()) == 0 && F[7] == 0.f && mask[0] == 0);
+            REQUIRE(cuFindFundamental(NULL, 0, F) == 0);
+        }
         cuMatch(d1, hostless);                                      // train side without a host buffer
         d2.num_pts = 0;
         cuMatch(d1, d2);                                            // empty train set (D10)

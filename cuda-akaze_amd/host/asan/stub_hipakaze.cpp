@@ -115,7 +115,20 @@ int hak_find_homography(hak_ctx*, const hak_match_pair* d, int n, int iterations
     }
     return 0;
 }
-// the HIP runtime calls of cuMatchKnn and cuFindHomography
+// as hak_find_homography's stub: every record read, every mask byte written; "inliers" are the indices that are multiples of 3
+int hak_find_fundamental(hak_ctx*, const hak_match_pair* d, int n, int iterations, float threshold, unsigned, unsigned char* mask,
+                         hak_fundamental* out)
+{
+    if (!out || (n > 0 && !d) || iterations < 1 || !(threshold > 0.f)) { g_err = "bad argument"; return 1; }
+    *out = hak_fundamental{{0.f, 0.f, 0.f, 0.f, 0.f, n >= 7 ? -1.f : 0.f, 0.f, n >= 7 ? 1.f : 0.f, 0.f}, 0, n >= 7 ? 0 : -1, 0, n};
+    for (int i = 0; i < n; i++) {
+        const bool in = n >= 7 && d[i].x1 == d[i].x1 && i % 3 == 0;
+        out->inliers += in;
+        if (mask) mask[i] = in;
+    }
+    return 0;
+}
+// the HIP runtime calls of cuMatchKnn, cuFindHomography and cuFindFundamental
 hipError_t hipMalloc(void** p, size_t n) { *p = malloc(n); return *p ? hipSuccess : hipErrorOutOfMemory; }
 hipError_t hipFree(void* p) { free(p); return hipSuccess; }
 }

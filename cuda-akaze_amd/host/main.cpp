@@ -3,7 +3,7 @@
 // `nrepeats` times and cuMatch once, and prints the same five result lines.
 //
 //   hipakaze_demo [device] [left.pgm right.pgm] [nrepeats] [--dump file] [--api-checks] [--pair] [--homography] [--retain-best N]
-//                 [--retain-grid G] [--guided R]
+//                 [--retain-grid G] [--guided R] [--fundamental]
 //
 // --dump file   writes the host-side results as raw 104-byte AkazePoint records:
 //               int32 n1, n2, then n1 + n2 records of the float path (image 1 after cuMatch),
@@ -18,6 +18,9 @@
 // --guided R   implies --homography; after RANSAC re-matches the pair under that homography (cuMatchGuided: every keypoint of image 1
 //               is searched only within R pixels of where H sends it; ratio 4/5 + cross-check inside that neighbourhood), runs
 //               cuFindHomography again on the guided list and prints both match and inlier counts
+// --fundamental  after the 2-NN match, estimates the fundamental matrix between the two images from its matches (cuFindFundamental:
+//               RANSAC, 1024 seven-point hypotheses, Sampson distance < 1 px, seed 0, no refit) and prints it; with --dump, appends
+//               after everything else int32 n, int32 inliers, float32 F[9], the n hak_match_pair records and the n inlier-mask bytes
 // --retain-best N  both AkazeData get capacity N (instead of 10000) and Akazer::setRetainBest(true): an image with more keypoints
 //               keeps its N strongest (hak_set_retain_best), in raster order, on the float and the FAST path alike
 // --retain-grid G  Akazer::setRetainGrid(G), G in 8..128: an image with more keypoints than the capacity (N of --retain-best, else
@@ -94,7 +97,7 @@ int main(int argc, char** argv)
     }
     std::cout << "===== Registration by HIP-AKAZE (MI355X) =====" << std::endl;
     std::string dumpPath;
-    bool apiChecks = false, pairCalls = false, homography = false;
+    bool apiChecks = false, pairCalls = false, homography = false, fundamental = false;
     int retainBest = 0, retainGrid = 0;
     float guided = 0.f;
     {   // strip the options; what is left are the reference demo's positional arguments (main.cpp:131-135)
@@ -104,6 +107,7 @@ int main(int argc, char** argv)
             else if (!strcmp(argv[i], "--api-checks")) apiChecks = true;
             else if (!strcmp(argv[i], "--pair")) pairCalls = true;
             else if (!strcmp(argv[i], "--homography")) homography = true;
+            else if (!strcmp(argv[i], "--fundamental")) fundamental = true;
             else if (!strcmp(argv[i], "--guided") && i + 1 < argc) { guided = (float)std::atof(argv[++i]); homography = true; }
             else if (!strcmp(argv[i], "--retain-best") && i + 1 < argc) retainBest = std::atoi(argv[++i]);
             else if (!strcmp(argv[i], "--retain-grid") && i + 1 < argc) retainGrid = std::atoi(argv[++i]);
@@ -200,6 +204,18 @@ int main(int argc, char** argv)
         for (int r = 0; r < 3; r++)
             std::cout << "  [" << hom[3 * r] << ", " << hom[3 * r + 1] << ", " << hom[3 * r + 2] << "]" << std::endl;
     }
+    float fund[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    std::vector<unsigned char> finlier(good.size(), 0);
+    int nfinlier = 0;
+    if (fundamental) {
+        float t6 = timer.read();
+        nfinlier = akaze::cuFindFundamental(good.data(), ngood, fund, finlier.data());
+        float t7 = timer.read();
+        std::cout << "Fundamental matrix (RANSAC 1024 x 1 px Sampson, no refit): " << nfinlier << " inliers of " << ngood << "  ("
+                  << t7 - t6 << " ms)" << std::endl;
+        for (int r = 0; r < 3; r++)
+            std::cout << "  [" << fund[3 * r] << ", " << fund[3 * r + 1] << ", " << fund[3 * r + 2] << "]" << std::endl;
+    }
     if (guided > 0.f) {
         std::vector<hak_match_pair> gm(good.size());
         float t8 = timer.read();
@@ -277,6 +293,14 @@ int main(int argc, char** argv)
         dump.write((const char*)hom, sizeof(hom));
         dump.write((const char*)good.data(), sizeof(hak_match_pair) * (size_t)ngood);
         dump.write((const char*)inlier.data(), (size_t)ngood);
+    }
+
+    if (fundamental && dump.is_open()) {
+        const int hdr[2] = {ngood, nfinlier};
+        dump.write((const char*)hdr, sizeof(hdr));
+        dump.write((const char*)fund, sizeof(fund));
+        dump.write((const char*)good.data(), sizeof(hak_match_pair) * (size_t)ngood);
+        dump.write((const char*)finlier.data(), (size_t)ngood);
     }
 
     akaze::freeAkazeData(akaze_data1);

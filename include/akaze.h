@@ -26,6 +26,12 @@ namespace akaze
     int cuFindHomography(const hak_match_pair* matches, int n, float H[9], unsigned char* inlier_mask = nullptr, int iterations = 1024,
                          float threshold = 3.f, unsigned seed = 0, bool refine = true);
 
+    // build-side addition: RANSAC fundamental matrix over a host match list, on the device (hak_find_fundamental): writes F (row-major,
+    // (x2 y2 1) F (x1 y1 1)^T = 0, largest |entry| 1; all zero when there is no model) and, when inlier_mask is not NULL, n bytes
+    // (1 = inlier of F: Sampson distance below `threshold` px); returns the inlier count.  The winning seven-point model, no refit.
+    int cuFindFundamental(const hak_match_pair* matches, int n, float F[9], unsigned char* inlier_mask = nullptr, int iterations = 1024,
+                          float threshold = 1.f, unsigned seed = 0);
+
     // build-side addition: guided matching (hak_match_guided) -- re-matches result1 against result2 under a homography H (row-major,
     // (x1, y1, 1) -> image 2, e.g. cuFindHomography's): every keypoint of result1 is searched only among the keypoints of result2
     // within `radius` pixels of where H sends it, ratio test and cross-check inside that neighbourhood.  Fills result1 like cuMatch

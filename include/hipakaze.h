@@ -250,6 +250,61 @@ int hak_find_homography_batch(hak_ctx* ctx, const hak_match_pair* d_matches, lon
                               int iterations, float threshold, unsigned seed, int refine, hak_homography* d_out,
                               unsigned char* d_masks);
 
+/* ---- geometric verification of a match list: RANSAC fundamental matrix (build-side addition).  The epipolar model of two
+ * views of a 3-D scene, x2^T F x1 = 0, next to the homography of a plane or a rotating camera; its inlier mask is the outlier
+ * filter of stereo, SfM and SLAM front ends.  A pure function of (matches, iterations, threshold, seed);
+ * tests/fundamental_ref.py is its bit-exact numpy statement.  Input as hak_find_homography; a record with a non-finite
+ * coordinate is never an inlier and makes any sample it is in degenerate.
+ *   1. Hypothesis h (0 <= h < iterations, 1 <= iterations <= 65536) draws r_d = mix64(seed + (32 h + d + 1) * 0x9E3779B97F4A7C15)
+ *      for d = 0..31 and takes index ((r_d >> 32) * n) >> 32 unless already chosen, until it has seven.  It is degenerate with
+ *      fewer than seven distinct indices (always when n < 7).
+ *   2. float64, no FMA, sums over the sample in draw order starting from 0: per image the centroid c = sum / 7, d_k = p_k - c,
+ *      q = sum (dx dx + dy dy), s = sqrt(14 / q), normalised point s d_k.  Degenerate if q is 0 or s is non-finite.
+ *   3. The 7 x 9 system has the row [u x, u y, u, v x, v y, v, x, y, 1] per point, (x, y) the normalised point of image 1 and
+ *      (u, v) that of image 2.  Gaussian elimination with partial pivoting over rows only, pivot columns 0..6 in order: the pivot
+ *      of column c is the largest |entry| of rows c..6, ties to the smallest row; degenerate if it is 0 or non-finite;
+ *      f = M[r][c] / M[c][c], M[r][q] = M[r][q] - f M[c][q].  Two null vectors by back substitution, i = 6..0:
+ *      f_i = ((-M[i][free]) - M[i][i+1] f_(i+1) - .. - M[i][6] f_6) / M[i][i] (subtractions in ascending j): A with
+ *      (f7, f8) = (1, 0), free = 7, and B with (f7, f8) = (0, 1), free = 8.  This is an F8-normalised parametrisation inside the
+ *      sample: a sample whose leading 7 x 7 block is ill-conditioned is not re-pivoted over columns, it simply scores badly.
+ *   4. det(a A + B) = c3 a^3 + c2 a^2 + c1 a + c0: c3 = det A, c0 = det B, c2 = (d0 + d1) + d2 with d_i = det(A with row i taken
+ *      from B), c1 likewise with A and B exchanged; det m = (m0 (m4 m8 - m5 m7) - m1 (m3 m8 - m5 m6)) + m2 (m3 m7 - m4 m6).
+ *      Degenerate if c3 is 0 or a coefficient is non-finite.
+ *   5. Real roots with + - * / sqrt only: b_k = c_k / c3, q(a) = ((a + b2) a + b1) a + b0, B = 1 + max |b_k| (degenerate if a b_k
+ *      or B is non-finite), D = b2 b2 - 3 b1.  D > 0: s = sqrt(D), t1 = (-b2 - s) / 3, t2 = (-b2 + s) / 3, brackets [-B, t1],
+ *      [t1, t2], [t2, B]; otherwise the one bracket [-B, B].  A bracket holds a root iff (q(lo) < 0) != (q(hi) < 0); there, 64
+ *      bisections: mid = 0.5 (lo + hi) replaces lo when (q(mid) < 0) == (q(lo_0) < 0), lo_0 the bracket's original lower end,
+ *      and hi otherwise; the root is 0.5 (lo + hi).  Roots are numbered 0.. in bracket order (one or three; a double root
+ *      comes out as two nearly equal ones).
+ *   6. Per root: Fn[k] = a A[k] + B[k], F = T2^T (Fn T1) with T = [s 0 -(s cx); 0 s -(s cy); 0 0 1], each product
+ *      C[i][j] = (A[i][0] B[0][j] + A[i][1] B[1][j]) + A[i][2] B[2][j]; divided by its entry of largest |value| (ties to the
+ *      smallest index) and rounded to float32.  The model is dropped if that entry is 0 or anything is non-finite.
+ *   7. float32, no FMA, Sampson distance: a = (F0 x1 + F1 y1) + F2, b = (F3 x1 + F4 y1) + F5, c = (F6 x1 + F7 y1) + F8,
+ *      e = (a x2 + b y2) + c, p = (F0 x2 + F3 y2) + F6, q = (F1 x2 + F4 y2) + F7, den = (a a + b b) + (p p + q q);
+ *      inlier iff e e < t2 den, t2 = threshold * threshold (threshold finite, > 0; NaN fails).
+ *   8. The model with the most inliers wins, ties to the smallest h, then the smallest root.
+ * Output: hypothesis = -1 means no model (F all zero, inliers = 0, mask all zero).  The optional mask gets 1 for every inlier of
+ * the returned F, 0 otherwise (n bytes).  There is NO least-squares refit: F is the winning seven-point model, exactly rank 2 up
+ * to rounding; a rank-2 refit over the inliers needs a 9 x 9 eigen-solve and is left to the caller.  Refused with a non-zero
+ * status and a message before any device is touched: iterations outside 1..65536, a threshold that is not finite or not > 0,
+ * n < 0, a NULL list with n > 0, NULL h_out / d_out / d_counts, npairs < 1, stride < 1, a NULL context for the batch form.
+ * Device code: csrc/kernels_fundamental.hip. */
+typedef struct hak_fundamental {
+    float F[9];              /* row-major, (x2 y2 1) F (x1 y1 1)^T = 0; the entry of largest |value| is 1 */
+    int   inliers;           /* inliers of F */
+    int   hypothesis;        /* winning hypothesis, -1 = no model (F = 0, inliers = 0) */
+    int   root;              /* which real root of the winner's cubic (0..2) */
+    int   n;                 /* matches considered */
+} hak_fundamental;           /* 52 bytes, as hak_homography */
+/* one list, synchronous; ctx may be NULL (default stream; the call allocates its own scratch); result to *h_out (host) */
+int hak_find_fundamental(hak_ctx* ctx, const hak_match_pair* d_matches, int n, int iterations, float threshold, unsigned seed,
+                         unsigned char* d_mask, hak_fundamental* h_out);
+/* batched, asynchronous on the context's stream, layouts as hak_find_homography_batch: the output of hak_match_knn2_batch or
+ * hak_match_guided_batch goes in without a host synchronisation */
+int hak_find_fundamental_batch(hak_ctx* ctx, const hak_match_pair* d_matches, long stride, const int* d_counts, int npairs,
+                               int iterations, float threshold, unsigned seed, hak_fundamental* d_out,
+                               unsigned char* d_masks);
+
 /* ---- guided matching: re-match a pair under its estimated homography (build-side addition; the stage behind
  * hak_find_homography).  The 2-NN search of hak_match_knn2 looks at the whole other image, so on repetitive texture its ratio
  * test rejects correct matches that lose to a look-alike elsewhere; once H is known, each query is searched only among the train
