@@ -104,6 +104,8 @@ SYMBOLS = {
     "hak_find_fundamental_batch": (C.c_int, [_vp, _vp, C.c_long, _vp, C.c_int, C.c_int, C.c_float, C.c_uint, _vp, _vp]),
     "hak_match_guided": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _fp, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _ip, _vp]),
     "hak_match_guided_batch": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp]),
+    "hak_match_epipolar": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _fp, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _ip, _vp]),
+    "hak_match_epipolar_batch": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp]),
     "hak_points_alloc": (C.c_int, [C.POINTER(_vp), C.c_int]),
     "hak_points_free": (C.c_int, [_vp]),
     "hak_image_alloc": (C.c_int, [C.POINTER(_vp), C.c_int, C.c_int, _ip]),
@@ -531,6 +533,25 @@ def cuMatchGuided(result1, result2, H, radius=8.0, ratio=(4, 5), cross_check=Tru
     check(lib.hak_match_guided(ctx, result1.d_data, n1, result2.d_data, result2.num_pts, h.ctypes.data_as(_fp), float(radius),
                                int(ratio[0]), int(ratio[1]), int(cross_check), int(max_dist), hptr, d_out.data_ptr(), C.byref(cnt),
                                h_out.ctypes.data))
+    return h_out[:cnt.value].copy()
+
+
+def cuMatchEpipolar(result1, result2, F, radius=2.0, ratio=(4, 5), cross_check=True, max_dist=0, akazer=None):
+    """Epipolar guided matching (hipakaze.h hak_match_epipolar): re-matches result1 against result2 under the fundamental matrix F
+    (9 values, row-major, (x2 y2 1) F (x1 y1 1)^T = 0, e.g. findFundamental's record["F"]): every query is searched only among the
+    train points closer than `radius` pixels to its epipolar line; ratio test and cross-check inside that band.  Updates result1
+    like cuMatch and returns the accepted matches (MATCH_PAIR_DTYPE, ascending query index)."""
+    import torch
+    ctx = akazer.ctx if akazer is not None else None
+    n1 = result1.num_pts
+    f = np.ascontiguousarray(np.asarray(F, np.float32).reshape(9))
+    d_out = torch.zeros(max(n1, 1) * MATCH_PAIR_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+    h_out = np.zeros(max(n1, 1), MATCH_PAIR_DTYPE)
+    cnt = C.c_int(0)
+    hptr = result1.h_data.ctypes.data if result1.h_data is not None else None
+    check(lib.hak_match_epipolar(ctx, result1.d_data, n1, result2.d_data, result2.num_pts, f.ctypes.data_as(_fp), float(radius),
+                                 int(ratio[0]), int(ratio[1]), int(cross_check), int(max_dist), hptr, d_out.data_ptr(), C.byref(cnt),
+                                 h_out.ctypes.data))
     return h_out[:cnt.value].copy()
 
 

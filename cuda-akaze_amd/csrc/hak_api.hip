@@ -837,16 +837,20 @@ static int guided_scratch(hak_ctx* c, size_t bytes)
     return 0;
 }
 
-extern "C" int hak_match_guided(hak_ctx* c, hak_point* d_pts1, int n1, const hak_point* d_pts2, int n2, const float* H, float radius,
-                                int ratio_num, int ratio_den, int cross_check, int max_dist, hak_point* h_pts1, hak_match_pair* d_out,
-                                int* count, hak_match_pair* h_out)
+// What the gated matchers (hak_match_guided, hak_match_epipolar) share behind their own model checks.  Single pair, synchronous:
+// search(stream, scratch, fwd) enqueues the bin step, the search and the reverse step.
+static int gated_args_single(const hak_point* d_pts1, int n1, const hak_point* d_pts2, int n2, const int* count)
 {
     if (!count) return fail("null argument");
     if (n1 < 0 || n2 < 0) return fail("negative point count");
     if ((!d_pts1 && n1 > 0) || (!d_pts2 && n2 > 0)) return fail("null point array");
-    if (!H) return fail("H is NULL");
-    for (int k = 0; k < 9; k++)
-        if (!std::isfinite(H[k])) return fail("H has a non-finite entry");
+    return 0;
+}
+template <typename Search>
+static int gated_match_single(hak_ctx* c, const char* what, hak_point* d_pts1, int n1, const hak_point* d_pts2, int n2, float radius,
+                              int ratio_num, int ratio_den, int cross_check, int max_dist, hak_point* h_pts1, hak_match_pair* d_out,
+                              int* count, hak_match_pair* h_out, Search search)
+{
     if (guided_args(radius, ratio_num, ratio_den)) return 1;
     if (h_out && !d_out) return fail("h_out needs d_out");
     if (!hak_mkey_fits(n1) || !hak_mkey_fits(n2)) return fail("more than 2^20 - 1 points");
@@ -868,32 +872,32 @@ extern "C" int hak_match_guided(hak_ctx* c, hak_point* d_pts1, int n1, const hak
     const int nb = (n1 + 1023) / 1024;
     if (!hak_match_scratch_reserve(sc, st, 0, 0, 0, (long)n1 + cap2, nb)) {
         if (!c) { pool_release(sc, false); (void)hipFree(buf); }
-        return fail("hak_match_guided: out of device memory for the search scratch");
+        return fail(std::string(what) + ": out of device memory for the search scratch");
     }
     int4* fwd = sc->knn;
     int4* rev = sc->knn + n1;
     *sc->h_cnt = -1;
     {
         ProfScope ps(c, HAK_PROF_MATCH);
-        hak_launch_guided(st, d_pts1, d_pts2, nullptr, nullptr, n1, n2, 0, 0, 1, nullptr, H, radius, cross_check ? 1 : 0,
-                          hak_guided_scratch_carve(buf, 1, cap2, rev, 0), fwd, 0);
+        search(st, hak_guided_scratch_carve(buf, 1, cap2, rev, 0), fwd);
         hak_launch_knn2_finish(st, d_pts1, d_pts2, nullptr, n1, 0, 0, 1, fwd, cross_check ? rev : nullptr, 0, ratio_num, ratio_den,
                                cross_check ? 1 : 0, max_dist, d_out, 0, sc->d_cnt, sc);
     }
     int rc = 0;
-    if (hipGetLastError() != hipSuccess) rc = fail("guided match launch failed");
-    if (!rc && hipStreamSynchronize(st) != hipSuccess) rc = fail("hipStreamSynchronize(guided match)");
+    if (hipGetLastError() != hipSuccess) rc = fail(std::string(what) + ": launch failed");
+    if (!rc && hipStreamSynchronize(st) != hipSuccess) rc = fail(std::string(what) + ": hipStreamSynchronize");
     rc = match_list_tail(c, sc, rc, h_pts1, d_pts1, n1, d_out, count, h_out);
     if (!c) (void)hipFree(buf);
     return rc;
 }
-
-extern "C" int hak_match_guided_batch(hak_ctx* c, hak_point* d_points, const int* d_num_pts, int npairs, const hak_homography* d_H,
-                                      float radius, int ratio_num, int ratio_den, int cross_check, int max_dist, hak_match_pair* d_out,
-                                      int* d_counts)
+// ... and the batch form, asynchronous on the context's stream: search(scratch, fwd, mp)
+template <typename Search>
+static int gated_match_batch(hak_ctx* c, const char* what, hak_point* d_points, const int* d_num_pts, int npairs, const void* d_model,
+                             float radius, int ratio_num, int ratio_den, int cross_check, int max_dist, hak_match_pair* d_out,
+                             int* d_counts, Search search)
 {
-    if (!c) return fail("hak_match_guided_batch needs a context");
-    if (!d_points || !d_num_pts || !d_H || !d_counts || npairs < 1) return fail("bad argument");
+    if (!c) return fail(std::string(what) + " needs a context");
+    if (!d_points || !d_num_pts || !d_model || !d_counts || npairs < 1) return fail("bad argument");
     if (2 * npairs > c->cfg.batch + 1) return fail("npairs exceeds the context's batch capacity");
     if (guided_args(radius, ratio_num, ratio_den)) return 1;
     if (max_dist <= 0) max_dist = HAK_MAX_DIST;
@@ -906,12 +910,64 @@ extern "C" int hak_match_guided_batch(hak_ctx* c, hak_point* d_points, const int
     int4* fwd = c->knn;
     int4* rev = c->knn + (size_t)npair_cap * mp;
     { ProfScope ps(c, HAK_PROF_MATCH);
-      hak_launch_guided(c->stream, d_points, d_points + mp, d_num_pts, d_num_pts + 1, (int)mp, (int)mp, 2 * mp, 2 * mp, npairs, d_H, nullptr,
-                        radius, cross_check ? 1 : 0, hak_guided_scratch_carve(c->guided, npair_cap, mp, rev, mp), fwd, mp);
+      search(hak_guided_scratch_carve(c->guided, npair_cap, mp, rev, mp), fwd, mp);
       hak_launch_knn2_finish(c->stream, d_points, d_points + mp, d_num_pts, 0, 2 * mp, 2 * mp, npairs, fwd, cross_check ? rev : nullptr,
                              mp, ratio_num, ratio_den, cross_check ? 1 : 0, max_dist, d_out, mp, d_counts); }
-    if (hipGetLastError() != hipSuccess) return fail("guided match launch failed");
+    if (hipGetLastError() != hipSuccess) return fail(std::string(what) + ": launch failed");
     return 0;
+}
+
+extern "C" int hak_match_guided(hak_ctx* c, hak_point* d_pts1, int n1, const hak_point* d_pts2, int n2, const float* H, float radius,
+                                int ratio_num, int ratio_den, int cross_check, int max_dist, hak_point* h_pts1, hak_match_pair* d_out,
+                                int* count, hak_match_pair* h_out)
+{
+    if (gated_args_single(d_pts1, n1, d_pts2, n2, count)) return 1;
+    if (!H) return fail("H is NULL");
+    for (int k = 0; k < 9; k++)
+        if (!std::isfinite(H[k])) return fail("H has a non-finite entry");
+    return gated_match_single(c, "hak_match_guided", d_pts1, n1, d_pts2, n2, radius, ratio_num, ratio_den, cross_check, max_dist, h_pts1,
+                              d_out, count, h_out, [&](hipStream_t st, const HakGuidedScratch& gs, int4* fwd) {
+                                  hak_launch_guided(st, d_pts1, d_pts2, nullptr, nullptr, n1, n2, 0, 0, 1, nullptr, H, radius,
+                                                    cross_check ? 1 : 0, gs, fwd, 0);
+                              });
+}
+
+extern "C" int hak_match_guided_batch(hak_ctx* c, hak_point* d_points, const int* d_num_pts, int npairs, const hak_homography* d_H,
+                                      float radius, int ratio_num, int ratio_den, int cross_check, int max_dist, hak_match_pair* d_out,
+                                      int* d_counts)
+{
+    return gated_match_batch(c, "hak_match_guided_batch", d_points, d_num_pts, npairs, d_H, radius, ratio_num, ratio_den, cross_check,
+                             max_dist, d_out, d_counts, [&](const HakGuidedScratch& gs, int4* fwd, long mp) {
+                                 hak_launch_guided(c->stream, d_points, d_points + mp, d_num_pts, d_num_pts + 1, (int)mp, (int)mp, 2 * mp,
+                                                   2 * mp, npairs, d_H, nullptr, radius, cross_check ? 1 : 0, gs, fwd, mp);
+                             });
+}
+
+// epipolar guided matching (kernels_epipolar.hip): a fundamental matrix in the homography's place
+extern "C" int hak_match_epipolar(hak_ctx* c, hak_point* d_pts1, int n1, const hak_point* d_pts2, int n2, const float* F, float radius,
+                                  int ratio_num, int ratio_den, int cross_check, int max_dist, hak_point* h_pts1, hak_match_pair* d_out,
+                                  int* count, hak_match_pair* h_out)
+{
+    if (gated_args_single(d_pts1, n1, d_pts2, n2, count)) return 1;
+    if (!F) return fail("F is NULL");
+    for (int k = 0; k < 9; k++)
+        if (!std::isfinite(F[k])) return fail("F has a non-finite entry");
+    return gated_match_single(c, "hak_match_epipolar", d_pts1, n1, d_pts2, n2, radius, ratio_num, ratio_den, cross_check, max_dist, h_pts1,
+                              d_out, count, h_out, [&](hipStream_t st, const HakGuidedScratch& gs, int4* fwd) {
+                                  hak_launch_epipolar(st, d_pts1, d_pts2, nullptr, nullptr, n1, n2, 0, 0, 1, nullptr, F, radius,
+                                                      cross_check ? 1 : 0, gs, fwd, 0);
+                              });
+}
+
+extern "C" int hak_match_epipolar_batch(hak_ctx* c, hak_point* d_points, const int* d_num_pts, int npairs, const hak_fundamental* d_F,
+                                        float radius, int ratio_num, int ratio_den, int cross_check, int max_dist, hak_match_pair* d_out,
+                                        int* d_counts)
+{
+    return gated_match_batch(c, "hak_match_epipolar_batch", d_points, d_num_pts, npairs, d_F, radius, ratio_num, ratio_den, cross_check,
+                             max_dist, d_out, d_counts, [&](const HakGuidedScratch& gs, int4* fwd, long mp) {
+                                 hak_launch_epipolar(c->stream, d_points, d_points + mp, d_num_pts, d_num_pts + 1, (int)mp, (int)mp, 2 * mp,
+                                                     2 * mp, npairs, d_F, nullptr, radius, cross_check ? 1 : 0, gs, fwd, mp);
+                             });
 }
 
 // ----------------------------------------------------------- memory helpers

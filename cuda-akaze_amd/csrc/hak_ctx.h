@@ -79,7 +79,7 @@ struct hak_ctx {
     unsigned* fund_models = nullptr;          // hak_find_fundamental scratch: 28 words per (pair, hypothesis), grown on demand
     long fund_cap = 0;                        // (its slots are hom_slots: both run on the context's stream)
     hak_fundamental* fund_rec = nullptr;      // the record of hak_find_fundamental before its download
-    void* guided = nullptr;         // guided-matching scratch (kernels_guided.hip): grown on demand, outside a launch sequence
+    void* guided = nullptr;         // guided-matching scratch (kernels_guided.hip, kernels_epipolar.hip): grown on demand, outside a launch sequence
     size_t guided_cap = 0;
     hak_point* pair_pts = nullptr;  // [2][cfg.max_pts]: the contiguous pair layout hak_detect_and_compute_pair detects into and matches on
     HakMatchScratch msc;            // sliced searches of one big pair (hak_match / hak_match_knn2): grows on demand, on this context's device

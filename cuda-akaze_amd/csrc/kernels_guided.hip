@@ -11,6 +11,8 @@
 //                    16 x (v_xor, v_bcnt) per passer; the two smallest packed keys (hak_mkey(d, j), hak_internal.h) give j1, d1, d2,
 //                    and an atomicMin of hak_mkey(d, i) on the train point's word gives rev(j) in the same pass
 //   k_guided_rev     reverse keys -> indices, the form k_knn2_finish reads
+// The bin and the reverse step are launchers of their own (hak_launch_guided_bin / _rev): the epipolar search of kernels_epipolar.hip
+// shares them, the scratch carve and the grid.
 // The accept rule and the compaction are the 2-NN matcher's own finish kernels (kernels_match.hip), unchanged.
 //
 // Why the result does not depend on the binning.  The grid only decides WHICH candidates a query looks at; whether a candidate
@@ -30,23 +32,10 @@
 #include "hak_internal.h"
 #include <cstddef>
 
-#define GD_N 64                  // cells per axis at most: 4096 LDS counters
 #define GD_THREADS 1024          // k_guided_bin's block
 #define GD_BOX 1048576.f         // |coordinate| beyond 2^20 does not stretch the box (such points sit in border cells)
 
-// non-decreasing in x for inv > 0; NaN lands in cell 0 (fmaxf drops it): listed there, and in no gate
-__device__ __forceinline__ int gd_cell(float x, float o, float inv, int n)
-{
-    return (int)fminf(fmaxf(floorf((x - o) * inv), 0.f), (float)(n - 1));
-}
-
-// the grid of one pair, written by k_guided_bin and read by k_guided_search
-struct GdGrid {
-    float ox, oy, inv;
-    int nx, ny;
-    int pad[3];
-};
-
+// (GD_N, GdGrid and gd_cell: hak_internal.h -- kernels_epipolar.hip searches the same grid)
 __global__ __launch_bounds__(GD_THREADS) void k_guided_bin(const hak_point* __restrict__ pts2_base, const int* __restrict__ n2_dev, int n2_host,
                                                             long stride2, int count_stride, float rp, HakGuidedScratch sc)
 {
@@ -229,6 +218,16 @@ HakGuidedScratch hak_guided_scratch_carve(void* base, long npairs, long pts_cap,
     return sc;
 }
 
+void hak_launch_guided_bin(hipStream_t st, const hak_point* pts2, const int* n2_dev, int n2_host, long stride2, int npairs, float rp,
+                           const HakGuidedScratch& sc)
+{
+    k_guided_bin<<<npairs, GD_THREADS, 0, st>>>(pts2, n2_dev, n2_host, stride2, 2, rp, sc);
+}
+void hak_launch_guided_rev(hipStream_t st, const int* n2_dev, int n2_host, int npairs, const HakGuidedScratch& sc)
+{
+    k_guided_rev<<<dim3(hak_grid_x((n2_host + 255) / 256), npairs), 256, 0, st>>>(n2_dev, n2_host, 2, sc);
+}
+
 // the forward search of npairs pairs into fwd ({j1, d1, d2, 0} per query) and, cross != 0, rev(j) into sc.rev ({i, d, 512, 0}).
 // With device-side counts n1_host / n2_host carry the capacity of the sets.  d_H: one record per pair on the device, or NULL:
 // h_H[9] (host) serves the only pair.
@@ -240,8 +239,8 @@ void hak_launch_guided(hipStream_t st, const hak_point* pts1, const hak_point* p
     hak_homography hv{};
     if (!d_H)
         for (int k = 0; k < 9; k++) hv.H[k] = h_H[k];
-    k_guided_bin<<<npairs, GD_THREADS, 0, st>>>(pts2, n2_dev, n2_host, stride2, 2, rp, sc);
+    hak_launch_guided_bin(st, pts2, n2_dev, n2_host, stride2, npairs, rp, sc);
     k_guided_search<<<dim3(hak_grid_x((n1_host + 255) / 256), npairs), 256, 0, st>>>(pts1, pts2, n1_dev, n1_host, stride1, stride2, 2, d_H, hv,
                                                                                       rp, r2, cross, sc, fwd, fwd_stride);
-    if (cross) k_guided_rev<<<dim3(hak_grid_x((n2_host + 255) / 256), npairs), 256, 0, st>>>(n2_dev, n2_host, 2, sc);
+    if (cross) hak_launch_guided_rev(st, n2_dev, n2_host, npairs, sc);
 }

@@ -89,6 +89,20 @@ namespace akaze
         return count;
     }
 
+    int cuMatchEpipolar(AkazeData& result1, AkazeData& result2, const float F[9], hak_match_pair* matches, float radius, int ratio_num,
+                        int ratio_den, bool cross_check)
+    {
+        int count = 0;
+        hak_match_pair* d_out = nullptr;
+        const int cap = result1.num_pts > 0 ? result1.num_pts : 1;
+        if (matches && hipMalloc((void**)&d_out, sizeof(hak_match_pair) * (size_t)cap) != hipSuccess) die("cuMatchEpipolar alloc");
+        if (hak_match_epipolar(NULL, result1.d_data, result1.num_pts, result2.d_data, result2.num_pts, F, radius, ratio_num, ratio_den,
+                               cross_check ? 1 : 0, 0, result1.h_data, d_out, &count, matches))
+            die("cuMatchEpipolar");
+        if (d_out) (void)hipFree(d_out);
+        return count;
+    }
+
     int cuFindHomography(const hak_match_pair* matches, int n, float H[9], unsigned char* inlier_mask, int iterations, float threshold,
                          unsigned seed, bool refine)
     {

@@ -100,6 +100,12 @@ int hak_match_guided(hak_ctx*, hak_point* p1, int n1, const hak_point* p2, int n
     if (!H || !(radius > 0.f) || H[8] != H[8]) { g_err = "bad argument"; return 1; }
     return hak_match_knn2(nullptr, p1, n1, p2, n2, rn, rd, cc, md, h1, d_out, count, h_out);
 }
+int hak_match_epipolar(hak_ctx*, hak_point* p1, int n1, const hak_point* p2, int n2, const float* F, float radius, int rn, int rd, int cc,
+                       int md, hak_point* h1, hak_match_pair* d_out, int* count, hak_match_pair* h_out)
+{
+    if (!F || !(radius > 0.f) || F[8] != F[8]) { g_err = "bad argument"; return 1; }
+    return hak_match_knn2(nullptr, p1, n1, p2, n2, rn, rd, cc, md, h1, d_out, count, h_out);
+}
 int hak_memcpy_h2d(void* dst, const void* src, long bytes) { memcpy(dst, src, (size_t)bytes); return 0; }
 int hak_memcpy_d2h(void* dst, const void* src, long bytes) { memcpy(dst, src, (size_t)bytes); return 0; }
 // reads every record and writes every mask byte (an undersized caller buffer is an ASan error); "inliers" are the even indices

@@ -3,7 +3,7 @@
 // `nrepeats` times and cuMatch once, and prints the same five result lines.
 //
 //   hipakaze_demo [device] [left.pgm right.pgm] [nrepeats] [--dump file] [--api-checks] [--pair] [--homography] [--retain-best N]
-//                 [--retain-grid G] [--guided R] [--fundamental]
+//                 [--retain-grid G] [--guided R] [--fundamental] [--epipolar R]
 //
 // --dump file   writes the host-side results as raw 104-byte AkazePoint records:
 //               int32 n1, n2, then n1 + n2 records of the float path (image 1 after cuMatch),
@@ -21,6 +21,9 @@
 // --fundamental  after the 2-NN match, estimates the fundamental matrix between the two images from its matches (cuFindFundamental:
 //               RANSAC, 1024 seven-point hypotheses, Sampson distance < 1 px, seed 0, no refit) and prints it; with --dump, appends
 //               after everything else int32 n, int32 inliers, float32 F[9], the n hak_match_pair records and the n inlier-mask bytes
+// --epipolar R  implies --fundamental; after RANSAC re-matches the pair under that fundamental matrix (cuMatchEpipolar: every keypoint
+//               of image 1 is searched only within R pixels of its epipolar line; ratio 4/5 + cross-check inside that band), runs
+//               cuFindFundamental again on the new list and prints both match and inlier counts
 // --retain-best N  both AkazeData get capacity N (instead of 10000) and Akazer::setRetainBest(true): an image with more keypoints
 //               keeps its N strongest (hak_set_retain_best), in raster order, on the float and the FAST path alike
 // --retain-grid G  Akazer::setRetainGrid(G), G in 8..128: an image with more keypoints than the capacity (N of --retain-best, else
@@ -99,7 +102,7 @@ int main(int argc, char** argv)
     std::string dumpPath;
     bool apiChecks = false, pairCalls = false, homography = false, fundamental = false;
     int retainBest = 0, retainGrid = 0;
-    float guided = 0.f;
+    float guided = 0.f, epipolar = 0.f;
     {   // strip the options; what is left are the reference demo's positional arguments (main.cpp:131-135)
         int n = 1;
         for (int i = 1; i < argc; i++) {
@@ -109,6 +112,7 @@ int main(int argc, char** argv)
             else if (!strcmp(argv[i], "--homography")) homography = true;
             else if (!strcmp(argv[i], "--fundamental")) fundamental = true;
             else if (!strcmp(argv[i], "--guided") && i + 1 < argc) { guided = (float)std::atof(argv[++i]); homography = true; }
+            else if (!strcmp(argv[i], "--epipolar") && i + 1 < argc) { epipolar = (float)std::atof(argv[++i]); fundamental = true; }
             else if (!strcmp(argv[i], "--retain-best") && i + 1 < argc) retainBest = std::atoi(argv[++i]);
             else if (!strcmp(argv[i], "--retain-grid") && i + 1 < argc) retainGrid = std::atoi(argv[++i]);
             else argv[n++] = argv[i];
@@ -227,6 +231,18 @@ int main(int argc, char** argv)
         const int ninlier2 = akaze::cuFindHomography(gm.data(), nguided, hom2);
         std::cout << "Homography of the guided matches: " << ninlier2 << " inliers of " << nguided << " against " << ninlier << " of "
                   << ngood << std::endl;
+    }
+    if (epipolar > 0.f) {
+        std::vector<hak_match_pair> em(good.size());
+        float t8 = timer.read();
+        const int nepi = akaze::cuMatchEpipolar(akaze_data1, akaze_data2, fund, em.data(), epipolar, 4, 5, true);
+        float t9 = timer.read();
+        std::cout << "Epipolar matches (radius " << epipolar << " px, ratio 0.8 + cross-check): " << nepi << " against " << ngood
+                  << " of the 2-NN match  (" << t9 - t8 << " ms)" << std::endl;
+        float fund2[9];
+        const int nfinlier2 = akaze::cuFindFundamental(em.data(), nepi, fund2);
+        std::cout << "Fundamental matrix of the epipolar matches: " << nfinlier2 << " inliers of " << nepi << " against " << nfinlier
+                  << " of " << ngood << std::endl;
     }
 
     // ---- the reference's second demo (main.cpp:227-300): the integer FAST path on the uint8 images

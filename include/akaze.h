@@ -39,6 +39,14 @@ namespace akaze
     int cuMatchGuided(AkazeData& result1, AkazeData& result2, const float H[9], hak_match_pair* matches, float radius = 8.f,
                       int ratio_num = 4, int ratio_den = 5, bool cross_check = true);
 
+    // build-side addition: epipolar guided matching (hak_match_epipolar) -- re-matches result1 against result2 under a fundamental
+    // matrix F (row-major, (x2 y2 1) F (x1 y1 1)^T = 0, e.g. cuFindFundamental's): every keypoint of result1 is searched only among
+    // the keypoints of result2 closer than `radius` pixels to its epipolar line, ratio test and cross-check inside that band.  Fills
+    // result1 like cuMatch and returns the accepted matches in query order (host array `matches`, capacity >= result1.num_pts; may
+    // be NULL to only count).
+    int cuMatchEpipolar(AkazeData& result1, AkazeData& result2, const float F[9], hak_match_pair* matches, float radius = 2.f,
+                        int ratio_num = 4, int ratio_den = 5, bool cross_check = true);
+
     class Akazer
     {
     public:

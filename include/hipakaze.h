@@ -340,6 +340,51 @@ int hak_match_guided_batch(hak_ctx* ctx, hak_point* d_points, const int* d_num_p
                            int ratio_num, int ratio_den, int cross_check, int max_dist,
                            hak_match_pair* d_out, int* d_counts);
 
+/* ---- epipolar guided matching: re-match a pair under its estimated fundamental matrix (build-side addition; the stage behind
+ * hak_find_fundamental, as hak_match_guided is the stage behind hak_find_homography).  For two views of a 3-D scene there is no
+ * point-to-point map, but F sends query i to a LINE in image 2; each query is searched only among the train points closer than
+ * `radius` to its line.  A pure function of its arguments -- in particular it does not depend on how the implementation bins the
+ * points; tests/epipolar_match_ref.py is its bit-exact numpy statement.
+ *   Line of query i, float32, no FMA, (x, y) = pts1[i].x, .y, F row-major with (x2 y2 1) F (x1 y1 1)^T = 0 as hak_fundamental:
+ *      a = (F0 x + F1 y) + F2, b = (F3 x + F4 y) + F5, c = (F6 x + F7 y) + F8, den = a a + b b -- the a, b, c of step 7 of
+ *      hak_find_fundamental.
+ *   Domain, L = 16384, DEN_MIN = 2^-100: query i has no gate unless |x| <= L and |y| <= L and den is finite and >= DEN_MIN; train
+ *      point j is in no gate unless |x2_j| <= L and |y2_j| <= L.  NaN fails every comparison.  These bounds belong to the rule, not
+ *      to an implementation: they are what makes a conservative search window provable.  The floor on den keeps e e from
+ *      underflowing into a pass far from the line; a query at the epipole has a = b = 0 and, correctly, no band.
+ *   Gate G(i, j): the domain holds and, with e = (a x2_j + b y2_j) + c, e e < r2 den, r2 = radius * radius, all in float32: the
+ *      distance of train point j from the line of query i in image 2 is below radius.  The Sampson distance of hak_find_fundamental
+ *      divides the same e e by a LARGER denominator (den + p p + q q), so it is never larger than this distance: up to rounding,
+ *      every accepted match is an inlier of F at threshold = radius.
+ *   Distance d(i, j): the Hamming distance of hak_match_knn2 (the 61 descriptor bytes).
+ *   Forward: J_i = { j : G(i, j) }; j1 = the member of J_i with the smallest d, ties to the smallest j; d1 = d(i, j1);
+ *      d2 = the smallest d over J_i \ {j1}, 512 when there is none.
+ *   Reverse: I_j = { i : G(i, j) } -- the same gate, no transposed F; rev(j) = the member of I_j with the smallest d, ties to the
+ *      smallest i.
+ *   Accept query i iff J_i is not empty and d1 < max_dist and d1 * ratio_den < d2 * ratio_num (64-bit products)
+ *      and (cross_check == 0 or rev(j1) == i).
+ *   Outputs as hak_match_knn2: match / distance / match_x / match_y of an accepted query, -1 / -1 / -1.f / -1.f of a rejected one
+ *      (copied to h_pts1 when given); the accepted matches in ascending query order to d_out (capacity >= n1; may be NULL) with
+ *      second = d2; *count their number; h_out (needs d_out) receives the list as well.
+ * Known limit: the band runs across the whole image, so a look-alike that happens to lie on the line is NOT excluded -- the ratio
+ * test inside the band is what guards against it.  The gate is one-dimensional where the homography's is two-dimensional.
+ * Synchronous; ctx may be NULL (default stream, scratch allocated for the call).  F: 9 floats on the HOST, row-major.
+ * max_dist <= 0 selects 96.  Refused with a non-zero status and a message before any device is touched: radius not finite or
+ * not > 0, radius * radius not finite in float32, F NULL or with a non-finite entry, a negative count, a ratio term <= 0, a NULL
+ * point array with a positive count.  Fewer than 2^20 points per side.  Device code: csrc/kernels_epipolar.hip. */
+int hak_match_epipolar(hak_ctx* ctx, hak_point* d_pts1, int n1, const hak_point* d_pts2, int n2,
+                       const float F[9] /* host */, float radius, int ratio_num, int ratio_den, int cross_check,
+                       int max_dist, hak_point* h_pts1, hak_match_pair* d_out, int* count, hak_match_pair* h_out);
+/* batched over the pairs of a detect batch, layouts and outputs as hak_match_knn2_batch; asynchronous on the context's stream.
+ * F of pair k is read ON THE DEVICE from d_F[k], the record hak_find_fundamental_batch wrote: the chain detect batch ->
+ * hak_match_knn2_batch -> hak_find_fundamental_batch -> hak_match_epipolar_batch needs no host synchronisation.  A pair whose
+ * record has hypothesis < 0 or a non-finite entry of F has no model: count 0, every query rejected (an all-zero F has no gate
+ * anyway).  A NULL d_F and a NULL context are refused. */
+int hak_match_epipolar_batch(hak_ctx* ctx, hak_point* d_points, const int* d_num_pts, int npairs,
+                             const hak_fundamental* d_F /* device, one per pair */, float radius,
+                             int ratio_num, int ratio_den, int cross_check, int max_dist,
+                             hak_match_pair* d_out, int* d_counts);
+
 /* ---- memory helpers: initAkazeData/freeAkazeData (akaze.cpp:26-52) and the
  * image upload of main.cpp:172-188 */
 int hak_points_alloc(hak_point** d_points, int count);
