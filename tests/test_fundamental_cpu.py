@@ -190,3 +190,96 @@ def test_refusals_need_no_device(ah):
     if ah.device_count() == 0:
         assert lib.hak_find_fundamental(None, None, 0, 10, 1.0, 0, None, out) != 0
         assert "no HIP device" in lib.hak_last_error().decode()
+
+
+# ---- the committed cases of test_gpu_fundamental.py::test_randomised_parity: drawn here so that what they reach can be asserted
+# on the statement alone
+PARITY_SEED, PARITY_CASES = 2027, 150
+PARITY_SCENES = ("general", "planar", "translation", "lattice", "collinear")
+
+
+def parity_case(k):
+    """case k of the randomised parity run: dict(recs (n, 4) float32, iterations, threshold, seed, ctx, scene, group).  A pure
+    function of k.  Cases 8 b .. 8 b + 3 of every third block b of eight share iterations / threshold / seed and also go through
+    hak_find_fundamental_batch as one ragged group (`group` = b, else -1)."""
+    from akaze_hip import synth
+    rng = np.random.default_rng([PARITY_SEED, k])
+    pick = lambda seq: seq[int(rng.integers(len(seq)))]
+    n = int(pick((rng.integers(0, 7), 7, 8, rng.integers(9, 301), rng.integers(9, 301), rng.integers(300, 3001))))
+    scene = pick(PARITY_SCENES)
+    m = max(n, 8)
+    s = int(rng.integers(1 << 30))
+    if scene == "general":
+        recs = synth.two_view_matches(m, 0, s, noise=float(pick((0.0, 0.3, 1.0))))[0].astype(np.float64)
+    else:
+        x1 = np.stack([rng.uniform(0, 1920, m), rng.uniform(0, 1080, m)], axis=1)
+        if scene == "collinear":                                        # every point of both images on one line each
+            t = rng.uniform(0, 1, m)
+            x1 = np.stack([100 + 1500 * t, 200 + 700 * t], axis=1)
+            x2 = np.stack([300 + 1200 * t ** 1.1, 900 - 650 * t], axis=1)
+        elif scene == "planar":                                         # one homography: F is not determined, many models tie
+            H = np.array([[1.02, 0.03, 15.0], [-0.02, 0.97, -8.0], [2e-5, -1e-5, 1.0]]) + rng.normal(0, [[0.02, 0.02, 5], [0.02, 0.02, 5], [1e-5, 1e-5, 0]])
+            p = np.concatenate([x1, np.ones((m, 1))], axis=1) @ H.T
+            x2 = p[:, :2] / p[:, 2:]
+        elif scene == "translation":                                    # pure translation: parallax along lines through one epipole
+            ep = np.array([rng.uniform(-2000, 4000), rng.uniform(-2000, 3000)])
+            x2 = x1 + (x1 - ep) * rng.uniform(0.02, 0.2, (m, 1))
+        else:                                                           # lattice: few distinct integer values, ties in the counts
+            q = int(pick((2, 3, 5)))
+            x1 = np.stack([rng.integers(0, q, m), rng.integers(0, q, m)], axis=1) * float(pick((1, 7, 100)))
+            x2 = np.stack([rng.integers(0, q, m), rng.integers(0, q + 1, m)], axis=1) * float(pick((1, 7, 100)))
+        recs = np.concatenate([x1, x2], axis=1)
+        if scene != "lattice":
+            recs += rng.normal(0, float(pick((0.0, 0.0, 0.3))), recs.shape)
+    rate = float(rng.uniform(0.0, 0.9)) if rng.random() < 0.7 else 0.0
+    out = rng.random(m) < rate
+    lo, hi = recs[np.isfinite(recs).all(axis=1)].min(), recs.max()
+    recs[out] = np.floor(rng.uniform(lo, hi + 1, (int(out.sum()), 4))) if scene == "lattice" else rng.uniform(lo, hi + 1, (int(out.sum()), 4))
+    if rng.random() < 0.3:
+        recs += float(pick((-16000.0, 16000.0))) * np.array([rng.integers(0, 2), rng.integers(0, 2), rng.integers(0, 2), 1.0])
+    recs = (recs * 2.0 ** int(pick((0, 0, 0, -20, -8, 8, 20)))).astype(np.float32)[:n]
+    if n and rng.random() < 0.3:                                        # NaN / inf rows
+        bad = rng.random(n) < 0.15
+        recs[bad, rng.integers(0, 4, int(bad.sum()))] = np.array([np.nan, np.inf, -np.inf], np.float32)[rng.integers(0, 3, int(bad.sum()))]
+    if n and rng.random() < 0.25:                                       # exact duplicates, up to all-equal
+        share = float(pick((0.25, 0.6, 1.0)))
+        recs[rng.random(n) < share] = recs[int(rng.integers(n))]
+    c = dict(recs=recs, iterations=int(pick((1, 7, 64, 100, 257))), threshold=float(np.float32(rng.uniform(0.2, 8.0))),
+             seed=int(pick((0, 0xFFFFFFFF, int(rng.integers(0, 2 ** 32)), int(rng.integers(0, 2 ** 32))))), ctx=bool(rng.integers(2)),
+             scene=scene, group=-1)
+    if (k // 8) % 3 == 0 and k % 8 < 4:
+        g = np.random.default_rng([PARITY_SEED, k // 8, 5])
+        c.update(iterations=int((1, 7, 64, 100, 257)[int(g.integers(5))]), threshold=float(np.float32(g.uniform(0.2, 8.0))),
+                 seed=int((0, 0xFFFFFFFF, int(g.integers(0, 2 ** 32)))[int(g.integers(3))]), group=k // 8)
+    return c
+
+
+def test_parity_cases_reach_the_rare_branches():
+    """what the statement alone says about the committed cases: winners on a later root, lists without a model, ties between
+    different (h, root) on the winning inlier count (the smallest-h-then-smallest-root rule decides), and winners whose cubic gave
+    exactly one model (the one-root branch) and exactly three (fundamental_ref.models' `valid` row of the winning hypothesis: a
+    three-root cubic with a rejected model counts as neither)"""
+    assert parity_case(5)["recs"].tobytes() == parity_case(5)["recs"].tobytes() and parity_case(5)["seed"] == parity_case(5)["seed"]
+    later_root = no_model = ties = one_root = three_roots = 0
+    scenes = set()
+    for k in range(PARITY_CASES):
+        c = parity_case(k)
+        scenes.add(c["scene"])
+        r, mask = fr.find_fundamental(c["recs"], c["iterations"], c["threshold"], c["seed"])
+        later_root += r["root"] > 0
+        no_model += r["hypothesis"] < 0
+        if r["hypothesis"] < 0:
+            continue
+        rec = hr.records(c["recs"])
+        F, valid = fr.models(rec, c["seed"], np.arange(c["iterations"]))
+        nroots = int(valid[r["hypothesis"]].sum())                       # the models the winner's cubic gave
+        one_root += nroots == 1
+        three_roots += nroots == 3
+        hh, rr = np.nonzero(valid)
+        t2 = np.float32(c["threshold"]) * np.float32(c["threshold"])
+        cnt = fr.inlier_mask(F[hh, rr], rec, t2).sum(axis=1)
+        assert cnt.max() == r["inliers"] and (hh[np.argmax(cnt)], rr[np.argmax(cnt)]) == (r["hypothesis"], r["root"])
+        ties += (cnt == cnt.max()).sum() >= 2
+    assert scenes == set(PARITY_SCENES)
+    assert later_root >= 10 and no_model >= 10 and ties >= 10 and one_root >= 5 and three_roots >= 5, \
+        (later_root, no_model, ties, one_root, three_roots)

