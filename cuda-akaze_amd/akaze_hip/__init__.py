@@ -102,6 +102,8 @@ SYMBOLS = {
     "hak_find_homography_batch": (C.c_int, [_vp, _vp, C.c_long, _vp, C.c_int, C.c_int, C.c_float, C.c_uint, C.c_int, _vp, _vp]),
     "hak_find_fundamental": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_float, C.c_uint, _vp, _vp]),
     "hak_find_fundamental_batch": (C.c_int, [_vp, _vp, C.c_long, _vp, C.c_int, C.c_int, C.c_float, C.c_uint, _vp, _vp]),
+    "hak_refine_fundamental": (C.c_int, [_vp, _vp, C.c_int, C.c_float, C.c_int, _vp, _vp]),
+    "hak_refine_fundamental_batch": (C.c_int, [_vp, _vp, C.c_long, _vp, C.c_int, C.c_float, C.c_int, _vp, _vp]),
     "hak_match_guided": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _fp, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _ip, _vp]),
     "hak_match_guided_batch": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp]),
     "hak_match_epipolar": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _fp, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _ip, _vp]),
@@ -578,7 +580,8 @@ def findHomography(matches, iterations=1024, threshold=3.0, seed=0, refine=True,
 def findFundamental(matches, iterations=1024, threshold=1.0, seed=0, akazer=None):
     """RANSAC fundamental matrix over a match list (hipakaze.h hak_find_fundamental), on the device.  `matches` as findHomography's.
     Returns (record of FUNDAMENTAL_DTYPE, inlier mask as a uint8 numpy array); F = record["F"].reshape(3, 3) satisfies
-    (x2, y2, 1) F (x1, y1, 1)^T = 0 for the inliers.  The seven-point model of the winning sample: there is no refit."""
+    (x2, y2, 1) F (x1, y1, 1)^T = 0 for the inliers.  The seven-point model of the winning sample; refineFundamental refits it over its
+    inliers."""
     import torch
     ctx = akazer.ctx if akazer is not None else None
     if isinstance(matches, torch.Tensor):
@@ -592,4 +595,24 @@ def findFundamental(matches, iterations=1024, threshold=1.0, seed=0, akazer=None
     out = np.zeros((), FUNDAMENTAL_DTYPE)
     check(lib.hak_find_fundamental(ctx, d_m.data_ptr(), n, int(iterations), float(threshold), int(seed) & 0xFFFFFFFF,
                                    d_mask.data_ptr(), out.ctypes.data))
+    return out, d_mask[:n].cpu().numpy()
+
+
+def refineFundamental(matches, record, threshold=1.0, rounds=3, akazer=None):
+    """Rank-2 least-squares refit of a fundamental matrix over its inliers, iterated up to `rounds` (1..8) times (hipakaze.h
+    hak_refine_fundamental), on the device.  `matches` as findHomography's; `record`: a FUNDAMENTAL_DTYPE record, findFundamental's
+    or an earlier refit's (it is not modified).  Returns (record, inlier mask as a uint8 numpy array): record["root"] == 3 when a
+    refit was accepted, and record["inliers"] is never below the input F's count at `threshold`."""
+    import torch
+    ctx = akazer.ctx if akazer is not None else None
+    if isinstance(matches, torch.Tensor):
+        d_m = matches.contiguous()
+        n = d_m.numel() * d_m.element_size() // MATCH_PAIR_DTYPE.itemsize
+    else:
+        host = np.ascontiguousarray(matches, MATCH_PAIR_DTYPE)
+        n = len(host)
+        d_m = torch.from_numpy(host.view(np.uint8).reshape(-1)).cuda() if n else torch.zeros(32, dtype=torch.uint8, device="cuda")
+    d_mask = torch.zeros(max(n, 1), dtype=torch.uint8, device="cuda")
+    out = np.array(record, FUNDAMENTAL_DTYPE).reshape(())
+    check(lib.hak_refine_fundamental(ctx, d_m.data_ptr(), n, float(threshold), int(rounds), d_mask.data_ptr(), out.ctypes.data))
     return out, d_mask[:n].cpu().numpy()

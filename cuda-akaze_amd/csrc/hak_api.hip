@@ -815,6 +815,61 @@ extern "C" int hak_find_fundamental_batch(hak_ctx* c, const hak_match_pair* d_ma
     return 0;
 }
 
+// ----------------------------------------------------------- rank-2 refit of a fundamental matrix (kernels_fundrefit.hip)
+static int refine_args(float threshold, int rounds)
+{
+    if (rounds < 1 || rounds > 8) return fail("rounds must be in 1 .. 8");
+    if (!std::isfinite(threshold) || !(threshold > 0.f)) return fail("threshold must be finite and > 0");
+    return 0;
+}
+
+extern "C" int hak_refine_fundamental(hak_ctx* c, const hak_match_pair* d_matches, int n, float threshold, int rounds,
+                                      unsigned char* d_mask, hak_fundamental* h_inout)
+{
+    if (!h_inout || (!d_matches && n > 0)) return fail("null argument");
+    if (n < 0) return fail("n < 0");
+    if ((reinterpret_cast<uintptr_t>(d_matches) & 15) != 0) return fail("d_matches must be 16-byte aligned");
+    if (refine_args(threshold, rounds)) return 1;
+    if (hak_device_count() == 0) return fail("no HIP device: libhipakaze has no CPU fallback");
+    // no scratch.  The record's device copy is the context's, or without a context a device global that calls take in turn:
+    // nothing is allocated
+    static std::mutex null_ctx_record;
+    std::unique_lock<std::mutex> turn(null_ctx_record, std::defer_lock);
+    hak_fundamental* d_rec = nullptr;
+    if (c) {
+        if (!c->fund_rec) HIP_TRY(hipMalloc((void**)&c->fund_rec, sizeof(hak_fundamental)));
+        d_rec = c->fund_rec;
+    } else {
+        turn.lock();
+        d_rec = hak_fundamental_refit_record();
+        if (!d_rec) return fail("hipGetSymbolAddress(refit record)");
+    }
+    hipStream_t st = c ? c->stream : nullptr;
+    order_after_null_stream(c, st);
+    int rc = 0;
+    if (hipMemcpyAsync(d_rec, h_inout, sizeof(hak_fundamental), hipMemcpyHostToDevice, st) != hipSuccess) rc = fail("record upload");
+    if (!rc) {
+        hak_launch_fundamental_refit(st, d_matches, n, nullptr, n, 1, threshold, rounds, d_rec, d_mask, 0);
+        if (hipGetLastError() != hipSuccess) rc = fail("fundamental refit launch failed");
+    }
+    if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = fail("hipStreamSynchronize(fundamental refit)");
+    if (!rc && hipMemcpy(h_inout, d_rec, sizeof(hak_fundamental), hipMemcpyDeviceToHost) != hipSuccess) rc = fail("record download");
+    return rc;
+}
+
+extern "C" int hak_refine_fundamental_batch(hak_ctx* c, const hak_match_pair* d_matches, long stride, const int* d_counts,
+                                            int npairs, float threshold, int rounds, hak_fundamental* d_inout,
+                                            unsigned char* d_masks)
+{
+    if (!c || !d_matches || !d_counts || !d_inout || npairs < 1 || stride < 1) return fail("bad argument");
+    if ((reinterpret_cast<uintptr_t>(d_matches) & 15) != 0) return fail("d_matches must be 16-byte aligned");
+    if (refine_args(threshold, rounds)) return 1;
+    order_after_null_stream(c, c->stream);
+    hak_launch_fundamental_refit(c->stream, d_matches, stride, d_counts, 0, npairs, threshold, rounds, d_inout, d_masks, stride);
+    if (hipGetLastError() != hipSuccess) return fail("fundamental refit launch failed");
+    return 0;
+}
+
 // ----------------------------------------------------------- guided matching (kernels_guided.hip; the rule: include/hipakaze.h)
 static int guided_args(float radius, int ratio_num, int ratio_den)
 {

@@ -790,6 +790,12 @@ long hak_fundamental_words(int npairs, int iterations);
 void hak_launch_fundamental(hipStream_t st, const hak_match_pair* matches, long stride, const int* counts, int n_host, int npairs,
                             int iterations, float threshold, unsigned seed, unsigned* models, unsigned long long* slots,
                             hak_fundamental* out, unsigned char* masks, long mask_stride);
+// rank-2 refit of a fundamental matrix (kernels_fundrefit.hip): record k is read from and rewritten to inout[k]; no scratch.
+// hak_fundamental_refit_record(): the current device's one record for calls without a context (NULL on failure)
+hak_fundamental* hak_fundamental_refit_record();
+void hak_launch_fundamental_refit(hipStream_t st, const hak_match_pair* matches, long stride, const int* counts, int n_host,
+                                  int npairs, float threshold, int rounds, hak_fundamental* inout, unsigned char* masks,
+                                  long mask_stride);
 
 // A launcher that cannot do what it was asked (a precondition its caller should have checked) records the reason here instead
 // of aborting; enqueue_detect turns it into the call's error (hak_sequence.hip).  Thread-local, like hak_last_error().

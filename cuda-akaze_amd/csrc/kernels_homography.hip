@@ -15,6 +15,7 @@
 // k_hom_finish: one wave per pair: reduces the slots, re-derives the winner through the same device function, refits, re-scores,
 //   writes the mask and the record.
 #include "hak_internal.h"
+#include "geom_common.h"
 
 #define HG_CHUNK 1024            // records per LDS chunk: 16 KB, so that several blocks share a CU
 #define HG_THREADS 256
@@ -130,19 +131,6 @@ __device__ bool hg_hypothesis(const hak_match_pair* m, int n, unsigned seed, int
     A[6] = S1[3] * S1[7] - S1[4] * S1[6]; A[7] = S1[1] * S1[6] - S1[0] * S1[7]; A[8] = S1[0] * S1[4] - S1[1] * S1[3];
     hg_mul3(S2, A, F);
     return hg_to_float(F, H);
-}
-
-__device__ __forceinline__ double hg_wsum(double v)
-{
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v = v + __shfl_xor(v, off);
-    return v;
-}
-__device__ __forceinline__ int hg_wsum(int v)
-{
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-    return v;
 }
 
 // inliers of H over the pair (one wave, every lane returns the total)

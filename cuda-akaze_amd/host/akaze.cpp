@@ -143,6 +143,27 @@ namespace akaze
         return r.inliers;
     }
 
+    int cuRefineFundamental(const hak_match_pair* matches, int n, float F[9], unsigned char* inlier_mask, float threshold, int rounds)
+    {
+        if (n < 0 || (n > 0 && !matches) || !F) { fprintf(stderr, "hip-akaze: cuRefineFundamental: bad argument\n"); exit(-1); }
+        hak_match_pair* d_matches = nullptr;
+        unsigned char* d_mask = nullptr;
+        if (n > 0) {
+            if (hipMalloc((void**)&d_matches, sizeof(hak_match_pair) * (size_t)n) != hipSuccess) die("cuRefineFundamental alloc");
+            if (inlier_mask && hipMalloc((void**)&d_mask, (size_t)n) != hipSuccess) die("cuRefineFundamental alloc");
+            if (hak_memcpy_h2d(d_matches, matches, (long)(sizeof(hak_match_pair) * (size_t)n))) die("cuRefineFundamental upload");
+        }
+        hak_fundamental r{};
+        for (int k = 0; k < 9; k++) r.F[k] = F[k];
+        r.n = n;
+        if (hak_refine_fundamental(NULL, d_matches, n, threshold, rounds, d_mask, &r)) die("cuRefineFundamental");
+        if (d_mask && hak_memcpy_d2h(inlier_mask, d_mask, n)) die("cuRefineFundamental download");
+        for (int k = 0; k < 9; k++) F[k] = r.F[k];
+        if (d_mask) (void)hipFree(d_mask);
+        if (d_matches) (void)hipFree(d_matches);
+        return r.inliers;
+    }
+
     Akazer::Akazer() { hak_default_config(&cfg); }
 
     Akazer::~Akazer() { hak_destroy(ctx); }                              // akaze.cpp:74-77

@@ -54,6 +54,8 @@ int main()
             REQUIRE(cuFindFundamental(pairs.data(), np, F) == (np + 2) / 3);
             REQUIRE(cuFindFundamental(pairs.data(), 6, F, mask.data()) == 0 && F[7] == 0.f && mask[0] == 0);
             REQUIRE(cuFindFundamental(NULL, 0, F) == 0);
+            REQUIRE(cuFindFundamental(pairs.data(), np, F) == (np + 2) / 3);
+            REQUIRE(cuRefineFundamental(pairs.data(), np, F, mask.data()) == (np + 2) / 3 && mask[3] == 1 && mask[1] == 0 && F[7] == 1.f);
         }
         cuMatch(d1, hostless);                                      // train side without a host buffer
         d2.num_pts = 0;

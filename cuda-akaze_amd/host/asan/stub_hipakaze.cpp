@@ -134,7 +134,23 @@ int hak_find_fundamental(hak_ctx*, const hak_match_pair* d, int n, int iteration
     }
     return 0;
 }
-// the HIP runtime calls of cuMatchKnn, cuFindHomography and cuFindFundamental
+// as hak_find_fundamental's stub: every record read, every mask byte written, the record rewritten in place with root = 3
+int hak_refine_fundamental(hak_ctx*, const hak_match_pair* d, int n, float threshold, int rounds, unsigned char* mask,
+                           hak_fundamental* inout)
+{
+    if (!inout || (n > 0 && !d) || rounds < 1 || rounds > 8 || !(threshold > 0.f)) { g_err = "bad argument"; return 1; }
+    const bool model = inout->hypothesis >= 0 && n >= 8;
+    inout->inliers = 0;
+    inout->root = model ? 3 : inout->root;
+    inout->n = n;
+    for (int i = 0; i < n; i++) {
+        const bool in = model && d[i].x1 == d[i].x1 && i % 3 == 0;
+        inout->inliers += in;
+        if (mask) mask[i] = in;
+    }
+    return 0;
+}
+// the HIP runtime calls of cuMatchKnn, cuFindHomography, cuFindFundamental and cuRefineFundamental
 hipError_t hipMalloc(void** p, size_t n) { *p = malloc(n); return *p ? hipSuccess : hipErrorOutOfMemory; }
 hipError_t hipFree(void* p) { free(p); return hipSuccess; }
 }

@@ -3,7 +3,7 @@
 // `nrepeats` times and cuMatch once, and prints the same five result lines.
 //
 //   hipakaze_demo [device] [left.pgm right.pgm] [nrepeats] [--dump file] [--api-checks] [--pair] [--homography] [--retain-best N]
-//                 [--retain-grid G] [--guided R] [--fundamental] [--epipolar R]
+//                 [--retain-grid G] [--guided R] [--fundamental] [--refine N] [--epipolar R]
 //
 // --dump file   writes the host-side results as raw 104-byte AkazePoint records:
 //               int32 n1, n2, then n1 + n2 records of the float path (image 1 after cuMatch),
@@ -21,6 +21,9 @@
 // --fundamental  after the 2-NN match, estimates the fundamental matrix between the two images from its matches (cuFindFundamental:
 //               RANSAC, 1024 seven-point hypotheses, Sampson distance < 1 px, seed 0, no refit) and prints it; with --dump, appends
 //               after everything else int32 n, int32 inliers, float32 F[9], the n hak_match_pair records and the n inlier-mask bytes
+// --refine N    implies --fundamental; behind RANSAC refits F over its inliers, up to N rounds of 1..8 (cuRefineFundamental: rank-2
+//               least squares, kept when it scores at least as well), prints the inlier count before and after, and F, the count
+//               and the mask of the dump and of --epipolar are the refitted ones
 // --epipolar R  implies --fundamental; after RANSAC re-matches the pair under that fundamental matrix (cuMatchEpipolar: every keypoint
 //               of image 1 is searched only within R pixels of its epipolar line; ratio 4/5 + cross-check inside that band), runs
 //               cuFindFundamental again on the new list and prints both match and inlier counts
@@ -101,7 +104,7 @@ int main(int argc, char** argv)
     std::cout << "===== Registration by HIP-AKAZE (MI355X) =====" << std::endl;
     std::string dumpPath;
     bool apiChecks = false, pairCalls = false, homography = false, fundamental = false;
-    int retainBest = 0, retainGrid = 0;
+    int retainBest = 0, retainGrid = 0, refine = 0;
     float guided = 0.f, epipolar = 0.f;
     {   // strip the options; what is left are the reference demo's positional arguments (main.cpp:131-135)
         int n = 1;
@@ -112,6 +115,7 @@ int main(int argc, char** argv)
             else if (!strcmp(argv[i], "--homography")) homography = true;
             else if (!strcmp(argv[i], "--fundamental")) fundamental = true;
             else if (!strcmp(argv[i], "--guided") && i + 1 < argc) { guided = (float)std::atof(argv[++i]); homography = true; }
+            else if (!strcmp(argv[i], "--refine") && i + 1 < argc) { refine = std::atoi(argv[++i]); fundamental = true; }
             else if (!strcmp(argv[i], "--epipolar") && i + 1 < argc) { epipolar = (float)std::atof(argv[++i]); fundamental = true; }
             else if (!strcmp(argv[i], "--retain-best") && i + 1 < argc) retainBest = std::atoi(argv[++i]);
             else if (!strcmp(argv[i], "--retain-grid") && i + 1 < argc) retainGrid = std::atoi(argv[++i]);
@@ -219,6 +223,12 @@ int main(int argc, char** argv)
                   << t7 - t6 << " ms)" << std::endl;
         for (int r = 0; r < 3; r++)
             std::cout << "  [" << fund[3 * r] << ", " << fund[3 * r + 1] << ", " << fund[3 * r + 2] << "]" << std::endl;
+        if (refine > 0) {
+            const int before = nfinlier;
+            nfinlier = akaze::cuRefineFundamental(good.data(), ngood, fund, finlier.data(), 1.f, refine);
+            std::cout << "Refit of the fundamental matrix (rank-2 least squares, up to " << refine << " rounds): " << nfinlier
+                      << " inliers against " << before << "  (" << timer.read() - t7 << " ms)" << std::endl;
+        }
     }
     if (guided > 0.f) {
         std::vector<hak_match_pair> gm(good.size());

@@ -32,6 +32,13 @@ namespace akaze
     int cuFindFundamental(const hak_match_pair* matches, int n, float F[9], unsigned char* inlier_mask = nullptr, int iterations = 1024,
                           float threshold = 1.f, unsigned seed = 0);
 
+    // build-side addition: rank-2 least-squares refit of a fundamental matrix over its inliers among a host match list, iterated up to
+    // `rounds` (1..8) times, on the device (hak_refine_fundamental): F (e.g. cuFindFundamental's; an all-zero F stays as it is) is
+    // replaced by the refitted matrix when that scores at least as well at `threshold`, the optional inlier_mask (n bytes) gets the
+    // inliers of the returned F, and the return value is their count -- never fewer than F had at that threshold.
+    int cuRefineFundamental(const hak_match_pair* matches, int n, float F[9], unsigned char* inlier_mask = nullptr, float threshold = 1.f,
+                            int rounds = 3);
+
     // build-side addition: guided matching (hak_match_guided) -- re-matches result1 against result2 under a homography H (row-major,
     // (x1, y1, 1) -> image 2, e.g. cuFindHomography's): every keypoint of result1 is searched only among the keypoints of result2
     // within `radius` pixels of where H sends it, ratio test and cross-check inside that neighbourhood.  Fills result1 like cuMatch

@@ -284,8 +284,8 @@ int hak_find_homography_batch(hak_ctx* ctx, const hak_match_pair* d_matches, lon
  *      inlier iff e e < t2 den, t2 = threshold * threshold (threshold finite, > 0; NaN fails).
  *   8. The model with the most inliers wins, ties to the smallest h, then the smallest root.
  * Output: hypothesis = -1 means no model (F all zero, inliers = 0, mask all zero).  The optional mask gets 1 for every inlier of
- * the returned F, 0 otherwise (n bytes).  There is NO least-squares refit: F is the winning seven-point model, exactly rank 2 up
- * to rounding; a rank-2 refit over the inliers needs a 9 x 9 eigen-solve and is left to the caller.  Refused with a non-zero
+ * the returned F, 0 otherwise (n bytes).  F is the winning seven-point model, exactly rank 2 up to rounding; the rank-2
+ * least-squares refit over its inliers is the next stage, hak_refine_fundamental below.  Refused with a non-zero
  * status and a message before any device is touched: iterations outside 1..65536, a threshold that is not finite or not > 0,
  * n < 0, a NULL list with n > 0, NULL h_out / d_out / d_counts, npairs < 1, stride < 1, a NULL context for the batch form.
  * Device code: csrc/kernels_fundamental.hip. */
@@ -293,7 +293,7 @@ typedef struct hak_fundamental {
     float F[9];              /* row-major, (x2 y2 1) F (x1 y1 1)^T = 0; the entry of largest |value| is 1 */
     int   inliers;           /* inliers of F */
     int   hypothesis;        /* winning hypothesis, -1 = no model (F = 0, inliers = 0) */
-    int   root;              /* which real root of the winner's cubic (0..2) */
+    int   root;              /* which real root of the winner's cubic (0..2); 3 = refitted by hak_refine_fundamental */
     int   n;                 /* matches considered */
 } hak_fundamental;           /* 52 bytes, as hak_homography */
 /* one list, synchronous; ctx may be NULL (default stream; the call allocates its own scratch); result to *h_out (host) */
@@ -304,6 +304,52 @@ int hak_find_fundamental(hak_ctx* ctx, const hak_match_pair* d_matches, int n, i
 int hak_find_fundamental_batch(hak_ctx* ctx, const hak_match_pair* d_matches, long stride, const int* d_counts, int npairs,
                                int iterations, float threshold, unsigned seed, hak_fundamental* d_out,
                                unsigned char* d_masks);
+
+/* ---- rank-2 least-squares refit of a fundamental matrix over its inliers, iterated (build-side addition; the stage behind
+ * hak_find_fundamental, and the local-optimisation step of LO-RANSAC).  The seven-point winner is fitted to seven noisy points;
+ * the refit fits all of its inliers, re-scores, and repeats from the larger inlier set.  A pure function of (matches, input
+ * record, threshold, rounds); tests/fundamental_refit_ref.py is its bit-exact numpy statement.  float64, no FMA, + - * / sqrt
+ * only; records are read as by hak_find_fundamental (a non-finite coordinate is never an inlier and enters no sum).
+ *   0. 1 <= rounds <= 8, threshold finite and > 0, t2 = threshold * threshold in float32.  A record with hypothesis < 0 or a
+ *      non-finite entry of F has no model: the output is the no-model record (F = 0, inliers 0, hypothesis -1, root 0, n) and an
+ *      all-zero mask.  Otherwise cur = F and cnt = the inliers of cur by step 7 of hak_find_fundamental at THIS call's t2.
+ *      Steps 1-7 repeat up to `rounds` times and stop at the first round that fails or is not accepted.
+ *   1. I = the inliers of cur, m = |I|.  The round fails if m < 8.
+ *   2. Every sum over I is taken in the order of hak_find_homography's refit: lane l of one wave takes the matches i = l (mod 64)
+ *      in ascending i, non-inliers skipped, every partial sum starting from 0.0; then an xor butterfly over 32, 16, .., 1.
+ *   3. Hartley normalisation per image: c = sum / m, d = p - c, q = sum (dx dx + dy dy), s = sqrt((2 m) / q).  The round fails
+ *      unless q > 0 and s is finite.  Normalised points (x, y) = s1 d1, (u, v) = s2 d2.
+ *   4. w = [u x, u y, u, v x, v y, v, x, y, 1]; the 45 sums N[p][q] += w[p] * w[q], p <= q, mirrored afterwards.
+ *   5. jacobi(A, n, S), cyclic Jacobi: V = I; for sweep = 0..S-1, p = 0..n-2, q = p+1..n-1: apq = A[p][q]; nothing if apq == 0;
+ *      th = (A[q][q] - A[p][p]) / (2 apq), sg = +1 if th >= 0 else -1, t = sg / (|th| + sqrt(th th + 1)),
+ *      c = 1 / sqrt(t t + 1), sn = t c; for k not in {p, q}, x = A[k][p], y = A[k][q]: A[k][p] = A[p][k] = c x - sn y,
+ *      A[k][q] = A[q][k] = sn x + c y; A[p][p] = A[p][p] - t apq, A[q][q] = A[q][q] + t apq, A[p][q] = A[q][p] = 0; for all k,
+ *      x = V[k][p], y = V[k][q]: V[k][p] = c x - sn y, V[k][q] = sn x + c y.  The answer is the column j of V with the smallest
+ *      A[j][j] (found with <, from j = 0: ties to the smallest j).  f = jacobi(N, 9, 8); the round fails if an entry of f is
+ *      non-finite.
+ *   6. Rank 2: Fn = f as 3 x 3, row-major; G[i][j] = (Fn[0][i] Fn[0][j] + Fn[1][i] Fn[1][j]) + Fn[2][i] Fn[2][j];
+ *      v = jacobi(G, 3, 6); g_i = (Fn[i][0] v0 + Fn[i][1] v1) + Fn[i][2] v2; Fn'[i][j] = Fn[i][j] - g_i v_j -- Fn without its
+ *      smallest singular triplet, the closest rank-2 matrix in the Frobenius norm.
+ *   7. F = T2^T (Fn' T1), divided by its entry of largest |value| (ties to the smallest index) and rounded to float32, exactly
+ *      as step 6 of hak_find_fundamental; the round fails if that entry is 0 or anything is non-finite.  cnt' = the inliers of
+ *      that F.  The round is accepted iff cnt' >= cnt; then cur = F, cnt = cnt'.
+ *   8. Output: F = cur, inliers = cnt, hypothesis unchanged, n = the matches considered, root = 3 if a round was accepted and
+ *      the input's root otherwise; the optional mask gets the inliers of cur at this call's threshold.  So inliers never falls
+ *      below the input F's count at the same threshold, and a refitted record may be passed in again.
+ * Limits: an unweighted algebraic (eight-point) fit -- no Sampson weighting, no re-weighting; nothing is estimated beyond F.
+ * Refused with a non-zero status and a message before any device is touched: rounds outside 1..8, a threshold that is not finite
+ * or not > 0, n < 0, a NULL list with n > 0, a list that is not 16-byte aligned, NULL h_inout / d_inout / d_counts, npairs < 1,
+ * stride < 1, a NULL context for the batch form.  Device code: csrc/kernels_fundrefit.hip. */
+/* one list, synchronous; ctx may be NULL (default stream; the call needs no scratch and allocates nothing: calls without a
+ * context share one device-resident record and take it in turn).  *h_inout (host): in = a record of hak_find_fundamental,
+ * out = the result */
+int hak_refine_fundamental(hak_ctx* ctx, const hak_match_pair* d_matches, int n, float threshold, int rounds,
+                           unsigned char* d_mask, hak_fundamental* h_inout);
+/* batched, asynchronous on the context's stream, layouts as hak_find_fundamental_batch; d_inout[k] (device) is read and rewritten
+ * in place, so detect batch -> hak_match_knn2_batch -> hak_find_fundamental_batch -> hak_refine_fundamental_batch ->
+ * hak_match_epipolar_batch needs no host synchronisation */
+int hak_refine_fundamental_batch(hak_ctx* ctx, const hak_match_pair* d_matches, long stride, const int* d_counts, int npairs,
+                                 float threshold, int rounds, hak_fundamental* d_inout, unsigned char* d_masks);
 
 /* ---- guided matching: re-match a pair under its estimated homography (build-side addition; the stage behind
  * hak_find_homography).  The 2-NN search of hak_match_knn2 looks at the whole other image, so on repetitive texture its ratio
