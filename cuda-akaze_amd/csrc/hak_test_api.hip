@@ -397,3 +397,12 @@ extern "C" int hak_debug_fill_match_scratch(hak_ctx* c, int byte)
     if (c->msc.part && c->msc.part_cap > 0) HIP_TRY(hipMemsetAsync(c->msc.part, byte, sizeof(uint2) * (size_t)c->msc.part_cap, c->stream));
     return 0;
 }
+
+// the launch shape both RANSAC estimators take for (npairs, iterations): hak_homography_blocks and nothing else, no device
+extern "C" int hak_op_ransac_shape(int npairs, int iterations, int* hp, int* hblocks)
+{
+    if (!hp || !hblocks) return fail("null argument");
+    if (npairs < 1 || iterations < 1 || iterations > 65536) return fail("npairs must be >= 1 and iterations in 1 .. 65536");
+    *hblocks = hak_homography_blocks(npairs, iterations, hp);
+    return 0;
+}

@@ -95,6 +95,10 @@ int hak_op_hess_probe(int w, int h, int nimg, int step, int iters, double* ms_pe
 /* hak_debug_fill_match_scratch: fills the context's per-slice match summaries (kernels_match.hip: `part`) with `byte`, on the context's
  * stream -- the hand-off stress run makes a stale summary visible with it (tests/stress_handoff.py) */
 int hak_debug_fill_match_scratch(hak_ctx* ctx, int byte);
+/* hak_op_ransac_shape: the launch shape the homography and the fundamental-matrix RANSAC calls (single and batch) take for `npairs`
+ * lists and `iterations` hypotheses -- *hp hypotheses per score block (16 .. 256) and *hblocks score blocks per pair.  It asks the
+ * launchers' own rule and touches no device: the shape tests (tests/ransac_shapes.py) read the rule here and do not restate it. */
+int hak_op_ransac_shape(int npairs, int iterations, int* hp, int* hblocks);
 
 #ifdef __cplusplus
 }

@@ -234,6 +234,63 @@ def test_randomised_parity(ah, torch):
     assert not fails, f"{len(fails)} of 200 differ: " + "; ".join(fails[:3])
 
 
+def test_randomised_families(ah, torch):
+    """the cases of test_homography_cpu.all_parity_cases -- 150 drawn from six scene families (planted projective, similarity,
+    integer lattice at unit and coarse spacing, mirrored image 2, a model whose wz = 0 line crosses the cloud, collinear), with
+    outliers, NaN / inf rows, duplicates up to all-equal, coordinates scaled by 2^-20 .. 2^20 and offset by +-16000, n from 0,
+    iterations 1 .. 257, thresholds 0.2 .. 8, seeds 0 and 0xFFFFFFFF, plus the hand-made singular refits -- record and mask byte for
+    byte against the statement with the refit off and on, with and without a context; every third block of eight also as one
+    ragged hak_find_homography_batch call per refit setting.  What the cases reach (no model, ties, refit accepted / rejected / singular, records
+    behind the wz = 0 line, samples the orientation test rejects) is asserted in test_homography_cpu.py."""
+    from test_homography_cpu import all_parity_cases
+    fails = []
+    cases = all_parity_cases()
+    det = ah.Akazer()
+    det.init((256, 192, 256), max_pts=500, batch=2)
+    wants = []
+    for k, c in enumerate(cases):
+        pairs = as_pairs(ah, c["recs"])
+        wants.append({})
+        for refine in (0, 1):
+            want, wm = wants[k][refine] = hr.find_homography(pairs, c["iterations"], c["threshold"], c["seed"], bool(refine))
+            got, gm = gpu_single(ah, torch, pairs, c["iterations"], c["threshold"], c["seed"], refine, ctx=det.ctx if c["ctx"] else None)
+            try:
+                assert_same(got, gm, want, wm, (k, c["scene"], refine))
+            except AssertionError as e:
+                fails.append(str(e)[:300])
+    groups = sorted({c["group"] for c in cases if c["group"] >= 0})
+    for g in groups:
+        ks = [k for k, c in enumerate(cases) if c["group"] == g]
+        c0 = cases[ks[0]]
+        stride = max(1, max(len(cases[k]["recs"]) for k in ks))
+        allp = np.zeros(len(ks) * stride, ah.MATCH_PAIR_DTYPE)
+        for f in ("x1", "y1", "x2", "y2"):
+            allp[f] = np.nan                                            # records past a pair's count are not the call's business
+        for slot, k in enumerate(ks):
+            allp[slot * stride:slot * stride + len(cases[k]["recs"])] = as_pairs(ah, cases[k]["recs"])
+        d = upload(torch, allp)
+        d_cnt = torch.tensor([len(cases[k]["recs"]) for k in ks], dtype=torch.int32, device="cuda")
+        for refine in (0, 1):
+            d_out = torch.zeros(len(ks) * ah.HOMOGRAPHY_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+            d_mask = torch.full((len(ks) * stride,), 0xEE, dtype=torch.uint8, device="cuda")
+            ah.check(ah.lib.hak_find_homography_batch(det.ctx, d.data_ptr(), stride, d_cnt.data_ptr(), len(ks), c0["iterations"],
+                                                      c0["threshold"], c0["seed"], refine, d_out.data_ptr(), d_mask.data_ptr()))
+            ah.check(ah.lib.hak_sync(det.ctx))
+            out = d_out.cpu().numpy().view(ah.HOMOGRAPHY_DTYPE)
+            masks = d_mask.cpu().numpy().reshape(len(ks), stride)
+            for slot, k in enumerate(ks):
+                n = len(cases[k]["recs"])
+                want, wm = wants[k][refine]
+                try:
+                    assert_same(out[slot], masks[slot, :n], want, wm, ("batch", g, k, refine))
+                    assert (masks[slot, n:] == 0xEE).all(), ("batch", g, k, "written past the count")
+                except AssertionError as e:
+                    fails.append(str(e)[:300])
+    det.close()
+    assert len(groups) >= 5
+    assert not fails, f"{len(fails)} differ: " + "; ".join(fails[:3])
+
+
 def test_bad_arguments(ah, torch):
     d = torch.zeros(64 * 32, dtype=torch.uint8, device="cuda")
     rec = np.zeros((), ah.HOMOGRAPHY_DTYPE)

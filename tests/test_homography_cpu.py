@@ -140,6 +140,172 @@ def test_refit_sums_follow_the_lane_order():
     assert np.array_equal(got, lanes[0])
 
 
+# ---- the committed cases of test_gpu_homography.py::test_randomised_families: drawn here so that what they reach can be asserted
+# on the statement alone
+PARITY_SEED, PARITY_CASES = 2040, 150
+PARITY_SCENES = ("projective", "similarity", "lattice", "mirrored", "vanishing", "collinear")
+
+
+def _project(H, x1):
+    with np.errstate(all="ignore"):
+        p = np.concatenate([x1, np.ones((len(x1), 1))], axis=1) @ H.T
+        return p[:, :2] / p[:, 2:]
+
+
+def parity_case(k):
+    """case k of the randomised family run: dict(recs (n, 4) float32, iterations, threshold, seed, ctx, scene, group).  A
+    pure function of k.  Cases 8 b .. 8 b + 3 of every third block b of eight share iterations / threshold / seed and also
+    go through hak_find_homography_batch as one ragged group (`group` = b, else -1)."""
+    rng = np.random.default_rng([PARITY_SEED, k])
+    pick = lambda seq: seq[int(rng.integers(len(seq)))]
+    n = int(pick((rng.integers(0, 6), 4, 5, rng.integers(6, 301), rng.integers(6, 301), rng.integers(300, 3001))))
+    scene = pick(PARITY_SCENES)
+    m = max(n, 8)
+    x1 = np.stack([rng.uniform(0, 1920, m), rng.uniform(0, 1080, m)], axis=1)
+    H = np.array([[1.02, 0.03, 15.0], [-0.02, 0.97, -8.0], [2e-5, -1e-5, 1.0]]) + rng.normal(0, [[0.02, 0.02, 5], [0.02, 0.02, 5], [1e-5, 1e-5, 0]])
+    if scene == "projective":
+        x2 = _project(H, x1)
+    elif scene == "similarity":
+        a, s = rng.uniform(-np.pi, np.pi), rng.uniform(0.5, 2.0)
+        x2 = x1 @ (s * np.array([[np.cos(a), -np.sin(a)], [np.sin(a), np.cos(a)]])).T + rng.uniform(-300, 300, 2)
+    elif scene == "lattice":                                            # unit spacing: |cross| of the smallest triangles is exactly 1
+        q, sp = int(pick((3, 5, 9))), float(pick((1, 1, 7, 100)))
+        g = np.stack([rng.integers(0, q, m), rng.integers(0, q, m)], axis=1).astype(np.float64)
+        A = np.array(pick(([[1, 0], [0, 1]], [[1, 1], [0, 1]], [[2, 0], [0, 1]], [[1, 0], [1, 1]])), np.float64)
+        x1, x2 = g * sp, (g @ A.T + rng.integers(-3, 4, 2)) * sp
+    elif scene == "mirrored":                                           # image 2 flipped: every planted sample fails the orientation test
+        x2 = _project(H, x1)
+        x2[:, 0] = 1920.0 - x2[:, 0]
+    elif scene == "vanishing":                                          # the line wz = 0 runs through the cloud; a third are mirrored too
+        c = np.array([rng.uniform(300, 1600), rng.uniform(200, 900)])   # a point of the line, and its normal direction
+        a = rng.uniform(0, 2 * np.pi)
+        d = np.array([np.cos(a), np.sin(a)])
+        gh = d / -(d @ c)                                               # g x + h y + 1 = 0 at c
+        H[2, :2] = gh
+        if rng.random() < 1 / 3:
+            H[0] = -H[0]
+        x2 = _project(H, x1)
+    else:                                                               # collinear in image 1
+        t = rng.uniform(0, 1, m)
+        x1 = np.stack([100 + 1500 * t, 200 + 700 * t], axis=1)
+        x2 = np.stack([300 + 1200 * t ** 1.1, 900 - 650 * t + 40 * np.sin(9 * t)], axis=1)
+    recs = np.concatenate([x1, x2], axis=1)
+    sigma = 0.0 if scene == "lattice" else float(pick((0.0, 0.3, 1.0)))
+    recs += rng.normal(0, sigma, recs.shape)
+    rate = float(rng.uniform(0.0, 0.9)) if rng.random() < 0.7 else 0.0
+    out = rng.random(m) < rate
+    fin = recs[np.isfinite(recs).all(axis=1)]
+    lo, hi = (float(np.clip(fin.min(), -4000, 0)), float(np.clip(fin.max(), 8, 4000))) if len(fin) else (0.0, 1920.0)
+    draw = rng.uniform(lo, hi + 1, (int(out.sum()), 4))
+    recs[out] = np.floor(draw) if scene == "lattice" else draw
+    if rng.random() < 0.3:
+        recs += float(pick((-16000.0, 16000.0))) * np.array([rng.integers(0, 2), rng.integers(0, 2), rng.integers(0, 2), 1.0])
+    with np.errstate(all="ignore"):
+        recs = (recs * 2.0 ** int(pick((0, 0, 0, 0, 0, -20, -8, 8, 20)))).astype(np.float32)[:n]
+    if n and rng.random() < 0.3:                                        # NaN / inf rows
+        bad = rng.random(n) < 0.15
+        recs[bad, rng.integers(0, 4, int(bad.sum()))] = np.array([np.nan, np.inf, -np.inf], np.float32)[rng.integers(0, 3, int(bad.sum()))]
+    if n and rng.random() < 0.25:                                       # exact duplicates, up to all-equal
+        share = float(pick((0.25, 0.6, 1.0)))
+        recs[rng.random(n) < share] = recs[int(rng.integers(n))]
+    # thresholds from 0.2 to 8, log-uniform; most of the noisy scenes get one near their noise, where a refit moves the count
+    thr = float(np.float32(sigma * rng.uniform(0.7, 1.5) if sigma > 0.0 and rng.random() < 0.7 else 0.2 * 40.0 ** rng.random()))
+    c = dict(recs=recs, iterations=int(pick((1, 7, 64, 100, 257))), threshold=thr,
+             seed=int(pick((0, 0xFFFFFFFF, int(rng.integers(0, 2 ** 32)), int(rng.integers(0, 2 ** 32))))),
+             ctx=bool(rng.integers(2)), scene=scene, group=-1)
+    if (k // 8) % 3 == 0 and k % 8 < 4:
+        g = np.random.default_rng([PARITY_SEED, k // 8, 5])
+        c.update(iterations=int((1, 7, 64, 100, 257)[int(g.integers(5))]), threshold=float(np.float32(0.2 * 40.0 ** g.random())),
+                 seed=int((0, 0xFFFFFFFF, int(g.integers(0, 2 ** 32)))[int(g.integers(3))]), group=k // 8)
+    return c
+
+
+def hand_cases():
+    """cases made by hand for the one branch drawing does not reach: a refit that is attempted and comes back singular or
+    non-finite.  The sample's own four points always fit their model, so a refit sees at least four points in general position
+    unless they fail the wz > 0 test: a mirrored model (det < 0) keeps the orientation of points BEHIND its wz = 0 line, so a sample
+    drawn there is accepted while its points do not count.  The records that count lie in front of the line, and here they are
+    copies of one record (Hartley's scale is 1 / 0) or lie on one line (a rank-deficient system)."""
+    Ht = np.array([[-1.0, 0.0, 300.0], [0.0, 1.0, 30.0], [-1.0 / 800.0, 0.0, 1.0]])     # wz = 1 - x / 800, det = -0.625
+    rng = np.random.default_rng(PARITY_SEED)
+    back = np.stack([rng.uniform(1000, 1900, 40), rng.uniform(0, 1080, 40)], axis=1)    # wz < 0
+    cases = []
+    for name, front in (("copies", np.tile([[200.0, 300.0]], (12, 1))),
+                        ("on a line", np.stack([np.linspace(50, 700, 12), np.full(12, 300.0)], axis=1))):
+        x1 = np.concatenate([back, front])
+        recs = np.concatenate([x1, _project(Ht, x1)], axis=1).astype(np.float32)
+        cases.append(dict(recs=recs, iterations=64, threshold=2.0, seed=3, ctx=False, scene="hand: " + name, group=-1))
+    return cases
+
+
+def all_parity_cases():
+    return [parity_case(k) for k in range(PARITY_CASES)] + hand_cases()
+
+
+def trace(c):
+    """what the statement does on case c with the refit on, step by step with homography_ref's own functions: dict(model, ties,
+    refit in {"none", "accepted", "rejected", "singular"}, behind (records with wz <= 0 under the returned model), flipped (samples
+    that pass both |cross| > 1 tests on every triple and fail the orientation test))"""
+    rec = hr.records(c["recs"])
+    t2 = np.float32(c["threshold"]) * np.float32(c["threshold"])
+    hs = np.arange(c["iterations"])
+    r, _ = hr.find_homography(c["recs"], c["iterations"], c["threshold"], c["seed"], True)
+    out = dict(model=bool(r["hypothesis"] >= 0), ties=False, refit="none", behind=0, flipped=0)
+    if len(rec) >= 4:
+        idx, ok = hr.sample_indices(c["seed"], hs, len(rec))
+        p = rec[np.where(idx < 0, 0, idx)].astype(np.float64)
+        big, same = ok.copy(), np.ones(len(hs), bool)
+        with np.errstate(all="ignore"):
+            for a, b, d in hr._TRIPLES:
+                c1 = (p[:, b, 0] - p[:, a, 0]) * (p[:, d, 1] - p[:, a, 1]) - (p[:, b, 1] - p[:, a, 1]) * (p[:, d, 0] - p[:, a, 0])
+                c2 = (p[:, b, 2] - p[:, a, 2]) * (p[:, d, 3] - p[:, a, 3]) - (p[:, b, 3] - p[:, a, 3]) * (p[:, d, 2] - p[:, a, 2])
+                big &= (np.abs(c1) > 1.0) & (np.abs(c2) > 1.0)
+                same &= (c1 > 0.0) == (c2 > 0.0)
+        out["flipped"] = int((big & ~same).sum())
+    if not out["model"]:
+        return out
+    H, ok = hr.hypotheses(rec, c["seed"], hs)
+    cnt = hr.inlier_mask(H[ok], rec, t2).sum(axis=1)
+    j = int(np.argmax(cnt))
+    assert hs[ok][j] == r["hypothesis"]                                 # the smallest h among the maxima
+    out["ties"] = bool((cnt == cnt.max()).sum() >= 2)
+    if cnt[j] >= 4:
+        R, rok = hr.refit(rec, hr.inlier_mask(H[ok][j], rec, t2)[0])
+        kept = rok and int(hr.inlier_mask(R, rec, t2)[0].sum()) >= cnt[j]
+        out["refit"] = "accepted" if kept else "rejected" if rok else "singular"
+        assert (r["refined"] == 1) == kept and (kept or r["inliers"] == cnt[j])
+    else:
+        assert r["refined"] == 0
+    h = r["H"]
+    with np.errstate(all="ignore"):
+        wz = (h[6] * rec[:, 0] + h[7] * rec[:, 1]) + np.float32(1.0)
+    out["behind"] = int((wz <= 0).sum())
+    return out
+
+
+def test_parity_cases_reach_the_rare_branches():
+    """what the statement alone says about the committed cases.  Counted when written (150 drawn + 2 hand-made cases): 93 lists
+    without a model, 37 winners decided by the smallest-h rule among equal counts, 45 refits accepted, 6 computed and rejected, 2
+    singular (the hand-made cases: no drawn case reaches that branch, which is why they exist), 24 lists with records behind the
+    returned model's wz = 0 line, 63 with samples that only the orientation test rejects.  A rejected refit is rare -- about one
+    case in 150 for most generator seeds -- so PARITY_SEED is one of the few seeds in 2028 .. 2067 whose cases give three or more.
+    The bounds: 10 where 150 draws give that easily, 3 for the rare ones."""
+    assert parity_case(5)["recs"].tobytes() == parity_case(5)["recs"].tobytes() and parity_case(5)["seed"] == parity_case(5)["seed"]
+    cases = all_parity_cases()
+    assert {c["scene"] for c in cases[:PARITY_CASES]} == set(PARITY_SCENES)
+    assert len({c["group"] for c in cases if c["group"] >= 0}) >= 5
+    assert {len(c["recs"]) for c in cases} >= {0, 1, 2, 3, 4, 5}
+    tr = [trace(c) for c in cases]
+    got = dict(no_model=sum(not t["model"] for t in tr), ties=sum(t["ties"] for t in tr),
+               accepted=sum(t["refit"] == "accepted" for t in tr), rejected=sum(t["refit"] == "rejected" for t in tr),
+               singular=sum(t["refit"] == "singular" for t in tr), behind=sum(t["model"] and t["behind"] > 0 for t in tr),
+               flipped=sum(t["flipped"] > 0 for t in tr),
+               mirrored_without_model=sum(c["scene"] == "mirrored" and not t["model"] for c, t in zip(cases, tr)))
+    assert [t["refit"] for t in tr[PARITY_CASES:]] == ["singular", "singular"]
+    assert got["no_model"] >= 10 and got["ties"] >= 10 and got["accepted"] >= 10 and got["flipped"] >= 10 and got["behind"] >= 10, got
+    assert got["rejected"] >= 3 and got["singular"] >= 2 and got["mirrored_without_model"] >= 10, got
+
+
 @pytest.mark.parametrize("seed", [2, 4, 5])
 def test_end_to_end_on_cpu_oracle(okz, seed):
     """detect (oracle) + 2-NN ratio 4/5 with cross-check + the reference RANSAC (1024 hypotheses, 1 px, refit) on
