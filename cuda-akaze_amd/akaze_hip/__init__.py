@@ -145,6 +145,21 @@ TEST_SYMBOLS = {
     "hak_op_rcp_check": (C.c_int, [C.c_uint, C.c_uint, C.POINTER(C.c_ulonglong)]),
     "hak_op_smooth_flow": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float]),
     "hak_op_hessian": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int]),
+    # ... and their twins on the integer FAST path (int32 planes, uint8 images, integer contrast factors)
+    "hak_op_fast_conv_u8": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int]),
+    "hak_op_fast_lowpass": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int]),
+    "hak_op_fast_base": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, _ip, _ip, _ip, _ip]),
+    "hak_op_fast_down_smooth": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "hak_op_fast_kcontrast": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_float, _ip, _ip, _ip]),
+    "hak_op_fast_flow": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "hak_op_fast_smooth_flow": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "hak_op_fast_nld_steps": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _fp, C.c_int]),
+    "hak_op_fast_nld_steps_batch": (C.c_int, [_vp, _vp, _vp, _vp, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, _fp, C.c_int]),
+    "hak_op_fast_fed_cycle": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.c_long, C.c_int, C.c_int, C.c_int,
+                                        C.c_int, _ip, _fp, C.c_int]),
+    "hak_op_fast_level_tile": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_long, C.c_int, C.c_int, C.c_int,
+                                         C.c_int, C.c_int, _ip, _fp, C.c_int, _ip]),
+    "hak_op_fast_hessian": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _ip]),
     "hak_debug_set_plane": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
     "hak_op_tail_begin": (C.c_int, [_vp]),
     "hak_op_tail_level": (C.c_int, [_vp, C.c_int, C.c_int, _vp]),

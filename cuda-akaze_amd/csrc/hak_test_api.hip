@@ -215,6 +215,248 @@ extern "C" int hak_op_hessian(const float* s, float* lx, float* ly, float* det, 
     return 0;
 }
 
+// ------------------------------------------------ the same operators on the integer FAST path (tests/test_gpu_fast_stages.py)
+// Each drives the `int` overload the launch sequence (build_level<int> / hessian_level<int>, hak_sequence.hip) calls.
+#define HAK_FAST_KC_MAX 46340                                       // kcontrast * kcontrast stays inside int32 (akazed.cu:4215)
+static void fast_taps(float var, int radius, int* it)              // akazed.cu:3896, as hak_create fills itaps1 / itaps_base
+{
+    float t[8];
+    hak_gauss_taps(var, radius, t);
+    for (int i = 0; i < 8; i++) it[i] = i <= radius ? (int)(t[i] * 65536 + 0.5f) : 0;
+}
+// a device HakImgState per image whose octave-0 contrast factor is set the way kf_kcontrast sets it; *out == nullptr on failure
+static int fast_state(HakImgState** out, const int* kcontrast, int nimg)
+{
+    *out = nullptr;
+    std::vector<HakImgState> hs((size_t)nimg);
+    for (int i = 0; i < nimg; i++) {
+        if (kcontrast[i] < 0 || kcontrast[i] > HAK_FAST_KC_MAX) return fail("integer contrast factor must be in 0 .. 46340");
+        hs[i] = HakImgState{};
+        hs[i].ikcontrast[0] = kcontrast[i];
+        hs[i].ikc[0] = 1.f / (float)(kcontrast[i] * kcontrast[i]);                // akazed.cu:4215 (0 -> inf)
+    }
+    HakImgState* st = nullptr;
+    HIP_TRY(hipMalloc((void**)&st, sizeof(HakImgState) * (size_t)nimg));
+    if (hipMemcpy(st, hs.data(), sizeof(HakImgState) * (size_t)nimg, hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipFree(st);
+        return fail("state upload");
+    }
+    *out = st;
+    return 0;
+}
+// contrast factor, lattice maximum and the reference's h_hist (hak_op_kcontrast has the bin-0 note) of a one-image state; frees it
+static int fast_state_result(HakImgState* st, int w, int h, int* kc, int* hmax, int* hist)
+{
+    HakImgState hs;
+    const hipError_t e = hipDeviceSynchronize();
+    const hipError_t e2 = e == hipSuccess ? hipMemcpy(&hs, st, sizeof(hs), hipMemcpyDeviceToHost) : e;
+    (void)hipFree(st);
+    if (e2 != hipSuccess) return fail(std::string("FAST contrast: ") + hipGetErrorString(e2));
+    if (kc) *kc = hs.ikcontrast[0];
+    if (hmax) *hmax = hs.ihmax;
+    if (hist) { memcpy(hist, hs.hist, sizeof(hs.hist)); hist[0] += hak_hist_extra0(w, h); }
+    return 0;
+}
+static int fast_sync(const char* what)
+{
+    const hipError_t e = hipDeviceSynchronize();
+    if (e != hipSuccess) return fail(std::string(what) + ": " + hipGetErrorString(e));
+    return 0;
+}
+
+extern "C" int hak_op_fast_conv_u8(const unsigned char* s, int sp, int* d, int w, int h, int p, float var, int radius)
+{
+    if (radius < 1 || radius > 5) return fail("radius must be 1..5");
+    int taps[8];
+    fast_taps(var, radius, taps);
+    hakf_launch_conv_u8(nullptr, s, 0, sp, d, 0, w, h, p, 1, taps, radius);
+    return fast_sync("hak_op_fast_conv_u8");
+}
+
+extern "C" int hak_op_fast_lowpass(const int* s, int* d, int w, int h, int p, float var, int radius)
+{
+    if (radius < 1 || radius > 5) return fail("radius must be 1..5");
+    int taps[8];
+    fast_taps(var, radius, taps);
+    hakf_launch_conv_int(nullptr, s, d, 0, w, h, p, 1, taps, radius);
+    return fast_sync("hak_op_fast_lowpass");
+}
+
+extern "C" int hak_op_fast_base(const unsigned char* img, int sp, int* lt, int w, int h, int p, float var_base, int radius, float per,
+                                int* kc, int* hmax, int* hist, int* route)
+{
+    if (radius < 1 || radius > 5) return fail("radius must be 1..5");
+    if (p % 4) return fail("pitch must be a multiple of 4");
+    int taps1[8], tapsb[8];
+    fast_taps(1.f, 2, taps1);
+    fast_taps(var_base, radius, tapsb);
+    const HakKnobs kn = hak_knobs_from_env();
+    // Lt, the gradient scratch and the sigma = 1 plane in ONE allocation, as in the arena: the streaming kernels address their
+    // output planes as 32-bit offsets from the lower one and decline planes that lie too far apart
+    const size_t plane = (size_t)h * p;
+    int* buf = nullptr;
+    HIP_TRY(hipMalloc((void**)&buf, sizeof(int) * 3 * plane));
+    HakImgState* st = nullptr;
+    if (hipMalloc((void**)&st, sizeof(HakImgState)) != hipSuccess) { (void)hipFree(buf); return fail("state alloc"); }
+    (void)hipMemset(st, 0, sizeof(HakImgState));
+    hakf_launch_reset(nullptr, st, 1);
+    int *Lt = buf, *grad = buf + plane, *smooth = buf + 2 * plane;
+    const bool based = hak_launch_base_level(nullptr, img, 0, sp, Lt, grad, 0, w, h, p, 1, taps1, tapsb, radius, st, per, 1, kn);
+    if (!based) {                                                                 // hak_sequence.hip build_level, akaze.cpp:589-623
+        hakf_launch_conv_u8(nullptr, img, 0, sp, smooth, 0, w, h, p, 1, taps1, 2);
+        hak_launch_contrast(nullptr, smooth, 0, w, h, p, 1, st, per, 1);
+        hakf_launch_conv_u8(nullptr, img, 0, sp, Lt, 0, w, h, p, 1, tapsb, radius);
+    }
+    // which kernel hak_launch_base_level took: the cover of launch_base_stream (kernels_base_stream.hip; its plane-distance clauses
+    // cannot trip on the single allocation above)
+    const bool streamed = radius >= 2 && radius <= 4 && (w & 3) == 0 && w >= 16 && h >= 16 && sp % 4 == 0 &&
+                          reinterpret_cast<uintptr_t>(img) % 4 == 0 && hak_stream_pays(kn.base_stream, w, h, 1);
+    if (route) *route = !based ? 3 : streamed ? 1 : 2;
+    int rc = fast_state_result(st, w, h, kc, hmax, hist);
+    if (!rc && hipMemcpy(lt, Lt, sizeof(int) * plane, hipMemcpyDeviceToDevice) != hipSuccess) rc = fail("hak_op_fast_base: copy");
+    (void)hipFree(buf);
+    return rc;
+}
+
+extern "C" int hak_op_fast_down_smooth(const int* s, int* d, int* sm, int sw, int sh, int sp, int dw, int dh, int dp)
+{
+    int taps[8];
+    fast_taps(1.f, 2, taps);
+    HakOct so{sw, sh, sp, (long)sh * sp}, dd{dw, dh, dp, (long)dh * dp};
+    hak_launch_down_smooth(nullptr, s, d, sm, 0, so, dd, 1, taps);
+    return fast_sync("hak_op_fast_down_smooth");
+}
+
+extern "C" int hak_op_fast_kcontrast(const int* smooth, int w, int h, int p, float per, int* kc, int* hmax, int* hist)
+{
+    HakImgState* st = nullptr;
+    HIP_TRY(hipMalloc((void**)&st, sizeof(HakImgState)));
+    (void)hipMemset(st, 0, sizeof(HakImgState));
+    hakf_launch_reset(nullptr, st, 1);
+    hak_launch_contrast(nullptr, smooth, 0, w, h, p, 1, st, per, 1);
+    return fast_state_result(st, w, h, kc, hmax, hist);
+}
+
+extern "C" int hak_op_fast_flow(const int* s, int* d, int w, int h, int p, int diffusivity, int kcontrast)
+{
+    HakImgState* st = nullptr;
+    if (fast_state(&st, &kcontrast, 1)) return 1;
+    hak_launch_flow(nullptr, s, d, 0, w, h, p, 1, diffusivity, st, 0);
+    const int rc = fast_sync("hak_op_fast_flow");
+    (void)hipFree(st);
+    return rc;
+}
+
+extern "C" int hak_op_fast_smooth_flow(const int* s, int* sm, int* fl, int w, int h, int p, int diffusivity, int kcontrast)
+{
+    int taps[8];
+    fast_taps(1.f, 2, taps);
+    HakImgState* st = nullptr;
+    if (fast_state(&st, &kcontrast, 1)) return 1;
+    hak_launch_smooth_flow(nullptr, s, sm, fl, 0, w, h, p, 1, taps, diffusivity, st, 0);
+    const int rc = fast_sync("hak_op_fast_smooth_flow");
+    (void)hipFree(st);
+    return rc;
+}
+
+// FAST keeps the 4-px groups (hak_sequence.hip build_level: max_fuse above 4 counts as 4; no deeper int kernel is built)
+static int fast_max_fuse() { const int m = hak_knobs_from_env().max_fuse; return m > 4 ? 4 : m; }
+
+extern "C" int hak_op_fast_nld_steps_batch(const int* src, const int* flow, int* dst, int* tmp, long stride, int w, int h, int p,
+                                           int nimg, const float* tau, int nsteps)
+{
+    if (nsteps < 1 || nimg < 1) return fail("nsteps < 1 or nimg < 1");
+    if (p % 4 || stride % 4) return fail("pitch and stride must be multiples of 4");
+    const int G = hak_fed_groups(nsteps, fast_max_fuse(), w, false);
+    const int* s = src;
+    int done = 0;
+    for (int g = 0; g < G; g++) {
+        const int ns = hak_fed_group_size(nsteps, G, g);
+        int* d = ((G - g) % 2 == 1) ? dst : tmp;
+        hak_launch_fed_group(nullptr, s, flow, d, stride, w, h, p, nimg, tau + done, ns);
+        done += ns;
+        s = d;
+    }
+    return fast_sync("hak_op_fast_nld_steps");
+}
+
+extern "C" int hak_op_fast_nld_steps(const int* src, const int* flow, int* dst, int* tmp, int w, int h, int p, const float* tau, int nsteps)
+{
+    return hak_op_fast_nld_steps_batch(src, flow, dst, tmp, 0, w, h, p, 1, tau, nsteps);
+}
+
+extern "C" int hak_op_fast_fed_cycle(const int* src, int head, int sw, int sh, int sp, int* smooth, int* flow, int* dst, int* tmp,
+                                     long stride, int w, int h, int p, int nimg, const int* kcontrast, const float* tau, int nsteps)
+{
+    if (nsteps < 1 || nimg < 1 || !kcontrast) return fail("nsteps < 1, nimg < 1 or no contrast factors");
+    if (p % 4 || stride % 4 || (head && sp % 4)) return fail("pitch and stride must be multiples of 4");
+    HakImgState* state = nullptr;
+    if (fast_state(&state, kcontrast, nimg)) return 1;
+    int taps[8];
+    fast_taps(1.f, 2, taps);
+    const int G = hak_fed_groups(nsteps, fast_max_fuse(), w, false);
+    const int ns0 = hak_fed_group_size(nsteps, G, 0);
+    int* dst0 = (G % 2 == 1) ? dst : tmp;
+    int rc = 0;
+    const bool ok = head ? hak_launch_fed_sf_head(nullptr, src, HakOct{sw, sh, sp, (long)sh * sp}, smooth, flow, dst0, stride,
+                                                  HakOct{w, h, p, (long)h * p}, nimg, taps, HAK_PM_G2, tau, ns0, state, 0, G > 1)
+                         : hak_launch_fed_sf(nullptr, src, smooth, flow, dst0, stride, w, h, p, nimg, taps, HAK_PM_G2, tau, ns0, state, 0, G > 1);
+    if (!ok) rc = fail("hak_op_fast_fed_cycle: k_fed_sf does not cover this case");
+    const int* s = dst0;
+    int done = ns0;
+    for (int g = 1; g < G && !rc; g++) {
+        const int ns = hak_fed_group_size(nsteps, G, g);
+        int* d = ((G - g) % 2 == 1) ? dst : tmp;
+        hak_launch_fed_group(nullptr, s, flow, d, stride, w, h, p, nimg, tau + done, ns);
+        done += ns;
+        s = d;
+    }
+    const int rs = fast_sync("hak_op_fast_fed_cycle");
+    (void)hipFree(state);
+    return rc ? rc : rs;
+}
+
+extern "C" int hak_op_fast_level_tile(const int* src, int head, int sw, int sh, int sp, int* smooth, int* dst, int* tmp, long stride,
+                                      int w, int h, int p, int nimg, int diffusivity, const int* kcontrast, const float* tau, int nsteps,
+                                      int* launches)
+{
+    if (nsteps < 1 || nimg < 1 || !kcontrast) return fail("nsteps < 1, nimg < 1 or no contrast factors");
+    if (p % 4 || stride % 4 || (head && sp % 4)) return fail("pitch and stride must be multiples of 4");      // (the kernel stores 16-byte groups)
+    if (head && (w != sw / 2 || h != sh / 2)) return fail("an octave head halves the source extents");
+    HakImgState* state = nullptr;
+    if (fast_state(&state, kcontrast, nimg)) return 1;
+    int taps[8];
+    fast_taps(1.f, 2, taps);
+    const HakOct dd{w, h, p, (long)h * p};
+    const int nl = hak_launch_level_tile(nullptr, src, head ? HakOct{sw, sh, sp, (long)sh * sp} : dd, head != 0, smooth, dst, tmp, stride, dd,
+                                         nimg, taps, diffusivity, tau, nsteps, state, 0);
+    if (launches) *launches = nl;
+    const int rc = fast_sync("hak_op_fast_level_tile");
+    (void)hipFree(state);
+    return rc;
+}
+
+extern "C" int hak_op_fast_hessian(const int* s, int* lx, int* ly, int* det, int w, int h, int p, int step, int* route)
+{
+    if (step < 1) return fail("step < 1");
+    // the interleaved derivatives and the determinant in ONE allocation (see hak_op_fast_base); the test interface keeps the
+    // reference's three planes
+    const size_t plane = (size_t)h * p;
+    int* buf = nullptr;
+    HIP_TRY(hipMalloc((void**)&buf, sizeof(int) * 3 * plane));
+    int *dxy = buf, *dt = buf + 2 * plane;
+    const HakKnobs kn = hak_knobs_from_env();
+    const bool fused = hak_launch_hessian_level(nullptr, s, dxy, dt, true, 0, w, h, p, 1, step, nullptr, nullptr, nullptr, 0, 0, 0);
+    hak_launch_deinterleave(nullptr, reinterpret_cast<const float*>(dxy), reinterpret_cast<float*>(lx), reinterpret_cast<float*>(ly), w, h, p);
+    // launch_hessian_level_t (kernels_hessian.hip): streaming where it pays and covers, else the tile kernel up to dilation 4
+    if (route) *route = !fused ? 3 : (hak_stream_pays(kn.hess_stream, w, h, 1) && hak_hessian_stream_covers(w, h, step, false)) ? 1 : 2;
+    int rc = fast_sync("hak_op_fast_hessian");
+    if (!rc && fused != (step <= 4)) rc = fail("hak_op_fast_hessian: unexpected route");
+    if (!rc && hipMemcpy(det, dt, sizeof(int) * plane, hipMemcpyDeviceToDevice) != hipSuccess) rc = fail("hak_op_fast_hessian: copy");
+    (void)hipFree(buf);
+    return rc;
+}
+
 // ---- detector tail / descriptors on hand-made inputs (include/hipakaze.h; tests/test_gpu_literal.py)
 static HakBatch tail_batch(hak_ctx* c)
 {

@@ -7,6 +7,8 @@
  *   hak_debug_*   planes / contrast factor of the last call on a context, writing a plane
  *   hak_op_*      single-stage operators (one h*() wrapper of akazed.cu each), the detector tail and the descriptor stages on
  *                 hand-made inputs, the conductivity's reciprocal self-check, bandwidth probes of the box
+ *   hak_op_fast_* the stage operators once more on the integer FAST path: int32 planes (any value: products wrap, conversions
+ *                 saturate), uint8 images, integer contrast factors; the `int` overloads of the same launchers
  */
 #ifndef HIPAKAZE_TEST_H
 #define HIPAKAZE_TEST_H
@@ -47,6 +49,41 @@ int hak_op_rcp_check(unsigned lo_bits, unsigned hi_bits, unsigned long long* mis
 int hak_op_smooth_flow(const float* d_src, float* d_smooth, float* d_flow, int w, int h, int p,
                        int diffusivity, float kcontrast);                                               /* hLowPass(var 1) + hFlow, akaze.cpp:403-404 */
 int hak_op_hessian(const float* d_src, float* d_lx, float* d_ly, float* d_det, int w, int h, int p, int step); /* hHessianDeterminant 2531 */
+
+/* ---- the same stage operators on the integer FAST path (namespace fastakaze, akazed.cu:2781-4367): int32 planes in 16.16 fixed
+ * point, uint8 images for the two operators that read one.  Each drives the `int` overload of the launcher its float twin drives
+ * (csrc/hak_internal.h), reads the knobs per call and synchronises before it returns.  Any int32 value is a valid plane element:
+ * products wrap, float -> int conversions saturate with NaN -> 0 (tests/fast_domain.py).  Contrast factors are the reference's
+ * integers, 0 .. 46340 (above that kcontrast * kcontrast is a signed overflow in the reference itself: rejected).
+ * The launchers do not report which kernel they took: route 3 is observed (the launcher's return value), routes 1 and 2 are INFERRED
+ * from a restatement of the streaming launchers' cover rules in hak_test_api.hip (launch_base_stream, hak_hessian_stream_covers +
+ * hak_stream_pays) -- keep the two in step when a launcher's guard changes.
+ *   route (hak_op_fast_base):    1 streaming prologue (k_base_stream), 2 tile prologue (kf_base), 3 unfused (the three launches
+ *                                of the launch sequence where hak_launch_base_level does not cover the radius)
+ *   route (hak_op_fast_hessian): 1 streaming (k_hessian_stream), 2 tile (k_hessian_fused), 3 dilation > 4 (kf_derivate + kf_hessian) */
+int hak_op_fast_conv_u8(const unsigned char* d_u8, int sp, int* d_dst, int w, int h, int p, float var, int radius);   /* gConv2d<R> 2990, gConv2dR2 2786 */
+int hak_op_fast_lowpass(const int* d_src, int* d_dst, int w, int h, int p, float var, int radius);                    /* gConv2dR2 (int) 2922 */
+/* the octave-0 prologue (akaze.cpp:589-623): Lt(0,0) = the base Gaussian (var_base, radius) of the image, and the contrast factor,
+ * lattice maximum and histogram of its sigma = 1 low-pass, through the fused prologue the context would pick under the knobs */
+int hak_op_fast_base(const unsigned char* d_u8, int sp, int* d_lt, int w, int h, int p, float var_base, int radius, float per,
+                     int* kcontrast, int* hmax, int* hist300, int* route);
+int hak_op_fast_down_smooth(const int* d_src, int* d_dst, int* d_smooth, int sw, int sh, int sp, int dw, int dh, int dp);
+int hak_op_fast_kcontrast(const int* d_smooth, int w, int h, int p, float per, int* kcontrast, int* hmax, int* hist300);
+int hak_op_fast_flow(const int* d_src, int* d_dst, int w, int h, int p, int diffusivity, int kcontrast);
+int hak_op_fast_smooth_flow(const int* d_src, int* d_smooth, int* d_flow, int w, int h, int p, int diffusivity, int kcontrast);
+/* n steps in the groups of the FAST launch sequence (at most 4 steps per launch whatever HAK_FED_MAX_FUSE allows the float path) */
+int hak_op_fast_nld_steps(const int* d_src, const int* d_flow, int* d_dst, int* d_tmp, int w, int h, int p, const float* tau, int nsteps);
+int hak_op_fast_nld_steps_batch(const int* d_src, const int* d_flow, int* d_dst, int* d_tmp, long stride, int w, int h, int p,
+                                int nimg, const float* tau, int nsteps);
+/* hak_op_fed_cycle on int32 planes (PM_G2 only; fails when the fused kernel does not cover the case); kcontrast: one per image */
+int hak_op_fast_fed_cycle(const int* d_src, int head, int sw, int sh, int sp, int* d_smooth, int* d_flow, int* d_dst, int* d_tmp,
+                          long stride, int w, int h, int p, int nimg, const int* kcontrast, const float* tau, int nsteps);
+/* one whole sublevel per launch out of LDS tiles (k_level_tile, without the level's Hessian): head != 0 decimates the sw x sh
+ * source plane first.  d_smooth and d_dst receive the low-pass and L after nsteps steps (d_tmp: cycles of more than 36 steps) */
+int hak_op_fast_level_tile(const int* d_src, int head, int sw, int sh, int sp, int* d_smooth, int* d_dst, int* d_tmp, long stride,
+                           int w, int h, int p, int nimg, int diffusivity, const int* kcontrast, const float* tau, int nsteps,
+                           int* launches);   /* *launches (may be NULL): what hak_launch_level_tile returns, the kernel launches of the cycle */
+int hak_op_fast_hessian(const int* d_src, int* d_lx, int* d_ly, int* d_det, int w, int h, int p, int step, int* route);
 
 /* ---- detector-tail and descriptor stages on hand-made inputs (tests/test_gpu_literal.py: micro-fixtures whose expected
  * output is derived by hand from the cited reference statements).  They drive the SAME launchers as the launch sequence, on

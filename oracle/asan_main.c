@@ -1,7 +1,8 @@
 /*
  * asan_main.c -- runs the CPU oracle (float path, integer FAST path, both matchers) under AddressSanitizer + UBSan on a few
  * seeded scenes, including odd sizes, a clamp below the keypoint count, no-descriptor and upright runs (SURVEY.md 5:
- * "sanitizers on the CPU build").  TEST INFRASTRUCTURE ONLY, like everything in oracle/: `make -C oracle asan`.
+ * "sanitizers on the CPU build"), and every stage function of the FAST path once on int32 planes far outside the uint8 range
+ * (run_stages).  TEST INFRASTRUCTURE ONLY, like everything in oracle/: `make -C oracle asan`.
  * Signed wrap-around in the FAST path is spelled out with unsigned arithmetic there, so UBSan's signed-overflow check stays on.
  */
 #include <stdio.h>
@@ -20,6 +21,14 @@ int fkz_detect_and_compute(const unsigned char* image, int w, int h, int sp, int
 void okz_match(Pt* pts1, int n1, const Pt* pts2, int n2);
 int okz_match_knn2(Pt* pts1, int n1, const Pt* pts2, int n2, int ratio_num, int ratio_den, int cross, int max_dist, MatchPair* out);
 int okz_sizeof_point(void);
+void fkz_gauss_taps(float var, int radius, int* ik);
+void fkz_conv_u8(const unsigned char* src, int sp, int* dst, int w, int h, int p, const int* k, int R);
+void fkz_conv_int(const int* src, int* dst, int w, int h, int p, const int* k, int R);
+void fkz_down_smooth(const int* src, int* dst, int* smooth, int sw, int sh, int sp, int dw, int dh, int dp, const int* k);
+int fkz_kcontrast(const int* smooth, int w, int h, int p, float per, int* hmax_out, int* hist_out);
+void fkz_flow(const int* src, int* dst, int type, int kcontrast, int w, int h, int p);
+void fkz_nld_step(const int* src, const int* flow, int* dst, float tau, int w, int h, int p);
+void fkz_hessian(const int* src, int* dxo, int* dyo, int* det, int step, int w, int h, int p);
 
 static unsigned rng_state;
 static unsigned rnd(void) { rng_state ^= rng_state << 13; rng_state ^= rng_state >> 17; rng_state ^= rng_state << 5; return rng_state; }
@@ -73,9 +82,63 @@ static int run_case(int w, int h, const Prm* prm, int max_pts, int desc)
     return n[0] + nf[0];
 }
 
+/* Every FAST stage function once on int32 planes far outside what a uint8 image yields (tests/fast_domain.py has the full-size
+ * generators): `ramp_blown`, the scene times an amplitude that rises from 2^6 to 2^22 across the plane, and `full_range`, random
+ * int32 with INT_MIN / INT_MAX / -1 / 0 on the border.  The statement claims to cover any int32 value and contrast factors
+ * 0 .. 46340: wrapping products, a negative sum of squares under sqrt, a saturating conversion -- none of it may be undefined here. */
+static long run_stages(int w, int h, int full_range)
+{
+    int p = (w + 63) / 64 * 64, dw = w / 2, dh = h / 2, dp = (dw + 63) / 64 * 64;
+    size_t n = (size_t)h * p;
+    unsigned char* u8 = malloc((size_t)w * h);
+    int *a = calloc(n, sizeof(int)), *sm = calloc(n, sizeof(int)), *g = calloc(n, sizeof(int)), *o1 = calloc(n, sizeof(int));
+    int *o2 = calloc(n, sizeof(int)), *o3 = calloc(n, sizeof(int)), *d1 = calloc((size_t)dh * dp, sizeof(int)), *d2 = calloc((size_t)dh * dp, sizeof(int));
+    scene(u8, w, h, 11u + (unsigned)full_range, 0);
+    static const int special[4] = {(int)0x80000000, 0x7FFFFFFF, -1, 0};
+    for (int y = 0; y < h; y++)
+        for (int x = 0; x < w; x++) {
+            if (full_range) {
+                unsigned v = rnd() ^ (rnd() << 7);
+                int edge = y == 0 || y == h - 1 || x == 0 || x == w - 1;
+                a[(size_t)y * p + x] = edge ? special[(x + y) & 3] : (int)v;
+            } else {
+                int shift = 6 + 16 * x / (w - 1);                              /* amplitude 2^6 .. 2^22: 255 << 22 < 2^31 */
+                a[(size_t)y * p + x] = (int)((unsigned)u8[(size_t)y * w + x] << shift);
+            }
+        }
+    int k1[8] = {0}, kb[8] = {0}, hist[300], hmax = 0;
+    long sum = 0;
+    fkz_gauss_taps(1.f, 2, k1);
+    fkz_gauss_taps(3.2f, 5, kb);
+    fkz_conv_u8(u8, w, o1, w, h, p, kb, 5);
+    fkz_conv_int(a, sm, w, h, p, k1, 2);
+    fkz_conv_int(a, o1, w, h, p, kb, 5);
+    fkz_down_smooth(a, d1, d2, w, h, p, dw, dh, dp, k1);
+    int kc = fkz_kcontrast(sm, w, h, p, 0.7f, &hmax, hist);
+    sum += fkz_kcontrast(a, w, h, p, 0.7f, &hmax, hist) + hist[0];
+    static const int kcs[4] = {0, 1, 46340, -1};                              /* -1: the plane's own */
+    for (int type = 0; type < 4; type++)
+        for (int i = 0; i < 4; i++) {
+            fkz_flow(a, g, type, kcs[i] < 0 ? kc : kcs[i], w, h, p);
+            fkz_nld_step(a, g, o1, 41.f, w, h, p);                             /* stepfac * step wraps (F1) */
+            fkz_nld_step(o1, g, o2, 0.07f, w, h, p);
+            sum += o2[(size_t)(h / 2) * p + w / 2];
+        }
+    for (int step = 1; step <= 6; step++) {
+        fkz_hessian(a, o1, o2, o3, step, w, h, p);
+        sum += o3[(size_t)(h / 2) * p + w / 2];
+    }
+    printf("  stage functions on a %3d x %-3d %s plane: own contrast factor %d, lattice maximum %d\n", w, h, full_range ? "full_range" : "ramp_blown",
+           kc, hmax);
+    free(u8); free(a); free(sm); free(g); free(o1); free(o2); free(o3); free(d1); free(d2);
+    return sum;
+}
+
 int main(void)
 {
     if (okz_sizeof_point() != (int)sizeof(Pt) || sizeof(Pt) != 104) { fprintf(stderr, "record layout drifted\n"); return 1; }
+    long stage_sum = run_stages(83, 81, 0) + run_stages(83, 81, 1) + run_stages(132, 70, 0) + run_stages(132, 70, 1);
+    (void)stage_sum;
     Prm d = {4, 4, 0.7f, 0.03f, 1.6f, 1, 1.5f, 0.001f, 1, 10, 0};     /* main.cpp:156-166 */
     int total = 0;
     total += run_case(320, 240, &d, 10000, 1);

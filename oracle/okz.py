@@ -314,6 +314,95 @@ def plane(r, kind, o, s):
 
 
 # ------------------------------------------------------------------ integer FAST path (akaze_oracle_fast.c)
+# ---- single stages on pitched int32 planes (shape (h, p), valid width w; uint8 images for fast_conv_u8); the statement covers
+# every int32 value and integer contrast factors 0 .. FAST_KC_MAX (oracle/README.md)
+FAST_KC_MAX = 46340                 # kcontrast * kcontrast is a signed overflow above it, in the reference as in fkz_flow
+
+
+def _i(a):
+    assert a.dtype == np.int32 and a.flags.c_contiguous
+    return a.ctypes.data_as(_ip)
+
+
+def fast_gauss_taps(var, radius):
+    k = np.zeros(8, np.int32)
+    lib().fkz_gauss_taps(C.c_float(var), C.c_int(radius), _i(k))
+    return k[:radius + 1].copy()
+
+
+def fast_deriv_factors():
+    a, b = C.c_int(), C.c_int()
+    lib().fkz_deriv_factors(C.byref(a), C.byref(b))
+    return a.value, b.value
+
+
+def _taps8(var, radius):
+    k = np.zeros(8, np.int32)
+    k[:radius + 1] = fast_gauss_taps(var, radius)
+    return k
+
+
+def fast_conv_u8(u8, w, p, var, radius):
+    """u8: uint8 (h, sp) pitched image -> int32 (h, p)"""
+    assert u8.dtype == np.uint8 and u8.flags.c_contiguous
+    h, sp = u8.shape
+    dst = np.zeros((h, p), np.int32)
+    lib().fkz_conv_u8(u8.ctypes.data_as(C.c_void_p), C.c_int(sp), _i(dst), C.c_int(w), C.c_int(h), C.c_int(p), _i(_taps8(var, radius)),
+                      C.c_int(radius))
+    return dst
+
+
+def fast_lowpass(src, w, var, radius):
+    h, p = src.shape
+    dst = np.zeros_like(src)
+    lib().fkz_conv_int(_i(src), _i(dst), C.c_int(w), C.c_int(h), C.c_int(p), _i(_taps8(var, radius)), C.c_int(radius))
+    return dst
+
+
+def fast_down_smooth(src, sw, dw, dh, dp):
+    sh, sp = src.shape
+    dst, sm = np.zeros((dh, dp), np.int32), np.zeros((dh, dp), np.int32)
+    lib().fkz_down_smooth(_i(src), _i(dst), _i(sm), C.c_int(sw), C.c_int(sh), C.c_int(sp), C.c_int(dw), C.c_int(dh), C.c_int(dp),
+                          _i(_taps8(1.0, 2)))
+    return dst, sm
+
+
+def fast_kcontrast(smooth, w, per):
+    """-> (kcontrast, hmax, hist[300]) of the sigma = 1 plane, all integers"""
+    h, p = smooth.shape
+    hmax = C.c_int()
+    hist = np.zeros(300, np.int32)
+    L = lib()
+    L.fkz_kcontrast.restype = C.c_int
+    kc = L.fkz_kcontrast(_i(smooth), C.c_int(w), C.c_int(h), C.c_int(p), C.c_float(per), C.byref(hmax), _i(hist))
+    return int(kc), int(hmax.value), hist
+
+
+def fast_flow(src, w, diffusivity, kc):
+    assert 0 <= int(kc) <= FAST_KC_MAX
+    h, p = src.shape
+    d = np.zeros_like(src)
+    lib().fkz_flow(_i(src), _i(d), C.c_int(diffusivity), C.c_int(int(kc)), C.c_int(w), C.c_int(h), C.c_int(p))
+    return d
+
+
+def fast_nld_steps(src, g, w, taus):
+    h, p = src.shape
+    cur = src.copy()
+    for t in taus:
+        nxt = np.zeros_like(cur)
+        lib().fkz_nld_step(_i(cur), _i(g), _i(nxt), C.c_float(float(t)), C.c_int(w), C.c_int(h), C.c_int(p))
+        cur = nxt
+    return cur
+
+
+def fast_hessian(src, w, step):
+    h, p = src.shape
+    lx, ly, det = np.zeros_like(src), np.zeros_like(src), np.zeros_like(src)
+    lib().fkz_hessian(_i(src), _i(lx), _i(ly), _i(det), C.c_int(step), C.c_int(w), C.c_int(h), C.c_int(p))
+    return lx, ly, det
+
+
 def fast_detect_and_compute(u8, params=None, max_pts=10000, desc=True, keep_arena=False):
     """u8: uint8 (h, w) image (dense).  Returns Result(points, kcontrast[, arena of int32])."""
     params = params or default_params()
