@@ -167,6 +167,7 @@ TEST_SYMBOLS = {
     "hak_op_tail_seed": (C.c_int, [_vp, _vp, _vp]),
     "hak_op_tail_finish": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _ip]),
     "hak_op_orient_describe": (C.c_int, [_vp, _vp, C.c_int, C.c_int]),
+    "hak_op_fast_orient_describe": (C.c_int, [_vp, _vp, C.c_int, C.c_int]),
     "hak_op_copy_probe": (C.c_int, [C.c_long, C.c_int, C.POINTER(C.c_double)]),
     "hak_op_copy_probe_shapes": (C.c_int, [C.c_long, C.c_int, C.POINTER(C.c_double), C.c_int]),
     "hak_op_stream_probe": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
@@ -423,8 +424,10 @@ class Akazer:
         return out
 
     def set_plane(self, kind, octave, sublevel, plane, img=0):
-        """hak_debug_set_plane: dense (h, w) float32 -> plane (0 Lt, 2 Lx, 3 Ly) of the level"""
-        plane = np.ascontiguousarray(plane, np.float32)
+        """hak_debug_set_plane: dense (h, w) float32 -> plane (0 Lt, 2 Lx, 3 Ly) of the level.  An int32 array (a plane of the FAST
+        path) goes in bit for bit: the entry point copies words"""
+        plane = np.asarray(plane)
+        plane = np.ascontiguousarray(plane).view(np.float32) if plane.dtype == np.int32 else np.ascontiguousarray(plane, np.float32)
         w, h, _ = self.geometry()[octave]
         assert plane.shape == (h, w), (plane.shape, (h, w))
         check(lib.hak_debug_set_plane(self.ctx, img, kind, octave, sublevel, plane.ctypes.data))
@@ -462,20 +465,25 @@ class Akazer:
         finally:
             freeAkazeData(data)
 
-    def orient_describe(self, points, desc=1):
-        """orientation + MLDB (desc=1) or MLDB with the records' own angles (desc=2) on host records; returns them updated"""
+    def orient_describe(self, points, desc=1, fast=False):
+        """orientation + MLDB (desc=1) or MLDB with the records' own angles (desc=2) on host records; returns them updated.
+        fast=True: hak_op_fast_orient_describe -- refinement + orientation + MLDB of the integer FAST path on int32 planes"""
         points = np.ascontiguousarray(points)
         assert points.dtype == POINT_DTYPE and len(points) >= 1
         data = AkazeData()
         initAkazeData(data, len(points), False, True)
         try:
             check(lib.hak_memcpy_h2d(data.d_data, points.ctypes.data, points.nbytes))
-            check(lib.hak_op_orient_describe(self.ctx, data.d_data, len(points), int(desc)))
+            op = lib.hak_op_fast_orient_describe if fast else lib.hak_op_orient_describe
+            check(op(self.ctx, data.d_data, len(points), int(desc)))
             out = np.zeros(len(points), POINT_DTYPE)
             check(lib.hak_memcpy_d2h(out.ctypes.data, data.d_data, out.nbytes))
             return out
         finally:
             freeAkazeData(data)
+
+    def fast_orient_describe(self, points, desc=1):
+        return self.orient_describe(points, desc, fast=True)
 
     def kcontrast(self, img=0):
         v = C.c_float()

@@ -460,7 +460,9 @@ extern "C" int hak_op_fast_hessian(const int* s, int* lx, int* ly, int* det, int
 // ---- detector tail / descriptors on hand-made inputs (include/hipakaze.h; tests/test_gpu_literal.py)
 static HakBatch tail_batch(hak_ctx* c)
 {
-    HakBatch b{c->arena, c->L.arena, 1, c->state, c->maps, c->L.oct[0].plane, c->bitmap, c->rowcount, c->cand, c->cand_cap, &c->knobs};
+    // (with the context's permutation buffer, as level_args of the launch sequence: HAK_DESC_SORT reaches the descriptor stages)
+    HakBatch b{c->arena, c->L.arena, 1, c->state, c->maps, c->L.oct[0].plane, c->bitmap, c->rowcount, c->cand, c->cand_cap, &c->knobs,
+               c->perm, c->cfg.max_pts};
     hak_batch_selection(c, b);                                      // (hak_op_tail_finish selects like the detect entry points)
     return b;
 }
@@ -572,6 +574,19 @@ extern "C" int hak_op_orient_describe(hak_ctx* c, hak_point* d_points, int n, in
     hak_launch_describe(c->stream, tail_batch(c), c->L, c->dtab, d_points, n, c->cfg.descriptor_pattern_size, c->cfg.upright, desc ? 1 : 0,
                         c->htab.dsc_plan_ok, desc == 2 ? 0 : 1);
     if (hipGetLastError() != hipSuccess) return fail("describe launch failed");
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// the FAST twin: k_orient<int> (refinement akazed.cu:3600 + orientation 3649) and the MLDB kernel (3723) on int32 planes, which go in
+// through hak_debug_set_plane as bit patterns.  Upright contexts still run k_orient<int>, for the refinement alone.
+extern "C" int hak_op_fast_orient_describe(hak_ctx* c, hak_point* d_points, int n, int desc)
+{
+    if (!c || !d_points || n < 1) return fail("bad argument");
+    HIP_TRY(hipMemcpy(&c->state[0].num_pts, &n, sizeof(int), hipMemcpyHostToDevice));
+    hakf_launch_describe(c->stream, tail_batch(c), c->L, c->dtab, d_points, n, c->cfg.descriptor_pattern_size, c->cfg.upright, desc ? 1 : 0,
+                         c->htab.dsc_plan_ok);
+    if (hipGetLastError() != hipSuccess) return fail("FAST describe launch failed");
     HIP_TRY(hipStreamSynchronize(c->stream));
     return 0;
 }

@@ -97,7 +97,11 @@ int hak_op_fast_hessian(const int* d_src, int* d_lx, int* d_ly, int* d_det, int 
  *   hak_op_tail_seed      hand-made full-resolution maps: response words (float or int bits) and layer ids (< 0: empty)
  *   hak_op_tail_finish    gNmsRNaive 1554 (+ gRefine 1615 when `refine`) -> d_points in raster order; *num_pts = survivors
  *   hak_op_orient_describe gCalcOrient 1665 + gDescribe2 1869 on the first n records of d_points, reading the planes the
- *                         arena holds now (desc: 0 none, 1 both, 2 descriptor only with the records' own angles) */
+ *                         arena holds now (desc: 0 none, 1 both, 2 descriptor only with the records' own angles)
+ *   hak_op_fast_orient_describe  the same on the integer FAST path: gRefine 3600 + gCalcOrient 3649 + gDescribe2 3723 through
+ *                         hakf_launch_describe, on int32 planes (written with hak_debug_set_plane, which copies bits: pass the int32
+ *                         array as it lies in memory).  desc: 0 refinement only, otherwise refinement + orientation (unless the
+ *                         context is upright) + MLDB; there is no descriptor-only mode, the FAST sequence has none */
 int hak_debug_set_plane(hak_ctx* ctx, int img, int kind, int octave, int sublevel, const float* h_src);
 int hak_op_tail_begin(hak_ctx* ctx);
 int hak_op_tail_level(hak_ctx* ctx, int octave, int sublevel, const float* h_src);
@@ -105,6 +109,7 @@ int hak_op_tail_det_level(hak_ctx* ctx, int octave, int sublevel, const float* h
 int hak_op_tail_seed(hak_ctx* ctx, const unsigned int* h_response_bits, const int* h_layer);
 int hak_op_tail_finish(hak_ctx* ctx, hak_point* d_points, int max_pts, int refine, int fast, int* num_pts);
 int hak_op_orient_describe(hak_ctx* ctx, hak_point* d_points, int n, int desc);
+int hak_op_fast_orient_describe(hak_ctx* ctx, hak_point* d_points, int n, int desc);
 
 /* ---- bandwidth ceilings of the box (SURVEY 8d "copy-kernel ceiling"; not on the hot path).
  * hak_op_copy_probe: float4 copy of `bytes` with the streaming kernels' access shape (16 B/lane), `iters` times per launch

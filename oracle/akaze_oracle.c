@@ -93,6 +93,54 @@ static inline int iabs(int a) { return a < 0 ? -a : a; }
 
 int okz_sizeof_point(void) { return (int)sizeof(OkzPoint); }
 
+/* Census of the point functions (tests/keypoint_stage.py): which of their narrow places the calls since okz_census_begin went
+ * through.  The tests assert these counts on the oracle alone, so that a change of the planted keypoints cannot silently stop
+ * exercising an edge.  Off (NULL) unless a test asks; per thread, so the pipeline's worker threads never see it. */
+typedef struct OkzCensus {
+    int clamp[4];               /* MLDB samples clamped at the left / right / top / bottom edge of the plane */
+    float min_edge;             /* smallest distance of an unrounded MLDB sample coordinate to the plane edge it is nearest to */
+    int bin_hi, bin_lo;         /* orientation samples whose bin was clamped from above 41 / from below 0 */
+    int bin0, bin41;            /* orientation samples that landed in bin 0 / 41 */
+    int maxk;                   /* winning window start of the last orientation call */
+    int refined;                /* the last refinement call moved its point (1) or rejected the step (0) */
+    int saturated;              /* FAST rotated derivatives that left the int range */
+    int tie;                    /* windows of the last orientation call that equal the winner's weight with another vector sum */
+} OkzCensus;
+_Thread_local OkzCensus* okz_census = NULL;
+void okz_census_begin(OkzCensus* c)
+{
+    if (c) { memset(c, 0, sizeof(*c)); c->min_edge = 1e30f; c->maxk = -1; c->refined = -1; }
+    okz_census = c;
+}
+void okz_census_sample(float fx, float fy, int xp, int yp, int w, int h)
+{
+    OkzCensus* c = okz_census;
+    if (!c) return;
+    c->clamp[0] += xp < 0; c->clamp[1] += xp > w - 1; c->clamp[2] += yp < 0; c->clamp[3] += yp > h - 1;
+    float d = fx;
+    if ((float)(w - 1) - fx < d) d = (float)(w - 1) - fx;
+    if (fy < d) d = fy;
+    if ((float)(h - 1) - fy < d) d = (float)(h - 1) - fy;
+    if (d < c->min_edge) c->min_edge = d;
+}
+void okz_census_winner(const float* re8x, const float* re8y, int maxk)
+{
+    OkzCensus* c = okz_census;
+    if (!c) return;
+    float maxr = re8x[maxk] * re8x[maxk] + re8y[maxk] * re8y[maxk];
+    c->maxk = maxk;
+    c->tie = 0;
+    for (int k = 0; k < 42; k++)
+        c->tie += k != maxk && maxr > 0.f && re8x[k] * re8x[k] + re8y[k] * re8y[k] == maxr && (re8x[k] != re8x[maxk] || re8y[k] != re8y[maxk]);
+}
+void okz_census_bin(int a)
+{
+    OkzCensus* c = okz_census;
+    if (!c) return;
+    c->bin_hi += a > 41; c->bin_lo += a < 0;
+    c->bin0 += a <= 0; c->bin41 += a >= 41;
+}
+
 /* The team size of the oracle's parallel loops, set explicitly: OMP_NUM_THREADS is read once, when libgomp initialises -- in a
  * process that has imported torch that happened long before the oracle's first call, and the loops then ran with one thread per
  * logical CPU of the box (256 on the GPU boxes: 10 x slower than 16, which is what bench.py's cpu_baseline reported until round 5). */
@@ -531,6 +579,7 @@ void okz_refine_point(OkzPoint* pt, const float* det, int o, int p)
     float dst0 = idd * (dxy * dy - dyy * dx);
     float dst1 = idd * (dxy * dx - dxx * dy);
     int weak = dst0 < -1.f || dst0 > 1.f || dst1 < -1.f || dst1 > 1.f;
+    if (okz_census) okz_census->refined = !weak;
     if (weak) return;
     int ratio = 1 << o;
     pt->y = ratio * (y + dst1);
@@ -570,6 +619,7 @@ void okz_orient_point(OkzPoint* pt, const float* dxd, const float* dyd, int o, i
         float dy = gweight * dyd[pos];
         float angle = okz_atan2f(dy, dx);
         int a = okz_d2i(angle * (21 / OKZ_PI_D)) + 21;                  /* :1702 (double) */
+        okz_census_bin(a);
         a = a > 41 ? 41 : a;
         a = a < 0 ? 0 : a;
         resx[a] += dx;
@@ -589,6 +639,7 @@ void okz_orient_point(OkzPoint* pt, const float* dxd, const float* dyd, int o, i
         float r = re8x[k] * re8x[k] + re8y[k] * re8y[k];
         if (r > maxr) { maxr = r; maxk = k; }
     }
+    okz_census_winner(re8x, re8y, maxk);
     /* dFastAtan2 akazed.cu:173-185 */
     float yv = re8y[maxk], xv = re8x[maxk];
     float absx = fabsf(xv), absy = fabsf(yv);
@@ -652,6 +703,7 @@ void okz_describe_point(OkzPoint* pt, const float* imd, const float* dxd, const 
             int k = y - size2;
             int xp = okz_d2i(xf + scale * (k * co - l * si) + 0.5f);    /* :1921 */
             int yp = okz_d2i(yf + scale * (k * si + l * co) + 0.5f);    /* :1922 */
+            okz_census_sample(xf + scale * (k * co - l * si), yf + scale * (k * si + l * co), xp, yp, w, h);
             xp = clampi(xp, 0, w - 1);
             yp = clampi(yp, 0, h - 1);
             size_t pos = (size_t)yp * p + xp;
@@ -807,6 +859,32 @@ int okz_layout(int w, int h, int p, int noctaves, int max_scale, int* owhps, int
         offsets[k] = offsets[j] + osizes[j] * max_scale * 4;
     }
     return n;
+}
+
+/* The per-level constants of the detector as okz_detect_and_compute / fkz_detect_and_compute form them below (akaze.cpp:336-338,
+ * 357-366, 279): sizes, dilations (sigma_size) and borders of the noct * max_scale levels, for the tests that plant keypoints on
+ * given planes (tests/keypoint_stage.py).  Returns the border size psz of the NMS (akaze.cpp:434). */
+int okz_schedule(const OkzParams* prm, int noct, float* sizes, int* sigma_size, float* borders)
+{
+    int ms = prm->max_scale, oratio = 1;
+    float smax = (float)(10.0 * sqrtf(2.0f)), psz = 10000;
+    for (int i = 0; i < noct; i++) {
+        for (int j = 0; j < ms; j++) {
+            int l = i * ms + j;
+            if (j == 0 && i == 0) {
+                sizes[l] = prm->soffset * prm->derivative_factor;
+                sigma_size[l] = (int)(prm->soffset * prm->derivative_factor + 0.5f);
+            } else {
+                float esigma = prm->soffset * powf(2, (float)j / ms + i);
+                sizes[l] = esigma * prm->derivative_factor / oratio;
+                sigma_size[l] = (int)(sizes[l] + 0.5f);
+            }
+            borders[l] = smax * sigma_size[l];
+        }
+        psz = psz < borders[i * ms] * oratio ? psz : borders[i * ms] * oratio;
+        oratio *= 2;
+    }
+    return (int)psz;
 }
 
 /* number of floats okz_detect_and_compute needs in `arena` */

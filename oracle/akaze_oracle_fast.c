@@ -48,6 +48,12 @@ int okz_fed_tau(float T, int M, float tau_max, int reordering, float* tau, int c
 void okz_compare_indices(int* idx1, int* idx2);
 extern int okz_reading_variant;   /* akaze_oracle.c: alternative readings for tools/ref_render_check.py; 0 everywhere else */
 int okz_layout(int w, int h, int p, int noctaves, int max_scale, int* owhps, int* osizes, int* offsets);
+/* the census of the point functions (akaze_oracle.c) */
+typedef struct OkzCensus { int clamp[4]; float min_edge; int bin_hi, bin_lo, bin0, bin41, maxk, refined, saturated, tie; } OkzCensus;
+extern _Thread_local OkzCensus* okz_census;
+void okz_census_sample(float fx, float fy, int xp, int yp, int w, int h);
+void okz_census_bin(int a);
+void okz_census_winner(const float* re8x, const float* re8y, int maxk);
 
 static inline int fborder_add(int a, int b, int m) { int c = a + b; return c < m ? c : m + m - 2 - c; }
 static inline int fiabs(int a) { return a < 0 ? -a : a; }
@@ -365,7 +371,9 @@ void fkz_refine(FkPoint* pt, const int* det, int o, int p)
     float idd = dd != 0 ? (1.f / dd) : 0.f;
     float dst0 = idd * wsub(wmul(dxy, dy), wmul(dyy, dx));
     float dst1 = idd * wsub(wmul(dxy, dx), wmul(dxx, dy));
-    if (dst0 < -1.f || dst0 > 1.f || dst1 < -1.f || dst1 > 1.f) return;
+    int weak = dst0 < -1.f || dst0 > 1.f || dst1 < -1.f || dst1 > 1.f;
+    if (okz_census) okz_census->refined = !weak;
+    if (weak) return;
     int ratio = 1 << o;
     pt->y = ratio * (y + dst1);
     pt->x = ratio * (x + dst0);
@@ -398,6 +406,7 @@ void fkz_orient(FkPoint* pt, const int* dxd, const int* dyd, int o, int w, int h
         float dx = wtab[r2] * dxd[pos], dy = wtab[r2] * dyd[pos];
         float angle = fast_atan2(dy, dx);
         int a = d2i_sat(angle * (21 / OKZ_PI_D)) + 21;                 /* (NaN for a sample without gradient: 0 on the device) */
+        okz_census_bin(a);
         a = a > 41 ? 41 : a; a = a < 0 ? 0 : a;
         resx[a] += dx; resy[a] += dy;
     }
@@ -407,6 +416,7 @@ void fkz_orient(FkPoint* pt, const int* dxd, const int* dyd, int o, int w, int h
     }
     float maxr = 0.0f; int maxk = 0;
     for (int k = 0; k < 42; k++) { float r = re8x[k] * re8x[k] + re8y[k] * re8y[k]; if (r > maxr) { maxr = r; maxk = k; } }
+    okz_census_winner(re8x, re8y, maxk);
     float r = fast_atan2(re8y[maxk], re8x[maxk]);
     pt->angle = (r < 0.0f ? (float)(r + 2.0f * OKZ_PI_D) : r);
 }
@@ -426,12 +436,15 @@ void fkz_describe(FkPoint* pt, const int* imd, const int* dxd, const int* dyd, i
     for (int i = 0; i < winsize * winsize; i++) {
         int y = i / winsize, x = i - winsize * y, m = x > y ? x : y;
         int l = x - size2, k = y - size2;
-        int xp = clampi(f2i_sat(xf + scale * (k * co - l * si) + 0.5f), 0, w - 1);
-        int yp = clampi(f2i_sat(yf + scale * (k * si + l * co) + 0.5f), 0, h - 1);
+        int xp = f2i_sat(xf + scale * (k * co - l * si) + 0.5f), yp = f2i_sat(yf + scale * (k * si + l * co) + 0.5f);
+        okz_census_sample(xf + scale * (k * co - l * si), yf + scale * (k * si + l * co), xp, yp, w, h);
+        xp = clampi(xp, 0, w - 1);
+        yp = clampi(yp, 0, h - 1);
         size_t pos = (size_t)yp * p + xp;
         int im = imd[pos], dx = dxd[pos], dy = dyd[pos];
-        int rx = f2i_sat(wneg(dx) * si + dy * co);                           /* akazed.cu:3777 */
-        int ry = f2i_sat(dx * co + dy * si);
+        float frx = wneg(dx) * si + dy * co, fry = dx * co + dy * si;       /* akazed.cu:3777 */
+        int rx = f2i_sat(frx), ry = f2i_sat(fry);
+        if (okz_census) okz_census->saturated += (frx >= 2147483648.0f || frx < -2147483648.0f) + (fry >= 2147483648.0f || fry < -2147483648.0f);
         if (m < 2 * size2) { int c = 3 * ((y < size2 ? 0 : 2) + (x < size2 ? 0 : 1)); acc[c] = wadd(acc[c], im); acc[c + 1] = wadd(acc[c + 1], rx); acc[c + 2] = wadd(acc[c + 2], ry); }
         if (m < 3 * size3) {
             int x3 = (x < size3 ? 0 : (x < 2 * size3 ? 1 : 2)), y3 = (y < size3 ? 0 : (y < 2 * size3 ? 1 : 2));

@@ -2,7 +2,9 @@
  * asan_main.c -- runs the CPU oracle (float path, integer FAST path, both matchers) under AddressSanitizer + UBSan on a few
  * seeded scenes, including odd sizes, a clamp below the keypoint count, no-descriptor and upright runs (SURVEY.md 5:
  * "sanitizers on the CPU build"), and every stage function of the FAST path once on int32 planes far outside the uint8 range
- * (run_stages).  TEST INFRASTRUCTURE ONLY, like everything in oracle/: `make -C oracle asan`.
+ * (run_stages), and the six point functions on keypoints planted on the limits and corners of every level's accepted domain, turned to
+ * the diagonals (run_points; tests/keypoint_stage.py has the full case list).  TEST INFRASTRUCTURE ONLY, like everything in
+ * oracle/: `make -C oracle asan`.
  * Signed wrap-around in the FAST path is spelled out with unsigned arithmetic there, so UBSan's signed-overflow check stays on.
  */
 #include <stdio.h>
@@ -29,6 +31,19 @@ int fkz_kcontrast(const int* smooth, int w, int h, int p, float per, int* hmax_o
 void fkz_flow(const int* src, int* dst, int type, int kcontrast, int w, int h, int p);
 void fkz_nld_step(const int* src, const int* flow, int* dst, float tau, int w, int h, int p);
 void fkz_hessian(const int* src, int* dxo, int* dyo, int* det, int step, int w, int h, int p);
+
+int okz_layout(int w, int h, int p, int noctaves, int max_scale, int* owhps, int* osizes, int* offsets);
+int okz_schedule(const Prm* prm, int noct, float* sizes, int* sigma_size, float* borders);
+void okz_orient_weights(float* tab);
+void okz_compare_indices(int* idx1, int* idx2);
+void okz_derivate(const float* src, float* dxo, float* dyo, int step, int w, int h, int p);
+void okz_hessian(const float* dx, const float* dy, float* det, int step, int w, int h, int p);
+void okz_refine_point(Pt* pt, const float* det, int o, int p);
+void okz_orient_point(Pt* pt, const float* dxd, const float* dyd, int o, int w, int h, int p, const float* wtab);
+void okz_describe_point(Pt* pt, const float* imd, const float* dxd, const float* dyd, int o, int w, int h, int p, int patsize, const int* idx1, const int* idx2);
+void fkz_refine(Pt* pt, const int* det, int o, int p);
+void fkz_orient(Pt* pt, const int* dxd, const int* dyd, int o, int w, int h, int p, const float* wtab);
+void fkz_describe(Pt* pt, const int* imd, const int* dxd, const int* dyd, int o, int w, int h, int p, int patsize, const int* idx1, const int* idx2);
 
 static unsigned rng_state;
 static unsigned rnd(void) { rng_state ^= rng_state << 13; rng_state ^= rng_state >> 17; rng_state ^= rng_state << 5; return rng_state; }
@@ -134,10 +149,76 @@ static long run_stages(int w, int h, int full_range)
     return sum;
 }
 
+/* The six point functions on planted keypoints: the four corners and four limit mid-points of every level's accepted domain (the
+ * border rule of okz_extrema_map), at the integer position and one level pixel off it on either side, turned to the four
+ * diagonals -- where the farthest MLDB sample comes within a pixel of the plane edge (pattern 10) or is clamped (pattern 12).
+ * Every plane is allocated with exactly h * p elements: a read outside it is an ASan error.  The int planes hold any int32. */
+static long run_points(int w, int h, int patsize)
+{
+    Prm prm = {2, 4, 0.7f, 0.03f, 1.6f, 1, 1.5f, 0.001f, 1, patsize, 0};
+    int owhps[24], osizes[8], offsets[9], sig[8], idx1[488], idx2[488];
+    float sizes[8], borders[8], wtab[36];
+    int noct = okz_layout(w, h, (w + 127) / 128 * 128, prm.noctaves, prm.max_scale, owhps, osizes, offsets);
+    okz_schedule(&prm, noct, sizes, sig, borders);
+    okz_orient_weights(wtab);
+    okz_compare_indices(idx1, idx2);
+    long sum = 0, npts = 0;
+    rng_state = 977u + (unsigned)patsize;
+    for (int l = 0; l < noct * prm.max_scale; l++) {
+        int o = l / prm.max_scale, ow = owhps[3 * o], oh = owhps[3 * o + 1], op = owhps[3 * o + 2];
+        size_t n = (size_t)oh * op;
+        float *lt = malloc(n * sizeof(float)), *lx = malloc(n * sizeof(float)), *ly = malloc(n * sizeof(float)), *det = malloc(n * sizeof(float));
+        int *ilt = malloc(n * sizeof(int)), *ilx = malloc(n * sizeof(int)), *ily = malloc(n * sizeof(int)), *idet = malloc(n * sizeof(int));
+        for (size_t i = 0; i < n; i++) {
+            lt[i] = (float)(rnd() % 65536u) * (1.f / 65536.f);
+            ilt[i] = (int)(rnd() ^ (rnd() << 7));
+        }
+        okz_derivate(lt, lx, ly, sig[l], ow, oh, op);
+        okz_hessian(lx, ly, det, sig[l], ow, oh, op);
+        fkz_hessian(ilt, ilx, ily, idet, sig[l], ow, oh, op);
+        int lim[2][2];                                                  /* [axis][first, last] accepted coordinate */
+        for (int ax = 0; ax < 2; ax++) {
+            int ext = ax ? oh : ow, first = -1, last = -1;
+            for (int i = (int)borders[o * prm.max_scale]; i < ext; i++)
+                if ((int)(i - borders[l] + 0.5f) - 1 >= 0 && (int)(i + borders[l] + 0.5f) + 1 < ext) { if (first < 0) first = i; last = i; }
+            if (first < 0) { fprintf(stderr, "run_points: level %d has no accepted domain\n", l); exit(1); }
+            lim[ax][0] = first; lim[ax][1] = last;
+        }
+        int xs[3] = {lim[0][0], (lim[0][0] + lim[0][1]) / 2, lim[0][1]}, ys[3] = {lim[1][0], (lim[1][0] + lim[1][1]) / 2, lim[1][1]};
+        for (int yi = 0; yi < 3; yi++)
+            for (int xi = 0; xi < 3; xi++) {
+                if (xi == 1 && yi == 1) continue;
+                for (int k = 0; k < 4; k++) {
+                    Pt pt, fpt;
+                    memset(&pt, 0, sizeof(pt));
+                    pt.x = (float)(xs[xi] << o); pt.y = (float)(ys[yi] << o); pt.octave = l; pt.size = sizes[l];
+                    fpt = pt;
+                    fpt.x += (float)(k & o); fpt.y += (float)((k >> 1) & o);                  /* both parities at octave 1 */
+                    okz_refine_point(&pt, det, o, op);
+                    if (k == 1) { pt.x = (float)((xs[xi] - 1) << o); pt.y = (float)((ys[yi] - 1) << o); }      /* the refinement's range */
+                    if (k == 2) { pt.x = (float)((xs[xi] + 1) << o); pt.y = (float)((ys[yi] + 1) << o); }
+                    okz_orient_point(&pt, lx, ly, o, ow, oh, op, wtab);
+                    pt.angle = (float)((2 * k + 1) * 0.78539816339744831);
+                    okz_describe_point(&pt, lt, lx, ly, o, ow, oh, op, patsize, idx1, idx2);
+                    fkz_refine(&fpt, idet, o, op);
+                    fkz_orient(&fpt, ilx, ily, o, ow, oh, op, wtab);
+                    fpt.angle = pt.angle;
+                    fkz_describe(&fpt, ilt, ilx, ily, o, ow, oh, op, patsize, idx1, idx2);
+                    sum += pt.features[k] + fpt.features[60 - k];
+                    npts++;
+                }
+            }
+        free(lt); free(lx); free(ly); free(det); free(ilt); free(ilx); free(ily); free(idet);
+    }
+    printf("  point functions on %ld planted limit / corner keypoints of a %d x %d pyramid, pattern %d\n", 2 * npts, w, h, patsize);
+    return sum;
+}
+
 int main(void)
 {
     if (okz_sizeof_point() != (int)sizeof(Pt) || sizeof(Pt) != 104) { fprintf(stderr, "record layout drifted\n"); return 1; }
     long stage_sum = run_stages(83, 81, 0) + run_stages(83, 81, 1) + run_stages(132, 70, 0) + run_stages(132, 70, 1);
+    stage_sum += run_points(265, 245, 10) + run_points(265, 245, 12) + run_points(265, 245, 6);
     (void)stage_sum;
     Prm d = {4, 4, 0.7f, 0.03f, 1.6f, 1, 1.5f, 0.001f, 1, 10, 0};     /* main.cpp:156-166 */
     int total = 0;

@@ -262,6 +262,31 @@ def describe_point(pt, lt, lx, ly, o, w, patsize=10, fast=False):
     return rec[0]
 
 
+class Census(C.Structure):
+    """OkzCensus (akaze_oracle.c): which narrow places of the point functions the calls since census_begin() went through"""
+    _fields_ = [("clamp", C.c_int * 4), ("min_edge", C.c_float), ("bin_hi", C.c_int), ("bin_lo", C.c_int), ("bin0", C.c_int),
+                ("bin41", C.c_int), ("maxk", C.c_int), ("refined", C.c_int), ("saturated", C.c_int), ("tie", C.c_int)]
+
+
+def census_begin():
+    """start counting on the calling thread; returns the live structure (census_end() stops)"""
+    c = Census()
+    lib().okz_census_begin(C.byref(c))
+    return c
+
+
+def census_end():
+    lib().okz_census_begin(None)
+
+
+def schedule(params, noct):
+    """okz_schedule: (sizes, sigma_size, borders, psz) of the noct * max_scale levels as the pipeline oracles form them"""
+    n = noct * params.max_scale
+    sizes, sig, borders = np.zeros(n, np.float32), np.zeros(n, np.int32), np.zeros(n, np.float32)
+    psz = lib().okz_schedule(C.byref(params), C.c_int(noct), _f(sizes), sig.ctypes.data_as(_ip), _f(borders))
+    return sizes, sig, borders, int(psz)
+
+
 def match(pts1, pts2):
     """in-place on pts1 (structured arrays)"""
     lib().okz_match(pts1.ctypes.data_as(C.c_void_p), len(pts1), pts2.ctypes.data_as(C.c_void_p), len(pts2))
