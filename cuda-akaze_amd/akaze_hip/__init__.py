@@ -165,6 +165,10 @@ TEST_SYMBOLS = {
     "hak_op_tail_level": (C.c_int, [_vp, C.c_int, C.c_int, _vp]),
     "hak_op_tail_det_level": (C.c_int, [_vp, C.c_int, C.c_int, _vp]),
     "hak_op_tail_seed": (C.c_int, [_vp, _vp, _vp]),
+    "hak_debug_tail_total": (C.c_int, [_vp, _ip]),
+    "hak_op_fast_tail_level": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_int]),
+    "hak_op_fast_tail_det_level": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_int]),
+    "hak_debug_tail_maps": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(C.c_long), _ip]),
     "hak_op_tail_finish": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _ip]),
     "hak_op_orient_describe": (C.c_int, [_vp, _vp, C.c_int, C.c_int]),
     "hak_op_fast_orient_describe": (C.c_int, [_vp, _vp, C.c_int, C.c_int]),
@@ -444,6 +448,25 @@ class Akazer:
         det = np.ascontiguousarray(det, np.float32)
         check(lib.hak_op_tail_det_level(self.ctx, octave, sublevel, det.ctypes.data))
 
+    def fast_tail_level(self, octave, sublevel, lplane, threshold=65):
+        lplane = np.ascontiguousarray(lplane, np.int32)
+        check(lib.hak_op_fast_tail_level(self.ctx, octave, sublevel, lplane.ctypes.data, int(threshold)))
+
+    def fast_tail_det_level(self, octave, sublevel, det, threshold=65):
+        det = np.ascontiguousarray(det, np.int32)
+        check(lib.hak_op_fast_tail_det_level(self.ctx, octave, sublevel, det.ctypes.data, int(threshold)))
+
+    def tail_maps(self):
+        """hak_debug_tail_maps, between tail_begin and tail_finish: (response words (h, w) uint32, layers (h, w) int32 with -1 for an
+        empty pixel, candidate words in arrival order, the list's capacity, the candidate count)"""
+        w, h, _ = self.geometry()[0]
+        resp, layer = np.zeros((h, w), np.uint32), np.zeros((h, w), np.int32)
+        cap, n = C.c_long(0), C.c_int(0)
+        check(lib.hak_debug_tail_maps(self.ctx, resp.ctypes.data, layer.ctypes.data, None, C.byref(cap), C.byref(n)))
+        cand = np.zeros(cap.value, np.uint64)
+        check(lib.hak_debug_tail_maps(self.ctx, None, None, cand.ctypes.data, None, None))
+        return resp, layer, cand[:max(min(n.value, cap.value), 0)], cap.value, n.value
+
     def tail_seed(self, response, layer):
         """response: (h, w) float32 (or int32 for the FAST path's map), layer: (h, w) int32, < 0 = no candidate"""
         response = np.ascontiguousarray(response)
@@ -464,6 +487,12 @@ class Akazer:
             return data.h_data[:k].copy(), n.value
         finally:
             freeAkazeData(data)
+
+    def tail_total(self):
+        """hak_debug_tail_total: the survivors of the last tail_finish before the clamp to max_pts"""
+        n = C.c_int(0)
+        check(lib.hak_debug_tail_total(self.ctx, C.byref(n)))
+        return n.value
 
     def orient_describe(self, points, desc=1, fast=False):
         """orientation + MLDB (desc=1) or MLDB with the records' own angles (desc=2) on host records; returns them updated.

@@ -134,6 +134,8 @@ static int build_plan(hak_ctx* c, int w, int h)
     if (w < 80 || h < 80) return fail("image smaller than 80 px");
     // candidate entries carry 16 bits per full-resolution coordinate (hak_cand_word, hak_internal.h)
     if (w > 65535 || h > 65535) return fail("image larger than 65535 px in one dimension");
+    // the key map orders responses by their bits: the order of positive floats only (hak_ext_key, hak_internal.h; hipakaze.h)
+    if (!(cfg.dthreshold >= 0.f)) return fail("dthreshold must be >= 0 (and not a NaN): the key map orders positive responses only");
     HakLayout& L = c->L;
     memset(&L, 0, sizeof(L));
     L.ms = cfg.max_scale;

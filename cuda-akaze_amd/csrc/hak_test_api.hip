@@ -535,6 +535,87 @@ extern "C" int hak_op_tail_det_level(hak_ctx* c, int o, int s, const float* h_de
     return 0;
 }
 
+// the `int` twins of the two operators above, for the FAST path's planes (fastakaze::gCalcExtremaMap akazed.cu:3476): the same two
+// launchers through their `int` overloads, with the threshold as an argument (the launch sequence passes 65, dthreshold_of<int>)
+// (a negative threshold would let negative responses into the key map, whose unsigned word order holds for positive ones only:
+// refused, as hak_create refuses a negative dthreshold)
+static int fast_threshold_ok(int threshold) { return threshold < 0 ? fail("the integer threshold must be >= 0: the key map orders positive responses only") : 0; }
+
+extern "C" int hak_op_fast_tail_level(hak_ctx* c, int o, int s, const int* h_src, int threshold)
+{
+    if (tail_level_ok(c, o, s, h_src)) return 1;
+    if (fast_threshold_ok(threshold)) return 1;
+    const HakLayout& L = c->L;
+    const HakOct oc = L.oct[o];
+    int* A = reinterpret_cast<int*>(c->arena);
+    int* smooth = A + L.smooth_off[o];
+    HIP_TRY(hipMemcpy2D(smooth, sizeof(int) * oc.p, h_src, sizeof(int) * oc.w, sizeof(int) * oc.w, oc.h, hipMemcpyHostToDevice));
+    HakBatch b = tail_batch(c);
+    const int step = c->plan[(size_t)o * L.ms + s].sigma_size;
+    if (!hak_launch_hessian_level(c->stream, smooth, A + L.dxy(o, s), A + L.flow_off[o], false, L.arena, oc.w, oc.h, oc.p, 1, step, &b, &L,
+                                  &c->htab, o, s, threshold))
+        hak_launch_extrema_level(c->stream, b, L, &c->htab, o, s, threshold, L.flow_off[o]);
+    if (hipGetLastError() != hipSuccess) return fail("FAST tail level launch failed");
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+extern "C" int hak_op_fast_tail_det_level(hak_ctx* c, int o, int s, const int* h_det, int threshold)
+{
+    if (tail_level_ok(c, o, s, h_det)) return 1;
+    if (fast_threshold_ok(threshold)) return 1;
+    const HakLayout& L = c->L;
+    const HakOct oc = L.oct[o];
+    HIP_TRY(hipMemcpy2D(reinterpret_cast<int*>(c->arena) + L.flow_off[o], sizeof(int) * oc.p, h_det, sizeof(int) * oc.w, sizeof(int) * oc.w, oc.h,
+                        hipMemcpyHostToDevice));
+    hak_launch_extrema_level(c->stream, tail_batch(c), L, &c->htab, o, s, threshold, L.flow_off[o]);
+    if (hipGetLastError() != hipSuccess) return fail("FAST extrema launch failed");
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// The extrema stage by itself, between hak_op_tail_begin and hak_op_tail_finish: image 0's key map as dense w x h response words
+// and layers (an empty pixel: word 0, layer -1), the first min(ncand, cand_cap) words of its candidate list in the kernels'
+// arrival order (layer << 32 | y << 16 | x), the list's capacity and the number of candidates the kernels counted.  Every output
+// pointer may be NULL; h_cand holds cand_cap words (ask for the capacity first, with h_cand == NULL).
+extern "C" int hak_debug_tail_maps(hak_ctx* c, unsigned int* h_resp_bits, int* h_layer, unsigned long long* h_cand, long* cand_cap_out,
+                                   int* ncand_out)
+{
+    if (!c) return fail("null context");
+    const HakOct oc = c->L.oct[0];
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HakImgState hs;
+    HIP_TRY(hipMemcpy(&hs, c->state, sizeof(hs), hipMemcpyDeviceToHost));
+    if (ncand_out) *ncand_out = hs.ncand;
+    if (cand_cap_out) *cand_cap_out = c->cand_cap;
+    if (h_resp_bits || h_layer) {
+        std::vector<unsigned long long> keys((size_t)oc.w * oc.h);
+        HIP_TRY(hipMemcpy2D(keys.data(), sizeof(unsigned long long) * oc.w, c->maps, sizeof(unsigned long long) * oc.p,
+                            sizeof(unsigned long long) * oc.w, oc.h, hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < keys.size(); i++) {                                // hak_ext_key (hak_internal.h)
+            if (h_resp_bits) h_resp_bits[i] = (unsigned)(keys[i] >> 32);
+            if (h_layer) h_layer[i] = keys[i] ? (int)(0xFFFFFFFFu - (unsigned)keys[i]) : -1;
+        }
+    }
+    if (h_cand) {
+        long n = hs.ncand < 0 ? 0 : hs.ncand;
+        n = n < c->cand_cap ? n : c->cand_cap;
+        if (n > 0) HIP_TRY(hipMemcpy(h_cand, c->cand, sizeof(unsigned long long) * (size_t)n, hipMemcpyDeviceToHost));
+    }
+    return 0;
+}
+
+// survivors of image 0's last NMS before the clamp to max_pts (k_row_scan: total_pts); after hak_op_tail_finish
+extern "C" int hak_debug_tail_total(hak_ctx* c, int* total)
+{
+    if (!c || !total) return fail("null argument");
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HakImgState hs;
+    HIP_TRY(hipMemcpy(&hs, c->state, sizeof(hs), hipMemcpyDeviceToHost));
+    *total = hs.total_pts;
+    return 0;
+}
+
 extern "C" int hak_op_tail_seed(hak_ctx* c, const unsigned int* h_resp_bits, const int* h_layer)
 {
     if (!c || !h_resp_bits || !h_layer) return fail("null argument");

@@ -94,8 +94,17 @@ int hak_op_fast_hessian(const int* d_src, int* d_lx, int* d_ly, int* d_det, int 
  *                         fused kernel the context would pick (knobs as in hak_create), threshold = cfg.dthreshold
  *   hak_op_tail_det_level gCalcExtremaMap 1334 alone (the stand-alone kernel of the dilation > 4 fallback) on a dense host
  *                         determinant plane
+ *   hak_op_fast_tail_level / hak_op_fast_tail_det_level  the `int` twins of the two above (fastakaze::gCalcExtremaMap 3476) on dense
+ *                         int32 planes, through the `int` overloads of the same launchers; `threshold` is the integer response
+ *                         threshold (the FAST launch sequence uses 65); >= 0, a negative one is refused (hak_create, hipakaze.h, has the reason)
+ *   hak_debug_tail_maps   between begin and finish: image 0's key map as dense w x h response words and layers (empty pixel: word 0,
+ *                         layer -1), the first min(ncand, capacity) words of its candidate list in arrival order
+ *                         (layer << 32 | y << 16 | x, full resolution), the list's capacity and the candidate count.  Any output
+ *                         pointer may be NULL; h_cand holds `capacity` words (ask with h_cand == NULL first).
+ *                         The extrema stage by itself: after the NMS a missed or extra candidate is mostly masked
  *   hak_op_tail_seed      hand-made full-resolution maps: response words (float or int bits) and layer ids (< 0: empty)
  *   hak_op_tail_finish    gNmsRNaive 1554 (+ gRefine 1615 when `refine`) -> d_points in raster order; *num_pts = survivors
+ *   hak_debug_tail_total  after finish: the survivors of the NMS before the clamp to max_pts (*num_pts above is the clamped count)
  *   hak_op_orient_describe gCalcOrient 1665 + gDescribe2 1869 on the first n records of d_points, reading the planes the
  *                         arena holds now (desc: 0 none, 1 both, 2 descriptor only with the records' own angles)
  *   hak_op_fast_orient_describe  the same on the integer FAST path: gRefine 3600 + gCalcOrient 3649 + gDescribe2 3723 through
@@ -106,8 +115,13 @@ int hak_debug_set_plane(hak_ctx* ctx, int img, int kind, int octave, int subleve
 int hak_op_tail_begin(hak_ctx* ctx);
 int hak_op_tail_level(hak_ctx* ctx, int octave, int sublevel, const float* h_src);
 int hak_op_tail_det_level(hak_ctx* ctx, int octave, int sublevel, const float* h_det);
+int hak_op_fast_tail_level(hak_ctx* ctx, int octave, int sublevel, const int* h_src, int threshold);
+int hak_op_fast_tail_det_level(hak_ctx* ctx, int octave, int sublevel, const int* h_det, int threshold);
+int hak_debug_tail_maps(hak_ctx* ctx, unsigned int* h_response_bits, int* h_layer, unsigned long long* h_cand, long* cand_cap_out,
+                        int* ncand_out);
 int hak_op_tail_seed(hak_ctx* ctx, const unsigned int* h_response_bits, const int* h_layer);
 int hak_op_tail_finish(hak_ctx* ctx, hak_point* d_points, int max_pts, int refine, int fast, int* num_pts);
+int hak_debug_tail_total(hak_ctx* ctx, int* total);
 int hak_op_orient_describe(hak_ctx* ctx, hak_point* d_points, int n, int desc);
 int hak_op_fast_orient_describe(hak_ctx* ctx, hak_point* d_points, int n, int desc);
 
