@@ -160,6 +160,8 @@ TEST_SYMBOLS = {
     "hak_op_fast_level_tile": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_long, C.c_int, C.c_int, C.c_int,
                                          C.c_int, C.c_int, _ip, _fp, C.c_int, _ip]),
     "hak_op_fast_hessian": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _ip]),
+    "hak_op_hessian_batch": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _ip]),
+    "hak_op_fast_hessian_batch": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _ip]),
     "hak_debug_set_plane": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
     "hak_op_tail_begin": (C.c_int, [_vp]),
     "hak_op_tail_level": (C.c_int, [_vp, C.c_int, C.c_int, _vp]),

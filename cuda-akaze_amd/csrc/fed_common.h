@@ -47,6 +47,28 @@ __device__ __forceinline__ int wave_shl1(int v)
     asm volatile("" : "+v"(r));
     return r;
 }
+// The same shifts with the end lane (no source) keeping `keep` instead of reading 0 (bound_ctrl off): a strip's end lane takes a
+// value from outside the strip (kernels_hessian_stream.hip).  The integer form stays opaque like the one above.
+__device__ __forceinline__ float wave_shr1_keep(float keep, float v)
+{
+    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(keep), __float_as_int(v), 0x138, 0xf, 0xf, false));
+}
+__device__ __forceinline__ float wave_shl1_keep(float keep, float v)
+{
+    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(keep), __float_as_int(v), 0x130, 0xf, 0xf, false));
+}
+__device__ __forceinline__ int wave_shr1_keep(int keep, int v)
+{
+    int r = __builtin_amdgcn_update_dpp(keep, v, 0x138, 0xf, 0xf, false);
+    asm volatile("" : "+v"(r));
+    return r;
+}
+__device__ __forceinline__ int wave_shl1_keep(int keep, int v)
+{
+    int r = __builtin_amdgcn_update_dpp(keep, v, 0x130, 0xf, 0xf, false);
+    asm volatile("" : "+v"(r));
+    return r;
+}
 
 // 16-byte store with the `nt` bit: planes that are written once and next read sparsely or much later should not displace
 // the streams other kernels are reading from L2 / Infinity Cache (measured: Hessian -3 %, +3 % end to end)

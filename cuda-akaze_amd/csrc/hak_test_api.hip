@@ -457,6 +457,41 @@ extern "C" int hak_op_fast_hessian(const int* s, int* lx, int* ly, int* det, int
     return rc;
 }
 
+// Hessian of one level on a batch, either element type (tests/test_gpu_strip_seams.py).  Per image the arena slot holds the interleaved
+// derivatives, the determinant and then the source plane: the last image's last source row ends the allocation, as an image's last
+// row ends the caller's buffer when its pitch is its width.
+template <typename V>
+static int hessian_batch_t(const char* who, const V* s, V* lx, V* ly, V* det, int w, int h, int p, int nimg, int step, int* route)
+{
+    if (nimg < 1 || step < 1 || p % 4 || p < w) return fail(std::string(who) + ": nimg < 1, step < 1 or a bad pitch");
+    const size_t plane = (size_t)h * p;
+    const long stride = 4 * (long)plane;
+    V* buf = nullptr;
+    HIP_TRY(hipMalloc((void**)&buf, sizeof(V) * (size_t)stride * nimg));
+    int rc = 0;
+    if (hipMemcpy2D(buf + 3 * plane, sizeof(V) * stride, s, sizeof(V) * plane, sizeof(V) * plane, nimg, hipMemcpyDeviceToDevice) != hipSuccess)
+        rc = fail(std::string(who) + ": copy in");
+    const HakKnobs kn = hak_knobs_from_env();
+    const V thr = 0;
+    if (!rc && !hak_launch_hessian_level(nullptr, buf + 3 * plane, buf, buf + 2 * plane, true, stride, w, h, p, nimg, step, nullptr, nullptr,
+                                         nullptr, 0, 0, thr))
+        rc = fail(std::string(who) + ": the fused kernels do not cover this dilation");
+    for (int i = 0; i < nimg && !rc; i++)
+        hak_launch_deinterleave(nullptr, reinterpret_cast<const float*>(buf + i * stride), reinterpret_cast<float*>(lx + i * plane),
+                                reinterpret_cast<float*>(ly + i * plane), w, h, p);
+    if (route) *route = (hak_stream_pays(kn.hess_stream, w, h, nimg) && hak_hessian_stream_covers(w, h, step, false)) ? 1 : 2;
+    const hipError_t e = hipDeviceSynchronize();
+    if (!rc && e != hipSuccess) rc = fail(std::string(who) + ": " + hipGetErrorString(e));
+    if (!rc && hipMemcpy2D(det, sizeof(V) * plane, buf + 2 * plane, sizeof(V) * stride, sizeof(V) * plane, nimg, hipMemcpyDeviceToDevice) != hipSuccess)
+        rc = fail(std::string(who) + ": copy out");
+    (void)hipFree(buf);
+    return rc;
+}
+extern "C" int hak_op_hessian_batch(const float* s, float* lx, float* ly, float* det, int w, int h, int p, int nimg, int step, int* route)
+{ return hessian_batch_t<float>("hak_op_hessian_batch", s, lx, ly, det, w, h, p, nimg, step, route); }
+extern "C" int hak_op_fast_hessian_batch(const int* s, int* lx, int* ly, int* det, int w, int h, int p, int nimg, int step, int* route)
+{ return hessian_batch_t<int>("hak_op_fast_hessian_batch", s, lx, ly, det, w, h, p, nimg, step, route); }
+
 // ---- detector tail / descriptors on hand-made inputs (include/hipakaze.h; tests/test_gpu_literal.py)
 static HakBatch tail_batch(hak_ctx* c)
 {

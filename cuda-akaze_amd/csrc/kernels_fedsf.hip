@@ -15,7 +15,7 @@
 // so the pass reads 4 B/px and writes 8 (or 12) B/px instead of 24.  Rings (static slots, loop unrolled by 6):
 // L 6 rows, rp 6 rows, smooth 3 rows (+ its two x-neighbour columns), the g-sum rings and per-level windows of
 // the FED kernel.  No LDS, no barriers.  NS = 5..8 (float only) run on 2-px lanes like k_fed_multi's deep groups (kernels_fed.hip):
-// 135-145 VGPRs, three waves per SIMD, x halo 2 + 1 + NS rounded up to 8 or 12 of a 128-px strip; the unrolled body then covers 18 rows.
+// 135-145 VGPRs, three waves per SIMD, x halo 2 + 1 + NS rounded up to 8 or 12 (10 where that saves a strip: fs_hx_for) of a 128-px strip; the unrolled body then covers 18 rows.
 //
 // Bit-exactness: every stage evaluates the reference expression in the reference order (Gaussian: c*k0, then
 // += k1*(l1+r1), then += k2*(l2+r2), akazed.cu:227-239 / 283-288; Scharr / conductivity akazed.cu:1088-1106).
@@ -280,16 +280,25 @@ __device__ __forceinline__ void fs_strip(const V* __restrict__ L, V* __restrict_
 
 // x halo: 2 (Gaussian) + 1 (Scharr) + NS (FED), a multiple of 4, at least 8; stored strip width
 constexpr int fs_hx(int ns) { return ns + 3 <= 8 ? 8 : (ns + 3 + 3) & ~3; }
-constexpr int fs_xv(int ns) { return 64 * fed_lane_px(ns) - 2 * fs_hx(ns); }
+// The halo is a launch argument, not a constant of the kernel: on 2-px lanes a lane's loads and stores are 8 bytes, so a halo that is
+// a multiple of 2 is aligned as well (the DEC head's 16-byte loads start at twice an even column) -- 10 instead of 12 for NS = 6, 7,
+// 108 stored columns instead of 104.  Strips of 108 columns start on 16-byte, not 32-byte, boundaries of the planes they store,
+// which costs where it saves no strip (measured on 512 planes of 480 x 270, k_fed_sf<6> / <7>: 312 -> 330 us, 335 -> 348 us), so
+// the launch takes the narrow halo only at widths where it needs fewer strips: 960 columns (octave 1 of 1080p), 9 strips
+// instead of 10 (1041 -> 966 us, 1148 -> 1060 us; profiles/strip_seams.txt).
+constexpr int fs_hx_min(int ns) { return ns + 3 <= 8 ? 8 : (ns + 3 + fed_lane_px(ns) - 1) & ~(fed_lane_px(ns) - 1); }
+static int fs_strips(int ns, int hx, int w) { const int xv = 64 * fed_lane_px(ns) - 2 * hx; return (w + xv - 1) / xv; }
+static int fs_hx_for(int ns, int w) { return fs_strips(ns, fs_hx_min(ns), w) < fs_strips(ns, fs_hx(ns), w) ? fs_hx_min(ns) : fs_hx(ns); }
 
 // grid: hak_xcd_grid(strips, strip-row groups, images); a block's four waves take four consecutive row segments
 template <typename V, int NS, bool WRITE_G, bool DEC, bool WRITE_SM>
 __global__ __launch_bounds__(256) void k_fed_sf(const V* __restrict__ src, V* __restrict__ smooth, V* __restrict__ flow,
                                                 V* __restrict__ dst, long stride, int w, int h, int p,
                                                 FedFacs<V, NS> fac, SfTaps<V> kk, const HakImgState* __restrict__ state, int octave,
-                                                float fixed_ikc, int ry, int nbx, int nby, int nimg, int lp, int sh)
+                                                float fixed_ikc, int ry, int nbx, int nby, int nimg, int lp, int sh, int HX)
 {
-    constexpr int W = fed_lane_px(NS), HX = fs_hx(NS), XV = fs_xv(NS);
+    constexpr int W = fed_lane_px(NS);
+    const int XV = 64 * W - 2 * HX;                         // HX: fs_hx_for
     int bx, by, img;
     if (!hak_xcd_decode(nbx, nby, nimg, bx, by, img)) return;
     const V* L = src + (long)img * stride;
@@ -319,23 +328,23 @@ void launch_fs(hipStream_t st, const V* src, V* smooth, V* flow, V* dst, long st
         if constexpr (std::is_same<V, float>::value) fac.f[k] = 0.5f * tau[k];      // akazed.cu:2515
         else fac.f[k] = (int)(0.5f * tau[k] * 65536 + 0.5f);                        // akazed.cu:4235
     }
-    constexpr int XV = fs_xv(NS);
-    const int gx = (w + XV - 1) / XV;
+    const int hx = fs_hx_for(NS, w);
+    const int gx = fs_strips(NS, hx, w);
     // rows per wave: tall segments amortise the NS+4 warm-up rows; shrink while the grid cannot fill the chip
     const int ry = hak_stream_rows(h, (long)gx * nimg, 8);
     const int gy = (h + 4 * ry - 1) / (4 * ry);
     const unsigned grid = hak_xcd_grid(gx, gy, nimg);
     if (!smooth) {                                          // (sublevels only; float only: launch_fs_any)
         if constexpr (std::is_same<V, float>::value) {
-            if (write_g) k_fed_sf<V, NS, true, false, false><<<grid, 256, 0, st>>>(src, smooth, flow, dst, stride, w, h, p, fac, kk, state, octave, fixed_ikc, ry, gx, gy, nimg, p, h);
-            else k_fed_sf<V, NS, false, false, false><<<grid, 256, 0, st>>>(src, smooth, flow, dst, stride, w, h, p, fac, kk, state, octave, fixed_ikc, ry, gx, gy, nimg, p, h);
+            if (write_g) k_fed_sf<V, NS, true, false, false><<<grid, 256, 0, st>>>(src, smooth, flow, dst, stride, w, h, p, fac, kk, state, octave, fixed_ikc, ry, gx, gy, nimg, p, h, hx);
+            else k_fed_sf<V, NS, false, false, false><<<grid, 256, 0, st>>>(src, smooth, flow, dst, stride, w, h, p, fac, kk, state, octave, fixed_ikc, ry, gx, gy, nimg, p, h, hx);
         }
     } else if (sp > 0) {
-        if (write_g) k_fed_sf<V, NS, true, true, true><<<grid, 256, 0, st>>>(src, smooth, flow, dst, stride, w, h, p, fac, kk, state, octave, fixed_ikc, ry, gx, gy, nimg, sp, sh);
-        else k_fed_sf<V, NS, false, true, true><<<grid, 256, 0, st>>>(src, smooth, flow, dst, stride, w, h, p, fac, kk, state, octave, fixed_ikc, ry, gx, gy, nimg, sp, sh);
+        if (write_g) k_fed_sf<V, NS, true, true, true><<<grid, 256, 0, st>>>(src, smooth, flow, dst, stride, w, h, p, fac, kk, state, octave, fixed_ikc, ry, gx, gy, nimg, sp, sh, hx);
+        else k_fed_sf<V, NS, false, true, true><<<grid, 256, 0, st>>>(src, smooth, flow, dst, stride, w, h, p, fac, kk, state, octave, fixed_ikc, ry, gx, gy, nimg, sp, sh, hx);
     } else {
-        if (write_g) k_fed_sf<V, NS, true, false, true><<<grid, 256, 0, st>>>(src, smooth, flow, dst, stride, w, h, p, fac, kk, state, octave, fixed_ikc, ry, gx, gy, nimg, p, h);
-        else k_fed_sf<V, NS, false, false, true><<<grid, 256, 0, st>>>(src, smooth, flow, dst, stride, w, h, p, fac, kk, state, octave, fixed_ikc, ry, gx, gy, nimg, p, h);
+        if (write_g) k_fed_sf<V, NS, true, false, true><<<grid, 256, 0, st>>>(src, smooth, flow, dst, stride, w, h, p, fac, kk, state, octave, fixed_ikc, ry, gx, gy, nimg, p, h, hx);
+        else k_fed_sf<V, NS, false, false, true><<<grid, 256, 0, st>>>(src, smooth, flow, dst, stride, w, h, p, fac, kk, state, octave, fixed_ikc, ry, gx, gy, nimg, p, h, hx);
     }
 }
 

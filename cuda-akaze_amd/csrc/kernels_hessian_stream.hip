@@ -19,6 +19,17 @@
 // rotate statically (row loop unrolled by R); the strip's outer M columns and the 2S+1 warm-up rows above / below a
 // segment are recomputed by the neighbouring wave.
 //
+// Strip geometry: M is 2S+1 rounded up to a multiple of 4 -- 4 / 8 / 8 for S = 1..3, so 248 / 240 / 240 stored columns -- except at
+// S = 4, which would need 9 and takes 8: every plane width of the pyramid is a multiple of 240 (1920 / 960 / 480 / 240, the 4K widths
+// likewise), and 240-column strips tile them exactly where the 232 columns of a margin of 12 took a ninth / fifth / third / second
+// strip per octave.  The one column the strip is short of on either side is needed by two taps only: the extremum test at strip
+// column 8 needs det at 7, that needs Lx / Ly at 3, those need the input at column -1 (hs_l<4, 3> in lane 0); mirrored, column 247
+// leads to input column 256 (hs_r<4, 0> in lane 63).  Per input row the two end lanes load exactly those elements -- one 4-byte
+// load into a ring of one register per slot that follows the input ring's y reflections (HsState::E) -- and the two wave
+// shifts keep that value in the end lane instead of reading 0 (hs_le / hs_re).  Lx / Ly are then valid on strip columns 3 .. 252, det on
+// 7 .. 248, extrema on 8 .. 247: the stored range.  Cost: 8 vector instructions per row (321 -> 329) and 11 VGPRs (float 234 -> 250,
+// int 207 -> 229: two waves per SIMD as before, no scratch).
+//
 // Reflect-101 (akazed.cu:1284-1291, 1318-1325): in x the reference reflects the INDEX it reads the plane at, so the
 // lane that holds image column 0 (w-1) replaces the shifted-in values by its own / its neighbour's components; in y
 // a row arriving at 1..S is also written to the ring slot of row -1..-S and the virtual rows h..h+S-1 are copies of
@@ -43,8 +54,12 @@ template <int S, bool LP> struct HsGeo {
     // 14.26 / 14.30 ms per 512 images).  One row in flight at S = 2 or 4 is slower (+1 %), a third row at any S was (+3 .. +9 %).
     static constexpr int PD = S == 3 ? 1 : 2;
     static constexpr int R = 2 * S + 1 + PD;                        // ring slots = unroll factor: 2S+1 live rows + PD rows being loaded
-    // strip margin: multiple of 4, >= 2S+1 (+2 for the low-pass taps of the LP variant)
-    static constexpr int M = LP ? (S <= 2 ? 8 : 12) : (S == 1 ? 4 : S == 4 ? 12 : 8);
+    // strip margin: multiple of 4, >= 2S+1 (+2 for the low-pass taps of the LP variant).  S = 4 would need 9: it takes 8 and
+    // fetches the ninth input column of either side on its own (EX below), so that its strips tile the pyramid's plane widths --
+    // every one a multiple of 240 -- exactly: 8 / 4 / 2 / 1 strips per octave of 1080p where a margin of 12 took 9 / 5 / 3 / 2
+    static constexpr int M = LP ? (S <= 2 ? 8 : 12) : (S == 1 ? 4 : 8);
+    // one input column outside the strip on either side, in a ring of its own (HsState::E)
+    static constexpr bool EX = !LP && S == 4;
     static constexpr int XV = 256 - 2 * M;                          // columns a wave stores
     // waves per SIMD the register allocator must make room for (LP: the row-pass ring adds ~24 VGPRs)
     static constexpr int MINW = LP ? (S <= 1 ? 3 : 2) : (S <= 3 ? 3 : 2);
@@ -61,6 +76,9 @@ template <typename V, int S, bool LP> struct HsState {
     using V4 = typename FedV<V>::V4;
     static constexpr int R = HsGeo<S, LP>::R;
     V4 A[R], X[R];                                                  // slot = iteration index mod R
+    // EX only: the input column just outside the strip, of the rows in A -- lane 0 holds strip column -1, lane 63 column 256 (the
+    // other lanes' values are never read)
+    V E[HsGeo<S, LP>::EX ? R : 1];
     // LP only (static slots: the allocator keeps just the live ones): raw rows in flight, row t+2 in slot (U+2) mod R; row-pass
     // rows t-2 .. t+2
     V4 W[LP ? R : 1], Rp[LP ? R : 1];
@@ -92,6 +110,21 @@ __device__ __forceinline__ auto hs_r(const V4& r)
 {
     if constexpr (K + S <= 3) return hs_c<K + S>(r);
     else return wave_shl1(hs_c<K + S - 4>(r));
+}
+// The same two taps of the input ring where the strip's margin is one column short (HsGeo::EX): the left lane's column 3 is the
+// tap of column x0 - 1 and lane 0 has no left lane, so there the shift keeps `e`, lane 0's element of the extra ring (strip column
+// -1); mirrored, lane 63 keeps strip column 256.  Every other lane gets what hs_l / hs_r deliver.
+template <int S, int K, bool EX, typename V4, typename V>
+__device__ __forceinline__ auto hs_le(const V4& r, const V e)
+{
+    if constexpr (EX && K - S == -1) return wave_shr1_keep(e, r.w);
+    else return hs_l<S, K>(r);
+}
+template <int S, int K, bool EX, typename V4, typename V>
+__device__ __forceinline__ auto hs_re(const V4& r, const V e)
+{
+    if constexpr (EX && K + S == 4) return wave_shl1_keep(e, r.x);
+    else return hs_r<S, K>(r);
 }
 // Reflect-101 in x, once per ring row instead of once per tap (round 4).  The reference reflects the INDEX it reads a plane at
 // (akazed.cu:1284-1291, 1318-1325): column -k reads column k, column w-1+k reads column w-1-k -- in EVERY plane (smooth, Lx, Ly)
@@ -184,14 +217,15 @@ __device__ __forceinline__ void hs_emit(const bool hit, const V v, const int x, 
 }
 
 template <typename V, int S, int U, int XE, bool YEDGE, bool LP>
-__device__ __forceinline__ void hs_iter(HsState<V, S, LP>& T, const int t, const HsArgs<V>& a, const int xl, const int x0,
-                                        const int ybeg, const int yend, const bool owns, const unsigned xok, const int lane,
+__device__ __forceinline__ void hs_iter(HsState<V, S, LP>& T, const int t, const HsArgs<V>& a, const int xl, const int xe,
+                                        const int x0, const int ybeg, const int yend, const bool owns, const unsigned xok, const int lane,
                                         const __amdgpu_buffer_rsrc_t orsrc, const unsigned (&ovoff)[3], const int er0, const int er1,
                                         const HsCold* cold)
 {
     using V4 = typename FedV<V>::V4;
     constexpr int R = HsGeo<S, LP>::R;
     constexpr int PD = HsGeo<S, LP>::PD;
+    constexpr bool EX = HsGeo<S, LP>::EX;
     const V fac1 = a.fac1, fac2 = a.fac2;
     const int w = a.w, h = a.h, p = a.p;
     [[maybe_unused]] const bool le = x0 == 0, re = x0 + 3 == w - 1;      // (LP row pass only)
@@ -201,6 +235,7 @@ __device__ __forceinline__ void hs_iter(HsState<V, S, LP>& T, const int t, const
     // rotating a prefetch queue by moves made the compiler wait for vmcnt(0) every iteration.
     if constexpr (!LP) {
         T.A[pmod(U + PD, R)] = hak_load_stream(reinterpret_cast<const V4*>(a.src + (unsigned)(min(t + PD, h - 1) * p + xl)));
+        if constexpr (EX) T.E[pmod(U + PD, R)] = a.src[(unsigned)(min(t + PD, h - 1) * p + xe)];
     } else {
         // ---- LP: raw row r = t + 2 arrived in W[(U+2) mod R]; request row r + PD into the slot it will be consumed from
         const int r = t + 2;
@@ -249,6 +284,11 @@ __device__ __forceinline__ void hs_iter(HsState<V, S, LP>& T, const int t, const
         for (int j = 1; j <= S; j++) {
             if (t == j) T.A[pmod(U - 2 * j, R)] = T.A[pmod(U, R)];                   // row -j := row j
             if (t == h - 1 + j) T.A[pmod(U, R)] = T.A[pmod(U - 2 * j, R)];           // row h-1+j := row h-1-j
+            if constexpr (EX) {                                 // (selects on loaded values: a ?: of two ring slots is a select of
+                const V en = T.E[pmod(U, R)], eo = T.E[pmod(U - 2 * j, R)];      // their addresses and sends the ring to scratch)
+                T.E[pmod(U - 2 * j, R)] = t == j ? en : eo;
+                T.E[pmod(U, R)] = t == h - 1 + j ? eo : en;
+            }
         }
     }
     // ---- Lx, Ly of row b = t - S
@@ -256,12 +296,14 @@ __device__ __forceinline__ void hs_iter(HsState<V, S, LP>& T, const int t, const
     {
         const int b = t - S;
         const V4 ru = T.A[pmod(U - 2 * S, R)], rc = T.A[pmod(U - S, R)], rl = T.A[pmod(U, R)];
+        V eu = 0, ec = 0, el = 0;                               // (EX: the extra column of the same three rows)
+        if constexpr (EX) { eu = T.E[pmod(U - 2 * S, R)]; ec = T.E[pmod(U - S, R)]; el = T.E[pmod(U, R)]; }
         V4 vx, vy;
 #define HS_S1(k, K)                                                                                         \
         {                                                                                                   \
-            const V ul = hs_l<S, K>(ru), ur = hs_r<S, K>(ru);                                               \
-            const V cl = hs_l<S, K>(rc), cr = hs_r<S, K>(rc);                                               \
-            const V ll = hs_l<S, K>(rl), lr = hs_r<S, K>(rl);                                               \
+            const V ul = hs_le<S, K, EX>(ru, eu), ur = hs_re<S, K, EX>(ru, eu);                             \
+            const V cl = hs_le<S, K, EX>(rc, ec), cr = hs_re<S, K, EX>(rc, ec);                             \
+            const V ll = hs_le<S, K, EX>(rl, el), lr = hs_re<S, K, EX>(rl, el);                             \
             vx.k = HS_DX(ul, ur, cl, cr, ll, lr);                                                           \
             vy.k = HS_DY(ul, ru.k, ur, ll, rl.k, lr);                                                       \
         }
@@ -381,11 +423,11 @@ __device__ __forceinline__ void hs_iter(HsState<V, S, LP>& T, const int t, const
 
 template <typename V, int S, int XE, bool YEDGE, bool LP, int... U>
 __device__ __forceinline__ void hs_group(std::integer_sequence<int, U...>, HsState<V, S, LP>& T, const int tb, const HsArgs<V>& a,
-                                         const int xl, const int x0, const int ybeg, const int yend, const bool owns,
+                                         const int xl, const int xe, const int x0, const int ybeg, const int yend, const bool owns,
                                          const unsigned xok, const int lane, const __amdgpu_buffer_rsrc_t orsrc, const unsigned (&ovoff)[3],
                                          const int er0, const int er1, const HsCold* cold)
 {
-    (hs_iter<V, S, U, XE, YEDGE, LP>(T, tb + U, a, xl, x0, ybeg, yend, owns, xok, lane, orsrc, ovoff, er0, er1, cold), ...);
+    (hs_iter<V, S, U, XE, YEDGE, LP>(T, tb + U, a, xl, xe, x0, ybeg, yend, owns, xok, lane, orsrc, ovoff, er0, er1, cold), ...);
 }
 
 template <typename V, int S, int XE, bool LP>
@@ -397,6 +439,17 @@ __device__ __forceinline__ void hs_strip(const HsArgs<V>& a, const int x0, const
     using V4 = typename FedV<V>::V4;
     const int h = a.h, w = a.w;
     const int xl = min(max(x0, 0), a.p - 4);                    // keep every lane's loads inside the plane
+    // EX: the column of the extra ring -- the one left of the strip in the wave's lower half, the one right of it in the upper
+    // half (lanes 0 and 63 are the readers).  Always a column of the image: reflected like every index the reference reads
+    // the plane at (w = the strip's column 256: its tap is column w-2), then clamped -- where the column lies further out,
+    // in the outermost strips, the end lanes hold no image column and nothing reads their derivatives.
+    int xe = 0;
+    if constexpr (G::EX) {
+        const int sx0 = x0 - 4 * lane;
+        xe = lane < 32 ? sx0 - 1 : sx0 + 256;
+        xe = xe >= w ? 2 * (w - 1) - xe : xe;
+        xe = min(max(xe, 0), w - 1);
+    }
     // first input row of the derivative pipeline.  LP: its smooth row needs row-pass rows t0-2 .. t0+2, i.e. four more
     // iterations in front (raw row t+2 enters at iteration t; rows -2, -1 are written when rows 2, 1 arrive: from t = -2)
     const int t0 = LP ? max(max(0, ybeg - 1 - 2 * S) - 4, -2) : max(0, ybeg - 1 - 2 * S);
@@ -444,14 +497,20 @@ __device__ __forceinline__ void hs_strip(const HsArgs<V>& a, const int x0, const
     } else {
 #pragma unroll
         for (int i = 0; i < G::PD; i++) T.A[i] = hak_load_stream(reinterpret_cast<const V4*>(a.src + (unsigned)(min(t0 + i, h - 1) * a.p + xl)));
+        if constexpr (G::EX) {
+#pragma unroll
+            for (int i = 0; i < G::R; i++) T.E[i] = zz;
+#pragma unroll
+            for (int i = 0; i < G::PD; i++) T.E[i] = a.src[(unsigned)(min(t0 + i, h - 1) * a.p + xe)];
+        }
     }
     for (int tb = t0; tb <= tend; tb += G::R) {
         // reflect injections fire while a ring is at rows 1..S (t <= 2S) or at the virtual rows past h-1 (LP: the raw row of
         // iteration t is t+2)
         if (tb <= 2 * S || tb + G::R - 1 >= h - (LP ? 2 : 0))
-            hs_group<V, S, XE, true, LP>(std::make_integer_sequence<int, G::R>{}, T, tb, a, xl, x0, ybeg, yend, owns, xok, lane, orsrc, ovoff, er0, er1, cold);
+            hs_group<V, S, XE, true, LP>(std::make_integer_sequence<int, G::R>{}, T, tb, a, xl, xe, x0, ybeg, yend, owns, xok, lane, orsrc, ovoff, er0, er1, cold);
         else
-            hs_group<V, S, XE, false, LP>(std::make_integer_sequence<int, G::R>{}, T, tb, a, xl, x0, ybeg, yend, owns, xok, lane, orsrc, ovoff, er0, er1, cold);
+            hs_group<V, S, XE, false, LP>(std::make_integer_sequence<int, G::R>{}, T, tb, a, xl, xe, x0, ybeg, yend, owns, xok, lane, orsrc, ovoff, er0, er1, cold);
     }
     if (a.ex.maps != nullptr) hs_flush(T.cb, cold, lane);
 }

@@ -107,7 +107,7 @@ __global__ __launch_bounds__(256) void k_stream_probe(const float* __restrict__ 
 }
 
 // ---- the streaming Hessian's access shape with the arithmetic taken out (k_hessian_stream<float, S, false>, kernels_hessian_stream.hip):
-// strips of 256 - 2 M columns (M = 4 / 8 / 8 / 12 for S = 1..4), row segments cut by hak_stream_rows, 2 S + 1 warm-up rows above and
+// strips of 256 - 2 M columns (M = 4 / 8 / 8 / 8 for S = 1..4; S = 4 also loads its one extra dword per row), row segments cut by hak_stream_rows, 2 S + 1 warm-up rows above and
 // 2 S rows below every segment, one 16-byte load per lane and row with PD rows in flight, and per row the interleaved {Lx, Ly} store
 // exactly as the kernel issues it: the lane's four pixels of both derivatives turned through per-wave LDS (one staging row + a ring
 // row), read back as pixel pairs, two dense 16-byte nt buffer stores per lane.  The block carries the kernel's LDS footprint
@@ -118,7 +118,7 @@ template <int S>
 __global__ __launch_bounds__(256, (S <= 3 ? 3 : 2)) void k_hess_probe(const float* __restrict__ src, float* __restrict__ dxy, long stride, int w, int h,
                                                                      int p, int ry, int nbx, int nby, int nimg)
 {
-    constexpr int PD = S == 3 ? 1 : 2, R = 2 * S + 1 + PD, M = S == 1 ? 4 : S == 4 ? 12 : 8, XV = 256 - 2 * M;
+    constexpr int PD = S == 3 ? 1 : 2, R = 2 * S + 1 + PD, M = S == 1 ? 4 : 8, XV = 256 - 2 * M;
     __shared__ float4 yring[4 * R * 64];
     __shared__ float4 xstage[4 * 64];
     __shared__ unsigned long long cbuf[4 * 256];
@@ -135,6 +135,7 @@ __global__ __launch_bounds__(256, (S <= 3 ? 3 : 2)) void k_hess_probe(const floa
     const int yend = min(ybeg + ry, h);
     const int xl = min(max(x0, 0), p - 4);
     const int sx = x0 - 4 * lane;
+    const int xe = min(max(lane < 32 ? sx - 1 : sx + 256, 0), w - 1);       // S = 4: the column outside the strip (HsGeo::EX)
     auto pair_off = [&](int q) -> unsigned {
         const int x = sx + q;
         return q >= M && q < M + XV && x >= 0 && x < w ? (unsigned)x * 8u : HAK_BUF_OOB;
@@ -156,6 +157,7 @@ __global__ __launch_bounds__(256, (S <= 3 ? 3 : 2)) void k_hess_probe(const floa
             q[(u + PD) % (PD + 1)] = hak_load_stream(reinterpret_cast<const float4*>(L + (unsigned)(min(row + PD, h - 1) * p + xl)));
             const float4 c = q[u];
             acc.x += c.x; acc.y += c.y; acc.z += c.z; acc.w += c.w;
+            if constexpr (S == 4) acc.x += L[(unsigned)(min(row + PD, h - 1) * p + xe)];
             const int b = row - S;                              // the derivative row this iteration stores
             __builtin_amdgcn_wave_barrier();
             XS[lane] = c;
@@ -293,7 +295,7 @@ int hak_launch_hess_probe(int w, int h, int nimg, int step, int iters, double* m
     if (hipMalloc((void**)&s, sizeof(float) * (size_t)plane * nimg) != hipSuccess) return 1;
     if (hipMalloc((void**)&d, sizeof(float) * (size_t)plane * nimg * 2) != hipSuccess) { (void)hipFree(s); return 1; }
     (void)hipMemset(s, 0, sizeof(float) * (size_t)plane * nimg);
-    const int M = step == 1 ? 4 : step == 4 ? 12 : 8, XV = 256 - 2 * M;
+    const int M = step == 1 ? 4 : 8, XV = 256 - 2 * M;
     const int gx = (w + XV - 1) / XV;
     const int ry = hak_stream_rows(h, (long)gx * nimg, 16);
     const int gy = (h + 4 * ry - 1) / (4 * ry);

@@ -84,6 +84,10 @@ int hak_op_fast_level_tile(const int* d_src, int head, int sw, int sh, int sp, i
                            int w, int h, int p, int nimg, int diffusivity, const int* kcontrast, const float* tau, int nsteps,
                            int* launches);   /* *launches (may be NULL): what hak_launch_level_tile returns, the kernel launches of the cycle */
 int hak_op_fast_hessian(const int* d_src, int* d_lx, int* d_ly, int* d_det, int w, int h, int p, int step, int* route);
+/* hak_op_hessian / hak_op_fast_hessian on a batch of `nimg` dense planes (image i lies h * p elements behind image i-1, inputs and
+ * outputs alike), through the fused kernel the knobs pick; *route as above (1 streaming, 2 tile).  Fails above dilation 4. */
+int hak_op_hessian_batch(const float* d_src, float* d_lx, float* d_ly, float* d_det, int w, int h, int p, int nimg, int step, int* route);
+int hak_op_fast_hessian_batch(const int* d_src, int* d_lx, int* d_ly, int* d_det, int w, int h, int p, int nimg, int step, int* route);
 
 /* ---- detector-tail and descriptor stages on hand-made inputs (tests/test_gpu_literal.py: micro-fixtures whose expected
  * output is derived by hand from the cited reference statements).  They drive the SAME launchers as the launch sequence, on
