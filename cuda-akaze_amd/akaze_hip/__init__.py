@@ -49,6 +49,10 @@ assert HOMOGRAPHY_DTYPE.itemsize == 52
 FUNDAMENTAL_DTYPE = np.dtype([("F", "<f4", (9,)), ("inliers", "<i4"), ("hypothesis", "<i4"), ("root", "<i4"),
                               ("n", "<i4")])                                                  # hak_fundamental
 assert FUNDAMENTAL_DTYPE.itemsize == 52
+INTRINSICS_DTYPE = np.dtype([("fx", "<f4"), ("fy", "<f4"), ("cx", "<f4"), ("cy", "<f4")])     # hak_intrinsics
+POSE_DTYPE = np.dtype([("R", "<f4", (9,)), ("t", "<f4", (3,)), ("inliers", "<i4"), ("in_front", "<i4"), ("candidate", "<i4"),
+                       ("n", "<i4")])                                                         # hak_pose
+assert INTRINSICS_DTYPE.itemsize == 16 and POSE_DTYPE.itemsize == 64
 
 
 class HakError(RuntimeError):
@@ -104,6 +108,8 @@ SYMBOLS = {
     "hak_find_fundamental_batch": (C.c_int, [_vp, _vp, C.c_long, _vp, C.c_int, C.c_int, C.c_float, C.c_uint, _vp, _vp]),
     "hak_refine_fundamental": (C.c_int, [_vp, _vp, C.c_int, C.c_float, C.c_int, _vp, _vp]),
     "hak_refine_fundamental_batch": (C.c_int, [_vp, _vp, C.c_long, _vp, C.c_int, C.c_float, C.c_int, _vp, _vp]),
+    "hak_recover_pose": (C.c_int, [_vp, _vp, C.c_int, _fp, _vp, _vp, C.c_float, C.c_float, _vp, _vp, _vp]),
+    "hak_recover_pose_batch": (C.c_int, [_vp, _vp, C.c_long, _vp, C.c_int, _vp, _vp, _vp, C.c_float, C.c_float, _vp, _vp, _vp]),
     "hak_match_guided": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _fp, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _ip, _vp]),
     "hak_match_guided_batch": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp]),
     "hak_match_epipolar": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _fp, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _ip, _vp]),
@@ -671,3 +677,43 @@ def refineFundamental(matches, record, threshold=1.0, rounds=3, akazer=None):
     out = np.array(record, FUNDAMENTAL_DTYPE).reshape(())
     check(lib.hak_refine_fundamental(ctx, d_m.data_ptr(), n, float(threshold), int(rounds), d_mask.data_ptr(), out.ctypes.data))
     return out, d_mask[:n].cpu().numpy()
+
+
+def intrinsics(K):
+    """an INTRINSICS_DTYPE record from (fx, fy, cx, cy), a 3 x 3 pinhole matrix (zero skew) or such a record"""
+    if isinstance(K, np.ndarray) and K.dtype == INTRINSICS_DTYPE:
+        return K.reshape(()).copy()
+    K = np.asarray(K, np.float64)
+    return np.array((K[0, 0], K[1, 1], K[0, 2], K[1, 2]) if K.shape == (3, 3) else tuple(K.reshape(4)), INTRINSICS_DTYPE)
+
+
+def recoverPose(matches, F_or_record, K1, K2=None, threshold=1.0, max_depth=float("inf"), akazer=None):
+    """Relative pose from a fundamental matrix and the cameras' intrinsics (hipakaze.h hak_recover_pose), on the device.
+    `matches` as findHomography's; `F_or_record`: 9 values, row-major, or a FUNDAMENTAL_DTYPE record (one with hypothesis < 0 has
+    no model and gives the no-pose record); K1, K2: (fx, fy, cx, cy), a 3 x 3 matrix or an INTRINSICS_DTYPE record, K2 = K1 when
+    omitted.  Returns (record of POSE_DTYPE, mask uint8 (n,), xyz float32 (n, 3)): X2 = R X1 + t with |t| = 1, the mask marks the
+    inliers of F in front of both cameras, xyz their points in the first camera's frame in units of the baseline; candidate = -1
+    means no pose."""
+    import torch
+    ctx = akazer.ctx if akazer is not None else None
+    if isinstance(matches, torch.Tensor):
+        d_m = matches.contiguous()
+        n = d_m.numel() * d_m.element_size() // MATCH_PAIR_DTYPE.itemsize
+    else:
+        host = np.ascontiguousarray(matches, MATCH_PAIR_DTYPE)
+        n = len(host)
+        d_m = torch.from_numpy(host.view(np.uint8).reshape(-1)).cuda() if n else torch.zeros(32, dtype=torch.uint8, device="cuda")
+    if getattr(F_or_record, "dtype", None) is not None and F_or_record.dtype.names:
+        f = np.array(F_or_record["F"], np.float32).reshape(9)
+        if int(F_or_record["hypothesis"]) < 0:
+            f = np.full(9, np.nan, np.float32)                          # no model: the rule's step 1
+    else:
+        f = np.ascontiguousarray(np.asarray(F_or_record, np.float32).reshape(9))
+    k1 = intrinsics(K1)
+    k2 = k1 if K2 is None else intrinsics(K2)
+    d_mask = torch.zeros(max(n, 1), dtype=torch.uint8, device="cuda")
+    d_xyz = torch.zeros(3 * max(n, 1), dtype=torch.float32, device="cuda")
+    out = np.zeros((), POSE_DTYPE)
+    check(lib.hak_recover_pose(ctx, d_m.data_ptr(), n, f.ctypes.data_as(_fp), k1.ctypes.data, k2.ctypes.data, float(threshold),
+                               float(max_depth), d_mask.data_ptr(), d_xyz.data_ptr(), out.ctypes.data))
+    return out, d_mask[:n].cpu().numpy(), d_xyz[:3 * n].cpu().numpy().reshape(n, 3)

@@ -157,3 +157,62 @@ def two_view_matches(n_in, n_out, seed, w=1920, h=1080, focal=1500.0, noise=0.0,
     Ki = np.linalg.inv(K)
     F = Ki.T @ tx @ R @ Ki
     return recs[perm], flags[perm], F / np.linalg.norm(F)
+
+
+def rotation_zyx(angles_deg):
+    """R = Rz Ry Rx for (ax, ay, az) in degrees, as two_view_matches builds its fixed rotation"""
+    ax, ay, az = np.deg2rad(np.asarray(angles_deg, np.float64))
+    Rx = np.array([[1, 0, 0], [0, np.cos(ax), -np.sin(ax)], [0, np.sin(ax), np.cos(ax)]])
+    Ry = np.array([[np.cos(ay), 0, np.sin(ay)], [0, 1, 0], [-np.sin(ay), 0, np.cos(ay)]])
+    Rz = np.array([[np.cos(az), -np.sin(az), 0], [np.sin(az), np.cos(az), 0], [0, 0, 1]])
+    return Rz @ Ry @ Rx
+
+
+def two_view_scene(n_in, n_out, seed, angles_deg=(2.0, -5.0, 1.5), baseline=(-1.0, 0.05, 0.1), w=1920, h=1080, focal=1500.0,
+                   noise=0.0, depth=(4.0, 12.0), swap=False):
+    """two_view_matches with the relative pose chosen by the caller, for the pose-recovery tests and the timing tool, pure numpy.
+
+    The second camera sees X2 = R X1 + t with R = rotation_zyx(angles_deg) and t = baseline (any length > 0; `depth` is in the
+    same unit).  Points, noise, outliers and the shuffle as in two_view_matches.  swap = True exchanges the two images: the
+    records become {x2, y2, x1, y1} and the pose its inverse (R^T, -R^T t).
+    -> (records (n_in + n_out, 4) float32, inlier flags (n_in + n_out,) bool, F_true (3, 3) float64 of Frobenius norm 1,
+        K (3, 3) float64, R (3, 3) float64, t (3,) float64 of unit length,
+        z (n_in + n_out,) float64: the planted depth in the FIRST image's camera in units of the baseline length, NaN for outliers)"""
+    rng = np.random.default_rng(seed)
+    K = np.array([[focal, 0.0, w / 2.0], [0.0, focal, h / 2.0], [0.0, 0.0, 1.0]])
+    R = rotation_zyx(angles_deg)
+    t = np.asarray(baseline, np.float64).reshape(3)
+    length = float(np.linalg.norm(t))
+    assert length > 0.0
+    p1, p2, z1, z2 = np.zeros((0, 2)), np.zeros((0, 2)), np.zeros(0), np.zeros(0)
+    for _ in range(400):                                                # rejection: keep the points both cameras see
+        if len(p1) >= n_in:
+            break
+        m = 2 * n_in + 16
+        z = rng.uniform(depth[0], depth[1], m)
+        px = np.stack([rng.uniform(0, w, m), rng.uniform(0, h, m), np.ones(m)], axis=1)
+        X = (np.linalg.solve(K, px.T) * z).T                            # camera-1 coordinates
+        X2 = X @ R.T + t
+        q = X2 @ K.T
+        with np.errstate(all="ignore"):
+            q = q[:, :2] / q[:, 2:]
+        keep = (X2[:, 2] > 0.5) & (q[:, 0] >= 0) & (q[:, 0] < w) & (q[:, 1] >= 0) & (q[:, 1] < h)
+        p1, p2 = np.concatenate([p1, px[keep, :2]]), np.concatenate([p2, q[keep]])
+        z1, z2 = np.concatenate([z1, z[keep]]), np.concatenate([z2, X2[keep, 2]])
+    assert len(p1) >= n_in, "the two cameras share too little of the scene"
+    p1, p2, z1, z2 = p1[:n_in], p2[:n_in], z1[:n_in], z2[:n_in]
+    if noise > 0.0:
+        p1 = p1 + rng.normal(0.0, noise, p1.shape)
+        p2 = p2 + rng.normal(0.0, noise, p2.shape)
+    if swap:
+        p1, p2, z1 = p2, p1, z2
+        R, t = R.T, -(R.T @ t)
+    o = np.stack([rng.uniform(0, w, n_out), rng.uniform(0, h, n_out), rng.uniform(0, w, n_out), rng.uniform(0, h, n_out)], axis=1)
+    recs = np.concatenate([np.concatenate([p1, p2], axis=1), o]).astype(np.float32)
+    flags = np.concatenate([np.ones(n_in, bool), np.zeros(n_out, bool)])
+    zs = np.concatenate([z1 / length, np.full(n_out, np.nan)])
+    perm = rng.permutation(n_in + n_out)
+    tx = np.array([[0.0, -t[2], t[1]], [t[2], 0.0, -t[0]], [-t[1], t[0], 0.0]])
+    Ki = np.linalg.inv(K)
+    F = Ki.T @ tx @ R @ Ki
+    return recs[perm], flags[perm], F / np.linalg.norm(F), K, R, t / length, zs[perm]

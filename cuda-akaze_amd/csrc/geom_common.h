@@ -1,6 +1,7 @@
 // geom_common.h -- device helpers shared by the geometric-verification kernels (kernels_homography.hip, kernels_fundamental.hip,
-// kernels_fundrefit.hip): the wave sum whose order the refits' rules fix, and the record load, count clamp, Sampson test and
-// 3 x 3 product of the fundamental matrix.  Every file that includes it is built with -ffp-contract=off.
+// kernels_fundrefit.hip, kernels_pose.hip): the wave sum whose order the refits' rules fix, the record load, count clamp, Sampson
+// test and 3 x 3 product of the fundamental matrix, and the 3 x 3 cyclic Jacobi of the refit's rule.  Every file that includes it
+// is built with -ffp-contract=off.
 #pragma once
 #include "hak_internal.h"
 
@@ -52,4 +53,59 @@ __device__ __forceinline__ void fd_mul3(const double A[9], const double B[9], do
     for (int i = 0; i < 3; i++)
 #pragma unroll
         for (int j = 0; j < 3; j++) C[3 * i + j] = (A[3 * i] * B[j] + A[3 * i + 1] * B[3 + j]) + A[3 * i + 2] * B[6 + j];
+}
+
+// the rotation that annihilates apq (step 5 of hak_refine_fundamental)
+__device__ __forceinline__ void fr_angle(double app, double aqq, double apq, double& t, double& c, double& sn)
+{
+    const double th = (aqq - app) / (2.0 * apq);
+    const double sg = th >= 0.0 ? 1.0 : -1.0;
+    t = sg / (fabs(th) + sqrt(th * th + 1.0));
+    c = 1.0 / sqrt(t * t + 1.0);
+    sn = t * c;
+}
+
+// the sweeps of jacobi(G, 3, sweeps) of that rule, every lane the whole problem: G is left with the eigenvalues on its diagonal,
+// V gets the eigenvectors as columns
+__device__ __forceinline__ void fd_jacobi3(double G[3][3], double V[3][3], const int sweeps)
+{
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+        for (int j = 0; j < 3; j++) V[i][j] = i == j ? 1.0 : 0.0;
+#pragma unroll 1
+    for (int sweep = 0; sweep < sweeps; sweep++)
+#pragma unroll
+        for (int p = 0; p < 2; p++)
+#pragma unroll
+            for (int q = p + 1; q < 3; q++) {
+                const double apq = G[p][q];
+                if (apq == 0.0) continue;
+                double t, c, sn;
+                fr_angle(G[p][p], G[q][q], apq, t, c, sn);
+                const int k = 3 - p - q;                            // the one index that is neither p nor q
+                const double x = G[k][p], y = G[k][q];
+                G[k][p] = G[p][k] = c * x - sn * y;
+                G[k][q] = G[q][k] = sn * x + c * y;
+                G[p][p] = G[p][p] - t * apq;
+                G[q][q] = G[q][q] + t * apq;
+                G[p][q] = G[q][p] = 0.0;
+#pragma unroll
+                for (int i = 0; i < 3; i++) {
+                    const double vp = V[i][p], vq = V[i][q];
+                    V[i][p] = c * vp - sn * vq;
+                    V[i][q] = sn * vp + c * vq;
+                }
+            }
+}
+
+// the column of the smallest eigenvalue (<, ties to the smallest j)
+__device__ __forceinline__ int fd_jacobi3_smallest(const double G[3][3])
+{
+    int best = 0;
+    double dbest = G[0][0];
+#pragma unroll
+    for (int j = 1; j < 3; j++)
+        if (G[j][j] < dbest) { dbest = G[j][j]; best = j; }
+    return best;
 }

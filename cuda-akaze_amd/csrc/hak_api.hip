@@ -872,6 +872,58 @@ extern "C" int hak_refine_fundamental_batch(hak_ctx* c, const hak_match_pair* d_
     return 0;
 }
 
+// ----------------------------------------------------------- relative pose from a fundamental matrix (kernels_pose.hip)
+static int pose_args(const hak_intrinsics* K1, const hak_intrinsics* K2, float threshold, float max_depth)
+{
+    if (!K1 || !K2) return fail("null intrinsics");
+    if (!std::isfinite(threshold) || !(threshold > 0.f)) return fail("threshold must be finite and > 0");
+    if (!(max_depth > 0.f)) return fail("max_depth must be > 0 (+inf allowed)");
+    for (const hak_intrinsics* K : {K1, K2}) {
+        if (!std::isfinite(K->fx) || !std::isfinite(K->fy) || K->fx == 0.f || K->fy == 0.f)
+            return fail("fx and fy must be finite and non-zero");
+        if (!std::isfinite(K->cx) || !std::isfinite(K->cy)) return fail("cx and cy must be finite");
+    }
+    return 0;
+}
+
+extern "C" int hak_recover_pose(hak_ctx* c, const hak_match_pair* d_matches, int n, const float F[9], const hak_intrinsics* K1,
+                                const hak_intrinsics* K2, float threshold, float max_depth, unsigned char* d_mask, float* d_xyz,
+                                hak_pose* h_out)
+{
+    if (!h_out || !F || (!d_matches && n > 0)) return fail("null argument");
+    if (n < 0) return fail("n < 0");
+    if ((reinterpret_cast<uintptr_t>(d_matches) & 15) != 0) return fail("d_matches must be 16-byte aligned");
+    if (pose_args(K1, K2, threshold, max_depth)) return 1;
+    if (hak_device_count() == 0) return fail("no HIP device: libhipakaze has no CPU fallback");
+    // no scratch.  The record's device copy is a device global that calls take in turn: nothing is allocated
+    static std::mutex record_turn;
+    std::lock_guard<std::mutex> turn(record_turn);
+    hak_pose* d_rec = hak_pose_record();
+    if (!d_rec) return fail("hipGetSymbolAddress(pose record)");
+    hipStream_t st = c ? c->stream : nullptr;
+    order_after_null_stream(c, st);
+    int rc = 0;
+    hak_launch_pose(st, d_matches, n > 0 ? n : 1, nullptr, n, 1, nullptr, F, *K1, *K2, threshold, max_depth, d_rec, d_mask, d_xyz);
+    if (hipGetLastError() != hipSuccess) rc = fail("pose launch failed");
+    if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = fail("hipStreamSynchronize(pose)");
+    if (!rc && hipMemcpy(h_out, d_rec, sizeof(hak_pose), hipMemcpyDeviceToHost) != hipSuccess) rc = fail("record download");
+    return rc;
+}
+
+extern "C" int hak_recover_pose_batch(hak_ctx* c, const hak_match_pair* d_matches, long stride, const int* d_counts, int npairs,
+                                      const hak_fundamental* d_F, const hak_intrinsics* K1, const hak_intrinsics* K2,
+                                      float threshold, float max_depth, hak_pose* d_out, unsigned char* d_masks, float* d_xyz)
+{
+    if (!c || !d_matches || !d_counts || !d_F || !d_out || npairs < 1 || stride < 1) return fail("bad argument");
+    if ((reinterpret_cast<uintptr_t>(d_matches) & 15) != 0) return fail("d_matches must be 16-byte aligned");
+    if (pose_args(K1, K2, threshold, max_depth)) return 1;
+    order_after_null_stream(c, c->stream);
+    hak_launch_pose(c->stream, d_matches, stride, d_counts, 0, npairs, d_F, nullptr, *K1, *K2, threshold, max_depth, d_out, d_masks,
+                    d_xyz);
+    if (hipGetLastError() != hipSuccess) return fail("pose launch failed");
+    return 0;
+}
+
 // ----------------------------------------------------------- guided matching (kernels_guided.hip; the rule: include/hipakaze.h)
 static int guided_args(float radius, int ratio_num, int ratio_den)
 {

@@ -796,6 +796,13 @@ hak_fundamental* hak_fundamental_refit_record();
 void hak_launch_fundamental_refit(hipStream_t st, const hak_match_pair* matches, long stride, const int* counts, int n_host,
                                   int npairs, float threshold, int rounds, hak_fundamental* inout, unsigned char* masks,
                                   long mask_stride);
+// relative pose from a fundamental matrix (kernels_pose.hip): F of pair k from d_F[k] on the device, or d_F = NULL: h_F[9] on the
+// host serves the only pair; masks and xyz (3 floats per record) at the lists' stride, either may be NULL; no scratch.
+// hak_pose_record(): the current device's one record for the synchronous call (NULL on failure)
+hak_pose* hak_pose_record();
+void hak_launch_pose(hipStream_t st, const hak_match_pair* matches, long stride, const int* counts, int n_host, int npairs,
+                     const hak_fundamental* d_F, const float* h_F, const hak_intrinsics& K1, const hak_intrinsics& K2,
+                     float threshold, float max_depth, hak_pose* out, unsigned char* masks, float* xyz);
 
 // A launcher that cannot do what it was asked (a precondition its caller should have checked) records the reason here instead
 // of aborting; enqueue_detect turns it into the call's error (hak_sequence.hip).  Thread-local, like hak_last_error().

@@ -33,16 +33,6 @@ __device__ __forceinline__ double fr_lane(double v, int lane)
     return __hiloint2double(hi, lo);
 }
 
-// the rotation that annihilates apq
-__device__ __forceinline__ void fr_angle(double app, double aqq, double apq, double& t, double& c, double& sn)
-{
-    const double th = (aqq - app) / (2.0 * apq);
-    const double sg = th >= 0.0 ? 1.0 : -1.0;
-    t = sg / (fabs(th) + sqrt(th * th + 1.0));
-    c = 1.0 / sqrt(t * t + 1.0);
-    sn = t * c;
-}
-
 // rotation (p, q) of the lane-distributed 9 x 9 problem: A = this lane's row `row` of A, V = its row of V
 __device__ __forceinline__ void fr_rotate9(double (&A)[9], double (&V)[9], const int row, const int p, const int q)
 {
@@ -109,36 +99,9 @@ __device__ void fr_jacobi9(const double Nf[45], double f[9])
 // jacobi(G, 3, 6) of the rule, every lane the whole problem; G is destroyed
 __device__ void fr_jacobi3(double G[3][3], double v[3])
 {
-    double V[3][3] = {{1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}};
-#pragma unroll 1
-    for (int sweep = 0; sweep < FR_SWEEPS3; sweep++)
-#pragma unroll
-        for (int p = 0; p < 2; p++)
-#pragma unroll
-            for (int q = p + 1; q < 3; q++) {
-                const double apq = G[p][q];
-                if (apq == 0.0) continue;
-                double t, c, sn;
-                fr_angle(G[p][p], G[q][q], apq, t, c, sn);
-                const int k = 3 - p - q;                            // the one index that is neither p nor q
-                const double x = G[k][p], y = G[k][q];
-                G[k][p] = G[p][k] = c * x - sn * y;
-                G[k][q] = G[q][k] = sn * x + c * y;
-                G[p][p] = G[p][p] - t * apq;
-                G[q][q] = G[q][q] + t * apq;
-                G[p][q] = G[q][p] = 0.0;
-#pragma unroll
-                for (int i = 0; i < 3; i++) {
-                    const double vp = V[i][p], vq = V[i][q];
-                    V[i][p] = c * vp - sn * vq;
-                    V[i][q] = sn * vp + c * vq;
-                }
-            }
-    int best = 0;
-    double dbest = G[0][0];
-#pragma unroll
-    for (int j = 1; j < 3; j++)
-        if (G[j][j] < dbest) { dbest = G[j][j]; best = j; }
+    double V[3][3];
+    fd_jacobi3(G, V, FR_SWEEPS3);
+    const int best = fd_jacobi3_smallest(G);
 #pragma unroll
     for (int i = 0; i < 3; i++) v[i] = best == 0 ? V[i][0] : (best == 1 ? V[i][1] : V[i][2]);
 }

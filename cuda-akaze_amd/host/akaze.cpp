@@ -164,6 +164,27 @@ namespace akaze
         return r.inliers;
     }
 
+    int cuRecoverPose(const hak_match_pair* matches, int n, const float F[9], const hak_intrinsics& K1, const hak_intrinsics& K2,
+                      float R[9], float t[3], unsigned char* front_mask, float threshold, float max_depth)
+    {
+        if (n < 0 || (n > 0 && !matches) || !F || !R || !t) { fprintf(stderr, "hip-akaze: cuRecoverPose: bad argument\n"); exit(-1); }
+        hak_match_pair* d_matches = nullptr;
+        unsigned char* d_mask = nullptr;
+        if (n > 0) {
+            if (hipMalloc((void**)&d_matches, sizeof(hak_match_pair) * (size_t)n) != hipSuccess) die("cuRecoverPose alloc");
+            if (front_mask && hipMalloc((void**)&d_mask, (size_t)n) != hipSuccess) die("cuRecoverPose alloc");
+            if (hak_memcpy_h2d(d_matches, matches, (long)(sizeof(hak_match_pair) * (size_t)n))) die("cuRecoverPose upload");
+        }
+        hak_pose r;
+        if (hak_recover_pose(NULL, d_matches, n, F, &K1, &K2, threshold, max_depth, d_mask, NULL, &r)) die("cuRecoverPose");
+        if (d_mask && hak_memcpy_d2h(front_mask, d_mask, n)) die("cuRecoverPose download");
+        for (int k = 0; k < 9; k++) R[k] = r.R[k];
+        for (int k = 0; k < 3; k++) t[k] = r.t[k];
+        if (d_mask) (void)hipFree(d_mask);
+        if (d_matches) (void)hipFree(d_matches);
+        return r.candidate < 0 ? -1 : r.in_front;
+    }
+
     Akazer::Akazer() { hak_default_config(&cfg); }
 
     Akazer::~Akazer() { hak_destroy(ctx); }                              // akaze.cpp:74-77

@@ -56,6 +56,14 @@ int main()
             REQUIRE(cuFindFundamental(NULL, 0, F) == 0);
             REQUIRE(cuFindFundamental(pairs.data(), np, F) == (np + 2) / 3);
             REQUIRE(cuRefineFundamental(pairs.data(), np, F, mask.data()) == (np + 2) / 3 && mask[3] == 1 && mask[1] == 0 && F[7] == 1.f);
+            const hak_intrinsics K{1500.f, 1500.f, 960.f, 540.f};      // pose over the host list: exact-size mask
+            float R[9], t[3];
+            REQUIRE(cuRecoverPose(pairs.data(), np, F, K, K, R, t, mask.data()) == (np + 2) / 3 && mask[3] == 1 && mask[1] == 0 &&
+                    R[4] == 1.f && t[0] == 1.f);
+            REQUIRE(cuRecoverPose(pairs.data(), np, F, K, K, R, t) == (np + 2) / 3);
+            REQUIRE(cuRecoverPose(NULL, 0, F, K, K, R, t) == 0);
+            F[7] = 0.f;                                                 // the stub's "no pose"
+            REQUIRE(cuRecoverPose(pairs.data(), np, F, K, K, R, t, mask.data()) == -1 && t[0] == 0.f && mask[3] == 0);
         }
         cuMatch(d1, hostless);                                      // train side without a host buffer
         d2.num_pts = 0;

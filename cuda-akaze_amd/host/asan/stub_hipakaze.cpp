@@ -150,7 +150,27 @@ int hak_refine_fundamental(hak_ctx*, const hak_match_pair* d, int n, float thres
     }
     return 0;
 }
-// the HIP runtime calls of cuMatchKnn, cuFindHomography, cuFindFundamental and cuRefineFundamental
+// as hak_find_fundamental's stub: every record read, every mask byte and xyz float written; F[7] == 0 stands for "no pose";
+// "in front" are the indices that are multiples of 3
+int hak_recover_pose(hak_ctx*, const hak_match_pair* d, int n, const float* F, const hak_intrinsics* K1, const hak_intrinsics* K2,
+                     float threshold, float max_depth, unsigned char* mask, float* xyz, hak_pose* out)
+{
+    if (!out || !F || !K1 || !K2 || (n > 0 && !d) || !(threshold > 0.f) || !(max_depth > 0.f) || K1->fx == 0.f || K2->fy == 0.f) {
+        g_err = "bad argument";
+        return 1;
+    }
+    const bool model = F[7] != 0.f && F[8] == F[8];
+    *out = hak_pose{{1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f}, {model ? 1.f : 0.f, 0.f, 0.f}, 0, 0, model ? 0 : -1, n};
+    for (int i = 0; i < n; i++) {
+        const bool in = model && d[i].x1 == d[i].x1 && i % 3 == 0;
+        out->inliers += in;
+        out->in_front += in;
+        if (mask) mask[i] = in;
+        if (xyz) xyz[3 * i] = xyz[3 * i + 1] = xyz[3 * i + 2] = in ? 1.f : 0.f;
+    }
+    return 0;
+}
+// the HIP runtime calls of cuMatchKnn, cuFindHomography, cuFindFundamental, cuRefineFundamental and cuRecoverPose
 hipError_t hipMalloc(void** p, size_t n) { *p = malloc(n); return *p ? hipSuccess : hipErrorOutOfMemory; }
 hipError_t hipFree(void* p) { free(p); return hipSuccess; }
 }

@@ -3,7 +3,7 @@
 // `nrepeats` times and cuMatch once, and prints the same five result lines.
 //
 //   hipakaze_demo [device] [left.pgm right.pgm] [nrepeats] [--dump file] [--api-checks] [--pair] [--homography] [--retain-best N]
-//                 [--retain-grid G] [--guided R] [--fundamental] [--refine N] [--epipolar R]
+//                 [--retain-grid G] [--guided R] [--fundamental] [--refine N] [--epipolar R] [--pose FX FY CX CY]
 //
 // --dump file   writes the host-side results as raw 104-byte AkazePoint records:
 //               int32 n1, n2, then n1 + n2 records of the float path (image 1 after cuMatch),
@@ -27,6 +27,10 @@
 // --epipolar R  implies --fundamental; after RANSAC re-matches the pair under that fundamental matrix (cuMatchEpipolar: every keypoint
 //               of image 1 is searched only within R pixels of its epipolar line; ratio 4/5 + cross-check inside that band), runs
 //               cuFindFundamental again on the new list and prints both match and inlier counts
+// --pose FX FY CX CY  implies --fundamental; behind RANSAC (and --refine) recovers the relative pose of the two images from F and the
+//               pinhole intrinsics, the same for both cameras (hak_recover_pose: 1 px, no depth limit), and prints R, the unit
+//               baseline direction t and the counts; with --dump, appends after the fundamental section the 64-byte hak_pose record,
+//               the n front-mask bytes and the 3 n float32 of the points
 // --retain-best N  both AkazeData get capacity N (instead of 10000) and Akazer::setRetainBest(true): an image with more keypoints
 //               keeps its N strongest (hak_set_retain_best), in raster order, on the float and the FAST path alike
 // --retain-grid G  Akazer::setRetainGrid(G), G in 8..128: an image with more keypoints than the capacity (N of --retain-best, else
@@ -105,6 +109,8 @@ int main(int argc, char** argv)
     std::string dumpPath;
     bool apiChecks = false, pairCalls = false, homography = false, fundamental = false;
     int retainBest = 0, retainGrid = 0, refine = 0;
+    bool pose = false;
+    hak_intrinsics poseK{0.f, 0.f, 0.f, 0.f};
     float guided = 0.f, epipolar = 0.f;
     {   // strip the options; what is left are the reference demo's positional arguments (main.cpp:131-135)
         int n = 1;
@@ -116,6 +122,12 @@ int main(int argc, char** argv)
             else if (!strcmp(argv[i], "--fundamental")) fundamental = true;
             else if (!strcmp(argv[i], "--guided") && i + 1 < argc) { guided = (float)std::atof(argv[++i]); homography = true; }
             else if (!strcmp(argv[i], "--refine") && i + 1 < argc) { refine = std::atoi(argv[++i]); fundamental = true; }
+            else if (!strcmp(argv[i], "--pose") && i + 4 < argc) {
+                poseK.fx = (float)std::atof(argv[i + 1]); poseK.fy = (float)std::atof(argv[i + 2]);
+                poseK.cx = (float)std::atof(argv[i + 3]); poseK.cy = (float)std::atof(argv[i + 4]);
+                i += 4;
+                pose = fundamental = true;
+            }
             else if (!strcmp(argv[i], "--epipolar") && i + 1 < argc) { epipolar = (float)std::atof(argv[++i]); fundamental = true; }
             else if (!strcmp(argv[i], "--retain-best") && i + 1 < argc) retainBest = std::atoi(argv[++i]);
             else if (!strcmp(argv[i], "--retain-grid") && i + 1 < argc) retainGrid = std::atoi(argv[++i]);
@@ -230,6 +242,36 @@ int main(int argc, char** argv)
                       << " inliers against " << before << "  (" << timer.read() - t7 << " ms)" << std::endl;
         }
     }
+    hak_pose poseRec{};
+    std::vector<unsigned char> front(good.size(), 0);
+    std::vector<float> xyz(3 * good.size(), 0.f);
+    if (pose) {
+        hak_match_pair* dGood = NULL;
+        unsigned char* dFront = NULL;
+        float* dXyz = NULL;
+        const size_t cap = ngood > 0 ? (size_t)ngood : 1;
+        CHECK(hipMalloc((void**)&dGood, sizeof(hak_match_pair) * cap));
+        CHECK(hipMalloc((void**)&dFront, cap));
+        CHECK(hipMalloc((void**)&dXyz, sizeof(float) * 3 * cap));
+        CHECK(hipMemcpy(dGood, good.data(), sizeof(hak_match_pair) * (size_t)ngood, hipMemcpyHostToDevice));
+        float t8 = timer.read();
+        if (hak_recover_pose(NULL, dGood, ngood, fund, &poseK, &poseK, 1.f, INFINITY, dFront, dXyz, &poseRec)) {
+            std::cerr << "hak_recover_pose: " << hak_last_error() << std::endl;
+            return -1;
+        }
+        float t9 = timer.read();
+        CHECK(hipMemcpy(front.data(), dFront, (size_t)ngood, hipMemcpyDeviceToHost));
+        CHECK(hipMemcpy(xyz.data(), dXyz, sizeof(float) * 3 * (size_t)ngood, hipMemcpyDeviceToHost));
+        CHECK(hipFree(dGood));
+        CHECK(hipFree(dFront));
+        CHECK(hipFree(dXyz));
+        std::cout << "Relative pose from the fundamental matrix (candidate " << poseRec.candidate << "): " << poseRec.in_front
+                  << " in front of both cameras of " << poseRec.inliers << " inliers of " << poseRec.n << "  (" << t9 - t8 << " ms)"
+                  << std::endl;
+        for (int r = 0; r < 3; r++)
+            std::cout << "  R [" << poseRec.R[3 * r] << ", " << poseRec.R[3 * r + 1] << ", " << poseRec.R[3 * r + 2] << "]" << std::endl;
+        std::cout << "  t [" << poseRec.t[0] << ", " << poseRec.t[1] << ", " << poseRec.t[2] << "]" << std::endl;
+    }
     if (guided > 0.f) {
         std::vector<hak_match_pair> gm(good.size());
         float t8 = timer.read();
@@ -327,6 +369,11 @@ int main(int argc, char** argv)
         dump.write((const char*)fund, sizeof(fund));
         dump.write((const char*)good.data(), sizeof(hak_match_pair) * (size_t)ngood);
         dump.write((const char*)finlier.data(), (size_t)ngood);
+        if (pose) {
+            dump.write((const char*)&poseRec, sizeof(poseRec));
+            dump.write((const char*)front.data(), (size_t)ngood);
+            dump.write((const char*)xyz.data(), sizeof(float) * 3 * (size_t)ngood);
+        }
     }
 
     akaze::freeAkazeData(akaze_data1);

@@ -39,6 +39,15 @@ namespace akaze
     int cuRefineFundamental(const hak_match_pair* matches, int n, float F[9], unsigned char* inlier_mask = nullptr, float threshold = 1.f,
                             int rounds = 3);
 
+    // build-side addition: relative pose from a fundamental matrix F (e.g. cuRefineFundamental's) and the two cameras' pinhole
+    // intrinsics over a host match list, on the device (hak_recover_pose): writes R (row-major) and the unit baseline direction t with
+    // X2 = R X1 + t (identity and 0 when there is no pose) and, when front_mask is not NULL, n bytes (1 = an inlier of F at
+    // `threshold` px that lies in front of both cameras, nearer than max_depth baselines); returns the number of such matches, or
+    // -1 when F gives no pose.
+    int cuRecoverPose(const hak_match_pair* matches, int n, const float F[9], const hak_intrinsics& K1, const hak_intrinsics& K2,
+                      float R[9], float t[3], unsigned char* front_mask = nullptr, float threshold = 1.f,
+                      float max_depth = __builtin_inff());
+
     // build-side addition: guided matching (hak_match_guided) -- re-matches result1 against result2 under a homography H (row-major,
     // (x1, y1, 1) -> image 2, e.g. cuFindHomography's): every keypoint of result1 is searched only among the keypoints of result2
     // within `radius` pixels of where H sends it, ratio test and cross-check inside that neighbourhood.  Fills result1 like cuMatch

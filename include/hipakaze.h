@@ -342,7 +342,8 @@ int hak_find_fundamental_batch(hak_ctx* ctx, const hak_match_pair* d_matches, lo
  *   8. Output: F = cur, inliers = cnt, hypothesis unchanged, n = the matches considered, root = 3 if a round was accepted and
  *      the input's root otherwise; the optional mask gets the inliers of cur at this call's threshold.  So inliers never falls
  *      below the input F's count at the same threshold, and a refitted record may be passed in again.
- * Limits: an unweighted algebraic (eight-point) fit -- no Sampson weighting, no re-weighting; nothing is estimated beyond F.
+ * Limits: an unweighted algebraic (eight-point) fit -- no Sampson weighting, no re-weighting; nothing is estimated beyond F (the pose is the
+ * next stage, hak_recover_pose below).
  * Refused with a non-zero status and a message before any device is touched: rounds outside 1..8, a threshold that is not finite
  * or not > 0, n < 0, a NULL list with n > 0, a list that is not 16-byte aligned, NULL h_inout / d_inout / d_counts, npairs < 1,
  * stride < 1, a NULL context for the batch form.  Device code: csrc/kernels_fundrefit.hip. */
@@ -356,6 +357,70 @@ int hak_refine_fundamental(hak_ctx* ctx, const hak_match_pair* d_matches, int n,
  * hak_match_epipolar_batch needs no host synchronisation */
 int hak_refine_fundamental_batch(hak_ctx* ctx, const hak_match_pair* d_matches, long stride, const int* d_counts, int npairs,
                                  float threshold, int rounds, hak_fundamental* d_inout, unsigned char* d_masks);
+
+/* ---- relative pose from a fundamental matrix (build-side addition; the stage behind hak_find_fundamental and
+ * hak_refine_fundamental, and what a stereo, SfM or SLAM front end consumes).  From F and the two cameras' pinhole intrinsics:
+ * the rotation and the baseline's direction between the cameras, which matches lie in front of both, and a first 3-D point per
+ * such match.  Conventions: X2 = R X1 + t with X1, X2 the same point in the first and the second camera's frame; |t| = 1 (the
+ * baseline's length is not observable); points are in the FIRST camera's frame in units of the baseline.  A pure function of
+ * (matches, F, K1, K2, threshold, max_depth); tests/pose_ref.py is its bit-exact numpy statement.  float64, no FMA, + - * / sqrt
+ * only; records are read as by hak_find_fundamental (a non-finite coordinate is never an inlier).  dot(a, b) below is
+ * (a0 b0 + a1 b1) + a2 b2, cross(a, b) = (a1 b2 - a2 b1, a2 b0 - a0 b2, a0 b1 - a1 b0), M v has the entries dot(row i of M, v).
+ *   1. No model: a record with hypothesis < 0 (batch form), or an F with a non-finite entry, gives the no-pose record
+ *      (R = identity, t = 0, inliers = 0, in_front = 0, candidate = -1, n) and an all-zero mask and xyz.
+ *   2. Essential matrix: E = K2^T (F K1), K = [fx 0 cx; 0 fy cy; 0 0 1] widened to float64, both products as in step 6 of
+ *      hak_find_fundamental; every entry of E is divided by E's entry of largest |value| (ties to the smallest index; E stays
+ *      float64).  No pose (the record of step 1) if that entry is 0 or non-finite.
+ *   3. Decomposition: G[i][j] = (E[0][i] E[0][j] + E[1][i] E[1][j]) + E[2][i] E[2][j]; the sweeps of jacobi(G, 3, 6) of
+ *      hak_refine_fundamental leave the eigenvalues on G's diagonal and the eigenvectors in V's columns.  j3 = the column with the
+ *      smallest G[j][j] (<, ties to the smallest j); v1, v2 = the other two columns in ascending order; v3 = cross(v1, v2).
+ *      x = E v1, l1 = sqrt(dot(x, x)), u1 = x / l1; y = E v2, d = dot(u1, y), w = y - d u1, l2 = sqrt(dot(w, w)), u2 = w / l2;
+ *      u3 = cross(u1, u2).  No pose unless l1 and l2 are finite and > 0.  [u1 u2 u3] and [v1 v2 v3] have determinant +1 by
+ *      construction, so both rotations below are proper.
+ *   4. Candidates: Ra[i][j] = (u2_i v1_j - u1_i v2_j) + u3_i v3_j (= U W V^T, W = [0 -1 0; 1 0 0; 0 0 1]),
+ *      Rb[i][j] = (u1_i v2_j - u2_i v1_j) + u3_i v3_j (= U W^T V^T); candidates 0..3 = (Ra, u3), (Ra, -u3), (Rb, u3), (Rb, -u3),
+ *      all float64 (nothing is rounded before step 6).
+ *   5. Depths, for every inlier of F by step 7 of hak_find_fundamental at t2 = threshold * threshold in float32, under a
+ *      candidate (R, t): x = (x1 - cx1) / fx1, y = (y1 - cy1) / fy1, a_i = (R[i][0] x + R[i][1] y) + R[i][2],
+ *      b = ((x2 - cx2) / fx2, (y2 - cy2) / fy2, 1); aa = dot(a, a), bb = dot(b, b), ab = dot(a, b), at = dot(a, t),
+ *      bt = dot(b, t); det = aa bb - ab ab, z1 = (ab bt - bb at) / det, z2 = (aa bt - ab at) / det -- the least-squares solution
+ *      of z1 a + t = z2 b.  In front iff det > 0 and 0 < z1 < max_depth and 0 < z2 < max_depth (max_depth widened to float64;
+ *      NaN fails).
+ *   6. The candidate with the most inliers in front wins, ties to the smallest index.  R and t are the winner's, rounded to
+ *      float32; inliers = the inliers of F, in_front = the winner's count, candidate = its index.  The optional mask gets 1 for
+ *      an inlier in front under the winner, 0 otherwise (n bytes); the optional xyz gets (float32(z1 x), float32(z1 y),
+ *      float32(z1)) for such a match and (0, 0, 0) otherwise (3 n floats).  in_front = 0 is still a pose: candidate = -1 only
+ *      comes from steps 1-3.
+ * Every value reduced across lanes is an integer count, so the result does not depend on the launch shape.
+ * Limits: the pose comes from F and the intrinsics, not from a five-point essential-matrix RANSAC; no lens distortion, no skew;
+ * no bundle adjustment; depths are a linear two-ray solve, not a reprojection-error minimum.  A planar scene or a pure rotation
+ * gives an F that does not determine the pose: the call returns whatever wins, and in_front / inliers is the caller's signal.
+ * Refused with a non-zero status and a message before any device is touched: a threshold that is not finite or not > 0, a
+ * max_depth that is NaN or not > 0 (+inf is allowed), fx or fy not finite or 0, a non-finite cx or cy, NULL F / K1 / K2 / h_out /
+ * d_out / d_F / d_counts, n < 0, a NULL list with n > 0, a list that is not 16-byte aligned, npairs < 1, stride < 1, a NULL context
+ * for the batch form.  Device code: csrc/kernels_pose.hip. */
+typedef struct hak_intrinsics { float fx, fy, cx, cy; } hak_intrinsics;   /* pinhole, zero skew */
+typedef struct hak_pose {
+    float R[9];              /* row-major, X2 = R X1 + t */
+    float t[3];              /* unit length: the baseline's direction, its scale is not observable */
+    int   inliers;           /* Sampson inliers of F at this call's threshold */
+    int   in_front;          /* of those, the matches in front of both cameras under (R, t) */
+    int   candidate;         /* 0..3: which of the four decompositions won; -1 = no pose (R = identity, t = 0) */
+    int   n;                 /* matches considered */
+} hak_pose;                  /* 64 bytes */
+/* one list, synchronous; ctx may be NULL (default stream); F: 9 floats on the HOST, row-major as hak_fundamental.F; d_mask (device,
+ * n bytes) and d_xyz (device, 3 n floats) may each be NULL; result to *h_out (host).  The call needs no scratch and allocates
+ * nothing: calls share one device-resident record and take it in turn. */
+int hak_recover_pose(hak_ctx* ctx, const hak_match_pair* d_matches, int n, const float F[9] /* host */,
+                     const hak_intrinsics* K1, const hak_intrinsics* K2, float threshold, float max_depth,
+                     unsigned char* d_mask, float* d_xyz, hak_pose* h_out);
+/* batched, asynchronous on the context's stream, layouts as hak_refine_fundamental_batch; K1 and K2 are host arguments, the same
+ * for every pair of the call.  F of pair k is read ON THE DEVICE from d_F[k]; record k to d_out[k], mask of pair k to
+ * d_masks + k*stride, its points to d_xyz + 3*k*stride (each unless NULL).  The chain detect batch -> hak_match_knn2_batch ->
+ * hak_find_fundamental_batch (-> hak_refine_fundamental_batch) -> hak_recover_pose_batch needs no host synchronisation. */
+int hak_recover_pose_batch(hak_ctx* ctx, const hak_match_pair* d_matches, long stride, const int* d_counts, int npairs,
+                           const hak_fundamental* d_F, const hak_intrinsics* K1, const hak_intrinsics* K2,
+                           float threshold, float max_depth, hak_pose* d_out, unsigned char* d_masks, float* d_xyz);
 
 /* ---- guided matching: re-match a pair under its estimated homography (build-side addition; the stage behind
  * hak_find_homography).  The 2-NN search of hak_match_knn2 looks at the whole other image, so on repetitive texture its ratio
