@@ -53,6 +53,11 @@ INTRINSICS_DTYPE = np.dtype([("fx", "<f4"), ("fy", "<f4"), ("cx", "<f4"), ("cy",
 POSE_DTYPE = np.dtype([("R", "<f4", (9,)), ("t", "<f4", (3,)), ("inliers", "<i4"), ("in_front", "<i4"), ("candidate", "<i4"),
                        ("n", "<i4")])                                                         # hak_pose
 assert INTRINSICS_DTYPE.itemsize == 16 and POSE_DTYPE.itemsize == 64
+CORR3D_DTYPE = np.dtype([("X", "<f4"), ("Y", "<f4"), ("Z", "<f4"), ("u", "<f4"), ("v", "<f4"), ("src3d", "<i4"), ("src2d", "<i4"),
+                         ("pad", "<i4")])                                                     # hak_corr3d
+ABS_POSE_DTYPE = np.dtype([("R", "<f4", (9,)), ("t", "<f4", (3,)), ("inliers", "<i4"), ("hypothesis", "<i4"), ("solution", "<i4"),
+                           ("n", "<i4")])                                                     # hak_abs_pose
+assert CORR3D_DTYPE.itemsize == 32 and ABS_POSE_DTYPE.itemsize == 64
 
 
 class HakError(RuntimeError):
@@ -110,6 +115,10 @@ SYMBOLS = {
     "hak_refine_fundamental_batch": (C.c_int, [_vp, _vp, C.c_long, _vp, C.c_int, C.c_float, C.c_int, _vp, _vp]),
     "hak_recover_pose": (C.c_int, [_vp, _vp, C.c_int, _fp, _vp, _vp, C.c_float, C.c_float, _vp, _vp, _vp]),
     "hak_recover_pose_batch": (C.c_int, [_vp, _vp, C.c_long, _vp, C.c_int, _vp, _vp, _vp, C.c_float, C.c_float, _vp, _vp, _vp]),
+    "hak_link_tracks": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _ip, _vp]),
+    "hak_link_tracks_batch": (C.c_int, [_vp, _vp, C.c_long, _vp, C.c_int, _vp, _vp, _vp, C.c_long, _vp, C.c_int, C.c_int, _vp, C.c_long, _vp]),
+    "hak_solve_pnp": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, C.c_float, C.c_uint, _vp, _vp]),
+    "hak_solve_pnp_batch": (C.c_int, [_vp, _vp, C.c_long, _vp, C.c_int, _vp, C.c_int, C.c_float, C.c_uint, _vp, _vp]),
     "hak_match_guided": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _fp, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _ip, _vp]),
     "hak_match_guided_batch": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp]),
     "hak_match_epipolar": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _fp, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _ip, _vp]),
@@ -717,3 +726,57 @@ def recoverPose(matches, F_or_record, K1, K2=None, threshold=1.0, max_depth=floa
     check(lib.hak_recover_pose(ctx, d_m.data_ptr(), n, f.ctypes.data_as(_fp), k1.ctypes.data, k2.ctypes.data, float(threshold),
                                float(max_depth), d_mask.data_ptr(), d_xyz.data_ptr(), out.ctypes.data))
     return out, d_mask[:n].cpu().numpy(), d_xyz[:3 * n].cpu().numpy().reshape(n, 3)
+
+
+def _device_records(a, dtype):
+    """(device uint8 tensor, record count) of a host structured array or of a device tensor of such records (used in place)"""
+    import torch
+    if isinstance(a, torch.Tensor):
+        d = a.contiguous()
+        return d, d.numel() * d.element_size() // dtype.itemsize
+    host = np.ascontiguousarray(a, dtype)
+    n = len(host)
+    return (torch.from_numpy(host.view(np.uint8).reshape(-1)).cuda() if n else torch.zeros(32, dtype=torch.uint8, device="cuda")), n
+
+
+def linkTracks(matchesA, xyzA, matchesB, maskA=None, max_index=None, akazer=None):
+    """Joins the match list of images (I0, I1) with its points (recoverPose's xyz, (nA, 3) float32) and the match list of images
+    (I1, I2) on the shared image into 3-D to 2-D correspondences (hipakaze.h hak_link_tracks), on the device.  The lists as
+    findHomography's; maskA: nA bytes (recoverPose's front mask) or None; max_index: a bound above every keypoint index of I1
+    (default: one above the largest train index of a host list A).  Returns a CORR3D_DTYPE array in ascending order of B."""
+    import torch
+    ctx = akazer.ctx if akazer is not None else None
+    d_a, na = _device_records(matchesA, MATCH_PAIR_DTYPE)
+    d_b, nb = _device_records(matchesB, MATCH_PAIR_DTYPE)
+    if max_index is None:
+        if isinstance(matchesA, torch.Tensor):
+            raise HakError("linkTracks: max_index is needed with a device list")
+        max_index = int(np.asarray(matchesA["train"]).max()) + 1 if na else 1
+    d_xyz = xyzA.contiguous() if isinstance(xyzA, torch.Tensor) else torch.from_numpy(
+        np.ascontiguousarray(xyzA, np.float32).reshape(-1)).cuda() if na else torch.zeros(4, dtype=torch.float32, device="cuda")
+    d_mask = None
+    if maskA is not None:
+        d_mask = maskA.contiguous() if isinstance(maskA, torch.Tensor) else torch.from_numpy(
+            np.ascontiguousarray(maskA, np.uint8).reshape(-1)).cuda() if na else torch.zeros(4, dtype=torch.uint8, device="cuda")
+    d_out = torch.zeros(max(nb, 1) * CORR3D_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+    out = np.zeros(max(nb, 1), CORR3D_DTYPE)
+    count = C.c_int(0)
+    check(lib.hak_link_tracks(ctx, d_a.data_ptr(), na, d_mask.data_ptr() if d_mask is not None else None, d_xyz.data_ptr(),
+                              d_b.data_ptr(), nb, int(max_index), d_out.data_ptr(), C.byref(count), out.ctypes.data))
+    return out[:count.value].copy()
+
+
+def solvePnP(corr, K, iterations=1024, threshold=2.0, seed=0, akazer=None):
+    """RANSAC absolute pose from 3-D to 2-D correspondences by the three-point solve (hipakaze.h hak_solve_pnp), on the device.
+    `corr`: the CORR3D_DTYPE array linkTracks returns (host), or a device tensor of such records (used in place); K: (fx, fy, cx, cy),
+    a 3 x 3 matrix or an INTRINSICS_DTYPE record.  Returns (record of ABS_POSE_DTYPE, inlier mask as a uint8 numpy array):
+    Xc = R X + t in the units of the points; hypothesis = -1 means no model."""
+    import torch
+    ctx = akazer.ctx if akazer is not None else None
+    d_c, n = _device_records(corr, CORR3D_DTYPE)
+    k = intrinsics(K)
+    d_mask = torch.zeros(max(n, 1), dtype=torch.uint8, device="cuda")
+    out = np.zeros((), ABS_POSE_DTYPE)
+    check(lib.hak_solve_pnp(ctx, d_c.data_ptr(), n, k.ctypes.data, int(iterations), float(threshold), int(seed) & 0xFFFFFFFF,
+                            d_mask.data_ptr(), out.ctypes.data))
+    return out, d_mask[:n].cpu().numpy()

@@ -9,6 +9,8 @@ to_float(u8)       -> float32 in [0,1] exactly as main.cpp:149 (convertTo(CV_32F
 random_descriptors -> AkazePoint arrays for the 10k x 10k matcher config.
 two_view_matches(n_in, n_out, seed) -> (records, inlier flags, F_true): matches of a 3-D point cloud seen by two pinhole
                      cameras with a known relative pose, plus uniformly random outlier records.
+three_view_scene(seed, n, noise_px, outlier_share) -> K, the two relative poses and the match lists of (I0, I1) and (I1, I2)
+                     over shared keypoint indices of I1, for the track-linking and absolute-pose stages.
 """
 import numpy as np
 
@@ -216,3 +218,81 @@ def two_view_scene(n_in, n_out, seed, angles_deg=(2.0, -5.0, 1.5), baseline=(-1.
     Ki = np.linalg.inv(K)
     F = Ki.T @ tx @ R @ Ki
     return recs[perm], flags[perm], F / np.linalg.norm(F), K, R, t / length, zs[perm]
+
+
+MATCH_DTYPE = np.dtype([("query", "<i4"), ("train", "<i4"), ("distance", "<i4"), ("second", "<i4"),
+                        ("x1", "<f4"), ("y1", "<f4"), ("x2", "<f4"), ("y2", "<f4")])      # hak_match_pair
+
+
+def three_view_scene(seed, n, noise_px=0.0, outlier_share=0.0, angles01=(2.0, -5.0, 1.5), t01=(-1.0, 0.05, 0.1),
+                     angles12=(-1.5, -4.0, 2.0), t12=(-0.9, -0.1, 0.25), w=1920, h=1080, focal=1500.0, depth=(4.0, 12.0)):
+    """Three pinhole views of one point cloud as two match lists that share the middle image, for the track-linking and
+    absolute-pose tests and the timing tool, built beside two_view_scene, pure numpy.
+
+    n 3-D points, uniformly random in the first camera's frustum at depths `depth`, that all three cameras see; camera 1 sees
+    X1 = R01 X0 + t01, camera 2 sees X2 = R12 X1 + t12 (R = rotation_zyx(angles), t in the unit of `depth`, any length > 0).
+    Every image has 2 n keypoints in a random order: the n projections, with `noise_px` of Gaussian noise added once per keypoint
+    (so image 1's records are the same in both lists), and n spurious ones, uniformly random in the image.  List A holds one match
+    per point from image 0 (query) to image 1 (train), list B one per point from image 1 (query) to image 2 (train), both in
+    ascending query order as hak_match_knn2 writes them; a share `outlier_share` of each list, chosen independently, has its train
+    end replaced by a randomly chosen other keypoint of that image (so train indices may repeat).
+    -> (K (3, 3) float64, (R01, t01), (R12, t12), A, B: MATCH_DTYPE arrays of n records,
+        flagsA, flagsB: (n,) bool, True for a correct match,
+        X0: (n, 3) float64, the point behind each record of A in the FIRST camera's frame,
+        pointA, pointB: (n,) int64, which point each record of A and of B belongs to)"""
+    rng = np.random.default_rng(seed)
+    K = np.array([[focal, 0.0, w / 2.0], [0.0, focal, h / 2.0], [0.0, 0.0, 1.0]])
+    R01, R12 = rotation_zyx(angles01), rotation_zyx(angles12)
+    t01, t12 = np.asarray(t01, np.float64).reshape(3), np.asarray(t12, np.float64).reshape(3)
+
+    def project(X):
+        q = X @ K.T
+        with np.errstate(all="ignore"):
+            return q[:, :2] / q[:, 2:]
+
+    def inside(X, p):
+        return (X[:, 2] > 0.5) & (p[:, 0] >= 0) & (p[:, 0] < w) & (p[:, 1] >= 0) & (p[:, 1] < h)
+
+    X0 = np.zeros((0, 3))
+    for _ in range(400):                                                # rejection: keep the points all three cameras see
+        if len(X0) >= n:
+            break
+        m = 2 * n + 16
+        z = rng.uniform(depth[0], depth[1], m)
+        px = np.stack([rng.uniform(0, w, m), rng.uniform(0, h, m), np.ones(m)], axis=1)
+        X = (np.linalg.solve(K, px.T) * z).T
+        X1 = X @ R01.T + t01
+        X2 = X1 @ R12.T + t12
+        X0 = np.concatenate([X0, X[inside(X1, project(X1)) & inside(X2, project(X2))]])
+    assert len(X0) >= n, "the three cameras share too little of the scene"
+    X0 = X0[:n]
+    X1 = X0 @ R01.T + t01
+    X2 = X1 @ R12.T + t12
+    pos, index = [], []
+    for X in (X0, X1, X2):
+        p = project(X)
+        if noise_px > 0.0:
+            p = p + rng.normal(0.0, noise_px, p.shape)
+        spurious = np.stack([rng.uniform(0, w, n), rng.uniform(0, h, n)], axis=1)
+        order = rng.permutation(2 * n)                                  # keypoint index of point j: order[j]; spurious: order[n + j]
+        allp = np.zeros((2 * n, 2))
+        allp[order] = np.concatenate([p, spurious])
+        pos.append(allp)
+        index.append(order[:n])
+
+    def matches(a, b):
+        lst = np.zeros(n, MATCH_DTYPE)
+        good = np.ones(n, bool)
+        good[rng.permutation(n)[:int(round(outlier_share * n))]] = False
+        other = (index[b] + 1 + rng.integers(0, max(2 * n - 1, 1), n)) % (2 * n)      # any keypoint but the right one
+        train = np.where(good, index[b], other)
+        lst["query"], lst["train"] = index[a], train
+        lst["distance"], lst["second"] = 20, 60
+        lst["x1"], lst["y1"] = pos[a][index[a], 0], pos[a][index[a], 1]
+        lst["x2"], lst["y2"] = pos[b][train, 0], pos[b][train, 1]
+        by_query = np.argsort(lst["query"], kind="stable")
+        return lst[by_query], good[by_query], by_query
+
+    A, flagsA, pointA = matches(0, 1)
+    B, flagsB, pointB = matches(1, 2)
+    return K, (R01, t01), (R12, t12), A, B, flagsA, flagsB, X0[pointA], pointA.astype(np.int64), pointB.astype(np.int64)

@@ -1,7 +1,8 @@
 // geom_common.h -- device helpers shared by the geometric-verification kernels (kernels_homography.hip, kernels_fundamental.hip,
-// kernels_fundrefit.hip, kernels_pose.hip): the wave sum whose order the refits' rules fix, the record load, count clamp, Sampson
-// test and 3 x 3 product of the fundamental matrix, and the 3 x 3 cyclic Jacobi of the refit's rule.  Every file that includes it
-// is built with -ffp-contract=off.
+// kernels_fundrefit.hip, kernels_pose.hip, kernels_pnp.hip): the wave sum whose order the refits' rules fix, the record load, count
+// clamp, Sampson test and 3 x 3 product of the fundamental matrix, the real roots of a monic cubic by bracketing and bisection (step
+// 5 of hak_find_fundamental, also the critical points of hak_solve_pnp's quartic), and the 3 x 3 cyclic Jacobi of the refit's rule.
+// Every file that includes it is built with -ffp-contract=off.
 #pragma once
 #include "hak_internal.h"
 
@@ -53,6 +54,52 @@ __device__ __forceinline__ void fd_mul3(const double A[9], const double B[9], do
     for (int i = 0; i < 3; i++)
 #pragma unroll
         for (int j = 0; j < 3; j++) C[3 * i + j] = (A[3 * i] * B[j] + A[3 * i + 1] * B[3 + j]) + A[3 * i + 2] * B[6 + j];
+}
+
+// the monic cubic ((a + b2) a + b1) a + b0
+__device__ __forceinline__ double fd_q(double a, double b2, double b1, double b0) { return ((a + b2) * a + b1) * a + b0; }
+
+// 64 bisections of [lo, hi]; *has = the ends differ in the sign test
+__device__ __forceinline__ double fd_bisect(double lo, double hi, double b2, double b1, double b0, bool* has)
+{
+    const bool neg = fd_q(lo, b2, b1, b0) < 0.0;
+    *has = neg != (fd_q(hi, b2, b1, b0) < 0.0);
+#pragma unroll 1
+    for (int it = 0; it < 64; it++) {
+        const double mid = 0.5 * (lo + hi);
+        const bool left = (fd_q(mid, b2, b1, b0) < 0.0) == neg;
+        lo = left ? mid : lo;
+        hi = left ? hi : mid;
+    }
+    return 0.5 * (lo + hi);
+}
+
+// step 5 of hak_find_fundamental from the monic coefficients on: the real roots of ((a + b2) a + b1) a + b0 in bracket order to
+// av[0 .. *count); false if a coefficient or the bound is non-finite.  Shared with the quartic's critical points of hak_solve_pnp.
+__device__ __forceinline__ bool fd_cubic_roots(double b2, double b1, double b0, double av[3], int* count)
+{
+    double mx = fabs(b2);
+    if (fabs(b1) > mx) mx = fabs(b1);
+    if (fabs(b0) > mx) mx = fabs(b0);
+    const double bound = 1.0 + mx;
+    if (!(__builtin_isfinite(b2) && __builtin_isfinite(b1) && __builtin_isfinite(b0) && __builtin_isfinite(bound))) return false;
+    const double D = b2 * b2 - 3.0 * b1;
+    const bool three = D > 0.0;
+    const double sq = sqrt(three ? D : 0.0);
+    const double t1 = (-b2 - sq) / 3.0, t2 = (-b2 + sq) / 3.0;
+    double root[3];
+    bool has[3];
+    root[0] = fd_bisect(-bound, three ? t1 : bound, b2, b1, b0, &has[0]);
+    root[1] = fd_bisect(t1, t2, b2, b1, b0, &has[1]);
+    root[2] = fd_bisect(t2, bound, b2, b1, b0, &has[2]);
+    has[1] = has[1] && three;
+    has[2] = has[2] && three;
+    // roots are numbered in bracket order: compact them (selects)
+    *count = (int)has[0] + (int)has[1] + (int)has[2];
+    av[0] = has[0] ? root[0] : (has[1] ? root[1] : root[2]);
+    av[1] = (has[0] && has[1]) ? root[1] : root[2];
+    av[2] = root[2];
+    return true;
 }
 
 // the rotation that annihilates apq (step 5 of hak_refine_fundamental)

@@ -324,7 +324,7 @@ extern "C" void hak_destroy(hak_ctx* c)
         for (auto ev : p.ev) (void)hipEventDestroy(ev);
     hak_match_scratch_free(&c->msc);
     void* bufs[] = {c->arena, c->maps, c->bitmap, c->rowcount, c->cand, c->state, c->d_num, c->dtab, c->knn, c->d_cnt, c->perm, c->pair_pts,
-                    c->hom_slots, c->hom_rec, c->fund_models, c->fund_rec, c->sel.st, c->sel.bins, c->sel.tie, c->grid.st, c->grid.count, c->grid.comp, c->guided};
+                    c->hom_slots, c->hom_rec, c->fund_models, c->fund_rec, c->pnp_models, c->pnp_rec, c->link_tab, c->sel.st, c->sel.bins, c->sel.tie, c->grid.st, c->grid.count, c->grid.comp, c->guided};
     for (void* b : bufs) (void)hipFree(b);
     if (c->h_num) (void)hipHostFree(c->h_num);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -921,6 +921,150 @@ extern "C" int hak_recover_pose_batch(hak_ctx* c, const hak_match_pair* d_matche
     hak_launch_pose(c->stream, d_matches, stride, d_counts, 0, npairs, d_F, nullptr, *K1, *K2, threshold, max_depth, d_out, d_masks,
                     d_xyz);
     if (hipGetLastError() != hipSuccess) return fail("pose launch failed");
+    return 0;
+}
+
+// ----------------------------------------------------------- track linking and RANSAC absolute pose (kernels_pnp.hip)
+// grow-only and outside a launch sequence, as homography_scratch; words = 0 / entries = 0: that part is not needed
+static int pnp_scratch(hak_ctx* c, long slots, long words, long entries)
+{
+    if (slots > 0 && homography_scratch(c, slots)) return 1;
+    if (words > c->pnp_cap) {
+        if (c->pnp_models) HIP_TRY(hipFree(c->pnp_models));
+        c->pnp_models = nullptr;
+        c->pnp_cap = 0;
+        HIP_TRY(hipMalloc((void**)&c->pnp_models, sizeof(unsigned) * (size_t)words));
+        c->pnp_cap = words;
+    }
+    if (entries > c->link_cap) {
+        if (c->link_tab) HIP_TRY(hipFree(c->link_tab));
+        c->link_tab = nullptr;
+        c->link_cap = 0;
+        HIP_TRY(hipMalloc((void**)&c->link_tab, sizeof(int) * (size_t)entries));
+        c->link_cap = entries;
+    }
+    if (!c->pnp_rec) HIP_TRY(hipMalloc((void**)&c->pnp_rec, 80));
+    return 0;
+}
+
+static int pnp_args(const hak_intrinsics* K, int iterations, float threshold)
+{
+    if (!K) return fail("null intrinsics");
+    if (homography_args(iterations, threshold, 0)) return 1;
+    if (!std::isfinite(K->fx) || !std::isfinite(K->fy) || K->fx == 0.f || K->fy == 0.f)
+        return fail("fx and fy must be finite and non-zero");
+    if (!std::isfinite(K->cx) || !std::isfinite(K->cy)) return fail("cx and cy must be finite");
+    return 0;
+}
+
+static bool misaligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
+
+extern "C" int hak_link_tracks(hak_ctx* c, const hak_match_pair* d_A, int nA, const unsigned char* d_maskA, const float* d_xyzA,
+                               const hak_match_pair* d_B, int nB, int max_index, hak_corr3d* d_out, int* count, hak_corr3d* h_out)
+{
+    if (!count || (!d_A && nA > 0) || (!d_xyzA && nA > 0) || (!d_B && nB > 0) || (!d_out && nB > 0)) return fail("null argument");
+    if (nA < 0 || nB < 0 || nA >= (1 << 30) || nB >= (1 << 30)) return fail("a count is negative or not below 2^30");
+    if (max_index < 1) return fail("max_index < 1");
+    if (misaligned16(d_A) || misaligned16(d_B) || misaligned16(d_out)) return fail("the lists must be 16-byte aligned");
+    if (hak_device_count() == 0) return fail("no HIP device: libhipakaze has no CPU fallback");
+    int* d_tab = nullptr;
+    int* d_cnt = nullptr;
+    if (c) {
+        if (pnp_scratch(c, 0, 0, max_index)) return 1;
+        d_tab = c->link_tab;
+        d_cnt = reinterpret_cast<int*>(c->pnp_rec + 64);
+    } else {
+        // one allocation: count (16 bytes) | table
+        char* p = nullptr;
+        HIP_TRY(hipMalloc((void**)&p, 16 + sizeof(int) * (size_t)max_index));
+        d_cnt = reinterpret_cast<int*>(p);
+        d_tab = reinterpret_cast<int*>(p + 16);
+    }
+    hipStream_t st = c ? c->stream : nullptr;
+    order_after_null_stream(c, st);
+    hak_launch_link(st, d_A, nA > 0 ? nA : 1, nullptr, 1, nA, d_maskA, d_xyzA, d_B, nB > 0 ? nB : 1, nullptr, 1, nB, 1, max_index, d_tab,
+                    d_out, nB > 0 ? nB : 1, d_cnt);
+    int rc = 0;
+    if (hipGetLastError() != hipSuccess) rc = fail("link launch failed");
+    if (!rc && hipStreamSynchronize(st) != hipSuccess) rc = fail("hipStreamSynchronize(link)");
+    if (!rc && hipMemcpy(count, d_cnt, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) rc = fail("count download");
+    if (!rc && h_out && *count > 0 &&
+        hipMemcpy(h_out, d_out, sizeof(hak_corr3d) * (size_t)*count, hipMemcpyDeviceToHost) != hipSuccess)
+        rc = fail("list download");
+    if (!c) (void)hipFree(d_cnt);
+    return rc;
+}
+
+extern "C" int hak_link_tracks_batch(hak_ctx* c, const hak_match_pair* d_A, long strideA, const int* d_countsA, int count_stepA,
+                                     const unsigned char* d_masksA, const float* d_xyzA, const hak_match_pair* d_B, long strideB,
+                                     const int* d_countsB, int count_stepB, int npairs, hak_corr3d* d_out, long out_stride,
+                                     int* d_counts)
+{
+    if (!c) return fail("null context");
+    if (!d_A || !d_countsA || !d_xyzA || !d_B || !d_countsB || !d_out || !d_counts) return fail("null argument");
+    if (npairs < 1 || strideA < 1 || strideB < 1 || out_stride < 1 || count_stepA < 1 || count_stepB < 1)
+        return fail("npairs, the strides and the count steps must be >= 1");
+    if (misaligned16(d_A) || misaligned16(d_B) || misaligned16(d_out)) return fail("the lists must be 16-byte aligned");
+    if (c->cfg.max_pts < 1) return fail("max_index < 1");
+    if (pnp_scratch(c, 0, 0, (long)npairs * c->cfg.max_pts)) return 1;
+    order_after_null_stream(c, c->stream);
+    hak_launch_link(c->stream, d_A, strideA, d_countsA, count_stepA, 0, d_masksA, d_xyzA, d_B, strideB, d_countsB, count_stepB, 0,
+                    npairs, c->cfg.max_pts, c->link_tab, d_out, out_stride, d_counts);
+    if (hipGetLastError() != hipSuccess) return fail("link launch failed");
+    return 0;
+}
+
+extern "C" int hak_solve_pnp(hak_ctx* c, const hak_corr3d* d_corr, int n, const hak_intrinsics* K, int iterations, float threshold,
+                             unsigned seed, unsigned char* d_mask, hak_abs_pose* h_out)
+{
+    if (!h_out || (!d_corr && n > 0)) return fail("null argument");
+    if (n < 0) return fail("n < 0");
+    if (misaligned16(d_corr)) return fail("d_corr must be 16-byte aligned");
+    if (pnp_args(K, iterations, threshold)) return 1;
+    if (hak_device_count() == 0) return fail("no HIP device: libhipakaze has no CPU fallback");
+    const long slots = hak_homography_blocks(1, iterations, nullptr), words = hak_pnp_words(1, iterations);
+    unsigned long long* d_slots = nullptr;
+    unsigned* d_models = nullptr;
+    hak_abs_pose* d_rec = nullptr;
+    if (c) {
+        if (pnp_scratch(c, slots, words, 0)) return 1;
+        d_slots = c->hom_slots;
+        d_models = c->pnp_models;
+        d_rec = reinterpret_cast<hak_abs_pose*>(c->pnp_rec);
+    } else {
+        // one allocation: slots | record (64 bytes) | models
+        char* p = nullptr;
+        HIP_TRY(hipMalloc((void**)&p, sizeof(unsigned long long) * (size_t)slots + 64 + sizeof(unsigned) * (size_t)words));
+        d_slots = reinterpret_cast<unsigned long long*>(p);
+        d_rec = reinterpret_cast<hak_abs_pose*>(p + sizeof(unsigned long long) * (size_t)slots);
+        d_models = reinterpret_cast<unsigned*>(p + sizeof(unsigned long long) * (size_t)slots + 64);
+    }
+    hipStream_t st = c ? c->stream : nullptr;
+    order_after_null_stream(c, st);
+    hak_launch_pnp(st, d_corr, n > 0 ? n : 1, nullptr, n, 1, *K, iterations, threshold, seed, d_models, d_slots, d_rec, d_mask, 0);
+    int rc = 0;
+    if (hipGetLastError() != hipSuccess) rc = fail("pnp launch failed");
+    if (!rc && hipStreamSynchronize(st) != hipSuccess) rc = fail("hipStreamSynchronize(pnp)");
+    if (!rc && hipMemcpy(h_out, d_rec, sizeof(hak_abs_pose), hipMemcpyDeviceToHost) != hipSuccess) rc = fail("pnp download");
+    if (!c) (void)hipFree(d_slots);
+    return rc;
+}
+
+extern "C" int hak_solve_pnp_batch(hak_ctx* c, const hak_corr3d* d_corr, long stride, const int* d_counts, int npairs,
+                                   const hak_intrinsics* K, int iterations, float threshold, unsigned seed, hak_abs_pose* d_out,
+                                   unsigned char* d_masks)
+{
+    if (!c) return fail("null context");
+    if (!d_corr || !d_counts || !d_out) return fail("null argument");
+    if (npairs < 1 || stride < 1) return fail("npairs and the stride must be >= 1");
+    if (misaligned16(d_corr)) return fail("d_corr must be 16-byte aligned");
+    if (pnp_args(K, iterations, threshold)) return 1;
+    if (pnp_scratch(c, (long)npairs * hak_homography_blocks(npairs, iterations, nullptr), hak_pnp_words(npairs, iterations), 0))
+        return 1;
+    order_after_null_stream(c, c->stream);
+    hak_launch_pnp(c->stream, d_corr, stride, d_counts, 0, npairs, *K, iterations, threshold, seed, c->pnp_models, c->hom_slots, d_out,
+                   d_masks, stride);
+    if (hipGetLastError() != hipSuccess) return fail("pnp launch failed");
     return 0;
 }
 

@@ -79,7 +79,12 @@ struct hak_ctx {
     unsigned* fund_models = nullptr;          // hak_find_fundamental scratch: 28 words per (pair, hypothesis), grown on demand
     long fund_cap = 0;                        // (its slots are hom_slots: both run on the context's stream)
     hak_fundamental* fund_rec = nullptr;      // the record of hak_find_fundamental before its download
-    void* guided = nullptr;         // guided-matching scratch (kernels_guided.hip, kernels_epipolar.hip): grown on demand, outside a launch sequence
+    unsigned* pnp_models = nullptr;           // hak_solve_pnp scratch: 49 words per (list, hypothesis), grown on demand (slots: hom_slots)
+    long pnp_cap = 0;
+    char* pnp_rec = nullptr;                  // 64 + 16 bytes: the record of hak_solve_pnp and the count of hak_link_tracks before their download
+    int* link_tab = nullptr;                  // hak_link_tracks scratch: the table train -> a, max_index ints per pair, grown on demand
+    long link_cap = 0;
+    void* guided = nullptr;        // guided-matching scratch (kernels_guided.hip, kernels_epipolar.hip): grown on demand, outside a launch sequence
     size_t guided_cap = 0;
     hak_point* pair_pts = nullptr;  // [2][cfg.max_pts]: the contiguous pair layout hak_detect_and_compute_pair detects into and matches on
     HakMatchScratch msc;            // sliced searches of one big pair (hak_match / hak_match_knn2): grows on demand, on this context's device

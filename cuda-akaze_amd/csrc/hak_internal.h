@@ -803,6 +803,17 @@ hak_pose* hak_pose_record();
 void hak_launch_pose(hipStream_t st, const hak_match_pair* matches, long stride, const int* counts, int n_host, int npairs,
                      const hak_fundamental* d_F, const float* h_F, const hak_intrinsics& K1, const hak_intrinsics& K2,
                      float threshold, float max_depth, hak_pose* out, unsigned char* masks, float* xyz);
+// RANSAC absolute pose (kernels_pnp.hip): the score blocks are hak_homography_blocks'; `models` is scratch of hak_pnp_words(npairs,
+// iterations) 32-bit words, `slots` as hak_launch_homography's
+long hak_pnp_words(int npairs, int iterations);
+void hak_launch_pnp(hipStream_t st, const hak_corr3d* corr, long stride, const int* counts, int n_host, int npairs,
+                    const hak_intrinsics& K, int iterations, float threshold, unsigned seed, unsigned* models,
+                    unsigned long long* slots, hak_abs_pose* out, unsigned char* masks, long mask_stride);
+// track linking (kernels_pnp.hip): countsA / countsB NULL: nA_host / nB_host serve the only pair; `table`: npairs * max_index ints
+// of scratch, cleared by the launch; masksA may be NULL
+void hak_launch_link(hipStream_t st, const hak_match_pair* A, long strideA, const int* countsA, int stepA, int nA_host,
+                     const unsigned char* masksA, const float* xyzA, const hak_match_pair* B, long strideB, const int* countsB,
+                     int stepB, int nB_host, int npairs, int max_index, int* table, hak_corr3d* out, long out_stride, int* out_counts);
 
 // A launcher that cannot do what it was asked (a precondition its caller should have checked) records the reason here instead
 // of aborting; enqueue_detect turns it into the call's error (hak_sequence.hip).  Thread-local, like hak_last_error().

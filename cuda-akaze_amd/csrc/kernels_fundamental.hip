@@ -69,24 +69,6 @@ __device__ __forceinline__ bool fd_normalise(double x[7], double y[7], double& c
     return q != 0.0 && __builtin_isfinite(s);
 }
 
-// the monic cubic ((a + b2) a + b1) a + b0
-__device__ __forceinline__ double fd_q(double a, double b2, double b1, double b0) { return ((a + b2) * a + b1) * a + b0; }
-
-// 64 bisections of [lo, hi]; *has = the ends differ in the sign test
-__device__ __forceinline__ double fd_bisect(double lo, double hi, double b2, double b1, double b0, bool* has)
-{
-    const bool neg = fd_q(lo, b2, b1, b0) < 0.0;
-    *has = neg != (fd_q(hi, b2, b1, b0) < 0.0);
-#pragma unroll 1
-    for (int it = 0; it < 64; it++) {
-        const double mid = 0.5 * (lo + hi);
-        const bool left = (fd_q(mid, b2, b1, b0) < 0.0) == neg;
-        lo = left ? mid : lo;
-        hi = left ? hi : mid;
-    }
-    return 0.5 * (lo + hi);
-}
-
 // hypothesis h of a pair with n matches, steps 1-6 of the rule: up to three float32 models to Fo[3][9], returns the mask of
 // the roots that gave one (0 = degenerate)
 __device__ int fd_hypothesis(const hak_match_pair* m, int n, unsigned seed, int h, float Fo[3][9])
@@ -168,25 +150,9 @@ __device__ int fd_hypothesis(const hak_match_pair* m, int n, unsigned seed, int 
     if (!(c3 != 0.0) || !__builtin_isfinite(c3) || !__builtin_isfinite(c2) || !__builtin_isfinite(c1) || !__builtin_isfinite(c0))
         return 0;
     const double b2 = c2 / c3, b1 = c1 / c3, b0 = c0 / c3;
-    double mx = fabs(b2);
-    if (fabs(b1) > mx) mx = fabs(b1);
-    if (fabs(b0) > mx) mx = fabs(b0);
-    const double bound = 1.0 + mx;
-    if (!(__builtin_isfinite(b2) && __builtin_isfinite(b1) && __builtin_isfinite(b0) && __builtin_isfinite(bound))) return 0;
-    const double D = b2 * b2 - 3.0 * b1;
-    const bool three = D > 0.0;
-    const double sq = sqrt(three ? D : 0.0);
-    const double t1 = (-b2 - sq) / 3.0, t2 = (-b2 + sq) / 3.0;
-    double root[3];
-    bool has[3];
-    root[0] = fd_bisect(-bound, three ? t1 : bound, b2, b1, b0, &has[0]);
-    root[1] = fd_bisect(t1, t2, b2, b1, b0, &has[1]);
-    root[2] = fd_bisect(t2, bound, b2, b1, b0, &has[2]);
-    has[1] = has[1] && three;
-    has[2] = has[2] && three;
-    // roots are numbered in bracket order: compact them (selects)
-    const int count = (int)has[0] + (int)has[1] + (int)has[2];
-    const double av[3] = {has[0] ? root[0] : (has[1] ? root[1] : root[2]), (has[0] && has[1]) ? root[1] : root[2], root[2]};
+    double av[3];
+    int count;
+    if (!fd_cubic_roots(b2, b1, b0, av, &count)) return 0;
     const double T1[9] = {s1, 0.0, -(s1 * cx1), 0.0, s1, -(s1 * cy1), 0.0, 0.0, 1.0};
     const double T2t[9] = {s2, 0.0, 0.0, 0.0, s2, 0.0, -(s2 * cx2), -(s2 * cy2), 1.0};
     int valid = 0;

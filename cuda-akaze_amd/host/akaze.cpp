@@ -185,6 +185,54 @@ namespace akaze
         return r.candidate < 0 ? -1 : r.in_front;
     }
 
+    int cuLinkTracks(const hak_match_pair* A, int nA, const float* xyzA, const unsigned char* maskA, const hak_match_pair* B, int nB,
+                     int max_index, hak_corr3d* out)
+    {
+        if (nA < 0 || nB < 0 || (nA > 0 && (!A || !xyzA)) || (nB > 0 && (!B || !out))) {
+            fprintf(stderr, "hip-akaze: cuLinkTracks: bad argument\n");
+            exit(-1);
+        }
+        if (nA == 0 || nB == 0) return 0;
+        // one device block: A | B | out | xyzA | maskA (the 32-byte records first: every part stays 16-byte aligned)
+        const size_t rec = sizeof(hak_match_pair), bytesA = rec * (size_t)nA, bytesB = rec * (size_t)nB;
+        const size_t bytesX = sizeof(float) * 3 * (size_t)nA;
+        char* d = nullptr;
+        if (hipMalloc((void**)&d, bytesA + 2 * bytesB + bytesX + (maskA ? (size_t)nA : 0)) != hipSuccess) die("cuLinkTracks alloc");
+        hak_match_pair* d_A = reinterpret_cast<hak_match_pair*>(d);
+        hak_match_pair* d_B = reinterpret_cast<hak_match_pair*>(d + bytesA);
+        hak_corr3d* d_out = reinterpret_cast<hak_corr3d*>(d + bytesA + bytesB);
+        float* d_xyz = reinterpret_cast<float*>(d + bytesA + 2 * bytesB);
+        unsigned char* d_mask = maskA ? reinterpret_cast<unsigned char*>(d + bytesA + 2 * bytesB + bytesX) : nullptr;
+        if (hak_memcpy_h2d(d_A, A, (long)bytesA) || hak_memcpy_h2d(d_B, B, (long)bytesB) || hak_memcpy_h2d(d_xyz, xyzA, (long)bytesX) ||
+            (maskA && hak_memcpy_h2d(d_mask, maskA, nA)))
+            die("cuLinkTracks upload");
+        int count = 0;
+        if (hak_link_tracks(NULL, d_A, nA, d_mask, d_xyz, d_B, nB, max_index, d_out, &count, out)) die("cuLinkTracks");
+        (void)hipFree(d);
+        return count;
+    }
+
+    int cuSolvePnP(const hak_corr3d* corr, int n, const hak_intrinsics& K, float R[9], float t[3], unsigned char* inlier_mask,
+                   int iterations, float threshold, unsigned seed)
+    {
+        if (n < 0 || (n > 0 && !corr) || !R || !t) { fprintf(stderr, "hip-akaze: cuSolvePnP: bad argument\n"); exit(-1); }
+        hak_corr3d* d_corr = nullptr;
+        unsigned char* d_mask = nullptr;
+        if (n > 0) {
+            if (hipMalloc((void**)&d_corr, sizeof(hak_corr3d) * (size_t)n) != hipSuccess) die("cuSolvePnP alloc");
+            if (inlier_mask && hipMalloc((void**)&d_mask, (size_t)n) != hipSuccess) die("cuSolvePnP alloc");
+            if (hak_memcpy_h2d(d_corr, corr, (long)(sizeof(hak_corr3d) * (size_t)n))) die("cuSolvePnP upload");
+        }
+        hak_abs_pose r;
+        if (hak_solve_pnp(NULL, d_corr, n, &K, iterations, threshold, seed, d_mask, &r)) die("cuSolvePnP");
+        if (d_mask && hak_memcpy_d2h(inlier_mask, d_mask, n)) die("cuSolvePnP download");
+        for (int k = 0; k < 9; k++) R[k] = r.R[k];
+        for (int k = 0; k < 3; k++) t[k] = r.t[k];
+        if (d_mask) (void)hipFree(d_mask);
+        if (d_corr) (void)hipFree(d_corr);
+        return r.hypothesis < 0 ? -1 : r.inliers;
+    }
+
     Akazer::Akazer() { hak_default_config(&cfg); }
 
     Akazer::~Akazer() { hak_destroy(ctx); }                              // akaze.cpp:74-77

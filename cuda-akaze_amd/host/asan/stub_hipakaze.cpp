@@ -170,7 +170,43 @@ int hak_recover_pose(hak_ctx*, const hak_match_pair* d, int n, const float* F, c
     }
     return 0;
 }
-// the HIP runtime calls of cuMatchKnn, cuFindHomography, cuFindFundamental, cuRefineFundamental and cuRecoverPose
+// the link rule itself, on the host: every record of both lists, every used mask byte and point read, `count` records written
+int hak_link_tracks(hak_ctx*, const hak_match_pair* A, int nA, const unsigned char* maskA, const float* xyzA, const hak_match_pair* B,
+                    int nB, int max_index, hak_corr3d* d_out, int* count, hak_corr3d* h_out)
+{
+    if (!count || nA < 0 || nB < 0 || max_index < 1 || (nA > 0 && (!A || !xyzA)) || (nB > 0 && (!B || !d_out))) {
+        g_err = "bad argument";
+        return 1;
+    }
+    *count = 0;
+    for (int m = 0; m < nB; m++)
+        for (int a = 0; a < nA; a++)
+            if (A[a].train == B[m].query && A[a].train >= 0 && A[a].train < max_index && (!maskA || maskA[a])) {
+                d_out[*count] = hak_corr3d{xyzA[3 * a], xyzA[3 * a + 1], xyzA[3 * a + 2], B[m].x2, B[m].y2, a, m, 0};
+                if (h_out) h_out[*count] = d_out[*count];
+                ++*count;
+                break;
+            }
+    return 0;
+}
+// as hak_find_fundamental's stub: every record read, every mask byte written; "inliers" are the indices that are multiples of 3
+int hak_solve_pnp(hak_ctx*, const hak_corr3d* d, int n, const hak_intrinsics* K, int iterations, float threshold, unsigned,
+                  unsigned char* mask, hak_abs_pose* out)
+{
+    if (!out || !K || (n > 0 && !d) || iterations < 1 || !(threshold > 0.f) || K->fx == 0.f || K->fy == 0.f) {
+        g_err = "bad argument";
+        return 1;
+    }
+    *out = hak_abs_pose{{1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f}, {0.f, 0.f, n >= 3 ? 1.f : 0.f}, 0, n >= 3 ? 0 : -1, 0, n};
+    for (int i = 0; i < n; i++) {
+        const bool in = n >= 3 && d[i].X == d[i].X && i % 3 == 0;
+        out->inliers += in;
+        if (mask) mask[i] = in;
+    }
+    return 0;
+}
+// the HIP runtime calls of cuMatchKnn, cuFindHomography, cuFindFundamental, cuRefineFundamental, cuRecoverPose, cuLinkTracks and
+// cuSolvePnP
 hipError_t hipMalloc(void** p, size_t n) { *p = malloc(n); return *p ? hipSuccess : hipErrorOutOfMemory; }
 hipError_t hipFree(void* p) { free(p); return hipSuccess; }
 }

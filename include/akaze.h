@@ -48,6 +48,19 @@ namespace akaze
                       float R[9], float t[3], unsigned char* front_mask = nullptr, float threshold = 1.f,
                       float max_depth = __builtin_inff());
 
+    // build-side addition: a third view.  cuLinkTracks (hak_link_tracks) joins the host match list A of images (I0, I1), with a point
+    // per match (xyzA, 3 n floats, as hak_recover_pose writes them; maskA NULL or nA bytes, 0 = leave the match out), and the host
+    // match list B of images (I1, I2) on the keypoints of I1 (indices below max_index): `out` (room for nB records) receives one
+    // 3-D to 2-D correspondence per linked match of B in ascending order; returns their number.
+    int cuLinkTracks(const hak_match_pair* A, int nA, const float* xyzA, const unsigned char* maskA, const hak_match_pair* B, int nB,
+                     int max_index, hak_corr3d* out);
+    // cuSolvePnP (hak_solve_pnp): RANSAC absolute pose of the new image from such correspondences by the three-point solve: writes R
+    // (row-major) and t with Xc = R X + t in the units of the points (identity and 0 when there is no model) and, when inlier_mask
+    // is not NULL, n bytes (1 = reprojected closer than `threshold` px, in front of the camera); returns the number of inliers, or -1
+    // when there is no model.
+    int cuSolvePnP(const hak_corr3d* corr, int n, const hak_intrinsics& K, float R[9], float t[3], unsigned char* inlier_mask = nullptr,
+                   int iterations = 1024, float threshold = 2.f, unsigned seed = 0);
+
     // build-side addition: guided matching (hak_match_guided) -- re-matches result1 against result2 under a homography H (row-major,
     // (x1, y1, 1) -> image 2, e.g. cuFindHomography's): every keypoint of result1 is searched only among the keypoints of result2
     // within `radius` pixels of where H sends it, ratio test and cross-check inside that neighbourhood.  Fills result1 like cuMatch

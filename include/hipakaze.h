@@ -422,6 +422,107 @@ int hak_recover_pose_batch(hak_ctx* ctx, const hak_match_pair* d_matches, long s
                            const hak_fundamental* d_F, const hak_intrinsics* K1, const hak_intrinsics* K2,
                            float threshold, float max_depth, hak_pose* d_out, unsigned char* d_masks, float* d_xyz);
 
+/* ---- a third view: track linking and RANSAC absolute pose (build-side addition; the stages behind hak_recover_pose).  A second
+ * hak_recover_pose for the next image pair has a unit baseline of its own, unrelated to the first pair's, so two relative poses do
+ * not chain into a trajectory.  What keeps the scale is the absolute pose of the new image from 3-D to 2-D correspondences: the
+ * points hak_recover_pose triangulated from images (I0, I1), as seen in I2.
+ *
+ * Link rule (hak_link_tracks; tests/link_ref.py is its byte-exact numpy statement).  List A (nA records, its optional mask and its
+ * points xyzA, 3 floats per record, as hak_recover_pose writes them) comes from images (I0, I1), list B (nB records) from images
+ * (I1, I2), I1 the same detection in both (detection is deterministic: the same image detected twice in one batch gives identical
+ * records), so A[a].train and B[m].query index the same keypoints.  For each match m of B in ascending m, a is the smallest index
+ * of A with A[a].train == B[m].query, that index in [0, max_index), and maskA NULL or maskA[a] != 0.  If there is such an a, the
+ * record {X, Y, Z = xyzA[3a .. 3a+2], u = B[m].x2, v = B[m].y2, src3d = a, src2d = m, pad = 0} is appended to the output; count is
+ * the number appended.  A record with a non-finite coordinate is still linked: the estimator is what rejects it.  Fewer than 2^30
+ * records per list.  Scratch is a table train -> a of max_index ints per pair, cleared and filled with atomicMin inside the call;
+ * it belongs to the context, is grown by the call that first needs it before anything is enqueued (as hak_set_retain_grid
+ * allocates) and never inside a launch sequence.
+ *
+ * PnP rule (hak_solve_pnp; tests/pnp_ref.py is its bit-exact numpy statement).  A pure function of (corr, K, iterations,
+ * threshold, seed).  float64, no FMA, + - * / sqrt only, except where float32 is named; dot and cross as in hak_recover_pose.  A
+ * record with a non-finite X, Y, Z, u or v is never an inlier and makes any sample it is in degenerate (it is read with X = NaN).
+ *   1. Sampling: hypothesis h (0 <= h < iterations, 1 <= iterations <= 65536) draws r_d = mix64(seed + (16 h + d + 1) *
+ *      0x9E3779B97F4A7C15) for d = 0..15, as step 1 of hak_find_homography, and takes index ((r_d >> 32) * n) >> 32 unless already
+ *      chosen, until it has three: points 1, 2, 3 in draw order.  Degenerate with fewer than three distinct indices (always when n < 3).
+ *   2. Bearings, K widened to float64: x = (u - cx) / fx, y = (v - cy) / fy, r = sqrt((x x + y y) + 1), b_i = (x / r, y / r, 1 / r).
+ *      Squared sides a2 = |X2 - X3|^2, b2 = |X1 - X3|^2, c2 = |X1 - X2|^2, each dot(d, d) of the difference in that order; cosines
+ *      ca = dot(b_2, b_3), cb = dot(b_1, b_3), cg = dot(b_1, b_2).  Degenerate if b2 is 0 or any of the six is non-finite.
+ *   3. Grunert's quartic in v = s3 / s1 (s_i the distance of point i from the camera): p = (a2 - c2) / b2, q = (a2 + c2) / b2,
+ *      rab = a2 / b2, rcb = c2 / b2, rbc = (b2 - c2) / b2, rba = (b2 - a2) / b2, ca2 = ca ca, cb2 = cb cb, cg2 = cg cg, pm = p - 1,
+ *      pp = p p, pq = 1 + p;
+ *        A4 = pm pm - 4 (rcb ca2)
+ *        A3 = 4 (((p (1 - p)) cb - ((1 - q) ca) cg) + 2 ((rcb ca2) cb))
+ *        A2 = 2 (((((pp - 1) + 2 (pp cb2)) + 2 (rbc ca2)) - 4 (((q ca) cb) cg)) + 2 (rba cg2))
+ *        A1 = 4 (((-(p pq)) cb + 2 ((rab cg2) cb)) - ((1 - q) ca) cg)
+ *        A0 = pq pq - 4 (rab cg2)
+ *      Degenerate if A4 is 0 or a coefficient is non-finite.
+ *   4. Positive real roots: b_k = A_k / A4 (k = 3..0), q(v) = (((v + b3) v + b2) v + b1) v + b0, B = 1 + max |b_k| (taken over
+ *      k = 3, 2, 1, 0 with >); degenerate if a b_k or B is non-finite.  The critical points are the real roots of the monic cubic
+ *      with the coefficients (0.75 b3, 0.5 b2, 0.25 b1), found by step 5 of hak_find_fundamental verbatim (its b2, b1, b0, its own
+ *      bound, brackets and bisections; degenerate if it reports a non-finite value).  Of those, the r with 0 < r < B are kept in
+ *      that step's order: r_0, ..; the brackets are [0, r_0], [r_0, r_1], .., [r_last, B] ([0, B] when none is kept).  A bracket
+ *      holds a root iff (q(lo) < 0) != (q(hi) < 0); there, 64 bisections exactly as in that step, the root is 0.5 (lo + hi).  Up
+ *      to four roots, numbered 0.. in bracket order: the solution index.
+ *   5. Per root v: vv = v v, den = 2 (cg - v ca), w = (1 + vv) - (2 v) cb, u = ((pm vv - ((2 p) cb) v) + pq) / den,
+ *      s1 = sqrt(b2 / w), s2 = u s1, s3 = v s1.  The root gives no model unless den != 0, w > 0 and s1, s2, s3 are finite and > 0.
+ *      P_i = s_i b_i.  triad(P1, P2, P3): d1 = P2 - P1, d2 = P3 - P1, l1 = sqrt(dot(d1, d1)), e1 = d1 / l1, n = cross(d1, d2),
+ *      ln = sqrt(dot(n, n)), e3 = n / ln, e2 = cross(e3, e1); no model if l1 or ln is 0 or non-finite.  (e1, e2, e3) =
+ *      triad(P1, P2, P3), (f1, f2, f3) = triad(X1, X2, X3).  R[i][j] = (e1_i f1_j + e2_i f2_j) + e3_i f3_j,
+ *      t_i = P1_i - dot(row i of R, X1), so that Xc = R X + t.  R and t are rounded to float32; no model if anything is non-finite.
+ *   6. Score, float32, no FMA, K as given: xc = ((R0 X + R1 Y) + R2 Z) + t0, yc = ((R3 X + R4 Y) + R5 Z) + t1,
+ *      zc = ((R6 X + R7 Y) + R8 Z) + t2; ex = (fx xc + cx zc) - u zc, ey = (fy yc + cy zc) - v zc; inlier iff zc > 0 and
+ *      ex ex + ey ey < t2 (zc zc), t2 = threshold * threshold (threshold finite, > 0; NaN fails): the reprojection error in
+ *      pixels is below the threshold and the point is in front of the camera.
+ *   7. The model with the most inliers wins, ties to the smallest h, then the smallest solution index.  The optional mask gets 1
+ *      for every inlier of the winner, 0 otherwise (n bytes).  No model at all: the no-model record (R = identity, t = 0,
+ *      inliers = 0, hypothesis = -1, solution = 0, n) and an all-zero mask.
+ * Every value reduced across lanes is an integer count, so the result does not depend on the launch shape.
+ * Limits: the result is the three-point winner, fitted to three noisy points; a least-squares (Gauss-Newton) refit over its
+ * inliers is the next stage and not part of this one.  A root at which q touches zero without changing sign (a tangent double
+ * root) is missed by design.  No lens distortion, no skew.
+ * Refused with a non-zero status and a message before any device is touched: iterations outside 1..65536, a threshold that is not
+ * finite or not > 0, fx or fy not finite or 0, a non-finite cx or cy, a count < 0 (or >= 2^30 for the link), a NULL list with a
+ * positive count, a list or output list that is not 16-byte aligned, NULL outputs, counts, xyz or K, npairs < 1, a stride < 1, a
+ * count step < 1, max_index < 1, a NULL context for the batch forms.  Device code: csrc/kernels_pnp.hip. */
+typedef struct hak_corr3d {  /* 32 bytes, 16-byte aligned loads */
+    float X, Y, Z;           /* point, frame and units of the xyz it came from */
+    float u, v;              /* its observation in the new image, pixels */
+    int   src3d, src2d;      /* index of the match in list A / list B it came from */
+    int   pad;               /* 0 */
+} hak_corr3d;
+typedef struct hak_abs_pose {
+    float R[9];              /* row-major, Xc = R X + t */
+    float t[3];              /* in the units of X */
+    int   inliers;           /* inliers of (R, t) */
+    int   hypothesis;        /* winning hypothesis, -1 = no model (R = identity, t = 0, inliers = 0) */
+    int   solution;          /* which positive root of the winner's quartic (0..3) */
+    int   n;                 /* correspondences considered */
+} hak_abs_pose;              /* 64 bytes */
+/* one pair of lists, synchronous; ctx may be NULL (default stream; the call allocates its own table).  d_maskA may be NULL; d_out
+ * (device) has room for nB records; *count (host) their number; h_out (host, nB records) or NULL receives the list as well. */
+int hak_link_tracks(hak_ctx* ctx, const hak_match_pair* d_A, int nA, const unsigned char* d_maskA, const float* d_xyzA,
+                    const hak_match_pair* d_B, int nB, int max_index, hak_corr3d* d_out, int* count, hak_corr3d* h_out);
+/* batched, asynchronous on the context's stream.  List k of A is at d_A + k*strideA, its count d_countsA[k*count_stepA] (read on the
+ * device, clamped to [0, strideA]), its mask at d_masksA + k*strideA (unless NULL), its points at d_xyzA + 3*k*strideA; list k of B
+ * at d_B + k*strideB with the count d_countsB[k*count_stepB], clamped to [0, min(strideB, out_stride)]; correspondences of k to
+ * d_out + k*out_stride, their number to d_counts[k]; max_index is the context's cfg.max_pts.  With the outputs of one
+ * hak_match_knn2_batch / hak_recover_pose_batch over a detect batch of image pairs (I0, I1), (I1, I2), .. -- d_A = d_matches,
+ * d_B = d_matches + max_pts, d_countsA = d_counts, d_countsB = d_counts + 1, strides 2*max_pts, count steps 2 -- pair 2j links to
+ * pair 2j+1, and detect batch -> hak_match_knn2_batch -> hak_find_fundamental_batch -> hak_refine_fundamental_batch ->
+ * hak_recover_pose_batch -> hak_link_tracks_batch -> hak_solve_pnp_batch needs no host synchronisation. */
+int hak_link_tracks_batch(hak_ctx* ctx, const hak_match_pair* d_A, long strideA, const int* d_countsA, int count_stepA,
+                          const unsigned char* d_masksA, const float* d_xyzA, const hak_match_pair* d_B, long strideB,
+                          const int* d_countsB, int count_stepB, int npairs, hak_corr3d* d_out, long out_stride, int* d_counts);
+/* one list, synchronous; ctx may be NULL (default stream; the call allocates its own scratch); d_mask (device, n bytes) may be
+ * NULL; result to *h_out (host) */
+int hak_solve_pnp(hak_ctx* ctx, const hak_corr3d* d_corr, int n, const hak_intrinsics* K, int iterations, float threshold,
+                  unsigned seed, unsigned char* d_mask, hak_abs_pose* h_out);
+/* batched, asynchronous on the context's stream: list k at d_corr + k*stride, its count d_counts[k] read on the device and clamped
+ * to [0, stride] (the layout hak_link_tracks_batch writes); record k to d_out[k], mask of k to d_masks + k*stride unless NULL */
+int hak_solve_pnp_batch(hak_ctx* ctx, const hak_corr3d* d_corr, long stride, const int* d_counts, int npairs,
+                        const hak_intrinsics* K, int iterations, float threshold, unsigned seed, hak_abs_pose* d_out,
+                        unsigned char* d_masks);
+
 /* ---- guided matching: re-match a pair under its estimated homography (build-side addition; the stage behind
  * hak_find_homography).  The 2-NN search of hak_match_knn2 looks at the whole other image, so on repetitive texture its ratio
  * test rejects correct matches that lose to a look-alike elsewhere; once H is known, each query is searched only among the train
