@@ -324,7 +324,7 @@ extern "C" void hak_destroy(hak_ctx* c)
         for (auto ev : p.ev) (void)hipEventDestroy(ev);
     hak_match_scratch_free(&c->msc);
     void* bufs[] = {c->arena, c->maps, c->bitmap, c->rowcount, c->cand, c->state, c->d_num, c->dtab, c->knn, c->d_cnt, c->perm, c->pair_pts,
-                    c->hom_slots, c->hom_rec, c->fund_models, c->fund_rec, c->pnp_models, c->pnp_rec, c->link_tab, c->sel.st, c->sel.bins, c->sel.tie, c->grid.st, c->grid.count, c->grid.comp, c->guided};
+                    c->ransac_slots, c->ransac_models, c->geom_rec, c->link_tab, c->sel.st, c->sel.bins, c->sel.tie, c->grid.st, c->grid.count, c->grid.comp, c->guided};
     for (void* b : bufs) (void)hipFree(b);
     if (c->h_num) (void)hipHostFree(c->h_num);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -680,8 +680,30 @@ extern "C" int hak_match_knn2_batch(hak_ctx* c, hak_point* d_points, const int* 
     return 0;
 }
 
-// ----------------------------------------------------------- geometric verification: RANSAC homography (kernels_homography.hip)
-static int homography_args(int iterations, float threshold, int refine)
+// ----------------------------------------------------------- geometric verification: what its entry points share
+static bool misaligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
+
+// the list of a single call / the lists of a batch call; `unaligned`, and for the batch forms that tell them apart `no_ctx`, `null`
+// and `shape`, are the call's own messages
+static int list_args(const void* h_out, const void* d_list, int n, const char* unaligned)
+{
+    if (!h_out || (!d_list && n > 0)) return fail("null argument");
+    if (n < 0) return fail("n < 0");
+    if (misaligned16(d_list)) return fail(unaligned);
+    return 0;
+}
+static int list_args_batch(const hak_ctx* c, const void* d_list, const int* d_counts, const void* d_out, int npairs, long stride,
+                           const char* unaligned, const char* no_ctx = "bad argument", const char* null = "bad argument",
+                           const char* shape = "bad argument")
+{
+    if (!c) return fail(no_ctx);
+    if (!d_list || !d_counts || !d_out) return fail(null);
+    if (npairs < 1 || stride < 1) return fail(shape);
+    if (misaligned16(d_list)) return fail(unaligned);
+    return 0;
+}
+
+static int ransac_args(int iterations, float threshold, int refine)
 {
     if (iterations < 1 || iterations > 65536) return fail("iterations must be in 1 .. 65536");
     if (!std::isfinite(threshold) || !(threshold > 0.f)) return fail("threshold must be finite and > 0");
@@ -689,130 +711,124 @@ static int homography_args(int iterations, float threshold, int refine)
     return 0;
 }
 
-// grow-only; a buffer being replaced may still be read by an earlier call on the context's stream (hipFree waits for the device)
-static int homography_scratch(hak_ctx* c, long slots)
+static int intrinsics_args(const hak_intrinsics* K)
 {
-    if (slots > c->hom_cap) {
-        if (c->hom_slots) HIP_TRY(hipFree(c->hom_slots));
-        c->hom_slots = nullptr;
-        c->hom_cap = 0;
-        HIP_TRY(hipMalloc((void**)&c->hom_slots, sizeof(unsigned long long) * (size_t)slots));
-        c->hom_cap = slots;
-    }
-    if (!c->hom_rec) HIP_TRY(hipMalloc((void**)&c->hom_rec, sizeof(hak_homography)));
+    if (!K) return fail("null intrinsics");
+    if (!std::isfinite(K->fx) || !std::isfinite(K->fy) || K->fx == 0.f || K->fy == 0.f) return fail("fx and fy must be finite and non-zero");
+    if (!std::isfinite(K->cx) || !std::isfinite(K->cy)) return fail("cx and cy must be finite");
     return 0;
 }
 
+// a context's buffer of `need` elements, grow-only and outside a launch sequence; a buffer being replaced may still be read by an
+// earlier call on the context's stream (hipFree waits for the device)
+template <typename T>
+static int grow_scratch(T*& p, long& cap, long need, size_t elem = sizeof(T))
+{
+    if (need <= cap) return 0;
+    if (p) HIP_TRY(hipFree(p));
+    p = nullptr;
+    cap = 0;
+    HIP_TRY(hipMalloc((void**)&p, elem * (size_t)need));
+    cap = need;
+    return 0;
+}
+
+#define HAK_REC_BYTES 64         // room for the largest record (hak_abs_pose); hak_link_tracks' count follows it
+static int geom_record(hak_ctx* c)
+{
+    if (!c->geom_rec) HIP_TRY(hipMalloc((void**)&c->geom_rec, HAK_REC_BYTES + 16));
+    return 0;
+}
+
+// the scratch of one RANSAC call (words = 0: no models kernel): the context's, or without a context one block slots | record | models
+// that single_tail frees
+struct RansacScratch { unsigned long long* slots = nullptr; void* rec = nullptr; unsigned* models = nullptr; void* block = nullptr; };
+static int ransac_scratch(hak_ctx* c, long slots, long words, RansacScratch& s)
+{
+    if (c) {
+        if (grow_scratch(c->ransac_slots, c->ransac_slots_cap, slots) || grow_scratch(c->ransac_models, c->ransac_models_cap, words) ||
+            geom_record(c))
+            return 1;
+        s.slots = c->ransac_slots; s.rec = c->geom_rec; s.models = c->ransac_models;
+        return 0;
+    }
+    char* p = nullptr;
+    HIP_TRY(hipMalloc((void**)&p, sizeof(unsigned long long) * (size_t)slots + HAK_REC_BYTES + sizeof(unsigned) * (size_t)words));
+    s.block = s.slots = reinterpret_cast<unsigned long long*>(p);
+    s.rec = p + sizeof(unsigned long long) * (size_t)slots;
+    s.models = reinterpret_cast<unsigned*>(p + sizeof(unsigned long long) * (size_t)slots + HAK_REC_BYTES);
+    return 0;
+}
+
+// the end of a single call after its launches (rc: what went wrong before them): launch error, sync, download of `bytes` from d_rec
+// to h_out, release of the call's own block
+static int single_tail(int rc, hipStream_t st, const std::string& what, const char* download, void* h_out, const void* d_rec,
+                       size_t bytes, void* block = nullptr)
+{
+    if (!rc && hipGetLastError() != hipSuccess) rc = fail(what + " launch failed");
+    if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = fail("hipStreamSynchronize(" + what + ")");
+    if (!rc && hipMemcpy(h_out, d_rec, bytes, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(download);
+    if (block) (void)hipFree(block);
+    return rc;
+}
+
+// ----------------------------------------------------------- RANSAC homography (kernels_homography.hip)
 extern "C" int hak_find_homography(hak_ctx* c, const hak_match_pair* d_matches, int n, int iterations, float threshold,
                                    unsigned seed, int refine, unsigned char* d_mask, hak_homography* h_out)
 {
-    if (!h_out || (!d_matches && n > 0)) return fail("null argument");
-    if (n < 0) return fail("n < 0");
-    if ((reinterpret_cast<uintptr_t>(d_matches) & 15) != 0) return fail("d_matches must be 16-byte aligned");
-    if (homography_args(iterations, threshold, refine)) return 1;
+    if (list_args(h_out, d_matches, n, "d_matches must be 16-byte aligned") || ransac_args(iterations, threshold, refine)) return 1;
     if (hak_device_count() == 0) return fail("no HIP device: libhipakaze has no CPU fallback");
-    const long slots = hak_homography_blocks(1, iterations, nullptr);
-    unsigned long long* d_slots = nullptr;
-    hak_homography* d_rec = nullptr;
-    if (c) {
-        if (homography_scratch(c, slots)) return 1;
-        d_slots = c->hom_slots;
-        d_rec = c->hom_rec;
-    } else {
-        HIP_TRY(hipMalloc((void**)&d_slots, sizeof(unsigned long long) * (size_t)slots));
-        if (hipMalloc((void**)&d_rec, sizeof(hak_homography)) != hipSuccess) { (void)hipFree(d_slots); return fail("hipMalloc"); }
-    }
+    RansacScratch s;
+    if (ransac_scratch(c, hak_homography_blocks(1, iterations, nullptr), 0, s)) return 1;
     hipStream_t st = c ? c->stream : nullptr;
     order_after_null_stream(c, st);
-    hak_launch_homography(st, d_matches, n, nullptr, n, 1, iterations, threshold, seed, refine, d_slots, d_rec, d_mask, 0);
-    int rc = 0;
-    if (hipGetLastError() != hipSuccess) rc = fail("homography launch failed");
-    if (!rc && hipStreamSynchronize(st) != hipSuccess) rc = fail("hipStreamSynchronize(homography)");
-    if (!rc && hipMemcpy(h_out, d_rec, sizeof(hak_homography), hipMemcpyDeviceToHost) != hipSuccess) rc = fail("homography download");
-    if (!c) { (void)hipFree(d_slots); (void)hipFree(d_rec); }
-    return rc;
+    hak_launch_homography(st, d_matches, n > 0 ? n : 1, nullptr, n, 1, iterations, threshold, seed, refine, s.slots,
+                          static_cast<hak_homography*>(s.rec), d_mask, 0);
+    return single_tail(0, st, "homography", "homography download", h_out, s.rec, sizeof(hak_homography), s.block);
 }
 
 extern "C" int hak_find_homography_batch(hak_ctx* c, const hak_match_pair* d_matches, long stride, const int* d_counts, int npairs,
                                          int iterations, float threshold, unsigned seed, int refine, hak_homography* d_out,
                                          unsigned char* d_masks)
 {
-    if (!c || !d_matches || !d_counts || !d_out || npairs < 1 || stride < 1) return fail("bad argument");
-    if ((reinterpret_cast<uintptr_t>(d_matches) & 15) != 0) return fail("d_matches must be 16-byte aligned");
-    if (homography_args(iterations, threshold, refine)) return 1;
-    if (homography_scratch(c, (long)npairs * hak_homography_blocks(npairs, iterations, nullptr))) return 1;
+    if (list_args_batch(c, d_matches, d_counts, d_out, npairs, stride, "d_matches must be 16-byte aligned")) return 1;
+    if (ransac_args(iterations, threshold, refine)) return 1;
+    RansacScratch s;
+    if (ransac_scratch(c, (long)npairs * hak_homography_blocks(npairs, iterations, nullptr), 0, s)) return 1;
     order_after_null_stream(c, c->stream);
-    hak_launch_homography(c->stream, d_matches, stride, d_counts, 0, npairs, iterations, threshold, seed, refine, c->hom_slots, d_out,
+    hak_launch_homography(c->stream, d_matches, stride, d_counts, 0, npairs, iterations, threshold, seed, refine, s.slots, d_out,
                           d_masks, stride);
     if (hipGetLastError() != hipSuccess) return fail("homography launch failed");
     return 0;
 }
 
 // ----------------------------------------------------------- RANSAC fundamental matrix (kernels_fundamental.hip)
-// grow-only, outside a launch sequence, as homography_scratch (whose slots it shares)
-static int fundamental_scratch(hak_ctx* c, long slots, long words)
-{
-    if (homography_scratch(c, slots)) return 1;
-    if (words > c->fund_cap) {
-        if (c->fund_models) HIP_TRY(hipFree(c->fund_models));
-        c->fund_models = nullptr;
-        c->fund_cap = 0;
-        HIP_TRY(hipMalloc((void**)&c->fund_models, sizeof(unsigned) * (size_t)words));
-        c->fund_cap = words;
-    }
-    if (!c->fund_rec) HIP_TRY(hipMalloc((void**)&c->fund_rec, sizeof(hak_fundamental)));
-    return 0;
-}
-
 extern "C" int hak_find_fundamental(hak_ctx* c, const hak_match_pair* d_matches, int n, int iterations, float threshold,
                                     unsigned seed, unsigned char* d_mask, hak_fundamental* h_out)
 {
-    if (!h_out || (!d_matches && n > 0)) return fail("null argument");
-    if (n < 0) return fail("n < 0");
-    if ((reinterpret_cast<uintptr_t>(d_matches) & 15) != 0) return fail("d_matches must be 16-byte aligned");
-    if (homography_args(iterations, threshold, 0)) return 1;
+    if (list_args(h_out, d_matches, n, "d_matches must be 16-byte aligned") || ransac_args(iterations, threshold, 0)) return 1;
     if (hak_device_count() == 0) return fail("no HIP device: libhipakaze has no CPU fallback");
-    const long slots = hak_homography_blocks(1, iterations, nullptr), words = hak_fundamental_words(1, iterations);
-    unsigned long long* d_slots = nullptr;
-    unsigned* d_models = nullptr;
-    hak_fundamental* d_rec = nullptr;
-    if (c) {
-        if (fundamental_scratch(c, slots, words)) return 1;
-        d_slots = c->hom_slots;
-        d_models = c->fund_models;
-        d_rec = c->fund_rec;
-    } else {
-        // one allocation: slots | record (64 bytes) | models
-        char* p = nullptr;
-        HIP_TRY(hipMalloc((void**)&p, sizeof(unsigned long long) * (size_t)slots + 64 + sizeof(unsigned) * (size_t)words));
-        d_slots = reinterpret_cast<unsigned long long*>(p);
-        d_rec = reinterpret_cast<hak_fundamental*>(p + sizeof(unsigned long long) * (size_t)slots);
-        d_models = reinterpret_cast<unsigned*>(p + sizeof(unsigned long long) * (size_t)slots + 64);
-    }
+    RansacScratch s;
+    if (ransac_scratch(c, hak_homography_blocks(1, iterations, nullptr), hak_fundamental_words(1, iterations), s)) return 1;
     hipStream_t st = c ? c->stream : nullptr;
     order_after_null_stream(c, st);
-    hak_launch_fundamental(st, d_matches, n, nullptr, n, 1, iterations, threshold, seed, d_models, d_slots, d_rec, d_mask, 0);
-    int rc = 0;
-    if (hipGetLastError() != hipSuccess) rc = fail("fundamental launch failed");
-    if (!rc && hipStreamSynchronize(st) != hipSuccess) rc = fail("hipStreamSynchronize(fundamental)");
-    if (!rc && hipMemcpy(h_out, d_rec, sizeof(hak_fundamental), hipMemcpyDeviceToHost) != hipSuccess) rc = fail("fundamental download");
-    if (!c) (void)hipFree(d_slots);
-    return rc;
+    hak_launch_fundamental(st, d_matches, n > 0 ? n : 1, nullptr, n, 1, iterations, threshold, seed, s.models, s.slots,
+                           static_cast<hak_fundamental*>(s.rec), d_mask, 0);
+    return single_tail(0, st, "fundamental", "fundamental download", h_out, s.rec, sizeof(hak_fundamental), s.block);
 }
 
 extern "C" int hak_find_fundamental_batch(hak_ctx* c, const hak_match_pair* d_matches, long stride, const int* d_counts, int npairs,
                                           int iterations, float threshold, unsigned seed, hak_fundamental* d_out,
                                           unsigned char* d_masks)
 {
-    if (!c || !d_matches || !d_counts || !d_out || npairs < 1 || stride < 1) return fail("bad argument");
-    if ((reinterpret_cast<uintptr_t>(d_matches) & 15) != 0) return fail("d_matches must be 16-byte aligned");
-    if (homography_args(iterations, threshold, 0)) return 1;
-    if (fundamental_scratch(c, (long)npairs * hak_homography_blocks(npairs, iterations, nullptr),
-                            hak_fundamental_words(npairs, iterations)))
+    if (list_args_batch(c, d_matches, d_counts, d_out, npairs, stride, "d_matches must be 16-byte aligned")) return 1;
+    if (ransac_args(iterations, threshold, 0)) return 1;
+    RansacScratch s;
+    if (ransac_scratch(c, (long)npairs * hak_homography_blocks(npairs, iterations, nullptr), hak_fundamental_words(npairs, iterations), s))
         return 1;
     order_after_null_stream(c, c->stream);
-    hak_launch_fundamental(c->stream, d_matches, stride, d_counts, 0, npairs, iterations, threshold, seed, c->fund_models,
-                           c->hom_slots, d_out, d_masks, stride);
+    hak_launch_fundamental(c->stream, d_matches, stride, d_counts, 0, npairs, iterations, threshold, seed, s.models, s.slots, d_out,
+                           d_masks, stride);
     if (hipGetLastError() != hipSuccess) return fail("fundamental launch failed");
     return 0;
 }
@@ -828,10 +844,7 @@ static int refine_args(float threshold, int rounds)
 extern "C" int hak_refine_fundamental(hak_ctx* c, const hak_match_pair* d_matches, int n, float threshold, int rounds,
                                       unsigned char* d_mask, hak_fundamental* h_inout)
 {
-    if (!h_inout || (!d_matches && n > 0)) return fail("null argument");
-    if (n < 0) return fail("n < 0");
-    if ((reinterpret_cast<uintptr_t>(d_matches) & 15) != 0) return fail("d_matches must be 16-byte aligned");
-    if (refine_args(threshold, rounds)) return 1;
+    if (list_args(h_inout, d_matches, n, "d_matches must be 16-byte aligned") || refine_args(threshold, rounds)) return 1;
     if (hak_device_count() == 0) return fail("no HIP device: libhipakaze has no CPU fallback");
     // no scratch.  The record's device copy is the context's, or without a context a device global that calls take in turn:
     // nothing is allocated
@@ -839,8 +852,8 @@ extern "C" int hak_refine_fundamental(hak_ctx* c, const hak_match_pair* d_matche
     std::unique_lock<std::mutex> turn(null_ctx_record, std::defer_lock);
     hak_fundamental* d_rec = nullptr;
     if (c) {
-        if (!c->fund_rec) HIP_TRY(hipMalloc((void**)&c->fund_rec, sizeof(hak_fundamental)));
-        d_rec = c->fund_rec;
+        if (geom_record(c)) return 1;
+        d_rec = reinterpret_cast<hak_fundamental*>(c->geom_rec);
     } else {
         turn.lock();
         d_rec = hak_fundamental_refit_record();
@@ -850,21 +863,15 @@ extern "C" int hak_refine_fundamental(hak_ctx* c, const hak_match_pair* d_matche
     order_after_null_stream(c, st);
     int rc = 0;
     if (hipMemcpyAsync(d_rec, h_inout, sizeof(hak_fundamental), hipMemcpyHostToDevice, st) != hipSuccess) rc = fail("record upload");
-    if (!rc) {
-        hak_launch_fundamental_refit(st, d_matches, n, nullptr, n, 1, threshold, rounds, d_rec, d_mask, 0);
-        if (hipGetLastError() != hipSuccess) rc = fail("fundamental refit launch failed");
-    }
-    if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = fail("hipStreamSynchronize(fundamental refit)");
-    if (!rc && hipMemcpy(h_inout, d_rec, sizeof(hak_fundamental), hipMemcpyDeviceToHost) != hipSuccess) rc = fail("record download");
-    return rc;
+    if (!rc) hak_launch_fundamental_refit(st, d_matches, n, nullptr, n, 1, threshold, rounds, d_rec, d_mask, 0);
+    return single_tail(rc, st, "fundamental refit", "record download", h_inout, d_rec, sizeof(hak_fundamental));
 }
 
 extern "C" int hak_refine_fundamental_batch(hak_ctx* c, const hak_match_pair* d_matches, long stride, const int* d_counts,
                                             int npairs, float threshold, int rounds, hak_fundamental* d_inout,
                                             unsigned char* d_masks)
 {
-    if (!c || !d_matches || !d_counts || !d_inout || npairs < 1 || stride < 1) return fail("bad argument");
-    if ((reinterpret_cast<uintptr_t>(d_matches) & 15) != 0) return fail("d_matches must be 16-byte aligned");
+    if (list_args_batch(c, d_matches, d_counts, d_inout, npairs, stride, "d_matches must be 16-byte aligned")) return 1;
     if (refine_args(threshold, rounds)) return 1;
     order_after_null_stream(c, c->stream);
     hak_launch_fundamental_refit(c->stream, d_matches, stride, d_counts, 0, npairs, threshold, rounds, d_inout, d_masks, stride);
@@ -878,21 +885,14 @@ static int pose_args(const hak_intrinsics* K1, const hak_intrinsics* K2, float t
     if (!K1 || !K2) return fail("null intrinsics");
     if (!std::isfinite(threshold) || !(threshold > 0.f)) return fail("threshold must be finite and > 0");
     if (!(max_depth > 0.f)) return fail("max_depth must be > 0 (+inf allowed)");
-    for (const hak_intrinsics* K : {K1, K2}) {
-        if (!std::isfinite(K->fx) || !std::isfinite(K->fy) || K->fx == 0.f || K->fy == 0.f)
-            return fail("fx and fy must be finite and non-zero");
-        if (!std::isfinite(K->cx) || !std::isfinite(K->cy)) return fail("cx and cy must be finite");
-    }
-    return 0;
+    return intrinsics_args(K1) || intrinsics_args(K2);
 }
 
 extern "C" int hak_recover_pose(hak_ctx* c, const hak_match_pair* d_matches, int n, const float F[9], const hak_intrinsics* K1,
                                 const hak_intrinsics* K2, float threshold, float max_depth, unsigned char* d_mask, float* d_xyz,
                                 hak_pose* h_out)
 {
-    if (!h_out || !F || (!d_matches && n > 0)) return fail("null argument");
-    if (n < 0) return fail("n < 0");
-    if ((reinterpret_cast<uintptr_t>(d_matches) & 15) != 0) return fail("d_matches must be 16-byte aligned");
+    if (list_args(F ? h_out : nullptr, d_matches, n, "d_matches must be 16-byte aligned")) return 1;
     if (pose_args(K1, K2, threshold, max_depth)) return 1;
     if (hak_device_count() == 0) return fail("no HIP device: libhipakaze has no CPU fallback");
     // no scratch.  The record's device copy is a device global that calls take in turn: nothing is allocated
@@ -902,20 +902,15 @@ extern "C" int hak_recover_pose(hak_ctx* c, const hak_match_pair* d_matches, int
     if (!d_rec) return fail("hipGetSymbolAddress(pose record)");
     hipStream_t st = c ? c->stream : nullptr;
     order_after_null_stream(c, st);
-    int rc = 0;
     hak_launch_pose(st, d_matches, n > 0 ? n : 1, nullptr, n, 1, nullptr, F, *K1, *K2, threshold, max_depth, d_rec, d_mask, d_xyz);
-    if (hipGetLastError() != hipSuccess) rc = fail("pose launch failed");
-    if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = fail("hipStreamSynchronize(pose)");
-    if (!rc && hipMemcpy(h_out, d_rec, sizeof(hak_pose), hipMemcpyDeviceToHost) != hipSuccess) rc = fail("record download");
-    return rc;
+    return single_tail(0, st, "pose", "record download", h_out, d_rec, sizeof(hak_pose));
 }
 
 extern "C" int hak_recover_pose_batch(hak_ctx* c, const hak_match_pair* d_matches, long stride, const int* d_counts, int npairs,
                                       const hak_fundamental* d_F, const hak_intrinsics* K1, const hak_intrinsics* K2,
                                       float threshold, float max_depth, hak_pose* d_out, unsigned char* d_masks, float* d_xyz)
 {
-    if (!c || !d_matches || !d_counts || !d_F || !d_out || npairs < 1 || stride < 1) return fail("bad argument");
-    if ((reinterpret_cast<uintptr_t>(d_matches) & 15) != 0) return fail("d_matches must be 16-byte aligned");
+    if (list_args_batch(c, d_matches, d_counts, d_F ? d_out : nullptr, npairs, stride, "d_matches must be 16-byte aligned")) return 1;
     if (pose_args(K1, K2, threshold, max_depth)) return 1;
     order_after_null_stream(c, c->stream);
     hak_launch_pose(c->stream, d_matches, stride, d_counts, 0, npairs, d_F, nullptr, *K1, *K2, threshold, max_depth, d_out, d_masks,
@@ -925,40 +920,6 @@ extern "C" int hak_recover_pose_batch(hak_ctx* c, const hak_match_pair* d_matche
 }
 
 // ----------------------------------------------------------- track linking and RANSAC absolute pose (kernels_pnp.hip)
-// grow-only and outside a launch sequence, as homography_scratch; words = 0 / entries = 0: that part is not needed
-static int pnp_scratch(hak_ctx* c, long slots, long words, long entries)
-{
-    if (slots > 0 && homography_scratch(c, slots)) return 1;
-    if (words > c->pnp_cap) {
-        if (c->pnp_models) HIP_TRY(hipFree(c->pnp_models));
-        c->pnp_models = nullptr;
-        c->pnp_cap = 0;
-        HIP_TRY(hipMalloc((void**)&c->pnp_models, sizeof(unsigned) * (size_t)words));
-        c->pnp_cap = words;
-    }
-    if (entries > c->link_cap) {
-        if (c->link_tab) HIP_TRY(hipFree(c->link_tab));
-        c->link_tab = nullptr;
-        c->link_cap = 0;
-        HIP_TRY(hipMalloc((void**)&c->link_tab, sizeof(int) * (size_t)entries));
-        c->link_cap = entries;
-    }
-    if (!c->pnp_rec) HIP_TRY(hipMalloc((void**)&c->pnp_rec, 80));
-    return 0;
-}
-
-static int pnp_args(const hak_intrinsics* K, int iterations, float threshold)
-{
-    if (!K) return fail("null intrinsics");
-    if (homography_args(iterations, threshold, 0)) return 1;
-    if (!std::isfinite(K->fx) || !std::isfinite(K->fy) || K->fx == 0.f || K->fy == 0.f)
-        return fail("fx and fy must be finite and non-zero");
-    if (!std::isfinite(K->cx) || !std::isfinite(K->cy)) return fail("cx and cy must be finite");
-    return 0;
-}
-
-static bool misaligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
-
 extern "C" int hak_link_tracks(hak_ctx* c, const hak_match_pair* d_A, int nA, const unsigned char* d_maskA, const float* d_xyzA,
                                const hak_match_pair* d_B, int nB, int max_index, hak_corr3d* d_out, int* count, hak_corr3d* h_out)
 {
@@ -969,29 +930,25 @@ extern "C" int hak_link_tracks(hak_ctx* c, const hak_match_pair* d_A, int nA, co
     if (hak_device_count() == 0) return fail("no HIP device: libhipakaze has no CPU fallback");
     int* d_tab = nullptr;
     int* d_cnt = nullptr;
+    char* block = nullptr;
     if (c) {
-        if (pnp_scratch(c, 0, 0, max_index)) return 1;
+        if (grow_scratch(c->link_tab, c->link_cap, max_index) || geom_record(c)) return 1;
         d_tab = c->link_tab;
-        d_cnt = reinterpret_cast<int*>(c->pnp_rec + 64);
+        d_cnt = reinterpret_cast<int*>(c->geom_rec + HAK_REC_BYTES);
     } else {
         // one allocation: count (16 bytes) | table
-        char* p = nullptr;
-        HIP_TRY(hipMalloc((void**)&p, 16 + sizeof(int) * (size_t)max_index));
-        d_cnt = reinterpret_cast<int*>(p);
-        d_tab = reinterpret_cast<int*>(p + 16);
+        HIP_TRY(hipMalloc((void**)&block, 16 + sizeof(int) * (size_t)max_index));
+        d_cnt = reinterpret_cast<int*>(block);
+        d_tab = reinterpret_cast<int*>(block + 16);
     }
     hipStream_t st = c ? c->stream : nullptr;
     order_after_null_stream(c, st);
     hak_launch_link(st, d_A, nA > 0 ? nA : 1, nullptr, 1, nA, d_maskA, d_xyzA, d_B, nB > 0 ? nB : 1, nullptr, 1, nB, 1, max_index, d_tab,
                     d_out, nB > 0 ? nB : 1, d_cnt);
-    int rc = 0;
-    if (hipGetLastError() != hipSuccess) rc = fail("link launch failed");
-    if (!rc && hipStreamSynchronize(st) != hipSuccess) rc = fail("hipStreamSynchronize(link)");
-    if (!rc && hipMemcpy(count, d_cnt, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) rc = fail("count download");
+    int rc = single_tail(0, st, "link", "count download", count, d_cnt, sizeof(int), block);
     if (!rc && h_out && *count > 0 &&
         hipMemcpy(h_out, d_out, sizeof(hak_corr3d) * (size_t)*count, hipMemcpyDeviceToHost) != hipSuccess)
         rc = fail("list download");
-    if (!c) (void)hipFree(d_cnt);
     return rc;
 }
 
@@ -1006,7 +963,7 @@ extern "C" int hak_link_tracks_batch(hak_ctx* c, const hak_match_pair* d_A, long
         return fail("npairs, the strides and the count steps must be >= 1");
     if (misaligned16(d_A) || misaligned16(d_B) || misaligned16(d_out)) return fail("the lists must be 16-byte aligned");
     if (c->cfg.max_pts < 1) return fail("max_index < 1");
-    if (pnp_scratch(c, 0, 0, (long)npairs * c->cfg.max_pts)) return 1;
+    if (grow_scratch(c->link_tab, c->link_cap, (long)npairs * c->cfg.max_pts)) return 1;
     order_after_null_stream(c, c->stream);
     hak_launch_link(c->stream, d_A, strideA, d_countsA, count_stepA, 0, d_masksA, d_xyzA, d_B, strideB, d_countsB, count_stepB, 0,
                     npairs, c->cfg.max_pts, c->link_tab, d_out, out_stride, d_counts);
@@ -1014,56 +971,39 @@ extern "C" int hak_link_tracks_batch(hak_ctx* c, const hak_match_pair* d_A, long
     return 0;
 }
 
+static int pnp_args(const hak_intrinsics* K, int iterations, float threshold)
+{
+    if (!K) return fail("null intrinsics");
+    return ransac_args(iterations, threshold, 0) || intrinsics_args(K);
+}
+
 extern "C" int hak_solve_pnp(hak_ctx* c, const hak_corr3d* d_corr, int n, const hak_intrinsics* K, int iterations, float threshold,
                              unsigned seed, unsigned char* d_mask, hak_abs_pose* h_out)
 {
-    if (!h_out || (!d_corr && n > 0)) return fail("null argument");
-    if (n < 0) return fail("n < 0");
-    if (misaligned16(d_corr)) return fail("d_corr must be 16-byte aligned");
-    if (pnp_args(K, iterations, threshold)) return 1;
+    if (list_args(h_out, d_corr, n, "d_corr must be 16-byte aligned") || pnp_args(K, iterations, threshold)) return 1;
     if (hak_device_count() == 0) return fail("no HIP device: libhipakaze has no CPU fallback");
-    const long slots = hak_homography_blocks(1, iterations, nullptr), words = hak_pnp_words(1, iterations);
-    unsigned long long* d_slots = nullptr;
-    unsigned* d_models = nullptr;
-    hak_abs_pose* d_rec = nullptr;
-    if (c) {
-        if (pnp_scratch(c, slots, words, 0)) return 1;
-        d_slots = c->hom_slots;
-        d_models = c->pnp_models;
-        d_rec = reinterpret_cast<hak_abs_pose*>(c->pnp_rec);
-    } else {
-        // one allocation: slots | record (64 bytes) | models
-        char* p = nullptr;
-        HIP_TRY(hipMalloc((void**)&p, sizeof(unsigned long long) * (size_t)slots + 64 + sizeof(unsigned) * (size_t)words));
-        d_slots = reinterpret_cast<unsigned long long*>(p);
-        d_rec = reinterpret_cast<hak_abs_pose*>(p + sizeof(unsigned long long) * (size_t)slots);
-        d_models = reinterpret_cast<unsigned*>(p + sizeof(unsigned long long) * (size_t)slots + 64);
-    }
+    RansacScratch s;
+    if (ransac_scratch(c, hak_homography_blocks(1, iterations, nullptr), hak_pnp_words(1, iterations), s)) return 1;
     hipStream_t st = c ? c->stream : nullptr;
     order_after_null_stream(c, st);
-    hak_launch_pnp(st, d_corr, n > 0 ? n : 1, nullptr, n, 1, *K, iterations, threshold, seed, d_models, d_slots, d_rec, d_mask, 0);
-    int rc = 0;
-    if (hipGetLastError() != hipSuccess) rc = fail("pnp launch failed");
-    if (!rc && hipStreamSynchronize(st) != hipSuccess) rc = fail("hipStreamSynchronize(pnp)");
-    if (!rc && hipMemcpy(h_out, d_rec, sizeof(hak_abs_pose), hipMemcpyDeviceToHost) != hipSuccess) rc = fail("pnp download");
-    if (!c) (void)hipFree(d_slots);
-    return rc;
+    hak_launch_pnp(st, d_corr, n > 0 ? n : 1, nullptr, n, 1, *K, iterations, threshold, seed, s.models, s.slots,
+                   static_cast<hak_abs_pose*>(s.rec), d_mask, 0);
+    return single_tail(0, st, "pnp", "pnp download", h_out, s.rec, sizeof(hak_abs_pose), s.block);
 }
 
 extern "C" int hak_solve_pnp_batch(hak_ctx* c, const hak_corr3d* d_corr, long stride, const int* d_counts, int npairs,
                                    const hak_intrinsics* K, int iterations, float threshold, unsigned seed, hak_abs_pose* d_out,
                                    unsigned char* d_masks)
 {
-    if (!c) return fail("null context");
-    if (!d_corr || !d_counts || !d_out) return fail("null argument");
-    if (npairs < 1 || stride < 1) return fail("npairs and the stride must be >= 1");
-    if (misaligned16(d_corr)) return fail("d_corr must be 16-byte aligned");
-    if (pnp_args(K, iterations, threshold)) return 1;
-    if (pnp_scratch(c, (long)npairs * hak_homography_blocks(npairs, iterations, nullptr), hak_pnp_words(npairs, iterations), 0))
+    if (list_args_batch(c, d_corr, d_counts, d_out, npairs, stride, "d_corr must be 16-byte aligned", "null context", "null argument",
+                        "npairs and the stride must be >= 1"))
         return 1;
+    if (pnp_args(K, iterations, threshold)) return 1;
+    RansacScratch s;
+    if (ransac_scratch(c, (long)npairs * hak_homography_blocks(npairs, iterations, nullptr), hak_pnp_words(npairs, iterations), s)) return 1;
     order_after_null_stream(c, c->stream);
-    hak_launch_pnp(c->stream, d_corr, stride, d_counts, 0, npairs, *K, iterations, threshold, seed, c->pnp_models, c->hom_slots, d_out,
-                   d_masks, stride);
+    hak_launch_pnp(c->stream, d_corr, stride, d_counts, 0, npairs, *K, iterations, threshold, seed, s.models, s.slots, d_out, d_masks,
+                   stride);
     if (hipGetLastError() != hipSuccess) return fail("pnp launch failed");
     return 0;
 }
@@ -1077,18 +1017,7 @@ static int guided_args(float radius, int ratio_num, int ratio_den)
     return 0;
 }
 
-// grow-only, outside a launch sequence; a buffer being replaced may still be read by an earlier call on the context's stream
-// (hipFree waits for the device)
-static int guided_scratch(hak_ctx* c, size_t bytes)
-{
-    if (bytes <= c->guided_cap) return 0;
-    if (c->guided) HIP_TRY(hipFree(c->guided));
-    c->guided = nullptr;
-    c->guided_cap = 0;
-    HIP_TRY(hipMalloc(&c->guided, bytes));
-    c->guided_cap = bytes;
-    return 0;
-}
+static int guided_scratch(hak_ctx* c, size_t bytes) { return grow_scratch(c->guided, c->guided_cap, (long)bytes, 1); }
 
 // What the gated matchers (hak_match_guided, hak_match_epipolar) share behind their own model checks.  Single pair, synchronous:
 // search(stream, scratch, fwd) enqueues the bin step, the search and the reverse step.

@@ -73,19 +73,18 @@ struct hak_ctx {
     double fed_fused_bytes = 0;     // compulsory HBM bytes per image of the FED launches as enqueued (read L [+ g], write L' [+ smooth, g])
     int4* knn = nullptr;            // 2-NN scratch: fwd[batch/2][max_pts] | rev[batch/2][max_pts], allocated on first use
     int* d_cnt = nullptr;
-    unsigned long long* hom_slots = nullptr;  // RANSAC scratch: best key per (pair, score block), grown on demand
-    long hom_cap = 0;
-    hak_homography* hom_rec = nullptr;        // the record of hak_find_homography before its download
-    unsigned* fund_models = nullptr;          // hak_find_fundamental scratch: 28 words per (pair, hypothesis), grown on demand
-    long fund_cap = 0;                        // (its slots are hom_slots: both run on the context's stream)
-    hak_fundamental* fund_rec = nullptr;      // the record of hak_find_fundamental before its download
-    unsigned* pnp_models = nullptr;           // hak_solve_pnp scratch: 49 words per (list, hypothesis), grown on demand (slots: hom_slots)
-    long pnp_cap = 0;
-    char* pnp_rec = nullptr;                  // 64 + 16 bytes: the record of hak_solve_pnp and the count of hak_link_tracks before their download
+    // RANSAC scratch of hak_find_homography, hak_find_fundamental and hak_solve_pnp, each grown on demand.  The estimators share it:
+    // every call that touches it is enqueued on the context's stream, so one call's kernels are through with it before the next
+    // call's start, and it is only ever grown outside a launch sequence (hipFree waits for the device).
+    unsigned long long* ransac_slots = nullptr;   // best key per (pair, score block)
+    long ransac_slots_cap = 0;
+    unsigned* ransac_models = nullptr;            // models of (pair, hypothesis), word-major (ransac_common.h): 28 words for F, 49 for PnP
+    long ransac_models_cap = 0;
+    char* geom_rec = nullptr;                 // 64 + 16 bytes: the record of a single-call estimator or refit, and the count of hak_link_tracks, before their download
     int* link_tab = nullptr;                  // hak_link_tracks scratch: the table train -> a, max_index ints per pair, grown on demand
     long link_cap = 0;
     void* guided = nullptr;        // guided-matching scratch (kernels_guided.hip, kernels_epipolar.hip): grown on demand, outside a launch sequence
-    size_t guided_cap = 0;
+    long guided_cap = 0;                     // bytes
     hak_point* pair_pts = nullptr;  // [2][cfg.max_pts]: the contiguous pair layout hak_detect_and_compute_pair detects into and matches on
     HakMatchScratch msc;            // sliced searches of one big pair (hak_match / hak_match_knn2): grows on demand, on this context's device
     HakKnobs knobs;                 // the HAK_* variables as hak_create found them: THIS context's (two contexts of a process may differ)

@@ -777,15 +777,17 @@ void hak_launch_epipolar(hipStream_t st, const hak_point* pts1, const hak_point*
                          int n2_host, long stride1, long stride2, int npairs, const hak_fundamental* d_F, const float* h_F, float radius,
                          int cross, const HakGuidedScratch& sc, int4* fwd, long fwd_stride);
 
-// RANSAC homography (kernels_homography.hip): score blocks per pair (and hypotheses per block through hp_out); the launcher
-// writes one uint64 slot per (pair, block) to `slots` (npairs * hak_homography_blocks(...) of them)
+// The three RANSAC estimators share one scaffold (ransac_common.h) and one launch-shape rule, hak_homography_blocks: score blocks per
+// pair (and hypotheses per block through hp_out).  A launcher writes one uint64 slot per (pair, block) to `slots` (npairs *
+// hak_homography_blocks(...) of them); those with a models kernel keep `models`, hak_*_words(npairs, iterations) 32-bit words, in the
+// scaffold's word-major layout.
+// RANSAC homography (kernels_homography.hip): no models kernel
 int hak_homography_blocks(int npairs, int iterations, int* hp_out);
 void hak_launch_homography(hipStream_t st, const hak_match_pair* matches, long stride, const int* counts, int n_host, int npairs,
                            int iterations, float threshold, unsigned seed, int refine, unsigned long long* slots,
                            hak_homography* out, unsigned char* masks, long mask_stride);
 
-// RANSAC fundamental matrix (kernels_fundamental.hip): the score blocks are hak_homography_blocks'; `models` is scratch of
-// hak_fundamental_words(npairs, iterations) 32-bit words (28 per hypothesis), `slots` as above
+// RANSAC fundamental matrix (kernels_fundamental.hip): 28 model words per hypothesis
 long hak_fundamental_words(int npairs, int iterations);
 void hak_launch_fundamental(hipStream_t st, const hak_match_pair* matches, long stride, const int* counts, int n_host, int npairs,
                             int iterations, float threshold, unsigned seed, unsigned* models, unsigned long long* slots,
@@ -803,8 +805,7 @@ hak_pose* hak_pose_record();
 void hak_launch_pose(hipStream_t st, const hak_match_pair* matches, long stride, const int* counts, int n_host, int npairs,
                      const hak_fundamental* d_F, const float* h_F, const hak_intrinsics& K1, const hak_intrinsics& K2,
                      float threshold, float max_depth, hak_pose* out, unsigned char* masks, float* xyz);
-// RANSAC absolute pose (kernels_pnp.hip): the score blocks are hak_homography_blocks'; `models` is scratch of hak_pnp_words(npairs,
-// iterations) 32-bit words, `slots` as hak_launch_homography's
+// RANSAC absolute pose (kernels_pnp.hip): 49 model words per hypothesis
 long hak_pnp_words(int npairs, int iterations);
 void hak_launch_pnp(hipStream_t st, const hak_corr3d* corr, long stride, const int* counts, int n_host, int npairs,
                     const hak_intrinsics& K, int iterations, float threshold, unsigned seed, unsigned* models,

@@ -9,29 +9,19 @@
 //
 // k_fund_models: grid (pair, hypothesis block of 64), one hypothesis per thread through the whole float64 solve.  The 7 x 9
 //   system lives in registers: every loop over it is unrolled with compile-time indices, a row swap is a chain of selects.
-//   Output to context scratch, word-major so that both kernels touch it coalesced: words [pair][w][iterations], w = 0..26 the
-//   float32 models of roots 0, 1, 2 (9 each), w = 27 a mask of the roots that gave a model (bit r = root r).
-// k_fund_score: k_hom_score's shape: grid (pair, hypothesis block), 256 threads; a block owns `hp` hypotheses (16 .. 256) and
-//   256 / hp match slices; the pair's records stream through LDS in chunks of FD_CHUNK float4 {x1, y1, x2, y2}.  A thread
-//   counts the inliers of its hypothesis' up to three models; each block writes its best key
-//   (inliers << 32 | ~(4 h + root), 0 = none) to its own slot [pair][block]: no atomics and nothing to clear before a call.
+//   Output to the models scratch of ransac_common.h: the float32 models of roots 0, 1, 2 (9 words each) and the mask of the roots
+//   that gave one.
+// k_fund_score: rs_score_block on the hypothesis' up to three models read back from scratch.
 // k_fund_finish: one wave per pair: reduces the slots, reads the winner's model back from scratch, writes the mask and the
 //   record.
-#include "hak_internal.h"
-#include "geom_common.h"
+#include "ransac_common.h"
 
-#define FD_CHUNK 1024            // records per LDS chunk: 16 KB, so that several blocks share a CU
-#define FD_THREADS 256
-#define FD_MTHREADS 64           // k_fund_models: one wave per block (1024 hypotheses of one pair spread over 16 CUs)
-#define FD_WORDS 28              // scratch words per hypothesis
-#define FD_DRAWS 32
-
-__device__ __forceinline__ unsigned long long fd_mix64(unsigned long long z)
-{
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
+// the scaffold's view of the estimator: three models (the cubic's roots) of 9 words per hypothesis
+struct fd_est : rs_match_records {
+    static constexpr int NM = 3, NW = 9, UNROLL = 2;
+    float t2;
+    __device__ __forceinline__ bool inlier(const float F[9], const float4 r) const { return fd_inlier(F, r, t2); }
+};
 
 __device__ __forceinline__ double fd_det(const double m[9])
 {
@@ -74,20 +64,8 @@ __device__ __forceinline__ bool fd_normalise(double x[7], double y[7], double& c
 __device__ int fd_hypothesis(const hak_match_pair* m, int n, unsigned seed, int h, float Fo[3][9])
 {
     if (n < 7) return 0;
-    int i0 = -1, i1 = -1, i2 = -1, i3 = -1, i4 = -1, i5 = -1, i6 = -1, k = 0;
-#pragma unroll 1
-    for (int d = 0; d < FD_DRAWS && k < 7; d++) {
-        const unsigned long long r =
-            fd_mix64((unsigned long long)seed + (unsigned long long)(FD_DRAWS * (unsigned)h + d + 1) * 0x9E3779B97F4A7C15ull);
-        const int j = (int)(((r >> 32) * (unsigned long long)n) >> 32);
-        if (j != i0 && j != i1 && j != i2 && j != i3 && j != i4 && j != i5) {
-            if (k == 0) i0 = j; else if (k == 1) i1 = j; else if (k == 2) i2 = j; else if (k == 3) i3 = j;
-            else if (k == 4) i4 = j; else if (k == 5) i5 = j; else i6 = j;
-            k++;
-        }
-    }
-    if (k < 7) return 0;
-    const int idx[7] = {i0, i1, i2, i3, i4, i5, i6};
+    int idx[7];
+    if (!rs_sample<7, 32>(seed, h, n, idx)) return 0;
     double x[7], y[7], u[7], v[7];
 #pragma unroll
     for (int q = 0; q < 7; q++) {
@@ -181,12 +159,12 @@ __device__ int fd_hypothesis(const hak_match_pair* m, int n, unsigned seed, int 
     return valid;
 }
 
-__global__ __launch_bounds__(FD_MTHREADS) void k_fund_models(const hak_match_pair* __restrict__ base, long stride,
+__global__ __launch_bounds__(RS_MTHREADS) void k_fund_models(const hak_match_pair* __restrict__ base, long stride,
                                                              const int* __restrict__ counts, int n_host, int iterations,
                                                              unsigned seed, unsigned* __restrict__ models)
 {
     const int pair = blockIdx.x;
-    const int h = blockIdx.y * FD_MTHREADS + threadIdx.x;
+    const int h = blockIdx.y * RS_MTHREADS + threadIdx.x;
     if (h >= iterations) return;
     const hak_match_pair* m = base + (long)pair * stride;
     const int n = fd_count(counts, pair, n_host, stride);
@@ -196,83 +174,20 @@ __global__ __launch_bounds__(FD_MTHREADS) void k_fund_models(const hak_match_pai
 #pragma unroll
         for (int q = 0; q < 9; q++) F[r][q] = 0.0f;
     const int valid = fd_hypothesis(m, n, seed, h, F);
-    unsigned* o = models + (long)pair * FD_WORDS * iterations + h;
 #pragma unroll
-    for (int r = 0; r < 3; r++)
-#pragma unroll
-        for (int q = 0; q < 9; q++) o[(long)(9 * r + q) * iterations] = __float_as_uint(F[r][q]);
-    o[(long)27 * iterations] = (unsigned)valid;
+    for (int r = 0; r < 3; r++) rs_write_model<fd_est>(models, pair, iterations, h, r, F[r]);
+    rs_write_valid<fd_est>(models, pair, iterations, h, valid);
 }
 
-__global__ __launch_bounds__(FD_THREADS) void k_fund_score(const hak_match_pair* __restrict__ base, long stride,
+__global__ __launch_bounds__(RS_THREADS) void k_fund_score(const hak_match_pair* __restrict__ base, long stride,
                                                            const int* __restrict__ counts, int n_host, int iterations, int hp,
                                                            float t2, const unsigned* __restrict__ models,
                                                            unsigned long long* __restrict__ slots)
 {
-    __shared__ float4 rec[FD_CHUNK];
-    __shared__ int part[3][FD_THREADS];
-    __shared__ unsigned long long wbest[FD_THREADS / HAK_WAVE];
-    const int pair = blockIdx.x, t = threadIdx.x;
-    const hak_match_pair* m = base + (long)pair * stride;
-    const int n = fd_count(counts, pair, n_host, stride);
-    const int h = blockIdx.y * hp + (t & (hp - 1));
-    const int slice = t / hp, nslice = FD_THREADS / hp;
-    float F0[9], F1[9], F2[9];
-    int valid = 0;
-    if (h < iterations) {
-        const unsigned* o = models + (long)pair * FD_WORDS * iterations + h;
-        valid = (int)o[(long)27 * iterations];
-#pragma unroll
-        for (int q = 0; q < 9; q++) {
-            F0[q] = __uint_as_float(o[(long)q * iterations]);
-            F1[q] = __uint_as_float(o[(long)(9 + q) * iterations]);
-            F2[q] = __uint_as_float(o[(long)(18 + q) * iterations]);
-        }
-    } else {
-#pragma unroll
-        for (int q = 0; q < 9; q++) F0[q] = F1[q] = F2[q] = 0.0f;
-    }
-    int c0 = 0, c1 = 0, c2 = 0;
-    for (int b0 = 0; b0 < n; b0 += FD_CHUNK) {
-        const int len = min(FD_CHUNK, n - b0);
-        __syncthreads();                                            // the previous chunk is consumed
-        for (int j = t; j < len; j += FD_THREADS) rec[j] = fd_load(m, b0 + j);
-        __syncthreads();
-        if (valid) {
-#pragma unroll 2
-            for (int j = slice; j < len; j += nslice) {
-                const float4 r = rec[j];
-                c0 += fd_inlier(F0, r, t2) ? 1 : 0;
-                c1 += fd_inlier(F1, r, t2) ? 1 : 0;
-                c2 += fd_inlier(F2, r, t2) ? 1 : 0;
-            }
-        }
-    }
-    part[0][t] = c0; part[1][t] = c1; part[2][t] = c2;
-    __syncthreads();
-    unsigned long long key = 0;
-    if (t < hp) {
-#pragma unroll
-        for (int r = 0; r < 3; r++) {
-            int s = 0;
-            for (int k = 0; k < nslice; k++) s += part[r][t + k * hp];
-            const unsigned long long kr = ((unsigned long long)s << 32) | (unsigned)~(4u * (unsigned)h + (unsigned)r);
-            if ((valid >> r & 1) && kr > key) key = kr;
-        }
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const unsigned long long o = __shfl_xor(key, off);
-        key = o > key ? o : key;
-    }
-    if ((t & (HAK_WAVE - 1)) == 0) wbest[t / HAK_WAVE] = key;
-    __syncthreads();
-    if (t == 0) {
-        unsigned long long b = wbest[0];
-#pragma unroll
-        for (int w = 1; w < FD_THREADS / HAK_WAVE; w++) b = wbest[w] > b ? wbest[w] : b;
-        slots[(long)pair * gridDim.y + blockIdx.y] = b;
-    }
+    const int pair = blockIdx.x;
+    float F[3][9];
+    const int valid = rs_read_models<fd_est>(models, pair, iterations, rs_block_hypothesis(hp), F);
+    rs_score_block(fd_est{{}, t2}, base + (long)pair * stride, fd_count(counts, pair, n_host, stride), hp, F, valid, slots);
 }
 
 __global__ __launch_bounds__(HAK_WAVE) void k_fund_finish(const hak_match_pair* __restrict__ base, long stride,
@@ -282,35 +197,15 @@ __global__ __launch_bounds__(HAK_WAVE) void k_fund_finish(const hak_match_pair* 
                                                           hak_fundamental* __restrict__ out, unsigned char* __restrict__ masks,
                                                           long mask_stride)
 {
-    const int pair = blockIdx.x, l = threadIdx.x;
+    const int pair = blockIdx.x;
     const hak_match_pair* m = base + (long)pair * stride;
     const int n = fd_count(counts, pair, n_host, stride);
-    unsigned long long key = 0;
-    for (int k = l; k < hblocks; k += HAK_WAVE) {
-        const unsigned long long v = slots[(long)pair * hblocks + k];
-        key = v > key ? v : key;
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const unsigned long long o = __shfl_xor(key, off);
-        key = o > key ? o : key;
-    }
     float F[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    int inl = 0, hyp = -1, root = 0;
-    if (key != 0) {
-        const unsigned id = ~(unsigned)key;                         // 4 h + root, h < iterations: its model is in scratch
-        hyp = (int)(id >> 2);
-        root = (int)(id & 3u);
-        inl = (int)(key >> 32);
-        const unsigned* o = models + (long)pair * FD_WORDS * iterations + hyp;
-#pragma unroll
-        for (int q = 0; q < 9; q++) F[q] = __uint_as_float(o[(long)(9 * root + q) * iterations]);
-    }
-    if (masks) {
-        unsigned char* mk = masks + (long)pair * mask_stride;
-        for (int i = l; i < n; i += HAK_WAVE) mk[i] = (hyp >= 0 && fd_inlier(F, fd_load(m, i), t2)) ? 1 : 0;
-    }
-    if (l == 0) {
+    int inl, hyp, root;
+    if (rs_decode(rs_best_slot(slots, hblocks), inl, hyp, root))    // hyp < iterations: its model is in scratch
+        rs_read_model<fd_est>(models, pair, iterations, hyp, root, F);
+    rs_write_mask(fd_est{{}, t2}, masks, mask_stride, m, n, F, hyp >= 0);
+    if (threadIdx.x == 0) {
         hak_fundamental o;
 #pragma unroll
         for (int q = 0; q < 9; q++) o.F[q] = F[q];
@@ -319,7 +214,7 @@ __global__ __launch_bounds__(HAK_WAVE) void k_fund_finish(const hak_match_pair* 
     }
 }
 
-long hak_fundamental_words(int npairs, int iterations) { return (long)npairs * FD_WORDS * iterations; }
+long hak_fundamental_words(int npairs, int iterations) { return (long)npairs * rs_words<fd_est>() * iterations; }
 
 void hak_launch_fundamental(hipStream_t st, const hak_match_pair* matches, long stride, const int* counts, int n_host, int npairs,
                             int iterations, float threshold, unsigned seed, unsigned* models, unsigned long long* slots,
@@ -328,9 +223,9 @@ void hak_launch_fundamental(hipStream_t st, const hak_match_pair* matches, long 
     int hp = 0;
     const int hblocks = hak_homography_blocks(npairs, iterations, &hp);
     const float t2 = threshold * threshold;
-    k_fund_models<<<dim3(npairs, (iterations + FD_MTHREADS - 1) / FD_MTHREADS), FD_MTHREADS, 0, st>>>(matches, stride, counts, n_host,
+    k_fund_models<<<dim3(npairs, (iterations + RS_MTHREADS - 1) / RS_MTHREADS), RS_MTHREADS, 0, st>>>(matches, stride, counts, n_host,
                                                                                                       iterations, seed, models);
-    k_fund_score<<<dim3(npairs, hblocks), FD_THREADS, 0, st>>>(matches, stride, counts, n_host, iterations, hp, t2, models, slots);
+    k_fund_score<<<dim3(npairs, hblocks), RS_THREADS, 0, st>>>(matches, stride, counts, n_host, iterations, hp, t2, models, slots);
     k_fund_finish<<<npairs, HAK_WAVE, 0, st>>>(matches, stride, counts, n_host, iterations, hblocks, t2, models, slots, out, masks,
                                                mask_stride);
 }

@@ -6,41 +6,11 @@
 // a fixed order (lane l of one wave takes matches i = l mod 64 in ascending i, then an xor butterfly over 32 .. 1).
 // The file is built with -ffp-contract=off: no FMA is formed, so every rounding is the one the reference makes.
 //
-// k_hom_score: grid (pair, hypothesis block), 256 threads.  A block owns `hp` hypotheses (16 .. 256, a power of two) and
-//   256 / hp match slices: thread t scores hypothesis t mod hp against the records j = t / hp (mod 256 / hp) of each chunk.
-//   Every thread draws and solves its hypothesis in registers; the pair's records stream through LDS in chunks of HG_CHUNK
-//   float4 {x1, y1, x2, y2}, read back with ds_read_b128 where the lanes of a wave share one address (hp >= 64) or four
-//   consecutive ones (hp = 16).  Each block writes its best key (inliers << 32 | ~h) to its own slot [pair][block]: no atomics
-//   and nothing to clear before a call.
+// k_hom_score: rs_score_block's shape (ransac_common.h) with one model per hypothesis: every thread draws and solves its hypothesis
+//   in registers (no models kernel, no scratch), then the scaffold counts its inliers and writes the block's slot.
 // k_hom_finish: one wave per pair: reduces the slots, re-derives the winner through the same device function, refits, re-scores,
 //   writes the mask and the record.
-#include "hak_internal.h"
-#include "geom_common.h"
-
-#define HG_CHUNK 1024            // records per LDS chunk: 16 KB, so that several blocks share a CU
-#define HG_THREADS 256
-
-__device__ __forceinline__ unsigned long long hg_mix64(unsigned long long z)
-{
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
-// the last 16 bytes of a hak_match_pair; a record with a non-finite coordinate gets x1 = NaN, which fails every test below
-__device__ __forceinline__ float4 hg_load(const hak_match_pair* m, int i)
-{
-    float4 r = *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(m + i) + 16);
-    if (!(__builtin_isfinite(r.x) && __builtin_isfinite(r.y) && __builtin_isfinite(r.z) && __builtin_isfinite(r.w)))
-        r.x = __builtin_nanf("");
-    return r;
-}
-
-__device__ __forceinline__ int hg_count(const int* counts, int pair, int n_host, long stride)
-{
-    long n = counts ? counts[pair] : n_host;
-    return (int)(n < 0 ? 0 : (n > stride ? stride : n));
-}
+#include "ransac_common.h"
 
 __device__ __forceinline__ bool hg_inlier(const float H[9], const float4 r, const float t2)
 {
@@ -64,14 +34,6 @@ __device__ __forceinline__ void hg_square_to_quad(const double x[4], const doubl
     S[6] = g; S[7] = h; S[8] = 1.0;
 }
 
-__device__ __forceinline__ void hg_mul3(const double A[9], const double B[9], double C[9])
-{
-#pragma unroll
-    for (int i = 0; i < 3; i++)
-#pragma unroll
-        for (int j = 0; j < 3; j++) C[3 * i + j] = (A[3 * i] * B[j] + A[3 * i + 1] * B[3 + j]) + A[3 * i + 2] * B[6 + j];
-}
-
 // divide by [2][2] and round to float32 with H[8] = 1; false if [2][2] is 0 or anything is non-finite
 __device__ __forceinline__ bool hg_to_float(const double F[9], float H[9])
 {
@@ -89,30 +51,24 @@ __device__ __forceinline__ double hg_cross(const double x[4], const double y[4],
     return (x[b] - x[a]) * (y[c] - y[a]) - (y[b] - y[a]) * (x[c] - x[a]);
 }
 
+// the scaffold's view of the estimator: one model of 9 words per hypothesis
+struct hg_est : rs_match_records {
+    static constexpr int NM = 1, NW = 9, UNROLL = 4;
+    float t2;
+    __device__ __forceinline__ bool inlier(const float H[9], const float4 r) const { return hg_inlier(H, r, t2); }
+};
+
 // hypothesis h of a pair with n matches: false when it is degenerate (no four distinct indices within 16 draws, a triple with
 // |cross| <= 1 px^2 or a flipped orientation in either image, a non-finite or singular solve)
 __device__ bool hg_hypothesis(const hak_match_pair* m, int n, unsigned seed, int h, float H[9])
 {
     if (n < 4) return false;
-    int i0 = -1, i1 = -1, i2 = -1, i3 = -1, k = 0;
-#pragma unroll
-    for (int d = 0; d < 16; d++) {
-        if (k < 4) {
-            const unsigned long long r =
-                hg_mix64((unsigned long long)seed + (unsigned long long)(16 * (unsigned)h + d + 1) * 0x9E3779B97F4A7C15ull);
-            const int j = (int)(((r >> 32) * (unsigned long long)n) >> 32);
-            if (j != i0 && j != i1 && j != i2) {
-                if (k == 0) i0 = j; else if (k == 1) i1 = j; else if (k == 2) i2 = j; else i3 = j;
-                k++;
-            }
-        }
-    }
-    if (k < 4) return false;
-    const int idx[4] = {i0, i1, i2, i3};
+    int idx[4];
+    if (!rs_sample<4, 16>(seed, h, n, idx)) return false;
     double ax[4], ay[4], bx[4], by[4];
 #pragma unroll
     for (int q = 0; q < 4; q++) {
-        const float4 r = hg_load(m, idx[q]);
+        const float4 r = fd_load(m, idx[q]);
         ax[q] = r.x; ay[q] = r.y; bx[q] = r.z; by[q] = r.w;
     }
     const int T[4][3] = {{0, 1, 2}, {0, 1, 3}, {0, 2, 3}, {1, 2, 3}};
@@ -129,7 +85,7 @@ __device__ bool hg_hypothesis(const hak_match_pair* m, int n, unsigned seed, int
     A[0] = S1[4] * S1[8] - S1[5] * S1[7]; A[1] = S1[2] * S1[7] - S1[1] * S1[8]; A[2] = S1[1] * S1[5] - S1[2] * S1[4];
     A[3] = S1[5] * S1[6] - S1[3] * S1[8]; A[4] = S1[0] * S1[8] - S1[2] * S1[6]; A[5] = S1[2] * S1[3] - S1[0] * S1[5];
     A[6] = S1[3] * S1[7] - S1[4] * S1[6]; A[7] = S1[1] * S1[6] - S1[0] * S1[7]; A[8] = S1[0] * S1[4] - S1[1] * S1[3];
-    hg_mul3(S2, A, F);
+    fd_mul3(S2, A, F);
     return hg_to_float(F, H);
 }
 
@@ -137,7 +93,7 @@ __device__ bool hg_hypothesis(const hak_match_pair* m, int n, unsigned seed, int
 __device__ int hg_count_inliers(const hak_match_pair* m, int n, const float H[9], float t2)
 {
     int c = 0;
-    for (int i = threadIdx.x; i < n; i += HAK_WAVE) c += hg_inlier(H, hg_load(m, i), t2) ? 1 : 0;
+    for (int i = threadIdx.x; i < n; i += HAK_WAVE) c += hg_inlier(H, fd_load(m, i), t2) ? 1 : 0;
     return hg_wsum(c);
 }
 
@@ -150,7 +106,7 @@ __device__ bool hg_refit(const hak_match_pair* m, int n, const float H[9], float
     int cnt = 0;
     double sx1 = 0.0, sy1 = 0.0, sx2 = 0.0, sy2 = 0.0;
     for (int i = l; i < n; i += HAK_WAVE) {
-        const float4 r = hg_load(m, i);
+        const float4 r = fd_load(m, i);
         if (!hg_inlier(H, r, t2)) continue;
         cnt++;
         sx1 = sx1 + (double)r.x; sy1 = sy1 + (double)r.y; sx2 = sx2 + (double)r.z; sy2 = sy2 + (double)r.w;
@@ -159,7 +115,7 @@ __device__ bool hg_refit(const hak_match_pair* m, int n, const float H[9], float
     const double c1x = hg_wsum(sx1) / mm, c1y = hg_wsum(sy1) / mm, c2x = hg_wsum(sx2) / mm, c2y = hg_wsum(sy2) / mm;
     double q1 = 0.0, q2 = 0.0;
     for (int i = l; i < n; i += HAK_WAVE) {
-        const float4 r = hg_load(m, i);
+        const float4 r = fd_load(m, i);
         if (!hg_inlier(H, r, t2)) continue;
         const double dx1 = (double)r.x - c1x, dy1 = (double)r.y - c1y, dx2 = (double)r.z - c2x, dy2 = (double)r.w - c2y;
         q1 = q1 + (dx1 * dx1 + dy1 * dy1);
@@ -174,7 +130,7 @@ __device__ bool hg_refit(const hak_match_pair* m, int n, const float H[9], float
 #pragma unroll
     for (int k = 0; k < 8; k++) g[k] = 0.0;
     for (int i = l; i < n; i += HAK_WAVE) {
-        const float4 r = hg_load(m, i);
+        const float4 r = fd_load(m, i);
         if (!hg_inlier(H, r, t2)) continue;
         const double X = s1 * ((double)r.x - c1x), Y = s1 * ((double)r.y - c1y);
         const double U = s2 * ((double)r.z - c2x), V = s2 * ((double)r.w - c2y);
@@ -233,57 +189,22 @@ __device__ bool hg_refit(const hak_match_pair* m, int n, const float H[9], float
     const double T1[9] = {s1, 0.0, -(s1 * c1x), 0.0, s1, -(s1 * c1y), 0.0, 0.0, 1.0};
     const double T2i[9] = {is2, 0.0, c2x, 0.0, is2, c2y, 0.0, 0.0, 1.0};
     double G[9], F[9];
-    hg_mul3(Hn, T1, G);
-    hg_mul3(T2i, G, F);
+    fd_mul3(Hn, T1, G);
+    fd_mul3(T2i, G, F);
     return hg_to_float(F, R);
 }
 
-__global__ __launch_bounds__(HG_THREADS) void k_hom_score(const hak_match_pair* __restrict__ base, long stride,
+__global__ __launch_bounds__(RS_THREADS) void k_hom_score(const hak_match_pair* __restrict__ base, long stride,
                                                           const int* __restrict__ counts, int n_host, int iterations, int hp,
                                                           float t2, unsigned seed, unsigned long long* __restrict__ slots)
 {
-    __shared__ float4 rec[HG_CHUNK];
-    __shared__ int part[HG_THREADS];
-    __shared__ unsigned long long wbest[HG_THREADS / HAK_WAVE];
-    const int pair = blockIdx.x, t = threadIdx.x;
+    const int pair = blockIdx.x;
     const hak_match_pair* m = base + (long)pair * stride;
-    const int n = hg_count(counts, pair, n_host, stride);
-    const int h = blockIdx.y * hp + (t & (hp - 1));
-    const int slice = t / hp, nslice = HG_THREADS / hp;
-    float H[9];
-    const bool ok = h < iterations && hg_hypothesis(m, n, seed, h, H);
-    int cnt = 0;
-    for (int c0 = 0; c0 < n; c0 += HG_CHUNK) {
-        const int len = min(HG_CHUNK, n - c0);
-        __syncthreads();                                            // the previous chunk is consumed
-        for (int j = t; j < len; j += HG_THREADS) rec[j] = hg_load(m, c0 + j);
-        __syncthreads();
-        if (ok) {
-#pragma unroll 4
-            for (int j = slice; j < len; j += nslice) cnt += hg_inlier(H, rec[j], t2) ? 1 : 0;
-        }
-    }
-    part[t] = cnt;
-    __syncthreads();
-    unsigned long long key = 0;
-    if (t < hp) {
-        int s = 0;
-        for (int k = 0; k < nslice; k++) s += part[t + k * hp];
-        if (ok) key = ((unsigned long long)s << 32) | (unsigned)~h;
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const unsigned long long o = __shfl_xor(key, off);
-        key = o > key ? o : key;
-    }
-    if ((t & (HAK_WAVE - 1)) == 0) wbest[t / HAK_WAVE] = key;
-    __syncthreads();
-    if (t == 0) {
-        unsigned long long b = wbest[0];
-#pragma unroll
-        for (int w = 1; w < HG_THREADS / HAK_WAVE; w++) b = wbest[w] > b ? wbest[w] : b;
-        slots[(long)pair * gridDim.y + blockIdx.y] = b;
-    }
+    const int n = fd_count(counts, pair, n_host, stride);
+    const int h = rs_block_hypothesis(hp);
+    float H[1][9];
+    const bool ok = h < iterations && hg_hypothesis(m, n, seed, h, H[0]);
+    rs_score_block(hg_est{{}, t2}, m, n, hp, H, ok ? 1 : 0, slots);
 }
 
 __global__ __launch_bounds__(HAK_WAVE) void k_hom_finish(const hak_match_pair* __restrict__ base, long stride,
@@ -292,24 +213,12 @@ __global__ __launch_bounds__(HAK_WAVE) void k_hom_finish(const hak_match_pair* _
                                                          hak_homography* __restrict__ out, unsigned char* __restrict__ masks,
                                                          long mask_stride)
 {
-    const int pair = blockIdx.x, l = threadIdx.x;
+    const int pair = blockIdx.x;
     const hak_match_pair* m = base + (long)pair * stride;
-    const int n = hg_count(counts, pair, n_host, stride);
-    unsigned long long key = 0;
-    for (int k = l; k < hblocks; k += HAK_WAVE) {
-        const unsigned long long v = slots[(long)pair * hblocks + k];
-        key = v > key ? v : key;
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const unsigned long long o = __shfl_xor(key, off);
-        key = o > key ? o : key;
-    }
+    const int n = fd_count(counts, pair, n_host, stride);
     float H[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f};
-    int inl = 0, hyp = -1, refined = 0;
-    if (key != 0) {
-        hyp = (int)~(unsigned)key;
-        inl = (int)(key >> 32);
+    int inl, hyp, model, refined = 0;
+    if (rs_decode(rs_best_slot(slots, hblocks), inl, hyp, model)) {
         hg_hypothesis(m, n, seed, hyp, H);                          // non-degenerate: its key was written by the same function
         float R[9];
         if (refine && inl >= 4 && hg_refit(m, n, H, t2, R)) {
@@ -322,11 +231,8 @@ __global__ __launch_bounds__(HAK_WAVE) void k_hom_finish(const hak_match_pair* _
             }
         }
     }
-    if (masks) {
-        unsigned char* mk = masks + (long)pair * mask_stride;
-        for (int i = l; i < n; i += HAK_WAVE) mk[i] = (hyp >= 0 && hg_inlier(H, hg_load(m, i), t2)) ? 1 : 0;
-    }
-    if (l == 0) {
+    rs_write_mask(hg_est{{}, t2}, masks, mask_stride, m, n, H, hyp >= 0);
+    if (threadIdx.x == 0) {
         hak_homography o;
 #pragma unroll
         for (int k = 0; k < 9; k++) o.H[k] = H[k];
@@ -352,7 +258,7 @@ void hak_launch_homography(hipStream_t st, const hak_match_pair* matches, long s
     int hp = 0;
     const int hblocks = hak_homography_blocks(npairs, iterations, &hp);
     const float t2 = threshold * threshold;
-    k_hom_score<<<dim3(npairs, hblocks), HG_THREADS, 0, st>>>(matches, stride, counts, n_host, iterations, hp, t2, seed, slots);
+    k_hom_score<<<dim3(npairs, hblocks), RS_THREADS, 0, st>>>(matches, stride, counts, n_host, iterations, hp, t2, seed, slots);
     k_hom_finish<<<npairs, HAK_WAVE, 0, st>>>(matches, stride, counts, n_host, hblocks, t2, seed, refine, slots, out, masks,
                                               mask_stride);
 }

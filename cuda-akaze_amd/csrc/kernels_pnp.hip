@@ -9,34 +9,19 @@
 // k_link_gather: k_knn2_finish's shape, one 1024-thread block per pair walks B in chunks and appends a correspondence per linked
 //   match at the running base through a ballot/popcount block scan: ascending m, deterministic.
 //
-// PnP, modelled on kernels_fundamental.hip:
+// PnP, on the scaffold of ransac_common.h:
 // k_pnp_models: grid (pair, hypothesis block of 64), one hypothesis per thread through the whole float64 solve (three points from 16
 //   draws, Grunert's quartic, its critical points by fd_cubic_roots, up to four brackets of 64 bisections, a pose per root).
-//   Output to context scratch, word-major so that both kernels touch it coalesced: words [pair][w][iterations], w = 0..47 the
-//   float32 models of solutions 0..3 (12 each: R row-major, t), w = 48 a mask of the solutions that gave a model.
-// k_pnp_score: k_fund_score's shape: grid (pair, hypothesis block), 256 threads; a block owns `hp` hypotheses (16 .. 256) and
-//   256 / hp slices of the list; the pair's records stream through LDS in chunks of PN_CHUNK {X, Y, Z, u} + {v}.  A thread counts
-//   the inliers of its hypothesis' up to four models; each block writes its best key (inliers << 32 | ~(4 h + solution), 0 = none)
-//   to its own slot [pair][block]: no atomics and nothing to clear before a call.  Only integer counts are reduced.
+//   Output to the models scratch: the float32 models of solutions 0..3 (12 words each: R row-major, t) and the mask of the solutions
+//   that gave one.
+// k_pnp_score: rs_score_block on the hypothesis' up to four models read back from scratch; a chunk is staged as {X, Y, Z, u} + {v}
+//   (20 KB).
 // k_pnp_finish: one wave per pair: reduces the slots, reads the winner's model back from scratch, writes the mask and the record.
-#include "hak_internal.h"
-#include "geom_common.h"
+#include "ransac_common.h"
 
-#define PN_CHUNK 1024            // records per LDS chunk: 20 KB
-#define PN_THREADS 256
-#define PN_MTHREADS 64           // k_pnp_models: one wave per block
-#define PN_WORDS 49              // scratch words per hypothesis
-#define PN_DRAWS 16
 #define LK_NONE 0x7F7F7F7F       // the table's cleared entry (memset byte 0x7F): above every index
 
 struct pn_rec { float4 a; float v; };                                 // a = {X, Y, Z, u}
-
-__device__ __forceinline__ unsigned long long pn_mix64(unsigned long long z)
-{
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
 
 // the first 20 bytes of a hak_corr3d; a record with a non-finite field gets X = NaN, which fails every test below
 __device__ __forceinline__ pn_rec pn_load(const hak_corr3d* c, int i)
@@ -61,6 +46,23 @@ __device__ __forceinline__ bool pn_inlier(const float M[12], const float4 a, con
     const float ey = (K.fy * yc + K.cy * zc) - v * zc;
     return zc > 0.f && ex * ex + ey * ey < t2 * (zc * zc);
 }
+
+// the scaffold's view of the estimator: four models (the quartic's roots) of 12 words per hypothesis
+struct pn_est {
+    typedef hak_corr3d list_t;
+    typedef pn_rec rec_t;
+    struct lds {
+        float4 a[RS_CHUNK];
+        float v[RS_CHUNK];
+        __device__ __forceinline__ void put(int j, const pn_rec r) { a[j] = r.a; v[j] = r.v; }
+        __device__ __forceinline__ pn_rec get(int j) const { return pn_rec{a[j], v[j]}; }
+    };
+    static constexpr int NM = 4, NW = 12, UNROLL = 2;
+    hak_intrinsics K;
+    float t2;
+    static __device__ __forceinline__ pn_rec load(const hak_corr3d* c, int i) { return pn_load(c, i); }
+    __device__ __forceinline__ bool inlier(const float M[12], const pn_rec r) const { return pn_inlier(M, r.a, r.v, K, t2); }
+};
 
 __device__ __forceinline__ double pn_dot(const double a[3], const double b[3]) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
 __device__ __forceinline__ void pn_cross(const double a[3], const double b[3], double c[3])
@@ -94,28 +96,16 @@ __device__ __forceinline__ double pn_q(double v, double b3, double b2, double b1
     return (((v + b3) * v + b2) * v + b1) * v + b0;
 }
 
-// hypothesis h of a list with n correspondences, steps 1-5 of the rule: the float32 models of its solutions go to
-// o[(12 s + q) * ostride] (zeros where solution s gave none), returns the mask of the solutions that gave one (0 = degenerate)
-__device__ int pn_hypothesis(const hak_corr3d* c, int n, const hak_intrinsics K, unsigned seed, int h, unsigned* o, long ostride)
+// hypothesis h of list `pair` with n correspondences, steps 1-5 of the rule: the float32 models of its solutions go to the models
+// scratch (zeros where solution s gave none), returns the mask of the solutions that gave one (0 = degenerate)
+__device__ int pn_hypothesis(const hak_corr3d* c, int n, const hak_intrinsics K, unsigned seed, int h, unsigned* models, int pair,
+                             int iterations)
 {
     int valid = 0, nsol = 0;
     bool ok = n >= 3;
-    int i0 = -1, i1 = -1, i2 = -1, k = 0;
+    int idx[3];
+    ok = ok && rs_sample<3, 16>(seed, h, n, idx);
     if (ok) {
-#pragma unroll 1
-        for (int d = 0; d < PN_DRAWS && k < 3; d++) {
-            const unsigned long long r =
-                pn_mix64((unsigned long long)seed + (unsigned long long)(PN_DRAWS * (unsigned)h + d + 1) * 0x9E3779B97F4A7C15ull);
-            const int j = (int)(((r >> 32) * (unsigned long long)n) >> 32);
-            if (j != i0 && j != i1) {
-                if (k == 0) i0 = j; else if (k == 1) i1 = j; else i2 = j;
-                k++;
-            }
-        }
-        ok = k == 3;
-    }
-    if (ok) {
-        const int idx[3] = {i0, i1, i2};
         const double fx = K.fx, fy = K.fy, cx = K.cx, cy = K.cy;
         double X[3][3], b[3][3];
 #pragma unroll
@@ -213,109 +203,39 @@ __device__ int pn_hypothesis(const hak_corr3d* c, int n, const hak_intrinsics K,
 #pragma unroll
                 for (int q2 = 0; q2 < 12; q2++) good = good && __builtin_isfinite(M[q2]);
 #pragma unroll
-                for (int q2 = 0; q2 < 12; q2++) o[(long)(12 * nsol + q2) * ostride] = __float_as_uint(good ? M[q2] : 0.0f);
+                for (int q2 = 0; q2 < 12; q2++) M[q2] = good ? M[q2] : 0.0f;
+                rs_write_model<pn_est>(models, pair, iterations, h, nsol, M);
                 valid |= good ? 1 << nsol : 0;
                 nsol++;
             }
         }
     }
-    for (int s = nsol; s < 4; s++)
-#pragma unroll
-        for (int q2 = 0; q2 < 12; q2++) o[(long)(12 * s + q2) * ostride] = 0u;
+    const float none[12] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    for (int s = nsol; s < 4; s++) rs_write_model<pn_est>(models, pair, iterations, h, s, none);
     return valid;
 }
 
-__global__ __launch_bounds__(PN_MTHREADS) void k_pnp_models(const hak_corr3d* __restrict__ base, long stride,
+__global__ __launch_bounds__(RS_MTHREADS) void k_pnp_models(const hak_corr3d* __restrict__ base, long stride,
                                                             const int* __restrict__ counts, int n_host, hak_intrinsics K,
                                                             int iterations, unsigned seed, unsigned* __restrict__ models)
 {
     const int pair = blockIdx.x;
-    const int h = blockIdx.y * PN_MTHREADS + threadIdx.x;
+    const int h = blockIdx.y * RS_MTHREADS + threadIdx.x;
     if (h >= iterations) return;
     const hak_corr3d* c = base + (long)pair * stride;
     const int n = fd_count(counts, pair, n_host, stride);
-    unsigned* o = models + (long)pair * PN_WORDS * iterations + h;
-    const int valid = pn_hypothesis(c, n, K, seed, h, o, iterations);
-    o[(long)48 * iterations] = (unsigned)valid;
+    rs_write_valid<pn_est>(models, pair, iterations, h, pn_hypothesis(c, n, K, seed, h, models, pair, iterations));
 }
 
-__global__ __launch_bounds__(PN_THREADS) void k_pnp_score(const hak_corr3d* __restrict__ base, long stride,
+__global__ __launch_bounds__(RS_THREADS) void k_pnp_score(const hak_corr3d* __restrict__ base, long stride,
                                                           const int* __restrict__ counts, int n_host, hak_intrinsics K,
                                                           int iterations, int hp, float t2, const unsigned* __restrict__ models,
                                                           unsigned long long* __restrict__ slots)
 {
-    __shared__ float4 rec[PN_CHUNK];
-    __shared__ float recv[PN_CHUNK];
-    __shared__ int part[4][PN_THREADS];
-    __shared__ unsigned long long wbest[PN_THREADS / HAK_WAVE];
-    const int pair = blockIdx.x, t = threadIdx.x;
-    const hak_corr3d* c = base + (long)pair * stride;
-    const int n = fd_count(counts, pair, n_host, stride);
-    const int h = blockIdx.y * hp + (t & (hp - 1));
-    const int slice = t / hp, nslice = PN_THREADS / hp;
-    float M0[12], M1[12], M2[12], M3[12];
-    int valid = 0;
-    if (h < iterations) {
-        const unsigned* o = models + (long)pair * PN_WORDS * iterations + h;
-        valid = (int)o[(long)48 * iterations];
-#pragma unroll
-        for (int q = 0; q < 12; q++) {
-            M0[q] = __uint_as_float(o[(long)q * iterations]);
-            M1[q] = __uint_as_float(o[(long)(12 + q) * iterations]);
-            M2[q] = __uint_as_float(o[(long)(24 + q) * iterations]);
-            M3[q] = __uint_as_float(o[(long)(36 + q) * iterations]);
-        }
-    } else {
-#pragma unroll
-        for (int q = 0; q < 12; q++) M0[q] = M1[q] = M2[q] = M3[q] = 0.0f;
-    }
-    int c0 = 0, c1 = 0, c2 = 0, c3 = 0;
-    for (int b0 = 0; b0 < n; b0 += PN_CHUNK) {
-        const int len = min(PN_CHUNK, n - b0);
-        __syncthreads();                                            // the previous chunk is consumed
-        for (int j = t; j < len; j += PN_THREADS) {
-            const pn_rec r = pn_load(c, b0 + j);
-            rec[j] = r.a;
-            recv[j] = r.v;
-        }
-        __syncthreads();
-        if (valid) {
-#pragma unroll 2
-            for (int j = slice; j < len; j += nslice) {
-                const float4 a = rec[j];
-                const float v = recv[j];
-                c0 += pn_inlier(M0, a, v, K, t2) ? 1 : 0;
-                c1 += pn_inlier(M1, a, v, K, t2) ? 1 : 0;
-                c2 += pn_inlier(M2, a, v, K, t2) ? 1 : 0;
-                c3 += pn_inlier(M3, a, v, K, t2) ? 1 : 0;
-            }
-        }
-    }
-    part[0][t] = c0; part[1][t] = c1; part[2][t] = c2; part[3][t] = c3;
-    __syncthreads();
-    unsigned long long key = 0;
-    if (t < hp) {
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-            int s = 0;
-            for (int k = 0; k < nslice; k++) s += part[r][t + k * hp];
-            const unsigned long long kr = ((unsigned long long)s << 32) | (unsigned)~(4u * (unsigned)h + (unsigned)r);
-            if ((valid >> r & 1) && kr > key) key = kr;
-        }
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const unsigned long long o = __shfl_xor(key, off);
-        key = o > key ? o : key;
-    }
-    if ((t & (HAK_WAVE - 1)) == 0) wbest[t / HAK_WAVE] = key;
-    __syncthreads();
-    if (t == 0) {
-        unsigned long long b = wbest[0];
-#pragma unroll
-        for (int w = 1; w < PN_THREADS / HAK_WAVE; w++) b = wbest[w] > b ? wbest[w] : b;
-        slots[(long)pair * gridDim.y + blockIdx.y] = b;
-    }
+    const int pair = blockIdx.x;
+    float M[4][12];
+    const int valid = rs_read_models<pn_est>(models, pair, iterations, rs_block_hypothesis(hp), M);
+    rs_score_block(pn_est{K, t2}, base + (long)pair * stride, fd_count(counts, pair, n_host, stride), hp, M, valid, slots);
 }
 
 __global__ __launch_bounds__(HAK_WAVE) void k_pnp_finish(const hak_corr3d* __restrict__ base, long stride,
@@ -325,38 +245,15 @@ __global__ __launch_bounds__(HAK_WAVE) void k_pnp_finish(const hak_corr3d* __res
                                                          hak_abs_pose* __restrict__ out, unsigned char* __restrict__ masks,
                                                          long mask_stride)
 {
-    const int pair = blockIdx.x, l = threadIdx.x;
+    const int pair = blockIdx.x;
     const hak_corr3d* c = base + (long)pair * stride;
     const int n = fd_count(counts, pair, n_host, stride);
-    unsigned long long key = 0;
-    for (int k = l; k < hblocks; k += HAK_WAVE) {
-        const unsigned long long v = slots[(long)pair * hblocks + k];
-        key = v > key ? v : key;
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const unsigned long long o = __shfl_xor(key, off);
-        key = o > key ? o : key;
-    }
     float M[12] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f};
-    int inl = 0, hyp = -1, sol = 0;
-    if (key != 0) {
-        const unsigned id = ~(unsigned)key;                         // 4 h + solution, h < iterations: its model is in scratch
-        hyp = (int)(id >> 2);
-        sol = (int)(id & 3u);
-        inl = (int)(key >> 32);
-        const unsigned* o = models + (long)pair * PN_WORDS * iterations + hyp;
-#pragma unroll
-        for (int q = 0; q < 12; q++) M[q] = __uint_as_float(o[(long)(12 * sol + q) * iterations]);
-    }
-    if (masks) {
-        unsigned char* mk = masks + (long)pair * mask_stride;
-        for (int i = l; i < n; i += HAK_WAVE) {
-            const pn_rec r = pn_load(c, i);
-            mk[i] = (hyp >= 0 && pn_inlier(M, r.a, r.v, K, t2)) ? 1 : 0;
-        }
-    }
-    if (l == 0) {
+    int inl, hyp, sol;
+    if (rs_decode(rs_best_slot(slots, hblocks), inl, hyp, sol))     // hyp < iterations: its model is in scratch
+        rs_read_model<pn_est>(models, pair, iterations, hyp, sol, M);
+    rs_write_mask(pn_est{K, t2}, masks, mask_stride, c, n, M, hyp >= 0);
+    if (threadIdx.x == 0) {
         hak_abs_pose o;
 #pragma unroll
         for (int q = 0; q < 9; q++) o.R[q] = M[q];
@@ -367,7 +264,7 @@ __global__ __launch_bounds__(HAK_WAVE) void k_pnp_finish(const hak_corr3d* __res
     }
 }
 
-long hak_pnp_words(int npairs, int iterations) { return (long)npairs * PN_WORDS * iterations; }
+long hak_pnp_words(int npairs, int iterations) { return (long)npairs * rs_words<pn_est>() * iterations; }
 
 void hak_launch_pnp(hipStream_t st, const hak_corr3d* corr, long stride, const int* counts, int n_host, int npairs,
                     const hak_intrinsics& K, int iterations, float threshold, unsigned seed, unsigned* models,
@@ -376,9 +273,9 @@ void hak_launch_pnp(hipStream_t st, const hak_corr3d* corr, long stride, const i
     int hp = 0;
     const int hblocks = hak_homography_blocks(npairs, iterations, &hp);
     const float t2 = threshold * threshold;
-    k_pnp_models<<<dim3(npairs, (iterations + PN_MTHREADS - 1) / PN_MTHREADS), PN_MTHREADS, 0, st>>>(corr, stride, counts, n_host, K,
+    k_pnp_models<<<dim3(npairs, (iterations + RS_MTHREADS - 1) / RS_MTHREADS), RS_MTHREADS, 0, st>>>(corr, stride, counts, n_host, K,
                                                                                                     iterations, seed, models);
-    k_pnp_score<<<dim3(npairs, hblocks), PN_THREADS, 0, st>>>(corr, stride, counts, n_host, K, iterations, hp, t2, models, slots);
+    k_pnp_score<<<dim3(npairs, hblocks), RS_THREADS, 0, st>>>(corr, stride, counts, n_host, K, iterations, hp, t2, models, slots);
     k_pnp_finish<<<npairs, HAK_WAVE, 0, st>>>(corr, stride, counts, n_host, K, iterations, hblocks, t2, models, slots, out, masks,
                                               mask_stride);
 }

@@ -294,7 +294,7 @@ int hak_find_homography_batch(hak_ctx* ctx, const hak_match_pair* d_matches, lon
  * least-squares refit over its inliers is the next stage, hak_refine_fundamental below.  Refused with a non-zero
  * status and a message before any device is touched: iterations outside 1..65536, a threshold that is not finite or not > 0,
  * n < 0, a NULL list with n > 0, NULL h_out / d_out / d_counts, npairs < 1, stride < 1, a NULL context for the batch form.
- * Device code: csrc/kernels_fundamental.hip. */
+ * Device code: csrc/kernels_fundamental.hip (RANSAC scaffold: csrc/ransac_common.h). */
 typedef struct hak_fundamental {
     float F[9];              /* row-major, (x2 y2 1) F (x1 y1 1)^T = 0; the entry of largest |value| is 1 */
     int   inliers;           /* inliers of F */
@@ -483,7 +483,8 @@ int hak_recover_pose_batch(hak_ctx* ctx, const hak_match_pair* d_matches, long s
  * Refused with a non-zero status and a message before any device is touched: iterations outside 1..65536, a threshold that is not
  * finite or not > 0, fx or fy not finite or 0, a non-finite cx or cy, a count < 0 (or >= 2^30 for the link), a NULL list with a
  * positive count, a list or output list that is not 16-byte aligned, NULL outputs, counts, xyz or K, npairs < 1, a stride < 1, a
- * count step < 1, max_index < 1, a NULL context for the batch forms.  Device code: csrc/kernels_pnp.hip. */
+ * count step < 1, max_index < 1, a NULL context for the batch forms.  Device code: csrc/kernels_pnp.hip
+ * (RANSAC scaffold: csrc/ransac_common.h). */
 typedef struct hak_corr3d {  /* 32 bytes, 16-byte aligned loads */
     float X, Y, Z;           /* point, frame and units of the xyz it came from */
     float u, v;              /* its observation in the new image, pixels */

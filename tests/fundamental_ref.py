@@ -7,7 +7,8 @@ kernels_fundamental.hip.
 """
 import numpy as np
 
-from homography_ref import _GOLD, _mul3, mix64, records
+import homography_ref as hr
+from homography_ref import _mul3, records
 
 FUNDAMENTAL_DTYPE = np.dtype([("F", "<f4", (9,)), ("inliers", "<i4"), ("hypothesis", "<i4"), ("root", "<i4"), ("n", "<i4")])
 assert FUNDAMENTAL_DTYPE.itemsize == 52        # 9 floats + 4 ints
@@ -17,18 +18,7 @@ DRAWS = 32
 
 def sample_indices(seed, h, n):
     """(len(h), 7) int64 indices (-1 where not drawn) and a validity flag per hypothesis"""
-    h = np.asarray(h, np.uint64)
-    idx = np.full((len(h), 7), -1, np.int64)
-    k = np.zeros(len(h), np.int64)
-    rows = np.arange(len(h))
-    with np.errstate(over="ignore"):
-        for d in range(DRAWS):
-            r = mix64(np.uint64(seed) + (np.uint64(DRAWS) * h + np.uint64(d + 1)) * _GOLD)
-            j = (((r >> np.uint64(32)) * np.uint64(n)) >> np.uint64(32)).astype(np.int64)
-            take = (k < 7) & (j[:, None] != idx).all(axis=1)
-            idx[rows[take], k[take]] = j[take]
-            k = k + take
-    return idx, k == 7
+    return hr.sample_indices(seed, h, n, 7, DRAWS)
 
 
 def _normalise(x, y):
@@ -200,17 +190,8 @@ def find_fundamental(matches, iterations=1024, threshold=1.0, seed=0, block=256)
     t2 = np.float32(threshold) * np.float32(threshold)
     out = np.zeros((), FUNDAMENTAL_DTYPE)
     out["hypothesis"], out["n"] = -1, n
-    best = (-1, -1, -1, None)                                           # inliers, h, root, F
-    for h0 in range(0, iterations, block):
-        hs = np.arange(h0, min(iterations, h0 + block))
-        F, valid = models(rec, seed, hs)
-        if not valid.any():
-            continue
-        hh, rr = np.nonzero(valid)                                      # ascending (h, root)
-        cnt = inlier_mask(F[hh, rr], rec, t2).sum(axis=1)
-        j = int(np.argmax(cnt))                                         # first maximum: the smallest (h, root) of this block
-        if cnt[j] > best[0]:
-            best = (int(cnt[j]), int(hs[hh[j]]), int(rr[j]), F[hh[j], rr[j]].copy())
+    best = hr.best_model(iterations, block, lambda hs: models(rec, seed, hs),               # inliers, h, root, F
+                         lambda F: inlier_mask(F, rec, t2).sum(axis=1))
     mask = np.zeros(n, np.uint8)
     if best[1] < 0:
         return out, mask

@@ -35,20 +35,39 @@ def records(matches):
     return r
 
 
-def sample_indices(seed, h, n):
-    """(len(h), 4) int64 indices and a validity flag per hypothesis"""
+def sample_indices(seed, h, n, k=4, draws=16):
+    """the sample generator of all three estimators (the homography's k and draws by default): (len(h), k) int64 indices (-1 where
+    not drawn) and a validity flag per hypothesis"""
     h = np.asarray(h, np.uint64)
-    idx = np.full((len(h), 4), -1, np.int64)
-    k = np.zeros(len(h), np.int64)
+    idx = np.full((len(h), k), -1, np.int64)
+    got = np.zeros(len(h), np.int64)
     rows = np.arange(len(h))
     with np.errstate(over="ignore"):
-        for d in range(16):
-            r = mix64(np.uint64(seed) + (np.uint64(16) * h + np.uint64(d + 1)) * _GOLD)
+        for d in range(draws):
+            r = mix64(np.uint64(seed) + (np.uint64(draws) * h + np.uint64(d + 1)) * _GOLD)
             j = (((r >> np.uint64(32)) * np.uint64(n)) >> np.uint64(32)).astype(np.int64)
-            take = (k < 4) & (j != idx[:, 0]) & (j != idx[:, 1]) & (j != idx[:, 2])
-            idx[rows[take], k[take]] = j[take]
-            k = k + take
-    return idx, k == 4
+            take = (got < k) & (j[:, None] != idx).all(axis=1)
+            idx[rows[take], got[take]] = j[take]
+            got = got + take
+    return idx, got == k
+
+
+def best_model(iterations, block, models, count):
+    """the RANSAC loop of all three estimators: (inliers, hypothesis, r, model) of the winner, (-1, -1, -1, None) if there is none.
+    models(hs) -> (M (len(hs), NM, NW) float32, valid (len(hs), NM) bool); count(M (k, NW)) -> (k,) inlier counts.  The largest
+    count wins, ties go to the smallest hypothesis and then its smallest r, whatever the block size"""
+    best = (-1, -1, -1, None)
+    for h0 in range(0, iterations, block):
+        hs = np.arange(h0, min(iterations, h0 + block))
+        M, valid = models(hs)
+        if not valid.any():
+            continue
+        hh, rr = np.nonzero(valid)                                      # ascending (h, r)
+        cnt = count(M[hh, rr])
+        j = int(np.argmax(cnt))                                         # first maximum: the smallest (h, r) of this block
+        if cnt[j] > best[0]:
+            best = (int(cnt[j]), int(hs[hh[j]]), int(rr[j]), M[hh[j], rr[j]].copy())
+    return best
 
 
 def _square_to_quad(x, y):
@@ -189,21 +208,12 @@ def find_homography(matches, iterations=1024, threshold=3.0, seed=0, refine=True
     t2 = np.float32(threshold) * np.float32(threshold)
     out = np.zeros((), HOMOGRAPHY_DTYPE)
     out["H"], out["hypothesis"], out["n"] = _IDENT, -1, n
-    best_cnt, best_h = -1, -1
-    for h0 in range(0, iterations, block):
-        hs = np.arange(h0, min(iterations, h0 + block))
-        H, ok = hypotheses(rec, seed, hs)
-        if not ok.any():
-            continue
-        cnt = inlier_mask(H[ok], rec, t2).sum(axis=1)
-        j = int(np.argmax(cnt))                                          # first maximum: the smallest h of this block
-        if cnt[j] > best_cnt:
-            best_cnt, best_h = int(cnt[j]), int(hs[ok][j])
+    inl, best_h, _, H = best_model(iterations, block, lambda hs: tuple(v[:, None] for v in hypotheses(rec, seed, hs)),
+                                   lambda M: inlier_mask(M, rec, t2).sum(axis=1))
     mask = np.zeros(n, np.uint8)
     if best_h < 0:
         return out, mask
-    H = hypotheses(rec, seed, [best_h])[0][0]
-    inl, refined = best_cnt, 0
+    refined = 0
     if refine and inl >= 4:
         R, ok = refit(rec, inlier_mask(H, rec, t2)[0])
         if ok:

@@ -7,8 +7,8 @@ for the scoring.  numpy forms no FMA, and every expression below is written in t
 """
 import numpy as np
 
+import homography_ref as hr
 from fundamental_ref import real_roots
-from homography_ref import _GOLD, mix64
 from pose_ref import _cross, _dot, intrinsics
 
 CORR3D_DTYPE = np.dtype([("X", "<f4"), ("Y", "<f4"), ("Z", "<f4"), ("u", "<f4"), ("v", "<f4"), ("src3d", "<i4"), ("src2d", "<i4"),
@@ -34,18 +34,7 @@ def records(corr):
 
 def sample_indices(seed, h, n):
     """step 1: (len(h), 3) int64 indices (-1 where not drawn) and a validity flag per hypothesis"""
-    h = np.asarray(h, np.uint64)
-    idx = np.full((len(h), 3), -1, np.int64)
-    k = np.zeros(len(h), np.int64)
-    rows = np.arange(len(h))
-    with np.errstate(over="ignore"):
-        for d in range(DRAWS):
-            r = mix64(np.uint64(seed) + (np.uint64(DRAWS) * h + np.uint64(d + 1)) * _GOLD)
-            j = (((r >> np.uint64(32)) * np.uint64(n)) >> np.uint64(32)).astype(np.int64)
-            take = (k < 3) & (j != idx[:, 0]) & (j != idx[:, 1])
-            idx[rows[take], k[take]] = j[take]
-            k = k + take
-    return idx, k == 3
+    return hr.sample_indices(seed, h, n, 3, DRAWS)
 
 
 def _sub(a, b):
@@ -196,17 +185,8 @@ def solve_pnp(corr, K, iterations=1024, threshold=1.0, seed=0, block=256):
     t2 = np.float32(threshold) * np.float32(threshold)
     out = np.zeros((), ABS_POSE_DTYPE)
     out["R"], out["hypothesis"], out["n"] = np.eye(3, dtype=np.float32).reshape(9), -1, n
-    best = (-1, -1, -1, None)                                           # inliers, h, solution, model
-    for h0 in range(0, iterations, block):
-        hs = np.arange(h0, min(iterations, h0 + block))
-        M, valid = models(rec, K, seed, hs)
-        if not valid.any():
-            continue
-        hh, ss = np.nonzero(valid)                                      # ascending (h, solution)
-        cnt = inlier_mask(M[hh, ss], rec, K, t2).sum(axis=1)
-        j = int(np.argmax(cnt))                                         # first maximum: the smallest (h, solution) of this block
-        if cnt[j] > best[0]:
-            best = (int(cnt[j]), int(hs[hh[j]]), int(ss[j]), M[hh[j], ss[j]].copy())
+    best = hr.best_model(iterations, block, lambda hs: models(rec, K, seed, hs),              # inliers, h, solution, model
+                         lambda M: inlier_mask(M, rec, K, t2).sum(axis=1))
     mask = np.zeros(n, np.uint8)
     if best[1] < 0:
         return out, mask

@@ -39,7 +39,7 @@ SHAPES = (
 )
 KINDS = ("H", "F")
 SAMPLE = {"H": 4, "F": 7}
-LONG = (1024, 1025, 2050)           # list lengths around HG_CHUNK / FD_CHUNK = 1024 records
+LONG = (1024, 1025, 2050)           # list lengths around RS_CHUNK = 1024 records
 LONG_SHAPES = ((32, 129), (64, 257))
 
 # (npairs, iterations) -> {pair: (target hypotheses, beyond)}.  The planted records of that pair's list sit on the slots the
