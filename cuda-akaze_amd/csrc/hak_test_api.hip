@@ -779,3 +779,29 @@ extern "C" int hak_op_ransac_shape(int npairs, int iterations, int* hp, int* hbl
     *hblocks = hak_homography_blocks(npairs, iterations, hp);
     return 0;
 }
+
+// the RANSAC scratch of the last H, F or P3P call on the context, as that call left it: the models words [pair][word][iterations]
+// (ransac_common.h) as they lie, and every score block's slot decoded here by rs_decode's rule, so that no test restates the key.
+// Launches nothing.
+extern "C" int hak_debug_ransac_scratch(hak_ctx* c, int npairs, int words_per_hypothesis, int iterations, int hblocks,
+                                        unsigned* h_models, int* h_slots)
+{
+    if (!c) return fail("null context");
+    if (npairs < 1 || words_per_hypothesis < 0 || iterations < 1 || iterations > 65536 || hblocks < 1)
+        return fail("npairs, iterations and hblocks must be >= 1, words_per_hypothesis >= 0, iterations <= 65536");
+    const long words = (long)npairs * words_per_hypothesis * iterations, slots = (long)npairs * hblocks;
+    if (!h_slots || (words > 0 && !h_models)) return fail("null output");
+    if (words > c->ransac_models_cap || slots > c->ransac_slots_cap) return fail("more than the context's RANSAC scratch holds");
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (words > 0) HIP_TRY(hipMemcpy(h_models, c->ransac_models, sizeof(unsigned) * (size_t)words, hipMemcpyDeviceToHost));
+    std::vector<unsigned long long> keys((size_t)slots);
+    HIP_TRY(hipMemcpy(keys.data(), c->ransac_slots, sizeof(unsigned long long) * (size_t)slots, hipMemcpyDeviceToHost));
+    for (long k = 0; k < slots; k++) {
+        const unsigned long long key = keys[(size_t)k];
+        const unsigned id = ~(unsigned)key;                             // 4 h + r
+        h_slots[3 * k] = (int)(key >> 32);
+        h_slots[3 * k + 1] = key != 0 ? (int)(id >> 2) : -1;
+        h_slots[3 * k + 2] = key != 0 ? (int)(id & 3u) : 0;
+    }
+    return 0;
+}

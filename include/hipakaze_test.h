@@ -4,7 +4,7 @@
  * NOT part of the product: a maintainer who binds the reference's interface needs include/hipakaze.h (libhipakaze.so) or
  * include/akaze.h only.  This library links against libhipakaze.so and drives the SAME launchers and kernels the launch
  * sequence uses, one stage at a time, so that tests/ can compare every stage with the oracle and with hand-derived fixtures:
- *   hak_debug_*   planes / contrast factor of the last call on a context, writing a plane
+ *   hak_debug_*   planes / contrast factor / RANSAC scratch of the last call on a context, writing a plane
  *   hak_op_*      single-stage operators (one h*() wrapper of akazed.cu each), the detector tail and the descriptor stages on
  *                 hand-made inputs, the conductivity's reciprocal self-check, bandwidth probes of the box
  *   hak_op_fast_* the stage operators once more on the integer FAST path: int32 planes (any value: products wrap, conversions
@@ -159,6 +159,19 @@ int hak_debug_fill_match_scratch(hak_ctx* ctx, int byte);
  * lists and `iterations` hypotheses -- *hp hypotheses per score block (16 .. 256) and *hblocks score blocks per pair.  It asks the
  * launchers' own rule and touches no device: the shape tests (tests/ransac_shapes.py) read the rule here and do not restate it. */
 int hak_op_ransac_shape(int npairs, int iterations, int* hp, int* hblocks);
+/* hak_debug_ransac_scratch: what the last hak_find_homography / hak_find_fundamental / hak_solve_pnp call (single or batch) on `ctx`
+ * left in the context's RANSAC scratch, so that the tests (tests/ransac_trace.py) see every hypothesis and every score block and not
+ * only the winner.  Synchronises the context's stream and launches nothing.
+ *   h_models  npairs * words_per_hypothesis * iterations 32-bit words, as they lie: [pair][word][iterations], word NW r + q = word q of
+ *             model r, the last word the mask of the models that exist (bit r = model r).  28 words per hypothesis for the fundamental
+ *             matrix (3 models of 9), 49 for P3P (4 models of 12); 0 for the homography, which keeps no models: nothing is copied and
+ *             h_models may be NULL.
+ *   h_slots   npairs * hblocks triples of int32 {inliers, hypothesis, model}: the best of each score block, [pair][block], decoded
+ *             from the block's key on the host; a block without a model gives {0, -1, 0}.
+ * npairs, iterations and hblocks (hak_op_ransac_shape) are those of that call.  Refused with a message: a NULL context, a NULL
+ * h_slots, a NULL h_models with words to copy, sizes out of range or beyond what the context's scratch holds. */
+int hak_debug_ransac_scratch(hak_ctx* ctx, int npairs, int words_per_hypothesis, int iterations, int hblocks, unsigned* h_models,
+                             int* h_slots);
 
 #ifdef __cplusplus
 }

@@ -19,7 +19,7 @@ import link_ref as lr
 import pnp_ref as pn
 import pose_ref as pr
 from test_gpu_fundamental import det, synth, torch, upload  # noqa: F401 (fixtures)
-from test_pnp_cpu import K_TABLE, FOCAL, H, W, corr_array, pairs, refusals
+from test_pnp_cpu import K_TABLE, FOCAL, H, W, PARITY_CASES, corr_array, pairs, parity_case, refusals
 from test_ransac_shapes_cpu import shape_of
 
 pytestmark = pytest.mark.gpu
@@ -161,6 +161,45 @@ def test_batch_ragged_bit_exact(ah, torch, det, ragged, iterations, hp):
             assert_same(out[k], masks[k, :len(lst)], s, sm[:len(lst)], ("batch vs single", k))
         bare = _pnp_batch(ah, torch, det, lists, stride, counts, K_TABLE, iterations, 1.0, 11, with_mask=False)
         assert bare[0].tobytes() == out.tobytes() and (bare[1] == 0xEE).all()
+
+
+def test_randomised_parity(ah, torch, det):
+    """the 150 seeded cases of test_pnp_cpu.parity_case -- sizes from 0 to 3000 and the LDS chunk edge, six scene families (general,
+    coplanar and rings, collinear, integer lattice, near or behind the centre of projection, far), five cameras, outliers, NaN / inf
+    rows, duplicates up to all-equal, the world scaled by 2^-20 .. 2^20 and offset by +-16000, iterations, thresholds, seeds 0 and
+    0xFFFFFFFF -- record and mask byte for byte against the statement, with and without a context; every third block of eight also
+    as one ragged hak_solve_pnp_batch call.  What the cases reach (0 .. 4 solutions, every rejection, ties, later solutions, no
+    model) is asserted in test_pnp_cpu.py; every hypothesis of them is compared in test_gpu_ransac_trace.py."""
+    fails = []
+    cases = [parity_case(k) for k in range(PARITY_CASES)]
+    wants = []
+    for k, c in enumerate(cases):
+        n = len(c["corr"])
+        want, wm = pn.solve_pnp(c["corr"], c["K"], c["iterations"], c["threshold"], c["seed"])
+        wants.append((want, wm))
+        got, gm = gpu_pnp(ah, torch, c["corr"], c["K"], c["iterations"], c["threshold"], c["seed"], ctx=det.ctx if c["ctx"] else None)
+        try:
+            assert_same(got, gm[:n], want, wm, (k, c["scene"], c["camera"]))
+            assert (gm[n:] == 0xEE).all(), (k, "written past the count")
+        except AssertionError as e:
+            fails.append(str(e)[:300])
+    groups = sorted({c["group"] for c in cases if c["group"] >= 0})
+    for g in groups:
+        ks = [k for k, c in enumerate(cases) if c["group"] == g]
+        c0 = cases[ks[0]]
+        lists = [cases[k]["corr"] for k in ks]
+        stride = max(1, max(len(lst) for lst in lists))
+        out, masks = _pnp_batch(ah, torch, det, lists, stride, [len(lst) for lst in lists], c0["K"], c0["iterations"], c0["threshold"],
+                                c0["seed"])
+        for slot, k in enumerate(ks):
+            n = len(lists[slot])
+            try:
+                assert_same(out[slot], masks[slot, :n], wants[k][0], wants[k][1], ("batch", g, k))
+                assert (masks[slot, n:] == 0xEE).all(), ("batch", g, k, "written past the count")
+            except AssertionError as e:
+                fails.append(str(e)[:300])
+    assert len(groups) >= 5
+    assert not fails, f"{len(fails)} differ: " + "; ".join(fails[:3])
 
 
 # ------------------------------------------------------------------------------------------------------------------- link

@@ -14,7 +14,7 @@ import fundamental_refit_ref as rr
 import pose_ref as pr
 from conftest import ROOT
 from test_gpu_fundamental import as_pairs, det, synth, torch, upload  # noqa: F401 (fixtures)
-from test_pose_cpu import TABLE, f32_model, first_winners, table_case
+from test_pose_cpu import PARITY_CASES, TABLE, f32_model, first_winners, parity_case, table_case
 
 pytestmark = pytest.mark.gpu
 
@@ -128,7 +128,7 @@ def test_every_candidate_wins(ah, torch, synth):
         assert got["candidate"] == c and got["in_front"] == len(recs)
 
 
-def _batch(ah, torch, det, lists, stride, records, K, thr, md, counts, extra=1, with_out=True):
+def _batch(ah, torch, det, lists, stride, records, K, thr, md, counts, extra=1, with_out=True, K2=None):
     """one hak_recover_pose_batch call; `extra` records past npairs are sentinels -> (records, masks, xyz bytes)"""
     np_ = len(lists)
     allp = np.zeros(np_ * stride, ah.MATCH_PAIR_DTYPE)
@@ -144,8 +144,9 @@ def _batch(ah, torch, det, lists, stride, records, K, thr, md, counts, extra=1, 
     d_mask = torch.full((np_ * stride,), 0xEE, dtype=torch.uint8, device="cuda")
     d_xyz = torch.full((np_ * stride * 12,), 0xEE, dtype=torch.uint8, device="cuda")
     k1 = ah.intrinsics(K)
+    k2 = k1 if K2 is None else ah.intrinsics(K2)
     ah.check(ah.lib.hak_recover_pose_batch(det.ctx, d.data_ptr(), stride, d_cnt.data_ptr(), np_, d_F.data_ptr(), k1.ctypes.data,
-                                           k1.ctypes.data, thr, md, d_out.data_ptr(), d_mask.data_ptr() if with_out else None,
+                                           k2.ctypes.data, thr, md, d_out.data_ptr(), d_mask.data_ptr() if with_out else None,
                                            d_xyz.data_ptr() if with_out else None))
     ah.check(ah.lib.hak_sync(det.ctx))
     raw = d_out.cpu().numpy()
@@ -184,6 +185,51 @@ def test_batch_ragged_equals_single_calls(ah, torch, synth, det):
             assert out[k]["candidate"] == -1 and out[k]["inliers"] == 0 and not masks[k, :900].any() and not xyz[k, :12 * 900].any()
     bare = _batch(ah, torch, det, lists, stride, records, K, 1.0, 9.0, counts, with_out=False)
     assert bare[0].tobytes() == out.tobytes() and (bare[1] == 0xEE).all() and (bare[2] == 0xEE).all()
+
+
+def test_randomised_parity(ah, torch, det):
+    """the 150 seeded cases of test_pose_cpu.parity_case -- sizes from 0 to 3000 with the block and chunk edges, six scene families
+    (general, sideways and forward translation, nearly pure rotation, planar, integer lattice under K = (1, 1, 0, 0)), matches at
+    infinity and behind the cameras, six kinds of model (planted, the statements' RANSAC and refit records, random, rank 1, zero),
+    negated, scaled by 2^-100 .. 2^100, with NaN / inf entries, K1 = K2 or not over five cameras, five depth limits, NaN rows,
+    duplicates, coordinates offset by +-16000 -- record, mask and points byte for byte against the statement, with and without a
+    context; every third block of eight also as one ragged hak_recover_pose_batch call with the records on the device, the ones
+    with hypothesis -1 included.  What the cases reach (every candidate, ties, every j3, every cause of "no pose", det <= 0, the
+    depth limit) is asserted in test_pose_cpu.py."""
+    fails = []
+    cases = [parity_case(k) for k in range(PARITY_CASES)]
+    for k, c in enumerate(cases):
+        n = len(c["recs"])
+        pairs = as_pairs(ah, c["recs"])
+        F = c["record"]["F"]
+        want, wm, wx = pr.recover_pose(pairs, F, c["K1"], c["K2"], c["threshold"], c["max_depth"])
+        got, gm, gx = gpu_pose(ah, torch, pairs, F, c["K1"], c["K2"], c["threshold"], c["max_depth"], ctx=det.ctx if c["ctx"] else None)
+        try:
+            assert_same(got, gm[:n], gx[:12 * n], want, wm, wx, (k, c["scene"], c["model"], c["depth"]))
+            assert (gm[n:] == 0xEE).all() and (gx[12 * n:] == 0xEE).all(), (k, "written past the count")
+        except AssertionError as e:
+            fails.append(str(e)[:300])
+    groups = sorted({c["group"] for c in cases if c["group"] >= 0})
+    broken = 0
+    for g in groups:
+        ks = [k for k, c in enumerate(cases) if c["group"] == g]
+        c0 = cases[ks[0]]
+        lists = [as_pairs(ah, cases[k]["recs"]) for k in ks]
+        records = [cases[k]["record"] for k in ks]
+        stride = max(1, max(len(lst) for lst in lists))
+        out, masks, xyz = _batch(ah, torch, det, lists, stride, records, c0["K1"], c0["threshold"], c0["max_depth"],
+                                 [len(lst) for lst in lists], K2=c0["K2"])
+        for slot, k in enumerate(ks):
+            n = len(lists[slot])
+            broken += records[slot]["hypothesis"] < 0
+            want, wm, wx = pr.recover_pose(lists[slot], records[slot], c0["K1"], c0["K2"], c0["threshold"], c0["max_depth"])
+            try:
+                assert_same(out[slot], masks[slot, :n], xyz[slot, :12 * n], want, wm, wx, ("batch", g, k))
+                assert (masks[slot, n:] == 0xEE).all() and (xyz[slot, 12 * n:] == 0xEE).all(), ("batch", g, k, "written past the count")
+            except AssertionError as e:
+                fails.append(str(e)[:300])
+    assert len(groups) >= 5 and broken >= 3
+    assert not fails, f"{len(fails)} differ: " + "; ".join(fails[:3])
 
 
 def test_chain_detect_match_fundamental_refine_pose(ah, torch, synth):
