@@ -119,6 +119,8 @@ SYMBOLS = {
     "hak_link_tracks_batch": (C.c_int, [_vp, _vp, C.c_long, _vp, C.c_int, _vp, _vp, _vp, C.c_long, _vp, C.c_int, C.c_int, _vp, C.c_long, _vp]),
     "hak_solve_pnp": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, C.c_float, C.c_uint, _vp, _vp]),
     "hak_solve_pnp_batch": (C.c_int, [_vp, _vp, C.c_long, _vp, C.c_int, _vp, C.c_int, C.c_float, C.c_uint, _vp, _vp]),
+    "hak_refine_pnp": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_float, C.c_int, _vp, _vp]),
+    "hak_refine_pnp_batch": (C.c_int, [_vp, _vp, C.c_long, _vp, C.c_int, _vp, C.c_float, C.c_int, _vp, _vp]),
     "hak_match_guided": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _fp, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _ip, _vp]),
     "hak_match_guided_batch": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp]),
     "hak_match_epipolar": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _fp, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _ip, _vp]),
@@ -780,4 +782,19 @@ def solvePnP(corr, K, iterations=1024, threshold=2.0, seed=0, akazer=None):
     out = np.zeros((), ABS_POSE_DTYPE)
     check(lib.hak_solve_pnp(ctx, d_c.data_ptr(), n, k.ctypes.data, int(iterations), float(threshold), int(seed) & 0xFFFFFFFF,
                             d_mask.data_ptr(), out.ctypes.data))
+    return out, d_mask[:n].cpu().numpy()
+
+
+def refinePnP(corr, K, record, threshold=2.0, rounds=3, akazer=None):
+    """Gauss-Newton refit of an absolute pose over its inliers, iterated up to `rounds` (1..8) times (hipakaze.h hak_refine_pnp), on
+    the device.  `corr` and K as solvePnP's; `record`: an ABS_POSE_DTYPE record, solvePnP's or an earlier refit's (it is not
+    modified).  Returns (record, inlier mask as a uint8 numpy array): record["solution"] == 4 when a refit was accepted, and
+    record["inliers"] is never below the input pose's count at `threshold`."""
+    import torch
+    ctx = akazer.ctx if akazer is not None else None
+    d_c, n = _device_records(corr, CORR3D_DTYPE)
+    k = intrinsics(K)
+    d_mask = torch.zeros(max(n, 1), dtype=torch.uint8, device="cuda")
+    out = np.array(record, ABS_POSE_DTYPE).reshape(())
+    check(lib.hak_refine_pnp(ctx, d_c.data_ptr(), n, k.ctypes.data, float(threshold), int(rounds), d_mask.data_ptr(), out.ctypes.data))
     return out, d_mask[:n].cpu().numpy()

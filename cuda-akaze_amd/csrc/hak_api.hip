@@ -1008,6 +1008,48 @@ extern "C" int hak_solve_pnp_batch(hak_ctx* c, const hak_corr3d* d_corr, long st
     return 0;
 }
 
+// ----------------------------------------------------------- Gauss-Newton refit of an absolute pose (kernels_pnprefit.hip)
+extern "C" int hak_refine_pnp(hak_ctx* c, const hak_corr3d* d_corr, int n, const hak_intrinsics* K, float threshold, int rounds,
+                              unsigned char* d_mask, hak_abs_pose* h_inout)
+{
+    if (list_args(h_inout, d_corr, n, "d_corr must be 16-byte aligned") || refine_args(threshold, rounds) || intrinsics_args(K))
+        return 1;
+    if (hak_device_count() == 0) return fail("no HIP device: libhipakaze has no CPU fallback");
+    // no scratch.  The record's device copy is the context's, or without a context a device global that calls take in turn:
+    // nothing is allocated
+    static std::mutex null_ctx_record;
+    std::unique_lock<std::mutex> turn(null_ctx_record, std::defer_lock);
+    hak_abs_pose* d_rec = nullptr;
+    if (c) {
+        if (geom_record(c)) return 1;
+        d_rec = reinterpret_cast<hak_abs_pose*>(c->geom_rec);
+    } else {
+        turn.lock();
+        d_rec = hak_pnp_refit_record();
+        if (!d_rec) return fail("hipGetSymbolAddress(pnp refit record)");
+    }
+    hipStream_t st = c ? c->stream : nullptr;
+    order_after_null_stream(c, st);
+    int rc = 0;
+    if (hipMemcpyAsync(d_rec, h_inout, sizeof(hak_abs_pose), hipMemcpyHostToDevice, st) != hipSuccess) rc = fail("record upload");
+    if (!rc) hak_launch_pnp_refit(st, d_corr, n, nullptr, n, 1, *K, threshold, rounds, d_rec, d_mask, 0);
+    return single_tail(rc, st, "pnp refit", "record download", h_inout, d_rec, sizeof(hak_abs_pose));
+}
+
+extern "C" int hak_refine_pnp_batch(hak_ctx* c, const hak_corr3d* d_corr, long stride, const int* d_counts, int npairs,
+                                    const hak_intrinsics* K, float threshold, int rounds, hak_abs_pose* d_inout,
+                                    unsigned char* d_masks)
+{
+    if (list_args_batch(c, d_corr, d_counts, d_inout, npairs, stride, "d_corr must be 16-byte aligned", "null context", "null argument",
+                        "npairs and the stride must be >= 1"))
+        return 1;
+    if (refine_args(threshold, rounds) || intrinsics_args(K)) return 1;
+    order_after_null_stream(c, c->stream);
+    hak_launch_pnp_refit(c->stream, d_corr, stride, d_counts, 0, npairs, *K, threshold, rounds, d_inout, d_masks, stride);
+    if (hipGetLastError() != hipSuccess) return fail("pnp refit launch failed");
+    return 0;
+}
+
 // ----------------------------------------------------------- guided matching (kernels_guided.hip; the rule: include/hipakaze.h)
 static int guided_args(float radius, int ratio_num, int ratio_den)
 {

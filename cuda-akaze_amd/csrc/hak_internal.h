@@ -810,6 +810,12 @@ long hak_pnp_words(int npairs, int iterations);
 void hak_launch_pnp(hipStream_t st, const hak_corr3d* corr, long stride, const int* counts, int n_host, int npairs,
                     const hak_intrinsics& K, int iterations, float threshold, unsigned seed, unsigned* models,
                     unsigned long long* slots, hak_abs_pose* out, unsigned char* masks, long mask_stride);
+// Gauss-Newton refit of an absolute pose (kernels_pnprefit.hip): record k is read from and rewritten to inout[k]; no scratch.
+// hak_pnp_refit_record(): the current device's one record for calls without a context (NULL on failure)
+hak_abs_pose* hak_pnp_refit_record();
+void hak_launch_pnp_refit(hipStream_t st, const hak_corr3d* corr, long stride, const int* counts, int n_host, int npairs,
+                          const hak_intrinsics& K, float threshold, int rounds, hak_abs_pose* inout, unsigned char* masks,
+                          long mask_stride);
 // track linking (kernels_pnp.hip): countsA / countsB NULL: nA_host / nB_host serve the only pair; `table`: npairs * max_index ints
 // of scratch, cleared by the launch; masksA may be NULL
 void hak_launch_link(hipStream_t st, const hak_match_pair* A, long strideA, const int* countsA, int stepA, int nA_host,

@@ -233,6 +233,30 @@ namespace akaze
         return r.hypothesis < 0 ? -1 : r.inliers;
     }
 
+    int cuRefinePnP(const hak_corr3d* corr, int n, const hak_intrinsics& K, float R[9], float t[3], unsigned char* inlier_mask,
+                    float threshold, int rounds)
+    {
+        if (n < 0 || (n > 0 && !corr) || !R || !t) { fprintf(stderr, "hip-akaze: cuRefinePnP: bad argument\n"); exit(-1); }
+        hak_corr3d* d_corr = nullptr;
+        unsigned char* d_mask = nullptr;
+        if (n > 0) {
+            if (hipMalloc((void**)&d_corr, sizeof(hak_corr3d) * (size_t)n) != hipSuccess) die("cuRefinePnP alloc");
+            if (inlier_mask && hipMalloc((void**)&d_mask, (size_t)n) != hipSuccess) die("cuRefinePnP alloc");
+            if (hak_memcpy_h2d(d_corr, corr, (long)(sizeof(hak_corr3d) * (size_t)n))) die("cuRefinePnP upload");
+        }
+        hak_abs_pose r{};
+        for (int k = 0; k < 9; k++) r.R[k] = R[k];
+        for (int k = 0; k < 3; k++) r.t[k] = t[k];
+        r.n = n;
+        if (hak_refine_pnp(NULL, d_corr, n, &K, threshold, rounds, d_mask, &r)) die("cuRefinePnP");
+        if (d_mask && hak_memcpy_d2h(inlier_mask, d_mask, n)) die("cuRefinePnP download");
+        for (int k = 0; k < 9; k++) R[k] = r.R[k];
+        for (int k = 0; k < 3; k++) t[k] = r.t[k];
+        if (d_mask) (void)hipFree(d_mask);
+        if (d_corr) (void)hipFree(d_corr);
+        return r.inliers;
+    }
+
     Akazer::Akazer() { hak_default_config(&cfg); }
 
     Akazer::~Akazer() { hak_destroy(ctx); }                              // akaze.cpp:74-77

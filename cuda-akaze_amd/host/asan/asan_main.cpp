@@ -64,6 +64,14 @@ int main()
             REQUIRE(cuRecoverPose(NULL, 0, F, K, K, R, t) == 0);
             F[7] = 0.f;                                                 // the stub's "no pose"
             REQUIRE(cuRecoverPose(pairs.data(), np, F, K, K, R, t, mask.data()) == -1 && t[0] == 0.f && mask[3] == 0);
+            std::vector<hak_corr3d> corr(np);                           // absolute pose and its refit: exact-size list and mask
+            for (int i = 0; i < np; i++) corr[i] = hak_corr3d{(float)i, 1.f, 5.f, pairs[i].x2, pairs[i].y2, i, i, 0};
+            REQUIRE(cuSolvePnP(corr.data(), np, K, R, t, mask.data()) == (np + 2) / 3 && mask[3] == 1 && mask[1] == 0 && t[2] == 1.f);
+            mask[3] = 0;
+            REQUIRE(cuRefinePnP(corr.data(), np, K, R, t, mask.data()) == (np + 2) / 3 && mask[3] == 1 && mask[1] == 0 && t[2] == 1.f);
+            REQUIRE(cuRefinePnP(corr.data(), np, K, R, t) == (np + 2) / 3);
+            REQUIRE(cuRefinePnP(corr.data(), 3, K, R, t, mask.data()) == 0 && mask[0] == 0);
+            REQUIRE(cuRefinePnP(NULL, 0, K, R, t) == 0);
         }
         cuMatch(d1, hostless);                                      // train side without a host buffer
         d2.num_pts = 0;

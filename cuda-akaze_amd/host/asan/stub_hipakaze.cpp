@@ -205,8 +205,27 @@ int hak_solve_pnp(hak_ctx*, const hak_corr3d* d, int n, const hak_intrinsics* K,
     }
     return 0;
 }
-// the HIP runtime calls of cuMatchKnn, cuFindHomography, cuFindFundamental, cuRefineFundamental, cuRecoverPose, cuLinkTracks and
-// cuSolvePnP
+// as hak_solve_pnp's stub: every record read, every mask byte written, the record rewritten in place with solution = 4
+int hak_refine_pnp(hak_ctx*, const hak_corr3d* d, int n, const hak_intrinsics* K, float threshold, int rounds, unsigned char* mask,
+                   hak_abs_pose* inout)
+{
+    if (!inout || !K || (n > 0 && !d) || rounds < 1 || rounds > 8 || !(threshold > 0.f) || K->fx == 0.f || K->fy == 0.f) {
+        g_err = "bad argument";
+        return 1;
+    }
+    const bool model = inout->hypothesis >= 0 && n >= 4;
+    inout->inliers = 0;
+    inout->solution = model ? 4 : inout->solution;
+    inout->n = n;
+    for (int i = 0; i < n; i++) {
+        const bool in = model && d[i].X == d[i].X && i % 3 == 0;
+        inout->inliers += in;
+        if (mask) mask[i] = in;
+    }
+    return 0;
+}
+// the HIP runtime calls of cuMatchKnn, cuFindHomography, cuFindFundamental, cuRefineFundamental, cuRecoverPose, cuLinkTracks,
+// cuSolvePnP and cuRefinePnP
 hipError_t hipMalloc(void** p, size_t n) { *p = malloc(n); return *p ? hipSuccess : hipErrorOutOfMemory; }
 hipError_t hipFree(void* p) { free(p); return hipSuccess; }
 }

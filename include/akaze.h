@@ -60,6 +60,12 @@ namespace akaze
     // when there is no model.
     int cuSolvePnP(const hak_corr3d* corr, int n, const hak_intrinsics& K, float R[9], float t[3], unsigned char* inlier_mask = nullptr,
                    int iterations = 1024, float threshold = 2.f, unsigned seed = 0);
+    // cuRefinePnP (hak_refine_pnp): Gauss-Newton refit of an absolute pose over its inliers among the host correspondences, iterated
+    // up to `rounds` (1..8) times, on the device: R and t (e.g. cuSolvePnP's, when that found a model) are replaced by the refitted
+    // pose when that scores at least as well at `threshold`, the optional inlier_mask (n bytes) gets the inliers of the returned
+    // pose, and the return value is their count -- never fewer than the given pose had at that threshold.
+    int cuRefinePnP(const hak_corr3d* corr, int n, const hak_intrinsics& K, float R[9], float t[3], unsigned char* inlier_mask = nullptr,
+                    float threshold = 2.f, int rounds = 3);
 
     // build-side addition: guided matching (hak_match_guided) -- re-matches result1 against result2 under a homography H (row-major,
     // (x1, y1, 1) -> image 2, e.g. cuFindHomography's): every keypoint of result1 is searched only among the keypoints of result2

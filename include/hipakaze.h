@@ -477,8 +477,8 @@ int hak_recover_pose_batch(hak_ctx* ctx, const hak_match_pair* d_matches, long s
  *      for every inlier of the winner, 0 otherwise (n bytes).  No model at all: the no-model record (R = identity, t = 0,
  *      inliers = 0, hypothesis = -1, solution = 0, n) and an all-zero mask.
  * Every value reduced across lanes is an integer count, so the result does not depend on the launch shape.
- * Limits: the result is the three-point winner, fitted to three noisy points; a least-squares (Gauss-Newton) refit over its
- * inliers is the next stage and not part of this one.  A root at which q touches zero without changing sign (a tangent double
+ * Limits: the result is the three-point winner, fitted to three noisy points; the least-squares (Gauss-Newton) refit over its
+ * inliers is the next stage, hak_refine_pnp below.  A root at which q touches zero without changing sign (a tangent double
  * root) is missed by design.  No lens distortion, no skew.
  * Refused with a non-zero status and a message before any device is touched: iterations outside 1..65536, a threshold that is not
  * finite or not > 0, fx or fy not finite or 0, a non-finite cx or cy, a count < 0 (or >= 2^30 for the link), a NULL list with a
@@ -496,7 +496,7 @@ typedef struct hak_abs_pose {
     float t[3];              /* in the units of X */
     int   inliers;           /* inliers of (R, t) */
     int   hypothesis;        /* winning hypothesis, -1 = no model (R = identity, t = 0, inliers = 0) */
-    int   solution;          /* which positive root of the winner's quartic (0..3) */
+    int   solution;          /* which positive root of the winner's quartic, 0..3; 4 = refitted by hak_refine_pnp */
     int   n;                 /* correspondences considered */
 } hak_abs_pose;              /* 64 bytes */
 /* one pair of lists, synchronous; ctx may be NULL (default stream; the call allocates its own table).  d_maskA may be NULL; d_out
@@ -510,7 +510,7 @@ int hak_link_tracks(hak_ctx* ctx, const hak_match_pair* d_A, int nA, const unsig
  * hak_match_knn2_batch / hak_recover_pose_batch over a detect batch of image pairs (I0, I1), (I1, I2), .. -- d_A = d_matches,
  * d_B = d_matches + max_pts, d_countsA = d_counts, d_countsB = d_counts + 1, strides 2*max_pts, count steps 2 -- pair 2j links to
  * pair 2j+1, and detect batch -> hak_match_knn2_batch -> hak_find_fundamental_batch -> hak_refine_fundamental_batch ->
- * hak_recover_pose_batch -> hak_link_tracks_batch -> hak_solve_pnp_batch needs no host synchronisation. */
+ * hak_recover_pose_batch -> hak_link_tracks_batch -> hak_solve_pnp_batch -> hak_refine_pnp_batch needs no host synchronisation. */
 int hak_link_tracks_batch(hak_ctx* ctx, const hak_match_pair* d_A, long strideA, const int* d_countsA, int count_stepA,
                           const unsigned char* d_masksA, const float* d_xyzA, const hak_match_pair* d_B, long strideB,
                           const int* d_countsB, int count_stepB, int npairs, hak_corr3d* d_out, long out_stride, int* d_counts);
@@ -523,6 +523,59 @@ int hak_solve_pnp(hak_ctx* ctx, const hak_corr3d* d_corr, int n, const hak_intri
 int hak_solve_pnp_batch(hak_ctx* ctx, const hak_corr3d* d_corr, long stride, const int* d_counts, int npairs,
                         const hak_intrinsics* K, int iterations, float threshold, unsigned seed, hak_abs_pose* d_out,
                         unsigned char* d_masks);
+
+/* ---- Gauss-Newton refit of the absolute pose over its inliers, iterated (build-side addition; the stage behind hak_solve_pnp).
+ * The three-point winner is fitted to three noisy correspondences; the refit minimises the reprojection error over all of its
+ * inliers, re-scores, and repeats from the larger inlier set.  A pure function of (corr, input record, K, threshold, rounds);
+ * tests/pnp_refit_ref.py is its bit-exact numpy statement.  float64, no FMA, + - * / only, except where float32 is named; records
+ * are read as by hak_solve_pnp (a record with a non-finite field is never an inlier and enters no sum).
+ *   0. 1 <= rounds <= 8, threshold finite and > 0, t2 = threshold * threshold in float32.  A record with hypothesis < 0 or a
+ *      non-finite entry of R or t has no model: the output is hak_solve_pnp's no-model record (R = identity, t = 0, inliers 0,
+ *      hypothesis -1, solution 0, n) and an all-zero mask.  Otherwise cur = (R, t) as float32 and cnt = the inliers of cur by step 6
+ *      of hak_solve_pnp at THIS call's t2.  Steps 1-5 repeat up to `rounds` times and stop at the first round that fails or is not
+ *      accepted.
+ *   1. I = the inliers of cur, m = |I|.  The round fails if m < 4.
+ *   2. Per inlier, M = cur and K widened to float64: xc = ((M0 X + M1 Y) + M2 Z) + t0, yc = ((M3 X + M4 Y) + M5 Z) + t1,
+ *      zc = ((M6 X + M7 Y) + M8 Z) + t2; iz = 1 / zc, a = xc iz, b = yc iz; residuals rx = (fx a + cx) - u, ry = (fy b + cy) - v;
+ *      px = fx iz, py = fy iz.  The Jacobian rows with respect to the left perturbation Xc' = Xc + w x Xc + dt, unknowns
+ *      (w0, w1, w2, dt0, dt1, dt2):
+ *        jx = [ -((px a) yc), px zc + (px a) xc, -(px yc), px, 0, -(px a) ]
+ *        jy = [ (-(py zc)) - (py b) yc, (py b) xc, py xc, 0, py, -(py b) ]
+ *   3. The 21 sums N[p][q] += jx[p] jx[q] + jy[p] jy[q], p <= q, mirrored afterwards, and the 6 sums g[p] += -(jx[p] rx + jy[p] ry),
+ *      over I in the order of hak_find_homography's refit: lane l of one wave takes the correspondences i = l (mod 64) in ascending
+ *      i, non-inliers skipped, every partial sum starting from 0.0; then an xor butterfly over 32, 16, .., 1.
+ *   4. [N | g] (6 x 7) is solved by Gaussian elimination with partial pivoting exactly as step 5 of hak_find_homography solves its
+ *      8 x 9 system: the pivot of column c is the largest |entry| of rows c..5, ties to the smallest row; the round fails if it is
+ *      0 or non-finite; f = M[r][c] / M[c][c], M[r][q] = M[r][q] - f M[c][q]; back substitution i = 5..0 with the subtractions in
+ *      ascending j.  The solution is d; the round fails if an entry of d is non-finite.
+ *   5. Update by the Cayley map (rational: no sin / cos, an exact rotation up to rounding): w = 0.5 (d0, d1, d2),
+ *      ww = (w0 w0 + w1 w1) + w2 w2, k = 1 - ww, den = 1 + ww,
+ *        C = [ k + 2 (w0 w0), 2 (w0 w1 - w2), 2 (w0 w2 + w1);  2 (w0 w1 + w2), k + 2 (w1 w1), 2 (w1 w2 - w0);
+ *              2 (w0 w2 - w1), 2 (w1 w2 + w0), k + 2 (w2 w2) ], every entry divided by den;
+ *      R' = C R and t' = C t + (d3, d4, d5), every entry (c0 r0 + c1 r1) + c2 r2 (then + d for t'), rounded to float32; the round
+ *      fails if anything is non-finite.  cnt' = the inliers of (R', t').  The round is accepted iff cnt' >= cnt; then
+ *      cur = (R', t'), cnt = cnt'.
+ *   6. Output: R, t = cur, inliers = cnt, hypothesis unchanged, n = the correspondences considered, solution = 4 if a round was
+ *      accepted and the input's otherwise; the optional mask gets the inliers of cur at this call's threshold.  So inliers never
+ *      falls below the input pose's count at the same threshold, and a refitted record may be passed in again.
+ * Limits: an unweighted reprojection-error minimum over a hard inlier set -- no robust kernel, no damping (plain Gauss-Newton, one
+ * step per round), no refinement of the 3-D points or of K.  R is re-rounded to float32 every round and is not re-orthonormalised
+ * (the drift after 8 rounds is of the order of 1e-7 in |R R^T - I|).  Coplanar or near-collinear inlier sets give an
+ * ill-conditioned N; nothing rescues the round: it scores badly and is rejected.
+ * Refused with a non-zero status and a message before any device is touched: rounds outside 1..8, a threshold that is not finite
+ * or not > 0, fx or fy not finite or 0, a non-finite cx or cy, NULL K, n < 0, a NULL list with n > 0, a list that is not 16-byte
+ * aligned, NULL h_inout / d_inout / d_counts, npairs < 1, stride < 1, a NULL context for the batch form.
+ * Device code: csrc/kernels_pnprefit.hip. */
+/* one list, synchronous; ctx may be NULL (default stream; the call needs no scratch and allocates nothing: calls without a
+ * context share one device-resident record and take it in turn).  K is a host argument.  *h_inout (host): in = a record of
+ * hak_solve_pnp or of an earlier refit, out = the result; d_mask (device, n bytes) may be NULL */
+int hak_refine_pnp(hak_ctx* ctx, const hak_corr3d* d_corr, int n, const hak_intrinsics* K, float threshold, int rounds,
+                   unsigned char* d_mask, hak_abs_pose* h_inout);
+/* batched, asynchronous on the context's stream, layouts as hak_solve_pnp_batch; K is a host argument, the same for every list;
+ * d_inout[k] (device) is read and rewritten in place, so .. -> hak_link_tracks_batch -> hak_solve_pnp_batch ->
+ * hak_refine_pnp_batch needs no host synchronisation */
+int hak_refine_pnp_batch(hak_ctx* ctx, const hak_corr3d* d_corr, long stride, const int* d_counts, int npairs,
+                         const hak_intrinsics* K, float threshold, int rounds, hak_abs_pose* d_inout, unsigned char* d_masks);
 
 /* ---- guided matching: re-match a pair under its estimated homography (build-side addition; the stage behind
  * hak_find_homography).  The 2-NN search of hak_match_knn2 looks at the whole other image, so on repetitive texture its ratio
