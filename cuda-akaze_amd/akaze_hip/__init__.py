@@ -197,6 +197,7 @@ TEST_SYMBOLS = {
     "hak_op_hess_probe": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "hak_debug_fill_match_scratch": (C.c_int, [_vp, C.c_int]),
     "hak_op_ransac_shape": (C.c_int, [C.c_int, C.c_int, _ip, _ip]),
+    "hak_op_match_shape": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _ip]),
     "hak_debug_ransac_scratch": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp]),
     "hak_op_gather_probe": (C.c_int, [C.c_long, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]),
 }

@@ -632,6 +632,8 @@ extern "C" int hak_match_knn2(hak_ctx* c, hak_point* d_pts1, int n1, const hak_p
     if (!d_pts1 || (!d_pts2 && n2 > 0) || !count) return fail("null argument");
     if (ratio_num <= 0 || ratio_den <= 0) return fail("ratio must be a positive fraction");
     if (h_out && !d_out) return fail("h_out needs d_out");
+    // (both sets are a train set once: the reverse search of the cross-check packs query indices into the same key)
+    if (!hak_mkey_fits(n1) || !hak_mkey_fits(n2)) return fail("more than 2^20 - 1 points");
     *count = 0;
     if (n1 <= 0) return 0;
     if (max_dist <= 0) max_dist = HAK_MAX_DIST;
@@ -665,9 +667,10 @@ extern "C" int hak_match_knn2_batch(hak_ctx* c, hak_point* d_points, const int* 
     if (2 * npairs > c->cfg.batch + 1) return fail("npairs exceeds the context's batch capacity");
     if (ratio_num <= 0 || ratio_den <= 0) return fail("ratio must be a positive fraction");
     if (max_dist <= 0) max_dist = HAK_MAX_DIST;
+    const long mp = c->cfg.max_pts;
+    if (!hak_mkey_fits(mp)) return fail("max_pts must stay below 2^20 for the matcher");
     if (knn_scratch(c)) return 1;
     order_after_null_stream(c, c->stream);
-    const long mp = c->cfg.max_pts;
     int4* fwd = c->knn;
     int4* rev = c->knn + (size_t)((c->cfg.batch + 1) / 2) * mp;
     { ProfScope ps(c, HAK_PROF_MATCH);

@@ -725,6 +725,23 @@ struct HakMatchScratch {
 // users of the buffers ran on (synchronised before a buffer is replaced).
 bool hak_match_scratch_reserve(HakMatchScratch* sc, hipStream_t st, long keys, long tickets, long parts, long knn, long blks);
 void hak_match_scratch_free(HakMatchScratch* sc);
+// What a search or the 2-NN finish launches for a call -- decided in ONE host function (hak_match_plan) that touches no device;
+// hak_launch_match, hak_launch_knn2 and hak_launch_knn2_finish launch what it says (their one decision left: a sliced plan whose
+// scratch cannot be reserved runs unsliced), and the test ABI
+// (hak_op_match_shape) hands the same plan to the tests, which assert with it that a case reached the path it was made for.
+struct HakMatchPlan {
+    int kernel = 0;             // 0: k_match_mfma (matrix cores); 1: the vector-pipe kernels k_match / k_knn2
+    int qt = 1;                 // k_match_mfma: query tiles per wave; k_match: queries per thread
+    int gx = 1;                 // grid.x: query blocks
+    int slices = 1;             // train-set slices; 1: not sliced
+    int rows_per_slice = 0;     // rows of a slice cut on the host; 0: not sliced, or cut inside the kernel (device-side counts)
+    int chunks_per_slice = 0;   // LDS chunks one block pass stages (k_match_mfma: 192 rows, a tail counts; k_match: tiles of 128) --
+                                // of the whole set when not sliced, of the capacity with device-side counts
+    int finish_blocks = 1;      // 2-NN accept rule + compaction: 1 = one block per pair, > 1 = two passes of that many blocks
+};
+// search: 0 = hak_launch_match, 1 = hak_launch_knn2 (queries n1_host, train set n2_host; with device-side counts both carry the
+// CAPACITY of a set); finish_blocks is hak_launch_knn2_finish's for n1_host queries.  scratch: a HakMatchScratch is at hand.
+HakMatchPlan hak_match_plan(const HakMatchKnobs& mk, int search, bool device_counts, int n1_host, int n2_host, int npairs, bool scratch);
 void hak_launch_match(hipStream_t st, hak_point* pts1, const hak_point* pts2, const int* n1_dev, const int* n2_dev,
                       int n1_host, int n2_host, long pair_stride1, long pair_stride2, int npairs,
                       HakMatchScratch* scratch = nullptr);

@@ -780,6 +780,19 @@ extern "C" int hak_op_ransac_shape(int npairs, int iterations, int* hp, int* hbl
     return 0;
 }
 
+// the launch plan of a matcher call: hak_match_plan with the environment's knobs and nothing else, no device
+extern "C" int hak_op_match_shape(int search, int n1, int n2, int npairs, int device_counts, int capacity, int scratch, int* plan)
+{
+    if (!plan) return fail("null argument");
+    if (search < 0 || search > 1 || n1 < 0 || n2 < 0 || npairs < 1 || capacity < 0) return fail("search must be 0 or 1, counts >= 0, npairs >= 1");
+    // (with device-side counts the launchers see the capacity in the place of both counts)
+    const HakMatchPlan p = hak_match_plan(hak_match_knobs_from_env(), search, device_counts != 0, device_counts ? capacity : n1,
+                                          device_counts ? capacity : n2, npairs, scratch != 0);
+    const int v[7] = {p.kernel, p.qt, p.gx, p.slices, p.rows_per_slice, p.chunks_per_slice, p.finish_blocks};
+    memcpy(plan, v, sizeof(v));
+    return 0;
+}
+
 // the RANSAC scratch of the last H, F or P3P call on the context, as that call left it: the models words [pair][word][iterations]
 // (ransac_common.h) as they lie, and every score block's slot decoded here by rs_decode's rule, so that no test restates the key.
 // Launches nothing.

@@ -877,15 +877,100 @@ static int mfma_slices(int gx, int n2, int* rows_per_slice, int want_blocks, int
     return (tiles + tps - 1) / tps;
 }
 
-// One big pair with host-side counts whose query blocks alone cannot fill the chip: the slices of its train set for k_match_mfma,
-// their tickets and summaries reserved in `sc`; 1: the pair is not sliced (no scratch, the query blocks suffice or cover fewer than
-// nq queries, too few tiles, out of memory).  The same decision for both searches.
-static int mm_single_pair_slices(HakMatchScratch* sc, hipStream_t st, const HakMatchKnobs& mk, int gx, int nq, int n2, int* rows_per_slice)
+// One big pair with host-side counts whose query blocks alone cannot fill the chip: the slices of its train set for k_match_mfma;
+// 1: the pair is not sliced (the query blocks suffice or cover fewer than nq queries, too few tiles).  The same decision for both
+// searches.
+static int mm_single_pair_slices(const HakMatchKnobs& mk, int gx, int nq, int n2, int* rows_per_slice)
 {
     const int qpb = 128 * mk.qt;
-    if (!sc || gx >= 384 || (long)gx * qpb < nq) return 1;
-    const int slices = mfma_slices(gx, n2, rows_per_slice, mk.qt == 2 ? 256 : 512, mk.slices);
-    return slices > 1 && hak_match_scratch_reserve(sc, st, 0, gx, (long)slices * gx * qpb, 0, 0) ? slices : 1;
+    if (gx >= 384 || (long)gx * qpb < nq) return 1;
+    return mfma_slices(gx, n2, rows_per_slice, mk.qt == 2 ? 256 : 512, mk.slices);
+}
+
+// LDS chunks of MM_BCH rows (a tail counts) that one block pass of k_match_mfma over `rows` rows stages
+static int mm_chunks(int rows) { return rows < 1 ? 0 : (rows + MM_BCH - 1) / MM_BCH; }
+
+// blocks of the 2-NN accept rule + compaction for n1_host queries (hak_launch_knn2_finish): big single pairs with host-side counts
+// take two passes of one block per 1024 queries (k_knn2_finish_a / _b, which need the scratch's counters), everything else one
+// block per pair (k_knn2_finish)
+static int knn2_finish_blocks(bool device_counts, int n1_host, int npairs, bool scratch)
+{
+    const int nb = (n1_host + 1023) / 1024;
+    return scratch && !device_counts && npairs == 1 && nb > 1 ? nb : 1;
+}
+
+// Every launch decision of the matcher (HakMatchPlan, hak_internal.h).  Host arithmetic only: the launchers below and the test ABI
+// (hak_op_match_shape) both ask here.
+// Big single pairs (hak_match with host-side counts, e.g. 10k x 10k) are SLICED: the train set is cut so that query blocks x
+// slices fill the chip; the slices merge through the scratch (HakMatchScratch: owned by the calling context or handed out by
+// hak_api.hip's per-device pool -- never a process-wide pointer that could belong to another device).
+HakMatchPlan hak_match_plan(const HakMatchKnobs& mk, int search, bool device_counts, int n1_host, int n2_host, int npairs, bool scratch)
+{
+    HakMatchPlan p;
+    const int qt = mk.qt, qpb = 128 * qt;
+    p.finish_blocks = knn2_finish_blocks(device_counts, n1_host, npairs, scratch);
+    if (search == 1) {
+        // (with device-side counts n1_host / n2_host carry the CAPACITY of the sets)
+        if (mk.valu == 0 && n2_host <= MM_MAX_ROWS) {
+            // the matrix-core kernel with its 2-NN epilogue
+            p.kernel = 0; p.qt = qt;
+            p.gx = hak_grid_x(device_counts ? (qt == 2 ? 43 : 83) : (n1_host + qpb - 1) / qpb);
+            int rps = 0;
+            const int slices = scratch && !device_counts && npairs == 1 ? mm_single_pair_slices(mk, p.gx, n1_host, n2_host, &rps) : 1;
+            if (slices > 1) { p.slices = slices; p.rows_per_slice = rps; }
+            p.chunks_per_slice = mm_chunks(slices > 1 ? rps : n2_host);
+            return p;
+        }
+        p.kernel = 1; p.qt = 1;
+        p.gx = hak_grid_x(device_counts ? 640 : (n1_host + MQ - 1) / MQ);
+        return p;                                                   // (k_knn2 reads the records from memory: no LDS chunks)
+    }
+    // k_match_mfma: a wave = 32 QT queries x the train set, four waves per block.  HAK_MATCH_VALU=1: the VALU / LDS kernel k_match
+    const bool valu = mk.valu != 0 || n2_host > MM_MAX_ROWS;       // (device-side counts: n2_host = the capacity)
+    const int nq = device_counts ? 0 : n1_host;
+    const bool two = device_counts ? npairs >= 8 : (long)((nq + 2 * MQ - 1) / (2 * MQ)) * npairs >= 2048;    // (k_match only: queries per thread)
+    const int qb = valu ? (two ? 2 * MQ : MQ) : qpb;                // queries per block
+    // device-side counts: k_match loops over the queries; k_match_mfma gets blocks for 10 240 queries (waves past n1 leave at once)
+    // (83 / 43, not 80 / 40: blocks go to the eight XCDs by linear index mod 8, and with a multiple of 8 per pair the blocks of every
+    // pair that find queries would land on the same XCDs pair after pair -- two XCDs with three of them, six with two: 1.33 x the mean)
+    int gx = hak_grid_x(device_counts ? (valu ? (two ? 320 : 640) : (qt == 2 ? 43 : 83)) : (nq + qb - 1) / qb);
+    // with device-side counts n1_host carries the CAPACITY of a query set (the context's max_pts; 0: unknown).  The sliced path
+    // below gives every query block its own ticket and partial-result rows, so its grid must cover the capacity -- the plain
+    // kernel's blocks loop over the queries and need no such bound.
+    const int cap_blocks = device_counts && n1_host > 0 ? (n1_host + qpb - 1) / qpb : 0;
+    p.kernel = valu ? 1 : 0;
+    p.qt = valu ? (two ? 2 : 1) : qt;
+    p.gx = gx;
+    p.chunks_per_slice = valu ? (n2_host + MT - 1) / MT : mm_chunks(n2_host);
+    // one pair with host-side counts whose query blocks alone cannot fill the chip: slice the train set as well
+    if (scratch && !device_counts && npairs == 1 && (long)gx * qb >= nq) {
+        int rps = 0;
+        const int mslices = valu ? 1 : mm_single_pair_slices(mk, gx, nq, n2_host, &rps);
+        if (mslices > 1) {
+            p.slices = mslices; p.rows_per_slice = rps; p.chunks_per_slice = mm_chunks(rps);
+            return p;
+        }
+        const int tiles = (n2_host + MT - 1) / MT;
+        if (valu && !two && gx < 2048 && tiles >= 4) {
+            int slices = (2048 + gx - 1) / gx;
+            if (slices > tiles / 2) slices = tiles / 2;
+            const int tps = (tiles + slices - 1) / slices;
+            slices = (tiles + tps - 1) / tps;
+            if (slices > 1) {
+                p.slices = slices; p.rows_per_slice = tps * MT; p.chunks_per_slice = tps;
+                return p;
+            }
+        }
+    }
+    // few pairs with device-side counts (the pair call, batches of a handful of images): few of a pair's blocks find queries,
+    // each walks the whole train set while most of the chip idles -- slice the train sets as for one big pair
+    if (!valu && scratch && device_counts && npairs <= 12 && cap_blocks > 0 && cap_blocks <= 4096) {
+        if (cap_blocks > gx) p.gx = cap_blocks | 3;                 // (odd, as 83: not a multiple of the eight XCDs)
+        p.slices = (npairs <= 2 ? 8 : npairs <= 4 ? 4 : npairs <= 8 ? 3 : 2) * (qt == 2 ? 2 : 1);
+        p.rows_per_slice = 0;                                       // (cut inside the kernel from the count on the device)
+        p.chunks_per_slice = mm_chunks((((n2_host + 31) >> 5) + p.slices - 1) / p.slices * 32);
+    }
+    return p;
 }
 
 // (qt: query tiles per wave of k_match_mfma, HakMatchKnobs::qt)
@@ -896,28 +981,25 @@ static void mm_launch(int qt, dim3 grid, hipStream_t st, A... a)
     else k_match_mfma<KNN, 1><<<grid, 256, 0, st>>>(a...);
 }
 
+// (a sliced plan whose scratch cannot be reserved -- out of device memory -- runs unsliced on the same grid)
 void hak_launch_knn2(hipStream_t st, const hak_point* ptsA, const hak_point* ptsB, const int* nA_dev, const int* nB_dev,
                      int nA_host, int nB_host, long strideA, long strideB, int npairs, int4* out, long out_stride, HakMatchScratch* sc)
 {
     const HakMatchKnobs mk = hak_match_knobs_from_env();           // (per call, as in hak_launch_match)
-    // (with device-side counts nA_host / nB_host carry the CAPACITY of the sets)
-    if (mk.valu == 0 && nB_host <= MM_MAX_ROWS) {
-        // the matrix-core kernel with its 2-NN epilogue (the point records are only read: ptsA is not written)
-        const int qt = mk.qt, qpb = 128 * qt;
-        const int gx = hak_grid_x(nA_dev ? (qt == 2 ? 43 : 83) : (nA_host + qpb - 1) / qpb);
-        int rps = 0;
-        const int slices = !nA_dev && npairs == 1 ? mm_single_pair_slices(sc, st, mk, gx, nA_host, nB_host, &rps) : 1;
-        if (slices > 1) {
-            mm_launch<true>(qt, dim3(gx, slices), st, const_cast<hak_point*>(ptsA), ptsB, (const int*)nullptr, (const int*)nullptr, nA_host, nB_host, 0L, 0L,
-                            2, rps, out, 0L, sc->ticket, sc->part, gx * qpb);
+    const HakMatchPlan p = hak_match_plan(mk, 1, nA_dev != nullptr, nA_host, nB_host, npairs, sc != nullptr);
+    if (p.kernel == 0) {
+        // (the point records are only read: ptsA is not written)
+        const int qpb = 128 * p.qt;
+        if (p.slices > 1 && hak_match_scratch_reserve(sc, st, 0, p.gx, (long)p.slices * p.gx * qpb, 0, 0)) {
+            mm_launch<true>(p.qt, dim3(p.gx, p.slices), st, const_cast<hak_point*>(ptsA), ptsB, (const int*)nullptr, (const int*)nullptr, nA_host, nB_host, 0L, 0L,
+                            2, p.rows_per_slice, out, 0L, sc->ticket, sc->part, p.gx * qpb);
             return;
         }
-        mm_launch<true>(qt, dim3(gx, npairs), st, const_cast<hak_point*>(ptsA), ptsB, nA_dev, nB_dev, nA_host, nB_host, strideA, strideB,
+        mm_launch<true>(p.qt, dim3(p.gx, npairs), st, const_cast<hak_point*>(ptsA), ptsB, nA_dev, nB_dev, nA_host, nB_host, strideA, strideB,
                         2, 0, out, out_stride, (int*)nullptr, (uint2*)nullptr, 0);
         return;
     }
-    const int gx = hak_grid_x(nA_dev ? 640 : (nA_host + MQ - 1) / MQ);
-    k_knn2<<<dim3(gx, npairs), 256, 0, st>>>(ptsA, ptsB, nA_dev, nB_dev, nA_host, nB_host, strideA, strideB, 2, out, out_stride);
+    k_knn2<<<dim3(p.gx, npairs), 256, 0, st>>>(ptsA, ptsB, nA_dev, nB_dev, nA_host, nB_host, strideA, strideB, 2, out, out_stride);
 }
 
 void hak_launch_knn2_finish(hipStream_t st, hak_point* pts1, const hak_point* pts2, const int* n1_dev, int n1_host, long stride1,
@@ -925,8 +1007,8 @@ void hak_launch_knn2_finish(hipStream_t st, hak_point* pts1, const hak_point* pt
                             int ratio_den, int cross, int max_dist, hak_match_pair* out, long out_stride, int* out_count,
                             HakMatchScratch* sc)
 {
-    const int nb = (n1_host + 1023) / 1024;
-    if (sc && !n1_dev && npairs == 1 && nb > 1 && hak_match_scratch_reserve(sc, st, 0, 0, 0, 0, nb)) {
+    const int nb = knn2_finish_blocks(n1_dev != nullptr, n1_host, npairs, sc != nullptr);
+    if (nb > 1 && hak_match_scratch_reserve(sc, st, 0, 0, 0, 0, nb)) {
         k_knn2_finish_a<<<nb, 1024, 0, st>>>(pts1, pts2, n1_host, fwd, rev, ratio_num, ratio_den, cross, max_dist, sc->blk);
         k_knn2_finish_b<<<nb, 1024, 0, st>>>(pts1, pts2, n1_host, fwd, rev, ratio_num, ratio_den, cross, max_dist, sc->blk, out, out_count,
                                              sc->h_cnt);
@@ -936,63 +1018,32 @@ void hak_launch_knn2_finish(hipStream_t st, hak_point* pts1, const hak_point* pt
                                            ratio_den, cross, max_dist, out, out_stride, out_count, 1);
 }
 
-// Big single pairs (hak_match with host-side counts, e.g. 10k x 10k) are SLICED: the train set is cut so that query blocks x
-// slices fill the chip; the slices merge through `scratch` (HakMatchScratch: owned by the calling context or handed out by
-// hak_api.hip's per-device pool -- never a process-wide pointer that could belong to another device).
 void hak_launch_match(hipStream_t st, hak_point* pts1, const hak_point* pts2, const int* n1_dev, const int* n2_dev,
                       int n1_host, int n2_host, long pair_stride1, long pair_stride2, int npairs, HakMatchScratch* sc)
 {
-    // k_match_mfma: a wave = 32 QT queries x the train set, four waves per block.  HAK_MATCH_VALU=1: the VALU / LDS kernel k_match
     const HakMatchKnobs mk = hak_match_knobs_from_env();           // (per call: the tests run both kernels in one process)
-    const bool valu = mk.valu != 0 || n2_host > MM_MAX_ROWS;       // (device-side counts: n2_host = the capacity)
-    const int qt = mk.qt, qpb = 128 * qt;
-    const int nq = n1_dev ? 0 : n1_host;
-    const bool two = n1_dev ? npairs >= 8 : (long)((nq + 2 * MQ - 1) / (2 * MQ)) * npairs >= 2048;    // (k_match only: queries per thread)
-    const int qb = valu ? (two ? 2 * MQ : MQ) : qpb;                // queries per block
-    // device-side counts: k_match loops over the queries; k_match_mfma gets blocks for 10 240 queries (waves past n1 leave at once)
-    // (83 / 43, not 80 / 40: blocks go to the eight XCDs by linear index mod 8, and with a multiple of 8 per pair the blocks of every
-    // pair that find queries would land on the same XCDs pair after pair -- two XCDs with three of them, six with two: 1.33 x the mean)
-    int gx = hak_grid_x(n1_dev ? (valu ? (two ? 320 : 640) : (qt == 2 ? 43 : 83)) : (nq + qb - 1) / qb);
-    // with device-side counts n1_host carries the CAPACITY of a query set (the context's max_pts; 0: unknown).  The sliced path
-    // below gives every query block its own ticket and partial-result rows, so its grid must cover the capacity -- the plain
-    // kernel's blocks loop over the queries and need no such bound.
-    const int cap_blocks = n1_dev && n1_host > 0 ? (n1_host + qpb - 1) / qpb : 0;
-    // one pair with host-side counts whose query blocks alone cannot fill the chip: slice the train set as well
-    if (sc && !n1_dev && npairs == 1 && (long)gx * qb >= nq) {
-        int rps = 0;
-        const int mslices = valu ? 1 : mm_single_pair_slices(sc, st, mk, gx, nq, n2_host, &rps);
-        if (mslices > 1) {
-            mm_launch<false>(qt, dim3(gx, mslices), st, pts1, pts2, (const int*)nullptr, (const int*)nullptr, n1_host, n2_host, 0L, 0L, 2, rps,
-                             (int4*)nullptr, 0L, sc->ticket, sc->part, gx * qpb);
-            return;
-        }
-        const int tiles = (n2_host + MT - 1) / MT;
-        if (valu && !two && gx < 2048 && tiles >= 4) {
-            int slices = (2048 + gx - 1) / gx;
-            if (slices > tiles / 2) slices = tiles / 2;
-            const int tps = (tiles + slices - 1) / slices;
-            slices = (tiles + tps - 1) / tps;
-            if (slices > 1 && hak_match_scratch_reserve(sc, st, (long)n1_host * MC, 0, 0, 0, 0)) {
-                k_match<1><<<dim3(gx, slices), 256, 0, st>>>(pts1, pts2, nullptr, nullptr, n1_host, n2_host, 0, 0, 2, sc->keys, tps);
-                k_match_finish<<<(n1_host + 255) / 256, 256, 0, st>>>(pts1, pts2, n1_host, n2_host, sc->keys);
+    const HakMatchPlan p = hak_match_plan(mk, 0, n1_dev != nullptr, n1_host, n2_host, npairs, sc != nullptr);
+    if (p.slices > 1 && p.kernel == 0) {
+        const int qpb = 128 * p.qt;
+        if (!n1_dev) {                                              // one big pair, host-side counts
+            if (hak_match_scratch_reserve(sc, st, 0, p.gx, (long)p.slices * p.gx * qpb, 0, 0)) {
+                mm_launch<false>(p.qt, dim3(p.gx, p.slices), st, pts1, pts2, (const int*)nullptr, (const int*)nullptr, n1_host, n2_host, 0L, 0L, 2,
+                                 p.rows_per_slice, (int4*)nullptr, 0L, sc->ticket, sc->part, p.gx * qpb);
                 return;
             }
-        }
-    }
-    // few pairs with device-side counts (the pair call, batches of a handful of images): few of a pair's blocks find queries,
-    // each walks the whole train set while most of the chip idles -- slice the train sets as for one big pair
-    if (!valu && sc && n1_dev && npairs <= 12 && cap_blocks > 0 && cap_blocks <= 4096) {
-        if (cap_blocks > gx) gx = cap_blocks | 3;                   // (odd, as 83: not a multiple of the eight XCDs)
-        const int slices = (npairs <= 2 ? 8 : npairs <= 4 ? 4 : npairs <= 8 ? 3 : 2) * (qt == 2 ? 2 : 1);
-        if (hak_match_scratch_reserve(sc, st, 0, (long)npairs * gx, (long)npairs * slices * gx * qpb, 0, 0)) {
-            mm_launch<false>(qt, dim3(gx, slices, npairs), st, pts1, pts2, n1_dev, n2_dev, n1_host, n2_host, pair_stride1, pair_stride2,
-                             2, 0, (int4*)nullptr, 0L, sc->ticket, sc->part, gx * qpb);
+        } else if (hak_match_scratch_reserve(sc, st, 0, (long)npairs * p.gx, (long)npairs * p.slices * p.gx * qpb, 0, 0)) {
+            mm_launch<false>(p.qt, dim3(p.gx, p.slices, npairs), st, pts1, pts2, n1_dev, n2_dev, n1_host, n2_host, pair_stride1, pair_stride2,
+                             2, 0, (int4*)nullptr, 0L, sc->ticket, sc->part, p.gx * qpb);
             return;
         }
+    } else if (p.slices > 1 && hak_match_scratch_reserve(sc, st, (long)n1_host * MC, 0, 0, 0, 0)) {
+        k_match<1><<<dim3(p.gx, p.slices), 256, 0, st>>>(pts1, pts2, nullptr, nullptr, n1_host, n2_host, 0, 0, 2, sc->keys, p.rows_per_slice / MT);
+        k_match_finish<<<(n1_host + 255) / 256, 256, 0, st>>>(pts1, pts2, n1_host, n2_host, sc->keys);
+        return;
     }
-    dim3 grid(gx, npairs);
-    if (!valu) mm_launch<false>(qt, grid, st, pts1, pts2, n1_dev, n2_dev, n1_host, n2_host, pair_stride1, pair_stride2, 2, 0,
-                                (int4*)nullptr, 0L, (int*)nullptr, (uint2*)nullptr, 0);
-    else if (two) k_match<2><<<grid, 256, 0, st>>>(pts1, pts2, n1_dev, n2_dev, n1_host, n2_host, pair_stride1, pair_stride2, 2, nullptr, 0);
+    dim3 grid(p.gx, npairs);
+    if (p.kernel == 0) mm_launch<false>(p.qt, grid, st, pts1, pts2, n1_dev, n2_dev, n1_host, n2_host, pair_stride1, pair_stride2, 2, 0,
+                                        (int4*)nullptr, 0L, (int*)nullptr, (uint2*)nullptr, 0);
+    else if (p.qt == 2) k_match<2><<<grid, 256, 0, st>>>(pts1, pts2, n1_dev, n2_dev, n1_host, n2_host, pair_stride1, pair_stride2, 2, nullptr, 0);
     else k_match<1><<<grid, 256, 0, st>>>(pts1, pts2, n1_dev, n2_dev, n1_host, n2_host, pair_stride1, pair_stride2, 2, nullptr, 0);
 }

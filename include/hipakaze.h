@@ -202,7 +202,8 @@ int hak_match_batch(hak_ctx* ctx, hak_point* d_points, const int* d_num_pts, int
  *          and (cross_check == 0 or the nearest query of train point j1(i) is i, ties to the smallest index).
  * Writes match/distance/match_x/match_y of pts1 like cuMatch (rejected: -1; copied to h_pts1 when given) and appends the accepted
  * matches, in ascending query order, to d_out (capacity >= n1; may be NULL); *count receives their number.
- * ctx may be NULL (scratch is then allocated per call).  max_dist <= 0 selects 96 (akazed.cu:6). */
+ * ctx may be NULL (scratch is then allocated per call).  max_dist <= 0 selects 96 (akazed.cu:6).  Fewer than 2^20 points per
+ * side (the batch form: a context whose max_pts is below 2^20); more is refused before a buffer is touched. */
 typedef struct hak_match_pair {
     int   query, train;      /* indices into pts1 / pts2 */
     int   distance, second;  /* d1, d2 */

@@ -159,6 +159,20 @@ int hak_debug_fill_match_scratch(hak_ctx* ctx, int byte);
  * lists and `iterations` hypotheses -- *hp hypotheses per score block (16 .. 256) and *hblocks score blocks per pair.  It asks the
  * launchers' own rule and touches no device: the shape tests (tests/ransac_shapes.py) read the rule here and do not restate it. */
 int hak_op_ransac_shape(int npairs, int iterations, int* hp, int* hblocks);
+/* hak_op_match_shape: the launch plan the matcher takes for a call, from the launchers' own rule (one host function, which reads
+ * the HAK_MATCH_* variables as every call does) and without touching a device.  The limit tests (tests/match_limits.py) assert with
+ * it that a case reached the path it was made for and choose where to plant rows; they never form an expected match from it.
+ *   search          0: the 1-NN search of hak_match / hak_match_batch; 1: one 2-NN search of hak_match_knn2 / hak_match_knn2_batch
+ *                   (n1 queries against n2 train rows; the reverse search is the same call with the counts exchanged)
+ *   device_counts   != 0: a batch call (counts on the device); the launchers then see `capacity` (the context's max_pts) in the place
+ *                   of both counts, and n1 / n2 are ignored
+ *   scratch         != 0: a match scratch is at hand (a context's, or the per-device pool's for ctx == NULL: always, for the public
+ *                   entry points)
+ *   plan            7 int32: {kernel (0 = matrix-core k_match_mfma, 1 = vector-pipe k_match / k_knn2), query tiles per wave (k_match:
+ *                   queries per thread), gx = query blocks, train slices (1 = not sliced), rows per slice (0 = not sliced or cut inside
+ *                   the kernel), LDS chunks per block pass (192 rows, a tail counts; k_match: tiles of 128; k_knn2: 0), blocks of the
+ *                   2-NN finish for n1 queries (1 = one block per pair, else two passes of that many)} */
+int hak_op_match_shape(int search, int n1, int n2, int npairs, int device_counts, int capacity, int scratch, int* plan);
 /* hak_debug_ransac_scratch: what the last hak_find_homography / hak_find_fundamental / hak_solve_pnp call (single or batch) on `ctx`
  * left in the context's RANSAC scratch, so that the tests (tests/ransac_trace.py) see every hypothesis and every score block and not
  * only the winner.  Synchronises the context's stream and launches nothing.

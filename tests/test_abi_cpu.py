@@ -46,7 +46,7 @@ def test_test_abi_is_a_separate_library(ah):
     declared = set(re.findall(r"\b(hak_[a-z0-9_]+)\s*\(", hdr))
     assert declared == set(ah.TEST_SYMBOLS), declared ^ set(ah.TEST_SYMBOLS)
     assert all(n.startswith(("hak_op_", "hak_debug_")) for n in declared) and len(declared) >= 20
-    assert {"hak_op_ransac_shape", "hak_debug_ransac_scratch"} <= declared
+    assert {"hak_op_ransac_shape", "hak_debug_ransac_scratch", "hak_op_match_shape"} <= declared
     out = subprocess.check_output(["nm", "-D", "--defined-only", ah.TEST_LIB_PATH], text=True)
     exported = set(re.findall(r" T (hak_[a-z0-9_]+)", out))
     assert declared <= exported, declared - exported
