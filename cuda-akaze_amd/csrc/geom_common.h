@@ -1,8 +1,10 @@
 // geom_common.h -- device arithmetic shared by the geometric-verification kernels (kernels_homography.hip, kernels_fundamental.hip,
 // kernels_fundrefit.hip, kernels_pose.hip, kernels_pnp.hip, kernels_pnprefit.hip): the wave sum whose order the refits' rules fix,
-// the match-list record load and count clamp of all of them, the 3 x 3 product, the Sampson test of the fundamental matrix, the real roots of a monic cubic
-// by bracketing and bisection (step 5 of hak_find_fundamental, also the critical points of hak_solve_pnp's quartic), and the 3 x 3
-// cyclic Jacobi of the refit's rule.  The RANSAC scaffold of the three estimators is ransac_common.h, which includes this.
+// the match-list record load and count clamp of all of them, the 3 x 3 product, the transfer-error test of the homography and the
+// Sampson test of the fundamental matrix, the real roots of a monic cubic by bracketing and bisection (step 5 of
+// hak_find_fundamental, also the critical points of hak_solve_pnp's quartic), and the 3 x 3 cyclic Jacobi of the refit's rule.
+// The RANSAC scaffold of the three estimators is ransac_common.h, which includes this and holds the views hg_est and fd_est; the
+// refit scaffold (inlier count, Hartley passes, normal equations, elimination, round loop) is refit_common.h on top of that.
 // Every file that includes it is built with -ffp-contract=off.
 #pragma once
 #include "hak_internal.h"
@@ -34,6 +36,16 @@ __device__ __forceinline__ int fd_count(const int* counts, int pair, int n_host,
 {
     long n = counts ? counts[pair] : n_host;
     return (int)(n < 0 ? 0 : (n > stride ? stride : n));
+}
+
+// transfer error of the homography H (H[8] = 1) below the threshold in front of the camera (t2 = threshold^2); NaN fails
+__device__ __forceinline__ bool hg_inlier(const float H[9], const float4 r, const float t2)
+{
+    const float wz = (H[6] * r.x + H[7] * r.y) + 1.0f;
+    const float u = (H[0] * r.x + H[1] * r.y) + H[2];
+    const float v = (H[3] * r.x + H[4] * r.y) + H[5];
+    const float ex = u - r.z * wz, ey = v - r.w * wz;
+    return wz > 0.0f && ex * ex + ey * ey < t2 * (wz * wz);
 }
 
 // Sampson distance below the threshold (t2 = threshold^2); NaN fails

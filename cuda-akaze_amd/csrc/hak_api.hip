@@ -736,7 +736,7 @@ static int grow_scratch(T*& p, long& cap, long need, size_t elem = sizeof(T))
     return 0;
 }
 
-#define HAK_REC_BYTES 64         // room for the largest record (hak_abs_pose); hak_link_tracks' count follows it
+// the context's record: HAK_REC_BYTES (hak_internal.h); hak_link_tracks' count follows it
 static int geom_record(hak_ctx* c)
 {
     if (!c->geom_rec) HIP_TRY(hipMalloc((void**)&c->geom_rec, HAK_REC_BYTES + 16));
@@ -844,30 +844,40 @@ static int refine_args(float threshold, int rounds)
     return 0;
 }
 
-extern "C" int hak_refine_fundamental(hak_ctx* c, const hak_match_pair* d_matches, int n, float threshold, int rounds,
-                                      unsigned char* d_mask, hak_fundamental* h_inout)
+// one refine call on one record after its argument checks.  No scratch: the record's device copy is the context's, or without a
+// context the device global hak_refit_record() that calls take in turn, so nothing is allocated.  launch(stream, d_rec) enqueues the
+// refit of the uploaded record in place.
+static std::mutex g_refit_record_turn;
+template <class Launch>
+static int refine_single(hak_ctx* c, void* h_inout, size_t bytes, const char* what, const char* no_symbol, Launch launch)
 {
-    if (list_args(h_inout, d_matches, n, "d_matches must be 16-byte aligned") || refine_args(threshold, rounds)) return 1;
     if (hak_device_count() == 0) return fail("no HIP device: libhipakaze has no CPU fallback");
-    // no scratch.  The record's device copy is the context's, or without a context a device global that calls take in turn:
-    // nothing is allocated
-    static std::mutex null_ctx_record;
-    std::unique_lock<std::mutex> turn(null_ctx_record, std::defer_lock);
-    hak_fundamental* d_rec = nullptr;
+    std::unique_lock<std::mutex> turn(g_refit_record_turn, std::defer_lock);
+    void* d_rec = nullptr;
     if (c) {
         if (geom_record(c)) return 1;
-        d_rec = reinterpret_cast<hak_fundamental*>(c->geom_rec);
+        d_rec = c->geom_rec;
     } else {
         turn.lock();
-        d_rec = hak_fundamental_refit_record();
-        if (!d_rec) return fail("hipGetSymbolAddress(refit record)");
+        d_rec = hak_refit_record();
+        if (!d_rec) return fail(no_symbol);
     }
     hipStream_t st = c ? c->stream : nullptr;
     order_after_null_stream(c, st);
     int rc = 0;
-    if (hipMemcpyAsync(d_rec, h_inout, sizeof(hak_fundamental), hipMemcpyHostToDevice, st) != hipSuccess) rc = fail("record upload");
-    if (!rc) hak_launch_fundamental_refit(st, d_matches, n, nullptr, n, 1, threshold, rounds, d_rec, d_mask, 0);
-    return single_tail(rc, st, "fundamental refit", "record download", h_inout, d_rec, sizeof(hak_fundamental));
+    if (hipMemcpyAsync(d_rec, h_inout, bytes, hipMemcpyHostToDevice, st) != hipSuccess) rc = fail("record upload");
+    if (!rc) launch(st, d_rec);
+    return single_tail(rc, st, what, "record download", h_inout, d_rec, bytes);
+}
+
+extern "C" int hak_refine_fundamental(hak_ctx* c, const hak_match_pair* d_matches, int n, float threshold, int rounds,
+                                      unsigned char* d_mask, hak_fundamental* h_inout)
+{
+    if (list_args(h_inout, d_matches, n, "d_matches must be 16-byte aligned") || refine_args(threshold, rounds)) return 1;
+    auto launch = [&](hipStream_t st, void* d_rec) {
+        hak_launch_fundamental_refit(st, d_matches, n, nullptr, n, 1, threshold, rounds, static_cast<hak_fundamental*>(d_rec), d_mask, 0);
+    };
+    return refine_single(c, h_inout, sizeof(hak_fundamental), "fundamental refit", "hipGetSymbolAddress(refit record)", launch);
 }
 
 extern "C" int hak_refine_fundamental_batch(hak_ctx* c, const hak_match_pair* d_matches, long stride, const int* d_counts,
@@ -1017,26 +1027,10 @@ extern "C" int hak_refine_pnp(hak_ctx* c, const hak_corr3d* d_corr, int n, const
 {
     if (list_args(h_inout, d_corr, n, "d_corr must be 16-byte aligned") || refine_args(threshold, rounds) || intrinsics_args(K))
         return 1;
-    if (hak_device_count() == 0) return fail("no HIP device: libhipakaze has no CPU fallback");
-    // no scratch.  The record's device copy is the context's, or without a context a device global that calls take in turn:
-    // nothing is allocated
-    static std::mutex null_ctx_record;
-    std::unique_lock<std::mutex> turn(null_ctx_record, std::defer_lock);
-    hak_abs_pose* d_rec = nullptr;
-    if (c) {
-        if (geom_record(c)) return 1;
-        d_rec = reinterpret_cast<hak_abs_pose*>(c->geom_rec);
-    } else {
-        turn.lock();
-        d_rec = hak_pnp_refit_record();
-        if (!d_rec) return fail("hipGetSymbolAddress(pnp refit record)");
-    }
-    hipStream_t st = c ? c->stream : nullptr;
-    order_after_null_stream(c, st);
-    int rc = 0;
-    if (hipMemcpyAsync(d_rec, h_inout, sizeof(hak_abs_pose), hipMemcpyHostToDevice, st) != hipSuccess) rc = fail("record upload");
-    if (!rc) hak_launch_pnp_refit(st, d_corr, n, nullptr, n, 1, *K, threshold, rounds, d_rec, d_mask, 0);
-    return single_tail(rc, st, "pnp refit", "record download", h_inout, d_rec, sizeof(hak_abs_pose));
+    auto launch = [&](hipStream_t st, void* d_rec) {
+        hak_launch_pnp_refit(st, d_corr, n, nullptr, n, 1, *K, threshold, rounds, static_cast<hak_abs_pose*>(d_rec), d_mask, 0);
+    };
+    return refine_single(c, h_inout, sizeof(hak_abs_pose), "pnp refit", "hipGetSymbolAddress(pnp refit record)", launch);
 }
 
 extern "C" int hak_refine_pnp_batch(hak_ctx* c, const hak_corr3d* d_corr, long stride, const int* d_counts, int npairs,

@@ -810,8 +810,9 @@ void hak_launch_fundamental(hipStream_t st, const hak_match_pair* matches, long 
                             int iterations, float threshold, unsigned seed, unsigned* models, unsigned long long* slots,
                             hak_fundamental* out, unsigned char* masks, long mask_stride);
 // rank-2 refit of a fundamental matrix (kernels_fundrefit.hip): record k is read from and rewritten to inout[k]; no scratch.
-// hak_fundamental_refit_record(): the current device's one record for calls without a context (NULL on failure)
-hak_fundamental* hak_fundamental_refit_record();
+// hak_refit_record(): the current device's one record for this refit's and hak_refine_pnp's calls without a context (NULL on failure)
+#define HAK_REC_BYTES 64         // room for the largest record of an estimator or refit (hak_abs_pose)
+void* hak_refit_record();
 void hak_launch_fundamental_refit(hipStream_t st, const hak_match_pair* matches, long stride, const int* counts, int n_host,
                                   int npairs, float threshold, int rounds, hak_fundamental* inout, unsigned char* masks,
                                   long mask_stride);
@@ -828,8 +829,6 @@ void hak_launch_pnp(hipStream_t st, const hak_corr3d* corr, long stride, const i
                     const hak_intrinsics& K, int iterations, float threshold, unsigned seed, unsigned* models,
                     unsigned long long* slots, hak_abs_pose* out, unsigned char* masks, long mask_stride);
 // Gauss-Newton refit of an absolute pose (kernels_pnprefit.hip): record k is read from and rewritten to inout[k]; no scratch.
-// hak_pnp_refit_record(): the current device's one record for calls without a context (NULL on failure)
-hak_abs_pose* hak_pnp_refit_record();
 void hak_launch_pnp_refit(hipStream_t st, const hak_corr3d* corr, long stride, const int* counts, int n_host, int npairs,
                           const hak_intrinsics& K, float threshold, int rounds, hak_abs_pose* inout, unsigned char* masks,
                           long mask_stride);

@@ -12,16 +12,10 @@
 //   Output to the models scratch of ransac_common.h: the float32 models of roots 0, 1, 2 (9 words each) and the mask of the roots
 //   that gave one.
 // k_fund_score: rs_score_block on the hypothesis' up to three models read back from scratch.
-// k_fund_finish: one wave per pair: reduces the slots, reads the winner's model back from scratch, writes the mask and the
-//   record.
+// k_fund_finish: rs_finish: one wave per pair reduces the slots, reads the winner's model back from scratch, writes the mask and
+//   the record.
+// The Sampson test fd_inlier is in geom_common.h, the scaffold's view fd_est in ransac_common.h.
 #include "ransac_common.h"
-
-// the scaffold's view of the estimator: three models (the cubic's roots) of 9 words per hypothesis
-struct fd_est : rs_match_records {
-    static constexpr int NM = 3, NW = 9, UNROLL = 2;
-    float t2;
-    __device__ __forceinline__ bool inlier(const float F[9], const float4 r) const { return fd_inlier(F, r, t2); }
-};
 
 __device__ __forceinline__ double fd_det(const double m[9])
 {
@@ -198,20 +192,8 @@ __global__ __launch_bounds__(HAK_WAVE) void k_fund_finish(const hak_match_pair* 
                                                           long mask_stride)
 {
     const int pair = blockIdx.x;
-    const hak_match_pair* m = base + (long)pair * stride;
-    const int n = fd_count(counts, pair, n_host, stride);
-    float F[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    int inl, hyp, root;
-    if (rs_decode(rs_best_slot(slots, hblocks), inl, hyp, root))    // hyp < iterations: its model is in scratch
-        rs_read_model<fd_est>(models, pair, iterations, hyp, root, F);
-    rs_write_mask(fd_est{{}, t2}, masks, mask_stride, m, n, F, hyp >= 0);
-    if (threadIdx.x == 0) {
-        hak_fundamental o;
-#pragma unroll
-        for (int q = 0; q < 9; q++) o.F[q] = F[q];
-        o.inliers = inl; o.hypothesis = hyp; o.root = root; o.n = n;
-        out[pair] = o;
-    }
+    rs_finish(fd_est{{}, t2}, base + (long)pair * stride, fd_count(counts, pair, n_host, stride), iterations, hblocks, models, slots,
+              out, masks, mask_stride);
 }
 
 long hak_fundamental_words(int npairs, int iterations) { return (long)npairs * rs_words<fd_est>() * iterations; }

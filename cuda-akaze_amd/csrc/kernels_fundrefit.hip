@@ -7,23 +7,22 @@
 // re-scoring; the round is kept when it scores at least as well.  float64, + - * / sqrt only; the file is built with
 // -ffp-contract=off: no FMA is formed, so every rounding is the one the reference makes.
 //
-// k_fund_refit: one wave per pair.  Three streaming passes over the list per round (count and centroids, scales, the 45 sums in
-//   registers), each closed by the xor butterfly, so every lane holds the same normal matrix.
+// k_fund_refit: one wave per pair, refit_record of refit_common.h: the record's check, the round loop, the mask (written once, after
+//   the last round) and the record (lane 0 rewrites it in place) are that header's, as are the pieces of a round it shares with the
+//   homography's and the pose's.  fr_refit::round is this rule's round:
+//   Three streaming passes over the list (rf_hartley's count and centroids, then scales; the 45 sums in registers by rf_tri_add),
+//   each closed by the xor butterfly, so every lane holds the same normal matrix.
 //   The 9 x 9 Jacobi is a chain of 288 dependent rotations.  Lane k < 9 owns row k of A and row k of V in registers (the other
 //   lanes shadow lane 0); the (p, q) loops are fully unrolled, so every register index and every lane number is a compile-time
 //   constant.  A rotation reads A[p][p], A[q][q], A[p][q] and rows p and q from lanes p and q with v_readlane (17 64-bit lane
 //   reads), every lane computes t, c and sn redundantly, lane k updates its entries of columns p and q, lanes p and q rebuild
 //   their own rows from the two broadcast rows -- by the symmetry of A these are the bits the column update gives -- and V's
 //   rotation needs no other lane.  No LDS, no scratch.
-//   The 3 x 3 Jacobi of the rank-2 step and the denormalisation run redundantly in every lane.  The mask is written once, after
-//   the last round; lane 0 rewrites the record in place.
-#include "hak_internal.h"
-#include "geom_common.h"
+//   The 3 x 3 Jacobi of the rank-2 step and the denormalisation run redundantly in every lane.
+#include "refit_common.h"
 
 #define FR_SWEEPS9 8
 #define FR_SWEEPS3 6
-#define FR_MIN_INLIERS 8
-#define FR_REFINED_ROOT 3
 
 // v of lane `lane` in every lane; `lane` is wave-uniform (a constant after unrolling)
 __device__ __forceinline__ double fr_lane(double v, int lane)
@@ -106,58 +105,30 @@ __device__ void fr_jacobi3(double G[3][3], double v[3])
     for (int i = 0; i < 3; i++) v[i] = best == 0 ? V[i][0] : (best == 1 ? V[i][1] : V[i][2]);
 }
 
-// inliers of F over the pair (every lane returns the total)
-__device__ int fr_count_inliers(const hak_match_pair* m, int n, const float F[9], float t2)
-{
-    int c = 0;
-    for (int i = threadIdx.x; i < n; i += HAK_WAVE) c += fd_inlier(F, fd_load(m, i), t2) ? 1 : 0;
-    return hg_wsum(c);
-}
+// the refit scaffold's view (refit_common.h)
+struct fr_refit : fd_est {
+    static constexpr int MIN_INLIERS = 8, REFINED = 3;              // REFINED: hak_fundamental.root of a refitted record
+    __device__ bool round(const hak_match_pair* m, int n, const float F[9], int* cnt, float R[9]) const;
+};
 
 // steps 1-7 of the rule up to the scoring, from the model F: *cnt = the inliers of F; true and R = the refitted model, false
 // when the round fails.  Every lane computes the same.
-__device__ bool fr_round(const hak_match_pair* m, int n, const float F[9], float t2, int* cnt, float R[9])
+__device__ bool fr_refit::round(const hak_match_pair* m, int n, const float F[9], int* cnt, float R[9]) const
 {
-    const int l = threadIdx.x;
-    int c = 0;
-    double sx1 = 0.0, sy1 = 0.0, sx2 = 0.0, sy2 = 0.0;
-    for (int i = l; i < n; i += HAK_WAVE) {
-        const float4 r = fd_load(m, i);
-        if (!fd_inlier(F, r, t2)) continue;
-        c++;
-        sx1 = sx1 + (double)r.x; sy1 = sy1 + (double)r.y; sx2 = sx2 + (double)r.z; sy2 = sy2 + (double)r.w;
-    }
-    c = hg_wsum(c);
-    *cnt = c;
-    if (c < FR_MIN_INLIERS) return false;
-    const double mm = (double)c;
-    const double c1x = hg_wsum(sx1) / mm, c1y = hg_wsum(sy1) / mm, c2x = hg_wsum(sx2) / mm, c2y = hg_wsum(sy2) / mm;
-    double q1 = 0.0, q2 = 0.0;
-    for (int i = l; i < n; i += HAK_WAVE) {
-        const float4 r = fd_load(m, i);
-        if (!fd_inlier(F, r, t2)) continue;
-        const double dx1 = (double)r.x - c1x, dy1 = (double)r.y - c1y, dx2 = (double)r.z - c2x, dy2 = (double)r.w - c2y;
-        q1 = q1 + (dx1 * dx1 + dy1 * dy1);
-        q2 = q2 + (dx2 * dx2 + dy2 * dy2);
-    }
-    q1 = hg_wsum(q1);
-    q2 = hg_wsum(q2);
-    const double s1 = sqrt((2.0 * mm) / q1), s2 = sqrt((2.0 * mm) / q2);
-    if (!(q1 > 0.0 && q2 > 0.0 && __builtin_isfinite(s1) && __builtin_isfinite(s2))) return false;
+    const rf_norm h = rf_hartley(*this, m, n, F);
+    *cnt = h.m;
+    if (h.m < MIN_INLIERS) return false;
+    const double s1 = h.s1, s2 = h.s2, c1x = h.c1x, c1y = h.c1y, c2x = h.c2x, c2y = h.c2y;
+    if (!(h.q1 > 0.0 && h.q2 > 0.0 && __builtin_isfinite(s1) && __builtin_isfinite(s2))) return false;
     double N[45];
-#pragma unroll
-    for (int k = 0; k < 45; k++) N[k] = 0.0;
-    for (int i = l; i < n; i += HAK_WAVE) {
+    rf_tri_zero(N);
+    for (int i = threadIdx.x; i < n; i += HAK_WAVE) {
         const float4 r = fd_load(m, i);
-        if (!fd_inlier(F, r, t2)) continue;
+        if (!inlier(F, r)) continue;
         const double x = s1 * ((double)r.x - c1x), y = s1 * ((double)r.y - c1y);
         const double u = s2 * ((double)r.z - c2x), v = s2 * ((double)r.w - c2y);
         const double w[9] = {u * x, u * y, u, v * x, v * y, v, x, y, 1.0};
-        int k = 0;
-#pragma unroll
-        for (int p = 0; p < 9; p++)
-#pragma unroll
-            for (int q = p; q < 9; q++, k++) N[k] = N[k] + w[p] * w[q];
+        rf_tri_add<9>(N, w);
     }
 #pragma unroll
     for (int k = 0; k < 45; k++) N[k] = hg_wsum(N[k]);
@@ -200,48 +171,18 @@ __global__ __launch_bounds__(HAK_WAVE) void k_fund_refit(const hak_match_pair* _
                                                          hak_fundamental* inout, unsigned char* __restrict__ masks,
                                                          long mask_stride)
 {
-    const int pair = blockIdx.x, l = threadIdx.x;
-    const hak_match_pair* m = base + (long)pair * stride;
-    const int n = fd_count(counts, pair, n_host, stride);
-    const hak_fundamental in = inout[pair];
-    float cur[9];
-    bool model = in.hypothesis >= 0;
-#pragma unroll
-    for (int k = 0; k < 9; k++) { cur[k] = in.F[k]; model = model && __builtin_isfinite(cur[k]); }
-    int cnt = 0, root = in.root;
-    if (model) {
-#pragma unroll 1
-        for (int r = 0; r < rounds; r++) {
-            float R[9];
-            if (!fr_round(m, n, cur, t2, &cnt, R)) break;
-            const int c = fr_count_inliers(m, n, R, t2);
-            if (c < cnt) break;
-#pragma unroll
-            for (int k = 0; k < 9; k++) cur[k] = R[k];
-            cnt = c;
-            root = FR_REFINED_ROOT;
-        }
-    }
-    if (masks) {
-        unsigned char* mk = masks + (long)pair * mask_stride;
-        for (int i = l; i < n; i += HAK_WAVE) mk[i] = (model && fd_inlier(cur, fd_load(m, i), t2)) ? 1 : 0;
-    }
-    if (l == 0) {
-        hak_fundamental o;
-#pragma unroll
-        for (int k = 0; k < 9; k++) o.F[k] = model ? cur[k] : 0.0f;
-        o.inliers = model ? cnt : 0; o.hypothesis = model ? in.hypothesis : -1; o.root = model ? root : 0; o.n = n;
-        inout[pair] = o;
-    }
+    const int pair = blockIdx.x;
+    refit_record(fr_refit{{{}, t2}}, base + (long)pair * stride, fd_count(counts, pair, n_host, stride), rounds, inout, masks,
+                 mask_stride);
 }
 
-// the record of a hak_refine_fundamental call that has no context: a device global, so that the call allocates nothing
-__device__ hak_fundamental g_refit_record;
+// the record of a hak_refine_fundamental or hak_refine_pnp call without a context: a device global, so the call allocates nothing
+__device__ __attribute__((aligned(16))) char g_refit_record[HAK_REC_BYTES];
 
-hak_fundamental* hak_fundamental_refit_record()
+void* hak_refit_record()
 {
     void* p = nullptr;
-    return hipGetSymbolAddress(&p, HIP_SYMBOL(g_refit_record)) == hipSuccess ? static_cast<hak_fundamental*>(p) : nullptr;
+    return hipGetSymbolAddress(&p, HIP_SYMBOL(g_refit_record)) == hipSuccess ? p : nullptr;
 }
 
 void hak_launch_fundamental_refit(hipStream_t st, const hak_match_pair* matches, long stride, const int* counts, int n_host,

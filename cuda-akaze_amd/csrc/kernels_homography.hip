@@ -8,18 +8,11 @@
 //
 // k_hom_score: rs_score_block's shape (ransac_common.h) with one model per hypothesis: every thread draws and solves its hypothesis
 //   in registers (no models kernel, no scratch), then the scaffold counts its inliers and writes the block's slot.
-// k_hom_finish: one wave per pair: reduces the slots, re-derives the winner through the same device function, refits, re-scores,
-//   writes the mask and the record.
-#include "ransac_common.h"
-
-__device__ __forceinline__ bool hg_inlier(const float H[9], const float4 r, const float t2)
-{
-    const float wz = (H[6] * r.x + H[7] * r.y) + 1.0f;
-    const float u = (H[0] * r.x + H[1] * r.y) + H[2];
-    const float v = (H[3] * r.x + H[4] * r.y) + H[5];
-    const float ex = u - r.z * wz, ey = v - r.w * wz;
-    return wz > 0.0f && ex * ex + ey * ey < t2 * (wz * wz);
-}
+// k_hom_finish: one wave per pair: reduces the slots, re-derives the winner through the same device function and hands it to
+//   refit_iterate (refit_common.h) for at most one round of hg_refit::round: refit, re-score, keep if not worse, mask and record.
+//   The round's Hartley passes, normal equations and elimination are that header's; its rows and the denormalisation are here.
+// The inlier test hg_inlier is in geom_common.h, the scaffold's view hg_est in ransac_common.h.
+#include "refit_common.h"
 
 // the closed-form map of the unit square (0,0) (1,0) (1,1) (0,1) onto the quad x[0..3], y[0..3] (Heckbert), S[8] = 1
 __device__ __forceinline__ void hg_square_to_quad(const double x[4], const double y[4], double S[9])
@@ -50,13 +43,6 @@ __device__ __forceinline__ double hg_cross(const double x[4], const double y[4],
 {
     return (x[b] - x[a]) * (y[c] - y[a]) - (y[b] - y[a]) * (x[c] - x[a]);
 }
-
-// the scaffold's view of the estimator: one model of 9 words per hypothesis
-struct hg_est : rs_match_records {
-    static constexpr int NM = 1, NW = 9, UNROLL = 4;
-    float t2;
-    __device__ __forceinline__ bool inlier(const float H[9], const float4 r) const { return hg_inlier(H, r, t2); }
-};
 
 // hypothesis h of a pair with n matches: false when it is degenerate (no four distinct indices within 16 draws, a triple with
 // |cross| <= 1 px^2 or a flipped orientation in either image, a non-finite or singular solve)
@@ -89,110 +75,48 @@ __device__ bool hg_hypothesis(const hak_match_pair* m, int n, unsigned seed, int
     return hg_to_float(F, H);
 }
 
-// inliers of H over the pair (one wave, every lane returns the total)
-__device__ int hg_count_inliers(const hak_match_pair* m, int n, const float H[9], float t2)
-{
-    int c = 0;
-    for (int i = threadIdx.x; i < n; i += HAK_WAVE) c += hg_inlier(H, fd_load(m, i), t2) ? 1 : 0;
-    return hg_wsum(c);
-}
-
-// least-squares refit of H's inliers (one wave; every lane computes the same): Hartley normalisation, 8x8 normal equations
-// with h22 = 1, Gaussian elimination with partial pivoting, all in float64.  False when the system is singular or the result
-// is not finite.
-__device__ bool hg_refit(const hak_match_pair* m, int n, const float H[9], float t2, float R[9])
-{
-    const int l = threadIdx.x;
-    int cnt = 0;
-    double sx1 = 0.0, sy1 = 0.0, sx2 = 0.0, sy2 = 0.0;
-    for (int i = l; i < n; i += HAK_WAVE) {
-        const float4 r = fd_load(m, i);
-        if (!hg_inlier(H, r, t2)) continue;
-        cnt++;
-        sx1 = sx1 + (double)r.x; sy1 = sy1 + (double)r.y; sx2 = sx2 + (double)r.z; sy2 = sy2 + (double)r.w;
-    }
-    const double mm = (double)hg_wsum(cnt);
-    const double c1x = hg_wsum(sx1) / mm, c1y = hg_wsum(sy1) / mm, c2x = hg_wsum(sx2) / mm, c2y = hg_wsum(sy2) / mm;
-    double q1 = 0.0, q2 = 0.0;
-    for (int i = l; i < n; i += HAK_WAVE) {
-        const float4 r = fd_load(m, i);
-        if (!hg_inlier(H, r, t2)) continue;
-        const double dx1 = (double)r.x - c1x, dy1 = (double)r.y - c1y, dx2 = (double)r.z - c2x, dy2 = (double)r.w - c2y;
-        q1 = q1 + (dx1 * dx1 + dy1 * dy1);
-        q2 = q2 + (dx2 * dx2 + dy2 * dy2);
-    }
-    const double s1 = sqrt((2.0 * mm) / hg_wsum(q1)), s2 = sqrt((2.0 * mm) / hg_wsum(q2));
-    // rows a = [X, Y, 1, 0, 0, 0, -X U, -Y U] (target U), b = [0, 0, 0, X, Y, 1, -X V, -Y V] (target V); N = upper triangle of
-    // sum a^T a + b^T b, row-major; g = sum a U + b V
-    double N[36], g[8];
-#pragma unroll
-    for (int k = 0; k < 36; k++) N[k] = 0.0;
-#pragma unroll
-    for (int k = 0; k < 8; k++) g[k] = 0.0;
-    for (int i = l; i < n; i += HAK_WAVE) {
-        const float4 r = fd_load(m, i);
-        if (!hg_inlier(H, r, t2)) continue;
-        const double X = s1 * ((double)r.x - c1x), Y = s1 * ((double)r.y - c1y);
-        const double U = s2 * ((double)r.z - c2x), V = s2 * ((double)r.w - c2y);
-        const double a[8] = {X, Y, 1.0, 0.0, 0.0, 0.0, -(X * U), -(Y * U)};
-        const double b[8] = {0.0, 0.0, 0.0, X, Y, 1.0, -(X * V), -(Y * V)};
-        int k = 0;
-#pragma unroll
-        for (int p = 0; p < 8; p++)
-#pragma unroll
-            for (int q = p; q < 8; q++, k++) N[k] = N[k] + (a[p] * a[q] + b[p] * b[q]);
-#pragma unroll
-        for (int p = 0; p < 8; p++) g[p] = g[p] + (a[p] * U + b[p] * V);
-    }
-    double M[8][9];
+// the refit scaffold's view (refit_common.h).  A round is the least-squares refit of H's inliers (one wave; every lane computes the
+// same): Hartley normalisation, 8x8 normal equations with h22 = 1, Gaussian elimination with partial pivoting, all in float64.
+// False below four inliers, when the system is singular or the result is not finite.
+struct hg_refit : hg_est {
+    static constexpr int MIN_INLIERS = 4, REFINED = 1;
+    __device__ bool round(const hak_match_pair* m, int n, const float H[9], int* cnt, float R[9]) const
     {
-        int k = 0;
+        const rf_norm h = rf_hartley(*this, m, n, H);
+        *cnt = h.m;
+        if (h.m < MIN_INLIERS) return false;
+        const double s1 = h.s1, s2 = h.s2, c1x = h.c1x, c1y = h.c1y, c2x = h.c2x, c2y = h.c2y;
+        // rows a = [X, Y, 1, 0, 0, 0, -X U, -Y U] (target U), b = [0, 0, 0, X, Y, 1, -X V, -Y V] (target V); N = upper triangle of
+        // sum a^T a + b^T b, row-major; g = sum a U + b V
+        double N[36], g[8];
+        rf_tri_zero(N);
+        rf_tri_zero(g);
+        for (int i = threadIdx.x; i < n; i += HAK_WAVE) {
+            const float4 r = fd_load(m, i);
+            if (!inlier(H, r)) continue;
+            const double X = s1 * ((double)r.x - c1x), Y = s1 * ((double)r.y - c1y);
+            const double U = s2 * ((double)r.z - c2x), V = s2 * ((double)r.w - c2y);
+            const double a[8] = {X, Y, 1.0, 0.0, 0.0, 0.0, -(X * U), -(Y * U)};
+            const double b[8] = {0.0, 0.0, 0.0, X, Y, 1.0, -(X * V), -(Y * V)};
+            rf_tri_add<8>(N, a, b);
 #pragma unroll
-        for (int p = 0; p < 8; p++)
-#pragma unroll
-            for (int q = p; q < 8; q++, k++) { const double v = hg_wsum(N[k]); M[p][q] = v; M[q][p] = v; }
-#pragma unroll
-        for (int p = 0; p < 8; p++) M[p][8] = hg_wsum(g[p]);
-    }
-#pragma unroll
-    for (int c = 0; c < 8; c++) {
-        int piv = c;
-        double best = fabs(M[c][c]);
-#pragma unroll
-        for (int r = c + 1; r < 8; r++) {
-            const double v = fabs(M[r][c]);
-            if (v > best) { best = v; piv = r; }
+            for (int p = 0; p < 8; p++) g[p] = g[p] + (a[p] * U + b[p] * V);
         }
-        if (!(best > 0.0) || !__builtin_isfinite(best)) return false;
+        double S[8][9], d[8], Hn[9];
+        rf_system<8>(N, g, S);
+        if (!rf_solve<8>(S, d)) return false;
 #pragma unroll
-        for (int r = c + 1; r < 8; r++)                             // (selects, no dynamic register indexing)
-            if (r == piv)
-#pragma unroll
-                for (int q = c; q < 9; q++) { const double t = M[c][q]; M[c][q] = M[r][q]; M[r][q] = t; }
-#pragma unroll
-        for (int r = c + 1; r < 8; r++) {
-            const double f = M[r][c] / M[c][c];
-#pragma unroll
-            for (int q = c + 1; q < 9; q++) M[r][q] = M[r][q] - f * M[c][q];
-        }
+        for (int k = 0; k < 8; k++) Hn[k] = d[k];
+        Hn[8] = 1.0;
+        const double is2 = 1.0 / s2;
+        const double T1[9] = {s1, 0.0, -(s1 * c1x), 0.0, s1, -(s1 * c1y), 0.0, 0.0, 1.0};
+        const double T2i[9] = {is2, 0.0, c2x, 0.0, is2, c2y, 0.0, 0.0, 1.0};
+        double G[9], F[9];
+        fd_mul3(Hn, T1, G);
+        fd_mul3(T2i, G, F);
+        return hg_to_float(F, R);
     }
-    double Hn[9];
-#pragma unroll
-    for (int i = 7; i >= 0; i--) {
-        double acc = M[i][8];
-#pragma unroll
-        for (int j = i + 1; j < 8; j++) acc = acc - M[i][j] * Hn[j];
-        Hn[i] = acc / M[i][i];
-    }
-    Hn[8] = 1.0;
-    const double is2 = 1.0 / s2;
-    const double T1[9] = {s1, 0.0, -(s1 * c1x), 0.0, s1, -(s1 * c1y), 0.0, 0.0, 1.0};
-    const double T2i[9] = {is2, 0.0, c2x, 0.0, is2, c2y, 0.0, 0.0, 1.0};
-    double G[9], F[9];
-    fd_mul3(Hn, T1, G);
-    fd_mul3(T2i, G, F);
-    return hg_to_float(F, R);
-}
+};
 
 __global__ __launch_bounds__(RS_THREADS) void k_hom_score(const hak_match_pair* __restrict__ base, long stride,
                                                           const int* __restrict__ counts, int n_host, int iterations, int hp,
@@ -216,29 +140,13 @@ __global__ __launch_bounds__(HAK_WAVE) void k_hom_finish(const hak_match_pair* _
     const int pair = blockIdx.x;
     const hak_match_pair* m = base + (long)pair * stride;
     const int n = fd_count(counts, pair, n_host, stride);
-    float H[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f};
-    int inl, hyp, model, refined = 0;
-    if (rs_decode(rs_best_slot(slots, hblocks), inl, hyp, model)) {
-        hg_hypothesis(m, n, seed, hyp, H);                          // non-degenerate: its key was written by the same function
-        float R[9];
-        if (refine && inl >= 4 && hg_refit(m, n, H, t2, R)) {
-            const int c = hg_count_inliers(m, n, R, t2);
-            if (c >= inl) {
-#pragma unroll
-                for (int k = 0; k < 9; k++) H[k] = R[k];
-                inl = c;
-                refined = 1;
-            }
-        }
-    }
-    rs_write_mask(hg_est{{}, t2}, masks, mask_stride, m, n, H, hyp >= 0);
-    if (threadIdx.x == 0) {
-        hak_homography o;
-#pragma unroll
-        for (int k = 0; k < 9; k++) o.H[k] = H[k];
-        o.inliers = inl; o.hypothesis = hyp; o.refined = refined; o.n = n;
-        out[pair] = o;
-    }
+    float H[9];
+    hg_est::no_model(H);
+    int inl, hyp, model;
+    const bool has = rs_decode(rs_best_slot(slots, hblocks), inl, hyp, model);
+    if (has) hg_hypothesis(m, n, seed, hyp, H);                     // non-degenerate: its key was written by the same function
+    // one round at most, from the winner and its decoded count: the score kernel counted the same test on the same records
+    refit_iterate(hg_refit{{{}, t2}}, m, n, refine ? 1 : 0, H, has, inl, hyp, 0, out, masks, mask_stride);
 }
 
 // hypotheses per score block: the largest power of two in 16 .. 256 that still gives >= 64 blocks over all pairs (a single pair

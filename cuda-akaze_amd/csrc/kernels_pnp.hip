@@ -16,28 +16,11 @@
 //   that gave one.
 // k_pnp_score: rs_score_block on the hypothesis' up to four models read back from scratch; a chunk is staged as {X, Y, Z, u} + {v}
 //   (20 KB).
-// k_pnp_finish: one wave per pair: reduces the slots, reads the winner's model back from scratch, writes the mask and the record.
-#include "ransac_common.h"
-#include "pnp_common.h"          // pn_rec, pn_load, pn_inlier: shared with the refit (kernels_pnprefit.hip)
+// k_pnp_finish: rs_finish: one wave per pair reduces the slots, reads the winner's model back from scratch, writes the mask and the
+//   record.
+#include "pnp_common.h"          // pn_rec, pn_load, pn_inlier and the view pn_est: shared with the refit (kernels_pnprefit.hip)
 
 #define LK_NONE 0x7F7F7F7F       // the table's cleared entry (memset byte 0x7F): above every index
-
-// the scaffold's view of the estimator: four models (the quartic's roots) of 12 words per hypothesis
-struct pn_est {
-    typedef hak_corr3d list_t;
-    typedef pn_rec rec_t;
-    struct lds {
-        float4 a[RS_CHUNK];
-        float v[RS_CHUNK];
-        __device__ __forceinline__ void put(int j, const pn_rec r) { a[j] = r.a; v[j] = r.v; }
-        __device__ __forceinline__ pn_rec get(int j) const { return pn_rec{a[j], v[j]}; }
-    };
-    static constexpr int NM = 4, NW = 12, UNROLL = 2;
-    hak_intrinsics K;
-    float t2;
-    static __device__ __forceinline__ pn_rec load(const hak_corr3d* c, int i) { return pn_load(c, i); }
-    __device__ __forceinline__ bool inlier(const float M[12], const pn_rec r) const { return pn_inlier(M, r.a, r.v, K, t2); }
-};
 
 __device__ __forceinline__ double pn_dot(const double a[3], const double b[3]) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
 __device__ __forceinline__ void pn_cross(const double a[3], const double b[3], double c[3])
@@ -221,22 +204,8 @@ __global__ __launch_bounds__(HAK_WAVE) void k_pnp_finish(const hak_corr3d* __res
                                                          long mask_stride)
 {
     const int pair = blockIdx.x;
-    const hak_corr3d* c = base + (long)pair * stride;
-    const int n = fd_count(counts, pair, n_host, stride);
-    float M[12] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f};
-    int inl, hyp, sol;
-    if (rs_decode(rs_best_slot(slots, hblocks), inl, hyp, sol))     // hyp < iterations: its model is in scratch
-        rs_read_model<pn_est>(models, pair, iterations, hyp, sol, M);
-    rs_write_mask(pn_est{K, t2}, masks, mask_stride, c, n, M, hyp >= 0);
-    if (threadIdx.x == 0) {
-        hak_abs_pose o;
-#pragma unroll
-        for (int q = 0; q < 9; q++) o.R[q] = M[q];
-#pragma unroll
-        for (int q = 0; q < 3; q++) o.t[q] = M[9 + q];
-        o.inliers = inl; o.hypothesis = hyp; o.solution = sol; o.n = n;
-        out[pair] = o;
-    }
+    rs_finish(pn_est{K, t2}, base + (long)pair * stride, fd_count(counts, pair, n_host, stride), iterations, hblocks, models, slots,
+              out, masks, mask_stride);
 }
 
 long hak_pnp_words(int npairs, int iterations) { return (long)npairs * rs_words<pn_est>() * iterations; }

@@ -14,13 +14,15 @@
 //                         reduced.  Each block writes its best key (inliers << 32 | ~(4 h + r), 0 = none) to its own slot
 //                         [pair][block]: no atomics and nothing to clear before a call.  The largest key is the largest count, then
 //                         the smallest hypothesis, then the smallest model of it, whatever hp is.
-//   rs_best_slot / rs_decode / rs_write_mask
-//                         head and tail of a finish kernel (one wave per pair): the pair's best key, its (inliers, hypothesis, model)
-//                         and the inlier mask of the winning model.
+//   rs_best_slot / rs_decode / rs_write_mask / rs_write_result
+//                         head and tail of a finish kernel (one wave per pair): the pair's best key, its (inliers, hypothesis, model),
+//                         the inlier mask of the winning model and the record.
+//   rs_finish<E>          the body of k_fund_finish and k_pnp_finish: all of the above around a read of the winner from scratch.
 //
 // An estimator E supplies: list_t (the list's element), rec_t (what the tests read of one), load(list, i), struct lds with put(j, rec) /
-// get(j) (a chunk's staging), NM models of NW float32 words per hypothesis, UNROLL (of the count loop, chosen per estimator) and
-// inlier(model, rec) const.  Every file that includes this is built with -ffp-contract=off.
+// get(j) (a chunk's staging), NM models of NW float32 words per hypothesis, UNROLL (of the count loop, chosen per estimator),
+// inlier(model, rec) const, and for its record out_t, store(record, model, inliers, hypothesis, tag, n) and no_model(model).
+// Every file that includes this is built with -ffp-contract=off.
 #pragma once
 #include "geom_common.h"
 
@@ -120,6 +122,55 @@ struct rs_match_records {
     static __device__ __forceinline__ float4 load(const hak_match_pair* m, int i) { return fd_load(m, i); }
 };
 
+// the views of the two estimators on match lists.  Beside what the score block needs, a view states its record: out_t, store and
+// no_model (the model of a record without one); those whose refit starts from a record (refit_common.h) add load_model (false
+// unless the record holds a finite model with hypothesis >= 0) and tag (the record's third int: root / solution).
+// homography: one model of 9 words per hypothesis; its refit runs inside the finish kernel, so no record is ever read
+struct hg_est : rs_match_records {
+    static constexpr int NM = 1, NW = 9, UNROLL = 4;
+    typedef hak_homography out_t;
+    float t2;
+    __device__ __forceinline__ bool inlier(const float H[9], const float4 r) const { return hg_inlier(H, r, t2); }
+    static __device__ __forceinline__ void store(hak_homography& o, const float H[9], int inliers, int hypothesis, int tag, int n)
+    {
+#pragma unroll
+        for (int k = 0; k < 9; k++) o.H[k] = H[k];
+        o.inliers = inliers; o.hypothesis = hypothesis; o.refined = tag; o.n = n;
+    }
+    static __device__ __forceinline__ void no_model(float H[9])
+    {
+#pragma unroll
+        for (int k = 0; k < 9; k++) H[k] = k % 4 == 0 ? 1.0f : 0.0f;
+    }
+};
+
+// fundamental matrix: three models (the cubic's roots) of 9 words per hypothesis
+struct fd_est : rs_match_records {
+    static constexpr int NM = 3, NW = 9, UNROLL = 2;
+    typedef hak_fundamental out_t;
+    float t2;
+    __device__ __forceinline__ bool inlier(const float F[9], const float4 r) const { return fd_inlier(F, r, t2); }
+    static __device__ __forceinline__ bool load_model(const hak_fundamental& o, float F[9])
+    {
+        bool model = o.hypothesis >= 0;
+#pragma unroll
+        for (int k = 0; k < 9; k++) { F[k] = o.F[k]; model = model && __builtin_isfinite(F[k]); }
+        return model;
+    }
+    static __device__ __forceinline__ int tag(const hak_fundamental& o) { return o.root; }
+    static __device__ __forceinline__ void store(hak_fundamental& o, const float F[9], int inliers, int hypothesis, int tag, int n)
+    {
+#pragma unroll
+        for (int k = 0; k < 9; k++) o.F[k] = F[k];
+        o.inliers = inliers; o.hypothesis = hypothesis; o.root = tag; o.n = n;
+    }
+    static __device__ __forceinline__ void no_model(float F[9])
+    {
+#pragma unroll
+        for (int k = 0; k < 9; k++) F[k] = 0.0f;
+    }
+};
+
 __device__ __forceinline__ unsigned long long rs_wmax(unsigned long long key)
 {
 #pragma unroll
@@ -217,4 +268,32 @@ __device__ __forceinline__ void rs_write_mask(const E est, unsigned char* masks,
     if (!masks) return;
     unsigned char* mk = masks + (long)blockIdx.x * mask_stride;
     for (int i = threadIdx.x; i < n; i += HAK_WAVE) mk[i] = (has && est.inlier(M, E::load(m, i))) ? 1 : 0;
+}
+
+// the end of every finish and refit kernel (one wave per pair): the mask of M, then lane 0 writes the pair's record.  Without a model
+// the caller passes E::no_model, inliers 0, hypothesis -1, tag 0.
+template <class E>
+__device__ __forceinline__ void rs_write_result(const E est, const typename E::list_t* m, int n, const float M[E::NW], int inliers,
+                                                int hypothesis, int tag, typename E::out_t* out, unsigned char* masks,
+                                                long mask_stride)
+{
+    rs_write_mask(est, masks, mask_stride, m, n, M, hypothesis >= 0);
+    if (threadIdx.x == 0) {
+        typename E::out_t o;
+        E::store(o, M, inliers, hypothesis, tag, n);
+        out[blockIdx.x] = o;
+    }
+}
+
+// the body of a finish kernel behind a models kernel: the winner is read back from scratch (its hypothesis is below `iterations`)
+template <class E>
+__device__ __forceinline__ void rs_finish(const E est, const typename E::list_t* m, int n, int iterations, int hblocks,
+                                          const unsigned* models, const unsigned long long* slots, typename E::out_t* out,
+                                          unsigned char* masks, long mask_stride)
+{
+    float M[E::NW];
+    E::no_model(M);
+    int inl, hyp, r;
+    if (rs_decode(rs_best_slot(slots, hblocks), inl, hyp, r)) rs_read_model<E>(models, blockIdx.x, iterations, hyp, r, M);
+    rs_write_result(est, m, n, M, inl, hyp, r, out, masks, mask_stride);
 }
