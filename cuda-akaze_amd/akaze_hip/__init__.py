@@ -58,6 +58,10 @@ CORR3D_DTYPE = np.dtype([("X", "<f4"), ("Y", "<f4"), ("Z", "<f4"), ("u", "<f4"),
 ABS_POSE_DTYPE = np.dtype([("R", "<f4", (9,)), ("t", "<f4", (3,)), ("inliers", "<i4"), ("hypothesis", "<i4"), ("solution", "<i4"),
                            ("n", "<i4")])                                                     # hak_abs_pose
 assert CORR3D_DTYPE.itemsize == 32 and ABS_POSE_DTYPE.itemsize == 64
+TRIANGULATION_DTYPE = np.dtype([("n", "<i4"), ("kept", "<i4"), ("rejected", "<i4", (3,)), ("model", "<i4"),
+                                ("pad", "<i4", (2,))])                                        # hak_triangulation
+assert TRIANGULATION_DTYPE.itemsize == 32
+VIEW_IDENTITY, VIEW_RELATIVE, VIEW_ABSOLUTE = 0, 1, 2                                         # HAK_VIEW_*
 
 
 class HakError(RuntimeError):
@@ -121,6 +125,9 @@ SYMBOLS = {
     "hak_solve_pnp_batch": (C.c_int, [_vp, _vp, C.c_long, _vp, C.c_int, _vp, C.c_int, C.c_float, C.c_uint, _vp, _vp]),
     "hak_refine_pnp": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_float, C.c_int, _vp, _vp]),
     "hak_refine_pnp_batch": (C.c_int, [_vp, _vp, C.c_long, _vp, C.c_int, _vp, C.c_float, C.c_int, _vp, _vp]),
+    "hak_triangulate": (C.c_int, [_vp, _vp, C.c_int, _fp, _fp, _vp, _vp, C.c_float, C.c_float, C.c_float, _vp, _vp, _vp]),
+    "hak_triangulate_batch": (C.c_int, [_vp, _vp, C.c_long, _vp, C.c_int, C.c_int, _vp, C.c_int, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp,
+                                        C.c_float, C.c_float, C.c_float, _vp, _vp, _vp]),
     "hak_match_guided": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _fp, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _ip, _vp]),
     "hak_match_guided_batch": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp]),
     "hak_match_epipolar": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _fp, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _ip, _vp]),
@@ -729,6 +736,46 @@ def recoverPose(matches, F_or_record, K1, K2=None, threshold=1.0, max_depth=floa
     out = np.zeros((), POSE_DTYPE)
     check(lib.hak_recover_pose(ctx, d_m.data_ptr(), n, f.ctypes.data_as(_fp), k1.ctypes.data, k2.ctypes.data, float(threshold),
                                float(max_depth), d_mask.data_ptr(), d_xyz.data_ptr(), out.ctypes.data))
+    return out, d_mask[:n].cpu().numpy(), d_xyz[:3 * n].cpu().numpy().reshape(n, 3)
+
+
+def _host_view(v):
+    """(twelve float32 {R row-major, t} or None for the identity, has a model) of a view given as None, twelve numbers, or a
+    POSE_DTYPE / ABS_POSE_DTYPE record"""
+    if v is None:
+        return None, True
+    model = True
+    if getattr(v, "dtype", None) is not None and v.dtype.names:
+        model = int(v["candidate"] if "candidate" in v.dtype.names else v["hypothesis"]) >= 0
+        v = np.concatenate([np.asarray(v["R"], np.float32).reshape(9), np.asarray(v["t"], np.float32).reshape(3)])
+    m = np.ascontiguousarray(np.asarray(v, np.float32).reshape(12))
+    return m, bool(model and np.isfinite(m).all())
+
+
+def triangulate(matches, viewA, viewB, KA, KB=None, threshold=2.0, max_depth=float("inf"), min_sin=0.0, akazer=None):
+    """3-D points of a match list under two known views (hipakaze.h hak_triangulate), on the device.  `matches` as
+    findHomography's, (x1, y1) seen by view A and (x2, y2) by view B; a view is None (the identity), twelve floats {R row-major, t}
+    with Xc = R X + t, a POSE_DTYPE record (recoverPose's) or an ABS_POSE_DTYPE record (solvePnP's, refinePnP's); KA, KB as
+    recoverPose's K1, K2.  Returns (record of TRIANGULATION_DTYPE, mask uint8 (n,), xyz float32 (n, 3)): the mask marks the
+    matches that pass the parallax gate (the sine of the rays' angle >= min_sin), the depth gate (0 < depth < max_depth in both
+    cameras) and the reprojection gate (below `threshold` px in both images); xyz holds their points in the frame the views map
+    from, zeros elsewhere.  A record view without a model, or with a non-finite entry, is step 1 of the rule, which needs no
+    device: the no-model record (model = 0), an all-zero mask and all-zero points."""
+    import torch
+    ctx = akazer.ctx if akazer is not None else None
+    d_m, n = _device_records(matches, MATCH_PAIR_DTYPE)
+    (a, model_a), (b, model_b) = _host_view(viewA), _host_view(viewB)
+    ka = intrinsics(KA)
+    kb = ka if KB is None else intrinsics(KB)
+    out = np.zeros((), TRIANGULATION_DTYPE)
+    if not (model_a and model_b):
+        out["n"] = n
+        return out, np.zeros(n, np.uint8), np.zeros((n, 3), np.float32)
+    d_mask = torch.zeros(max(n, 1), dtype=torch.uint8, device="cuda")
+    d_xyz = torch.zeros(3 * max(n, 1), dtype=torch.float32, device="cuda")
+    check(lib.hak_triangulate(ctx, d_m.data_ptr(), n, a.ctypes.data_as(_fp) if a is not None else None,
+                              b.ctypes.data_as(_fp) if b is not None else None, ka.ctypes.data, kb.ctypes.data, float(threshold),
+                              float(max_depth), float(min_sin), d_mask.data_ptr(), d_xyz.data_ptr(), out.ctypes.data))
     return out, d_mask[:n].cpu().numpy(), d_xyz[:3 * n].cpu().numpy().reshape(n, 3)
 
 

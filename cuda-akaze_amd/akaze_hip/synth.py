@@ -296,3 +296,80 @@ def three_view_scene(seed, n, noise_px=0.0, outlier_share=0.0, angles01=(2.0, -5
     A, flagsA, pointA = matches(0, 1)
     B, flagsB, pointB = matches(1, 2)
     return K, (R01, t01), (R12, t12), A, B, flagsA, flagsB, X0[pointA], pointA.astype(np.int64), pointB.astype(np.int64)
+
+
+def four_view_scene(seed, n, noise_px=0.0, outlier_share=0.0, angles01=(2.0, -5.0, 1.5), t01=(-1.0, 0.05, 0.1),
+                    angles12=(-1.5, -4.0, 2.0), t12=(-0.9, -0.1, 0.25), angles23=(1.0, -3.0, -1.0), t23=(-0.8, 0.1, 0.15),
+                    w=1920, h=1080, focal=1500.0, depth=(4.0, 12.0)):
+    """Four pinhole views of one point cloud as three match lists, each sharing an image with the next, for the triangulation
+    tests and the timing tool: three_view_scene's recipe with a third relative pose and a third list, built beside it, pure numpy.
+
+    n 3-D points, uniformly random in the first camera's frustum at depths `depth`, that all four cameras see; camera 1 sees
+    X1 = R01 X0 + t01, camera 2 sees X2 = R12 X1 + t12, camera 3 sees X3 = R23 X2 + t23.  Keypoints, noise, spurious keypoints,
+    the order of a list and its wrong matches as in three_view_scene; list C holds one match per point from image 2 (query) to
+    image 3 (train).  (The random draws are not three_view_scene's: the same seed gives another scene.)
+    -> (K (3, 3) float64, (R01, t01), (R12, t12), A, B: MATCH_DTYPE arrays of n records, flagsA, flagsB: (n,) bool,
+        X0: (n, 3) float64, the point behind each record of A in the FIRST camera's frame, pointA, pointB: (n,) int64
+        -- what three_view_scene returns -- and then
+        (R23, t23), C: MATCH_DTYPE array of n records, flagsC: (n,) bool, pointC: (n,) int64)"""
+    rng = np.random.default_rng(seed)
+    K = np.array([[focal, 0.0, w / 2.0], [0.0, focal, h / 2.0], [0.0, 0.0, 1.0]])
+    poses = [(rotation_zyx(a), np.asarray(t, np.float64).reshape(3)) for a, t in ((angles01, t01), (angles12, t12), (angles23, t23))]
+
+    def project(X):
+        q = X @ K.T
+        with np.errstate(all="ignore"):
+            return q[:, :2] / q[:, 2:]
+
+    def inside(X, p):
+        return (X[:, 2] > 0.5) & (p[:, 0] >= 0) & (p[:, 0] < w) & (p[:, 1] >= 0) & (p[:, 1] < h)
+
+    def views(X):
+        out = [X]
+        for R, t in poses:
+            out.append(out[-1] @ R.T + t)
+        return out
+
+    X0 = np.zeros((0, 3))
+    for _ in range(400):                                                # rejection: keep the points all four cameras see
+        if len(X0) >= n:
+            break
+        m = 2 * n + 16
+        z = rng.uniform(depth[0], depth[1], m)
+        px = np.stack([rng.uniform(0, w, m), rng.uniform(0, h, m), np.ones(m)], axis=1)
+        X = (np.linalg.solve(K, px.T) * z).T
+        seen = np.ones(m, bool)
+        for Xv in views(X)[1:]:
+            seen &= inside(Xv, project(Xv))
+        X0 = np.concatenate([X0, X[seen]])
+    assert len(X0) >= n, "the four cameras share too little of the scene"
+    X0 = X0[:n]
+    pos, index = [], []
+    for X in views(X0):
+        p = project(X)
+        if noise_px > 0.0:
+            p = p + rng.normal(0.0, noise_px, p.shape)
+        spurious = np.stack([rng.uniform(0, w, n), rng.uniform(0, h, n)], axis=1)
+        order = rng.permutation(2 * n)                                  # keypoint index of point j: order[j]; spurious: order[n + j]
+        allp = np.zeros((2 * n, 2))
+        allp[order] = np.concatenate([p, spurious])
+        pos.append(allp)
+        index.append(order[:n])
+
+    def matches(a, b):
+        lst = np.zeros(n, MATCH_DTYPE)
+        good = np.ones(n, bool)
+        good[rng.permutation(n)[:int(round(outlier_share * n))]] = False
+        other = (index[b] + 1 + rng.integers(0, max(2 * n - 1, 1), n)) % (2 * n)      # any keypoint but the right one
+        train = np.where(good, index[b], other)
+        lst["query"], lst["train"] = index[a], train
+        lst["distance"], lst["second"] = 20, 60
+        lst["x1"], lst["y1"] = pos[a][index[a], 0], pos[a][index[a], 1]
+        lst["x2"], lst["y2"] = pos[b][train, 0], pos[b][train, 1]
+        by_query = np.argsort(lst["query"], kind="stable")
+        return lst[by_query], good[by_query], by_query.astype(np.int64)
+
+    A, flagsA, pointA = matches(0, 1)
+    B, flagsB, pointB = matches(1, 2)
+    Cl, flagsC, pointC = matches(2, 3)
+    return K, poses[0], poses[1], A, B, flagsA, flagsB, X0[pointA], pointA, pointB, poses[2], Cl, flagsC, pointC

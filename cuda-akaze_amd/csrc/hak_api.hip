@@ -1047,6 +1047,68 @@ extern "C" int hak_refine_pnp_batch(hak_ctx* c, const hak_corr3d* d_corr, long s
     return 0;
 }
 
+// ----------------------------------------------------------- triangulation under two known views (kernels_triangulate.hip)
+static int triangulate_args(const hak_intrinsics* KA, const hak_intrinsics* KB, float threshold, float max_depth, float min_sin)
+{
+    if (pose_args(KA, KB, threshold, max_depth)) return 1;
+    if (!(min_sin >= 0.f && min_sin < 1.f)) return fail("min_sin must be in [0, 1)");
+    return 0;
+}
+
+static int host_view_args(const float* Rt)
+{
+    for (int k = 0; Rt && k < 12; k++)
+        if (!std::isfinite(Rt[k])) return fail("a host view has a non-finite entry");
+    return 0;
+}
+
+static int device_view_args(const void* d_views, int kind, int step)
+{
+    if (kind < HAK_VIEW_IDENTITY || kind > HAK_VIEW_ABSOLUTE) return fail("a view kind must be 0, 1 or 2");
+    if (kind != HAK_VIEW_IDENTITY && !d_views) return fail("null view array");
+    if (step < 0) return fail("a view step must be >= 0");
+    return 0;
+}
+
+extern "C" int hak_triangulate(hak_ctx* c, const hak_match_pair* d_matches, int n, const float* RtA, const float* RtB,
+                               const hak_intrinsics* KA, const hak_intrinsics* KB, float threshold, float max_depth, float min_sin,
+                               unsigned char* d_mask, float* d_xyz, hak_triangulation* h_out)
+{
+    if (list_args(h_out, d_matches, n, "d_matches must be 16-byte aligned")) return 1;
+    if (triangulate_args(KA, KB, threshold, max_depth, min_sin) || host_view_args(RtA) || host_view_args(RtB)) return 1;
+    if (hak_device_count() == 0) return fail("no HIP device: libhipakaze has no CPU fallback");
+    // no scratch.  The record's device copy is a device global that calls take in turn: nothing is allocated
+    static std::mutex record_turn;
+    std::lock_guard<std::mutex> turn(record_turn);
+    hak_triangulation* d_rec = hak_triangulation_record();
+    if (!d_rec) return fail("hipGetSymbolAddress(triangulation record)");
+    hipStream_t st = c ? c->stream : nullptr;
+    order_after_null_stream(c, st);
+    hak_launch_triangulate(st, d_matches, n > 0 ? n : 1, nullptr, 1, n, 1, nullptr, HAK_VIEW_IDENTITY, 0, RtA, nullptr,
+                           HAK_VIEW_IDENTITY, 0, RtB, *KA, *KB, threshold, max_depth, min_sin, d_rec, d_mask, d_xyz);
+    return single_tail(0, st, "triangulation", "record download", h_out, d_rec, sizeof(hak_triangulation));
+}
+
+extern "C" int hak_triangulate_batch(hak_ctx* c, const hak_match_pair* d_matches, long stride, const int* d_counts, int count_step,
+                                     int npairs, const void* d_viewsA, int kindA, int view_stepA, const void* d_viewsB, int kindB,
+                                     int view_stepB, const hak_intrinsics* KA, const hak_intrinsics* KB, float threshold,
+                                     float max_depth, float min_sin, hak_triangulation* d_out, unsigned char* d_masks, float* d_xyz)
+{
+    // the context is looked at last, so that every other refusal can be told from it
+    if (!d_matches || !d_counts || !d_out) return fail("null argument");
+    if (npairs < 1 || stride < 1) return fail("npairs and the stride must be >= 1");
+    if (count_step < 1) return fail("the count step must be >= 1");
+    if (misaligned16(d_matches)) return fail("d_matches must be 16-byte aligned");
+    if (device_view_args(d_viewsA, kindA, view_stepA) || device_view_args(d_viewsB, kindB, view_stepB)) return 1;
+    if (triangulate_args(KA, KB, threshold, max_depth, min_sin)) return 1;
+    if (!c) return fail("null context");
+    order_after_null_stream(c, c->stream);
+    hak_launch_triangulate(c->stream, d_matches, stride, d_counts, count_step, 0, npairs, d_viewsA, kindA, view_stepA, nullptr, d_viewsB,
+                           kindB, view_stepB, nullptr, *KA, *KB, threshold, max_depth, min_sin, d_out, d_masks, d_xyz);
+    if (hipGetLastError() != hipSuccess) return fail("triangulation launch failed");
+    return 0;
+}
+
 // ----------------------------------------------------------- guided matching (kernels_guided.hip; the rule: include/hipakaze.h)
 static int guided_args(float radius, int ratio_num, int ratio_den)
 {

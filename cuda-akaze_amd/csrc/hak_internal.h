@@ -832,6 +832,15 @@ void hak_launch_pnp(hipStream_t st, const hak_corr3d* corr, long stride, const i
 void hak_launch_pnp_refit(hipStream_t st, const hak_corr3d* corr, long stride, const int* counts, int n_host, int npairs,
                           const hak_intrinsics& K, float threshold, int rounds, hak_abs_pose* inout, unsigned char* masks,
                           long mask_stride);
+// triangulation under two known views (kernels_triangulate.hip): the count of list k is counts[k * count_step], or counts = NULL:
+// n_host serves the only list; view A of list k is record k * stepA of viewsA (kindA: HAK_VIEW_*), or h_A != NULL: these 12 host
+// floats serve every list; B likewise; masks and xyz (3 floats per record) at the lists' stride, either may be NULL; no scratch.
+// hak_triangulation_record(): the current device's one record for the synchronous call (NULL on failure)
+hak_triangulation* hak_triangulation_record();
+void hak_launch_triangulate(hipStream_t st, const hak_match_pair* matches, long stride, const int* counts, int count_step, int n_host,
+                            int npairs, const void* viewsA, int kindA, int stepA, const float* h_A, const void* viewsB, int kindB,
+                            int stepB, const float* h_B, const hak_intrinsics& KA, const hak_intrinsics& KB, float threshold,
+                            float max_depth, float min_sin, hak_triangulation* out, unsigned char* masks, float* xyz);
 // track linking (kernels_pnp.hip): countsA / countsB NULL: nA_host / nB_host serve the only pair; `table`: npairs * max_index ints
 // of scratch, cleared by the launch; masksA may be NULL
 void hak_launch_link(hipStream_t st, const hak_match_pair* A, long strideA, const int* countsA, int stepA, int nA_host,

@@ -1,6 +1,7 @@
 // pnp_common.h -- what the absolute-pose kernels share (kernels_pnp.hip, kernels_pnprefit.hip): the correspondence record as the
 // kernels load it, the reprojection test of step 6 of hak_solve_pnp (include/hipakaze.h) and the estimator's view for the scaffolds
 // of ransac_common.h and refit_common.h.
+// kernels_triangulate.hip takes the reprojection test from here as gate 2 of hak_triangulate.
 // Every file that includes it is built with -ffp-contract=off.
 #pragma once
 #include "ransac_common.h"

@@ -185,6 +185,29 @@ namespace akaze
         return r.candidate < 0 ? -1 : r.in_front;
     }
 
+    int cuTriangulate(const hak_match_pair* matches, int n, const float* RtA, const float* RtB, const hak_intrinsics& KA,
+                      const hak_intrinsics& KB, float* xyz, unsigned char* mask, float threshold, float max_depth, float min_sin)
+    {
+        if (n < 0 || (n > 0 && !matches)) { fprintf(stderr, "hip-akaze: cuTriangulate: bad argument\n"); exit(-1); }
+        hak_match_pair* d_matches = nullptr;
+        unsigned char* d_mask = nullptr;
+        float* d_xyz = nullptr;
+        if (n > 0) {
+            if (hipMalloc((void**)&d_matches, sizeof(hak_match_pair) * (size_t)n) != hipSuccess) die("cuTriangulate alloc");
+            if (mask && hipMalloc((void**)&d_mask, (size_t)n) != hipSuccess) die("cuTriangulate alloc");
+            if (xyz && hipMalloc((void**)&d_xyz, sizeof(float) * 3 * (size_t)n) != hipSuccess) die("cuTriangulate alloc");
+            if (hak_memcpy_h2d(d_matches, matches, (long)(sizeof(hak_match_pair) * (size_t)n))) die("cuTriangulate upload");
+        }
+        hak_triangulation r;
+        if (hak_triangulate(NULL, d_matches, n, RtA, RtB, &KA, &KB, threshold, max_depth, min_sin, d_mask, d_xyz, &r)) die("cuTriangulate");
+        if (d_mask && hak_memcpy_d2h(mask, d_mask, n)) die("cuTriangulate download");
+        if (d_xyz && hak_memcpy_d2h(xyz, d_xyz, (long)(sizeof(float) * 3 * (size_t)n))) die("cuTriangulate download");
+        if (d_xyz) (void)hipFree(d_xyz);
+        if (d_mask) (void)hipFree(d_mask);
+        if (d_matches) (void)hipFree(d_matches);
+        return r.kept;
+    }
+
     int cuLinkTracks(const hak_match_pair* A, int nA, const float* xyzA, const unsigned char* maskA, const hak_match_pair* B, int nB,
                      int max_index, hak_corr3d* out)
     {

@@ -64,6 +64,15 @@ int main()
             REQUIRE(cuRecoverPose(NULL, 0, F, K, K, R, t) == 0);
             F[7] = 0.f;                                                 // the stub's "no pose"
             REQUIRE(cuRecoverPose(pairs.data(), np, F, K, K, R, t, mask.data()) == -1 && t[0] == 0.f && mask[3] == 0);
+            {                                                           // triangulation: exact-size mask and points, host views
+                std::vector<float> xyz(3 * (size_t)np);
+                const float RtB[12] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f, -1.f, 0.f, 0.f};
+                REQUIRE(cuTriangulate(pairs.data(), np, NULL, RtB, K, K, xyz.data(), mask.data()) == (np + 2) / 3 && mask[3] == 1 &&
+                        mask[1] == 0 && xyz[9] == -1.f && xyz[11] == 1.f && xyz[3] == 0.f && xyz[3 * (size_t)np - 1] == ((np - 1) % 3 ? 0.f : 1.f));
+                REQUIRE(cuTriangulate(pairs.data(), np, RtB, RtB, K, K, xyz.data()) == (np + 2) / 3 && xyz[9] == -2.f);
+                REQUIRE(cuTriangulate(pairs.data(), np, RtB, NULL, K, K, NULL, mask.data()) == (np + 2) / 3 && mask[3] == 1);
+                REQUIRE(cuTriangulate(NULL, 0, NULL, RtB, K, K, NULL) == 0);
+            }
             std::vector<hak_corr3d> corr(np);                           // absolute pose and its refit: exact-size list and mask
             for (int i = 0; i < np; i++) corr[i] = hak_corr3d{(float)i, 1.f, 5.f, pairs[i].x2, pairs[i].y2, i, i, 0};
             REQUIRE(cuSolvePnP(corr.data(), np, K, R, t, mask.data()) == (np + 2) / 3 && mask[3] == 1 && mask[1] == 0 && t[2] == 1.f);

@@ -170,6 +170,37 @@ int hak_recover_pose(hak_ctx*, const hak_match_pair* d, int n, const float* F, c
     }
     return 0;
 }
+// as hak_recover_pose's stub: every record and every entry of a host view read, every mask byte and xyz float written; "kept" are
+// the indices that are multiples of 3, their point is (tA0 + tB0, 0, 1)
+int hak_triangulate(hak_ctx*, const hak_match_pair* d, int n, const float* RtA, const float* RtB, const hak_intrinsics* KA,
+                    const hak_intrinsics* KB, float threshold, float max_depth, float min_sin, unsigned char* mask, float* xyz,
+                    hak_triangulation* out)
+{
+    if (!out || !KA || !KB || n < 0 || (n > 0 && !d) || !(threshold > 0.f) || !(max_depth > 0.f) || !(min_sin >= 0.f && min_sin < 1.f) ||
+        KA->fx == 0.f || KB->fy == 0.f) {
+        g_err = "bad argument";
+        return 1;
+    }
+    float sum = 0.f;
+    for (int k = 0; k < 12; k++) sum += (RtA ? RtA[k] : 0.f) + (RtB ? RtB[k] : 0.f);
+    if (sum != sum) {
+        g_err = "a host view has a non-finite entry";
+        return 1;
+    }
+    *out = hak_triangulation{n, 0, {0, 0, 0}, 1, {0, 0}};
+    for (int i = 0; i < n; i++) {
+        const bool in = d[i].x1 == d[i].x1 && i % 3 == 0;
+        out->kept += in;
+        out->rejected[2] += !in;
+        if (mask) mask[i] = in;
+        if (xyz) {
+            xyz[3 * i] = in ? (RtA ? RtA[9] : 0.f) + (RtB ? RtB[9] : 0.f) : 0.f;
+            xyz[3 * i + 1] = 0.f;
+            xyz[3 * i + 2] = in ? 1.f : 0.f;
+        }
+    }
+    return 0;
+}
 // the link rule itself, on the host: every record of both lists, every used mask byte and point read, `count` records written
 int hak_link_tracks(hak_ctx*, const hak_match_pair* A, int nA, const unsigned char* maskA, const float* xyzA, const hak_match_pair* B,
                     int nB, int max_index, hak_corr3d* d_out, int* count, hak_corr3d* h_out)
@@ -224,7 +255,7 @@ int hak_refine_pnp(hak_ctx*, const hak_corr3d* d, int n, const hak_intrinsics* K
     }
     return 0;
 }
-// the HIP runtime calls of cuMatchKnn, cuFindHomography, cuFindFundamental, cuRefineFundamental, cuRecoverPose, cuLinkTracks,
+// the HIP runtime calls of cuMatchKnn, cuFindHomography, cuFindFundamental, cuRefineFundamental, cuRecoverPose, cuTriangulate, cuLinkTracks,
 // cuSolvePnP and cuRefinePnP
 hipError_t hipMalloc(void** p, size_t n) { *p = malloc(n); return *p ? hipSuccess : hipErrorOutOfMemory; }
 hipError_t hipFree(void* p) { free(p); return hipSuccess; }

@@ -48,6 +48,17 @@ namespace akaze
                       float R[9], float t[3], unsigned char* front_mask = nullptr, float threshold = 1.f,
                       float max_depth = __builtin_inff());
 
+    // build-side addition: a fourth view.  cuTriangulate (hak_triangulate) triangulates a host match list under two known views,
+    // on the device: RtA, RtB are 12 floats {R row-major, t} with Xc = R X + t (cuRecoverPose's, cuSolvePnP's or cuRefinePnP's R
+    // and t side by side), NULL = the identity.  xyz, when not NULL, gets 3 n floats (the midpoint of the two rays' common
+    // perpendicular in the frame the views map from; zeros for a rejected match) and mask, when not NULL, n bytes (1 = the rays'
+    // angle has a sine >= min_sin, the point lies in front of both cameras nearer than max_depth, and it reprojects within
+    // `threshold` px in both images).  Returns the number of such matches.  With (RtA, RtB) = (pose of I1, pose of I2) over the
+    // matches of (I1, I2), mask and xyz are what cuLinkTracks takes as maskA and xyzA to reach I3.
+    int cuTriangulate(const hak_match_pair* matches, int n, const float* RtA, const float* RtB, const hak_intrinsics& KA,
+                      const hak_intrinsics& KB, float* xyz, unsigned char* mask = nullptr, float threshold = 2.f,
+                      float max_depth = __builtin_inff(), float min_sin = 0.f);
+
     // build-side addition: a third view.  cuLinkTracks (hak_link_tracks) joins the host match list A of images (I0, I1), with a point
     // per match (xyzA, 3 n floats, as hak_recover_pose writes them; maskA NULL or nA bytes, 0 = leave the match out), and the host
     // match list B of images (I1, I2) on the keypoints of I1 (indices below max_index): `out` (room for nB records) receives one

@@ -578,6 +578,82 @@ int hak_refine_pnp(hak_ctx* ctx, const hak_corr3d* d_corr, int n, const hak_intr
 int hak_refine_pnp_batch(hak_ctx* ctx, const hak_corr3d* d_corr, long stride, const int* d_counts, int npairs,
                          const hak_intrinsics* K, float threshold, int rounds, hak_abs_pose* d_inout, unsigned char* d_masks);
 
+/* ---- a fourth view: triangulation under two known views (build-side addition; the stage behind hak_refine_pnp).  The only 3-D
+ * points the stages above produce are those hak_recover_pose computes from images (I0, I1).  With the pose of I1 (hak_recover_pose)
+ * and the absolute pose of I2 (hak_solve_pnp, hak_refine_pnp) both known in the first camera's frame, the matches of (I1, I2) are
+ * triangulated under those two views, in the same frame and scale and in the layout hak_link_tracks reads, so that linking them to
+ * the matches of (I2, I3) and another hak_solve_pnp give the pose of I3 -- and so on.  A view is Xc = R X + t; the points are in
+ * the frame the two views map FROM, in the units of their t.
+ * A pure function of (matches, view A, view B, KA, KB, threshold, max_depth, min_sin); tests/triangulate_ref.py is its bit-exact
+ * numpy statement.  float64, no FMA, + - * / only, except where float32 is named; records are read as by hak_find_fundamental
+ * (x1, y1 is seen by view A, x2, y2 by view B); dot as in hak_recover_pose.
+ *   1. No model: a view of kind HAK_VIEW_RELATIVE with candidate < 0, of kind HAK_VIEW_ABSOLUTE with hypothesis < 0, or with a
+ *      non-finite entry of R or t, gives the no-model record {n, 0, {0, 0, 0}, 0, 0, 0}, an all-zero mask and all-zero points.  An
+ *      identity view (kind HAK_VIEW_IDENTITY, or a NULL host view) is R = I, t = 0, always has a model and goes through every
+ *      expression below like any other.
+ *   2. Centres: R and t widened to float64; cA_j = -((RA[0][j] tA0 + RA[1][j] tA1) + RA[2][j] tA2) for j = 0..2, cB likewise;
+ *      w = cA - cB.
+ *   3. Rays, per match: xa = (x1 - cxA) / fxA, ya = (y1 - cyA) / fyA, a_j = (RA[0][j] xa + RA[1][j] ya) + RA[2][j] -- the bearing
+ *      turned into the common frame; b likewise from (x2, y2), KB and RB.  aa = dot(a, a), bb = dot(b, b), ab = dot(a, b),
+ *      aw = dot(a, w), bw = dot(b, w); det = aa bb - ab ab, z1 = (ab bw - bb aw) / det, z2 = (aa bw - ab aw) / det -- the
+ *      least-squares solution of cA + z1 a = cB + z2 b, in the form of step 5 of hak_recover_pose.  The bearings have third camera
+ *      coordinate 1, so z1 and z2 are depths along the optical axes, in the units of the views' t.
+ *   4. Gate 0, parallax: det > 0 and det >= s2 (aa bb), s2 = min_sin min_sin with min_sin widened to float64 first (det / (aa bb)
+ *      is the squared sine of the angle between the rays).  NaN fails, so a record with a non-finite coordinate is rejected here.
+ *   5. Gate 1, depth: 0 < z1 < max_depth and 0 < z2 < max_depth (max_depth widened to float64; both bounds strict).
+ *   6. Point: P_j = 0.5 ((cA_j + z1 a_j) + (cB_j + z2 b_j)), rounded to float32: the midpoint of the common perpendicular.
+ *   7. Gate 2, reprojection: the float32 test of step 6 of hak_solve_pnp, unchanged, of the float32 P under view A's float32
+ *      (R, t), KA and the observation (x1, y1), and again under view B with KB and (x2, y2); both must pass at
+ *      t2 = threshold * threshold in float32.
+ *   8. Outputs: mask 1 and xyz = P for a match that passes every gate, mask 0 and xyz (0, 0, 0) otherwise; kept = the matches
+ *      that passed, rejected[g] = the matches whose FIRST failed gate is g, so kept + rejected[0] + rejected[1] + rejected[2] = n
+ *      when there is a model.
+ * Every value reduced across lanes is an integer count, so the result does not depend on the launch shape.
+ * Limits: a midpoint solve under a reprojection gate, not a reprojection-error minimum, and there is no per-point refit -- three
+ * Gauss-Newton rounds per point moved no figure of the four-view accuracy table (README.md) by more than its last digit, except one
+ * translation direction on the 1 px leg, for the worse.  Two views only: no multi-view tracks, no bundle adjustment.  No lens
+ * distortion, no skew.  With A the identity and B a pair's own hak_pose the point set is close to hak_recover_pose's but not
+ * bit-identical: a different frame for the solve, a midpoint instead of a point on the first ray, a reprojection gate instead of
+ * a Sampson gate.
+ * Refused with a non-zero status and a message before any device is touched: a threshold that is not finite or not > 0, a
+ * max_depth that is NaN or not > 0 (+inf is allowed), a min_sin outside [0, 1) or NaN, a kind outside 0..2, a NULL view array for
+ * kind 1 or 2, a view step < 0, a count step < 1, fx or fy not finite or 0, a non-finite cx or cy, NULL KA / KB / h_out / d_out /
+ * d_counts, n < 0, a NULL list with n > 0, a list that is not 16-byte aligned, npairs < 1, stride < 1, a NULL context for the batch
+ * form, a non-finite entry of a host RtA or RtB.  Device code: csrc/kernels_triangulate.hip. */
+enum { HAK_VIEW_IDENTITY = 0, HAK_VIEW_RELATIVE = 1, HAK_VIEW_ABSOLUTE = 2 };
+typedef struct hak_triangulation {   /* 32 bytes */
+    int n;                   /* matches considered */
+    int kept;                /* matches that passed every gate: mask = 1, a point written */
+    int rejected[3];         /* by the FIRST gate a match fails: 0 parallax, 1 depth, 2 reprojection; kept + sum = n when model */
+    int model;               /* 1, or 0 = a view without a model: kept = 0, rejected = 0, all-zero mask and points */
+    int pad[2];              /* 0 */
+} hak_triangulation;
+/* one list, synchronous; ctx may be NULL (default stream); RtA / RtB: 12 floats on the HOST {R row-major, t}, Xc = R X + t,
+ * NULL = identity; d_mask (device, n bytes) and d_xyz (device, 3 n floats) may each be NULL; result to *h_out (host).  The call
+ * needs no scratch and allocates nothing: calls share one device-resident record and take it in turn. */
+int hak_triangulate(hak_ctx* ctx, const hak_match_pair* d_matches, int n, const float* RtA, const float* RtB,
+                    const hak_intrinsics* KA, const hak_intrinsics* KB, float threshold, float max_depth, float min_sin,
+                    unsigned char* d_mask, float* d_xyz, hak_triangulation* h_out);
+/* batched, asynchronous on the context's stream.  List k is at d_matches + k*stride, its count d_counts[k*count_step] (read on the
+ * device, clamped to [0, stride]); view A of list k is record k*view_stepA of d_viewsA, read ON THE DEVICE: an array of hak_pose
+ * for kindA = HAK_VIEW_RELATIVE, of hak_abs_pose for HAK_VIEW_ABSOLUTE (both are 64 bytes and begin with R[9], t[3]; no record is
+ * copied or converted), ignored (may be NULL) for HAK_VIEW_IDENTITY; view B likewise.  A step of 0 gives every list the same view.
+ * KA and KB are host arguments, the same for every list.  Record k to d_out[k], the mask of list k to d_masks + k*stride, its
+ * points to d_xyz + 3*k*stride (each unless NULL).  The call needs no scratch and allocates nothing.
+ * After a detect batch of six images per chain (I0, I1, I1, I2, I2, I3) and hak_match_knn2_batch, pairs 3j, 3j+1, 3j+2 are
+ * (I0, I1), (I1, I2), (I2, I3).  With d_pose from hak_recover_pose_batch (one record per pair) and d_abs from hak_refine_pnp_batch
+ * (one per chain), the call on (I1, I2) is d_matches + max_pts, stride 3*max_pts, d_counts + 1, count step 3, npairs = the
+ * chains, view A = d_pose, RELATIVE, step 3, view B = d_abs, ABSOLUTE, step 1, d_masks + max_pts and d_xyz + 3*max_pts of the
+ * buffers hak_recover_pose_batch wrote: mask and points of (I1, I2) then have that call's layout, a following
+ * hak_link_tracks_batch takes d_A = d_matches + max_pts, d_masksA = d_masks + max_pts, d_xyzA = d_xyz + 3*max_pts,
+ * d_B = d_matches + 2*max_pts with strides 3*max_pts and count steps 3, and .. -> hak_refine_pnp_batch -> hak_triangulate_batch ->
+ * hak_link_tracks_batch -> hak_solve_pnp_batch -> hak_refine_pnp_batch gives the pose of I3 with no host synchronisation.  With
+ * A = HAK_VIEW_IDENTITY and B = the pair's own hak_pose the call re-triangulates the first pair under a reprojection gate. */
+int hak_triangulate_batch(hak_ctx* ctx, const hak_match_pair* d_matches, long stride, const int* d_counts, int count_step,
+                          int npairs, const void* d_viewsA, int kindA, int view_stepA, const void* d_viewsB, int kindB,
+                          int view_stepB, const hak_intrinsics* KA, const hak_intrinsics* KB, float threshold,
+                          float max_depth, float min_sin, hak_triangulation* d_out, unsigned char* d_masks, float* d_xyz);
+
 /* ---- guided matching: re-match a pair under its estimated homography (build-side addition; the stage behind
  * hak_find_homography).  The 2-NN search of hak_match_knn2 looks at the whole other image, so on repetitive texture its ratio
  * test rejects correct matches that lose to a look-alike elsewhere; once H is known, each query is searched only among the train
