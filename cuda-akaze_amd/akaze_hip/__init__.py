@@ -577,9 +577,14 @@ class Akazer:
             pass
 
 
+def _ctx_of(akazer):
+    """the context of an optional Akazer; None: the call runs without one"""
+    return akazer.ctx if akazer is not None else None
+
+
 def cuMatch(result1, result2, akazer=None):
     """akaze.h:14, akaze.cpp:55-64: fills match/distance/match_x/match_y of result1."""
-    ctx = akazer.ctx if akazer is not None else None
+    ctx = _ctx_of(akazer)
     hptr = result1.h_data.ctypes.data if result1.h_data is not None else None
     check(lib.hak_match(ctx, result1.d_data, result1.num_pts, result2.d_data, result2.num_pts, hptr))
 
@@ -589,7 +594,7 @@ def cuMatchKnn(result1, result2, ratio=(1, 1), cross_check=True, max_dist=0, aka
     gMatch (akazed.cu:2028-2122) + symmetric cross-check + device-side compaction.  Updates result1 like
     cuMatch and returns the accepted matches (MATCH_PAIR_DTYPE, ascending query index)."""
     import torch
-    ctx = akazer.ctx if akazer is not None else None
+    ctx = _ctx_of(akazer)
     n1 = result1.num_pts
     d_out = torch.zeros(max(n1, 1) * MATCH_PAIR_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
     h_out = np.zeros(max(n1, 1), MATCH_PAIR_DTYPE)
@@ -606,7 +611,7 @@ def cuMatchGuided(result1, result2, H, radius=8.0, ratio=(4, 5), cross_check=Tru
     it; ratio test and cross-check inside that neighbourhood.  Updates result1 like cuMatch and returns the accepted matches
     (MATCH_PAIR_DTYPE, ascending query index)."""
     import torch
-    ctx = akazer.ctx if akazer is not None else None
+    ctx = _ctx_of(akazer)
     n1 = result1.num_pts
     h = np.ascontiguousarray(np.asarray(H, np.float32).reshape(9))
     d_out = torch.zeros(max(n1, 1) * MATCH_PAIR_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
@@ -625,7 +630,7 @@ def cuMatchEpipolar(result1, result2, F, radius=2.0, ratio=(4, 5), cross_check=T
     train points closer than `radius` pixels to its epipolar line; ratio test and cross-check inside that band.  Updates result1
     like cuMatch and returns the accepted matches (MATCH_PAIR_DTYPE, ascending query index)."""
     import torch
-    ctx = akazer.ctx if akazer is not None else None
+    ctx = _ctx_of(akazer)
     n1 = result1.num_pts
     f = np.ascontiguousarray(np.asarray(F, np.float32).reshape(9))
     d_out = torch.zeros(max(n1, 1) * MATCH_PAIR_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
@@ -638,24 +643,42 @@ def cuMatchEpipolar(result1, result2, F, radius=2.0, ratio=(4, 5), cross_check=T
     return h_out[:cnt.value].copy()
 
 
+def _device_records(a, dtype):
+    """(device uint8 tensor, record count) of a host structured array or of a device tensor of such records (used in place)"""
+    import torch
+    if isinstance(a, torch.Tensor):
+        d = a.contiguous()
+        return d, d.numel() * d.element_size() // dtype.itemsize
+    host = np.ascontiguousarray(a, dtype)
+    n = len(host)
+    return (torch.from_numpy(host.view(np.uint8).reshape(-1)).cuda() if n else torch.zeros(32, dtype=torch.uint8, device="cuda")), n
+
+
+def _out_buffers(n, xyz=False):
+    """the device outputs of a call over n records, never empty: (mask of max(n, 1) bytes, with `xyz` the points of 3 * max(n, 1)
+    floats, else None)"""
+    import torch
+    return (torch.zeros(max(n, 1), dtype=torch.uint8, device="cuda"),
+            torch.zeros(3 * max(n, 1), dtype=torch.float32, device="cuda") if xyz else None)
+
+
+def _out_host(n, d_mask, d_xyz=None):
+    """what a call over n records returns of _out_buffers: (mask uint8 (n,),) and, with d_xyz, xyz float32 (n, 3)"""
+    mask = (d_mask[:n].cpu().numpy(),)
+    return mask if d_xyz is None else mask + (d_xyz[:3 * n].cpu().numpy().reshape(n, 3),)
+
+
 def findHomography(matches, iterations=1024, threshold=3.0, seed=0, refine=True, akazer=None):
     """RANSAC homography over a match list (hipakaze.h hak_find_homography), on the device.  `matches`: the MATCH_PAIR_DTYPE
     array cuMatchKnn returns (host), or a device tensor of such records (then it is used in place).  Returns (record of
     HOMOGRAPHY_DTYPE, inlier mask as a uint8 numpy array); record["H"].reshape(3, 3) maps (x1, y1, 1) to image 2."""
-    import torch
-    ctx = akazer.ctx if akazer is not None else None
-    if isinstance(matches, torch.Tensor):
-        d_m = matches.contiguous()
-        n = d_m.numel() * d_m.element_size() // MATCH_PAIR_DTYPE.itemsize
-    else:
-        host = np.ascontiguousarray(matches, MATCH_PAIR_DTYPE)
-        n = len(host)
-        d_m = torch.from_numpy(host.view(np.uint8).reshape(-1)).cuda() if n else torch.zeros(32, dtype=torch.uint8, device="cuda")
-    d_mask = torch.zeros(max(n, 1), dtype=torch.uint8, device="cuda")
+    ctx = _ctx_of(akazer)
+    d_m, n = _device_records(matches, MATCH_PAIR_DTYPE)
+    d_mask, _ = _out_buffers(n)
     out = np.zeros((), HOMOGRAPHY_DTYPE)
     check(lib.hak_find_homography(ctx, d_m.data_ptr(), n, int(iterations), float(threshold), int(seed) & 0xFFFFFFFF, int(bool(refine)),
                                   d_mask.data_ptr(), out.ctypes.data))
-    return out, d_mask[:n].cpu().numpy()
+    return (out,) + _out_host(n, d_mask)
 
 
 def findFundamental(matches, iterations=1024, threshold=1.0, seed=0, akazer=None):
@@ -663,20 +686,13 @@ def findFundamental(matches, iterations=1024, threshold=1.0, seed=0, akazer=None
     Returns (record of FUNDAMENTAL_DTYPE, inlier mask as a uint8 numpy array); F = record["F"].reshape(3, 3) satisfies
     (x2, y2, 1) F (x1, y1, 1)^T = 0 for the inliers.  The seven-point model of the winning sample; refineFundamental refits it over its
     inliers."""
-    import torch
-    ctx = akazer.ctx if akazer is not None else None
-    if isinstance(matches, torch.Tensor):
-        d_m = matches.contiguous()
-        n = d_m.numel() * d_m.element_size() // MATCH_PAIR_DTYPE.itemsize
-    else:
-        host = np.ascontiguousarray(matches, MATCH_PAIR_DTYPE)
-        n = len(host)
-        d_m = torch.from_numpy(host.view(np.uint8).reshape(-1)).cuda() if n else torch.zeros(32, dtype=torch.uint8, device="cuda")
-    d_mask = torch.zeros(max(n, 1), dtype=torch.uint8, device="cuda")
+    ctx = _ctx_of(akazer)
+    d_m, n = _device_records(matches, MATCH_PAIR_DTYPE)
+    d_mask, _ = _out_buffers(n)
     out = np.zeros((), FUNDAMENTAL_DTYPE)
     check(lib.hak_find_fundamental(ctx, d_m.data_ptr(), n, int(iterations), float(threshold), int(seed) & 0xFFFFFFFF,
                                    d_mask.data_ptr(), out.ctypes.data))
-    return out, d_mask[:n].cpu().numpy()
+    return (out,) + _out_host(n, d_mask)
 
 
 def refineFundamental(matches, record, threshold=1.0, rounds=3, akazer=None):
@@ -684,19 +700,12 @@ def refineFundamental(matches, record, threshold=1.0, rounds=3, akazer=None):
     hak_refine_fundamental), on the device.  `matches` as findHomography's; `record`: a FUNDAMENTAL_DTYPE record, findFundamental's
     or an earlier refit's (it is not modified).  Returns (record, inlier mask as a uint8 numpy array): record["root"] == 3 when a
     refit was accepted, and record["inliers"] is never below the input F's count at `threshold`."""
-    import torch
-    ctx = akazer.ctx if akazer is not None else None
-    if isinstance(matches, torch.Tensor):
-        d_m = matches.contiguous()
-        n = d_m.numel() * d_m.element_size() // MATCH_PAIR_DTYPE.itemsize
-    else:
-        host = np.ascontiguousarray(matches, MATCH_PAIR_DTYPE)
-        n = len(host)
-        d_m = torch.from_numpy(host.view(np.uint8).reshape(-1)).cuda() if n else torch.zeros(32, dtype=torch.uint8, device="cuda")
-    d_mask = torch.zeros(max(n, 1), dtype=torch.uint8, device="cuda")
+    ctx = _ctx_of(akazer)
+    d_m, n = _device_records(matches, MATCH_PAIR_DTYPE)
+    d_mask, _ = _out_buffers(n)
     out = np.array(record, FUNDAMENTAL_DTYPE).reshape(())
     check(lib.hak_refine_fundamental(ctx, d_m.data_ptr(), n, float(threshold), int(rounds), d_mask.data_ptr(), out.ctypes.data))
-    return out, d_mask[:n].cpu().numpy()
+    return (out,) + _out_host(n, d_mask)
 
 
 def intrinsics(K):
@@ -714,15 +723,8 @@ def recoverPose(matches, F_or_record, K1, K2=None, threshold=1.0, max_depth=floa
     omitted.  Returns (record of POSE_DTYPE, mask uint8 (n,), xyz float32 (n, 3)): X2 = R X1 + t with |t| = 1, the mask marks the
     inliers of F in front of both cameras, xyz their points in the first camera's frame in units of the baseline; candidate = -1
     means no pose."""
-    import torch
-    ctx = akazer.ctx if akazer is not None else None
-    if isinstance(matches, torch.Tensor):
-        d_m = matches.contiguous()
-        n = d_m.numel() * d_m.element_size() // MATCH_PAIR_DTYPE.itemsize
-    else:
-        host = np.ascontiguousarray(matches, MATCH_PAIR_DTYPE)
-        n = len(host)
-        d_m = torch.from_numpy(host.view(np.uint8).reshape(-1)).cuda() if n else torch.zeros(32, dtype=torch.uint8, device="cuda")
+    ctx = _ctx_of(akazer)
+    d_m, n = _device_records(matches, MATCH_PAIR_DTYPE)
     if getattr(F_or_record, "dtype", None) is not None and F_or_record.dtype.names:
         f = np.array(F_or_record["F"], np.float32).reshape(9)
         if int(F_or_record["hypothesis"]) < 0:
@@ -731,12 +733,11 @@ def recoverPose(matches, F_or_record, K1, K2=None, threshold=1.0, max_depth=floa
         f = np.ascontiguousarray(np.asarray(F_or_record, np.float32).reshape(9))
     k1 = intrinsics(K1)
     k2 = k1 if K2 is None else intrinsics(K2)
-    d_mask = torch.zeros(max(n, 1), dtype=torch.uint8, device="cuda")
-    d_xyz = torch.zeros(3 * max(n, 1), dtype=torch.float32, device="cuda")
+    d_mask, d_xyz = _out_buffers(n, xyz=True)
     out = np.zeros((), POSE_DTYPE)
     check(lib.hak_recover_pose(ctx, d_m.data_ptr(), n, f.ctypes.data_as(_fp), k1.ctypes.data, k2.ctypes.data, float(threshold),
                                float(max_depth), d_mask.data_ptr(), d_xyz.data_ptr(), out.ctypes.data))
-    return out, d_mask[:n].cpu().numpy(), d_xyz[:3 * n].cpu().numpy().reshape(n, 3)
+    return (out,) + _out_host(n, d_mask, d_xyz)
 
 
 def _host_view(v):
@@ -761,8 +762,7 @@ def triangulate(matches, viewA, viewB, KA, KB=None, threshold=2.0, max_depth=flo
     cameras) and the reprojection gate (below `threshold` px in both images); xyz holds their points in the frame the views map
     from, zeros elsewhere.  A record view without a model, or with a non-finite entry, is step 1 of the rule, which needs no
     device: the no-model record (model = 0), an all-zero mask and all-zero points."""
-    import torch
-    ctx = akazer.ctx if akazer is not None else None
+    ctx = _ctx_of(akazer)
     d_m, n = _device_records(matches, MATCH_PAIR_DTYPE)
     (a, model_a), (b, model_b) = _host_view(viewA), _host_view(viewB)
     ka = intrinsics(KA)
@@ -771,23 +771,11 @@ def triangulate(matches, viewA, viewB, KA, KB=None, threshold=2.0, max_depth=flo
     if not (model_a and model_b):
         out["n"] = n
         return out, np.zeros(n, np.uint8), np.zeros((n, 3), np.float32)
-    d_mask = torch.zeros(max(n, 1), dtype=torch.uint8, device="cuda")
-    d_xyz = torch.zeros(3 * max(n, 1), dtype=torch.float32, device="cuda")
+    d_mask, d_xyz = _out_buffers(n, xyz=True)
     check(lib.hak_triangulate(ctx, d_m.data_ptr(), n, a.ctypes.data_as(_fp) if a is not None else None,
                               b.ctypes.data_as(_fp) if b is not None else None, ka.ctypes.data, kb.ctypes.data, float(threshold),
                               float(max_depth), float(min_sin), d_mask.data_ptr(), d_xyz.data_ptr(), out.ctypes.data))
-    return out, d_mask[:n].cpu().numpy(), d_xyz[:3 * n].cpu().numpy().reshape(n, 3)
-
-
-def _device_records(a, dtype):
-    """(device uint8 tensor, record count) of a host structured array or of a device tensor of such records (used in place)"""
-    import torch
-    if isinstance(a, torch.Tensor):
-        d = a.contiguous()
-        return d, d.numel() * d.element_size() // dtype.itemsize
-    host = np.ascontiguousarray(a, dtype)
-    n = len(host)
-    return (torch.from_numpy(host.view(np.uint8).reshape(-1)).cuda() if n else torch.zeros(32, dtype=torch.uint8, device="cuda")), n
+    return (out,) + _out_host(n, d_mask, d_xyz)
 
 
 def linkTracks(matchesA, xyzA, matchesB, maskA=None, max_index=None, akazer=None):
@@ -796,7 +784,7 @@ def linkTracks(matchesA, xyzA, matchesB, maskA=None, max_index=None, akazer=None
     findHomography's; maskA: nA bytes (recoverPose's front mask) or None; max_index: a bound above every keypoint index of I1
     (default: one above the largest train index of a host list A).  Returns a CORR3D_DTYPE array in ascending order of B."""
     import torch
-    ctx = akazer.ctx if akazer is not None else None
+    ctx = _ctx_of(akazer)
     d_a, na = _device_records(matchesA, MATCH_PAIR_DTYPE)
     d_b, nb = _device_records(matchesB, MATCH_PAIR_DTYPE)
     if max_index is None:
@@ -822,15 +810,14 @@ def solvePnP(corr, K, iterations=1024, threshold=2.0, seed=0, akazer=None):
     `corr`: the CORR3D_DTYPE array linkTracks returns (host), or a device tensor of such records (used in place); K: (fx, fy, cx, cy),
     a 3 x 3 matrix or an INTRINSICS_DTYPE record.  Returns (record of ABS_POSE_DTYPE, inlier mask as a uint8 numpy array):
     Xc = R X + t in the units of the points; hypothesis = -1 means no model."""
-    import torch
-    ctx = akazer.ctx if akazer is not None else None
+    ctx = _ctx_of(akazer)
     d_c, n = _device_records(corr, CORR3D_DTYPE)
     k = intrinsics(K)
-    d_mask = torch.zeros(max(n, 1), dtype=torch.uint8, device="cuda")
+    d_mask, _ = _out_buffers(n)
     out = np.zeros((), ABS_POSE_DTYPE)
     check(lib.hak_solve_pnp(ctx, d_c.data_ptr(), n, k.ctypes.data, int(iterations), float(threshold), int(seed) & 0xFFFFFFFF,
                             d_mask.data_ptr(), out.ctypes.data))
-    return out, d_mask[:n].cpu().numpy()
+    return (out,) + _out_host(n, d_mask)
 
 
 def refinePnP(corr, K, record, threshold=2.0, rounds=3, akazer=None):
@@ -838,11 +825,10 @@ def refinePnP(corr, K, record, threshold=2.0, rounds=3, akazer=None):
     the device.  `corr` and K as solvePnP's; `record`: an ABS_POSE_DTYPE record, solvePnP's or an earlier refit's (it is not
     modified).  Returns (record, inlier mask as a uint8 numpy array): record["solution"] == 4 when a refit was accepted, and
     record["inliers"] is never below the input pose's count at `threshold`."""
-    import torch
-    ctx = akazer.ctx if akazer is not None else None
+    ctx = _ctx_of(akazer)
     d_c, n = _device_records(corr, CORR3D_DTYPE)
     k = intrinsics(K)
-    d_mask = torch.zeros(max(n, 1), dtype=torch.uint8, device="cuda")
+    d_mask, _ = _out_buffers(n)
     out = np.array(record, ABS_POSE_DTYPE).reshape(())
     check(lib.hak_refine_pnp(ctx, d_c.data_ptr(), n, k.ctypes.data, float(threshold), int(rounds), d_mask.data_ptr(), out.ctypes.data))
-    return out, d_mask[:n].cpu().numpy()
+    return (out,) + _out_host(n, d_mask)

@@ -6,6 +6,7 @@
 // hak_find_fundamental, also the critical points of hak_solve_pnp's quartic), and the 3 x 3 cyclic Jacobi of the refit's rule.
 // The RANSAC scaffold of the three estimators is ransac_common.h, which includes this and holds the views hg_est and fd_est; the
 // refit scaffold (inlier count, Hartley passes, normal equations, elimination, round loop) is refit_common.h on top of that.
+// What the two point kernels share (kernels_pose.hip, kernels_triangulate.hip) is points_common.h, which also includes this.
 // Every file that includes it is built with -ffp-contract=off.
 #pragma once
 #include "hak_internal.h"
@@ -33,9 +34,10 @@ __device__ __forceinline__ float4 fd_load(const hak_match_pair* m, int i)
     return r;
 }
 
-__device__ __forceinline__ int fd_count(const int* counts, int pair, int n_host, long stride)
+// the count of list `pair`, clamped to 0 .. stride: counts[pair * step], or counts = NULL: n_host
+__device__ __forceinline__ int fd_count(const int* counts, int pair, int step, int n_host, long stride)
 {
-    long n = counts ? counts[pair] : n_host;
+    long n = counts ? counts[(long)pair * step] : n_host;
     return (int)(n < 0 ? 0 : (n > stride ? stride : n));
 }
 

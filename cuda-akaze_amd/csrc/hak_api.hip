@@ -844,40 +844,43 @@ static int refine_args(float threshold, int rounds)
     return 0;
 }
 
-// one refine call on one record after its argument checks.  No scratch: the record's device copy is the context's, or without a
-// context the device global hak_refit_record() that calls take in turn, so nothing is allocated.  launch(stream, d_rec) enqueues the
-// refit of the uploaded record in place.
-static std::mutex g_refit_record_turn;
-template <class Launch>
-static int refine_single(hak_ctx* c, void* h_inout, size_t bytes, const char* what, const char* no_symbol, Launch launch)
+// one synchronous one-list call on one record, after its argument checks, on c's stream (c may be NULL).  No scratch: the record's
+// device copy is `owner`'s geom_rec, or with owner = NULL the device global hak_shared_record(), so nothing is allocated.  The refits
+// pass their context as the owner; hak_recover_pose and hak_triangulate never name one.  h_in != NULL: the record is in/out and is
+// uploaded first.  launch(stream, d_rec) enqueues the kernel, and the record comes back to h_out.
+// The shared record has one mutex: calls without an owner take it in turn, whatever their kind.  Each of them synchronises its
+// stream before it returns anyway, so no two of them could have overlapped on the device.
+static std::mutex g_shared_record_turn;
+template <class Rec, class Launch>
+static int record_single(hak_ctx* c, hak_ctx* owner, const void* h_in, Rec* h_out, const char* what, Launch launch)
 {
+    static_assert(sizeof(Rec) <= HAK_REC_BYTES, "the one record holds every record type");
     if (hak_device_count() == 0) return fail("no HIP device: libhipakaze has no CPU fallback");
-    std::unique_lock<std::mutex> turn(g_refit_record_turn, std::defer_lock);
+    std::unique_lock<std::mutex> turn(g_shared_record_turn, std::defer_lock);
     void* d_rec = nullptr;
-    if (c) {
-        if (geom_record(c)) return 1;
-        d_rec = c->geom_rec;
+    if (owner) {
+        if (geom_record(owner)) return 1;
+        d_rec = owner->geom_rec;
     } else {
         turn.lock();
-        d_rec = hak_refit_record();
-        if (!d_rec) return fail(no_symbol);
+        d_rec = hak_shared_record();
+        if (!d_rec) return fail("hipGetSymbolAddress(shared record)");
     }
     hipStream_t st = c ? c->stream : nullptr;
     order_after_null_stream(c, st);
     int rc = 0;
-    if (hipMemcpyAsync(d_rec, h_inout, bytes, hipMemcpyHostToDevice, st) != hipSuccess) rc = fail("record upload");
-    if (!rc) launch(st, d_rec);
-    return single_tail(rc, st, what, "record download", h_inout, d_rec, bytes);
+    if (h_in && hipMemcpyAsync(d_rec, h_in, sizeof(Rec), hipMemcpyHostToDevice, st) != hipSuccess) rc = fail("record upload");
+    if (!rc) launch(st, static_cast<Rec*>(d_rec));
+    return single_tail(rc, st, what, "record download", h_out, d_rec, sizeof(Rec));
 }
 
 extern "C" int hak_refine_fundamental(hak_ctx* c, const hak_match_pair* d_matches, int n, float threshold, int rounds,
                                       unsigned char* d_mask, hak_fundamental* h_inout)
 {
     if (list_args(h_inout, d_matches, n, "d_matches must be 16-byte aligned") || refine_args(threshold, rounds)) return 1;
-    auto launch = [&](hipStream_t st, void* d_rec) {
-        hak_launch_fundamental_refit(st, d_matches, n, nullptr, n, 1, threshold, rounds, static_cast<hak_fundamental*>(d_rec), d_mask, 0);
-    };
-    return refine_single(c, h_inout, sizeof(hak_fundamental), "fundamental refit", "hipGetSymbolAddress(refit record)", launch);
+    return record_single(c, c, h_inout, h_inout, "fundamental refit", [&](hipStream_t st, hak_fundamental* d_rec) {
+        hak_launch_fundamental_refit(st, d_matches, n, nullptr, n, 1, threshold, rounds, d_rec, d_mask, 0);
+    });
 }
 
 extern "C" int hak_refine_fundamental_batch(hak_ctx* c, const hak_match_pair* d_matches, long stride, const int* d_counts,
@@ -907,16 +910,9 @@ extern "C" int hak_recover_pose(hak_ctx* c, const hak_match_pair* d_matches, int
 {
     if (list_args(F ? h_out : nullptr, d_matches, n, "d_matches must be 16-byte aligned")) return 1;
     if (pose_args(K1, K2, threshold, max_depth)) return 1;
-    if (hak_device_count() == 0) return fail("no HIP device: libhipakaze has no CPU fallback");
-    // no scratch.  The record's device copy is a device global that calls take in turn: nothing is allocated
-    static std::mutex record_turn;
-    std::lock_guard<std::mutex> turn(record_turn);
-    hak_pose* d_rec = hak_pose_record();
-    if (!d_rec) return fail("hipGetSymbolAddress(pose record)");
-    hipStream_t st = c ? c->stream : nullptr;
-    order_after_null_stream(c, st);
-    hak_launch_pose(st, d_matches, n > 0 ? n : 1, nullptr, n, 1, nullptr, F, *K1, *K2, threshold, max_depth, d_rec, d_mask, d_xyz);
-    return single_tail(0, st, "pose", "record download", h_out, d_rec, sizeof(hak_pose));
+    return record_single(c, nullptr, nullptr, h_out, "pose", [&](hipStream_t st, hak_pose* d_rec) {
+        hak_launch_pose(st, d_matches, n > 0 ? n : 1, nullptr, n, 1, nullptr, F, *K1, *K2, threshold, max_depth, d_rec, d_mask, d_xyz);
+    });
 }
 
 extern "C" int hak_recover_pose_batch(hak_ctx* c, const hak_match_pair* d_matches, long stride, const int* d_counts, int npairs,
@@ -1027,10 +1023,9 @@ extern "C" int hak_refine_pnp(hak_ctx* c, const hak_corr3d* d_corr, int n, const
 {
     if (list_args(h_inout, d_corr, n, "d_corr must be 16-byte aligned") || refine_args(threshold, rounds) || intrinsics_args(K))
         return 1;
-    auto launch = [&](hipStream_t st, void* d_rec) {
-        hak_launch_pnp_refit(st, d_corr, n, nullptr, n, 1, *K, threshold, rounds, static_cast<hak_abs_pose*>(d_rec), d_mask, 0);
-    };
-    return refine_single(c, h_inout, sizeof(hak_abs_pose), "pnp refit", "hipGetSymbolAddress(pnp refit record)", launch);
+    return record_single(c, c, h_inout, h_inout, "pnp refit", [&](hipStream_t st, hak_abs_pose* d_rec) {
+        hak_launch_pnp_refit(st, d_corr, n, nullptr, n, 1, *K, threshold, rounds, d_rec, d_mask, 0);
+    });
 }
 
 extern "C" int hak_refine_pnp_batch(hak_ctx* c, const hak_corr3d* d_corr, long stride, const int* d_counts, int npairs,
@@ -1076,17 +1071,10 @@ extern "C" int hak_triangulate(hak_ctx* c, const hak_match_pair* d_matches, int 
 {
     if (list_args(h_out, d_matches, n, "d_matches must be 16-byte aligned")) return 1;
     if (triangulate_args(KA, KB, threshold, max_depth, min_sin) || host_view_args(RtA) || host_view_args(RtB)) return 1;
-    if (hak_device_count() == 0) return fail("no HIP device: libhipakaze has no CPU fallback");
-    // no scratch.  The record's device copy is a device global that calls take in turn: nothing is allocated
-    static std::mutex record_turn;
-    std::lock_guard<std::mutex> turn(record_turn);
-    hak_triangulation* d_rec = hak_triangulation_record();
-    if (!d_rec) return fail("hipGetSymbolAddress(triangulation record)");
-    hipStream_t st = c ? c->stream : nullptr;
-    order_after_null_stream(c, st);
-    hak_launch_triangulate(st, d_matches, n > 0 ? n : 1, nullptr, 1, n, 1, nullptr, HAK_VIEW_IDENTITY, 0, RtA, nullptr,
-                           HAK_VIEW_IDENTITY, 0, RtB, *KA, *KB, threshold, max_depth, min_sin, d_rec, d_mask, d_xyz);
-    return single_tail(0, st, "triangulation", "record download", h_out, d_rec, sizeof(hak_triangulation));
+    return record_single(c, nullptr, nullptr, h_out, "triangulation", [&](hipStream_t st, hak_triangulation* d_rec) {
+        hak_launch_triangulate(st, d_matches, n > 0 ? n : 1, nullptr, 1, n, 1, nullptr, HAK_VIEW_IDENTITY, 0, RtA, nullptr,
+                               HAK_VIEW_IDENTITY, 0, RtB, *KA, *KB, threshold, max_depth, min_sin, d_rec, d_mask, d_xyz);
+    });
 }
 
 extern "C" int hak_triangulate_batch(hak_ctx* c, const hak_match_pair* d_matches, long stride, const int* d_counts, int count_step,

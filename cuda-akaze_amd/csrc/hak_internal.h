@@ -809,17 +809,16 @@ long hak_fundamental_words(int npairs, int iterations);
 void hak_launch_fundamental(hipStream_t st, const hak_match_pair* matches, long stride, const int* counts, int n_host, int npairs,
                             int iterations, float threshold, unsigned seed, unsigned* models, unsigned long long* slots,
                             hak_fundamental* out, unsigned char* masks, long mask_stride);
-// rank-2 refit of a fundamental matrix (kernels_fundrefit.hip): record k is read from and rewritten to inout[k]; no scratch.
-// hak_refit_record(): the current device's one record for this refit's and hak_refine_pnp's calls without a context (NULL on failure)
+// hak_shared_record(): the current device's one record of HAK_REC_BYTES (kernels_fundrefit.hip; NULL on failure) for the synchronous
+// one-list calls that own none: both refits without a context, hak_recover_pose and hak_triangulate always.  They take it in turn.
 #define HAK_REC_BYTES 64         // room for the largest record of an estimator or refit (hak_abs_pose)
-void* hak_refit_record();
+void* hak_shared_record();
+// rank-2 refit of a fundamental matrix (kernels_fundrefit.hip): record k is read from and rewritten to inout[k]; no scratch.
 void hak_launch_fundamental_refit(hipStream_t st, const hak_match_pair* matches, long stride, const int* counts, int n_host,
                                   int npairs, float threshold, int rounds, hak_fundamental* inout, unsigned char* masks,
                                   long mask_stride);
 // relative pose from a fundamental matrix (kernels_pose.hip): F of pair k from d_F[k] on the device, or d_F = NULL: h_F[9] on the
 // host serves the only pair; masks and xyz (3 floats per record) at the lists' stride, either may be NULL; no scratch.
-// hak_pose_record(): the current device's one record for the synchronous call (NULL on failure)
-hak_pose* hak_pose_record();
 void hak_launch_pose(hipStream_t st, const hak_match_pair* matches, long stride, const int* counts, int n_host, int npairs,
                      const hak_fundamental* d_F, const float* h_F, const hak_intrinsics& K1, const hak_intrinsics& K2,
                      float threshold, float max_depth, hak_pose* out, unsigned char* masks, float* xyz);
@@ -835,8 +834,6 @@ void hak_launch_pnp_refit(hipStream_t st, const hak_corr3d* corr, long stride, c
 // triangulation under two known views (kernels_triangulate.hip): the count of list k is counts[k * count_step], or counts = NULL:
 // n_host serves the only list; view A of list k is record k * stepA of viewsA (kindA: HAK_VIEW_*), or h_A != NULL: these 12 host
 // floats serve every list; B likewise; masks and xyz (3 floats per record) at the lists' stride, either may be NULL; no scratch.
-// hak_triangulation_record(): the current device's one record for the synchronous call (NULL on failure)
-hak_triangulation* hak_triangulation_record();
 void hak_launch_triangulate(hipStream_t st, const hak_match_pair* matches, long stride, const int* counts, int count_step, int n_host,
                             int npairs, const void* viewsA, int kindA, int stepA, const float* h_A, const void* viewsB, int kindB,
                             int stepB, const float* h_B, const hak_intrinsics& KA, const hak_intrinsics& KB, float threshold,

@@ -161,7 +161,7 @@ __global__ __launch_bounds__(RS_MTHREADS) void k_fund_models(const hak_match_pai
     const int h = blockIdx.y * RS_MTHREADS + threadIdx.x;
     if (h >= iterations) return;
     const hak_match_pair* m = base + (long)pair * stride;
-    const int n = fd_count(counts, pair, n_host, stride);
+    const int n = fd_count(counts, pair, 1, n_host, stride);
     float F[3][9];
 #pragma unroll
     for (int r = 0; r < 3; r++)
@@ -181,7 +181,7 @@ __global__ __launch_bounds__(RS_THREADS) void k_fund_score(const hak_match_pair*
     const int pair = blockIdx.x;
     float F[3][9];
     const int valid = rs_read_models<fd_est>(models, pair, iterations, rs_block_hypothesis(hp), F);
-    rs_score_block(fd_est{{}, t2}, base + (long)pair * stride, fd_count(counts, pair, n_host, stride), hp, F, valid, slots);
+    rs_score_block(fd_est{{}, t2}, base + (long)pair * stride, fd_count(counts, pair, 1, n_host, stride), hp, F, valid, slots);
 }
 
 __global__ __launch_bounds__(HAK_WAVE) void k_fund_finish(const hak_match_pair* __restrict__ base, long stride,
@@ -192,7 +192,7 @@ __global__ __launch_bounds__(HAK_WAVE) void k_fund_finish(const hak_match_pair* 
                                                           long mask_stride)
 {
     const int pair = blockIdx.x;
-    rs_finish(fd_est{{}, t2}, base + (long)pair * stride, fd_count(counts, pair, n_host, stride), iterations, hblocks, models, slots,
+    rs_finish(fd_est{{}, t2}, base + (long)pair * stride, fd_count(counts, pair, 1, n_host, stride), iterations, hblocks, models, slots,
               out, masks, mask_stride);
 }
 

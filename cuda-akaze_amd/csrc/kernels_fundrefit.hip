@@ -172,17 +172,17 @@ __global__ __launch_bounds__(HAK_WAVE) void k_fund_refit(const hak_match_pair* _
                                                          long mask_stride)
 {
     const int pair = blockIdx.x;
-    refit_record(fr_refit{{{}, t2}}, base + (long)pair * stride, fd_count(counts, pair, n_host, stride), rounds, inout, masks,
+    refit_record(fr_refit{{{}, t2}}, base + (long)pair * stride, fd_count(counts, pair, 1, n_host, stride), rounds, inout, masks,
                  mask_stride);
 }
 
-// the record of a hak_refine_fundamental or hak_refine_pnp call without a context: a device global, so the call allocates nothing
-__device__ __attribute__((aligned(16))) char g_refit_record[HAK_REC_BYTES];
+// the one record of the synchronous one-list calls that own none (hak_internal.h): a device global, so such a call allocates nothing
+__device__ __attribute__((aligned(16))) char g_shared_record[HAK_REC_BYTES];
 
-void* hak_refit_record()
+void* hak_shared_record()
 {
     void* p = nullptr;
-    return hipGetSymbolAddress(&p, HIP_SYMBOL(g_refit_record)) == hipSuccess ? p : nullptr;
+    return hipGetSymbolAddress(&p, HIP_SYMBOL(g_shared_record)) == hipSuccess ? p : nullptr;
 }
 
 void hak_launch_fundamental_refit(hipStream_t st, const hak_match_pair* matches, long stride, const int* counts, int n_host,

@@ -124,7 +124,7 @@ __global__ __launch_bounds__(RS_THREADS) void k_hom_score(const hak_match_pair* 
 {
     const int pair = blockIdx.x;
     const hak_match_pair* m = base + (long)pair * stride;
-    const int n = fd_count(counts, pair, n_host, stride);
+    const int n = fd_count(counts, pair, 1, n_host, stride);
     const int h = rs_block_hypothesis(hp);
     float H[1][9];
     const bool ok = h < iterations && hg_hypothesis(m, n, seed, h, H[0]);
@@ -139,7 +139,7 @@ __global__ __launch_bounds__(HAK_WAVE) void k_hom_finish(const hak_match_pair* _
 {
     const int pair = blockIdx.x;
     const hak_match_pair* m = base + (long)pair * stride;
-    const int n = fd_count(counts, pair, n_host, stride);
+    const int n = fd_count(counts, pair, 1, n_host, stride);
     float H[9];
     hg_est::no_model(H);
     int inl, hyp, model;

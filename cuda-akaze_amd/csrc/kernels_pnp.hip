@@ -181,7 +181,7 @@ __global__ __launch_bounds__(RS_MTHREADS) void k_pnp_models(const hak_corr3d* __
     const int h = blockIdx.y * RS_MTHREADS + threadIdx.x;
     if (h >= iterations) return;
     const hak_corr3d* c = base + (long)pair * stride;
-    const int n = fd_count(counts, pair, n_host, stride);
+    const int n = fd_count(counts, pair, 1, n_host, stride);
     rs_write_valid<pn_est>(models, pair, iterations, h, pn_hypothesis(c, n, K, seed, h, models, pair, iterations));
 }
 
@@ -193,7 +193,7 @@ __global__ __launch_bounds__(RS_THREADS) void k_pnp_score(const hak_corr3d* __re
     const int pair = blockIdx.x;
     float M[4][12];
     const int valid = rs_read_models<pn_est>(models, pair, iterations, rs_block_hypothesis(hp), M);
-    rs_score_block(pn_est{K, t2}, base + (long)pair * stride, fd_count(counts, pair, n_host, stride), hp, M, valid, slots);
+    rs_score_block(pn_est{K, t2}, base + (long)pair * stride, fd_count(counts, pair, 1, n_host, stride), hp, M, valid, slots);
 }
 
 __global__ __launch_bounds__(HAK_WAVE) void k_pnp_finish(const hak_corr3d* __restrict__ base, long stride,
@@ -204,7 +204,7 @@ __global__ __launch_bounds__(HAK_WAVE) void k_pnp_finish(const hak_corr3d* __res
                                                          long mask_stride)
 {
     const int pair = blockIdx.x;
-    rs_finish(pn_est{K, t2}, base + (long)pair * stride, fd_count(counts, pair, n_host, stride), iterations, hblocks, models, slots,
+    rs_finish(pn_est{K, t2}, base + (long)pair * stride, fd_count(counts, pair, 1, n_host, stride), iterations, hblocks, models, slots,
               out, masks, mask_stride);
 }
 

@@ -86,7 +86,7 @@ __global__ __launch_bounds__(HAK_WAVE) void k_pnp_refit(const hak_corr3d* __rest
                                                         long mask_stride)
 {
     const int pair = blockIdx.x;
-    refit_record(pr_refit{{K, t2}}, base + (long)pair * stride, fd_count(counts, pair, n_host, stride), rounds, inout, masks,
+    refit_record(pr_refit{{K, t2}}, base + (long)pair * stride, fd_count(counts, pair, 1, n_host, stride), rounds, inout, masks,
                  mask_stride);
 }
 

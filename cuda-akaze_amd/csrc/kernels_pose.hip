@@ -14,18 +14,14 @@
 //   to nor the order of the combine can change a bit of the result.  Pass 2 re-reads the list and writes the mask and the points
 //   under the winner.  No scratch, vector stores only; thread 0 writes the record.
 #include "hak_internal.h"
-#include "geom_common.h"
+#include "points_common.h"
 
 #define PO_BLOCK 512
 #define PO_WAVES (PO_BLOCK / HAK_WAVE)
 #define PO_SWEEPS3 6
 
-struct PoseCameras {
-    hak_intrinsics K1, K2;
-    float F[9];                                                         // the model of a call that keeps F on the host
-};
+typedef pt_cameras<9> PoseCameras;                                      // model: the F of a call that keeps it on the host
 
-__device__ __forceinline__ double po_dot(const double a[3], const double b[3]) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
 __device__ __forceinline__ void po_cross(const double a[3], const double b[3], double c[3])
 {
     c[0] = a[1] * b[2] - a[2] * b[1];
@@ -72,14 +68,14 @@ __device__ bool po_decompose(const float F[9], const hak_intrinsics& K1, const h
     po_cross(v1, v2, v3);
     double x[3], y[3], u1[3], u2[3], w[3];
     po_matvec(E, v1, x);
-    const double l1 = sqrt(po_dot(x, x));
+    const double l1 = sqrt(pt_dot(x, x));
 #pragma unroll
     for (int i = 0; i < 3; i++) u1[i] = x[i] / l1;
     po_matvec(E, v2, y);
-    const double dd = po_dot(u1, y);
+    const double dd = pt_dot(u1, y);
 #pragma unroll
     for (int i = 0; i < 3; i++) w[i] = y[i] - dd * u1[i];
-    const double l2 = sqrt(po_dot(w, w));
+    const double l2 = sqrt(pt_dot(w, w));
 #pragma unroll
     for (int i = 0; i < 3; i++) u2[i] = w[i] / l2;
     po_cross(u1, u2, u3);
@@ -102,12 +98,9 @@ __device__ __forceinline__ bool po_front(const double R[9], const double t[3], d
     double a[3];
 #pragma unroll
     for (int i = 0; i < 3; i++) a[i] = (R[3 * i] * x + R[3 * i + 1] * y) + R[3 * i + 2];
-    const double aa = po_dot(a, a), ab = po_dot(a, b), at = po_dot(a, t), bt = po_dot(b, t);
-    const double det = aa * bb - ab * ab;
-    const double za = (ab * bt - bb * at) / det;
-    const double zb = (aa * bt - ab * at) / det;
-    *z1 = za;
-    return det > 0.0 && za > 0.0 && za < md && zb > 0.0 && zb < md;
+    const pt_depths d = pt_two_rays(a, pt_dot(a, a), b, bb, t);
+    *z1 = d.z1;
+    return d.det > 0.0 && d.z1 > 0.0 && d.z1 < md && d.z2 > 0.0 && d.z2 < md;
 }
 
 __global__ __launch_bounds__(PO_BLOCK) void k_pose(const hak_match_pair* __restrict__ base, long stride,
@@ -119,7 +112,7 @@ __global__ __launch_bounds__(PO_BLOCK) void k_pose(const hak_match_pair* __restr
     __shared__ int part[PO_WAVES][5];
     const int pair = blockIdx.x, tid = threadIdx.x;
     const hak_match_pair* m = base + (long)pair * stride;
-    const int n = fd_count(counts, pair, n_host, stride);
+    const int n = fd_count(counts, pair, 1, n_host, stride);
     float F[9];
     bool model = true;
     if (d_F) {
@@ -129,7 +122,7 @@ __global__ __launch_bounds__(PO_BLOCK) void k_pose(const hak_match_pair* __restr
         for (int k = 0; k < 9; k++) F[k] = in.F[k];
     } else {
 #pragma unroll
-        for (int k = 0; k < 9; k++) F[k] = cam.F[k];
+        for (int k = 0; k < 9; k++) F[k] = cam.model[k];
     }
 #pragma unroll
     for (int k = 0; k < 9; k++) model = model && __builtin_isfinite(F[k]);
@@ -143,8 +136,7 @@ __global__ __launch_bounds__(PO_BLOCK) void k_pose(const hak_match_pair* __restr
     }
 #pragma unroll
     for (int k = 0; k < 3; k++) nu3[k] = -u3[k];
-    const double fx1 = (double)cam.K1.fx, fy1 = (double)cam.K1.fy, cx1 = (double)cam.K1.cx, cy1 = (double)cam.K1.cy;
-    const double fx2 = (double)cam.K2.fx, fy2 = (double)cam.K2.fy, cx2 = (double)cam.K2.cx, cy2 = (double)cam.K2.cy;
+    const pt_K k1(cam.K1), k2(cam.K2);
     const double md = (double)max_depth;
 
     // pass 1: the inliers of F and, of those, the matches in front under each candidate
@@ -153,9 +145,9 @@ __global__ __launch_bounds__(PO_BLOCK) void k_pose(const hak_match_pair* __restr
         for (int i = tid; i < n; i += PO_BLOCK) {
             const float4 r = fd_load(m, i);
             if (!fd_inlier(F, r, t2)) continue;
-            const double x = ((double)r.x - cx1) / fx1, y = ((double)r.y - cy1) / fy1;
-            const double b[3] = {((double)r.z - cx2) / fx2, ((double)r.w - cy2) / fy2, 1.0};
-            const double bb = po_dot(b, b);
+            const double x = k1.x(r.x), y = k1.y(r.y);
+            const double b[3] = {k2.x(r.z), k2.y(r.w), 1.0};
+            const double bb = pt_dot(b, b);
             double z;
             c[0] += po_front(Ra, u3, x, y, b, bb, md, &z) ? 1 : 0;
             c[1] += po_front(Ra, nu3, x, y, b, bb, md, &z) ? 1 : 0;
@@ -163,19 +155,7 @@ __global__ __launch_bounds__(PO_BLOCK) void k_pose(const hak_match_pair* __restr
             c[3] += po_front(Rb, nu3, x, y, b, bb, md, &z) ? 1 : 0;
             c[4]++;
         }
-#pragma unroll
-    for (int k = 0; k < 5; k++) {
-        c[k] = hg_wsum(c[k]);
-        if ((tid & (HAK_WAVE - 1)) == 0) part[tid / HAK_WAVE][k] = c[k];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < 5; k++) {
-        int s = 0;
-#pragma unroll
-        for (int w = 0; w < PO_WAVES; w++) s += part[w][k];
-        c[k] = s;
-    }
+    pt_block_sum<5, PO_WAVES>(c, part);
     int best = 0, in_front = c[0];
 #pragma unroll
     for (int k = 1; k < 4; k++)
@@ -188,26 +168,20 @@ __global__ __launch_bounds__(PO_BLOCK) void k_pose(const hak_match_pair* __restr
 
     // pass 2: the mask and the points under the winner
     if (masks || xyz) {
-        unsigned char* mk = masks ? masks + (long)pair * stride : nullptr;
-        float* pz = xyz ? xyz + 3 * ((long)pair * stride) : nullptr;
+        const pt_out o(masks, xyz, pair, stride);
         for (int i = tid; i < n; i += PO_BLOCK) {
             bool front = false;
             double x = 0.0, y = 0.0, z = 0.0;
             if (model) {
                 const float4 r = fd_load(m, i);
                 if (fd_inlier(F, r, t2)) {
-                    x = ((double)r.x - cx1) / fx1;
-                    y = ((double)r.y - cy1) / fy1;
-                    const double b[3] = {((double)r.z - cx2) / fx2, ((double)r.w - cy2) / fy2, 1.0};
-                    front = po_front(R, t, x, y, b, po_dot(b, b), md, &z);
+                    x = k1.x(r.x);
+                    y = k1.y(r.y);
+                    const double b[3] = {k2.x(r.z), k2.y(r.w), 1.0};
+                    front = po_front(R, t, x, y, b, pt_dot(b, b), md, &z);
                 }
             }
-            if (mk) mk[i] = front ? 1 : 0;
-            if (pz) {
-                pz[3 * (long)i] = front ? (float)(z * x) : 0.0f;
-                pz[3 * (long)i + 1] = front ? (float)(z * y) : 0.0f;
-                pz[3 * (long)i + 2] = front ? (float)z : 0.0f;
-            }
+            o.store(i, front, (float)(z * x), (float)(z * y), (float)z);
         }
     }
     if (tid == 0) {
@@ -221,15 +195,6 @@ __global__ __launch_bounds__(PO_BLOCK) void k_pose(const hak_match_pair* __restr
     }
 }
 
-// the record of a hak_recover_pose call: a device global, so that the call allocates nothing
-__device__ hak_pose g_pose_record;
-
-hak_pose* hak_pose_record()
-{
-    void* p = nullptr;
-    return hipGetSymbolAddress(&p, HIP_SYMBOL(g_pose_record)) == hipSuccess ? static_cast<hak_pose*>(p) : nullptr;
-}
-
 void hak_launch_pose(hipStream_t st, const hak_match_pair* matches, long stride, const int* counts, int n_host, int npairs,
                      const hak_fundamental* d_F, const float* h_F, const hak_intrinsics& K1, const hak_intrinsics& K2,
                      float threshold, float max_depth, hak_pose* out, unsigned char* masks, float* xyz)
@@ -237,7 +202,7 @@ void hak_launch_pose(hipStream_t st, const hak_match_pair* matches, long stride,
     PoseCameras cam;
     cam.K1 = K1;
     cam.K2 = K2;
-    for (int k = 0; k < 9; k++) cam.F[k] = h_F ? h_F[k] : 0.0f;
+    cam.put(0, h_F, 9);
     k_pose<<<npairs, PO_BLOCK, 0, st>>>(matches, stride, counts, n_host, d_F, cam, threshold * threshold, max_depth, out, masks,
                                         xyz);
 }

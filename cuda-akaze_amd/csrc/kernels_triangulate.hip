@@ -16,17 +16,13 @@
 //   atomics, no memset, no scratch, vector stores only; thread 0 writes the record.
 #include "hak_internal.h"
 #include "pnp_common.h"
+#include "points_common.h"
 
 #define TR_BLOCK 512
 #define TR_WAVES (TR_BLOCK / HAK_WAVE)
 #define TR_VIEW_HOST 3                                                  // launcher-only kind: the view is a kernel argument
 
-struct TriCameras {
-    hak_intrinsics KA, KB;
-    float A[12], B[12];                                                 // the views of a call that keeps them on the host
-};
-
-__device__ __forceinline__ double tr_dot(const double a[3], const double b[3]) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
+typedef pt_cameras<24> TriCameras;                                      // model: the views A, B of a call that keeps them on the host
 
 // step 1 of the rule for one view: M = {R row-major, t}; false = no model.  hak_pose and hak_abs_pose both begin with R[9], t[3];
 // the word that says whether there is a model is `candidate` (word 14) of the one and `hypothesis` (word 13) of the other.
@@ -78,22 +74,20 @@ __global__ __launch_bounds__(TR_BLOCK) void k_triangulate(const hak_match_pair* 
     __shared__ int part[TR_WAVES][4];
     const int pair = blockIdx.x, tid = threadIdx.x;
     const hak_match_pair* m = base + (long)pair * stride;
-    const int n = fd_count(counts ? counts + (long)pair * count_step : nullptr, 0, n_host, stride);
+    const int n = fd_count(counts, pair, count_step, n_host, stride);
     float MA[12], MB[12];
-    const bool modelA = tr_view(viewsA, kindA, stepA, pair, cam.A, MA);
-    const bool modelB = tr_view(viewsB, kindB, stepB, pair, cam.B, MB);
+    const bool modelA = tr_view(viewsA, kindA, stepA, pair, cam.model, MA);
+    const bool modelB = tr_view(viewsB, kindB, stepB, pair, cam.model + 12, MB);
     const bool model = modelA && modelB;                                // (block-uniform)
     double RA[9], RB[9], cA[3], cB[3], w[3];
     tr_centre(MA, RA, cA);
     tr_centre(MB, RB, cB);
 #pragma unroll
     for (int j = 0; j < 3; j++) w[j] = cA[j] - cB[j];
-    const double fxA = (double)cam.KA.fx, fyA = (double)cam.KA.fy, cxA = (double)cam.KA.cx, cyA = (double)cam.KA.cy;
-    const double fxB = (double)cam.KB.fx, fyB = (double)cam.KB.fy, cxB = (double)cam.KB.cx, cyB = (double)cam.KB.cy;
+    const pt_K kA(cam.K1), kB(cam.K2);
     const double md = (double)max_depth;
     const double s2 = (double)min_sin * (double)min_sin;
-    unsigned char* mk = masks ? masks + (long)pair * stride : nullptr;
-    float* pz = xyz ? xyz + 3 * ((long)pair * stride) : nullptr;
+    const pt_out o(masks, xyz, pair, stride);
 
     int c[4] = {0, 0, 0, 0};                                            // kept, rejected[0 .. 2]
     for (int i = tid; i < n; i += TR_BLOCK) {
@@ -102,20 +96,18 @@ __global__ __launch_bounds__(TR_BLOCK) void k_triangulate(const hak_match_pair* 
         if (model) {
             const float4 r = fd_load(m, i);
             double a[3], b[3];
-            tr_ray(RA, ((double)r.x - cxA) / fxA, ((double)r.y - cyA) / fyA, a);
-            tr_ray(RB, ((double)r.z - cxB) / fxB, ((double)r.w - cyB) / fyB, b);
-            const double aa = tr_dot(a, a), bb = tr_dot(b, b), ab = tr_dot(a, b), aw = tr_dot(a, w), bw = tr_dot(b, w);
-            const double det = aa * bb - ab * ab;
-            const double z1 = (ab * bw - bb * aw) / det;
-            const double z2 = (aa * bw - ab * aw) / det;
+            tr_ray(RA, kA.x(r.x), kA.y(r.y), a);
+            tr_ray(RB, kB.x(r.z), kB.y(r.w), b);
+            const double aa = pt_dot(a, a), bb = pt_dot(b, b);
+            const pt_depths d = pt_two_rays(a, aa, b, bb, w);
             int gate = 3;                                               // the first gate failed; 3 = none
-            if (!(det > 0.0 && det >= s2 * (aa * bb))) gate = 0;
-            else if (!(z1 > 0.0 && z1 < md && z2 > 0.0 && z2 < md)) gate = 1;
+            if (!(d.det > 0.0 && d.det >= s2 * (aa * bb))) gate = 0;
+            else if (!(d.z1 > 0.0 && d.z1 < md && d.z2 > 0.0 && d.z2 < md)) gate = 1;
             else {
 #pragma unroll
-                for (int j = 0; j < 3; j++) P[j] = (float)(0.5 * ((cA[j] + z1 * a[j]) + (cB[j] + z2 * b[j])));
-                if (!(pn_inlier(MA, make_float4(P[0], P[1], P[2], r.x), r.y, cam.KA, t2) &&
-                      pn_inlier(MB, make_float4(P[0], P[1], P[2], r.z), r.w, cam.KB, t2)))
+                for (int j = 0; j < 3; j++) P[j] = (float)(0.5 * ((cA[j] + d.z1 * a[j]) + (cB[j] + d.z2 * b[j])));
+                if (!(pn_inlier(MA, make_float4(P[0], P[1], P[2], r.x), r.y, cam.K1, t2) &&
+                      pn_inlier(MB, make_float4(P[0], P[1], P[2], r.z), r.w, cam.K2, t2)))
                     gate = 2;
             }
             keep = gate == 3;
@@ -124,41 +116,15 @@ __global__ __launch_bounds__(TR_BLOCK) void k_triangulate(const hak_match_pair* 
             c[2] += gate == 1 ? 1 : 0;
             c[3] += gate == 2 ? 1 : 0;
         }
-        if (mk) mk[i] = keep ? 1 : 0;
-        if (pz) {
-            pz[3 * (long)i] = keep ? P[0] : 0.0f;
-            pz[3 * (long)i + 1] = keep ? P[1] : 0.0f;
-            pz[3 * (long)i + 2] = keep ? P[2] : 0.0f;
-        }
+        o.store(i, keep, P[0], P[1], P[2]);
     }
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        c[k] = hg_wsum(c[k]);
-        if ((tid & (HAK_WAVE - 1)) == 0) part[tid / HAK_WAVE][k] = c[k];
-    }
-    __syncthreads();
+    pt_block_sum<4, TR_WAVES>(c, part);
     if (tid == 0) {
-        hak_triangulation o;
-        int s[4];
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            s[k] = 0;
-#pragma unroll
-            for (int wv = 0; wv < TR_WAVES; wv++) s[k] += part[wv][k];
-        }
-        o.n = n; o.kept = s[0]; o.rejected[0] = s[1]; o.rejected[1] = s[2]; o.rejected[2] = s[3]; o.model = model ? 1 : 0;
-        o.pad[0] = o.pad[1] = 0;
-        out[pair] = o;
+        hak_triangulation t;
+        t.n = n; t.kept = c[0]; t.rejected[0] = c[1]; t.rejected[1] = c[2]; t.rejected[2] = c[3]; t.model = model ? 1 : 0;
+        t.pad[0] = t.pad[1] = 0;
+        out[pair] = t;
     }
-}
-
-// the record of a hak_triangulate call: a device global, so that the call allocates nothing
-__device__ hak_triangulation g_triangulation_record;
-
-hak_triangulation* hak_triangulation_record()
-{
-    void* p = nullptr;
-    return hipGetSymbolAddress(&p, HIP_SYMBOL(g_triangulation_record)) == hipSuccess ? static_cast<hak_triangulation*>(p) : nullptr;
 }
 
 void hak_launch_triangulate(hipStream_t st, const hak_match_pair* matches, long stride, const int* counts, int count_step, int n_host,
@@ -167,12 +133,10 @@ void hak_launch_triangulate(hipStream_t st, const hak_match_pair* matches, long 
                             float max_depth, float min_sin, hak_triangulation* out, unsigned char* masks, float* xyz)
 {
     TriCameras cam;
-    cam.KA = KA;
-    cam.KB = KB;
-    for (int k = 0; k < 12; k++) {
-        cam.A[k] = h_A ? h_A[k] : 0.0f;
-        cam.B[k] = h_B ? h_B[k] : 0.0f;
-    }
+    cam.K1 = KA;
+    cam.K2 = KB;
+    cam.put(0, h_A, 12);
+    cam.put(12, h_B, 12);
     k_triangulate<<<npairs, TR_BLOCK, 0, st>>>(matches, stride, counts, count_step, n_host, viewsA, h_A ? TR_VIEW_HOST : kindA, stepA,
                                                viewsB, h_B ? TR_VIEW_HOST : kindB, stepB, cam, threshold * threshold, max_depth,
                                                min_sin, out, masks, xyz);

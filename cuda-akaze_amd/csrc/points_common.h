@@ -1,0 +1,83 @@
+// points_common.h -- what the two point kernels share (kernels_pose.hip, kernels_triangulate.hip): the 3-vector dot product, the
+// least-squares two-ray solve of step 5 of hak_recover_pose (also the solve of hak_triangulate, include/hipakaze.h), the intrinsics
+// widened to float64, the kernel argument of two cameras and a model kept on the host, the close of the per-lane integer counters
+// and the store of a match's mask byte and point.  The gates on the solve stay with the kernels: they differ.
+// Every file that includes it is built with -ffp-contract=off, so one source expression gives one rounding in both kernels.
+#pragma once
+#include "geom_common.h"
+
+__device__ __forceinline__ double pt_dot(const double a[3], const double b[3]) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
+
+// the depths z1 along ray a and z2 along ray b at which the two rays, their origins w = (origin of a) - (origin of b) apart, come
+// closest; aa = a.a and bb = b.b are the caller's, which may hold one of them for several solves.  det <= 0: no solve
+struct pt_depths { double det, z1, z2; };
+__device__ __forceinline__ pt_depths pt_two_rays(const double a[3], double aa, const double b[3], double bb, const double w[3])
+{
+    const double ab = pt_dot(a, b), aw = pt_dot(a, w), bw = pt_dot(b, w);
+    pt_depths d;
+    d.det = aa * bb - ab * ab;
+    d.z1 = (ab * bw - bb * aw) / d.det;
+    d.z2 = (aa * bw - ab * aw) / d.det;
+    return d;
+}
+
+// a camera's intrinsics widened to float64; x, y: a pixel coordinate normalised
+struct pt_K {
+    double fx, fy, cx, cy;
+    __device__ __forceinline__ explicit pt_K(const hak_intrinsics& K) : fx((double)K.fx), fy((double)K.fy), cx((double)K.cx), cy((double)K.cy) {}
+    __device__ __forceinline__ double x(float px) const { return ((double)px - cx) / fx; }
+    __device__ __forceinline__ double y(float py) const { return ((double)py - cy) / fy; }
+};
+
+// the kernel argument of a call: the two cameras and W model words that a call may keep on the host
+template <int W>
+struct pt_cameras {
+    hak_intrinsics K1, K2;
+    float model[W];
+    // (host) words at .. at + count - 1 from h, zeros without one
+    void put(int at, const float* h, int count)
+    {
+        for (int k = 0; k < count; k++) model[at + k] = h ? h[k] : 0.0f;
+    }
+};
+
+// closes N per-lane integer counters over a block of WAVES waves: the xor butterfly per wave, one row of part per wave, and the
+// sum over the rows; every thread returns with the block's totals in c (k_pose chooses its winner from them in every thread;
+// k_triangulate uses them in thread 0 only, and summing there alone measured the same).  The sums are integer counts, so no
+// order changes a bit.  (block-uniform: holds a __syncthreads)
+template <int N, int WAVES>
+__device__ __forceinline__ void pt_block_sum(int c[N], int part[WAVES][N])
+{
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int k = 0; k < N; k++) {
+        c[k] = hg_wsum(c[k]);
+        if ((tid & (HAK_WAVE - 1)) == 0) part[tid / HAK_WAVE][k] = c[k];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < N; k++) {
+        int s = 0;
+#pragma unroll
+        for (int w = 0; w < WAVES; w++) s += part[w][k];
+        c[k] = s;
+    }
+}
+
+// where list `pair` of `stride` records writes its mask bytes and its points (3 floats per record); either array may be NULL
+struct pt_out {
+    unsigned char* mk;
+    float* pz;
+    __device__ __forceinline__ pt_out(unsigned char* masks, float* xyz, int pair, long stride)
+        : mk(masks ? masks + (long)pair * stride : nullptr), pz(xyz ? xyz + 3 * ((long)pair * stride) : nullptr) {}
+    // record i: the mask byte, and the point or zeros unless kept
+    __device__ __forceinline__ void store(int i, bool keep, float X, float Y, float Z) const
+    {
+        if (mk) mk[i] = keep ? 1 : 0;
+        if (pz) {
+            pz[3 * (long)i] = keep ? X : 0.0f;
+            pz[3 * (long)i + 1] = keep ? Y : 0.0f;
+            pz[3 * (long)i + 2] = keep ? Z : 0.0f;
+        }
+    }
+};

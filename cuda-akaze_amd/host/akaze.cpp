@@ -6,6 +6,7 @@
 #include <cstdlib>
 #include <mutex>
 #include <set>
+#include <string>
 
 namespace
 {
@@ -17,6 +18,39 @@ namespace
     // host buffers handed out pinned (device-visible), so that freeAkazeData knows how to release them
     std::mutex g_pinned_mu;
     std::set<void*> g_pinned;
+
+    // The device side of a wrapper over one host list: the list's device copy, uploaded here, and the device buffers of the mask
+    // and the points the caller asked for.  `name` is the wrapper's, for the messages; others_ok: its further pointers are there.
+    // An empty list allocates nothing, and every pointer stays NULL.
+    template <class Rec>
+    struct DeviceList {
+        const char* name;
+        int n;
+        Rec* d = nullptr;
+        unsigned char* d_mask = nullptr;
+        float* d_xyz = nullptr;
+
+        DeviceList(const char* name, const Rec* h, int n, bool others_ok, bool mask, bool xyz = false) : name(name), n(n)
+        {
+            if (n < 0 || (n > 0 && !h) || !others_ok) { fprintf(stderr, "hip-akaze: %s: bad argument\n", name); exit(-1); }
+            if (n == 0) return;
+            if (hipMalloc((void**)&d, sizeof(Rec) * (size_t)n) != hipSuccess) fail("alloc");
+            if (mask && hipMalloc((void**)&d_mask, (size_t)n) != hipSuccess) fail("alloc");
+            if (xyz && hipMalloc((void**)&d_xyz, sizeof(float) * 3 * (size_t)n) != hipSuccess) fail("alloc");
+            if (hak_memcpy_h2d(d, h, (long)(sizeof(Rec) * (size_t)n))) fail("upload");
+        }
+        DeviceList(const DeviceList&) = delete;
+        DeviceList& operator=(const DeviceList&) = delete;
+        ~DeviceList()
+        {
+            if (d_xyz) (void)hipFree(d_xyz);
+            if (d_mask) (void)hipFree(d_mask);
+            if (d) (void)hipFree(d);
+        }
+        void mask_to(unsigned char* h) const { if (d_mask && hak_memcpy_d2h(h, d_mask, n)) fail("download"); }
+        void xyz_to(float* h) const { if (d_xyz && hak_memcpy_d2h(h, d_xyz, (long)(sizeof(float) * 3 * (size_t)n))) fail("download"); }
+        void fail(const char* step) const { die((std::string(name) + " " + step).c_str()); }
+    };
 }
 
 namespace akaze
@@ -106,105 +140,57 @@ namespace akaze
     int cuFindHomography(const hak_match_pair* matches, int n, float H[9], unsigned char* inlier_mask, int iterations, float threshold,
                          unsigned seed, bool refine)
     {
-        if (n < 0 || (n > 0 && !matches) || !H) { fprintf(stderr, "hip-akaze: cuFindHomography: bad argument\n"); exit(-1); }
-        hak_match_pair* d_matches = nullptr;
-        unsigned char* d_mask = nullptr;
-        if (n > 0) {
-            if (hipMalloc((void**)&d_matches, sizeof(hak_match_pair) * (size_t)n) != hipSuccess) die("cuFindHomography alloc");
-            if (inlier_mask && hipMalloc((void**)&d_mask, (size_t)n) != hipSuccess) die("cuFindHomography alloc");
-            if (hak_memcpy_h2d(d_matches, matches, (long)(sizeof(hak_match_pair) * (size_t)n))) die("cuFindHomography upload");
-        }
+        DeviceList<hak_match_pair> l("cuFindHomography", matches, n, H != nullptr, inlier_mask != nullptr);
         hak_homography r;
-        if (hak_find_homography(NULL, d_matches, n, iterations, threshold, seed, refine ? 1 : 0, d_mask, &r)) die("cuFindHomography");
-        if (d_mask && hak_memcpy_d2h(inlier_mask, d_mask, n)) die("cuFindHomography download");
+        if (hak_find_homography(NULL, l.d, n, iterations, threshold, seed, refine ? 1 : 0, l.d_mask, &r)) die(l.name);
+        l.mask_to(inlier_mask);
         for (int k = 0; k < 9; k++) H[k] = r.H[k];
-        if (d_mask) (void)hipFree(d_mask);
-        if (d_matches) (void)hipFree(d_matches);
         return r.inliers;
     }
 
     int cuFindFundamental(const hak_match_pair* matches, int n, float F[9], unsigned char* inlier_mask, int iterations, float threshold,
                           unsigned seed)
     {
-        if (n < 0 || (n > 0 && !matches) || !F) { fprintf(stderr, "hip-akaze: cuFindFundamental: bad argument\n"); exit(-1); }
-        hak_match_pair* d_matches = nullptr;
-        unsigned char* d_mask = nullptr;
-        if (n > 0) {
-            if (hipMalloc((void**)&d_matches, sizeof(hak_match_pair) * (size_t)n) != hipSuccess) die("cuFindFundamental alloc");
-            if (inlier_mask && hipMalloc((void**)&d_mask, (size_t)n) != hipSuccess) die("cuFindFundamental alloc");
-            if (hak_memcpy_h2d(d_matches, matches, (long)(sizeof(hak_match_pair) * (size_t)n))) die("cuFindFundamental upload");
-        }
+        DeviceList<hak_match_pair> l("cuFindFundamental", matches, n, F != nullptr, inlier_mask != nullptr);
         hak_fundamental r;
-        if (hak_find_fundamental(NULL, d_matches, n, iterations, threshold, seed, d_mask, &r)) die("cuFindFundamental");
-        if (d_mask && hak_memcpy_d2h(inlier_mask, d_mask, n)) die("cuFindFundamental download");
+        if (hak_find_fundamental(NULL, l.d, n, iterations, threshold, seed, l.d_mask, &r)) die(l.name);
+        l.mask_to(inlier_mask);
         for (int k = 0; k < 9; k++) F[k] = r.F[k];
-        if (d_mask) (void)hipFree(d_mask);
-        if (d_matches) (void)hipFree(d_matches);
         return r.inliers;
     }
 
     int cuRefineFundamental(const hak_match_pair* matches, int n, float F[9], unsigned char* inlier_mask, float threshold, int rounds)
     {
-        if (n < 0 || (n > 0 && !matches) || !F) { fprintf(stderr, "hip-akaze: cuRefineFundamental: bad argument\n"); exit(-1); }
-        hak_match_pair* d_matches = nullptr;
-        unsigned char* d_mask = nullptr;
-        if (n > 0) {
-            if (hipMalloc((void**)&d_matches, sizeof(hak_match_pair) * (size_t)n) != hipSuccess) die("cuRefineFundamental alloc");
-            if (inlier_mask && hipMalloc((void**)&d_mask, (size_t)n) != hipSuccess) die("cuRefineFundamental alloc");
-            if (hak_memcpy_h2d(d_matches, matches, (long)(sizeof(hak_match_pair) * (size_t)n))) die("cuRefineFundamental upload");
-        }
+        DeviceList<hak_match_pair> l("cuRefineFundamental", matches, n, F != nullptr, inlier_mask != nullptr);
         hak_fundamental r{};
         for (int k = 0; k < 9; k++) r.F[k] = F[k];
         r.n = n;
-        if (hak_refine_fundamental(NULL, d_matches, n, threshold, rounds, d_mask, &r)) die("cuRefineFundamental");
-        if (d_mask && hak_memcpy_d2h(inlier_mask, d_mask, n)) die("cuRefineFundamental download");
+        if (hak_refine_fundamental(NULL, l.d, n, threshold, rounds, l.d_mask, &r)) die(l.name);
+        l.mask_to(inlier_mask);
         for (int k = 0; k < 9; k++) F[k] = r.F[k];
-        if (d_mask) (void)hipFree(d_mask);
-        if (d_matches) (void)hipFree(d_matches);
         return r.inliers;
     }
 
     int cuRecoverPose(const hak_match_pair* matches, int n, const float F[9], const hak_intrinsics& K1, const hak_intrinsics& K2,
                       float R[9], float t[3], unsigned char* front_mask, float threshold, float max_depth)
     {
-        if (n < 0 || (n > 0 && !matches) || !F || !R || !t) { fprintf(stderr, "hip-akaze: cuRecoverPose: bad argument\n"); exit(-1); }
-        hak_match_pair* d_matches = nullptr;
-        unsigned char* d_mask = nullptr;
-        if (n > 0) {
-            if (hipMalloc((void**)&d_matches, sizeof(hak_match_pair) * (size_t)n) != hipSuccess) die("cuRecoverPose alloc");
-            if (front_mask && hipMalloc((void**)&d_mask, (size_t)n) != hipSuccess) die("cuRecoverPose alloc");
-            if (hak_memcpy_h2d(d_matches, matches, (long)(sizeof(hak_match_pair) * (size_t)n))) die("cuRecoverPose upload");
-        }
+        DeviceList<hak_match_pair> l("cuRecoverPose", matches, n, F && R && t, front_mask != nullptr);
         hak_pose r;
-        if (hak_recover_pose(NULL, d_matches, n, F, &K1, &K2, threshold, max_depth, d_mask, NULL, &r)) die("cuRecoverPose");
-        if (d_mask && hak_memcpy_d2h(front_mask, d_mask, n)) die("cuRecoverPose download");
+        if (hak_recover_pose(NULL, l.d, n, F, &K1, &K2, threshold, max_depth, l.d_mask, NULL, &r)) die(l.name);
+        l.mask_to(front_mask);
         for (int k = 0; k < 9; k++) R[k] = r.R[k];
         for (int k = 0; k < 3; k++) t[k] = r.t[k];
-        if (d_mask) (void)hipFree(d_mask);
-        if (d_matches) (void)hipFree(d_matches);
         return r.candidate < 0 ? -1 : r.in_front;
     }
 
     int cuTriangulate(const hak_match_pair* matches, int n, const float* RtA, const float* RtB, const hak_intrinsics& KA,
                       const hak_intrinsics& KB, float* xyz, unsigned char* mask, float threshold, float max_depth, float min_sin)
     {
-        if (n < 0 || (n > 0 && !matches)) { fprintf(stderr, "hip-akaze: cuTriangulate: bad argument\n"); exit(-1); }
-        hak_match_pair* d_matches = nullptr;
-        unsigned char* d_mask = nullptr;
-        float* d_xyz = nullptr;
-        if (n > 0) {
-            if (hipMalloc((void**)&d_matches, sizeof(hak_match_pair) * (size_t)n) != hipSuccess) die("cuTriangulate alloc");
-            if (mask && hipMalloc((void**)&d_mask, (size_t)n) != hipSuccess) die("cuTriangulate alloc");
-            if (xyz && hipMalloc((void**)&d_xyz, sizeof(float) * 3 * (size_t)n) != hipSuccess) die("cuTriangulate alloc");
-            if (hak_memcpy_h2d(d_matches, matches, (long)(sizeof(hak_match_pair) * (size_t)n))) die("cuTriangulate upload");
-        }
+        DeviceList<hak_match_pair> l("cuTriangulate", matches, n, true, mask != nullptr, xyz != nullptr);
         hak_triangulation r;
-        if (hak_triangulate(NULL, d_matches, n, RtA, RtB, &KA, &KB, threshold, max_depth, min_sin, d_mask, d_xyz, &r)) die("cuTriangulate");
-        if (d_mask && hak_memcpy_d2h(mask, d_mask, n)) die("cuTriangulate download");
-        if (d_xyz && hak_memcpy_d2h(xyz, d_xyz, (long)(sizeof(float) * 3 * (size_t)n))) die("cuTriangulate download");
-        if (d_xyz) (void)hipFree(d_xyz);
-        if (d_mask) (void)hipFree(d_mask);
-        if (d_matches) (void)hipFree(d_matches);
+        if (hak_triangulate(NULL, l.d, n, RtA, RtB, &KA, &KB, threshold, max_depth, min_sin, l.d_mask, l.d_xyz, &r)) die(l.name);
+        l.mask_to(mask);
+        l.xyz_to(xyz);
         return r.kept;
     }
 
@@ -238,45 +224,27 @@ namespace akaze
     int cuSolvePnP(const hak_corr3d* corr, int n, const hak_intrinsics& K, float R[9], float t[3], unsigned char* inlier_mask,
                    int iterations, float threshold, unsigned seed)
     {
-        if (n < 0 || (n > 0 && !corr) || !R || !t) { fprintf(stderr, "hip-akaze: cuSolvePnP: bad argument\n"); exit(-1); }
-        hak_corr3d* d_corr = nullptr;
-        unsigned char* d_mask = nullptr;
-        if (n > 0) {
-            if (hipMalloc((void**)&d_corr, sizeof(hak_corr3d) * (size_t)n) != hipSuccess) die("cuSolvePnP alloc");
-            if (inlier_mask && hipMalloc((void**)&d_mask, (size_t)n) != hipSuccess) die("cuSolvePnP alloc");
-            if (hak_memcpy_h2d(d_corr, corr, (long)(sizeof(hak_corr3d) * (size_t)n))) die("cuSolvePnP upload");
-        }
+        DeviceList<hak_corr3d> l("cuSolvePnP", corr, n, R && t, inlier_mask != nullptr);
         hak_abs_pose r;
-        if (hak_solve_pnp(NULL, d_corr, n, &K, iterations, threshold, seed, d_mask, &r)) die("cuSolvePnP");
-        if (d_mask && hak_memcpy_d2h(inlier_mask, d_mask, n)) die("cuSolvePnP download");
+        if (hak_solve_pnp(NULL, l.d, n, &K, iterations, threshold, seed, l.d_mask, &r)) die(l.name);
+        l.mask_to(inlier_mask);
         for (int k = 0; k < 9; k++) R[k] = r.R[k];
         for (int k = 0; k < 3; k++) t[k] = r.t[k];
-        if (d_mask) (void)hipFree(d_mask);
-        if (d_corr) (void)hipFree(d_corr);
         return r.hypothesis < 0 ? -1 : r.inliers;
     }
 
     int cuRefinePnP(const hak_corr3d* corr, int n, const hak_intrinsics& K, float R[9], float t[3], unsigned char* inlier_mask,
                     float threshold, int rounds)
     {
-        if (n < 0 || (n > 0 && !corr) || !R || !t) { fprintf(stderr, "hip-akaze: cuRefinePnP: bad argument\n"); exit(-1); }
-        hak_corr3d* d_corr = nullptr;
-        unsigned char* d_mask = nullptr;
-        if (n > 0) {
-            if (hipMalloc((void**)&d_corr, sizeof(hak_corr3d) * (size_t)n) != hipSuccess) die("cuRefinePnP alloc");
-            if (inlier_mask && hipMalloc((void**)&d_mask, (size_t)n) != hipSuccess) die("cuRefinePnP alloc");
-            if (hak_memcpy_h2d(d_corr, corr, (long)(sizeof(hak_corr3d) * (size_t)n))) die("cuRefinePnP upload");
-        }
+        DeviceList<hak_corr3d> l("cuRefinePnP", corr, n, R && t, inlier_mask != nullptr);
         hak_abs_pose r{};
         for (int k = 0; k < 9; k++) r.R[k] = R[k];
         for (int k = 0; k < 3; k++) r.t[k] = t[k];
         r.n = n;
-        if (hak_refine_pnp(NULL, d_corr, n, &K, threshold, rounds, d_mask, &r)) die("cuRefinePnP");
-        if (d_mask && hak_memcpy_d2h(inlier_mask, d_mask, n)) die("cuRefinePnP download");
+        if (hak_refine_pnp(NULL, l.d, n, &K, threshold, rounds, l.d_mask, &r)) die(l.name);
+        l.mask_to(inlier_mask);
         for (int k = 0; k < 9; k++) R[k] = r.R[k];
         for (int k = 0; k < 3; k++) t[k] = r.t[k];
-        if (d_mask) (void)hipFree(d_mask);
-        if (d_corr) (void)hipFree(d_corr);
         return r.inliers;
     }
 

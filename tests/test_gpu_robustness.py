@@ -634,6 +634,82 @@ def test_four_host_threads_four_contexts(ah, torch, synth):
         j["det"].close()
 
 
+def test_four_host_threads_share_the_one_record(ah, torch, synth):
+    """the synchronous one-list calls that own no record (hak_recover_pose, hak_triangulate, and both refits without a context) keep
+    their record in one device global and take it in turn: four host threads, one per kind of call, each a dozen calls over a list
+    of 70 records (more than a wave, less than a block: the counters of the two point kernels close over more than one LDS row),
+    and every record, mask and point array must equal, byte for byte, what the same call delivered alone"""
+    import threading
+    n = 70
+    K, (R01, t01), _, A, _, _, _, X0, _, _ = synth.three_view_scene(41, n, noise_px=0.3, outlier_share=0.1)
+    A = np.ascontiguousarray(A, ah.MATCH_PAIR_DTYPE)
+    Ki = np.linalg.inv(K)
+    tx = np.array([[0.0, -t01[2], t01[1]], [t01[2], 0.0, -t01[0]], [-t01[1], t01[0], 0.0]])
+    F = Ki.T @ tx @ R01 @ Ki
+    f = np.ascontiguousarray((F / np.linalg.norm(F)).astype(np.float32).reshape(9))
+    view = np.ascontiguousarray(np.concatenate([R01.reshape(9), t01]).astype(np.float32))
+    corr = np.zeros(n, ah.CORR3D_DTYPE)
+    corr["X"], corr["Y"], corr["Z"], corr["u"], corr["v"] = X0[:, 0], X0[:, 1], X0[:, 2], A["x2"], A["y2"]
+    f_in = np.zeros((), ah.FUNDAMENTAL_DTYPE)
+    f_in["F"], f_in["n"] = f, n
+    p_in = np.zeros((), ah.ABS_POSE_DTYPE)
+    p_in["R"], p_in["t"], p_in["n"] = view[:9], view[9:] + np.float32(0.002), n       # at most 1.1 px off at these depths
+    k = ah.intrinsics(K)
+    d_A = torch.from_numpy(A.view(np.uint8).reshape(-1)).cuda()
+    d_corr = torch.from_numpy(corr.view(np.uint8).reshape(-1)).cuda()
+    fp = C.POINTER(C.c_float)
+    lib = ah.lib
+
+    def pose(rec, mask, xyz):
+        return lib.hak_recover_pose(None, d_A.data_ptr(), n, f.ctypes.data_as(fp), k.ctypes.data, k.ctypes.data, 1.0, float("inf"),
+                                    mask.data_ptr(), xyz.data_ptr(), rec.ctypes.data)
+
+    def triangulation(rec, mask, xyz):
+        return lib.hak_triangulate(None, d_A.data_ptr(), n, None, view.ctypes.data_as(fp), k.ctypes.data, k.ctypes.data, 2.0,
+                                   float("inf"), 0.0, mask.data_ptr(), xyz.data_ptr(), rec.ctypes.data)
+
+    def fund_refit(rec, mask, xyz):
+        return lib.hak_refine_fundamental(None, d_A.data_ptr(), n, 1.0, 3, mask.data_ptr(), rec.ctypes.data)
+
+    def pnp_refit(rec, mask, xyz):
+        return lib.hak_refine_pnp(None, d_corr.data_ptr(), n, k.ctypes.data, 2.0, 3, mask.data_ptr(), rec.ctypes.data)
+
+    kinds = [(pose, np.zeros((), ah.POSE_DTYPE), "in_front"), (triangulation, np.zeros((), ah.TRIANGULATION_DTYPE), "kept"),
+             (fund_refit, f_in, "inliers"), (pnp_refit, p_in, "inliers")]
+
+    def one_call(kind):
+        call, rec_in, _ = kinds[kind]
+        rec = rec_in.copy()
+        mask = torch.full((n,), 0xEE, dtype=torch.uint8, device="cuda")
+        xyz = torch.full((12 * n,), 0xEE, dtype=torch.uint8, device="cuda")
+        ah.check(call(rec, mask, xyz))
+        return rec.tobytes(), mask.cpu().numpy().tobytes(), xyz.cpu().numpy().tobytes()
+
+    alone = [one_call(kind) for kind in range(4)]
+    for kind, (_, rec_in, field) in enumerate(kinds):
+        got = np.frombuffer(alone[kind][0], rec_in.dtype)[0]
+        assert got["n"] == n and got[field] > n // 2, (kind, got)       # 63 of the 70 are correct matches, 0.3 px of noise
+    errors, results = [], [[] for _ in kinds]
+
+    def worker(kind):
+        try:
+            for _ in range(12):
+                results[kind].append(one_call(kind))
+        except Exception as e:                            # noqa: BLE001 -- reported below, in the test's thread
+            errors.append((kind, repr(e)))
+
+    threads = [threading.Thread(target=worker, args=(kind,)) for kind in range(4)]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join()
+    assert not errors, errors
+    for kind, rounds in enumerate(results):
+        assert len(rounds) == 12
+        for r in rounds:
+            assert r == alone[kind], kind
+
+
 def test_calls_are_ordered_behind_the_callers_null_stream_work(ah, okz, torch, synth):
     """the reference runs on the default stream, so what its caller enqueued there before a call (an asynchronous copy into the image, a
     hipMemset of an output array) is done when the call starts (akaze.cpp:101-150); a context's streams are non-blocking, and every
