@@ -11,14 +11,9 @@
 template <typename V> struct FedV;
 template <> struct FedV<float> { using V4 = float4; };
 template <> struct FedV<int> { using V4 = int4; };
+// (vadd / vsub / vmul / vneg, wrapping for int: pixel_rules.h)
 __device__ __forceinline__ float4 mk4(float a, float b, float c, float d) { return make_float4(a, b, c, d); }
 __device__ __forceinline__ int4 mk4(int a, int b, int c, int d) { return make_int4(a, b, c, d); }
-__device__ __forceinline__ float vadd(float a, float b) { return a + b; }
-__device__ __forceinline__ float vsub(float a, float b) { return a - b; }
-__device__ __forceinline__ float vmul(float a, float b) { return a * b; }
-__device__ __forceinline__ int vadd(int a, int b) { return (int)((unsigned)a + (unsigned)b); }
-__device__ __forceinline__ int vsub(int a, int b) { return (int)((unsigned)a - (unsigned)b); }
-__device__ __forceinline__ int vmul(int a, int b) { return (int)((unsigned)a * (unsigned)b); }
 // L' from the flux sum:  float: fma(0.5*tau, sum, L) (akazed.cu:1263);  int: ((stepfac * (sum >> 16)) >> 16) + L (akazed.cu:3468-3469)
 __device__ __forceinline__ float vstep(float f, float sum, float L) { return fmaf(f, sum, L); }
 __device__ __forceinline__ int vstep(int f, int sum, int L) { return vadd(vmul(f, sum >> 16) >> 16, L); }
@@ -136,9 +131,6 @@ __device__ __forceinline__ int4 hak_load_stream(const int4* p)
 }
 
 constexpr int pmod(int a, int m) { return ((a % m) + m) % m; }
-
-__device__ __forceinline__ float vneg(float a) { return -a; }
-__device__ __forceinline__ int vneg(int a) { return (int)(0u - (unsigned)a); }
 
 // ---- the lane vector of the FED kernels: the W consecutive pixels of one row that a lane owns.  W = 4 (a wave's strip is 256 px
 // wide, 16 bytes per lane and row) or W = 2 (128 px, 8 bytes): every ring of the streaming kernels costs W registers per slot, so
@@ -273,35 +265,7 @@ constexpr int fed_gsum_slots(int ns) { return ns + 1 <= 6 ? 6 : 9; }
 constexpr int fed_unroll(int ns) { return ns + 1 <= 6 ? 6 : 18; }
 
 
-// ---- sigma=1 low-pass taps and the conductivity, per element type (kernels_smoothflow.hip, kernels_fedsf.hip).
-// int: every pass of the separable Gaussian ends in >> 16 (akazed.cu:2922-2985), the gradient energy is formed in wrapping
-// int32 and the conductivity is kept as (int)(g * 65536 + 0.5f) (akazed.cu:3406-3445).
-template <typename V> struct SfTaps { V k0, k1, k2; };
-__device__ __forceinline__ float sf_conv(float c, float a1, float b1, float a2, float b2, const SfTaps<float>& t)
-{
-    float ws = c * t.k0;
-    ws += t.k1 * (a1 + b1);
-    ws += t.k2 * (a2 + b2);
-    return ws;
-}
-__device__ __forceinline__ int sf_conv(int c, int a1, int b1, int a2, int b2, const SfTaps<int>& t)
-{
-    const unsigned ws = (unsigned)c * (unsigned)t.k0 + (unsigned)t.k1 * (unsigned)(a1 + b1) + (unsigned)t.k2 * (unsigned)(a2 + b2);
-    return (int)ws >> 16;
-}
-__device__ __forceinline__ float sf_dif2(float dx, float dy, float ikc) { return ikc * (dx * dx + dy * dy); }
-__device__ __forceinline__ float sf_dif2(int dx, int dy, float ikc)
-{
-    return (float)(int)((unsigned)dx * (unsigned)dx + (unsigned)dy * (unsigned)dy) * ikc;
-}
-__device__ __forceinline__ void sf_store_g(float* o, float g) { *o = g; }
-__device__ __forceinline__ void sf_store_g(int* o, float g) { *o = (int)(g * 65536 + 0.5f); }
-
-__device__ __forceinline__ float sf_g_value(float g) { return g; }
-__device__ __forceinline__ int sf_g_value_int(float g) { return (int)(g * 65536 + 0.5f); }
-template <typename V> __device__ __forceinline__ V sf_g_as(float g);
-template <> __device__ __forceinline__ float sf_g_as<float>(float g) { return g; }
-template <> __device__ __forceinline__ int sf_g_as<int>(float g) { return (int)(g * 65536 + 0.5f); }
+// (the sigma=1 low-pass hak_conv5 / SfTaps, the gradient energy hak_dif2 and the conductivity as the element type hak_g_as: pixel_rules.h)
 
 // ---- 1 / d for the PM_G2 conductivity g = 1 / (1 + dif2).  hipcc's correctly rounded float division costs ~11 instructions
 // (v_div_scale x2, v_rcp, four fmas, v_div_fmas, v_div_fixup).  For 1 <= d < 2^64 the three-instruction sequence below --

@@ -203,8 +203,8 @@ static int build_plan(hak_ctx* c, int w, int h)
     }
     for (int r2 = 0; r2 < 36; r2++) c->htab.orient_w[r2] = hak_expf(-r2 * 0.08f);  // akazed.cu:1697
     hak_deriv_factors(&c->htab.fac1, &c->htab.fac2);
-    c->htab.ifac1 = (int)(c->htab.fac1 * 65536 + 0.5f);                           // akazed.cu:4183-4184
-    c->htab.ifac2 = (int)(c->htab.fac2 * 65536 + 0.5f);
+    c->htab.ifac1 = hak_fix16(c->htab.fac1);                                      // akazed.cu:4183-4184
+    c->htab.ifac2 = hak_fix16(c->htab.fac2);
     hak_compare_indices(c->htab.comp1, c->htab.comp2);
     for (int b = 0; b < 61; b++)
         for (int i = 0; i < 8; i++) {
@@ -218,8 +218,8 @@ static int build_plan(hak_ctx* c, int w, int h)
     if (ksz > 11) return fail("Kernels larger than 11 not implemented");
     hak_gauss_taps(cfg.soffset * cfg.soffset, c->base_R, c->taps_base);
     for (int i = 0; i < 8; i++) {
-        c->itaps1[i] = i <= 2 ? (int)(c->taps1[i] * 65536 + 0.5f) : 0;
-        c->itaps_base[i] = i <= c->base_R ? (int)(c->taps_base[i] * 65536 + 0.5f) : 0;
+        c->itaps1[i] = i <= 2 ? hak_fix16(c->taps1[i]) : 0;
+        c->itaps_base[i] = i <= c->base_R ? hak_fix16(c->taps_base[i]) : 0;
     }
     return 0;
 }

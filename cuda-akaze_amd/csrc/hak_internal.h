@@ -43,7 +43,6 @@ struct HakImgState {
     int ncand;                                  // entries in the image's extrema candidate list
     int total_pts;                              // NMS survivors before clamping to max_pts
     int num_pts;                                // min(total, max_pts)
-    int hist_done;                              // blocks of the histogram pass that have added their bins (the last one finishes the contrast factor)
 };
 
 // Read-only tables shared by all images of a context.
@@ -85,16 +84,6 @@ __host__ __device__ inline bool hak_on_lattice(int x, int y, int w, int h)
 }
 __host__ __device__ inline int hak_hist_extra0(int w, int h) { return ((w + 31) / 32 * 32 - w) * h + ((h + 15) / 16 * 16 - h) * w; }
 
-// reflect-101 as the reference: left/top abs(i), right/bottom borderAdd (akazed.cu:162-170)
-__device__ __forceinline__ int hak_refl(int i, int m)
-{
-    i = i < 0 ? -i : i;
-    i = i < m ? i : m + m - 2 - i;
-    // tiles hanging over the image can index past one reflection; those values are never used
-    i = i < 0 ? 0 : i;
-    return i < m ? i : m - 1;
-}
-
 // Workgroup barrier that orders LDS traffic only.  __syncthreads() lowers to
 // `s_waitcnt vmcnt(0) lgkmcnt(0); s_barrier`, i.e. it also drains every outstanding global load and
 // store of the wave -- which serialises a register prefetch and exposes the store latency at each
@@ -133,19 +122,7 @@ __device__ __forceinline__ void hak_lds_barrier()
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
 
-// ---- dilated Scharr / determinant / key helpers of the Hessian kernels (kernels_hessian.hip, kernels_hessian_stream.hip,
-// kernels_scalespace.hip) and of the keypoint refinement.  Shared by both pipelines: V = float (akaze) and V = int
-// (fastakaze 16.16 fixed point, akazed.cu:3339-3403: every weighted sum is followed by >> 16; the determinant is not shifted).
-__device__ __forceinline__ float hs_d(float f1, float f2, float a, float b) { return f1 * a + f2 * b; }
-__device__ __forceinline__ int hs_d(int f1, int f2, int a, int b)
-{
-    return (int)((unsigned)f1 * (unsigned)a + (unsigned)f2 * (unsigned)b) >> 16;
-}
-__device__ __forceinline__ float hs_det(float dxx, float dyy, float dxy) { return dxx * dyy - dxy * dxy; }
-__device__ __forceinline__ int hs_det(int dxx, int dyy, int dxy)
-{
-    return (int)((unsigned)dxx * (unsigned)dyy - (unsigned)dxy * (unsigned)dxy);
-}
+// ---- key helpers of the Hessian kernels (the dilated Scharr and the determinant: pixel_rules.h)
 __device__ __forceinline__ unsigned hs_key_bits(float v) { return __float_as_uint(v); }     // positive floats order like their bits
 __device__ __forceinline__ unsigned hs_key_bits(int v) { return (unsigned)v; }              // positive ints
 __device__ __forceinline__ unsigned hs_key_bits(unsigned v) { return v; }                   // a response word as it is (k_seed_maps)
@@ -221,25 +198,6 @@ __device__ __forceinline__ void hak_ext_append_wave(bool hit, V v, int x, int y,
     }
 }
 
-// Hessian determinant of one level at (x, y), re-evaluated from the interleaved derivative plane with the expressions and
-// the reflect-101 index rule of the Hessian kernels (akazed.cu:1318-1330): bit-identical to the value those kernels
-// compared in their extrema test.  The determinant plane itself is never written (hak_internal.h HakLayout).
-template <typename V>
-__device__ __forceinline__ V hak_det_at(const V* __restrict__ dxy, int x, int y, int S, int w, int h, int p, V f1, V f2)
-{
-    const long x0 = hak_refl(x - S, w), x1 = x, x2 = hak_refl(x + S, w);
-    const long o0 = (long)hak_refl(y - S, h) * p, o1 = (long)y * p, o2 = (long)hak_refl(y + S, h) * p;
-    const V xul = dxy[2 * (o0 + x0)], xuc = dxy[2 * (o0 + x1)], xur = dxy[2 * (o0 + x2)];
-    const V xcl = dxy[2 * (o1 + x0)], xcr = dxy[2 * (o1 + x2)];
-    const V xll = dxy[2 * (o2 + x0)], xlc = dxy[2 * (o2 + x1)], xlr = dxy[2 * (o2 + x2)];
-    const V yul = dxy[2 * (o0 + x0) + 1], yuc = dxy[2 * (o0 + x1) + 1], yur = dxy[2 * (o0 + x2) + 1];
-    const V yll = dxy[2 * (o2 + x0) + 1], ylc = dxy[2 * (o2 + x1) + 1], ylr = dxy[2 * (o2 + x2) + 1];
-    const V dxx = hs_d(f1, f2, xur + xlr - xul - xll, xcr - xcl);
-    const V dxy_ = hs_d(f1, f2, xlr + xll - xur - xul, xlc - xuc);
-    const V dyy = hs_d(f1, f2, ylr + yll - yur - yul, ylc - yuc);
-    return hs_det(dxx, dyy, dxy_);
-}
-
 // ------------------------------------------------- deterministic float32 math
 // Same operation sequence as the parity oracle's (oracle/okz_math.h): one IEEE
 // binary32 op per step, explicit fmaf only.  The reference's libdevice /
@@ -312,6 +270,9 @@ __host__ __device__ __forceinline__ float hak_expf(float x)
     float e = fmaf(p, r * r, r) + 1.0f;
     return ldexpf(e, (int)k);
 }
+
+// the per-pixel rules of both pipelines (element arithmetic, reflect-101, Gaussian, Scharr, histogram, conductivity, determinant)
+#include "pixel_rules.h"
 
 // ---------------------------------------------------------------- launchers
 // (defined in the kernel files; all asynchronous on `st`; nimg = batch images,
@@ -402,16 +363,27 @@ static inline HakExtremaArgs<V> hak_extrema_args(const HakBatch* b, const HakLay
     return ex;
 }
 
-// scale space (kernels_scalespace.hip)
+// scale space (kernels_scalespace.hip): one template per kernel, launchers overloaded on the element type.  taps: float, or
+// 16.16 as hak_fix16(tap) for int planes; the int low-pass also reads the uint8 image
 void hak_launch_lowpass(hipStream_t st, const float* src, long src_stride, int src_pitch, float* dst, long dst_stride,
                         int w, int h, int p, int nimg, const float* taps, int R);
+void hak_launch_lowpass(hipStream_t st, const unsigned char* src, long src_stride, int src_pitch, int* dst, long dst_stride,
+                        int w, int h, int p, int nimg, const int* taps, int R);
+void hak_launch_lowpass(hipStream_t st, const int* src, long src_stride, int src_pitch, int* dst, long dst_stride,
+                        int w, int h, int p, int nimg, const int* taps, int R);
 void hak_launch_down_smooth(hipStream_t st, const float* src, float* dst, float* smooth, long stride,
                             HakOct so, HakOct dd, int nimg, const float* taps);
+void hak_launch_down_smooth(hipStream_t st, const int* src, int* dst, int* smooth, long stride,
+                            HakOct so, HakOct dd, int nimg, const int* taps);
 void hak_launch_contrast(hipStream_t st, const float* smooth, long stride, int w, int h, int p, int nimg,
                          HakImgState* state, float per, int noct);
-void hak_launch_reset_state(hipStream_t st, HakImgState* state, int nimg);
+void hak_launch_contrast(hipStream_t st, const int* smooth, long stride, int w, int h, int p, int nimg,
+                         HakImgState* state, float per, int noct);
+void hak_launch_reset_state(hipStream_t st, HakImgState* state, int nimg);      // every field either pipeline uses
 void hak_launch_flow(hipStream_t st, const float* src, float* dst, long stride, int w, int h, int p, int nimg,
                      int diffusivity, const HakImgState* state, int octave, float fixed_ikc = 0.f);
+void hak_launch_flow(hipStream_t st, const int* src, int* dst, long stride, int w, int h, int p, int nimg,
+                     int diffusivity, const HakImgState* state, int octave);
 // derivate + determinant of one level, with the level's extrema search fused in when b != nullptr
 // (kernels_hessian.hip); returns false when the caller still has to run hak_launch_extrema_level
 // The register-streaming kernels (k_hessian_stream, k_fed_sf) need a few thousand waves of >= 32 rows to fill the chip;
@@ -458,7 +430,7 @@ bool hak_launch_hessian_stream(hipStream_t st, const float* src, float* dxy, flo
 bool hak_launch_hessian_stream(hipStream_t st, const int* src, int* dxy, int* det, bool store_det, long stride,
                                int w, int h, int p, int nimg, int step, int fac1, int fac2,
                                const HakBatch* b, const HakLayout* L, const HakTables* htab, int octave, int sub, int idthreshold);
-// (dilation > 4: derivate + hessian, FAST: hakf_launch_hessian, fill `det`; the caller adds hak_launch_extrema_level)
+// (dilation > 4: hak_launch_derivate + hak_launch_hessian fill `det`; the caller adds hak_launch_extrema_level)
 bool hak_launch_hessian_level(hipStream_t st, const float* src, float* dxy, float* det, bool store_det, long stride,
                               int w, int h, int p, int nimg, int step,
                               const HakBatch* b, const HakLayout* L, const HakTables* htab, int octave, int sub, float dthreshold,
@@ -475,7 +447,7 @@ bool hak_launch_base_stream(hipStream_t st, const unsigned char* img, long img_s
 bool hak_launch_base_level(hipStream_t st, const float* img, long img_stride, int sp, float* lt, float* grad_scratch, long stride,
                            int w, int h, int p, int nimg, const float* taps1, const float* taps_base, int R,
                            HakImgState* state, float per, int noct, const HakKnobs& knobs);
-// FAST (kernels_fast.hip): img is uint8; false: R not covered (caller: hakf_launch_conv_u8 x2 + hak_launch_contrast)
+// FAST (kf_base<R>): img is uint8; false: R not covered (caller: hak_launch_lowpass x2 + hak_launch_contrast)
 bool hak_launch_base_level(hipStream_t st, const unsigned char* img, long img_stride, int sp, int* lt, int* grad_scratch, long stride,
                            int w, int h, int p, int nimg, const int* taps1, const int* taps_base, int R, HakImgState* state,
                            float per, int noct, const HakKnobs& knobs);
@@ -521,7 +493,7 @@ bool hak_launch_fed_sf(hipStream_t st, const float* src, float* smooth, float* f
 bool hak_launch_fed_sf(hipStream_t st, const int* src, int* smooth, int* flow, int* dst, long stride,
                        int w, int h, int p, int nimg, const int* taps, int diffusivity, const float* tau, int ns,
                        const HakImgState* state, int octave, bool write_g);
-// fused FED groups (kernels_fed.hip); w % 4 != 0: one step (tau[0]) per launch, k_fed_generic / kf_nld_step
+// fused FED groups (kernels_fed.hip); w % 4 != 0: one step (tau[0]) per launch, k_fed_generic (float) / kf_nld_step (int)
 int hak_fed_groups(int n, int max_fuse, int w, bool wide_only);
 bool hak_fed_wide_only(int octave, int w);
 int hak_fed_group_size(int n, int G, int g);
@@ -529,11 +501,19 @@ void hak_launch_fed_group(hipStream_t st, const float* src, const float* flow, f
                           int w, int h, int p, int nimg, const float* tau, int ns);
 void hak_launch_fed_group(hipStream_t st, const int* src, const int* flow, int* dst, long stride,
                           int w, int h, int p, int nimg, const float* tau, int ns);
-void hak_launch_derivate(hipStream_t st, const float* src, float* dxy, long stride,
-                         int w, int h, int p, int nimg, int step);
-void hak_launch_hessian(hipStream_t st, const float* dxy, float* det, long stride,
-                        int w, int h, int p, int nimg, int step);
+// the unfused pair (dilations > 4, debug / test planes): src -> interleaved {Lx, Ly}, and {Lx, Ly} -> determinant
+void hak_launch_derivate(hipStream_t st, const float* src, float* dxy, long stride, int w, int h, int p, int nimg, int step);
+void hak_launch_derivate(hipStream_t st, const int* src, int* dxy, long stride, int w, int h, int p, int nimg, int step);
+void hak_launch_hessian(hipStream_t st, const float* dxy, float* det, long stride, int w, int h, int p, int nimg, int step);
+void hak_launch_hessian(hipStream_t st, const int* dxy, int* det, long stride, int w, int h, int p, int nimg, int step);
 void hak_deriv_factors(float* fac1, float* fac2);            // akazed.cu:2537-2539
+template <typename V> static inline void hak_deriv_factors_as(V& f1, V& f2)     // ... as the element type (int: 16.16, akazed.cu:4183-4184)
+{
+    float a, b;
+    hak_deriv_factors(&a, &b);
+    f1 = hak_fac_as(a, V());
+    f2 = hak_fac_as(b, V());
+}
 // interleaved {a, b} plane (pitch 2p) -> two dense planes (pitch p); bytes are copied, so it serves both element types
 void hak_launch_deinterleave(hipStream_t st, const float* ab, float* a, float* b, int w, int h, int p);
 
@@ -562,21 +542,7 @@ void hak_launch_select(hipStream_t st, const HakBatch& b, const HakLayout& L, in
 void hak_launch_grid_select(hipStream_t st, const HakBatch& b, const HakLayout& L, int max_pts, int cap0, int cap1, int fast);
 void hak_launch_seed_maps(hipStream_t st, const HakBatch& b, const HakLayout& L, const unsigned* d_resp_bits, const int* d_layer);
 
-// integer FAST path (kernels_fast.hip); planes are int32 in the same arena layout.  Overloads of the launchers above ...
-void hak_launch_down_smooth(hipStream_t st, const int* src, int* dst, int* smooth, long stride, HakOct so, HakOct dd, int nimg,
-                            const int* taps);
-void hak_launch_contrast(hipStream_t st, const int* smooth, long stride, int w, int h, int p, int nimg, HakImgState* state,
-                         float per, int noct);
-void hak_launch_flow(hipStream_t st, const int* src, int* dst, long stride, int w, int h, int p, int nimg, int type,
-                     const HakImgState* state, int octave);
-// ... and what has no float counterpart, or one with the same parameter types (reset, describe)
-void hakf_launch_reset(hipStream_t st, HakImgState* state, int nimg);
-void hakf_launch_conv_u8(hipStream_t st, const unsigned char* src, long src_stride, int sp, int* dst, long dst_stride,
-                         int w, int h, int p, int nimg, const int* taps, int R);
-void hakf_launch_conv_int(hipStream_t st, const int* src, int* dst, long stride, int w, int h, int p, int nimg, const int* taps, int R);
-void hakf_launch_nld_step(hipStream_t st, const int* src, const int* flow, int* dst, long stride, int w, int h, int p, int nimg, float tau);
-void hakf_launch_hessian(hipStream_t st, const int* src, int* dxy, int* det, long stride, int w, int h, int p, int nimg, int step);   // src -> dxy and det
-void hakf_launch_det(hipStream_t st, const int* dxy, int* det, long stride, int w, int h, int p, int nimg, int step);
+// integer FAST path: what has a float counterpart with the same parameter types
 void hakf_launch_describe(hipStream_t st, const HakBatch& b, const HakLayout& L, const HakTables* tab, hak_point* points, int max_pts,
                           int patsize, int upright, int desc, int planned);
 

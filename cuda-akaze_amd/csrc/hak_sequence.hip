@@ -134,9 +134,9 @@ static void build_level(LevelArgs& a, int o, int s, hipStream_t st, V* smooth_al
                                                  c->state, cfg.per, L.noct, kn);
         if constexpr (is_fast<V>) {                                           // akaze.cpp:589-623 when the fused prologue does not cover base_R
             if (!based) {
-                hakf_launch_conv_u8(st, img, a.image_stride, a.pitch, smooth, S, oc.w, oc.h, oc.p, nimg, taps1, 2);
+                hak_launch_lowpass(st, img, a.image_stride, a.pitch, smooth, S, oc.w, oc.h, oc.p, nimg, taps1, 2);
                 hak_launch_contrast(st, smooth, S, oc.w, oc.h, oc.p, nimg, c->state, cfg.per, L.noct);
-                hakf_launch_conv_u8(st, img, a.image_stride, a.pitch, Lt, S, oc.w, oc.h, oc.p, nimg, taps_base, c->base_R);
+                hak_launch_lowpass(st, img, a.image_stride, a.pitch, Lt, S, oc.w, oc.h, oc.p, nimg, taps_base, c->base_R);
             }
         } else (void)based;
         return;
@@ -428,7 +428,7 @@ int enqueue_fast_detect(hak_ctx* c, const unsigned char* d_images, long image_st
     LevelArgs a = level_args(c, d_images, image_stride, pitch, nimg);
     c->last_fast = true;
     c->sync_stream = c->stream;
-    hakf_launch_reset(st, c->state, nimg);              // (the key map is all zero here: hak_create / k_clear_cand_maps / maps_guard)
+    hak_launch_reset_state(st, c->state, nimg);              // (the key map is all zero here: hak_create / k_clear_cand_maps / maps_guard)
     for (int o = 0; o < L.noct; o++)
         for (int s = 0; s < L.ms; s++) {
             build_level<int>(a, o, s, st);

@@ -6,6 +6,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <type_traits>
 
 extern "C" int hak_debug_plane(hak_ctx* c, int img, int kind, int o, int s, float* h_dst)
 {
@@ -26,7 +27,7 @@ extern "C" int hak_debug_plane(hak_ctx* c, int img, int kind, int o, int s, floa
     const float* src = tmp;
     if (kind == HAK_PLANE_DET) {
         const int step = c->plan[(size_t)o * L.ms + s].sigma_size;
-        if (c->last_fast) hakf_launch_det(nullptr, reinterpret_cast<const int*>(arena + L.dxy(o, s)), reinterpret_cast<int*>(tmp), 0, oc.w, oc.h, oc.p, 1, step);
+        if (c->last_fast) hak_launch_hessian(nullptr, reinterpret_cast<const int*>(arena + L.dxy(o, s)), reinterpret_cast<int*>(tmp), 0, oc.w, oc.h, oc.p, 1, step);
         else hak_launch_hessian(nullptr, arena + L.dxy(o, s), tmp, 0, oc.w, oc.h, oc.p, 1, step);
     } else {
         hak_launch_deinterleave(nullptr, arena + L.dxy(o, s), tmp, tmp + oc.plane, oc.w, oc.h, oc.p);
@@ -50,50 +51,158 @@ extern "C" int hak_debug_kcontrast(hak_ctx* c, int img, float* kc)
 }
 
 // ------------------------------------------------ single-stage test operators
-extern "C" int hak_op_lowpass(const float* s, float* d, int w, int h, int p, float var, int radius)
+// One template per operator serves the float operator and its integer FAST twin (tests/test_gpu_stages.py, tests/test_gpu_fast_stages.py):
+// each drives the launcher overload the launch sequence (build_level<V> / hessian_level<V>, hak_sequence.hip) calls.  `who` is the
+// text a failed device call is reported with: the operator's name, or for the float operators the call their HIP_TRY has always named.
+#define HAK_FAST_KC_MAX 46340                                       // kcontrast * kcontrast stays inside int32 (akazed.cu:4215)
+#define HAK_SYNC_TEXT "hipDeviceSynchronize()"
+template <typename V> constexpr bool op_fast = std::is_same<V, int>::value;
+// taps as V: the float taps, or 16.16 (akazed.cu:3896, as hak_create fills itaps1 / itaps_base)
+template <typename V> static void op_taps(float var, int radius, V* out)
 {
-    if (radius < 1 || radius > 5) return fail("radius must be 1..5");
-    float taps[8];
-    hak_gauss_taps(var, radius, taps);
-    hak_launch_lowpass(nullptr, s, 0, p, d, 0, w, h, p, 1, taps, radius);
-    HIP_TRY(hipDeviceSynchronize());
-    return 0;
+    float t[8];
+    hak_gauss_taps(var, radius, t);
+    for (int i = 0; i < 8; i++) {
+        if constexpr (op_fast<V>) out[i] = i <= radius ? hak_fix16(t[i]) : 0;
+        else out[i] = t[i];
+    }
 }
-
-extern "C" int hak_op_down_smooth(const float* s, float* d, float* sm, int sw, int sh, int sp, int dw, int dh, int dp)
+// a device HakImgState per image whose octave-0 contrast factor is set the way k_kcontrast<V> sets it; *out == nullptr on failure
+template <typename V> static int op_state(HakImgState** out, const V* kcontrast, int nimg)
 {
-    float taps[8];
-    hak_gauss_taps(1.f, 2, taps);
-    HakOct so{sw, sh, sp, (long)sh * sp}, dd{dw, dh, dp, (long)dh * dp};
-    hak_launch_down_smooth(nullptr, s, d, sm, 0, so, dd, 1, taps);
-    HIP_TRY(hipDeviceSynchronize());
-    return 0;
-}
-
-extern "C" int hak_op_kcontrast(const float* smooth, int w, int h, int p, float per, float* kc, float* hmax, int* hist)
-{
+    *out = nullptr;
+    std::vector<HakImgState> hs((size_t)nimg);
+    for (int i = 0; i < nimg; i++) {
+        hs[i] = HakImgState{};
+        if constexpr (op_fast<V>) {
+            if (kcontrast[i] < 0 || kcontrast[i] > HAK_FAST_KC_MAX) return fail("integer contrast factor must be in 0 .. 46340");
+            hs[i].ikcontrast[0] = kcontrast[i];
+            hs[i].ikc[0] = 1.f / (float)(kcontrast[i] * kcontrast[i]);            // akazed.cu:4215 (0 -> inf)
+        } else {
+            hs[i].kcontrast[0] = kcontrast[i];
+            hs[i].ikc[0] = 1.f / (kcontrast[i] * kcontrast[i]);                   // akazed.cu:2493
+        }
+    }
     HakImgState* st = nullptr;
-    HIP_TRY(hipMalloc((void**)&st, sizeof(HakImgState)));
-    hak_launch_reset_state(nullptr, st, 1);
-    hak_launch_contrast(nullptr, smooth, 0, w, h, p, 1, st, per, 1);
+    HIP_TRY(hipMalloc((void**)&st, sizeof(HakImgState) * (size_t)nimg));
+    if (hipMemcpy(st, hs.data(), sizeof(HakImgState) * (size_t)nimg, hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipFree(st);
+        return fail("state upload");
+    }
+    *out = st;
+    return 0;
+}
+static int op_sync(const char* who)
+{
+    const hipError_t e = hipDeviceSynchronize();
+    if (e != hipSuccess) return fail(std::string(who) + ": " + hipGetErrorString(e));
+    return 0;
+}
+// ... and frees a state on the way out
+static int op_sync_free(const char* who, HakImgState* st)
+{
+    const int rc = op_sync(who);
+    (void)hipFree(st);
+    return rc;
+}
+// contrast factor, lattice maximum and the reference's h_hist of a one-image state; frees it.  h_hist: the w x h pixels plus what
+// the threads beside / below the image add to bin 0 (hak_hist_extra0; the kernels carry that constant into `thresh` instead of
+// adding it to the device histogram)
+template <typename V> static int op_state_result(const char* who, HakImgState* st, int w, int h, V* kc, V* hmax, int* hist)
+{
     HakImgState hs;
-    HIP_TRY(hipMemcpy(&hs, st, sizeof(hs), hipMemcpyDeviceToHost));
-    HIP_TRY(hipFree(st));
-    if (kc) *kc = hs.kcontrast[0];
-    if (hmax) memcpy(hmax, &hs.hmax_bits, 4);
-    // the reference's h_hist: the w x h pixels plus what the threads beside / below the image add to bin 0 (hak_hist_extra0; the
-    // kernels carry that constant into `thresh` instead of adding it to the device histogram)
+    const hipError_t e = hipDeviceSynchronize();
+    const hipError_t e2 = e == hipSuccess ? hipMemcpy(&hs, st, sizeof(hs), hipMemcpyDeviceToHost) : e;
+    (void)hipFree(st);
+    if (e2 != hipSuccess) return fail(std::string(who) + ": " + hipGetErrorString(e2));
+    if constexpr (op_fast<V>) {
+        if (kc) *kc = hs.ikcontrast[0];
+        if (hmax) *hmax = hs.ihmax;
+    } else {
+        if (kc) *kc = hs.kcontrast[0];
+        if (hmax) memcpy(hmax, &hs.hmax_bits, 4);
+    }
     if (hist) { memcpy(hist, hs.hist, sizeof(hs.hist)); hist[0] += hak_hist_extra0(w, h); }
     return 0;
 }
-
-extern "C" int hak_op_flow(const float* s, float* d, int w, int h, int p, int diffusivity, float kcontrast)
+// max_fuse of the environment; FAST keeps the 4-px groups (hak_sequence.hip build_level: above 4 counts as 4; no deeper int kernel is built)
+template <typename V> static int op_max_fuse()
 {
-    float ikc = 1.f / (kcontrast * kcontrast);                                    // akazed.cu:2493
-    hak_launch_flow(nullptr, s, d, 0, w, h, p, 1, diffusivity, nullptr, 0, ikc);
-    HIP_TRY(hipDeviceSynchronize());
-    return 0;
+    const int m = hak_knobs_from_env().max_fuse;
+    return op_fast<V> && m > 4 ? 4 : m;
 }
+// the FED ping-pong of a cycle cut into G launches: groups g0 .. G-1 from `s` (`done` steps are behind it), alternating dst / tmp so
+// that the last launch lands in dst
+template <typename V>
+static void op_fed_groups(const V* s, const V* flow, V* dst, V* tmp, long stride, int w, int h, int p, int nimg, const float* tau,
+                          int nsteps, int G, int g0, int done)
+{
+    for (int g = g0; g < G; g++) {
+        const int ns = hak_fed_group_size(nsteps, G, g);
+        V* d = ((G - g) % 2 == 1) ? dst : tmp;
+        hak_launch_fed_group(nullptr, s, flow, d, stride, w, h, p, nimg, tau + done, ns);
+        done += ns;
+        s = d;
+    }
+}
+
+template <typename In, typename V>
+static int lowpass_t(const char* who, const In* s, int sp, V* d, int w, int h, int p, float var, int radius)
+{
+    if (radius < 1 || radius > 5) return fail("radius must be 1..5");
+    V taps[8];
+    op_taps<V>(var, radius, taps);
+    hak_launch_lowpass(nullptr, s, 0, sp, d, 0, w, h, p, 1, taps, radius);
+    return op_sync(who);
+}
+extern "C" int hak_op_lowpass(const float* s, float* d, int w, int h, int p, float var, int radius)
+{ return lowpass_t(HAK_SYNC_TEXT, s, p, d, w, h, p, var, radius); }
+extern "C" int hak_op_fast_conv_u8(const unsigned char* s, int sp, int* d, int w, int h, int p, float var, int radius)
+{ return lowpass_t("hak_op_fast_conv_u8", s, sp, d, w, h, p, var, radius); }
+extern "C" int hak_op_fast_lowpass(const int* s, int* d, int w, int h, int p, float var, int radius)
+{ return lowpass_t("hak_op_fast_lowpass", s, p, d, w, h, p, var, radius); }
+
+template <typename V>
+static int down_smooth_t(const char* who, const V* s, V* d, V* sm, int sw, int sh, int sp, int dw, int dh, int dp)
+{
+    V taps[8];
+    op_taps<V>(1.f, 2, taps);
+    HakOct so{sw, sh, sp, (long)sh * sp}, dd{dw, dh, dp, (long)dh * dp};
+    hak_launch_down_smooth(nullptr, s, d, sm, 0, so, dd, 1, taps);
+    return op_sync(who);
+}
+extern "C" int hak_op_down_smooth(const float* s, float* d, float* sm, int sw, int sh, int sp, int dw, int dh, int dp)
+{ return down_smooth_t(HAK_SYNC_TEXT, s, d, sm, sw, sh, sp, dw, dh, dp); }
+extern "C" int hak_op_fast_down_smooth(const int* s, int* d, int* sm, int sw, int sh, int sp, int dw, int dh, int dp)
+{ return down_smooth_t("hak_op_fast_down_smooth", s, d, sm, sw, sh, sp, dw, dh, dp); }
+
+template <typename V>
+static int kcontrast_t(const char* who, const V* smooth, int w, int h, int p, float per, V* kc, V* hmax, int* hist)
+{
+    HakImgState* st = nullptr;
+    HIP_TRY(hipMalloc((void**)&st, sizeof(HakImgState)));
+    (void)hipMemset(st, 0, sizeof(HakImgState));
+    hak_launch_reset_state(nullptr, st, 1);
+    hak_launch_contrast(nullptr, smooth, 0, w, h, p, 1, st, per, 1);
+    return op_state_result<V>(who, st, w, h, kc, hmax, hist);
+}
+extern "C" int hak_op_kcontrast(const float* smooth, int w, int h, int p, float per, float* kc, float* hmax, int* hist)
+{ return kcontrast_t("hipMemcpy(&hs, st, sizeof(hs), hipMemcpyDeviceToHost)", smooth, w, h, p, per, kc, hmax, hist); }
+extern "C" int hak_op_fast_kcontrast(const int* smooth, int w, int h, int p, float per, int* kc, int* hmax, int* hist)
+{ return kcontrast_t("FAST contrast", smooth, w, h, p, per, kc, hmax, hist); }
+
+template <typename V>
+static int flow_t(const char* who, const V* s, V* d, int w, int h, int p, int diffusivity, V kcontrast)
+{
+    HakImgState* st = nullptr;
+    if (op_state<V>(&st, &kcontrast, 1)) return 1;
+    hak_launch_flow(nullptr, s, d, 0, w, h, p, 1, diffusivity, st, 0);
+    return op_sync_free(who, st);
+}
+extern "C" int hak_op_flow(const float* s, float* d, int w, int h, int p, int diffusivity, float kcontrast)
+{ return flow_t(HAK_SYNC_TEXT, s, d, w, h, p, diffusivity, kcontrast); }
+extern "C" int hak_op_fast_flow(const int* s, int* d, int w, int h, int p, int diffusivity, int kcontrast)
+{ return flow_t("hak_op_fast_flow", s, d, w, h, p, diffusivity, kcontrast); }
 
 extern "C" int hak_op_rcp_check(unsigned lo_bits, unsigned hi_bits, unsigned long long* mismatches)
 {
@@ -108,179 +217,83 @@ extern "C" int hak_op_rcp_check(unsigned lo_bits, unsigned hi_bits, unsigned lon
     return rc;
 }
 
-extern "C" int hak_op_smooth_flow(const float* s, float* sm, float* fl, int w, int h, int p, int diffusivity, float kcontrast)
+template <typename V>
+static int smooth_flow_t(const char* who, const V* s, V* sm, V* fl, int w, int h, int p, int diffusivity, V kcontrast)
 {
-    float taps[8];
-    hak_gauss_taps(1.f, 2, taps);
-    const float ikc = 1.f / (kcontrast * kcontrast);                              // akazed.cu:2493
-    hak_launch_smooth_flow(nullptr, s, sm, fl, 0, w, h, p, 1, taps, diffusivity, nullptr, 0, ikc);
-    HIP_TRY(hipDeviceSynchronize());
-    return 0;
+    V taps[8];
+    op_taps<V>(1.f, 2, taps);
+    HakImgState* st = nullptr;
+    if (op_state<V>(&st, &kcontrast, 1)) return 1;
+    hak_launch_smooth_flow(nullptr, s, sm, fl, 0, w, h, p, 1, taps, diffusivity, st, 0);
+    return op_sync_free(who, st);
 }
+extern "C" int hak_op_smooth_flow(const float* s, float* sm, float* fl, int w, int h, int p, int diffusivity, float kcontrast)
+{ return smooth_flow_t(HAK_SYNC_TEXT, s, sm, fl, w, h, p, diffusivity, kcontrast); }
+extern "C" int hak_op_fast_smooth_flow(const int* s, int* sm, int* fl, int w, int h, int p, int diffusivity, int kcontrast)
+{ return smooth_flow_t("hak_op_fast_smooth_flow", s, sm, fl, w, h, p, diffusivity, kcontrast); }
 
+// nsteps FED steps in the launches the sequence would cut them into; image i's planes lie `stride` elements behind image i-1's
+template <typename V>
+static int nld_steps_t(const char* who, const V* src, const V* flow, V* dst, V* tmp, long stride, int w, int h, int p, int nimg,
+                       const float* tau, int nsteps)
+{
+    if (nsteps < 1 || nimg < 1) return fail("nsteps < 1 or nimg < 1");
+    if (p % 4 || stride % 4) return fail("pitch and stride must be multiples of 4");
+    const int G = hak_fed_groups(nsteps, op_max_fuse<V>(), w, false);
+    op_fed_groups(src, flow, dst, tmp, stride, w, h, p, nimg, tau, nsteps, G, 0, 0);
+    return op_sync(who);
+}
 extern "C" int hak_op_nld_steps(const float* src, const float* flow, float* dst, float* tmp, int w, int h, int p,
                                 const float* tau, int nsteps)
 {
     if (nsteps < 1) return fail("nsteps < 1");
     if (p % 4) return fail("pitch must be a multiple of 4");
-    const int G = hak_fed_groups(nsteps, hak_knobs_from_env().max_fuse, w, false);
-    const float* s = src;
-    int done = 0;
-    for (int g = 0; g < G; g++) {
-        const int ns = hak_fed_group_size(nsteps, G, g);
-        float* d = ((G - g) % 2 == 1) ? dst : tmp;
-        hak_launch_fed_group(nullptr, s, flow, d, 0, w, h, p, 1, tau + done, ns);
-        done += ns;
-        s = d;
-    }
-    HIP_TRY(hipDeviceSynchronize());
-    return 0;
+    return nld_steps_t(HAK_SYNC_TEXT, src, flow, dst, tmp, 0, w, h, p, 1, tau, nsteps);
 }
-
-// hak_op_nld_steps on a batch: image i's planes lie `stride` elements behind image i-1's
 extern "C" int hak_op_nld_steps_batch(const float* src, const float* flow, float* dst, float* tmp, long stride, int w, int h, int p,
                                       int nimg, const float* tau, int nsteps)
-{
-    if (nsteps < 1 || nimg < 1) return fail("nsteps < 1 or nimg < 1");
-    if (p % 4 || stride % 4) return fail("pitch and stride must be multiples of 4");
-    const int G = hak_fed_groups(nsteps, hak_knobs_from_env().max_fuse, w, false);
-    const float* s = src;
-    int done = 0;
-    for (int g = 0; g < G; g++) {
-        const int ns = hak_fed_group_size(nsteps, G, g);
-        float* d = ((G - g) % 2 == 1) ? dst : tmp;
-        hak_launch_fed_group(nullptr, s, flow, d, stride, w, h, p, nimg, tau + done, ns);
-        done += ns;
-        s = d;
-    }
-    HIP_TRY(hipDeviceSynchronize());
-    return 0;
-}
+{ return nld_steps_t(HAK_SYNC_TEXT, src, flow, dst, tmp, stride, w, h, p, nimg, tau, nsteps); }
+extern "C" int hak_op_fast_nld_steps_batch(const int* src, const int* flow, int* dst, int* tmp, long stride, int w, int h, int p,
+                                           int nimg, const float* tau, int nsteps)
+{ return nld_steps_t("hak_op_fast_nld_steps", src, flow, dst, tmp, stride, w, h, p, nimg, tau, nsteps); }
+extern "C" int hak_op_fast_nld_steps(const int* src, const int* flow, int* dst, int* tmp, int w, int h, int p, const float* tau, int nsteps)
+{ return nld_steps_t("hak_op_fast_nld_steps", src, flow, dst, tmp, 0, w, h, p, 1, tau, nsteps); }
 
 // One whole FED cycle of a sublevel the way the launch sequence runs it on large batches: k_fed_sf (sigma=1 low-pass + PM_G2
 // conductivity + the first group of steps; head != 0: the decimating octave-head form, src = the sw x sh source plane of pitch sp)
 // followed by the remaining groups through k_fed_multi.  All planes of image i lie `stride` elements behind image i-1's;
 // kcontrast: one contrast factor per image.  Fails when k_fed_sf does not cover the case (no other kernel is substituted).
-extern "C" int hak_op_fed_cycle(const float* src, int head, int sw, int sh, int sp, float* smooth, float* flow, float* dst, float* tmp,
-                                long stride, int w, int h, int p, int nimg, const float* kcontrast, const float* tau, int nsteps)
+template <typename V>
+static int fed_cycle_t(const char* who, const V* src, int head, int sw, int sh, int sp, V* smooth, V* flow, V* dst, V* tmp,
+                       long stride, int w, int h, int p, int nimg, const V* kcontrast, const float* tau, int nsteps)
 {
     if (nsteps < 1 || nimg < 1 || !kcontrast) return fail("nsteps < 1, nimg < 1 or no contrast factors");
-    if (p % 4 || stride % 4) return fail("pitch and stride must be multiples of 4");
-    std::vector<HakImgState> hs((size_t)nimg);
-    for (int i = 0; i < nimg; i++) {
-        hs[i] = HakImgState{};
-        hs[i].kcontrast[0] = kcontrast[i];
-        hs[i].ikc[0] = 1.f / (kcontrast[i] * kcontrast[i]);                       // akazed.cu:2493
-    }
+    if (p % 4 || stride % 4 || (op_fast<V> && head && sp % 4)) return fail("pitch and stride must be multiples of 4");
     HakImgState* state = nullptr;
-    HIP_TRY(hipMalloc((void**)&state, sizeof(HakImgState) * (size_t)nimg));
-    int rc = 0;
-    if (hipMemcpy(state, hs.data(), sizeof(HakImgState) * (size_t)nimg, hipMemcpyHostToDevice) != hipSuccess) rc = fail("state upload");
-    float taps[8];
-    hak_gauss_taps(1.f, 2, taps);
-    const int G = hak_fed_groups(nsteps, hak_knobs_from_env().max_fuse, w, false);
+    if (op_state<V>(&state, kcontrast, nimg)) return 1;
+    V taps[8];
+    op_taps<V>(1.f, 2, taps);
+    const int G = hak_fed_groups(nsteps, op_max_fuse<V>(), w, false);
     const int ns0 = hak_fed_group_size(nsteps, G, 0);
-    float* dst0 = (G % 2 == 1) ? dst : tmp;
-    if (!rc) {
-        const bool ok = head ? hak_launch_fed_sf_head(nullptr, src, HakOct{sw, sh, sp, (long)sh * sp}, smooth, flow, dst0, stride,
-                                                      HakOct{w, h, p, (long)h * p}, nimg, taps, HAK_PM_G2, tau, ns0, state, 0, G > 1)
-                             : hak_launch_fed_sf(nullptr, src, smooth, flow, dst0, stride, w, h, p, nimg, taps, HAK_PM_G2, tau, ns0, state, 0,
-                                                 G > 1);
-        if (!ok) rc = fail("hak_op_fed_cycle: k_fed_sf does not cover this case");
-    }
-    const float* s = dst0;
-    int done = ns0;
-    for (int g = 1; g < G && !rc; g++) {
-        const int ns = hak_fed_group_size(nsteps, G, g);
-        float* d = ((G - g) % 2 == 1) ? dst : tmp;
-        hak_launch_fed_group(nullptr, s, flow, d, stride, w, h, p, nimg, tau + done, ns);
-        done += ns;
-        s = d;
-    }
-    if (hipDeviceSynchronize() != hipSuccess && !rc) rc = fail("hak_op_fed_cycle: kernel");
+    V* dst0 = (G % 2 == 1) ? dst : tmp;
+    int rc = 0;
+    const bool ok = head ? hak_launch_fed_sf_head(nullptr, src, HakOct{sw, sh, sp, (long)sh * sp}, smooth, flow, dst0, stride,
+                                                  HakOct{w, h, p, (long)h * p}, nimg, taps, HAK_PM_G2, tau, ns0, state, 0, G > 1)
+                         : hak_launch_fed_sf(nullptr, src, smooth, flow, dst0, stride, w, h, p, nimg, taps, HAK_PM_G2, tau, ns0, state, 0, G > 1);
+    if (!ok) rc = fail(std::string(who) + ": k_fed_sf does not cover this case");
+    else op_fed_groups<V>(dst0, flow, dst, tmp, stride, w, h, p, nimg, tau, nsteps, G, 1, ns0);
+    const hipError_t e = hipDeviceSynchronize();
+    // (the float operator has always reported a failed kernel as "kernel", its twin by the error's name)
+    if (e != hipSuccess && !rc) rc = fail(std::string(who) + ": " + (op_fast<V> ? hipGetErrorString(e) : "kernel"));
     (void)hipFree(state);
     return rc;
 }
-
-extern "C" int hak_op_hessian(const float* s, float* lx, float* ly, float* det, int w, int h, int p, int step)
-{
-    // the kernels write the derivatives interleaved (HakLayout); the test interface keeps the reference's three planes
-    float* dxy = nullptr;
-    HIP_TRY(hipMalloc((void**)&dxy, sizeof(float) * 2 * (size_t)h * p));
-    hak_launch_hessian_level(nullptr, s, dxy, det, true, 0, w, h, p, 1, step, nullptr, nullptr, nullptr, 0, 0, 0.f);
-    hak_launch_deinterleave(nullptr, dxy, lx, ly, w, h, p);
-    const hipError_t e = hipDeviceSynchronize();
-    (void)hipFree(dxy);
-    if (e != hipSuccess) return fail(std::string("hak_op_hessian: ") + hipGetErrorString(e));
-    return 0;
-}
-
-// ------------------------------------------------ the same operators on the integer FAST path (tests/test_gpu_fast_stages.py)
-// Each drives the `int` overload the launch sequence (build_level<int> / hessian_level<int>, hak_sequence.hip) calls.
-#define HAK_FAST_KC_MAX 46340                                       // kcontrast * kcontrast stays inside int32 (akazed.cu:4215)
-static void fast_taps(float var, int radius, int* it)              // akazed.cu:3896, as hak_create fills itaps1 / itaps_base
-{
-    float t[8];
-    hak_gauss_taps(var, radius, t);
-    for (int i = 0; i < 8; i++) it[i] = i <= radius ? (int)(t[i] * 65536 + 0.5f) : 0;
-}
-// a device HakImgState per image whose octave-0 contrast factor is set the way kf_kcontrast sets it; *out == nullptr on failure
-static int fast_state(HakImgState** out, const int* kcontrast, int nimg)
-{
-    *out = nullptr;
-    std::vector<HakImgState> hs((size_t)nimg);
-    for (int i = 0; i < nimg; i++) {
-        if (kcontrast[i] < 0 || kcontrast[i] > HAK_FAST_KC_MAX) return fail("integer contrast factor must be in 0 .. 46340");
-        hs[i] = HakImgState{};
-        hs[i].ikcontrast[0] = kcontrast[i];
-        hs[i].ikc[0] = 1.f / (float)(kcontrast[i] * kcontrast[i]);                // akazed.cu:4215 (0 -> inf)
-    }
-    HakImgState* st = nullptr;
-    HIP_TRY(hipMalloc((void**)&st, sizeof(HakImgState) * (size_t)nimg));
-    if (hipMemcpy(st, hs.data(), sizeof(HakImgState) * (size_t)nimg, hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipFree(st);
-        return fail("state upload");
-    }
-    *out = st;
-    return 0;
-}
-// contrast factor, lattice maximum and the reference's h_hist (hak_op_kcontrast has the bin-0 note) of a one-image state; frees it
-static int fast_state_result(HakImgState* st, int w, int h, int* kc, int* hmax, int* hist)
-{
-    HakImgState hs;
-    const hipError_t e = hipDeviceSynchronize();
-    const hipError_t e2 = e == hipSuccess ? hipMemcpy(&hs, st, sizeof(hs), hipMemcpyDeviceToHost) : e;
-    (void)hipFree(st);
-    if (e2 != hipSuccess) return fail(std::string("FAST contrast: ") + hipGetErrorString(e2));
-    if (kc) *kc = hs.ikcontrast[0];
-    if (hmax) *hmax = hs.ihmax;
-    if (hist) { memcpy(hist, hs.hist, sizeof(hs.hist)); hist[0] += hak_hist_extra0(w, h); }
-    return 0;
-}
-static int fast_sync(const char* what)
-{
-    const hipError_t e = hipDeviceSynchronize();
-    if (e != hipSuccess) return fail(std::string(what) + ": " + hipGetErrorString(e));
-    return 0;
-}
-
-extern "C" int hak_op_fast_conv_u8(const unsigned char* s, int sp, int* d, int w, int h, int p, float var, int radius)
-{
-    if (radius < 1 || radius > 5) return fail("radius must be 1..5");
-    int taps[8];
-    fast_taps(var, radius, taps);
-    hakf_launch_conv_u8(nullptr, s, 0, sp, d, 0, w, h, p, 1, taps, radius);
-    return fast_sync("hak_op_fast_conv_u8");
-}
-
-extern "C" int hak_op_fast_lowpass(const int* s, int* d, int w, int h, int p, float var, int radius)
-{
-    if (radius < 1 || radius > 5) return fail("radius must be 1..5");
-    int taps[8];
-    fast_taps(var, radius, taps);
-    hakf_launch_conv_int(nullptr, s, d, 0, w, h, p, 1, taps, radius);
-    return fast_sync("hak_op_fast_lowpass");
-}
+extern "C" int hak_op_fed_cycle(const float* src, int head, int sw, int sh, int sp, float* smooth, float* flow, float* dst, float* tmp,
+                                long stride, int w, int h, int p, int nimg, const float* kcontrast, const float* tau, int nsteps)
+{ return fed_cycle_t("hak_op_fed_cycle", src, head, sw, sh, sp, smooth, flow, dst, tmp, stride, w, h, p, nimg, kcontrast, tau, nsteps); }
+extern "C" int hak_op_fast_fed_cycle(const int* src, int head, int sw, int sh, int sp, int* smooth, int* flow, int* dst, int* tmp,
+                                     long stride, int w, int h, int p, int nimg, const int* kcontrast, const float* tau, int nsteps)
+{ return fed_cycle_t("hak_op_fast_fed_cycle", src, head, sw, sh, sp, smooth, flow, dst, tmp, stride, w, h, p, nimg, kcontrast, tau, nsteps); }
 
 extern "C" int hak_op_fast_base(const unsigned char* img, int sp, int* lt, int w, int h, int p, float var_base, int radius, float per,
                                 int* kc, int* hmax, int* hist, int* route)
@@ -288,8 +301,8 @@ extern "C" int hak_op_fast_base(const unsigned char* img, int sp, int* lt, int w
     if (radius < 1 || radius > 5) return fail("radius must be 1..5");
     if (p % 4) return fail("pitch must be a multiple of 4");
     int taps1[8], tapsb[8];
-    fast_taps(1.f, 2, taps1);
-    fast_taps(var_base, radius, tapsb);
+    op_taps<int>(1.f, 2, taps1);
+    op_taps<int>(var_base, radius, tapsb);
     const HakKnobs kn = hak_knobs_from_env();
     // Lt, the gradient scratch and the sigma = 1 plane in ONE allocation, as in the arena: the streaming kernels address their
     // output planes as 32-bit offsets from the lower one and decline planes that lie too far apart
@@ -299,121 +312,23 @@ extern "C" int hak_op_fast_base(const unsigned char* img, int sp, int* lt, int w
     HakImgState* st = nullptr;
     if (hipMalloc((void**)&st, sizeof(HakImgState)) != hipSuccess) { (void)hipFree(buf); return fail("state alloc"); }
     (void)hipMemset(st, 0, sizeof(HakImgState));
-    hakf_launch_reset(nullptr, st, 1);
+    hak_launch_reset_state(nullptr, st, 1);
     int *Lt = buf, *grad = buf + plane, *smooth = buf + 2 * plane;
     const bool based = hak_launch_base_level(nullptr, img, 0, sp, Lt, grad, 0, w, h, p, 1, taps1, tapsb, radius, st, per, 1, kn);
     if (!based) {                                                                 // hak_sequence.hip build_level, akaze.cpp:589-623
-        hakf_launch_conv_u8(nullptr, img, 0, sp, smooth, 0, w, h, p, 1, taps1, 2);
+        hak_launch_lowpass(nullptr, img, 0, sp, smooth, 0, w, h, p, 1, taps1, 2);
         hak_launch_contrast(nullptr, smooth, 0, w, h, p, 1, st, per, 1);
-        hakf_launch_conv_u8(nullptr, img, 0, sp, Lt, 0, w, h, p, 1, tapsb, radius);
+        hak_launch_lowpass(nullptr, img, 0, sp, Lt, 0, w, h, p, 1, tapsb, radius);
     }
     // which kernel hak_launch_base_level took: the cover of launch_base_stream (kernels_base_stream.hip; its plane-distance clauses
     // cannot trip on the single allocation above)
     const bool streamed = radius >= 2 && radius <= 4 && (w & 3) == 0 && w >= 16 && h >= 16 && sp % 4 == 0 &&
                           reinterpret_cast<uintptr_t>(img) % 4 == 0 && hak_stream_pays(kn.base_stream, w, h, 1);
     if (route) *route = !based ? 3 : streamed ? 1 : 2;
-    int rc = fast_state_result(st, w, h, kc, hmax, hist);
+    int rc = op_state_result<int>("FAST contrast", st, w, h, kc, hmax, hist);
     if (!rc && hipMemcpy(lt, Lt, sizeof(int) * plane, hipMemcpyDeviceToDevice) != hipSuccess) rc = fail("hak_op_fast_base: copy");
     (void)hipFree(buf);
     return rc;
-}
-
-extern "C" int hak_op_fast_down_smooth(const int* s, int* d, int* sm, int sw, int sh, int sp, int dw, int dh, int dp)
-{
-    int taps[8];
-    fast_taps(1.f, 2, taps);
-    HakOct so{sw, sh, sp, (long)sh * sp}, dd{dw, dh, dp, (long)dh * dp};
-    hak_launch_down_smooth(nullptr, s, d, sm, 0, so, dd, 1, taps);
-    return fast_sync("hak_op_fast_down_smooth");
-}
-
-extern "C" int hak_op_fast_kcontrast(const int* smooth, int w, int h, int p, float per, int* kc, int* hmax, int* hist)
-{
-    HakImgState* st = nullptr;
-    HIP_TRY(hipMalloc((void**)&st, sizeof(HakImgState)));
-    (void)hipMemset(st, 0, sizeof(HakImgState));
-    hakf_launch_reset(nullptr, st, 1);
-    hak_launch_contrast(nullptr, smooth, 0, w, h, p, 1, st, per, 1);
-    return fast_state_result(st, w, h, kc, hmax, hist);
-}
-
-extern "C" int hak_op_fast_flow(const int* s, int* d, int w, int h, int p, int diffusivity, int kcontrast)
-{
-    HakImgState* st = nullptr;
-    if (fast_state(&st, &kcontrast, 1)) return 1;
-    hak_launch_flow(nullptr, s, d, 0, w, h, p, 1, diffusivity, st, 0);
-    const int rc = fast_sync("hak_op_fast_flow");
-    (void)hipFree(st);
-    return rc;
-}
-
-extern "C" int hak_op_fast_smooth_flow(const int* s, int* sm, int* fl, int w, int h, int p, int diffusivity, int kcontrast)
-{
-    int taps[8];
-    fast_taps(1.f, 2, taps);
-    HakImgState* st = nullptr;
-    if (fast_state(&st, &kcontrast, 1)) return 1;
-    hak_launch_smooth_flow(nullptr, s, sm, fl, 0, w, h, p, 1, taps, diffusivity, st, 0);
-    const int rc = fast_sync("hak_op_fast_smooth_flow");
-    (void)hipFree(st);
-    return rc;
-}
-
-// FAST keeps the 4-px groups (hak_sequence.hip build_level: max_fuse above 4 counts as 4; no deeper int kernel is built)
-static int fast_max_fuse() { const int m = hak_knobs_from_env().max_fuse; return m > 4 ? 4 : m; }
-
-extern "C" int hak_op_fast_nld_steps_batch(const int* src, const int* flow, int* dst, int* tmp, long stride, int w, int h, int p,
-                                           int nimg, const float* tau, int nsteps)
-{
-    if (nsteps < 1 || nimg < 1) return fail("nsteps < 1 or nimg < 1");
-    if (p % 4 || stride % 4) return fail("pitch and stride must be multiples of 4");
-    const int G = hak_fed_groups(nsteps, fast_max_fuse(), w, false);
-    const int* s = src;
-    int done = 0;
-    for (int g = 0; g < G; g++) {
-        const int ns = hak_fed_group_size(nsteps, G, g);
-        int* d = ((G - g) % 2 == 1) ? dst : tmp;
-        hak_launch_fed_group(nullptr, s, flow, d, stride, w, h, p, nimg, tau + done, ns);
-        done += ns;
-        s = d;
-    }
-    return fast_sync("hak_op_fast_nld_steps");
-}
-
-extern "C" int hak_op_fast_nld_steps(const int* src, const int* flow, int* dst, int* tmp, int w, int h, int p, const float* tau, int nsteps)
-{
-    return hak_op_fast_nld_steps_batch(src, flow, dst, tmp, 0, w, h, p, 1, tau, nsteps);
-}
-
-extern "C" int hak_op_fast_fed_cycle(const int* src, int head, int sw, int sh, int sp, int* smooth, int* flow, int* dst, int* tmp,
-                                     long stride, int w, int h, int p, int nimg, const int* kcontrast, const float* tau, int nsteps)
-{
-    if (nsteps < 1 || nimg < 1 || !kcontrast) return fail("nsteps < 1, nimg < 1 or no contrast factors");
-    if (p % 4 || stride % 4 || (head && sp % 4)) return fail("pitch and stride must be multiples of 4");
-    HakImgState* state = nullptr;
-    if (fast_state(&state, kcontrast, nimg)) return 1;
-    int taps[8];
-    fast_taps(1.f, 2, taps);
-    const int G = hak_fed_groups(nsteps, fast_max_fuse(), w, false);
-    const int ns0 = hak_fed_group_size(nsteps, G, 0);
-    int* dst0 = (G % 2 == 1) ? dst : tmp;
-    int rc = 0;
-    const bool ok = head ? hak_launch_fed_sf_head(nullptr, src, HakOct{sw, sh, sp, (long)sh * sp}, smooth, flow, dst0, stride,
-                                                  HakOct{w, h, p, (long)h * p}, nimg, taps, HAK_PM_G2, tau, ns0, state, 0, G > 1)
-                         : hak_launch_fed_sf(nullptr, src, smooth, flow, dst0, stride, w, h, p, nimg, taps, HAK_PM_G2, tau, ns0, state, 0, G > 1);
-    if (!ok) rc = fail("hak_op_fast_fed_cycle: k_fed_sf does not cover this case");
-    const int* s = dst0;
-    int done = ns0;
-    for (int g = 1; g < G && !rc; g++) {
-        const int ns = hak_fed_group_size(nsteps, G, g);
-        int* d = ((G - g) % 2 == 1) ? dst : tmp;
-        hak_launch_fed_group(nullptr, s, flow, d, stride, w, h, p, nimg, tau + done, ns);
-        done += ns;
-        s = d;
-    }
-    const int rs = fast_sync("hak_op_fast_fed_cycle");
-    (void)hipFree(state);
-    return rc ? rc : rs;
 }
 
 extern "C" int hak_op_fast_level_tile(const int* src, int head, int sw, int sh, int sp, int* smooth, int* dst, int* tmp, long stride,
@@ -424,38 +339,44 @@ extern "C" int hak_op_fast_level_tile(const int* src, int head, int sw, int sh, 
     if (p % 4 || stride % 4 || (head && sp % 4)) return fail("pitch and stride must be multiples of 4");      // (the kernel stores 16-byte groups)
     if (head && (w != sw / 2 || h != sh / 2)) return fail("an octave head halves the source extents");
     HakImgState* state = nullptr;
-    if (fast_state(&state, kcontrast, nimg)) return 1;
+    if (op_state<int>(&state, kcontrast, nimg)) return 1;
     int taps[8];
-    fast_taps(1.f, 2, taps);
+    op_taps<int>(1.f, 2, taps);
     const HakOct dd{w, h, p, (long)h * p};
     const int nl = hak_launch_level_tile(nullptr, src, head ? HakOct{sw, sh, sp, (long)sh * sp} : dd, head != 0, smooth, dst, tmp, stride, dd,
                                          nimg, taps, diffusivity, tau, nsteps, state, 0);
     if (launches) *launches = nl;
-    const int rc = fast_sync("hak_op_fast_level_tile");
+    const int rc = op_sync("hak_op_fast_level_tile");
     (void)hipFree(state);
     return rc;
 }
 
-extern "C" int hak_op_fast_hessian(const int* s, int* lx, int* ly, int* det, int w, int h, int p, int step, int* route)
+// Hessian of one level into the reference's three planes (the kernels write the derivatives interleaved, HakLayout).  The interleaved
+// derivatives and the determinant lie in ONE allocation (see hak_op_fast_base).  route: 1 streaming, 2 tile kernel, 3 unfused pair
+template <typename V>
+static int hessian_t(const char* who, const V* s, V* lx, V* ly, V* det, int w, int h, int p, int step, int* route)
 {
-    if (step < 1) return fail("step < 1");
-    // the interleaved derivatives and the determinant in ONE allocation (see hak_op_fast_base); the test interface keeps the
-    // reference's three planes
+    if (op_fast<V> && step < 1) return fail("step < 1");
     const size_t plane = (size_t)h * p;
-    int* buf = nullptr;
-    HIP_TRY(hipMalloc((void**)&buf, sizeof(int) * 3 * plane));
-    int *dxy = buf, *dt = buf + 2 * plane;
+    V* buf = nullptr;
+    HIP_TRY(hipMalloc((void**)&buf, sizeof(V) * 3 * plane));
+    V *dxy = buf, *dt = buf + 2 * plane;
     const HakKnobs kn = hak_knobs_from_env();
-    const bool fused = hak_launch_hessian_level(nullptr, s, dxy, dt, true, 0, w, h, p, 1, step, nullptr, nullptr, nullptr, 0, 0, 0);
+    const V thr = 0;
+    const bool fused = hak_launch_hessian_level(nullptr, s, dxy, dt, true, 0, w, h, p, 1, step, nullptr, nullptr, nullptr, 0, 0, thr);
     hak_launch_deinterleave(nullptr, reinterpret_cast<const float*>(dxy), reinterpret_cast<float*>(lx), reinterpret_cast<float*>(ly), w, h, p);
     // launch_hessian_level_t (kernels_hessian.hip): streaming where it pays and covers, else the tile kernel up to dilation 4
     if (route) *route = !fused ? 3 : (hak_stream_pays(kn.hess_stream, w, h, 1) && hak_hessian_stream_covers(w, h, step, false)) ? 1 : 2;
-    int rc = fast_sync("hak_op_fast_hessian");
-    if (!rc && fused != (step <= 4)) rc = fail("hak_op_fast_hessian: unexpected route");
-    if (!rc && hipMemcpy(det, dt, sizeof(int) * plane, hipMemcpyDeviceToDevice) != hipSuccess) rc = fail("hak_op_fast_hessian: copy");
+    int rc = op_sync(who);
+    if (!rc && fused != (step <= 4)) rc = fail(std::string(who) + ": unexpected route");
+    if (!rc && hipMemcpy(det, dt, sizeof(V) * plane, hipMemcpyDeviceToDevice) != hipSuccess) rc = fail(std::string(who) + ": copy");
     (void)hipFree(buf);
     return rc;
 }
+extern "C" int hak_op_hessian(const float* s, float* lx, float* ly, float* det, int w, int h, int p, int step)
+{ return hessian_t("hak_op_hessian", s, lx, ly, det, w, h, p, step, nullptr); }
+extern "C" int hak_op_fast_hessian(const int* s, int* lx, int* ly, int* det, int w, int h, int p, int step, int* route)
+{ return hessian_t("hak_op_fast_hessian", s, lx, ly, det, w, h, p, step, route); }
 
 // Hessian of one level on a batch, either element type (tests/test_gpu_strip_seams.py).  Per image the arena slot holds the interleaved
 // derivatives, the determinant and then the source plane: the last image's last source row ends the allocation, as an image's last

@@ -4,7 +4,7 @@
 //   hLowPass(img -> smooth, var 1, ksz 5)         akazed.cu:2336 (gConv2d<2>)
 //   hScharrContrast: max |Scharr(smooth)|         akazed.cu:2410, 644 (float) / 3208 (fastakaze)
 //
-// Same outputs as the LDS tile kernels k_base_a<R> (kernels_base.hip) and kf_base<R> (kernels_fast.hip): Lt(0,0), the
+// Same outputs as the LDS tile kernels k_base_a<R> and kf_base<R> (kernels_base.hip): Lt(0,0), the
 // gradient magnitude of the sigma=1 image as a plane for the histogram pass, and its maximum.  Here a wave owns a 248-px
 // strip (float4 / 4 bytes per lane) and streams down its row segment like k_fed_sf: when image row t arrives,
 //     row passes of both Gaussians on row t (x neighbours -4..+4 are exactly the two neighbour lanes: 8 DPP shifts),
@@ -72,55 +72,29 @@ __device__ __forceinline__ int4 bsm_unpack(const BsRaw<int>& r, bool edge)
     return v;
 }
 
-// base Gaussian: c*b0, then += b[k] * (value at -k + value at +k), k = 1..R (akazed.cu:227-239 / 283-288); the integer
-// version ends in >> 16 (akazed.cu:2922-2985)
-template <int R>
-__device__ __forceinline__ float bsm_conv(const float c, const float (&m)[4], const float (&q)[4], const float (&b)[5])
+// base Gaussian (hak_conv, pixel_rules.h) on the centre c and the sample pairs m[k-1] (at -k), q[k-1] (at +k), k = 1..R
+template <int R, typename V>
+__device__ __forceinline__ V bsm_conv(const V c, const V (&m)[4], const V (&q)[4], const V (&b)[5])
 {
-    float ws = c * b[0];
-#pragma unroll
-    for (int k = 1; k <= R; k++) ws += b[k] * (m[k - 1] + q[k - 1]);
-    return ws;
-}
-template <int R>
-__device__ __forceinline__ int bsm_conv(const int c, const int (&m)[4], const int (&q)[4], const int (&b)[5])
-{
-    unsigned ws = (unsigned)b[0] * (unsigned)c;
-#pragma unroll
-    for (int k = 1; k <= R; k++) ws += (unsigned)b[k] * (unsigned)(m[k - 1] + q[k - 1]);
-    return (int)ws >> 16;
+    return hak_conv<R>(b, [&](int k) { return k == 0 ? c : k < 0 ? m[-k - 1] : q[k - 1]; });
 }
 
 // Scharr magnitude of the sigma=1 image (float: akazed.cu:664-666, un-normalised; int: akazed.cu:3208-3232)
 __device__ __forceinline__ float bsm_mag(float ul, float uc, float ur, float cl, float cr, float ll, float lc, float lr)
 {
-    const float dx = 10 * (cr - cl) + 3 * (ur + lr - ul - ll);
-    const float dy = 10 * (lc - uc) + 3 * (ll + lr - ul - ur);
-    return sqrtf(dx * dx + dy * dy);
+    float dx, dy;
+    hak_scharr(ul, uc, ur, cl, cr, ll, lc, lr, dx, dy);
+    return hak_grad_mag(dx, dy);
 }
 __device__ __forceinline__ int bsm_mag(int ul, int uc, int ur, int cl, int cr, int ll, int lc, int lr)
 {
-    const int dx = 10 * (cr - cl) + 3 * (ur + lr - ul - ll);
-    const int dy = 10 * (lc - uc) + 3 * (ll + lr - ul - ur);
+    int dx, dy;
+    hak_scharr(ul, uc, ur, cl, cr, ll, lc, lr, dx, dy);
+    // hak_grad_mag(int) of pixel_rules.h written out: through the call the compiler schedules k_base_stream<int> differently
     return (int)(sqrtf((float)(int)((unsigned)dx * (unsigned)dx + (unsigned)dy * (unsigned)dy)) + 0.5f);
 }
-__device__ __forceinline__ float bsm_max(float a, float b) { return fmaxf(a, b); }
-__device__ __forceinline__ int bsm_max(int a, int b) { return max(a, b); }
-// histogram bin of one gradient magnitude (akazed.cu:924-928 / 3319-3326); F = the per-image factor (float path: NBINS / hmax as a
-// double -- the exact double product truncated = __fmul_rz + float -> int; FAST path: the 16.16 factor, wrapping product)
-template <typename V> struct BsHistF;
-template <> struct BsHistF<float> { double f; };
-template <> struct BsHistF<int> { int f; };
-__device__ __forceinline__ int bsm_bin(float g, const BsHistF<float>& F)
-{
-    const int hi = (int)((double)g * F.f);
-    return hi >= HAK_NBINS ? HAK_NBINS - 1 : hi;
-}
-__device__ __forceinline__ int bsm_bin(int g, const BsHistF<int>& F)
-{
-    const int hi = (int)((unsigned)g * (unsigned)F.f) >> 16;
-    return hi >= HAK_NBINS ? HAK_NBINS - 1 : (hi < 0 ? 0 : hi);
-}
+// histogram factor of an image: hak_hist_factor's type (float path: a double, FAST path: 16.16)
+template <typename V> struct BsHistF { decltype(hak_hist_factor(V())) f; };
 #define BS_HIST_COPIES 8       // LDS histograms per block, selected by lane (LDS atomics on one address serialise)
 
 // Lt and the gradient plane as one raw buffer (lower pointer) + byte offsets: unconditional, countable stores (fed_common.h)
@@ -158,7 +132,7 @@ __device__ __forceinline__ void bsm_iter(BsmState<V>& S, const int t, const type
             const V m[4] = {win[3 + j], win[2 + j], win[1 + j], win[j]};
             const V q[4] = {win[5 + j], win[6 + j], win[7 + j], win[8 + j]};
             hb[j] = bsm_conv<R>(win[4 + j], m, q, tp.b);
-            h1[j] = sf_conv(win[4 + j], win[3 + j], win[5 + j], win[2 + j], win[6 + j], tp.a);
+            h1[j] = hak_conv5(win[4 + j], win[3 + j], win[5 + j], win[2 + j], win[6 + j], tp.a);
         }
         S.Hb[pmod(U, BS_RING)] = mk4(hb[0], hb[1], hb[2], hb[3]);
         S.H1[pmod(U, BS_RING)] = mk4(h1[0], h1[1], h1[2], h1[3]);
@@ -197,10 +171,10 @@ __device__ __forceinline__ void bsm_iter(BsmState<V>& S, const int t, const type
         const V4 cc = S.H1[pmod(U - 2, BS_RING)], u1 = S.H1[pmod(U - 3, BS_RING)], d1 = S.H1[pmod(U - 1, BS_RING)];
         const V4 u2 = S.H1[pmod(U - 4, BS_RING)], d2 = S.H1[pmod(U, BS_RING)];
         V4 sm;
-        sm.x = sf_conv(cc.x, u1.x, d1.x, u2.x, d2.x, tp.a);
-        sm.y = sf_conv(cc.y, u1.y, d1.y, u2.y, d2.y, tp.a);
-        sm.z = sf_conv(cc.z, u1.z, d1.z, u2.z, d2.z, tp.a);
-        sm.w = sf_conv(cc.w, u1.w, d1.w, u2.w, d2.w, tp.a);
+        sm.x = hak_conv5(cc.x, u1.x, d1.x, u2.x, d2.x, tp.a);
+        sm.y = hak_conv5(cc.y, u1.y, d1.y, u2.y, d2.y, tp.a);
+        sm.z = hak_conv5(cc.z, u1.z, d1.z, u2.z, d2.z, tp.a);
+        sm.w = hak_conv5(cc.w, u1.w, d1.w, u2.w, d2.w, tp.a);
         S.Sm[pmod(U, 3)] = sm;
         S.SmL[pmod(U, 3)] = wave_shr1(sm.w);
         S.SmR[pmod(U, 3)] = wave_shl1(sm.x);
@@ -223,13 +197,13 @@ __device__ __forceinline__ void bsm_iter(BsmState<V>& S, const int t, const type
             if (inr && owns) {
                 // (counting runs of equal bins in registers -- a lane's four pixels mostly share one -- and issuing one atomic per run
                 // was measured slower still: the pass is short of vector issue slots, not of LDS atomic throughput)
-                atomicAdd(&mine[bsm_bin(g.x, HF)], 1); atomicAdd(&mine[bsm_bin(g.y, HF)], 1);
-                atomicAdd(&mine[bsm_bin(g.z, HF)], 1); atomicAdd(&mine[bsm_bin(g.w, HF)], 1);
+                atomicAdd(&mine[hak_hist_bin(g.x, HF.f)], 1); atomicAdd(&mine[hak_hist_bin(g.y, HF.f)], 1);
+                atomicAdd(&mine[hak_hist_bin(g.z, HF.f)], 1); atomicAdd(&mine[hak_hist_bin(g.w, HF.f)], 1);
             }
         } else {
             hak_buf_store_nt(O.r, O.gr + (inr ? (unsigned)(b * p) * (unsigned)sizeof(V) : HAK_BUF_OOB), g);
             // the reference's maximum runs over the 16-px lattice only (hak_on_lattice): x0 % 4 == 0, so only g.x can be on it
-            if (inr && lat && (b & 15) == 0 && b < hcov) S.tmax = bsm_max(S.tmax, g.x);
+            if (inr && lat && (b & 15) == 0 && b < hcov) S.tmax = vmax(S.tmax, g.x);
         }
     }
 }
@@ -286,7 +260,7 @@ __device__ __forceinline__ V bsm_strip(const typename BsT<V>::In* __restrict__ s
 // Scharr magnitude (akazed.cu:644-666 / 3208-3232) at the lattice points x % 16 == 0 && y % 16 == 0 that gFindMaxContrastU4's grid
 // covers (hak_on_lattice) -- one thread per lattice point: 7 x 7 input pixels (reflect-101 on the input index, as everywhere),
 // 7 rows x 3 columns of the row pass, 3 x 3 of the column pass, one magnitude, one atomicMax.  Same expressions, same order as the
-// streaming pass and the tile kernels (sf_conv, bsm_mag): the value is bit-identical to the plane's.
+// streaming pass and the tile kernels (hak_conv5, hak_scharr, hak_grad_mag): the value is bit-identical to the plane's.
 template <typename V>
 __global__ __launch_bounds__(256) void k_lattice_hmax(const typename BsT<V>::In* __restrict__ img, long img_stride, int sp, int w, int h,
                                                       SfTaps<V> tp, HakImgState* state, int nlx, int nly)
@@ -311,16 +285,16 @@ __global__ __launch_bounds__(256) void k_lattice_hmax(const typename BsT<V>::In*
 #pragma unroll
                 for (int i = 0; i < 3; i++) {
                     const int xc = xs[i];
-                    rp[d][i] = sf_conv((V)q[xc], (V)q[hak_refl(xc - 1, w)], (V)q[hak_refl(xc + 1, w)], (V)q[hak_refl(xc - 2, w)],
+                    rp[d][i] = hak_conv5((V)q[xc], (V)q[hak_refl(xc - 1, w)], (V)q[hak_refl(xc + 1, w)], (V)q[hak_refl(xc - 2, w)],
                                        (V)q[hak_refl(xc + 2, w)], tp);
                 }
             }
 #pragma unroll
-            for (int i = 0; i < 3; i++) sm[j][i] = sf_conv(rp[2][i], rp[1][i], rp[3][i], rp[0][i], rp[4][i], tp);
+            for (int i = 0; i < 3; i++) sm[j][i] = hak_conv5(rp[2][i], rp[1][i], rp[3][i], rp[0][i], rp[4][i], tp);
         }
         m = bsm_mag(sm[0][0], sm[0][1], sm[0][2], sm[1][0], sm[1][2], sm[2][0], sm[2][1], sm[2][2]);
     }
-    for (int off = 32; off > 0; off >>= 1) m = bsm_max(m, __shfl_xor(m, off));
+    for (int off = 32; off > 0; off >>= 1) m = vmax(m, __shfl_xor(m, off));
     if ((threadIdx.x & 63) == 0) {
         if constexpr (std::is_same<V, float>::value) {
             if (m > 0.f) atomicMax(&state[im].hmax_bits, __float_as_uint(m));        // (floored at 0.03f by the reset, akazed.cu:2413)
@@ -349,8 +323,7 @@ __global__ __launch_bounds__(256) void k_base_stream(const typename BsT<V>::In* 
     BsHistF<V> HF{};
     if constexpr (HIST) {
         for (int i = threadIdx.x; i < BS_HIST_COPIES * HAK_NBINS; i += 256) shist[i] = 0;
-        if constexpr (std::is_same<V, float>::value) HF.f = (double)(HAK_NBINS / __uint_as_float(state[im].hmax_bits));   // akazed.cu:2450
-        else HF.f = (int)(HAK_NBINS / (float)state[im].ihmax * 65536 + 0.5f);                                          // akazed.cu:4133
+        HF.f = hak_hist_factor(hak_state_hmax<V>(state + im));
         __syncthreads();
     }
     int* mine = shist + (HIST ? (lane & (BS_HIST_COPIES - 1)) * HAK_NBINS : 0);
@@ -371,7 +344,7 @@ __global__ __launch_bounds__(256) void k_base_stream(const typename BsT<V>::In* 
         }
     } else {
         if (ybeg >= h) return;
-        for (int off = 32; off > 0; off >>= 1) m = bsm_max(m, __shfl_xor(m, off));
+        for (int off = 32; off > 0; off >>= 1) m = vmax(m, __shfl_xor(m, off));
         if (lane == 0) {
             if constexpr (std::is_same<V, float>::value) {
                 if (m > 0.f) atomicMax(&state[im].hmax_bits, __float_as_uint(m));        // lattice maximum (akazed.cu:827-877)

@@ -28,9 +28,7 @@
 
 // reduce accumulator rows [0, nrows) of the table in the reference's order:
 // b_t = a_t + a_{t+32}; tree over t with strides 1,2,4,8,16; lane c owns row c
-__device__ __forceinline__ float dsc_add(float a, float b) { return a + b; }
-__device__ __forceinline__ int dsc_add(int a, int b) { return (int)((unsigned)a + (unsigned)b); }    // wraps like the reference
-__device__ __forceinline__ int dsc_mul(int a, int b) { return (int)((unsigned)a * (unsigned)b); }
+// (sums through vadd, pixel_rules.h: int wraps like the reference)
 
 // dFastAtan2, akazed.cu:173-185 (0/0 -> 0)
 __device__ __forceinline__ float dsc_fast_atan2(float yv, float xv)
@@ -78,11 +76,11 @@ __device__ __forceinline__ void reduce_rows(const V* acc, V* vals, int nrows, in
 #pragma unroll 1
         for (int k = 0; k < 4; k++) {
             const V* q = a + 8 * k;
-            const V b0 = dsc_add(q[0], q[32]), b1 = dsc_add(q[1], q[33]), b2 = dsc_add(q[2], q[34]), b3 = dsc_add(q[3], q[35]);
-            const V b4 = dsc_add(q[4], q[36]), b5 = dsc_add(q[5], q[37]), b6 = dsc_add(q[6], q[38]), b7 = dsc_add(q[7], q[39]);
-            c[k] = dsc_add(dsc_add(dsc_add(b0, b1), dsc_add(b2, b3)), dsc_add(dsc_add(b4, b5), dsc_add(b6, b7)));
+            const V b0 = vadd(q[0], q[32]), b1 = vadd(q[1], q[33]), b2 = vadd(q[2], q[34]), b3 = vadd(q[3], q[35]);
+            const V b4 = vadd(q[4], q[36]), b5 = vadd(q[5], q[37]), b6 = vadd(q[6], q[38]), b7 = vadd(q[7], q[39]);
+            c[k] = vadd(vadd(vadd(b0, b1), vadd(b2, b3)), vadd(vadd(b4, b5), vadd(b6, b7)));
         }
-        vals[out_base + lane] = dsc_add(dsc_add(c[0], c[1]), dsc_add(c[2], c[3]));
+        vals[out_base + lane] = vadd(vadd(c[0], c[1]), vadd(c[2], c[3]));
     }
 }
 
@@ -146,10 +144,10 @@ __global__ __launch_bounds__(64) void k_orient(const V* __restrict__ base, long 
                 const int dx = (dv[1][2] - dv[1][0]) >> 1, dy = (dv[2][1] - dv[0][1]) >> 1;
                 const int dxx = dv[1][2] + dv[1][0] - v2, dyy = dv[2][1] + dv[0][1] - v2;
                 const int dxy = (dv[2][2] + dv[0][0] - dv[0][2] - dv[2][0]) >> 2;
-                const int dd = dsc_add(dsc_mul(dxx, dyy), -dsc_mul(dxy, dxy));
+                const int dd = vadd(vmul(dxx, dyy), -vmul(dxy, dxy));
                 const float idd = dd != 0 ? (1.f / dd) : 0.f;
-                const float dst0 = idd * dsc_add(dsc_mul(dxy, dy), -dsc_mul(dyy, dx));
-                const float dst1 = idd * dsc_add(dsc_mul(dxy, dx), -dsc_mul(dxx, dy));
+                const float dst0 = idd * vadd(vmul(dxy, dy), -vmul(dyy, dx));
+                const float dst1 = idd * vadd(vmul(dxy, dx), -vmul(dxx, dy));
                 if (!(dst0 < -1.f || dst0 > 1.f || dst1 < -1.f || dst1 > 1.f)) {
                     const int ratio = 1 << o;
                     pty = ratio * (y + dst1);
@@ -352,9 +350,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void k_
             for (int n = 0; n < MAX_SMP; n++) {
                 const unsigned e = (cellw[n] >> (8 * g)) & 0xFFu;
                 const bool cont = e & 0x80u;
-                rim = dsc_add(cont ? rim : V(0), vim[n]);
-                rrx = dsc_add(cont ? rrx : V(0), vrx[n]);
-                rry = dsc_add(cont ? rry : V(0), vry[n]);
+                rim = vadd(cont ? rim : V(0), vim[n]);
+                rrx = vadd(cont ? rrx : V(0), vrx[n]);
+                rry = vadd(cont ? rry : V(0), vry[n]);
                 const unsigned rr = (e & 0x7Fu) - (unsigned)row0;    // 0x7F (no row) lies beyond every window
                 if (((cellw[n] >> (24 + g)) & 1u) && rr < (unsigned)nrows) {
                     V* a = acc + rr * ACC_LD + lane;
@@ -558,9 +556,9 @@ __global__ __launch_bounds__(64) void k_describe(const V* __restrict__ base, lon
             auto add = [&](int row, V im, V rx, V ry) {
                 const int rr = row - r0;
                 if (rr >= 0 && rr < ACC_ROWS) {
-                    acc[rr * ACC_LD + lane] = dsc_add(acc[rr * ACC_LD + lane], im);
-                    acc[(rr + 1) * ACC_LD + lane] = dsc_add(acc[(rr + 1) * ACC_LD + lane], rx);
-                    acc[(rr + 2) * ACC_LD + lane] = dsc_add(acc[(rr + 2) * ACC_LD + lane], ry);
+                    acc[rr * ACC_LD + lane] = vadd(acc[rr * ACC_LD + lane], im);
+                    acc[(rr + 1) * ACC_LD + lane] = vadd(acc[(rr + 1) * ACC_LD + lane], rx);
+                    acc[(rr + 2) * ACC_LD + lane] = vadd(acc[(rr + 2) * ACC_LD + lane], ry);
                 }
             };
             auto scatter = [&](int x, int y, V im, V rx, V ry) {

@@ -245,7 +245,7 @@ static void launch_multi(hipStream_t st, const V* src, const V* flow, V* dst, lo
     FedFacs<V, NS> fac;
     for (int k = 0; k < NS; k++) {
         if constexpr (std::is_same<V, float>::value) fac.f[k] = 0.5f * tau[k];      // akazed.cu:2515
-        else fac.f[k] = (int)(0.5f * tau[k] * 65536 + 0.5f);                        // akazed.cu:4235
+        else fac.f[k] = hak_fix16(0.5f * tau[k]);                                   // akazed.cu:4235
     }
     constexpr int xv = fed_xv(NS);
     const int gx = (w + xv - 1) / xv;
@@ -287,15 +287,37 @@ int hak_fed_group_size(int n, int G, int g)
     return ns;
 }
 
+// ---- the FAST path's single step for widths without 16-byte rows (fastakaze::gNldStepNaive akazed.cu:3448): one pixel per lane on
+// 64 x 16 tiles, the four flux products and the step of fed_common.h's vstep in wrapping int32
+__global__ __launch_bounds__(256) void kf_nld_step(const int* __restrict__ src, const int* __restrict__ flow, int* __restrict__ dst,
+                                                   long stride, int w, int h, int p, int stepfac)
+{
+    const int* s = src + (long)blockIdx.z * stride;
+    const int* f = flow + (long)blockIdx.z * stride;
+    int* d = dst + (long)blockIdx.z * stride;
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y0 = blockIdx.y * 16 + (threadIdx.x >> 6);
+    if (x >= w) return;
+    const int x0 = x - 1 < 0 ? 1 - x : x - 1, x2 = x + 1 < w ? x + 1 : w + w - 3 - x;
+    for (int y = y0; y < blockIdx.y * 16 + 16 && y < h; y += 4) {
+        const long r0 = (long)(y - 1 < 0 ? 1 - y : y - 1) * p, r1 = (long)y * p, r2 = (long)(y + 1 < h ? y + 1 : h + h - 3 - y) * p;
+        const int L = s[r1 + x], F = f[r1 + x];
+        const int sum = vadd(vadd(vadd(vmul(F + f[r1 + x2], s[r1 + x2] - L), vmul(F + f[r1 + x0], s[r1 + x0] - L)),
+                                  vmul(F + f[r2 + x], s[r2 + x] - L)), vmul(F + f[r0 + x], s[r0 + x] - L));
+        d[r1 + x] = vstep(stepfac, sum, L);                                                       // akazed.cu:3468-3469
+    }
+}
+
 // ns fused steps src -> dst (dst != src), tau[0..ns); ns must be 1 when w % 4 != 0 (one step per launch: k_fed_generic, or the
-// FAST path's kf_nld_step of kernels_fast.hip).  int: fastakaze::hNldStep, akazed.cu:4231-4238, 16.16 steps
+// FAST path's kf_nld_step).  int: fastakaze::hNldStep, akazed.cu:4231-4238, 16.16 steps
 template <typename V>
 static void launch_fed_group_t(hipStream_t st, const V* src, const V* flow, V* dst, long stride,
                                int w, int h, int p, int nimg, const float* tau, int ns)
 {
     if (w % 4 != 0) {
-        if constexpr (std::is_same<V, int>::value) hakf_launch_nld_step(st, src, flow, dst, stride, w, h, p, nimg, tau[0]);
-        else {
+        if constexpr (std::is_same<V, int>::value) {
+            const int stepfac = hak_fix16(0.5f * tau[0]);                                          // akazed.cu:4237
+            kf_nld_step<<<dim3((w + 63) / 64, (h + 15) / 16, nimg), 256, 0, st>>>(src, flow, dst, stride, w, h, p, stepfac);
+        } else {
             const int gx = (w + 247) / 248;
             int ry = 16;
             while (ry > 2 && (long)gx * ((h + ry - 1) / ry) * nimg < 2048) ry >>= 1;

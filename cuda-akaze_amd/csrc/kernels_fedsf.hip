@@ -120,7 +120,7 @@ __device__ __forceinline__ void fs_iter(FsState<V, NS>& S, const int t, const V*
         }
         Px rp;
 #pragma unroll
-        for (int j = 0; j < W; j++) rp.e[j] = sf_conv(a[j + 2], a[j + 1], a[j + 3], a[j], a[j + 4], kk);
+        for (int j = 0; j < W; j++) rp.e[j] = hak_conv5(a[j + 2], a[j + 1], a[j + 3], a[j], a[j + 4], kk);
         S.Rp[pmod(U, 6)] = rp;
         if (YEDGE) {
             // selects on values, not conditional stores: two adjacent `if (t == ..) ring[slot] = rp` are merged by the optimiser
@@ -143,7 +143,7 @@ __device__ __forceinline__ void fs_iter(FsState<V, NS>& S, const int t, const V*
         const Px u2 = S.Rp[pmod(U - 4, 6)], d2 = S.Rp[pmod(U, 6)];
         Px sm;
 #pragma unroll
-        for (int j = 0; j < W; j++) sm.e[j] = sf_conv(c.e[j], u1.e[j], d1.e[j], u2.e[j], d2.e[j], kk);
+        for (int j = 0; j < W; j++) sm.e[j] = hak_conv5(c.e[j], u1.e[j], d1.e[j], u2.e[j], d2.e[j], kk);
         if constexpr (WRITE_SM)
             px_buf_store_nt(O.r, O.smo + (a >= ybeg && a < yend ? (unsigned)(a * p) * (unsigned)sizeof(V) : HAK_BUF_OOB), sm);
         V sl = wave_shr1(sm.e[W - 1]), sr = wave_shl1(sm.e[0]);
@@ -175,9 +175,9 @@ __device__ __forceinline__ void fs_iter(FsState<V, NS>& S, const int t, const V*
         bool fast = true;
 #pragma unroll
         for (int j = 0; j < W; j++) {
-            const V dx = 10 * (sc[j + 2] - sc[j]) + 3 * (su[j + 2] + sd[j + 2] - su[j] - sd[j]);
-            const V dy = 10 * (sd[j + 1] - su[j + 1]) + 3 * (sd[j] + sd[j + 2] - su[j] - su[j + 2]);
-            den[j] = 1.f + sf_dif2(dx, dy, ikc);
+            V dx, dy;
+            hak_scharr(su[j], su[j + 1], su[j + 2], sc[j], sc[j + 2], sd[j], sd[j + 1], sd[j + 2], dx, dy);
+            den[j] = 1.f + hak_dif2(dx, dy, ikc);
             fast = fast && den[j] < 0x1p64f;
         }
         // g = 1 / den: the 3-instruction reciprocal is bit-identical to the IEEE division on [1, 2^64) (fed_common.h); a wave
@@ -185,10 +185,10 @@ __device__ __forceinline__ void fs_iter(FsState<V, NS>& S, const int t, const V*
         Px g;
         if (__ballot(!fast) == 0ull) {
 #pragma unroll
-            for (int j = 0; j < W; j++) g.e[j] = sf_g_as<V>(hak_rcp_newton(den[j]));
+            for (int j = 0; j < W; j++) g.e[j] = hak_g_as<V>(hak_rcp_newton(den[j]));
         } else {
 #pragma unroll
-            for (int j = 0; j < W; j++) g.e[j] = sf_g_as<V>(1.f / den[j]);
+            for (int j = 0; j < W; j++) g.e[j] = hak_g_as<V>(1.f / den[j]);
         }
         if (WRITE_G) px_buf_store_nt(O.r, O.go + (tf >= ybeg && tf < yend ? (unsigned)(tf * p) * (unsigned)sizeof(V) : HAK_BUF_OOB), g);
         S.GH[pmod(U, GS)] = fed_gh(g);
@@ -326,7 +326,7 @@ void launch_fs(hipStream_t st, const V* src, V* smooth, V* flow, V* dst, long st
     FedFacs<V, NS> fac;
     for (int k = 0; k < NS; k++) {
         if constexpr (std::is_same<V, float>::value) fac.f[k] = 0.5f * tau[k];      // akazed.cu:2515
-        else fac.f[k] = (int)(0.5f * tau[k] * 65536 + 0.5f);                        // akazed.cu:4235
+        else fac.f[k] = hak_fix16(0.5f * tau[k]);                                   // akazed.cu:4235
     }
     const int hx = fs_hx_for(NS, w);
     const int gx = fs_strips(NS, hx, w);

@@ -310,8 +310,6 @@ __global__ __launch_bounds__(64 * HF_NW) void k_hessian_fused(const V* __restric
     }
 }
 
-static void deriv_factors(float& fac1, float& fac2) { hak_deriv_factors(&fac1, &fac2); }
-
 // HakKnobs::hess_stream: 0 never / 1 by size / 2 always.  HakKnobs::hess_cbuf: staged candidates per block actually used
 // (1..HF_CBUF); HAK_HESS_CBUF shrinks it so that the tests can drive the overflow path of the staging buffer with ordinary images.
 
@@ -319,11 +317,8 @@ template <typename V, int S>
 static void launch_fused(hipStream_t st, const V* src, V* dxy, V* det, long stride,
                          int w, int h, int p, int nimg, const HakExtremaArgs<V>& ex, int cbuf_cap)
 {
-    float f1, f2;
-    deriv_factors(f1, f2);
     V v1, v2;
-    if constexpr (std::is_same<V, float>::value) { v1 = f1; v2 = f2; }
-    else { v1 = (int)(f1 * 65536 + 0.5f); v2 = (int)(f2 * 65536 + 0.5f); }      // akazed.cu:4183-4184
+    hak_deriv_factors_as(v1, v2);
     const int ntx = (w + HF_TX - 1) / HF_TX, nty = (h + HessGeo<S>::TY - 1) / HessGeo<S>::TY;
     // tiles per persistent block: long runs while the grid still covers the chip several times
     int tpb = 8;
@@ -345,12 +340,11 @@ static bool launch_hessian_level_t(hipStream_t st, const V* src, V* dxy, V* det,
     // register-streaming kernel (kernels_hessian_stream.hip) when it covers the case; HAK_HESS_STREAM=0 forces the tile kernel
     const HakKnobs kn = hak_knobs_of(b);
     if (lp_taps || hak_stream_pays(kn.hess_stream, w, h, nimg)) {
-        float f1, f2;
-        deriv_factors(f1, f2);
+        V f1, f2;
+        hak_deriv_factors_as(f1, f2);
         bool streamed;
-        if constexpr (fast)                                                     // akazed.cu:4183-4184; no LP variant
-            streamed = hak_launch_hessian_stream(st, src, dxy, det, store_det, stride, w, h, p, nimg, step, (int)(f1 * 65536 + 0.5f),
-                                                 (int)(f2 * 65536 + 0.5f), b, L, htab, octave, sub, threshold);
+        if constexpr (fast)                                                     // no LP variant
+            streamed = hak_launch_hessian_stream(st, src, dxy, det, store_det, stride, w, h, p, nimg, step, f1, f2, b, L, htab, octave, sub, threshold);
         else
             streamed = hak_launch_hessian_stream(st, src, dxy, det, store_det, stride, w, h, p, nimg, step, f1, f2, b, L, htab, octave, sub,
                                                  threshold, lp_taps);
@@ -372,11 +366,8 @@ static bool launch_hessian_level_t(hipStream_t st, const V* src, V* dxy, V* det,
     default: break;
     }
     // dilation > 4: direct passes, the determinant goes to `det`
-    if constexpr (fast) hakf_launch_hessian(st, src, dxy, det, stride, w, h, p, nimg, step);        // kf_derivate + kf_hessian
-    else {
-        hak_launch_derivate(st, src, dxy, stride, w, h, p, nimg, step);
-        hak_launch_hessian(st, dxy, det, stride, w, h, p, nimg, step);
-    }
+    hak_launch_derivate(st, src, dxy, stride, w, h, p, nimg, step);
+    hak_launch_hessian(st, dxy, det, stride, w, h, p, nimg, step);
     return false;
 }
 

@@ -255,10 +255,10 @@ __device__ __forceinline__ void hs_iter(HsState<V, S, LP>& T, const int t, const
                 r2.w = re ? c.y : r2.w;                         // column w+1 -> w-3
             }
             V4 rp;
-            rp.x = sf_conv(c.x, l1.x, r1.x, l2.x, r2.x, kk);
-            rp.y = sf_conv(c.y, l1.y, r1.y, l2.y, r2.y, kk);
-            rp.z = sf_conv(c.z, l1.z, r1.z, l2.z, r2.z, kk);
-            rp.w = sf_conv(c.w, l1.w, r1.w, l2.w, r2.w, kk);
+            rp.x = hak_conv5(c.x, l1.x, r1.x, l2.x, r2.x, kk);
+            rp.y = hak_conv5(c.y, l1.y, r1.y, l2.y, r2.y, kk);
+            rp.z = hak_conv5(c.z, l1.z, r1.z, l2.z, r2.z, kk);
+            rp.w = hak_conv5(c.w, l1.w, r1.w, l2.w, r2.w, kk);
             T.Rp[pmod(U + 2, R)] = rp;
             if (YEDGE) {                                        // (selects on values: see kernels_fedsf.hip)
                 T.Rp[pmod(U, R)] = vsel4(r == 1, rp, T.Rp[pmod(U, R)]);                              // row -1 := row 1
@@ -271,10 +271,10 @@ __device__ __forceinline__ void hs_iter(HsState<V, S, LP>& T, const int t, const
             const V4 c = T.Rp[pmod(U, R)], u1 = T.Rp[pmod(U - 1, R)], d1 = T.Rp[pmod(U + 1, R)];
             const V4 u2 = T.Rp[pmod(U - 2, R)], d2 = T.Rp[pmod(U + 2, R)];
             V4 sm;
-            sm.x = sf_conv(c.x, u1.x, d1.x, u2.x, d2.x, kk);
-            sm.y = sf_conv(c.y, u1.y, d1.y, u2.y, d2.y, kk);
-            sm.z = sf_conv(c.z, u1.z, d1.z, u2.z, d2.z, kk);
-            sm.w = sf_conv(c.w, u1.w, d1.w, u2.w, d2.w, kk);
+            sm.x = hak_conv5(c.x, u1.x, d1.x, u2.x, d2.x, kk);
+            sm.y = hak_conv5(c.y, u1.y, d1.y, u2.y, d2.y, kk);
+            sm.z = hak_conv5(c.z, u1.z, d1.z, u2.z, d2.z, kk);
+            sm.w = hak_conv5(c.w, u1.w, d1.w, u2.w, d2.w, kk);
             T.A[pmod(U, R)] = sm;
         }
     }

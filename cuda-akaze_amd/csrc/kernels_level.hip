@@ -14,7 +14,7 @@
 // valid window shrinking by one pixel per step; a thread works on four pixels of a row at a time (16-byte LDS accesses).  One launch per sublevel: 94 -> 43 launches per image.
 //
 // Bit-exactness: every expression is the reference's (and the oracle's) own -- no regrouping: the separable Gaussian through
-// sf_conv, the Scharr / conductivity of k_smooth_flow, and  step = tE + tW + tS + tN  then  fma(stepfac, step, L)  with the
+// hak_conv5, the Scharr / conductivity of k_smooth_flow, and  step = tE + tW + tS + tN  then  fma(stepfac, step, L)  with the
 // neighbours taken at reflect-101 INDICES (abs / borderAdd, akazed.cu:1251-1254), never from mirrored halo cells: a mirrored
 // cell would add its N and S terms in the other order.  The raw tile alone is loaded through mirrored indices (on the
 // source extents for an octave head, akazed.cu:466-494), which is what the Gaussian's taps read.
@@ -37,29 +37,6 @@ template <typename V> struct LvHess {
 };
 
 namespace {
-
-// source index of decimated coordinate d (tile coordinates may lie outside the image): 2d mirrored on the SOURCE extent
-__device__ __forceinline__ int lv_src_index(int d, int sn)
-{
-    int i = 2 * d;
-    i = i < 0 ? -i : i;
-    i = i < sn ? i : sn + sn - 2 - i;                        // borderAdd on the source (akazed.cu:466, 490)
-    i = i < 0 ? 0 : i;
-    return i < sn ? i : sn - 1;                              // (beyond one reflection: never used)
-}
-
-template <typename V>
-__device__ __forceinline__ float lv_conductivity(V dx, V dy, float ikc, int type)
-{
-    const float dif2 = sf_dif2(dx, dy, ikc);
-    if (type == HAK_PM_G2) return 1.f / (1.f + dif2);
-    if (type == HAK_PM_G1) return hak_expf(-dif2);
-    if (type == HAK_WEICKERT) {
-        const float d2 = dif2 * dif2;
-        return 1.f - hak_expf(-3.315f / (d2 * d2));
-    }
-    return 1.f / sqrtf(1.f + dif2);
-}
 
 // ---- four pixels per thread: a thread owns one 16-byte group of a plane row per item, so a stencil row costs one ds_read_b128
 // plus the two edge words instead of six ds_read_b32, and the index arithmetic is paid once per four pixels (the scalar version
@@ -122,8 +99,8 @@ __global__ __launch_bounds__(LV_NT) void k_level_tile(const V* __restrict__ src,
         const int x = X0 + c, y = Y0 + r;
         V4 v;
         if (HEAD && FIRST) {
-            const V* row = s + (long)lv_src_index(y, sh) * sp;
-            v = mk4(row[lv_src_index(x, sw)], row[lv_src_index(x + 1, sw)], row[lv_src_index(x + 2, sw)], row[lv_src_index(x + 3, sw)]);
+            const V* row = s + (long)hak_refl(2 * y, sh) * sp;
+            v = mk4(row[hak_refl(2 * x, sw)], row[hak_refl(2 * (x + 1), sw)], row[hak_refl(2 * (x + 2), sw)], row[hak_refl(2 * (x + 3), sw)]);
         } else {
             const V* row = s + (long)hak_refl(y, h) * p;
             if (x >= 0 && x + 3 < w) v = *reinterpret_cast<const V4*>(row + x);
@@ -139,8 +116,8 @@ __global__ __launch_bounds__(LV_NT) void k_level_tile(const V* __restrict__ src,
             if (g >= 1 && g < NG - 1) {
                 const V* q = A + r * EW + c;
                 const V4 l = *reinterpret_cast<const V4*>(q - 4), m = *reinterpret_cast<const V4*>(q), rr = *reinterpret_cast<const V4*>(q + 4);
-                *reinterpret_cast<V4*>(B + r * EW + c) = mk4(sf_conv(m.x, l.w, m.y, l.z, m.z, t), sf_conv(m.y, m.x, m.z, l.w, m.w, t),
-                                                            sf_conv(m.z, m.y, m.w, m.x, rr.x, t), sf_conv(m.w, m.z, rr.x, m.y, rr.y, t));
+                *reinterpret_cast<V4*>(B + r * EW + c) = mk4(hak_conv5(m.x, l.w, m.y, l.z, m.z, t), hak_conv5(m.y, m.x, m.z, l.w, m.w, t),
+                                                            hak_conv5(m.z, m.y, m.w, m.x, rr.x, t), hak_conv5(m.w, m.z, rr.x, m.y, rr.y, t));
             }
         }
         hak_lds_barrier();
@@ -151,8 +128,8 @@ __global__ __launch_bounds__(LV_NT) void k_level_tile(const V* __restrict__ src,
                 const V* q = B + r * EW + c;
                 const V4 m = *reinterpret_cast<const V4*>(q), u1 = *reinterpret_cast<const V4*>(q - EW), d1 = *reinterpret_cast<const V4*>(q + EW);
                 const V4 u2 = *reinterpret_cast<const V4*>(q - 2 * EW), d2 = *reinterpret_cast<const V4*>(q + 2 * EW);
-                const V4 ws = mk4(sf_conv(m.x, u1.x, d1.x, u2.x, d2.x, t), sf_conv(m.y, u1.y, d1.y, u2.y, d2.y, t),
-                                  sf_conv(m.z, u1.z, d1.z, u2.z, d2.z, t), sf_conv(m.w, u1.w, d1.w, u2.w, d2.w, t));
+                const V4 ws = mk4(hak_conv5(m.x, u1.x, d1.x, u2.x, d2.x, t), hak_conv5(m.y, u1.y, d1.y, u2.y, d2.y, t),
+                                  hak_conv5(m.z, u1.z, d1.z, u2.z, d2.z, t), hak_conv5(m.w, u1.w, d1.w, u2.w, d2.w, t));
                 *reinterpret_cast<V4*>(C + r * EW + c) = ws;
                 const int x = X0 + c, y = Y0 + r;
                 if (r >= HY && r < HY + T && c >= HX && c < HX + T && y < h) {
@@ -217,9 +194,9 @@ __global__ __launch_bounds__(LV_NT) void k_level_tile(const V* __restrict__ src,
                 const V ul = lv_left(U, j, x), uc = U.v[j + 1], ur = lv_right(U, j, x, w);
                 const V cl = lv_left(M, j, x), cr = lv_right(M, j, x, w);
                 const V ll = lv_left(D, j, x), lc = D.v[j + 1], lr = lv_right(D, j, x, w);
-                const V dx = 10 * (cr - cl) + 3 * (ur + lr - ul - ll);
-                const V dy = 10 * (lc - uc) + 3 * (ll + lr - ul - ur);
-                gq[j] = sf_g_as<V>(lv_conductivity<V>(dx, dy, ikc, type));
+                V dx, dy;
+                hak_scharr(ul, uc, ur, cl, cr, ll, lc, lr, dx, dy);
+                gq[j] = hak_g_as<V>(hak_conductivity(hak_dif2(dx, dy, ikc), type));
             }
             *reinterpret_cast<V4*>(B + r * EW + c) = mk4(gq[0], gq[1], gq[2], gq[3]);
         }
@@ -326,7 +303,7 @@ void launch_level(hipStream_t st, const V* src, V* smooth, V* dst, long stride, 
     for (int k = 0; k < LV_MAX_STEPS; k++) {
         const float tk = k < ns ? tau[k] : 0.f;
         if constexpr (std::is_same<V, float>::value) fac.f[k] = 0.5f * tk;              // akazed.cu:2515
-        else fac.f[k] = (int)(0.5f * tk * 65536 + 0.5f);                                // akazed.cu:4235
+        else fac.f[k] = hak_fix16(0.5f * tk);                                           // akazed.cu:4235
     }
     // the largest tile (multiple of 8, at most 64) whose three planes fit the LDS budget
     const int HX = (ns + 5 + 3) & ~3;                      // (as in the kernel)
@@ -386,10 +363,7 @@ LvHess<V> level_hess(V* dxy, int step, int first_ns, const HakBatch* b, const Ha
     // size rule sends here, at the demo schedule); the caller launches the Hessian kernel otherwise
     *fused = b != nullptr && dxy != nullptr && step >= 1 && first_ns >= 2 * step;
     if (!*fused) return hs;
-    float f1, f2;
-    hak_deriv_factors(&f1, &f2);
-    if constexpr (std::is_same<V, float>::value) { hs.fac1 = f1; hs.fac2 = f2; }
-    else { hs.fac1 = (int)(f1 * 65536 + 0.5f); hs.fac2 = (int)(f2 * 65536 + 0.5f); }     // akazed.cu:4183-4184
+    hak_deriv_factors_as(hs.fac1, hs.fac2);
     hs.dxy = dxy; hs.S = step;
     hs.ex = hak_extrema_args<V>(b, L, htab, octave, sub, threshold);
     return hs;

@@ -1,49 +1,64 @@
-// kernels_scalespace.hip -- nonlinear scale space for gfx950 (CDNA4, wave64).
+// kernels_scalespace.hip -- nonlinear scale space for gfx950 (CDNA4, wave64), both pipelines: V = float (akaze) and V = int
+// (fastakaze, akazed.cu:2781-4367: int32 planes, 16.16 fixed-point weights, uint8 input).
 //
-// Stages (reference wrapper -> kernel here):
-//   hLowPass/gConv2d<R>            akazed.cu:2336, 204   -> k_lowpass<R>
-//   hDownWithSmooth                akazed.cu:2389, 449   -> k_down_smooth
-//   hScharrContrast                akazed.cu:2410, 644, 827, 901 -> k_grad_max, k_grad_hist, k_kcontrast
-//   hFlow/gFlowNaive               akazed.cu:2487, 1068  -> k_flow
-//   hNldStep/gNldStepNaive         akazed.cu:2509, 1241  -> kernels_fed.hip (the FED hot loop)
-//   hHessianDeterminant            akazed.cu:2531, 1267, 1299 -> k_derivate, k_hessian
+// Stages (reference wrapper -> kernel here; fastakaze lines after the slash):
+//   hLowPass/gConv2d<R>            akazed.cu:2336, 204 / 2990, 2786, 2922  -> k_lowpass<In, V, R>
+//   hDownWithSmooth                akazed.cu:2389, 449 / 3143              -> k_down_smooth<V>
+//   hScharrContrast                akazed.cu:2410, 644, 827, 901 / 3208-3336, 4101-4162 -> k_grad_max<V>, k_grad_hist<V>, k_kcontrast<V>
+//   hFlow/gFlowNaive               akazed.cu:2487, 1068 / 3406             -> k_flow<V>
+//   hNldStep/gNldStepNaive         akazed.cu:2509, 1241 / 3448             -> kernels_fed.hip (the FED hot loop)
+//   hHessianDeterminant            akazed.cu:2531, 1267, 1299 / 3339, 3371 -> k_derivate<V>, k_hessian<V>
 //
-// All kernels take the batch image in blockIdx.z.  Float evaluation order is
-// the reference's source order (no contraction: built with -ffp-contract=off);
+// All kernels take the batch image in blockIdx.z.  The arithmetic of every pixel is pixel_rules.h: float evaluation order is
+// the reference's source order (no contraction: built with -ffp-contract=off), int32 products wrap as in the oracle;
 // the only fused op is the explicit fmaf of the FED step (akazed.cu:1263).
 #include "hak_internal.h"
 
 #define TILE_X 64
 #define TILE_Y 16
 
-struct HakTaps { float k[8]; };
+// what differs between the pipelines and is not arithmetic: the taps as a kernel argument, and the state field that takes the
+// lattice maximum with the smallest value that may raise it (the float field is floored at 0.03f, the int one at 1: k_reset_state)
+template <typename V> struct SsT;
+template <> struct SsT<float> {
+    struct Taps { float k[8]; };
+    static __device__ __forceinline__ void raise_max(HakImgState* st, float m) { if (m > 0.f) atomicMax(&st->hmax_bits, __float_as_uint(m)); }
+};
+template <> struct SsT<int> {
+    struct Taps { int k[8]; };
+    static __device__ __forceinline__ void raise_max(HakImgState* st, int m) { if (m > 1) atomicMax(&st->ihmax, m); }
+};
+template <typename V> static typename SsT<V>::Taps ss_taps(const V* taps, int R)
+{
+    typename SsT<V>::Taps t;
+    for (int i = 0; i < 8; i++) t.k[i] = i <= R ? taps[i] : V(0);
+    return t;
+}
+static dim3 ss_grid(int w, int h, int nimg) { return dim3((w + TILE_X - 1) / TILE_X, (h + TILE_Y - 1) / TILE_Y, nimg); }
 
 // ------------------------------------------------------------------ lowpass
 // Separable Gaussian, reflect-101.  One 64x16 output tile per 256-thread
-// block: raw tile (+R halo) -> LDS, row pass -> LDS, column pass -> HBM.
-template <int R>
-__global__ __launch_bounds__(256) void k_lowpass(const float* __restrict__ src, long src_stride, int sp,
-                                                 float* __restrict__ dst, long dst_stride,
-                                                 int w, int h, int p, HakTaps taps)
+// block: raw tile (+R halo) -> LDS, row pass -> LDS, column pass -> HBM.  In = float, or uint8 / int for int planes
+template <typename In, typename V, int R>
+__global__ __launch_bounds__(256) void k_lowpass(const In* __restrict__ src, long src_stride, int sp,
+                                                 V* __restrict__ dst, long dst_stride,
+                                                 int w, int h, int p, typename SsT<V>::Taps taps)
 {
     constexpr int RW = TILE_X + 2 * R, RH = TILE_Y + 2 * R;
-    __shared__ float raw[RH][RW + 1];
-    __shared__ float rowp[RH][TILE_X];
-    const float* s = src + (long)blockIdx.z * src_stride;
-    float* d = dst + (long)blockIdx.z * dst_stride;
+    __shared__ V raw[RH][RW + 1];
+    __shared__ V rowp[RH][TILE_X];
+    const In* s = src + (long)blockIdx.z * src_stride;
+    V* d = dst + (long)blockIdx.z * dst_stride;
     const int x0 = blockIdx.x * TILE_X, y0 = blockIdx.y * TILE_Y, tid = threadIdx.x;
 
     for (int i = tid; i < RH * RW; i += 256) {
         int r = i / RW, c = i - r * RW;
-        raw[r][c] = s[(long)hak_refl(y0 - R + r, h) * sp + hak_refl(x0 - R + c, w)];
+        raw[r][c] = (V)s[(long)hak_refl(y0 - R + r, h) * sp + hak_refl(x0 - R + c, w)];
     }
     __syncthreads();
     for (int i = tid; i < RH * TILE_X; i += 256) {
         int r = i >> 6, c = i & 63;
-        float ws = raw[r][c + R] * taps.k[0];
-#pragma unroll
-        for (int k = 1; k <= R; k++) ws += taps.k[k] * (raw[r][c + R - k] + raw[r][c + R + k]);
-        rowp[r][c] = ws;
+        rowp[r][c] = hak_conv<R>(taps.k, [&](int k) { return raw[r][c + R + k]; });
     }
     __syncthreads();
     const int c = tid & 63, x = x0 + c;
@@ -51,60 +66,58 @@ __global__ __launch_bounds__(256) void k_lowpass(const float* __restrict__ src, 
     for (int rr = tid >> 6; rr < TILE_Y; rr += 4) {
         int y = y0 + rr;
         if (y >= h) break;
-        float ws = rowp[rr + R][c] * taps.k[0];
-#pragma unroll
-        for (int k = 1; k <= R; k++) ws += taps.k[k] * (rowp[rr + R - k][c] + rowp[rr + R + k][c]);
-        d[(long)y * p + x] = ws;
+        d[(long)y * p + x] = hak_conv<R>(taps.k, [&](int k) { return rowp[rr + R + k][c]; });
     }
 }
 
-void hak_launch_lowpass(hipStream_t st, const float* src, long src_stride, int src_pitch, float* dst, long dst_stride,
-                        int w, int h, int p, int nimg, const float* taps, int R)
+template <typename In, typename V>
+static void launch_lowpass_t(hipStream_t st, const In* src, long src_stride, int src_pitch, V* dst, long dst_stride,
+                             int w, int h, int p, int nimg, const V* taps, int R)
 {
-    HakTaps t;
-    for (int i = 0; i < 8; i++) t.k[i] = i <= R ? taps[i] : 0.f;
-    dim3 grid((w + TILE_X - 1) / TILE_X, (h + TILE_Y - 1) / TILE_Y, nimg);
+    const typename SsT<V>::Taps t = ss_taps<V>(taps, R);
+    const dim3 grid = ss_grid(w, h, nimg);
     switch (R) {
-    case 2: k_lowpass<2><<<grid, 256, 0, st>>>(src, src_stride, src_pitch, dst, dst_stride, w, h, p, t); break;
-    case 3: k_lowpass<3><<<grid, 256, 0, st>>>(src, src_stride, src_pitch, dst, dst_stride, w, h, p, t); break;
-    case 4: k_lowpass<4><<<grid, 256, 0, st>>>(src, src_stride, src_pitch, dst, dst_stride, w, h, p, t); break;
-    default: k_lowpass<5><<<grid, 256, 0, st>>>(src, src_stride, src_pitch, dst, dst_stride, w, h, p, t); break;
+    case 2: k_lowpass<In, V, 2><<<grid, 256, 0, st>>>(src, src_stride, src_pitch, dst, dst_stride, w, h, p, t); break;
+    case 3: k_lowpass<In, V, 3><<<grid, 256, 0, st>>>(src, src_stride, src_pitch, dst, dst_stride, w, h, p, t); break;
+    case 4: k_lowpass<In, V, 4><<<grid, 256, 0, st>>>(src, src_stride, src_pitch, dst, dst_stride, w, h, p, t); break;
+    default: k_lowpass<In, V, 5><<<grid, 256, 0, st>>>(src, src_stride, src_pitch, dst, dst_stride, w, h, p, t); break;
     }
 }
+void hak_launch_lowpass(hipStream_t st, const float* src, long src_stride, int src_pitch, float* dst, long dst_stride,
+                        int w, int h, int p, int nimg, const float* taps, int R)
+{ launch_lowpass_t(st, src, src_stride, src_pitch, dst, dst_stride, w, h, p, nimg, taps, R); }
+void hak_launch_lowpass(hipStream_t st, const unsigned char* src, long src_stride, int src_pitch, int* dst, long dst_stride,
+                        int w, int h, int p, int nimg, const int* taps, int R)
+{ launch_lowpass_t(st, src, src_stride, src_pitch, dst, dst_stride, w, h, p, nimg, taps, R); }
+void hak_launch_lowpass(hipStream_t st, const int* src, long src_stride, int src_pitch, int* dst, long dst_stride,
+                        int w, int h, int p, int nimg, const int* taps, int R)
+{ launch_lowpass_t(st, src, src_stride, src_pitch, dst, dst_stride, w, h, p, nimg, taps, R); }
 
 // ------------------------------------------------------------ down + smooth
 // dst = src[2y][2x]; smooth = G(sigma=1, R=2) on the decimated lattice with the
 // mirror taken on the SOURCE extents (akazed.cu:466, 477-494).
-__device__ __forceinline__ int refl_src(int i, int m)
-{
-    i = i < 0 ? -i : i;
-    i = i < m ? i : m + m - 2 - i;
-    i = i < 0 ? 0 : i;
-    return i < m ? i : m - 1;
-}
-
-__global__ __launch_bounds__(256) void k_down_smooth(const float* __restrict__ src, float* __restrict__ dst,
-                                                     float* __restrict__ smooth, long stride,
-                                                     HakOct so, HakOct dd, HakTaps taps)
+template <typename V>
+__global__ __launch_bounds__(256) void k_down_smooth(const V* __restrict__ src, V* __restrict__ dst,
+                                                     V* __restrict__ smooth, long stride,
+                                                     HakOct so, HakOct dd, typename SsT<V>::Taps taps)
 {
     constexpr int RW = TILE_X + 4, RH = TILE_Y + 4;
-    __shared__ float dec[RH][RW + 1];
-    __shared__ float rowp[RH][TILE_X];
-    const float* s = src + (long)blockIdx.z * stride;
-    float* d = dst + (long)blockIdx.z * stride;
-    float* sm = smooth + (long)blockIdx.z * stride;
+    __shared__ V dec[RH][RW + 1];
+    __shared__ V rowp[RH][TILE_X];
+    const V* s = src + (long)blockIdx.z * stride;
+    V* d = dst + (long)blockIdx.z * stride;
+    V* sm = smooth + (long)blockIdx.z * stride;
     const int x0 = blockIdx.x * TILE_X, y0 = blockIdx.y * TILE_Y, tid = threadIdx.x;
 
     for (int i = tid; i < RH * RW; i += 256) {
         int r = i / RW, c = i - r * RW;
-        int sy = refl_src(2 * (y0 - 2 + r), so.h), sx = refl_src(2 * (x0 - 2 + c), so.w);
+        int sy = hak_refl(2 * (y0 - 2 + r), so.h), sx = hak_refl(2 * (x0 - 2 + c), so.w);
         dec[r][c] = s[(long)sy * so.p + sx];
     }
     __syncthreads();
     for (int i = tid; i < RH * TILE_X; i += 256) {
         int r = i >> 6, c = i & 63;
-        rowp[r][c] = taps.k[0] * dec[r][c + 2] + taps.k[1] * (dec[r][c + 1] + dec[r][c + 3]) +
-                     taps.k[2] * (dec[r][c] + dec[r][c + 4]);
+        rowp[r][c] = hak_conv<2>(taps.k, [&](int k) { return dec[r][c + 2 + k]; });
     }
     __syncthreads();
     const int c = tid & 63, x = x0 + c;
@@ -114,49 +127,34 @@ __global__ __launch_bounds__(256) void k_down_smooth(const float* __restrict__ s
         if (y >= dd.h) break;
         long o = (long)y * dd.p + x;
         d[o] = dec[rr + 2][c + 2];
-        sm[o] = taps.k[0] * rowp[rr + 2][c] + taps.k[1] * (rowp[rr + 1][c] + rowp[rr + 3][c]) +
-                taps.k[2] * (rowp[rr][c] + rowp[rr + 4][c]);
+        sm[o] = hak_conv<2>(taps.k, [&](int k) { return rowp[rr + 2 + k][c]; });
     }
 }
 
+template <typename V>
+static void launch_down_smooth_t(hipStream_t st, const V* src, V* dst, V* smooth, long stride, HakOct so, HakOct dd, int nimg, const V* taps)
+{
+    k_down_smooth<V><<<ss_grid(dd.w, dd.h, nimg), 256, 0, st>>>(src, dst, smooth, stride, so, dd, ss_taps<V>(taps, 2));
+}
 void hak_launch_down_smooth(hipStream_t st, const float* src, float* dst, float* smooth, long stride,
                             HakOct so, HakOct dd, int nimg, const float* taps)
-{
-    HakTaps t;
-    for (int i = 0; i < 8; i++) t.k[i] = i <= 2 ? taps[i] : 0.f;
-    dim3 grid((dd.w + TILE_X - 1) / TILE_X, (dd.h + TILE_Y - 1) / TILE_Y, nimg);
-    k_down_smooth<<<grid, 256, 0, st>>>(src, dst, smooth, stride, so, dd, t);
-}
+{ launch_down_smooth_t(st, src, dst, smooth, stride, so, dd, nimg, taps); }
+void hak_launch_down_smooth(hipStream_t st, const int* src, int* dst, int* smooth, long stride,
+                            HakOct so, HakOct dd, int nimg, const int* taps)
+{ launch_down_smooth_t(st, src, dst, smooth, stride, so, dd, nimg, taps); }
 
 // ------------------------------------------------------- Scharr + contrast
-// un-normalised Scharr pair of akazed.cu:664-665 / 1088-1089
-__device__ __forceinline__ void scharr_dxdy(const float* __restrict__ s, int x, int y, int w, int h, int p,
-                                            float& dx, float& dy)
-{
-    int x0 = x - 1 < 0 ? 1 - x : x - 1;
-    int x2 = x + 1 < w ? x + 1 : w + w - 3 - x;
-    int y0 = y - 1 < 0 ? 1 - y : y - 1;
-    int y2 = y + 1 < h ? y + 1 : h + h - 3 - y;
-    const float* r0 = s + (long)y0 * p;
-    const float* r1 = s + (long)y * p;
-    const float* r2 = s + (long)y2 * p;
-    float ul = r0[x0], uc = r0[x], ur = r0[x2];
-    float cl = r1[x0], cr = r1[x2];
-    float ll = r2[x0], lc = r2[x], lr = r2[x2];
-    dx = 10 * (cr - cl) + 3 * (ur + lr - ul - ll);
-    dy = 10 * (lc - uc) + 3 * (ll + lr - ul - ur);
-}
-
+// every field of the image state either pipeline uses
 __global__ __launch_bounds__(256) void k_reset_state(HakImgState* state)
 {
     HakImgState* st = state + blockIdx.x;
     for (int i = threadIdx.x; i < HAK_NBINS; i += 256) st->hist[i] = 0;
     if (threadIdx.x == 0) {
         st->hmax_bits = __float_as_uint(0.03f);        // akazed.cu:2413
+        st->ihmax = 1;                                 // akazed.cu:4101
         st->ncand = 0;
         st->total_pts = 0;
         st->num_pts = 0;
-        st->hist_done = 0;
     }
 }
 
@@ -165,150 +163,136 @@ void hak_launch_reset_state(hipStream_t st, HakImgState* state, int nimg)
     k_reset_state<<<nimg, 256, 0, st>>>(state);
 }
 
-// pass 1: maximum gradient magnitude over the 16-px lattice (what gFindMaxContrastU4 delivers, hak_internal.h)
-__global__ __launch_bounds__(256) void k_grad_max(const float* __restrict__ smooth, long stride, int w, int h, int p,
+// pass 1: maximum gradient magnitude over the 16-px lattice (what gFindMaxContrastU4 delivers, hak_internal.h; akazed.cu:3245-3296)
+template <typename V>
+__global__ __launch_bounds__(256) void k_grad_max(const V* __restrict__ smooth, long stride, int w, int h, int p,
                                                   HakImgState* state)
 {
-    const float* s = smooth + (long)blockIdx.z * stride;
+    const V* s = smooth + (long)blockIdx.z * stride;
     const int x = blockIdx.x * TILE_X + (threadIdx.x & 63);
     const int y0 = blockIdx.y * TILE_Y + (threadIdx.x >> 6);
-    float m = 0.f;
+    V m = 0;
     if (x < w)
         for (int y = y0; y < blockIdx.y * TILE_Y + TILE_Y && y < h; y += 4) {
             if (!hak_on_lattice(x, y, w, h)) continue;
-            float dx, dy;
-            scharr_dxdy(s, x, y, w, h, p, dx, dy);
-            m = fmaxf(m, sqrtf(dx * dx + dy * dy));
+            V dx, dy;
+            hak_scharr_at(s, x, y, w, h, p, dx, dy);
+            m = vmax(m, hak_grad_mag(dx, dy));
         }
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-    if ((threadIdx.x & 63) == 0 && m > 0.f) atomicMax(&state[blockIdx.z].hmax_bits, __float_as_uint(m));
+    for (int o = 32; o > 0; o >>= 1) m = vmax(m, __shfl_xor(m, o));
+    if ((threadIdx.x & 63) == 0) SsT<V>::raise_max(state + blockIdx.z, m);
 }
 
 // pass 2: 300-bin histogram, gradient recomputed (cheaper than storing it)
-__global__ __launch_bounds__(256) void k_grad_hist(const float* __restrict__ smooth, long stride, int w, int h, int p,
+template <typename V>
+__global__ __launch_bounds__(256) void k_grad_hist(const V* __restrict__ smooth, long stride, int w, int h, int p,
                                                    HakImgState* state)
 {
     __shared__ int shist[HAK_NBINS];
     for (int i = threadIdx.x; i < HAK_NBINS; i += 256) shist[i] = 0;
     __syncthreads();
-    const float* s = smooth + (long)blockIdx.z * stride;
-    const float hmax = __uint_as_float(state[blockIdx.z].hmax_bits);
-    const float hfactor = HAK_NBINS / hmax;                       // akazed.cu:2450
+    const V* s = smooth + (long)blockIdx.z * stride;
+    const auto hfactor = hak_hist_factor(hak_state_hmax<V>(state + blockIdx.z));
     const int x = blockIdx.x * TILE_X + (threadIdx.x & 63);
     const int y0 = blockIdx.y * TILE_Y + (threadIdx.x >> 6);
     if (x < w)
         for (int y = y0; y < blockIdx.y * TILE_Y + TILE_Y && y < h; y += 4) {
-            float dx, dy;
-            scharr_dxdy(s, x, y, w, h, p, dx, dy);
-            float g = sqrtf(dx * dx + dy * dy);
-            // (int)__fmul_rz(g, factor): exact double product, truncated (akazed.cu:924)
-            int hi = (int)((double)g * (double)hfactor);
-            hi = hi >= HAK_NBINS ? HAK_NBINS - 1 : hi;
-            atomicAdd(&shist[hi], 1);
+            V dx, dy;
+            hak_scharr_at(s, x, y, w, h, p, dx, dy);
+            atomicAdd(&shist[hak_hist_bin(hak_grad_mag(dx, dy), hfactor)], 1);
         }
     __syncthreads();
     for (int i = threadIdx.x; i < HAK_NBINS; i += 256)
         if (shist[i]) atomicAdd(&state[blockIdx.z].hist[i], shist[i]);
 }
 
-// host half of hScharrContrast (akazed.cu:2467-2481) + the per-octave 0.75 decay
-// (akaze.cpp:371) and ikc = 1/(k*k) (akazed.cu:2493), kept on the device.
+// host half of hScharrContrast, kept on the device (hak_finish_kcontrast, pixel_rules.h)
+template <typename V>
 __global__ void k_kcontrast(HakImgState* state, int npix, int extra0, float per, int noct)
 {
-    HakImgState* st = state + blockIdx.x;
     if (threadIdx.x != 0) return;
-    const float hmax = __uint_as_float(st->hmax_bits);
-    const float hfactor = HAK_NBINS / hmax;
-    int thresh = (int)((npix - (st->hist[0] + extra0)) * per);
-    int cumuv = 0, k = 1;
-    while (k < HAK_NBINS) {
-        if (cumuv >= thresh) break;
-        cumuv += st->hist[k];
-        k++;
-    }
-    float kc = k / hfactor;
-    for (int o = 0; o < noct; o++) {
-        if (o > 0) kc *= 0.75f;
-        st->kcontrast[o] = kc;
-        st->ikc[o] = 1.f / (kc * kc);
-    }
+    hak_finish_kcontrast<V>(state + blockIdx.x, state[blockIdx.x].hist, npix, extra0, per, noct);
 }
 
+template <typename V>
+static void launch_contrast_t(hipStream_t st, const V* smooth, long stride, int w, int h, int p, int nimg,
+                              HakImgState* state, float per, int noct)
+{
+    const dim3 grid = ss_grid(w, h, nimg);
+    k_grad_max<V><<<grid, 256, 0, st>>>(smooth, stride, w, h, p, state);
+    k_grad_hist<V><<<grid, 256, 0, st>>>(smooth, stride, w, h, p, state);
+    k_kcontrast<V><<<nimg, 64, 0, st>>>(state, w * h, hak_hist_extra0(w, h), per, noct);
+}
 void hak_launch_contrast(hipStream_t st, const float* smooth, long stride, int w, int h, int p, int nimg,
                          HakImgState* state, float per, int noct)
-{
-    dim3 grid((w + TILE_X - 1) / TILE_X, (h + TILE_Y - 1) / TILE_Y, nimg);
-    k_grad_max<<<grid, 256, 0, st>>>(smooth, stride, w, h, p, state);
-    k_grad_hist<<<grid, 256, 0, st>>>(smooth, stride, w, h, p, state);
-    k_kcontrast<<<nimg, 64, 0, st>>>(state, w * h, hak_hist_extra0(w, h), per, noct);
-}
+{ launch_contrast_t(st, smooth, stride, w, h, p, nimg, state, per, noct); }
+void hak_launch_contrast(hipStream_t st, const int* smooth, long stride, int w, int h, int p, int nimg,
+                         HakImgState* state, float per, int noct)
+{ launch_contrast_t(st, smooth, stride, w, h, p, nimg, state, per, noct); }
 
 // --------------------------------------------------------------------- flow
-__global__ __launch_bounds__(256) void k_flow(const float* __restrict__ src, float* __restrict__ dst, long stride,
+template <typename V>
+__global__ __launch_bounds__(256) void k_flow(const V* __restrict__ src, V* __restrict__ dst, long stride,
                                               int w, int h, int p, int type, const HakImgState* state, int octave,
                                               float fixed_ikc)
 {
-    const float* s = src + (long)blockIdx.z * stride;
-    float* d = dst + (long)blockIdx.z * stride;
+    const V* s = src + (long)blockIdx.z * stride;
+    V* d = dst + (long)blockIdx.z * stride;
     const float ikc = state ? state[blockIdx.z].ikc[octave] : fixed_ikc;
     const int x = blockIdx.x * TILE_X + (threadIdx.x & 63);
     const int y0 = blockIdx.y * TILE_Y + (threadIdx.x >> 6);
     if (x >= w) return;
     for (int y = y0; y < blockIdx.y * TILE_Y + TILE_Y && y < h; y += 4) {
-        float dx, dy;
-        scharr_dxdy(s, x, y, w, h, p, dx, dy);
-        float dif2 = ikc * (dx * dx + dy * dy);
-        float g;
-        if (type == HAK_PM_G2) g = 1.f / (1.f + dif2);
-        else if (type == HAK_PM_G1) g = hak_expf(-dif2);
-        else if (type == HAK_WEICKERT) {
-            float d2 = dif2 * dif2;
-            g = 1.f - hak_expf(-3.315f / (d2 * d2));
-        } else g = 1.f / sqrtf(1.f + dif2);
-        d[(long)y * p + x] = g;
+        V dx, dy;
+        hak_scharr_at(s, x, y, w, h, p, dx, dy);
+        d[(long)y * p + x] = hak_g_as<V>(hak_conductivity(hak_dif2(dx, dy, ikc), type));
     }
 }
 
 void hak_launch_flow(hipStream_t st, const float* src, float* dst, long stride, int w, int h, int p, int nimg,
                      int diffusivity, const HakImgState* state, int octave, float fixed_ikc)
-{
-    dim3 grid((w + TILE_X - 1) / TILE_X, (h + TILE_Y - 1) / TILE_Y, nimg);
-    k_flow<<<grid, 256, 0, st>>>(src, dst, stride, w, h, p, diffusivity, state, octave, fixed_ikc);
-}
+{ k_flow<float><<<ss_grid(w, h, nimg), 256, 0, st>>>(src, dst, stride, w, h, p, diffusivity, state, octave, fixed_ikc); }
+void hak_launch_flow(hipStream_t st, const int* src, int* dst, long stride, int w, int h, int p, int nimg,
+                     int diffusivity, const HakImgState* state, int octave)
+{ k_flow<int><<<ss_grid(w, h, nimg), 256, 0, st>>>(src, dst, stride, w, h, p, diffusivity, state, octave, 0.f); }
 
 // ------------------------------------------------- derivatives + determinant
 // unfused fallback for dilations > 4 and the debug / test planes: dxy = interleaved {Lx, Ly} (HakLayout)
-__global__ __launch_bounds__(256) void k_derivate(const float* __restrict__ src, float* __restrict__ dxy, long stride, int w, int h, int p,
-                                                  int step, float fac1, float fac2)
+template <typename V>
+__global__ __launch_bounds__(256) void k_derivate(const V* __restrict__ src, V* __restrict__ dxy, long stride, int w, int h, int p,
+                                                  int step, V fac1, V fac2)
 {
-    const float* s = src + (long)blockIdx.z * stride;
-    float2* o = reinterpret_cast<float2*>(dxy + (long)blockIdx.z * stride);
+    const V* s = src + (long)blockIdx.z * stride;
+    V* o = dxy + (long)blockIdx.z * stride;
     const int x = blockIdx.x * TILE_X + (threadIdx.x & 63);
     const int y0 = blockIdx.y * TILE_Y + (threadIdx.x >> 6);
     if (x >= w) return;
     const int x0 = hak_refl(x - step, w), x2 = hak_refl(x + step, w);
     for (int y = y0; y < blockIdx.y * TILE_Y + TILE_Y && y < h; y += 4) {
-        const float* r0 = s + (long)hak_refl(y - step, h) * p;
-        const float* r1 = s + (long)y * p;
-        const float* r2 = s + (long)hak_refl(y + step, h) * p;
-        float ul = r0[x0], uc = r0[x], ur = r0[x2];
-        float cl = r1[x0], cr = r1[x2];
-        float ll = r2[x0], lc = r2[x], lr = r2[x2];
-        o[(long)y * p + x] = make_float2(fac1 * (ur + lr - ul - ll) + fac2 * (cr - cl),        // akazed.cu:1294
-                                         fac1 * (lr + ll - ur - ul) + fac2 * (lc - uc));       // akazed.cu:1295
+        const V* r0 = s + (long)hak_refl(y - step, h) * p;
+        const V* r1 = s + (long)y * p;
+        const V* r2 = s + (long)hak_refl(y + step, h) * p;
+        V ul = r0[x0], uc = r0[x], ur = r0[x2];
+        V cl = r1[x0], cr = r1[x2];
+        V ll = r2[x0], lc = r2[x], lr = r2[x2];
+        typedef V V2 __attribute__((ext_vector_type(2)));
+        const V2 v = {hs_d(fac1, fac2, ur + lr - ul - ll, cr - cl),        // akazed.cu:1294
+                      hs_d(fac1, fac2, lr + ll - ur - ul, lc - uc)};       // akazed.cu:1295
+        *reinterpret_cast<V2*>(o + 2 * ((long)y * p + x)) = v;
     }
 }
 
-__global__ __launch_bounds__(256) void k_hessian(const float* __restrict__ dxy, float* __restrict__ det, long stride, int w, int h, int p,
-                                                 int step, float fac1, float fac2)
+template <typename V>
+__global__ __launch_bounds__(256) void k_hessian(const V* __restrict__ dxy, V* __restrict__ det, long stride, int w, int h, int p,
+                                                 int step, V fac1, V fac2)
 {
-    const float* d = dxy + (long)blockIdx.z * stride;
-    float* o = det + (long)blockIdx.z * stride;
+    const V* d = dxy + (long)blockIdx.z * stride;
+    V* o = det + (long)blockIdx.z * stride;
     const int x = blockIdx.x * TILE_X + (threadIdx.x & 63);
     const int y0 = blockIdx.y * TILE_Y + (threadIdx.x >> 6);
     if (x >= w) return;
     for (int y = y0; y < blockIdx.y * TILE_Y + TILE_Y && y < h; y += 4)
-        o[(long)y * p + x] = hak_det_at<float>(d, x, y, step, w, h, p, fac1, fac2);             // akazed.cu:1318-1330
+        o[(long)y * p + x] = hak_det_at<V>(d, x, y, step, w, h, p, fac1, fac2);                 // akazed.cu:1318-1330
 }
 
 void hak_deriv_factors(float* fac1, float* fac2)
@@ -318,23 +302,28 @@ void hak_deriv_factors(float* fac1, float* fac2)
     *fac2 = wv * *fac1;
 }
 
-void hak_launch_derivate(hipStream_t st, const float* src, float* dxy, long stride,
-                         int w, int h, int p, int nimg, int step)
+template <typename V>
+static void launch_derivate_t(hipStream_t st, const V* src, V* dxy, long stride, int w, int h, int p, int nimg, int step)
 {
-    float f1, f2;
-    hak_deriv_factors(&f1, &f2);
-    dim3 grid((w + TILE_X - 1) / TILE_X, (h + TILE_Y - 1) / TILE_Y, nimg);
-    k_derivate<<<grid, 256, 0, st>>>(src, dxy, stride, w, h, p, step, f1, f2);
+    V f1, f2;
+    hak_deriv_factors_as(f1, f2);
+    k_derivate<V><<<ss_grid(w, h, nimg), 256, 0, st>>>(src, dxy, stride, w, h, p, step, f1, f2);
 }
-
-void hak_launch_hessian(hipStream_t st, const float* dxy, float* det, long stride,
-                        int w, int h, int p, int nimg, int step)
+template <typename V>
+static void launch_hessian_t(hipStream_t st, const V* dxy, V* det, long stride, int w, int h, int p, int nimg, int step)
 {
-    float f1, f2;
-    hak_deriv_factors(&f1, &f2);
-    dim3 grid((w + TILE_X - 1) / TILE_X, (h + TILE_Y - 1) / TILE_Y, nimg);
-    k_hessian<<<grid, 256, 0, st>>>(dxy, det, stride, w, h, p, step, f1, f2);
+    V f1, f2;
+    hak_deriv_factors_as(f1, f2);
+    k_hessian<V><<<ss_grid(w, h, nimg), 256, 0, st>>>(dxy, det, stride, w, h, p, step, f1, f2);
 }
+void hak_launch_derivate(hipStream_t st, const float* src, float* dxy, long stride, int w, int h, int p, int nimg, int step)
+{ launch_derivate_t(st, src, dxy, stride, w, h, p, nimg, step); }
+void hak_launch_derivate(hipStream_t st, const int* src, int* dxy, long stride, int w, int h, int p, int nimg, int step)
+{ launch_derivate_t(st, src, dxy, stride, w, h, p, nimg, step); }
+void hak_launch_hessian(hipStream_t st, const float* dxy, float* det, long stride, int w, int h, int p, int nimg, int step)
+{ launch_hessian_t(st, dxy, det, stride, w, h, p, nimg, step); }
+void hak_launch_hessian(hipStream_t st, const int* dxy, int* det, long stride, int w, int h, int p, int nimg, int step)
+{ launch_hessian_t(st, dxy, det, stride, w, h, p, nimg, step); }
 
 // interleaved {a, b} plane (pitch 2p) -> two dense planes (pitch p): stage tests and hak_debug_plane only
 __global__ __launch_bounds__(256) void k_deinterleave(const float2* __restrict__ ab, float* __restrict__ a, float* __restrict__ b,

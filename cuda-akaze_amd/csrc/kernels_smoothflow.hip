@@ -24,7 +24,7 @@
 #define SF_NPF ((SF_RW * SF_RH + 255) / 256)
 
 // Shared by both pipelines: V = float (akaze) and V = int (fastakaze, 16.16 fixed point: every pass of the separable
-// Gaussian ends in >> 16 (akazed.cu:2922-2985) and the conductivity is stored as (int)(g * 65536 + 0.5f), akazed.cu:3444).
+// Gaussian ends in >> 16 (akazed.cu:2922-2985) and the conductivity is stored in 16.16, akazed.cu:3444; rules: pixel_rules.h).
 template <typename V>
 __device__ __forceinline__ void sf_fetch(V (&pf)[SF_NPF], const V* __restrict__ s, int w, int h, int p,
                                          int x0, int y0, int tid)
@@ -71,7 +71,7 @@ __global__ __launch_bounds__(256) void k_smooth_flow(const V* __restrict__ src, 
         for (int idx = tid; idx < SF_RH * SF_PW; idx += 256) {
             const int r = idx / SF_PW, c = idx - r * SF_PW;
             const V* q = raw + r * SF_RW + c + 2;           // raw column of image column x0-1+c is c+2
-            rowp[idx] = sf_conv(q[0], q[-1], q[1], q[-2], q[2], t);
+            rowp[idx] = hak_conv5(q[0], q[-1], q[1], q[-2], q[2], t);
         }
         hak_lds_barrier();
         // ---- column pass (akazed.cu:283-288) -> smooth tile (halo 1) in LDS, centre -> HBM
@@ -79,7 +79,7 @@ __global__ __launch_bounds__(256) void k_smooth_flow(const V* __restrict__ src, 
         for (int idx = tid; idx < SF_SH * SF_PW; idx += 256) {
             const int r = idx / SF_PW, c = idx - r * SF_PW;
             const V* q = rowp + (r + 2) * SF_PW + c;        // rowp row of image row y0-1+r is r+2
-            const V ws = sf_conv(q[0], q[-SF_PW], q[SF_PW], q[-2 * SF_PW], q[2 * SF_PW], t);
+            const V ws = hak_conv5(q[0], q[-SF_PW], q[SF_PW], q[-2 * SF_PW], q[2 * SF_PW], t);
             sm[idx] = ws;
             const int x = x0 - 1 + c, y = y0 - 1 + r;
             if (c >= 1 && c <= SF_TX && r >= 1 && r <= SF_TY && x < w && y < h) osm[(long)y * p + x] = ws;
@@ -94,17 +94,9 @@ __global__ __launch_bounds__(256) void k_smooth_flow(const V* __restrict__ src, 
             const V ul = q[-SF_PW - 1], uc = q[-SF_PW], ur = q[-SF_PW + 1];
             const V cl = q[-1], cr = q[1];
             const V ll = q[SF_PW - 1], lc = q[SF_PW], lr = q[SF_PW + 1];
-            const V dx = 10 * (cr - cl) + 3 * (ur + lr - ul - ll);
-            const V dy = 10 * (lc - uc) + 3 * (ll + lr - ul - ur);
-            const float dif2 = sf_dif2(dx, dy, ikc);
-            float g;
-            if (type == HAK_PM_G2) g = 1.f / (1.f + dif2);
-            else if (type == HAK_PM_G1) g = hak_expf(-dif2);
-            else if (type == HAK_WEICKERT) {
-                float d2 = dif2 * dif2;
-                g = 1.f - hak_expf(-3.315f / (d2 * d2));
-            } else g = 1.f / sqrtf(1.f + dif2);
-            sf_store_g(og + (long)y * p + x, g);
+            V dx, dy;
+            hak_scharr(ul, uc, ur, cl, cr, ll, lc, lr, dx, dy);
+            og[(long)y * p + x] = hak_g_as<V>(hak_conductivity(hak_dif2(dx, dy, ikc), type));
         }
     }
 }

@@ -60,7 +60,7 @@ int hak_op_hessian(const float* d_src, float* d_lx, float* d_ly, float* d_det, i
  * hak_stream_pays) -- keep the two in step when a launcher's guard changes.
  *   route (hak_op_fast_base):    1 streaming prologue (k_base_stream), 2 tile prologue (kf_base), 3 unfused (the three launches
  *                                of the launch sequence where hak_launch_base_level does not cover the radius)
- *   route (hak_op_fast_hessian): 1 streaming (k_hessian_stream), 2 tile (k_hessian_fused), 3 dilation > 4 (kf_derivate + kf_hessian) */
+ *   route (hak_op_fast_hessian): 1 streaming (k_hessian_stream), 2 tile (k_hessian_fused), 3 dilation > 4 (k_derivate + k_hessian) */
 int hak_op_fast_conv_u8(const unsigned char* d_u8, int sp, int* d_dst, int w, int h, int p, float var, int radius);   /* gConv2d<R> 2990, gConv2dR2 2786 */
 int hak_op_fast_lowpass(const int* d_src, int* d_dst, int w, int h, int p, float var, int radius);                    /* gConv2dR2 (int) 2922 */
 /* the octave-0 prologue (akaze.cpp:589-623): Lt(0,0) = the base Gaussian (var_base, radius) of the image, and the contrast factor,

@@ -11,7 +11,7 @@ case $FILE in kernels_fed.hip|kernels_fedsf.hip|kernels_base_stream.hip|kernels_
 O=$(mktemp /tmp/hakvar_XXXX.o)
 (cd $C && /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -Wall -Wno-unused-result $NOSLP "$@" -c $FILE -o $O)
 OBJS=""
-for f in hak_api kernels_scalespace kernels_base kernels_base_stream kernels_fed kernels_fedsf kernels_level kernels_smoothflow kernels_hessian kernels_hessian_stream kernels_detect kernels_fast kernels_describe kernels_match; do
+for f in hak_api kernels_scalespace kernels_base kernels_base_stream kernels_fed kernels_fedsf kernels_level kernels_smoothflow kernels_hessian kernels_hessian_stream kernels_detect kernels_describe kernels_match; do
   if [ "$f.hip" = "$FILE" ]; then OBJS="$OBJS $O"; else OBJS="$OBJS $C/$f.o"; fi
 done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o $R/build/ab/libhak_$NAME.so $OBJS
