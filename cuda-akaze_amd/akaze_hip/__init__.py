@@ -132,6 +132,11 @@ SYMBOLS = {
     "hak_match_guided_batch": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp]),
     "hak_match_epipolar": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _fp, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _ip, _vp]),
     "hak_match_epipolar_batch": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp]),
+    "hak_match_projected": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _fp, _vp, C.c_float, C.c_int, C.c_int, C.c_int,
+                                      C.c_int, _vp, _ip, _vp]),
+    "hak_match_projected_batch": (C.c_int, [_vp, _vp, C.c_long, _vp, C.c_int, _vp, _vp, _vp, C.c_long, _vp, C.c_int, _vp, C.c_long, _vp, C.c_int,
+                                            C.c_int, _vp, C.c_int, C.c_int, _vp, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_long,
+                                            _vp]),
     "hak_points_alloc": (C.c_int, [C.POINTER(_vp), C.c_int]),
     "hak_points_free": (C.c_int, [_vp]),
     "hak_image_alloc": (C.c_int, [C.POINTER(_vp), C.c_int, C.c_int, _ip]),
@@ -802,6 +807,40 @@ def linkTracks(matchesA, xyzA, matchesB, maskA=None, max_index=None, akazer=None
     count = C.c_int(0)
     check(lib.hak_link_tracks(ctx, d_a.data_ptr(), na, d_mask.data_ptr() if d_mask is not None else None, d_xyz.data_ptr(),
                               d_b.data_ptr(), nb, int(max_index), d_out.data_ptr(), C.byref(count), out.ctypes.data))
+    return out[:count.value].copy()
+
+
+def matchProjected(matchesA, xyzA, result_desc, result2, view, K, radius=8.0, ratio=(4, 5), cross_check=True, max_dist=0, maskA=None,
+                   akazer=None):
+    """Projection-guided matching (hipakaze.h hak_match_projected): re-matches 3-D points against the keypoints of a new image under
+    its known pose, on the device.  `matchesA`: the match list the points came from, as findHomography's (only `train` is read: the
+    keypoint of result_desc whose descriptor stands for the landmark); xyzA: its points, (nA, 3) float32 (recoverPose's or
+    triangulate's); maskA: nA bytes or None; result_desc, result2: AkazeData of the image `train` indexes and of the new image;
+    `view`: the new image's pose in the forms triangulate accepts (None, twelve floats {R row-major, t}, a POSE_DTYPE or an
+    ABS_POSE_DTYPE record); K as recoverPose's.  Every landmark is searched only among the keypoints of result2 within `radius`
+    pixels of its projection; ratio test and cross-check inside that neighbourhood.  Returns a CORR3D_DTYPE array in ascending
+    landmark order: src3d = the landmark's index in matchesA, src2d = the KEYPOINT index in result2.  A record view without a model
+    gives the empty list (step 7 of the rule, which needs no device)."""
+    import torch
+    ctx = _ctx_of(akazer)
+    d_a, na = _device_records(matchesA, MATCH_PAIR_DTYPE)
+    m, model = _host_view(view)
+    if not model:
+        return np.zeros(0, CORR3D_DTYPE)
+    d_xyz = xyzA.contiguous() if isinstance(xyzA, torch.Tensor) else torch.from_numpy(
+        np.ascontiguousarray(xyzA, np.float32).reshape(-1)).cuda() if na else torch.zeros(4, dtype=torch.float32, device="cuda")
+    d_mask = None
+    if maskA is not None:
+        d_mask = maskA.contiguous() if isinstance(maskA, torch.Tensor) else torch.from_numpy(
+            np.ascontiguousarray(maskA, np.uint8).reshape(-1)).cuda() if na else torch.zeros(4, dtype=torch.uint8, device="cuda")
+    k = intrinsics(K)
+    d_out = torch.zeros(max(na, 1) * CORR3D_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+    out = np.zeros(max(na, 1), CORR3D_DTYPE)
+    count = C.c_int(0)
+    check(lib.hak_match_projected(ctx, d_a.data_ptr(), na, d_mask.data_ptr() if d_mask is not None else None, d_xyz.data_ptr(),
+                                  result_desc.d_data, result_desc.num_pts, result2.d_data, result2.num_pts,
+                                  m.ctypes.data_as(_fp) if m is not None else None, k.ctypes.data, float(radius), int(ratio[0]),
+                                  int(ratio[1]), int(cross_check), int(max_dist), d_out.data_ptr(), C.byref(count), out.ctypes.data))
     return out[:count.value].copy()
 
 

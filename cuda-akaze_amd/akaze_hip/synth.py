@@ -11,6 +11,8 @@ two_view_matches(n_in, n_out, seed) -> (records, inlier flags, F_true): matches 
                      cameras with a known relative pose, plus uniformly random outlier records.
 three_view_scene(seed, n, noise_px, outlier_share) -> K, the two relative poses and the match lists of (I0, I1) and (I1, I2)
                      over shared keypoint indices of I1, for the track-linking and absolute-pose stages.
+three_view_keypoints(seed, n, noise_px, lookalike_share) -> the same cameras as three KEYPOINT sets with descriptors and
+                     look-alike keypoints in the third image, for projection-guided matching.
 """
 import numpy as np
 
@@ -296,6 +298,89 @@ def three_view_scene(seed, n, noise_px=0.0, outlier_share=0.0, angles01=(2.0, -5
     A, flagsA, pointA = matches(0, 1)
     B, flagsB, pointB = matches(1, 2)
     return K, (R01, t01), (R12, t12), A, B, flagsA, flagsB, X0[pointA], pointA.astype(np.int64), pointB.astype(np.int64)
+
+
+FLEN = 61                                                                   # descriptor bytes, 486 bits used
+POINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("octave", "<i4"), ("response", "<f4"), ("size", "<f4"), ("angle", "<f4"),
+                        ("features", "u1", (FLEN,)), ("_pad", "u1", (3,)),
+                        ("match", "<i4"), ("distance", "<i4"), ("match_x", "<f4"), ("match_y", "<f4")])      # hak_point
+
+
+def three_view_keypoints(seed, n, noise_px=0.5, lookalike_share=0.3, angles01=(2.0, -5.0, 1.5), t01=(-1.0, 0.05, 0.1),
+                         angles12=(-1.5, -4.0, 2.0), t12=(-0.9, -0.1, 0.25), w=1920, h=1080, focal=1500.0, depth=(4.0, 12.0),
+                         lookalike_images=(2,)):
+    """Three pinhole views of one point cloud as three KEYPOINT sets with descriptors, for the projection-guided matching tests and
+    the timing tool, built beside three_view_scene (its cameras, its cloud recipe, its 2 n keypoints per image), pure numpy.  (The
+    random draws are not three_view_scene's: the same seed gives another scene.)
+
+    n 3-D points that all three cameras see.  Every point has a base descriptor of 486 random bits; its keypoint in each image is
+    its projection, with `noise_px` of Gaussian noise, and carries the base with 5 .. 30 random bits flipped.  The other n keypoints
+    of an image are spurious: uniformly random positions, random descriptors.  For a share `lookalike_share` of the points, one
+    spurious keypoint of the THIRD image only is a look-alike: wherever it happens to lie, its descriptor is the point's base with
+    0 .. 35 bits flipped -- what makes a whole-image ratio test drop, or mismatch, the point there (lookalike_images = (0, 1, 2)
+    plants look-alikes, for a share of the points drawn per image, in every image).  Keypoints are in a random order.
+    -> (K (3, 3) float64, (R01, t01), (R12, t12), [pts0, pts1, pts2]: POINT_DTYPE arrays of 2 n records (match fields -1),
+        index: (3, n) int64, the keypoint of point j in image i, X0: (n, 3) float64, the points in the FIRST camera's frame,
+        lookalike: (n,) int64, the look-alike keypoint of point j in image 2, or -1)"""
+    rng = np.random.default_rng(seed)
+    K = np.array([[focal, 0.0, w / 2.0], [0.0, focal, h / 2.0], [0.0, 0.0, 1.0]])
+    R01, R12 = rotation_zyx(angles01), rotation_zyx(angles12)
+    t01, t12 = np.asarray(t01, np.float64).reshape(3), np.asarray(t12, np.float64).reshape(3)
+
+    def project(X):
+        q = X @ K.T
+        with np.errstate(all="ignore"):
+            return q[:, :2] / q[:, 2:]
+
+    def inside(X, p):
+        return (X[:, 2] > 0.5) & (p[:, 0] >= 0) & (p[:, 0] < w) & (p[:, 1] >= 0) & (p[:, 1] < h)
+
+    def flipped(base, lo, hi):
+        """every row of the (m, 486) bit array with lo .. hi of its bits flipped"""
+        out = base.copy()
+        for r in range(len(out)):
+            out[r, rng.choice(486, size=int(rng.integers(lo, hi + 1)), replace=False)] ^= 1
+        return out
+
+    X0 = np.zeros((0, 3))
+    for _ in range(400):                                                # rejection: keep the points all three cameras see
+        if len(X0) >= n:
+            break
+        m = 2 * n + 16
+        z = rng.uniform(depth[0], depth[1], m)
+        px = np.stack([rng.uniform(0, w, m), rng.uniform(0, h, m), np.ones(m)], axis=1)
+        X = (np.linalg.solve(K, px.T) * z).T
+        X1 = X @ R01.T + t01
+        X2 = X1 @ R12.T + t12
+        X0 = np.concatenate([X0, X[inside(X1, project(X1)) & inside(X2, project(X2))]])
+    assert len(X0) >= n, "the three cameras share too little of the scene"
+    X0 = X0[:n]
+    X1 = X0 @ R01.T + t01
+    X2 = X1 @ R12.T + t12
+    base = rng.integers(0, 2, size=(n, 486), dtype=np.uint8)
+    nlook = int(round(lookalike_share * n))
+    lookalike = np.full(n, -1, np.int64)
+    sets, index = [], []
+    for i, X in enumerate((X0, X1, X2)):
+        p = project(X)
+        if noise_px > 0.0:
+            p = p + rng.normal(0.0, noise_px, p.shape)
+        spurious = np.stack([rng.uniform(0, w, n), rng.uniform(0, h, n)], axis=1)
+        bits = np.concatenate([flipped(base, 5, 30), rng.integers(0, 2, size=(n, 486), dtype=np.uint8)])
+        order = rng.permutation(2 * n)                                  # keypoint index of point j: order[j]; spurious: order[n + j]
+        if i in lookalike_images and nlook:
+            who = rng.permutation(n)[:nlook]                            # spurious keypoint k looks like point who[k]
+            bits[n:n + nlook] = flipped(base[who], 0, 35)
+            if i == 2:
+                lookalike[who] = order[n:n + nlook]
+        pts = np.zeros(2 * n, POINT_DTYPE)
+        pts["x"][order], pts["y"][order] = np.concatenate([p, spurious]).T
+        pts["features"][order] = np.packbits(np.pad(bits, ((0, 0), (0, 2))), axis=1, bitorder="little")
+        pts["size"], pts["response"] = 4.0, 0.01
+        pts["match"], pts["distance"], pts["match_x"], pts["match_y"] = -1, -1, -1.0, -1.0
+        sets.append(pts)
+        index.append(order[:n].astype(np.int64))
+    return K, (R01, t01), (R12, t12), sets, np.stack(index), X0, lookalike
 
 
 def four_view_scene(seed, n, noise_px=0.0, outlier_share=0.0, angles01=(2.0, -5.0, 1.5), t01=(-1.0, 0.05, 0.1),

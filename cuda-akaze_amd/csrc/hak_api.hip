@@ -1241,6 +1241,96 @@ extern "C" int hak_match_epipolar_batch(hak_ctx* c, hak_point* d_points, const i
                              });
 }
 
+// ----------------------------------------------------------- projection-guided matching (kernels_projected.hip; the rule: include/hipakaze.h)
+static int projected_args(const hak_intrinsics* K, float radius, int ratio_num, int ratio_den)
+{
+    if (!K) return fail("null intrinsics");
+    return guided_args(radius, ratio_num, ratio_den) || intrinsics_args(K);
+}
+
+extern "C" int hak_match_projected(hak_ctx* c, const hak_match_pair* d_A, int nA, const unsigned char* d_maskA, const float* d_xyzA,
+                                   const hak_point* d_desc, int n_desc, const hak_point* d_pts2, int n2, const float* Rt,
+                                   const hak_intrinsics* K, float radius, int ratio_num, int ratio_den, int cross_check, int max_dist,
+                                   hak_corr3d* d_out, int* count, hak_corr3d* h_out)
+{
+    if (!count) return fail("null argument");
+    if (nA < 0 || n_desc < 0 || n2 < 0) return fail("negative count");
+    if (!hak_mkey_fits(nA) || !hak_mkey_fits(n_desc) || !hak_mkey_fits(n2)) return fail("more than 2^20 - 1 records");
+    if (((!d_A || !d_xyzA) && nA > 0) || (!d_desc && n_desc > 0) || (!d_pts2 && n2 > 0)) return fail("null array with a positive count");
+    if (h_out && !d_out) return fail("h_out needs d_out");
+    if (misaligned16(d_A) || misaligned16(d_out)) return fail("the lists must be 16-byte aligned");
+    if (projected_args(K, radius, ratio_num, ratio_den) || host_view_args(Rt)) return 1;
+    *count = 0;
+    if (nA == 0) return 0;
+    if (max_dist <= 0) max_dist = HAK_MAX_DIST;
+    if (hak_device_count() == 0) return fail("no HIP device: libhipakaze has no CPU fallback");
+    hipStream_t st = c ? c->stream : nullptr;
+    const long cap2 = n2 > 0 ? n2 : 1;
+    const size_t bytes = hak_guided_scratch_bytes(1, cap2);
+    void* buf = nullptr;
+    if (c) {
+        if (guided_scratch(c, bytes)) return 1;
+        buf = c->guided;
+    } else
+        HIP_TRY(hipMalloc(&buf, bytes));
+    HakMatchScratch* sc = c ? &c->msc : pool_acquire();
+    order_after_null_stream(c, st);
+    if (!hak_match_scratch_reserve(sc, st, 0, 0, 0, (long)nA + cap2, 1)) {
+        if (!c) { pool_release(sc, false); (void)hipFree(buf); }
+        return fail("hak_match_projected: out of device memory for the search scratch");
+    }
+    {
+        ProfScope ps(c, HAK_PROF_MATCH);
+        hak_launch_projected(st, d_A, nA, nullptr, 1, nA, nA, d_maskA, d_xyzA, d_desc, n_desc > 0 ? n_desc : 1, nullptr, 1, n_desc, n_desc,
+                             d_pts2, cap2, nullptr, 1, n2, 1, nullptr, HAK_VIEW_IDENTITY, 0, Rt, *K, radius, ratio_num, ratio_den,
+                             cross_check ? 1 : 0, max_dist, hak_guided_scratch_carve(buf, 1, cap2, sc->knn + nA, 0), sc->knn, 0, d_out, nA,
+                             sc->d_cnt);
+    }
+    int rc = single_tail(0, st, "hak_match_projected", "count download", count, sc->d_cnt, sizeof(int), c ? nullptr : buf);
+    if (!c) pool_release(sc, rc == 0);
+    if (!rc && h_out && *count > 0 &&
+        hipMemcpy(h_out, d_out, sizeof(hak_corr3d) * (size_t)*count, hipMemcpyDeviceToHost) != hipSuccess)
+        rc = fail("list download");
+    return rc;
+}
+
+extern "C" int hak_match_projected_batch(hak_ctx* c, const hak_match_pair* d_A, long strideA, const int* d_countsA, int count_stepA,
+                                         const unsigned char* d_masksA, const float* d_xyzA, const hak_point* d_desc, long desc_stride,
+                                         const int* d_desc_counts, int desc_count_step, const hak_point* d_pts2, long stride2,
+                                         const int* d_counts2, int count_step2, int npairs, const void* d_views, int kind, int view_step,
+                                         const hak_intrinsics* K, float radius, int ratio_num, int ratio_den, int cross_check,
+                                         int max_dist, hak_corr3d* d_out, long out_stride, int* d_counts)
+{
+    // the context is looked at last, so that every other refusal can be told from it
+    if (!d_A || !d_countsA || !d_xyzA || !d_desc || !d_desc_counts || !d_pts2 || !d_counts2 || !d_out || !d_counts)
+        return fail("null argument");
+    if (npairs < 1 || strideA < 1 || desc_stride < 1 || stride2 < 1 || out_stride < 1 || count_stepA < 1 || desc_count_step < 1 ||
+        count_step2 < 1)
+        return fail("npairs, the strides and the count steps must be >= 1");
+    if (misaligned16(d_A) || misaligned16(d_out)) return fail("the lists must be 16-byte aligned");
+    if (device_view_args(d_views, kind, view_step)) return 1;
+    if (projected_args(K, radius, ratio_num, ratio_den)) return 1;
+    if (!c) return fail("hak_match_projected_batch needs a context");
+    const long npair_cap = (c->cfg.batch + 1) / 2;
+    if (npairs > npair_cap) return fail("npairs exceeds the context's pair capacity");
+    if (max_dist <= 0) max_dist = HAK_MAX_DIST;
+    const long mp = c->cfg.max_pts;
+    if (!hak_mkey_fits(mp)) return fail("max_pts must stay below 2^20 for the matcher");
+    if (knn_scratch(c)) return 1;
+    if (guided_scratch(c, hak_guided_scratch_bytes(npair_cap, mp))) return 1;
+    order_after_null_stream(c, c->stream);
+    const long capA = std::min(std::min(strideA, out_stride), mp), capD = std::min(desc_stride, mp), cap2 = std::min(stride2, mp);
+    int4* fwd = c->knn;
+    int4* rev = c->knn + (size_t)npair_cap * mp;
+    { ProfScope ps(c, HAK_PROF_MATCH);
+      hak_launch_projected(c->stream, d_A, strideA, d_countsA, count_stepA, 0, capA, d_masksA, d_xyzA, d_desc, desc_stride, d_desc_counts,
+                           desc_count_step, 0, capD, d_pts2, stride2, d_counts2, count_step2, (int)cap2, npairs, d_views, kind, view_step,
+                           nullptr, *K, radius, ratio_num, ratio_den, cross_check ? 1 : 0, max_dist,
+                           hak_guided_scratch_carve(c->guided, npairs, cap2, rev, mp), fwd, mp, d_out, out_stride, d_counts); }
+    if (hipGetLastError() != hipSuccess) return fail("hak_match_projected_batch: launch failed");
+    return 0;
+}
+
 // ----------------------------------------------------------- memory helpers
 extern "C" int hak_points_alloc(hak_point** d, int count)
 {

@@ -746,11 +746,12 @@ __device__ __forceinline__ int gd_cell(float x, float o, float inv, int n)
 }
 size_t hak_guided_scratch_bytes(long npairs, long pts_cap);
 HakGuidedScratch hak_guided_scratch_carve(void* base, long npairs, long pts_cap, int4* rev, long rev_stride);
-// the two steps both gated searches share: the bin step (train points of npairs pairs into sc's grid of cells of side >= rp; resets
-// the reverse keys) and, after a search, the reverse step (reverse keys -> the records k_knn2_finish reads)
+// the two steps the gated searches share: the bin step (train points of npairs pairs into sc's grid of cells of side >= rp; resets
+// the reverse keys) and, after a search, the reverse step (reverse keys -> the records k_knn2_finish reads).  The count of pair k
+// is n2_dev[k * count_step]: 2 in a detect batch of image pairs
 void hak_launch_guided_bin(hipStream_t st, const hak_point* pts2, const int* n2_dev, int n2_host, long stride2, int npairs, float rp,
-                           const HakGuidedScratch& sc);
-void hak_launch_guided_rev(hipStream_t st, const int* n2_dev, int n2_host, int npairs, const HakGuidedScratch& sc);
+                           const HakGuidedScratch& sc, int count_step = 2);
+void hak_launch_guided_rev(hipStream_t st, const int* n2_dev, int n2_host, int npairs, const HakGuidedScratch& sc, int count_step = 2);
 void hak_launch_guided(hipStream_t st, const hak_point* pts1, const hak_point* pts2, const int* n1_dev, const int* n2_dev, int n1_host,
                        int n2_host, long stride1, long stride2, int npairs, const hak_homography* d_H, const float* h_H, float radius,
                        int cross, const HakGuidedScratch& sc, int4* fwd, long fwd_stride);
@@ -759,6 +760,19 @@ void hak_launch_guided(hipStream_t st, const hak_point* pts1, const hak_point* p
 void hak_launch_epipolar(hipStream_t st, const hak_point* pts1, const hak_point* pts2, const int* n1_dev, const int* n2_dev, int n1_host,
                          int n2_host, long stride1, long stride2, int npairs, const hak_fundamental* d_F, const float* h_F, float radius,
                          int cross, const HakGuidedScratch& sc, int4* fwd, long fwd_stride);
+// projection-guided matching (kernels_projected.hip, hak_match_projected): landmark m of list A (its point xyzA[3m ..], its descriptor
+// desc[A[m].train]) is projected through a view and K and searched among the train points pts2 near the projection; the same
+// scratch and the same bin and reverse steps as hak_launch_guided.  Counts on the device (countsA[k * stepA], desc_counts[k *
+// desc_step], counts2[k * step2]) or, NULL, the host values for the only list (with device counts n2_host carries the capacity of
+// a train set); capA / capD / sc.pts_cap: what the counts are clamped to.  The view of list k is record k * view_step of `views` (kind: HAK_VIEW_*), or h_view != NULL: these 12 host floats.  The
+// accepted landmarks go to out + k * out_stride in ascending m (out may be NULL: count only), their number to out_counts[k].
+void hak_launch_projected(hipStream_t st, const hak_match_pair* A, long strideA, const int* countsA, int stepA, int nA_host, long capA,
+                          const unsigned char* masksA, const float* xyzA, const hak_point* desc, long desc_stride,
+                          const int* desc_counts, int desc_step, int nD_host, long capD, const hak_point* pts2, long stride2,
+                          const int* counts2, int step2, int n2_host, int npairs, const void* views, int kind, int view_step,
+                          const float* h_view, const hak_intrinsics& K, float radius, int ratio_num, int ratio_den, int cross,
+                          int max_dist, const HakGuidedScratch& sc, int4* fwd, long fwd_stride, hak_corr3d* out, long out_stride,
+                          int* out_counts);
 
 // The three RANSAC estimators share one scaffold (ransac_common.h) and one launch-shape rule, hak_homography_blocks: score blocks per
 // pair (and hypotheses per block through hp_out).  A launcher writes one uint64 slot per (pair, block) to `slots` (npairs *

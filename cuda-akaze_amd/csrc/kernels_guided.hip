@@ -219,13 +219,13 @@ HakGuidedScratch hak_guided_scratch_carve(void* base, long npairs, long pts_cap,
 }
 
 void hak_launch_guided_bin(hipStream_t st, const hak_point* pts2, const int* n2_dev, int n2_host, long stride2, int npairs, float rp,
-                           const HakGuidedScratch& sc)
+                           const HakGuidedScratch& sc, int count_step)
 {
-    k_guided_bin<<<npairs, GD_THREADS, 0, st>>>(pts2, n2_dev, n2_host, stride2, 2, rp, sc);
+    k_guided_bin<<<npairs, GD_THREADS, 0, st>>>(pts2, n2_dev, n2_host, stride2, count_step, rp, sc);
 }
-void hak_launch_guided_rev(hipStream_t st, const int* n2_dev, int n2_host, int npairs, const HakGuidedScratch& sc)
+void hak_launch_guided_rev(hipStream_t st, const int* n2_dev, int n2_host, int npairs, const HakGuidedScratch& sc, int count_step)
 {
-    k_guided_rev<<<dim3(hak_grid_x((n2_host + 255) / 256), npairs), 256, 0, st>>>(n2_dev, n2_host, 2, sc);
+    k_guided_rev<<<dim3(hak_grid_x((n2_host + 255) / 256), npairs), 256, 0, st>>>(n2_dev, n2_host, count_step, sc);
 }
 
 // the forward search of npairs pairs into fwd ({j1, d1, d2, 0} per query) and, cross != 0, rev(j) into sc.rev ({i, d, 512, 0}).

@@ -20,31 +20,9 @@
 
 #define TR_BLOCK 512
 #define TR_WAVES (TR_BLOCK / HAK_WAVE)
-#define TR_VIEW_HOST 3                                                  // launcher-only kind: the view is a kernel argument
 
 typedef pt_cameras<24> TriCameras;                                      // model: the views A, B of a call that keeps them on the host
-
-// step 1 of the rule for one view: M = {R row-major, t}; false = no model.  hak_pose and hak_abs_pose both begin with R[9], t[3];
-// the word that says whether there is a model is `candidate` (word 14) of the one and `hypothesis` (word 13) of the other.
-__device__ __forceinline__ bool tr_view(const void* views, int kind, int step, int pair, const float host[12], float M[12])
-{
-    bool model = true;
-    if (kind == HAK_VIEW_IDENTITY) {
-#pragma unroll
-        for (int k = 0; k < 12; k++) M[k] = (k < 9 && k % 4 == 0) ? 1.0f : 0.0f;
-    } else if (kind == TR_VIEW_HOST) {
-#pragma unroll
-        for (int k = 0; k < 12; k++) M[k] = host[k];
-    } else {
-        const float* rec = reinterpret_cast<const float*>(static_cast<const char*>(views) + 64 * ((long)pair * step));
-#pragma unroll
-        for (int k = 0; k < 12; k++) M[k] = rec[k];
-        model = reinterpret_cast<const int*>(rec)[kind == HAK_VIEW_RELATIVE ? 14 : 13] >= 0;
-    }
-#pragma unroll
-    for (int k = 0; k < 12; k++) model = model && __builtin_isfinite(M[k]);
-    return model;
-}
+// (step 1 of the rule for one view: pt_view, points_common.h)
 
 // step 2: the view widened to float64 and its centre
 __device__ __forceinline__ void tr_centre(const float M[12], double R[9], double c[3])
@@ -76,8 +54,8 @@ __global__ __launch_bounds__(TR_BLOCK) void k_triangulate(const hak_match_pair* 
     const hak_match_pair* m = base + (long)pair * stride;
     const int n = fd_count(counts, pair, count_step, n_host, stride);
     float MA[12], MB[12];
-    const bool modelA = tr_view(viewsA, kindA, stepA, pair, cam.model, MA);
-    const bool modelB = tr_view(viewsB, kindB, stepB, pair, cam.model + 12, MB);
+    const bool modelA = pt_view(viewsA, kindA, stepA, pair, cam.model, MA);
+    const bool modelB = pt_view(viewsB, kindB, stepB, pair, cam.model + 12, MB);
     const bool model = modelA && modelB;                                // (block-uniform)
     double RA[9], RB[9], cA[3], cB[3], w[3];
     tr_centre(MA, RA, cA);
@@ -137,7 +115,7 @@ void hak_launch_triangulate(hipStream_t st, const hak_match_pair* matches, long 
     cam.K2 = KB;
     cam.put(0, h_A, 12);
     cam.put(12, h_B, 12);
-    k_triangulate<<<npairs, TR_BLOCK, 0, st>>>(matches, stride, counts, count_step, n_host, viewsA, h_A ? TR_VIEW_HOST : kindA, stepA,
-                                               viewsB, h_B ? TR_VIEW_HOST : kindB, stepB, cam, threshold * threshold, max_depth,
+    k_triangulate<<<npairs, TR_BLOCK, 0, st>>>(matches, stride, counts, count_step, n_host, viewsA, h_A ? PT_VIEW_HOST : kindA, stepA,
+                                               viewsB, h_B ? PT_VIEW_HOST : kindB, stepB, cam, threshold * threshold, max_depth,
                                                min_sin, out, masks, xyz);
 }

@@ -1,4 +1,5 @@
-// points_common.h -- what the two point kernels share (kernels_pose.hip, kernels_triangulate.hip): the 3-vector dot product, the
+// points_common.h -- what the point kernels share (kernels_pose.hip, kernels_triangulate.hip; the view of a list also serves
+// kernels_projected.hip): the 3-vector dot product, the
 // least-squares two-ray solve of step 5 of hak_recover_pose (also the solve of hak_triangulate, include/hipakaze.h), the intrinsics
 // widened to float64, the kernel argument of two cameras and a model kept on the host, the close of the per-lane integer counters
 // and the store of a match's mask byte and point.  The gates on the solve stay with the kernels: they differ.
@@ -40,6 +41,31 @@ struct pt_cameras {
         for (int k = 0; k < count; k++) model[at + k] = h ? h[k] : 0.0f;
     }
 };
+
+// a view Xc = R X + t of list `pair` as M = {R row-major, t}; false = no model (step 1 of hak_triangulate, step 7 of
+// hak_match_projected).  kind: HAK_VIEW_*, or PT_VIEW_HOST (launcher-only): the view is the kernel argument `host`.  hak_pose and
+// hak_abs_pose both begin with R[9], t[3]; the word that says whether there is a model is `candidate` (word 14) of the one and
+// `hypothesis` (word 13) of the other.
+#define PT_VIEW_HOST 3
+__device__ __forceinline__ bool pt_view(const void* views, int kind, int step, int pair, const float host[12], float M[12])
+{
+    bool model = true;
+    if (kind == HAK_VIEW_IDENTITY) {
+#pragma unroll
+        for (int k = 0; k < 12; k++) M[k] = (k < 9 && k % 4 == 0) ? 1.0f : 0.0f;
+    } else if (kind == PT_VIEW_HOST) {
+#pragma unroll
+        for (int k = 0; k < 12; k++) M[k] = host[k];
+    } else {
+        const float* rec = reinterpret_cast<const float*>(static_cast<const char*>(views) + 64 * ((long)pair * step));
+#pragma unroll
+        for (int k = 0; k < 12; k++) M[k] = rec[k];
+        model = reinterpret_cast<const int*>(rec)[kind == HAK_VIEW_RELATIVE ? 14 : 13] >= 0;
+    }
+#pragma unroll
+    for (int k = 0; k < 12; k++) model = model && __builtin_isfinite(M[k]);
+    return model;
+}
 
 // closes N per-lane integer counters over a block of WAVES waves: the xor butterfly per wave, one row of part per wave, and the
 // sum over the rows; every thread returns with the block's totals in c (k_pose chooses its winner from them in every thread;

@@ -221,6 +221,34 @@ namespace akaze
         return count;
     }
 
+    int cuMatchProjected(const hak_match_pair* A, int nA, const float* xyzA, const unsigned char* maskA, AkazeData& result_desc,
+                         AkazeData& result2, const float* Rt, const hak_intrinsics& K, hak_corr3d* out, float radius, int ratio_num,
+                         int ratio_den, bool cross_check)
+    {
+        if (nA < 0 || (nA > 0 && (!A || !xyzA))) {
+            fprintf(stderr, "hip-akaze: cuMatchProjected: bad argument\n");
+            exit(-1);
+        }
+        if (nA == 0) return 0;
+        // one device block: A | out | xyzA | maskA (the 32-byte records first: every part stays 16-byte aligned)
+        const size_t bytesA = sizeof(hak_match_pair) * (size_t)nA, bytesO = out ? sizeof(hak_corr3d) * (size_t)nA : 0;
+        const size_t bytesX = sizeof(float) * 3 * (size_t)nA;
+        char* d = nullptr;
+        if (hipMalloc((void**)&d, bytesA + bytesO + bytesX + (maskA ? (size_t)nA : 0)) != hipSuccess) die("cuMatchProjected alloc");
+        hak_match_pair* d_A = reinterpret_cast<hak_match_pair*>(d);
+        hak_corr3d* d_out = out ? reinterpret_cast<hak_corr3d*>(d + bytesA) : nullptr;
+        float* d_xyz = reinterpret_cast<float*>(d + bytesA + bytesO);
+        unsigned char* d_mask = maskA ? reinterpret_cast<unsigned char*>(d + bytesA + bytesO + bytesX) : nullptr;
+        if (hak_memcpy_h2d(d_A, A, (long)bytesA) || hak_memcpy_h2d(d_xyz, xyzA, (long)bytesX) || (maskA && hak_memcpy_h2d(d_mask, maskA, nA)))
+            die("cuMatchProjected upload");
+        int count = 0;
+        if (hak_match_projected(NULL, d_A, nA, d_mask, d_xyz, result_desc.d_data, result_desc.num_pts, result2.d_data, result2.num_pts, Rt,
+                                &K, radius, ratio_num, ratio_den, cross_check ? 1 : 0, 0, d_out, &count, out))
+            die("cuMatchProjected");
+        (void)hipFree(d);
+        return count;
+    }
+
     int cuSolvePnP(const hak_corr3d* corr, int n, const hak_intrinsics& K, float R[9], float t[3], unsigned char* inlier_mask,
                    int iterations, float threshold, unsigned seed)
     {

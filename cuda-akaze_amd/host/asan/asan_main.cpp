@@ -81,6 +81,18 @@ int main()
             REQUIRE(cuRefinePnP(corr.data(), np, K, R, t) == (np + 2) / 3);
             REQUIRE(cuRefinePnP(corr.data(), 3, K, R, t, mask.data()) == 0 && mask[0] == 0);
             REQUIRE(cuRefinePnP(NULL, 0, K, R, t) == 0);
+            {                                                           // projection-guided matching: exact-size list, points, mask and output
+                std::vector<float> xyz(3 * (size_t)np, 2.f);
+                std::vector<unsigned char> use(np, 1);
+                use[3] = 0;
+                const float Rt[12] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 1.f};
+                REQUIRE(cuMatchProjected(pairs.data(), np, xyz.data(), NULL, d2, d1, Rt, K, corr.data()) == (np + 2) / 3 &&
+                        corr[1].src3d == 3 && corr[1].src2d == 3 % d1.num_pts && corr[1].Z == 2.f && corr[1].u == d1.h_data[3 % d1.num_pts].x);
+                REQUIRE(cuMatchProjected(pairs.data(), np, xyz.data(), use.data(), d2, d1, NULL, K, corr.data()) == (np + 2) / 3 - 1 &&
+                        corr[1].src3d == 6);
+                REQUIRE(cuMatchProjected(pairs.data(), np, xyz.data(), use.data(), d2, d1, Rt, K, NULL) == (np + 2) / 3 - 1);
+                REQUIRE(cuMatchProjected(NULL, 0, NULL, NULL, d2, d1, Rt, K, NULL) == 0);
+            }
         }
         cuMatch(d1, hostless);                                      // train side without a host buffer
         d2.num_pts = 0;

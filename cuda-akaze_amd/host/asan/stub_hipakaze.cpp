@@ -220,6 +220,37 @@ int hak_link_tracks(hak_ctx*, const hak_match_pair* A, int nA, const unsigned ch
             }
     return 0;
 }
+// every record of A, every used mask byte and point, the landmark's descriptor and every entry of a host view read, `count` records
+// written; "accepted" are the eligible landmarks whose index is a multiple of 3, matched to keypoint m % n2 of the new image
+int hak_match_projected(hak_ctx*, const hak_match_pair* A, int nA, const unsigned char* maskA, const float* xyzA, const hak_point* D,
+                        int nD, const hak_point* T, int n2, const float* Rt, const hak_intrinsics* K, float radius, int ratio_num,
+                        int ratio_den, int, int, hak_corr3d* d_out, int* count, hak_corr3d* h_out)
+{
+    if (!count || !K || nA < 0 || nD < 0 || n2 < 0 || (nA > 0 && (!A || !xyzA)) || (nD > 0 && !D) || (n2 > 0 && !T) || (h_out && !d_out) ||
+        !(radius > 0.f) || ratio_num <= 0 || ratio_den <= 0 || K->fx == 0.f || K->fy == 0.f) {
+        g_err = "bad argument";
+        return 1;
+    }
+    float sum = 0.f;
+    for (int k = 0; k < 12; k++) sum += Rt ? Rt[k] : 0.f;
+    if (sum != sum) {
+        g_err = "a host view has a non-finite entry";
+        return 1;
+    }
+    *count = 0;
+    for (int m = 0; m < nA; m++) {
+        const int e = A[m].train;
+        if (e < 0 || e >= nD || (maskA && !maskA[m]) || n2 == 0 || m % 3 != 0) continue;
+        static volatile int sink;
+        sink = D[e].features[60];                                           // (the descriptor's last byte is read)
+        const int j = m % n2;
+        const hak_corr3d r{xyzA[3 * m], xyzA[3 * m + 1], xyzA[3 * m + 2], T[j].x, T[j].y, m, j, 0};
+        if (d_out) d_out[*count] = r;
+        if (h_out) h_out[*count] = r;
+        ++*count;
+    }
+    return 0;
+}
 // as hak_find_fundamental's stub: every record read, every mask byte written; "inliers" are the indices that are multiples of 3
 int hak_solve_pnp(hak_ctx*, const hak_corr3d* d, int n, const hak_intrinsics* K, int iterations, float threshold, unsigned,
                   unsigned char* mask, hak_abs_pose* out)
@@ -256,7 +287,7 @@ int hak_refine_pnp(hak_ctx*, const hak_corr3d* d, int n, const hak_intrinsics* K
     return 0;
 }
 // the HIP runtime calls of cuMatchKnn, cuFindHomography, cuFindFundamental, cuRefineFundamental, cuRecoverPose, cuTriangulate, cuLinkTracks,
-// cuSolvePnP and cuRefinePnP
+// cuMatchProjected, cuSolvePnP and cuRefinePnP
 hipError_t hipMalloc(void** p, size_t n) { *p = malloc(n); return *p ? hipSuccess : hipErrorOutOfMemory; }
 hipError_t hipFree(void* p) { free(p); return hipSuccess; }
 }

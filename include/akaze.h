@@ -78,6 +78,17 @@ namespace akaze
     int cuRefinePnP(const hak_corr3d* corr, int n, const hak_intrinsics& K, float R[9], float t[3], unsigned char* inlier_mask = nullptr,
                     float threshold = 2.f, int rounds = 3);
 
+    // build-side addition: projection-guided matching (hak_match_projected) -- re-matches 3-D points against the keypoints of a new
+    // image under its known pose: landmark m is the point xyzA[3m ..] (cuRecoverPose's or cuTriangulate's) of the host match list A
+    // (maskA NULL or nA bytes, 0 = leave the landmark out) with the descriptor of keypoint A[m].train of result_desc; Rt is 12 floats
+    // {R row-major, t} with Xc = R X + t (cuSolvePnP's or cuRefinePnP's R and t side by side), NULL = the identity.  Every landmark
+    // is searched only among the keypoints of result2 within `radius` pixels of its projection, ratio test and cross-check inside
+    // that neighbourhood.  `out` (room for nA records; may be NULL to only count) receives one 3-D to 2-D correspondence per accepted
+    // landmark in ascending order -- src3d = m, src2d = the keypoint index in result2 -- the list cuRefinePnP takes; returns their number.
+    int cuMatchProjected(const hak_match_pair* A, int nA, const float* xyzA, const unsigned char* maskA, AkazeData& result_desc,
+                         AkazeData& result2, const float* Rt, const hak_intrinsics& K, hak_corr3d* out, float radius = 8.f,
+                         int ratio_num = 4, int ratio_den = 5, bool cross_check = true);
+
     // build-side addition: guided matching (hak_match_guided) -- re-matches result1 against result2 under a homography H (row-major,
     // (x1, y1, 1) -> image 2, e.g. cuFindHomography's): every keypoint of result1 is searched only among the keypoints of result2
     // within `radius` pixels of where H sends it, ratio test and cross-check inside that neighbourhood.  Fills result1 like cuMatch

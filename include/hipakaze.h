@@ -489,7 +489,8 @@ int hak_recover_pose_batch(hak_ctx* ctx, const hak_match_pair* d_matches, long s
 typedef struct hak_corr3d {  /* 32 bytes, 16-byte aligned loads */
     float X, Y, Z;           /* point, frame and units of the xyz it came from */
     float u, v;              /* its observation in the new image, pixels */
-    int   src3d, src2d;      /* index of the match in list A / list B it came from */
+    int   src3d, src2d;      /* hak_link_tracks: index of the match in list A / list B it came from.  hak_match_projected: src3d =
+                                the landmark's index in list A, src2d = the KEYPOINT index in the new image, not a match index */
     int   pad;               /* 0 */
 } hak_corr3d;
 typedef struct hak_abs_pose {
@@ -733,6 +734,74 @@ int hak_match_epipolar_batch(hak_ctx* ctx, hak_point* d_points, const int* d_num
                              const hak_fundamental* d_F /* device, one per pair */, float radius,
                              int ratio_num, int ratio_den, int cross_check, int max_dist,
                              hak_match_pair* d_out, int* d_counts);
+
+/* ---- projection-guided matching: re-match 3-D points under a known pose (build-side addition; the stage behind hak_solve_pnp /
+ * hak_refine_pnp, as hak_match_guided is the stage behind hak_find_homography and hak_match_epipolar the one behind
+ * hak_find_fundamental).  The 3-D to 2-D correspondences PnP sees come from hak_link_tracks, which joins two whole-image 2-NN lists:
+ * a landmark whose keypoint has a look-alike elsewhere in the new image is lost to the ratio test, or arrives as a wrong
+ * correspondence.  Once the pose of the new image is known the landmark projects to one pixel, and only the keypoints within a few
+ * pixels of it are candidates -- the "search by projection" of SLAM / SfM trackers.  A pure function of (list A, mask, xyz,
+ * descriptor set D, train set T, view, K, radius, ratio, cross_check, max_dist) -- in particular it does not depend on how the
+ * implementation bins the points; tests/projected_match_ref.py is its bit-exact numpy statement.
+ *   Inputs: list A, nA hak_match_pair records of which only `train` is read; an optional mask of nA bytes; xyz, 3 nA floats in the
+ *      layout hak_recover_pose(_batch) and hak_triangulate(_batch) write; descriptor set D, n_desc hak_point records of the image
+ *      that A's `train` indexes, of which only `features` is read; train set T, n2 hak_point records of the new image, of which x,
+ *      y and features are read; a view Xc = R X + t in float32; the intrinsics K.
+ *   1. Landmark m is eligible iff (mask is NULL or mask[m] != 0) and 0 <= A[m].train < n_desc; e(m) = A[m].train.
+ *   2. Projection, float32, no FMA, every operation correctly rounded, (X, Y, Z) = xyz[3m .. 3m+2]: xc, yc, zc are exactly the
+ *      expressions of step 6 of hak_solve_pnp; px = (fx * (xc / zc)) + cx, py = (fy * (yc / zc)) + cy.
+ *   3. Gate G(m, j): m is eligible, zc > 0 and, with dx = x2_j - px, dy = y2_j - py, (dx dx) + (dy dy) < r2, r2 = radius * radius
+ *      in float32.  Any NaN makes it false: a non-finite point, projection or train coordinate is in no gate.
+ *   4. Distance d(m, j): the Hamming distance of hak_match_knn2 between D[e(m)].features and T[j].features.
+ *   5. Forward, reverse and accept are those of hak_match_guided with the landmark index m in the query's place:
+ *      J_m = { j : G(m, j) }; j1 = the member of J_m with the smallest d, ties to the smallest j; d1 = d(m, j1); d2 = the smallest
+ *      d over J_m \ {j1}, 512 when there is none; rev(j) = the landmark with the smallest d among those that gate j, ties to the
+ *      smallest m; accept m iff J_m is not empty and d1 < max_dist and d1 * ratio_den < d2 * ratio_num (64-bit products) and
+ *      (cross_check == 0 or rev(j1) == m).  max_dist <= 0 selects 96.
+ *   6. Output: the accepted landmarks in ascending m as hak_corr3d {X, Y, Z = the three words of xyz, copied; u = T[j1].x,
+ *      v = T[j1].y; src3d = m; src2d = j1 -- here the keypoint index in the new image, not a match index; pad = 0}, then their
+ *      number.  No point record is written: D and T are const.
+ *   7. No model gives count 0: a view of kind HAK_VIEW_RELATIVE with candidate < 0, of kind HAK_VIEW_ABSOLUTE with hypothesis < 0,
+ *      or with a non-finite entry of R or t.  The identity view is R = I, t = 0 and goes through every expression.
+ * Limits: nA, n_desc and n2 below 2^20; no scale or octave prediction and no orientation check; the only bound in front of the
+ * camera is zc > 0; one descriptor per landmark (that of the keypoint it was triangulated from), no fusion over a track.  Points
+ * rejected by hak_triangulate have xyz = 0 and mask 0; with a NULL mask they project to t -- that is the caller's business.
+ * Refused with a non-zero status and a message before any device is touched: a radius that is not finite or not > 0,
+ * radius * radius not finite in float32, a ratio term <= 0, fx or fy not finite or 0, a non-finite cx or cy, NULL K, count or
+ * d_counts, a negative count or a count of 2^20 or more, a NULL array with a positive count, h_out without d_out, a list A or an
+ * output list that is not 16-byte aligned, a non-finite entry of a host view, a kind outside 0..2, a NULL view array for kind 1 or
+ * 2, a view step < 0, a stride or count step < 1, npairs < 1 or above the context's pair capacity ((batch + 1) / 2), a NULL
+ * context for the batch form.  Device code: csrc/kernels_projected.hip (bin and reverse steps: csrc/kernels_guided.hip). */
+/* one list, synchronous; ctx may be NULL (default stream, scratch allocated for the call).  Rt: 12 host floats {R row-major, t},
+ * NULL = identity.  d_out: room for nA records (may be NULL: count only); h_out (needs d_out) receives the list as well */
+int hak_match_projected(hak_ctx* ctx, const hak_match_pair* d_A, int nA, const unsigned char* d_maskA, const float* d_xyzA,
+                        const hak_point* d_desc, int n_desc, const hak_point* d_pts2, int n2, const float* Rt,
+                        const hak_intrinsics* K, float radius, int ratio_num, int ratio_den, int cross_check, int max_dist,
+                        hak_corr3d* d_out, int* count, hak_corr3d* h_out);
+/* batched, asynchronous on the context's stream; every count is read on the device.  List k of A is at d_A + k*strideA, its count
+ * d_countsA[k*count_stepA], clamped to [0, min(strideA, out_stride, max_pts)], its mask at d_masksA + k*strideA (unless NULL), its
+ * points at d_xyzA + 3*k*strideA -- as hak_link_tracks_batch addresses A; descriptor set k at d_desc + k*desc_stride with the
+ * count d_desc_counts[k*desc_count_step], clamped to [0, min(desc_stride, max_pts)]; train set k at d_pts2 + k*stride2 with the
+ * count d_counts2[k*count_step2], clamped to [0, min(stride2, max_pts)]; the view of list k is record k*view_step of d_views, read
+ * ON THE DEVICE by kind as hak_triangulate_batch reads it (a step of 0 gives every list the same view; HAK_VIEW_IDENTITY ignores
+ * d_views); K is a host argument, the same for every list.  Correspondences of k to d_out + k*out_stride, their number to
+ * d_counts[k], nothing past it: the layout hak_solve_pnp_batch / hak_refine_pnp_batch read.
+ * After a detect batch of four images per chain (I0, I1, I1, I2) and .. -> hak_refine_pnp_batch (d_abs, one record per chain): A is
+ * the list of pair 2j (d_matches, stride 2*max_pts, d_counts, count step 2, with d_masks and d_xyz of hak_recover_pose_batch), D is
+ * image 4j+1 (d_points + max_pts, stride 4*max_pts, d_num_pts + 1, count step 4), T is image 4j+3 (d_points + 3*max_pts, stride
+ * 4*max_pts, d_num_pts + 3, count step 4), the view is d_abs[j] of kind HAK_VIEW_ABSOLUTE with step 1.  So .. ->
+ * hak_refine_pnp_batch -> hak_match_projected_batch -> hak_refine_pnp_batch runs the refit on the larger list with no host
+ * synchronisation and no allocation in the launch sequence (scratch grows before anything is enqueued, as the gated matchers do
+ * it).  In the six-image chain (I0, I1, I1, I2, I2, I3) the landmarks for I3 are the triangulated matches of (I1, I2): A is the
+ * list of pair 3j+1 with the mask and points hak_triangulate_batch wrote, D is image 6j+3, T is image 6j+5, the view the refitted
+ * pose of I3. */
+int hak_match_projected_batch(hak_ctx* ctx, const hak_match_pair* d_A, long strideA, const int* d_countsA, int count_stepA,
+                              const unsigned char* d_masksA, const float* d_xyzA,
+                              const hak_point* d_desc, long desc_stride, const int* d_desc_counts, int desc_count_step,
+                              const hak_point* d_pts2, long stride2, const int* d_counts2, int count_step2, int npairs,
+                              const void* d_views, int kind, int view_step, const hak_intrinsics* K,
+                              float radius, int ratio_num, int ratio_den, int cross_check, int max_dist,
+                              hak_corr3d* d_out, long out_stride, int* d_counts);
 
 /* ---- memory helpers: initAkazeData/freeAkazeData (akaze.cpp:26-52) and the
  * image upload of main.cpp:172-188 */
