@@ -152,6 +152,8 @@ SYMBOLS = {
     "hak_gauss_taps": (None, [C.c_float, C.c_int, _fp]),
     "hak_compare_indices": (None, [_ip, _ip]),
     "hak_describe_plan_query": (C.c_int, [C.c_int, C.POINTER(C.c_uint), C.POINTER(C.c_uint)]),
+    "hak_describe_order_query": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_uint)]),
+    "hak_describe_order_bin": (C.c_int, [C.c_float]),
     "hak_query_schedule": (C.c_int, [_vp, _ip, _ip, _fp, _fp]),
     "hak_query_geometry": (C.c_int, [_vp, _ip]),
     "hak_query_traffic": (C.c_int, [_vp, C.c_int, C.POINTER(hak_traffic)]),
@@ -309,6 +311,18 @@ def describe_plan(pattern_size):
     cell = np.zeros((7, 64), np.uint32)
     ok = lib.hak_describe_plan_query(pattern_size, pos.ctypes.data_as(C.POINTER(C.c_uint)), cell.ctypes.data_as(C.POINTER(C.c_uint)))
     return bool(ok), pos, cell
+
+
+def describe_order(pattern_size, row):
+    """(NB, slots[7][64]) of hak_describe_order_query: row < NB the gather order of angle bin `row`, row NB the window order"""
+    slots = np.zeros((7, 64), np.uint32)
+    nb = lib.hak_describe_order_query(pattern_size, row, slots.ctypes.data_as(C.POINTER(C.c_uint)))
+    return nb, slots
+
+
+def describe_order_bin(angle):
+    """the order-table row k_describe_runs takes for a keypoint angle (hak_describe_order_bin)"""
+    return lib.hak_describe_order_bin(C.c_float(angle))
 
 
 # ------------------------------------------------------ reference-shaped API

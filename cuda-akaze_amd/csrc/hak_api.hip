@@ -103,10 +103,26 @@ extern "C" int hak_describe_plan_query(int pattern_size, unsigned int* pos, unsi
     if (pattern_size < 1) return 0;
     memset(&t, 0, sizeof(t));
     hak_describe_plan(&t, pattern_size);
-    if (pos) memcpy(pos, t.dsc_pos, sizeof(t.dsc_pos));
+    if (pos)                                                // the window-order row of the gather table, without the index bits
+        for (int j = 0; j < 7 * 64; j++) pos[j] = t.dsc_ord[HAK_DSC_NB * 7 * 64 + j] & 0x1FFFFu;
     if (cell) memcpy(cell, t.dsc_cell, sizeof(t.dsc_cell));
     return t.dsc_plan_ok;
 }
+
+extern "C" int hak_describe_order_query(int pattern_size, int row, unsigned int* slots)
+{
+    static HakTables t;
+    static std::mutex mu;
+    std::lock_guard<std::mutex> lock(mu);
+    if (pattern_size < 1 || row < 0 || row > HAK_DSC_NB) return 0;
+    memset(&t, 0, sizeof(t));
+    hak_describe_plan(&t, pattern_size);
+    if (!t.dsc_plan_ok) return 0;
+    if (slots) memcpy(slots, t.dsc_ord + (size_t)row * 7 * 64, sizeof(unsigned int) * 7 * 64);
+    return HAK_DSC_NB;
+}
+
+extern "C" int hak_describe_order_bin(float angle) { return hak_dsc_bin(angle); }
 
 extern "C" void hak_compare_indices(int* idx1, int* idx2)
 {

@@ -8,6 +8,7 @@
 
 #define HAK_NBINS 300        // akazed.cu:8
 #define HAK_WAVE 64
+#define HAK_DSC_NB 32        // angle bins of the MLDB gather-order table (a power of two; HakTables::dsc_ord)
 
 // ---------------------------------------------------------------- geometry
 struct HakOct {
@@ -58,15 +59,31 @@ struct HakTables {
     int comp1[488], comp2[488];                        // MLDB pair table (akazed.cu:65-159)
     unsigned char comp_packed[64 * 16];                // per descriptor byte: 8 x (idx1, idx2) as bytes
     // MLDB sample plan of the configured descriptor_pattern_size (hak_describe_plan, kernels_describe.hip): which sample a
-    // lane takes in its n-th turn and where it goes depends on (lane, n) only, never on the keypoint.  [n * 64 + lane]:
-    //   dsc_pos : bits 0..7 l = x - size2 (signed), 8..15 k = y - size2 (signed), bit 16 sample exists
+    // lane SUMS in its n-th turn (sample n * 64 + lane of the window) and where it goes depends on (lane, n) only, never on the
+    // keypoint.  [n * 64 + lane]:
     //   dsc_cell: byte g (2x2, 3x3, 4x4 grid) = accumulator row (0x7F none) | 0x80 when the lane's previous sample went to the
     //             same row; bit 24 + g: last sample of this lane in that row
-    unsigned int dsc_pos[7 * 64];
     unsigned int dsc_cell[7 * 64];
     int dsc_plan_ok;                                   // 0: pattern too large or a lane revisits a row -> generic k_describe
+    // Gather order of k_describe_runs: WHICH samples share a gather instruction.  Row b < HAK_DSC_NB lists the window's samples
+    // sorted by their image row, then column, under a rotation by the centre angle of bin b (v = k sin a + l cos a, then
+    // u = k cos a - l sin a; a = b * 2 pi / HAK_DSC_NB, hak_dsc_bin), so the 64 lanes of turn n gather neighbours along image rows,
+    // which share 128-byte lines; row HAK_DSC_NB is the window order (slot = sample).  [row][n * 64 + lane]: bits 0..7
+    // l = x - size2 (signed), 8..15 k = y - size2 (signed), bit 16 sample exists, bits 17..25 the window index i, where
+    // the kernel stages the values for the lane (i % 64, turn i / 64) that sums them.  A slot without a sample (the window's
+    // 7 * 64 - nsmp pads) has l = k = 0 and an index of its own >= nsmp: every row is a permutation of 0 .. 7 * 64 - 1.
+    unsigned int dsc_ord[(HAK_DSC_NB + 1) * 7 * 64];
 };
 void hak_describe_plan(HakTables* t, int patsize);
+
+// the order-table row of a keypoint angle: nearest bin centre, every float (NaN, +-inf, negative, huge) in 0 .. HAK_DSC_NB - 1.
+// The row only groups the gathers; results do not depend on it.
+__host__ __device__ inline int hak_dsc_bin(float angle)
+{
+    float t = angle * (float)(HAK_DSC_NB / (2.0 * 3.14159265358979323846));
+    t = fminf(fmaxf(t, -1.0e6f), 1.0e6f);              // (fmaxf drops a NaN; the cast below is then defined for every input)
+    return (int)floorf(t + 0.5f) & (HAK_DSC_NB - 1);
+}
 
 // ---------------------------------------------------------------- device helpers
 // hScharrContrast as the reference's kernels actually compute it (akazed.cu:827-877, 901-938 / 3245-3336; derivation:

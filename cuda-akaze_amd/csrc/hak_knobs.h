@@ -21,7 +21,9 @@ struct HakKnobs {
     int desc_plan = 1;            // HAK_DESC_PLAN: planned MLDB kernel (k_describe_runs) on / off
     int desc_sort = 1;            // HAK_DESC_SORT: the keypoint kernels visit an image's keypoints level by level (raster order within a
                                   // level) instead of in output order: 0 never / 1 in batches of 8 images and more / 2 always
-    int hess_lp = 0;              // HAK_HESS_LP=1: the streaming Hessian low-passes Lt(o,s-1) itself and k_fed_sf stops storing `smooth`.
+    int desc_gather = 1;          // HAK_DESC_GATHER: samples that share a gather instruction of k_describe_runs: 1 neighbours along image
+                                  // rows (the order table of the keypoint's angle bin) / 0 consecutive window samples
+    int hess_lp = 0;             // HAK_HESS_LP=1: the streaming Hessian low-passes Lt(o,s-1) itself and k_fed_sf stops storing `smooth`.
                                   // Off by default: measured 0.6 ms per 384 x 1080p SLOWER (FED -1.2 ms, Hessian +1.9 ms)
     int level_tile = 1;           // HAK_LEVEL_TILE: one launch per sublevel out of LDS tiles (k_level_tile) 0 never / 1 for launches of at
                                   // most HAK_LEVEL_TILE_MAX_PX pixels unless the streaming kernels are forced / 2 always

@@ -22,6 +22,7 @@ HakKnobs hak_knobs_from_env()
         {"HAK_DESC_ORDER", &HakKnobs::desc_order, 0, 255},
         {"HAK_DESC_PLAN", &HakKnobs::desc_plan, INT_MIN, INT_MAX},
         {"HAK_DESC_SORT", &HakKnobs::desc_sort, INT_MIN, INT_MAX},
+        {"HAK_DESC_GATHER", &HakKnobs::desc_gather, INT_MIN, INT_MAX},
         {"HAK_HESS_LP", &HakKnobs::hess_lp, INT_MIN, INT_MAX},
         {"HAK_LEVEL_TILE", &HakKnobs::level_tile, INT_MIN, INT_MAX},
         {"HAK_LEVEL_HESS", &HakKnobs::level_hess, INT_MIN, INT_MAX},

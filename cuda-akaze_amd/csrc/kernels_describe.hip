@@ -17,10 +17,17 @@
 // Both kernels issue every gather of a keypoint before any is consumed.  What bounds them (counters of the 256 x 1080p batch,
 // profiles/README.md): k_describe* the texture-address path -- TA stalled by the L1 for 81 % of the kernel, 939 L1 accesses and
 // 506 L2 requests per keypoint, two thirds of those L2 misses (random 64-byte sectors at 3.8 TB/s); cutting its VALU work by 40 %
-// and its LDS traffic by more (k_describe_runs against k_describe) moved it by 1 %.  k_orient was bound by LDS broadcast reads
-// until the bin sums were reorganised as a counting sort (0.95 -> 0.42 ms).
+// and its LDS traffic by more (k_describe_runs against k_describe) moved it by 1 %.  What it pays for are requests: the distinct
+// 128-byte lines a gather instruction touches.  WHICH samples share an instruction is free (the sums only fix which lane ADDS a
+// sample), so k_describe_runs gathers 64 neighbours along image rows per instruction (HakTables::dsc_ord, one row per angle bin)
+// and hands every value to its summing lane through LDS: 0.73 of the window order's lines per instruction in the model
+// (tests/test_describe_order_cpu.py), 5.66 -> 5.06 ms per 512 x 1080p images measured (0.89; profiles/describe_gather_order.txt).
+// k_orient was bound by LDS broadcast reads until the bin sums were reorganised as a counting sort (0.95 -> 0.42 ms).
 #include "hak_internal.h"
+#include <algorithm>
+#include <cmath>
 #include <type_traits>
+#include <vector>
 
 #define ACC_LD 65           // padded leading dimension of the per-thread accumulator table
 #define ACC_ROWS 30         // accumulator rows per round (multiple of 3): 87 rows in 3 rounds
@@ -272,10 +279,13 @@ __global__ __launch_bounds__(64) void k_orient(const V* __restrict__ base, long 
 template <typename V>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void k_describe_runs(const V* __restrict__ base, long stride, HakLayout L,
                                                       const HakTables* __restrict__ tab, const HakImgState* __restrict__ state,
-                                                      hak_point* points, int max_pts, int upright, int order, const int* __restrict__ perm)
+                                                      hak_point* points, int max_pts, int upright, int order, const int* __restrict__ perm,
+                                                      int gather)
 {
     __shared__ __attribute__((aligned(16))) V acc[(RUN_ROWS * ACC_LD + 3) / 4 * 4];
     __shared__ V vals[90];
+    // the staging table of the gathered samples ([value, dx', dy'][window index]) lives in `acc`, which is cleared behind it
+    static_assert(3 * MAX_SMP * 64 <= (RUN_ROWS * ACC_LD + 3) / 4 * 4, "the staging table must fit into the accumulator table");
     int img = blockIdx.y, first = blockIdx.x;
     if (order > 0) {                                                // images dealt in groups of `order`: image index fastest inside a group
         const unsigned lin = blockIdx.y * gridDim.x + blockIdx.x;
@@ -293,12 +303,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void k_
     const unsigned int cw[4] = {cmp.x, cmp.y, cmp.z, cmp.w};
 
     for (int pi = first; pi < npts; pi += gridDim.x) {
-        // the lane's sample offsets, loaded with the keypoint (before the gathers: a load issued between them would have to
-        // wait for them too, vmcnt counts in order); its accumulator rows are loaded behind the gathers, where they are used.
-        // Per keypoint, not per block: a block runs this loop once or twice, and hoisted copies cost a wave of occupancy.
         unsigned posw[MAX_SMP], cellw[MAX_SMP];
-#pragma unroll
-        for (int n = 0; n < MAX_SMP; n++) posw[n] = tab->dsc_pos[n * 64 + lane];
         hak_point* pt = pts + (perm ? perm[(long)img * max_pts + pi] : pi);
         const float ptx = pt->x, pty = pt->y, ptsize = pt->size;
         const int layer = __builtin_amdgcn_readfirstlane(pt->octave);
@@ -308,6 +313,17 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void k_
         const V* dxyd = arena + L.dxy(o, s);
         float angle = 0.f;
         if (!upright) angle = pt->angle;                            // written by k_orient
+        // the samples this lane GATHERS, turn by turn: the order-table row of the keypoint's angle (one row per wave; gather = 0:
+        // the window-order row), loaded behind the keypoint record and before the gathers (a load issued between them would have
+        // to wait for them too, vmcnt counts in order); the accumulator rows of the samples the lane SUMS are loaded behind the
+        // gathers, where they are used.  Per keypoint, not per block: a block runs this loop once or twice, and hoisted copies
+        // cost a wave of occupancy.
+        {
+            const int row = __builtin_amdgcn_readfirstlane(gather ? hak_dsc_bin(angle) : HAK_DSC_NB);
+            const unsigned int* ord = tab->dsc_ord + row * (MAX_SMP * 64) + lane;
+#pragma unroll
+            for (int n = 0; n < MAX_SMP; n++) posw[n] = ord[n * 64];
+        }
 
         V vim[MAX_SMP], vrx[MAX_SMP], vry[MAX_SMP];
         {
@@ -317,11 +333,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void k_
             const float yf = pty * iratio;
             float si, co;
             hak_sincosf(angle, &si, &co);
-            V gdx[MAX_SMP], gdy[MAX_SMP];
+            V gim[MAX_SMP], gdx[MAX_SMP], gdy[MAX_SMP];
 #pragma unroll
             for (int n = 0; n < MAX_SMP; n++) {
-                // a turn without a sample (posw = 0) gathers at the keypoint itself; it belongs to no row, so its values
-                // end in a running sum that is never written
+                // a slot without a sample (l = k = 0) gathers at the keypoint itself; its values go to a staging word of their
+                // own, whose reader belongs to no row: they end in a running sum that is never written
                 const int l = (int)(signed char)(posw[n] & 0xFF);
                 const int k = (int)(signed char)((posw[n] >> 8) & 0xFF);
                 int xp = (int)(xf + scale * (k * co - l * si) + 0.5f);  // akazed.cu:1921
@@ -329,18 +345,33 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void k_
                 xp = min(max(xp, 0), oc.w - 1);
                 yp = min(max(yp, 0), oc.h - 1);
                 const unsigned pos = (unsigned)(yp * oc.p + xp) * (unsigned)sizeof(V);
-                vim[n] = dsc_ld(imd, pos);
+                gim[n] = dsc_ld(imd, pos);
                 const auto d2 = dsc_ld2(dxyd, pos);
                 gdx[n] = d2.x;
                 gdy[n] = d2.y;
             }
 #pragma unroll
             for (int n = 0; n < MAX_SMP; n++) cellw[n] = tab->dsc_cell[n * 64 + lane];
+            // every value to the staging word of its window index (the table's rows are permutations of 0 .. 7 * 64 - 1: each word
+            // is written once per keypoint, by one lane), then lane t takes samples t, t + 64, ... back: from here on a sample
+            // sits where the reference's thread order wants it, whichever lane gathered it.  One wave per workgroup: its LDS
+            // operations complete in program order; wave_barrier keeps the compiler from moving the reads across the writes.
 #pragma unroll
             for (int n = 0; n < MAX_SMP; n++) {
-                vrx[n] = (V)(-gdx[n] * si + gdy[n] * co);           // akazed.cu:1931 / 3777
-                vry[n] = (V)(gdx[n] * co + gdy[n] * si);
+                V* st = acc + (posw[n] >> 17);
+                st[0] = gim[n];
+                st[MAX_SMP * 64] = (V)(-gdx[n] * si + gdy[n] * co); // akazed.cu:1931 / 3777
+                st[2 * MAX_SMP * 64] = (V)(gdx[n] * co + gdy[n] * si);
             }
+            __builtin_amdgcn_wave_barrier();
+#pragma unroll
+            for (int n = 0; n < MAX_SMP; n++) {
+                const V* st = acc + n * 64 + lane;
+                vim[n] = st[0];
+                vrx[n] = st[MAX_SMP * 64];
+                vry[n] = st[2 * MAX_SMP * 64];
+            }
+            __builtin_amdgcn_wave_barrier();                        // ... nor the clear below across the reads
         }
         // one grid in one round: the lane's running sums per row, written when the row's last sample has been added and the
         // row belongs to the round's window [row0, row0 + nrows)
@@ -436,7 +467,6 @@ void hak_describe_plan(HakTables* t, int patsize)
             rows[n][0] = have && m < 2 * size2 ? 3 * ((y < size2 ? 0 : 2) + (x < size2 ? 0 : 1)) : 0x7F;
             rows[n][1] = have && m < 3 * size3 ? 3 * (4 + y3 * 3 + x3) : 0x7F;
             rows[n][2] = have && m < 4 * size4 ? 39 + 3 * (y4 * 4 + x4) : 0x7F;
-            t->dsc_pos[n * 64 + lane] = have ? ((unsigned)((x - size2) & 0xFF) | ((unsigned)((y - size2) & 0xFF) << 8) | (1u << 16)) : 0u;
         }
         for (int n = 0; n < MAX_SMP; n++) {
             unsigned w = 0;
@@ -453,6 +483,26 @@ void hak_describe_plan(HakTables* t, int patsize)
         }
     }
     t->dsc_plan_ok = ok ? 1 : 0;
+
+    // the gather order (HakTables::dsc_ord): per angle bin the samples sorted by image row, then column, at the bin's centre angle.
+    // The keys are rounded to 2^-16 of a sample step so that samples of one image row (exact at the multiples of pi / 2) tie and
+    // fall back on the column; the window index breaks what is left.
+    struct Key { long long v, u; int i; };
+    std::vector<Key> keys((size_t)nsmp);
+    for (int b = 0; b <= HAK_DSC_NB; b++) {
+        unsigned int* row = t->dsc_ord + (size_t)b * MAX_SMP * 64;
+        const double a = b * (2.0 * HAK_PI_D / HAK_DSC_NB), sa = sin(a), ca = cos(a);
+        for (int i = 0; i < nsmp; i++) {
+            const int l = i % winsize - size2, k = i / winsize - size2;
+            keys[i] = b < HAK_DSC_NB ? Key{llround((k * sa + l * ca) * 65536.0), llround((k * ca - l * sa) * 65536.0), i} : Key{0, 0, i};
+        }
+        std::sort(keys.begin(), keys.end(), [](const Key& p, const Key& q) { return p.v != q.v ? p.v < q.v : (p.u != q.u ? p.u < q.u : p.i < q.i); });
+        for (int j = 0; j < MAX_SMP * 64; j++) {
+            if (j >= nsmp) { row[j] = (unsigned)j << 17; continue; }
+            const int i = keys[j].i, l = i % winsize - size2, k = i / winsize - size2;
+            row[j] = (unsigned)(l & 0xFF) | ((unsigned)(k & 0xFF) << 8) | (1u << 16) | ((unsigned)i << 17);
+        }
+    }
 }
 
 template <typename V>
@@ -699,7 +749,7 @@ void hak_launch_describe(hipStream_t st, const HakBatch& b, const HakLayout& L, 
     const int order = kn.desc_order < 0 ? 0 : (kn.desc_order > 255 ? 255 : kn.desc_order);
     const int* perm = desc ? launch_perm(st, b, L, points, max_pts, kn) : nullptr;
     if (desc && !upright && orient) k_orient<float><<<grido, 64, 0, st>>>(b.base, b.stride, L, tab, b.state, points, max_pts, 1, 0, perm);
-    if (desc && (planned && kn.desc_plan)) k_describe_runs<float><<<grid, 64, 0, st>>>(b.base, b.stride, L, tab, b.state, points, max_pts, upright, order, perm);
+    if (desc && (planned && kn.desc_plan)) k_describe_runs<float><<<grid, 64, 0, st>>>(b.base, b.stride, L, tab, b.state, points, max_pts, upright, order, perm, kn.desc_gather != 0);
     else if (desc) k_describe<float><<<grid, 64, 0, st>>>(b.base, b.stride, L, tab, b.state, points, max_pts, patsize, upright, desc);
 }
 
@@ -717,6 +767,6 @@ void hakf_launch_describe(hipStream_t st, const HakBatch& b, const HakLayout& L,
     const int* base = reinterpret_cast<const int*>(b.base);
     const int* perm = launch_perm(st, b, L, points, max_pts, kn);
     k_orient<int><<<grido, 64, 0, st>>>(base, b.stride, L, tab, b.state, points, max_pts, desc && !upright, 0, perm);
-    if (desc && (planned && kn.desc_plan)) k_describe_runs<int><<<grid, 64, 0, st>>>(base, b.stride, L, tab, b.state, points, max_pts, upright, order, perm);
+    if (desc && (planned && kn.desc_plan)) k_describe_runs<int><<<grid, 64, 0, st>>>(base, b.stride, L, tab, b.state, points, max_pts, upright, order, perm, kn.desc_gather != 0);
     else if (desc) k_describe<int><<<grid, 64, 0, st>>>(base, b.stride, L, tab, b.state, points, max_pts, patsize, upright, desc);
 }

@@ -839,6 +839,15 @@ void hak_compare_indices(int* idx1, int* idx2);
  * went to the same row; bit 24 + g: the lane's last sample in that row.  Returns 1 when the planned kernel serves this size (at
  * most 7 samples per lane and no lane returning to a row it has left), 0 when the generic kernel does. */
 int hak_describe_plan_query(int pattern_size, unsigned int* pos, unsigned int* cell);
+/* The planned MLDB kernel's gather order: which samples share a gather instruction.  Row `row` < NB lists the window's samples
+ * sorted by image row, then column, under a rotation by the bin's centre angle row * 2 pi / NB; row NB is the window order.
+ * slots: 7 * 64 words, [turn * 64 + lane], or NULL: bits 0..7 x - size2 (signed), 8..15 y - size2 (signed), bit 16 the slot holds a
+ * sample, bits 17..25 the sample's window index i (a slot without a sample: an index of its own >= the sample count, so that a
+ * row is a permutation of 0 .. 7 * 64 - 1).  Returns NB, or 0 for a size the generic kernel serves or a row outside 0 .. NB.
+ * hak_describe_order_bin: the row (0 .. NB - 1) the kernel takes for a keypoint angle -- any float, NaN and infinities included.
+ * The order groups memory accesses only; no result depends on it. */
+int hak_describe_order_query(int pattern_size, int row, unsigned int* slots);
+int hak_describe_order_bin(float angle);
 /* schedule the context was built with: per (octave, sublevel) the number of FED
  * steps, sigma_size, size, border; returns effective number of octaves. */
 int hak_query_schedule(const hak_ctx* ctx, int* nsteps, int* sigma_size, float* sizes, float* borders);
