@@ -624,23 +624,27 @@ def cuMatchKnn(result1, result2, ratio=(1, 1), cross_check=True, max_dist=0, aka
     return h_out[:cnt.value].copy()
 
 
+def _match_gated(entry, result1, result2, model, radius, ratio, cross_check, max_dist, akazer):
+    """the call behind cuMatchGuided and cuMatchEpipolar: `entry` re-matches result1 against result2 under the nine floats of `model`"""
+    import torch
+    ctx = _ctx_of(akazer)
+    n1 = result1.num_pts
+    m = np.ascontiguousarray(np.asarray(model, np.float32).reshape(9))
+    d_out = torch.zeros(max(n1, 1) * MATCH_PAIR_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+    h_out = np.zeros(max(n1, 1), MATCH_PAIR_DTYPE)
+    cnt = C.c_int(0)
+    hptr = result1.h_data.ctypes.data if result1.h_data is not None else None
+    check(entry(ctx, result1.d_data, n1, result2.d_data, result2.num_pts, m.ctypes.data_as(_fp), float(radius), int(ratio[0]),
+                int(ratio[1]), int(cross_check), int(max_dist), hptr, d_out.data_ptr(), C.byref(cnt), h_out.ctypes.data))
+    return h_out[:cnt.value].copy()
+
+
 def cuMatchGuided(result1, result2, H, radius=8.0, ratio=(4, 5), cross_check=True, max_dist=0, akazer=None):
     """Guided matching (hipakaze.h hak_match_guided): re-matches result1 against result2 under the homography H (9 values, row-major,
     e.g. findHomography's record["H"]): every query is searched only among the train points within `radius` pixels of where H sends
     it; ratio test and cross-check inside that neighbourhood.  Updates result1 like cuMatch and returns the accepted matches
     (MATCH_PAIR_DTYPE, ascending query index)."""
-    import torch
-    ctx = _ctx_of(akazer)
-    n1 = result1.num_pts
-    h = np.ascontiguousarray(np.asarray(H, np.float32).reshape(9))
-    d_out = torch.zeros(max(n1, 1) * MATCH_PAIR_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
-    h_out = np.zeros(max(n1, 1), MATCH_PAIR_DTYPE)
-    cnt = C.c_int(0)
-    hptr = result1.h_data.ctypes.data if result1.h_data is not None else None
-    check(lib.hak_match_guided(ctx, result1.d_data, n1, result2.d_data, result2.num_pts, h.ctypes.data_as(_fp), float(radius),
-                               int(ratio[0]), int(ratio[1]), int(cross_check), int(max_dist), hptr, d_out.data_ptr(), C.byref(cnt),
-                               h_out.ctypes.data))
-    return h_out[:cnt.value].copy()
+    return _match_gated(lib.hak_match_guided, result1, result2, H, radius, ratio, cross_check, max_dist, akazer)
 
 
 def cuMatchEpipolar(result1, result2, F, radius=2.0, ratio=(4, 5), cross_check=True, max_dist=0, akazer=None):
@@ -648,18 +652,7 @@ def cuMatchEpipolar(result1, result2, F, radius=2.0, ratio=(4, 5), cross_check=T
     (9 values, row-major, (x2 y2 1) F (x1 y1 1)^T = 0, e.g. findFundamental's record["F"]): every query is searched only among the
     train points closer than `radius` pixels to its epipolar line; ratio test and cross-check inside that band.  Updates result1
     like cuMatch and returns the accepted matches (MATCH_PAIR_DTYPE, ascending query index)."""
-    import torch
-    ctx = _ctx_of(akazer)
-    n1 = result1.num_pts
-    f = np.ascontiguousarray(np.asarray(F, np.float32).reshape(9))
-    d_out = torch.zeros(max(n1, 1) * MATCH_PAIR_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
-    h_out = np.zeros(max(n1, 1), MATCH_PAIR_DTYPE)
-    cnt = C.c_int(0)
-    hptr = result1.h_data.ctypes.data if result1.h_data is not None else None
-    check(lib.hak_match_epipolar(ctx, result1.d_data, n1, result2.d_data, result2.num_pts, f.ctypes.data_as(_fp), float(radius),
-                                 int(ratio[0]), int(ratio[1]), int(cross_check), int(max_dist), hptr, d_out.data_ptr(), C.byref(cnt),
-                                 h_out.ctypes.data))
-    return h_out[:cnt.value].copy()
+    return _match_gated(lib.hak_match_epipolar, result1, result2, F, radius, ratio, cross_check, max_dist, akazer)
 
 
 def _device_records(a, dtype):

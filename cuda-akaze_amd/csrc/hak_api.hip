@@ -1124,8 +1124,61 @@ static int guided_args(float radius, int ratio_num, int ratio_den)
 
 static int guided_scratch(hak_ctx* c, size_t bytes) { return grow_scratch(c->guided, c->guided_cap, (long)bytes, 1); }
 
-// What the gated matchers (hak_match_guided, hak_match_epipolar) share behind their own model checks.  Single pair, synchronous:
-// search(stream, scratch, fwd) enqueues the bin step, the search and the reverse step.
+// The scratch of a one-list gated call (gated_match_single, hak_match_projected): the grid's buffer -- the context's, or without a
+// context a hipMalloc that lives as long as the holder -- and the 2-NN scratch (the context's or the pool's) with room for nq + cap2
+// search records and `blks` block counts.  Without a context the holder gives back what it still holds when it goes: a caller whose
+// tail releases msc itself clears the pointer, the others say through `ok` how the pool gets it back.
+struct GatedScratch {
+    hak_ctx* c;
+    hipStream_t st;
+    long cap2;
+    void* buf = nullptr;
+    HakMatchScratch* msc = nullptr;
+    bool ok = false;
+
+    GatedScratch(hak_ctx* c, int n2) : c(c), st(c ? c->stream : nullptr), cap2(n2 > 0 ? n2 : 1) {}
+    GatedScratch(const GatedScratch&) = delete;
+    GatedScratch& operator=(const GatedScratch&) = delete;
+    ~GatedScratch()
+    {
+        if (!c && msc) pool_release(msc, ok);
+        if (!c) (void)hipFree(buf);
+    }
+    int acquire(const char* what, long nq, long blks)
+    {
+        const size_t bytes = hak_guided_scratch_bytes(1, cap2);
+        if (c) {
+            if (guided_scratch(c, bytes)) return 1;
+            buf = c->guided;
+        } else
+            HIP_TRY(hipMalloc(&buf, bytes));
+        msc = c ? &c->msc : pool_acquire();
+        order_after_null_stream(c, st);
+        if (!hak_match_scratch_reserve(msc, st, 0, 0, 0, nq + cap2, blks))
+            return fail(std::string(what) + ": out of device memory for the search scratch");
+        return 0;
+    }
+    // forward records at msc->knn, the reverse words of the nq queries' train set behind them
+    HakGuidedScratch carve(long nq) const { return hak_guided_scratch_carve(buf, 1, cap2, msc->knn + nq, 0); }
+};
+// ... and of a batch call, on the context: its 2-NN records split into a forward and a reverse half of the context's pair capacity
+// times max_pts (mp) each, and its grid buffer for as many pairs of max_pts train points
+static int gated_batch_scratch(hak_ctx* c, long& mp, int4*& fwd, int4*& rev)
+{
+    mp = c->cfg.max_pts;
+    if (!hak_mkey_fits(mp)) return fail("max_pts must stay below 2^20 for the matcher");
+    if (knn_scratch(c)) return 1;
+    const long npair_cap = (c->cfg.batch + 1) / 2;
+    if (guided_scratch(c, hak_guided_scratch_bytes(npair_cap, mp))) return 1;
+    order_after_null_stream(c, c->stream);
+    fwd = c->knn;
+    rev = c->knn + (size_t)npair_cap * mp;
+    return 0;
+}
+
+// What the matchers gated by a model of nine floats (hak_match_guided, hak_match_epipolar) share behind their own model checks;
+// hak_match_projected has lists of its own around the same scratch.  Single pair, synchronous: search(stream, scratch, fwd)
+// enqueues the bin step, the search and the reverse step.
 static int gated_args_single(const hak_point* d_pts1, int n1, const hak_point* d_pts2, int n2, const int* count)
 {
     if (!count) return fail("null argument");
@@ -1145,37 +1198,24 @@ static int gated_match_single(hak_ctx* c, const char* what, hak_point* d_pts1, i
     if (n1 == 0) return 0;
     if (max_dist <= 0) max_dist = HAK_MAX_DIST;
     if (hak_device_count() == 0) return fail("no HIP device: libhipakaze has no CPU fallback");
-    hipStream_t st = c ? c->stream : nullptr;
-    const long cap2 = n2 > 0 ? n2 : 1;
-    const size_t bytes = hak_guided_scratch_bytes(1, cap2);
-    void* buf = nullptr;
-    if (c) {
-        if (guided_scratch(c, bytes)) return 1;
-        buf = c->guided;
-    } else
-        HIP_TRY(hipMalloc(&buf, bytes));
-    HakMatchScratch* sc = c ? &c->msc : pool_acquire();
-    order_after_null_stream(c, st);
-    const int nb = (n1 + 1023) / 1024;
-    if (!hak_match_scratch_reserve(sc, st, 0, 0, 0, (long)n1 + cap2, nb)) {
-        if (!c) { pool_release(sc, false); (void)hipFree(buf); }
-        return fail(std::string(what) + ": out of device memory for the search scratch");
-    }
+    GatedScratch g(c, n2);
+    if (g.acquire(what, n1, (n1 + 1023) / 1024)) return 1;
+    hipStream_t st = g.st;
+    HakMatchScratch* sc = g.msc;
     int4* fwd = sc->knn;
     int4* rev = sc->knn + n1;
     *sc->h_cnt = -1;
     {
         ProfScope ps(c, HAK_PROF_MATCH);
-        search(st, hak_guided_scratch_carve(buf, 1, cap2, rev, 0), fwd);
+        search(st, g.carve(n1), fwd);
         hak_launch_knn2_finish(st, d_pts1, d_pts2, nullptr, n1, 0, 0, 1, fwd, cross_check ? rev : nullptr, 0, ratio_num, ratio_den,
                                cross_check ? 1 : 0, max_dist, d_out, 0, sc->d_cnt, sc);
     }
     int rc = 0;
     if (hipGetLastError() != hipSuccess) rc = fail(std::string(what) + ": launch failed");
     if (!rc && hipStreamSynchronize(st) != hipSuccess) rc = fail(std::string(what) + ": hipStreamSynchronize");
-    rc = match_list_tail(c, sc, rc, h_pts1, d_pts1, n1, d_out, count, h_out);
-    if (!c) (void)hipFree(buf);
-    return rc;
+    g.msc = nullptr;                                                    // (match_list_tail releases it)
+    return match_list_tail(c, sc, rc, h_pts1, d_pts1, n1, d_out, count, h_out);
 }
 // ... and the batch form, asynchronous on the context's stream: search(scratch, fwd, mp)
 template <typename Search>
@@ -1188,16 +1228,11 @@ static int gated_match_batch(hak_ctx* c, const char* what, hak_point* d_points, 
     if (2 * npairs > c->cfg.batch + 1) return fail("npairs exceeds the context's batch capacity");
     if (guided_args(radius, ratio_num, ratio_den)) return 1;
     if (max_dist <= 0) max_dist = HAK_MAX_DIST;
-    const long mp = c->cfg.max_pts;
-    if (!hak_mkey_fits(mp)) return fail("max_pts must stay below 2^20 for the matcher");
-    if (knn_scratch(c)) return 1;
-    const long npair_cap = (c->cfg.batch + 1) / 2;
-    if (guided_scratch(c, hak_guided_scratch_bytes(npair_cap, mp))) return 1;
-    order_after_null_stream(c, c->stream);
-    int4* fwd = c->knn;
-    int4* rev = c->knn + (size_t)npair_cap * mp;
+    long mp;
+    int4 *fwd, *rev;
+    if (gated_batch_scratch(c, mp, fwd, rev)) return 1;
     { ProfScope ps(c, HAK_PROF_MATCH);
-      search(hak_guided_scratch_carve(c->guided, npair_cap, mp, rev, mp), fwd, mp);
+      search(hak_guided_scratch_carve(c->guided, (c->cfg.batch + 1) / 2, mp, rev, mp), fwd, mp);
       hak_launch_knn2_finish(c->stream, d_points, d_points + mp, d_num_pts, 0, 2 * mp, 2 * mp, npairs, fwd, cross_check ? rev : nullptr,
                              mp, ratio_num, ratio_den, cross_check ? 1 : 0, max_dist, d_out, mp, d_counts); }
     if (hipGetLastError() != hipSuccess) return fail(std::string(what) + ": launch failed");
@@ -1214,7 +1249,7 @@ extern "C" int hak_match_guided(hak_ctx* c, hak_point* d_pts1, int n1, const hak
         if (!std::isfinite(H[k])) return fail("H has a non-finite entry");
     return gated_match_single(c, "hak_match_guided", d_pts1, n1, d_pts2, n2, radius, ratio_num, ratio_den, cross_check, max_dist, h_pts1,
                               d_out, count, h_out, [&](hipStream_t st, const HakGuidedScratch& gs, int4* fwd) {
-                                  hak_launch_guided(st, d_pts1, d_pts2, nullptr, nullptr, n1, n2, 0, 0, 1, nullptr, H, radius,
+                                  hak_launch_guided(st, d_pts1, d_pts2, nullptr, nullptr, 1, n1, n2, 0, 0, 1, nullptr, H, radius,
                                                     cross_check ? 1 : 0, gs, fwd, 0);
                               });
 }
@@ -1225,8 +1260,8 @@ extern "C" int hak_match_guided_batch(hak_ctx* c, hak_point* d_points, const int
 {
     return gated_match_batch(c, "hak_match_guided_batch", d_points, d_num_pts, npairs, d_H, radius, ratio_num, ratio_den, cross_check,
                              max_dist, d_out, d_counts, [&](const HakGuidedScratch& gs, int4* fwd, long mp) {
-                                 hak_launch_guided(c->stream, d_points, d_points + mp, d_num_pts, d_num_pts + 1, (int)mp, (int)mp, 2 * mp,
-                                                   2 * mp, npairs, d_H, nullptr, radius, cross_check ? 1 : 0, gs, fwd, mp);
+                                 hak_launch_guided(c->stream, d_points, d_points + mp, d_num_pts, d_num_pts + 1, 2, (int)mp, (int)mp,
+                                                   2 * mp, 2 * mp, npairs, d_H, nullptr, radius, cross_check ? 1 : 0, gs, fwd, mp);
                              });
 }
 
@@ -1241,7 +1276,7 @@ extern "C" int hak_match_epipolar(hak_ctx* c, hak_point* d_pts1, int n1, const h
         if (!std::isfinite(F[k])) return fail("F has a non-finite entry");
     return gated_match_single(c, "hak_match_epipolar", d_pts1, n1, d_pts2, n2, radius, ratio_num, ratio_den, cross_check, max_dist, h_pts1,
                               d_out, count, h_out, [&](hipStream_t st, const HakGuidedScratch& gs, int4* fwd) {
-                                  hak_launch_epipolar(st, d_pts1, d_pts2, nullptr, nullptr, n1, n2, 0, 0, 1, nullptr, F, radius,
+                                  hak_launch_epipolar(st, d_pts1, d_pts2, nullptr, nullptr, 1, n1, n2, 0, 0, 1, nullptr, F, radius,
                                                       cross_check ? 1 : 0, gs, fwd, 0);
                               });
 }
@@ -1252,8 +1287,8 @@ extern "C" int hak_match_epipolar_batch(hak_ctx* c, hak_point* d_points, const i
 {
     return gated_match_batch(c, "hak_match_epipolar_batch", d_points, d_num_pts, npairs, d_F, radius, ratio_num, ratio_den, cross_check,
                              max_dist, d_out, d_counts, [&](const HakGuidedScratch& gs, int4* fwd, long mp) {
-                                 hak_launch_epipolar(c->stream, d_points, d_points + mp, d_num_pts, d_num_pts + 1, (int)mp, (int)mp, 2 * mp,
-                                                     2 * mp, npairs, d_F, nullptr, radius, cross_check ? 1 : 0, gs, fwd, mp);
+                                 hak_launch_epipolar(c->stream, d_points, d_points + mp, d_num_pts, d_num_pts + 1, 2, (int)mp, (int)mp,
+                                                     2 * mp, 2 * mp, npairs, d_F, nullptr, radius, cross_check ? 1 : 0, gs, fwd, mp);
                              });
 }
 
@@ -1280,30 +1315,16 @@ extern "C" int hak_match_projected(hak_ctx* c, const hak_match_pair* d_A, int nA
     if (nA == 0) return 0;
     if (max_dist <= 0) max_dist = HAK_MAX_DIST;
     if (hak_device_count() == 0) return fail("no HIP device: libhipakaze has no CPU fallback");
-    hipStream_t st = c ? c->stream : nullptr;
-    const long cap2 = n2 > 0 ? n2 : 1;
-    const size_t bytes = hak_guided_scratch_bytes(1, cap2);
-    void* buf = nullptr;
-    if (c) {
-        if (guided_scratch(c, bytes)) return 1;
-        buf = c->guided;
-    } else
-        HIP_TRY(hipMalloc(&buf, bytes));
-    HakMatchScratch* sc = c ? &c->msc : pool_acquire();
-    order_after_null_stream(c, st);
-    if (!hak_match_scratch_reserve(sc, st, 0, 0, 0, (long)nA + cap2, 1)) {
-        if (!c) { pool_release(sc, false); (void)hipFree(buf); }
-        return fail("hak_match_projected: out of device memory for the search scratch");
-    }
+    GatedScratch g(c, n2);
+    if (g.acquire("hak_match_projected", nA, 1)) return 1;
     {
         ProfScope ps(c, HAK_PROF_MATCH);
-        hak_launch_projected(st, d_A, nA, nullptr, 1, nA, nA, d_maskA, d_xyzA, d_desc, n_desc > 0 ? n_desc : 1, nullptr, 1, n_desc, n_desc,
-                             d_pts2, cap2, nullptr, 1, n2, 1, nullptr, HAK_VIEW_IDENTITY, 0, Rt, *K, radius, ratio_num, ratio_den,
-                             cross_check ? 1 : 0, max_dist, hak_guided_scratch_carve(buf, 1, cap2, sc->knn + nA, 0), sc->knn, 0, d_out, nA,
-                             sc->d_cnt);
+        hak_launch_projected(g.st, d_A, nA, nullptr, 1, nA, nA, d_maskA, d_xyzA, d_desc, n_desc > 0 ? n_desc : 1, nullptr, 1, n_desc,
+                             n_desc, d_pts2, g.cap2, nullptr, 1, n2, 1, nullptr, HAK_VIEW_IDENTITY, 0, Rt, *K, radius, ratio_num, ratio_den,
+                             cross_check ? 1 : 0, max_dist, g.carve(nA), g.msc->knn, 0, d_out, nA, g.msc->d_cnt);
     }
-    int rc = single_tail(0, st, "hak_match_projected", "count download", count, sc->d_cnt, sizeof(int), c ? nullptr : buf);
-    if (!c) pool_release(sc, rc == 0);
+    int rc = single_tail(0, g.st, "hak_match_projected", "count download", count, g.msc->d_cnt, sizeof(int));
+    g.ok = rc == 0;
     if (!rc && h_out && *count > 0 &&
         hipMemcpy(h_out, d_out, sizeof(hak_corr3d) * (size_t)*count, hipMemcpyDeviceToHost) != hipSuccess)
         rc = fail("list download");
@@ -1327,17 +1348,12 @@ extern "C" int hak_match_projected_batch(hak_ctx* c, const hak_match_pair* d_A, 
     if (device_view_args(d_views, kind, view_step)) return 1;
     if (projected_args(K, radius, ratio_num, ratio_den)) return 1;
     if (!c) return fail("hak_match_projected_batch needs a context");
-    const long npair_cap = (c->cfg.batch + 1) / 2;
-    if (npairs > npair_cap) return fail("npairs exceeds the context's pair capacity");
+    if (npairs > (c->cfg.batch + 1) / 2) return fail("npairs exceeds the context's pair capacity");
     if (max_dist <= 0) max_dist = HAK_MAX_DIST;
-    const long mp = c->cfg.max_pts;
-    if (!hak_mkey_fits(mp)) return fail("max_pts must stay below 2^20 for the matcher");
-    if (knn_scratch(c)) return 1;
-    if (guided_scratch(c, hak_guided_scratch_bytes(npair_cap, mp))) return 1;
-    order_after_null_stream(c, c->stream);
+    long mp;
+    int4 *fwd, *rev;
+    if (gated_batch_scratch(c, mp, fwd, rev)) return 1;
     const long capA = std::min(std::min(strideA, out_stride), mp), capD = std::min(desc_stride, mp), cap2 = std::min(stride2, mp);
-    int4* fwd = c->knn;
-    int4* rev = c->knn + (size_t)npair_cap * mp;
     { ProfScope ps(c, HAK_PROF_MATCH);
       hak_launch_projected(c->stream, d_A, strideA, d_countsA, count_stepA, 0, capA, d_masksA, d_xyzA, d_desc, desc_stride, d_desc_counts,
                            desc_count_step, 0, capD, d_pts2, stride2, d_counts2, count_step2, (int)cap2, npairs, d_views, kind, view_step,

@@ -579,8 +579,9 @@ int hak_launch_hess_probe(int w, int h, int nimg, int step, int iters, double* m
 static inline int hak_grid_x(int blocks) { return blocks < 1 ? 1 : blocks > 4096 ? 4096 : blocks; }
 
 // ---- the matcher's rules (cuMatch / gHammingMatch akazed.cu:2144-2223 and the 2-NN post-processing), stated once for
-// every kernel of kernels_match.hip, kernels_guided.hip and kernels_epipolar.hip: the packed key, the descriptor words, the record a search leaves and the
-// two accept rules with the fields they write are defined here and nowhere else.
+// every kernel of kernels_match.hip and of the gated matchers (kernels_guided.hip, kernels_epipolar.hip, kernels_projected.hip): the
+// packed key, the descriptor words, the record a search leaves and the two accept rules with the fields they write are defined
+// here and nowhere else.
 // packed key: Hamming distance << 20 | point index.  An unsigned minimum keeps the smallest distance and, among equal distances,
 // the smallest index -- the reference's "first strict minimum in ascending order" (akazed.cu:2176-2187).
 #define HAK_MKEY_BITS 20                        // index bits: a set holds fewer than 2^20 points
@@ -748,41 +749,30 @@ struct HakGuidedScratch {
     int4* rev = nullptr;                        // [npairs][rev_stride] reverse keys, then {rev(j), d, 512, 0} (the 2-NN scratch's reverse half)
     long rev_stride = 0;
 };
-#define GD_N 64                  // cells per axis at most: 4096 LDS counters
-// the grid of one pair, written by k_guided_bin and read by the searches (k_guided_search, k_epipolar_search)
-struct GdGrid {
-    float ox, oy, inv;
-    int nx, ny;
-    int pad[3];
-};
-// the cell of a coordinate on one axis: non-decreasing in x for inv > 0; NaN lands in cell 0 (fmaxf drops it): listed there, and in
-// no gate
-__device__ __forceinline__ int gd_cell(float x, float o, float inv, int n)
-{
-    return (int)fminf(fmaxf(floorf((x - o) * inv), 0.f), (float)(n - 1));
-}
+// (the grid GdGrid / gd_cell and the device code the three searches share: gated_common.h)
 size_t hak_guided_scratch_bytes(long npairs, long pts_cap);
 HakGuidedScratch hak_guided_scratch_carve(void* base, long npairs, long pts_cap, int4* rev, long rev_stride);
 // the two steps the gated searches share: the bin step (train points of npairs pairs into sc's grid of cells of side >= rp; resets
 // the reverse keys) and, after a search, the reverse step (reverse keys -> the records k_knn2_finish reads).  The count of pair k
-// is n2_dev[k * count_step]: 2 in a detect batch of image pairs
+// is n2_dev[k * count_step]: 2 in a detect batch of image pairs.  gd_launch (gated_common.h) runs them around a search kernel
 void hak_launch_guided_bin(hipStream_t st, const hak_point* pts2, const int* n2_dev, int n2_host, long stride2, int npairs, float rp,
-                           const HakGuidedScratch& sc, int count_step = 2);
-void hak_launch_guided_rev(hipStream_t st, const int* n2_dev, int n2_host, int npairs, const HakGuidedScratch& sc, int count_step = 2);
-void hak_launch_guided(hipStream_t st, const hak_point* pts1, const hak_point* pts2, const int* n1_dev, const int* n2_dev, int n1_host,
-                       int n2_host, long stride1, long stride2, int npairs, const hak_homography* d_H, const float* h_H, float radius,
-                       int cross, const HakGuidedScratch& sc, int4* fwd, long fwd_stride);
+                           const HakGuidedScratch& sc, int count_step);
+void hak_launch_guided_rev(hipStream_t st, const int* n2_dev, int n2_host, int npairs, const HakGuidedScratch& sc, int count_step);
+void hak_launch_guided(hipStream_t st, const hak_point* pts1, const hak_point* pts2, const int* n1_dev, const int* n2_dev, int count_step,
+                       int n1_host, int n2_host, long stride1, long stride2, int npairs, const hak_homography* d_H, const float* h_H,
+                       float radius, int cross, const HakGuidedScratch& sc, int4* fwd, long fwd_stride);
 // epipolar guided matching (kernels_epipolar.hip, hak_match_epipolar): as hak_launch_guided with a fundamental matrix per pair
 // (d_F on the device, or NULL: h_F[9] on the host serves the only pair); the same scratch
-void hak_launch_epipolar(hipStream_t st, const hak_point* pts1, const hak_point* pts2, const int* n1_dev, const int* n2_dev, int n1_host,
-                         int n2_host, long stride1, long stride2, int npairs, const hak_fundamental* d_F, const float* h_F, float radius,
-                         int cross, const HakGuidedScratch& sc, int4* fwd, long fwd_stride);
+void hak_launch_epipolar(hipStream_t st, const hak_point* pts1, const hak_point* pts2, const int* n1_dev, const int* n2_dev, int count_step,
+                         int n1_host, int n2_host, long stride1, long stride2, int npairs, const hak_fundamental* d_F, const float* h_F,
+                         float radius, int cross, const HakGuidedScratch& sc, int4* fwd, long fwd_stride);
 // projection-guided matching (kernels_projected.hip, hak_match_projected): landmark m of list A (its point xyzA[3m ..], its descriptor
 // desc[A[m].train]) is projected through a view and K and searched among the train points pts2 near the projection; the same
 // scratch and the same bin and reverse steps as hak_launch_guided.  Counts on the device (countsA[k * stepA], desc_counts[k *
 // desc_step], counts2[k * step2]) or, NULL, the host values for the only list (with device counts n2_host carries the capacity of
-// a train set); capA / capD / sc.pts_cap: what the counts are clamped to.  The view of list k is record k * view_step of `views` (kind: HAK_VIEW_*), or h_view != NULL: these 12 host floats.  The
-// accepted landmarks go to out + k * out_stride in ascending m (out may be NULL: count only), their number to out_counts[k].
+// a train set); capA / capD / sc.pts_cap: what the counts are clamped to.  The view of list k is record k * view_step of `views`
+// (kind: HAK_VIEW_*), or h_view != NULL: these 12 host floats.  The accepted landmarks go to out + k * out_stride in ascending m
+// (out may be NULL: count only), their number to out_counts[k].
 void hak_launch_projected(hipStream_t st, const hak_match_pair* A, long strideA, const int* countsA, int stepA, int nA_host, long capA,
                           const unsigned char* masksA, const float* xyzA, const hak_point* desc, long desc_stride,
                           const int* desc_counts, int desc_step, int nD_host, long capD, const hak_point* pts2, long stride2,

@@ -5,7 +5,8 @@
 // (a, b, c) = F (x, y, 1)^T in image 2 and is searched only among the train points closer than `radius` to that line; 2-NN ratio
 // test and cross-check inside that band.  The train points are binned by kernels_guided.hip's k_guided_bin (hak_launch_guided_bin:
 // the same grid of at most 64 x 64 cells, the same scratch), the reverse keys are turned into records by its k_guided_rev, and the
-// accept rule and the compaction are the 2-NN matcher's finish kernels, unchanged.  New here:
+// accept rule and the compaction are the 2-NN matcher's finish kernels, unchanged.  The view of the scratch, the step a passer
+// goes through (gd_pass) and the launch sequence are gated_common.h's, shared with the other two gated searches.  New here:
 //   k_epipolar_search  one query per thread: the line, then a walk along the line's major axis -- grid rows for a mostly vertical
 //                      line (|a| >= |b|), grid columns otherwise; per row (column) the interval of the other coordinate the band can
 //                      reach, the cells of that interval, the exact float32 gate on every listed candidate, 16 x (v_xor, v_bcnt)
@@ -50,13 +51,11 @@
 // Cost: a 1080p pair with 2 260 points has cells of 30 px and about one point per cell; a query walks up to 64 rows of about
 // three cells each (the homography gate: 3 x 3 cells), tests the float32 gate on every listed candidate and loads the
 // descriptors of the few passers.
-#include "hak_internal.h"
+#include "gated_common.h"
 
 #define EP_L 16384.f             // |coordinate| bound of the rule's domain
 #define EP_DEN_MIN 0x1p-100f     // floor on den = a a + b b
 
-// F of pair `pair`: the device record (batch) or the by-value copy (single call).  A pair has no model when its record says so
-// or any entry of F is non-finite.
 __global__ __launch_bounds__(256) void k_epipolar_search(const hak_point* __restrict__ pts1_base, const hak_point* __restrict__ pts2_base,
                                                           const int* __restrict__ n1_dev, int n1_host, long stride1, long stride2,
                                                           int count_stride, const hak_fundamental* __restrict__ d_F, hak_fundamental Fval,
@@ -67,16 +66,11 @@ __global__ __launch_bounds__(256) void k_epipolar_search(const hak_point* __rest
     const int n1 = n1_dev ? min(n1_dev[pair * count_stride], n1_host) : n1_host;     // (device counts: n1_host is the capacity)
     const hak_point* pts1 = pts1_base + (long)pair * stride1;
     const hak_point* pts2 = pts2_base + (long)pair * stride2;
-    const int* idx = sc.idx + (long)pair * sc.pts_cap;
-    const float2* xy = sc.xy + (long)pair * sc.pts_cap;
-    const int* off = sc.off + (long)pair * (GD_N * GD_N + 1);
-    int4* rev = sc.rev + (long)pair * sc.rev_stride;
     int4* fwd = fwd_base + (long)pair * fwd_stride;
-    const GdGrid g = *reinterpret_cast<const GdGrid*>(sc.grid + (long)pair * 8);
+    const GdView view = gd_view(sc, pair);
+    const GdGrid& g = view.g;
     const hak_fundamental fr = d_F ? d_F[pair] : Fval;
-    bool model = fr.hypothesis >= 0;
-#pragma unroll
-    for (int k = 0; k < 9; k++) model = model && fabsf(fr.F[k]) < INFINITY;     // (false for NaN)
+    const bool model = gd_model(fr.F, fr.hypothesis);
     const double S = 1.0 / (double)g.inv;
     const double mg = S * 0x1p-15 + 1e-3;
 
@@ -88,25 +82,16 @@ __global__ __launch_bounds__(256) void k_epipolar_search(const hak_point* __rest
         const float c = (fr.F[6] * x + fr.F[7] * y) + fr.F[8];
         const float den = a * a + b * b;
         const float r2den = r2 * den;
-        unsigned best = HAK_MKEY_EMPTY, second = HAK_MKEY_EMPTY;
+        GdQuery qs;
         // the rule's domain (every compare is false for NaN); a non-finite c passes no candidate (e is inf or NaN): no search
         if (model && fabsf(x) <= EP_L && fabsf(y) <= EP_L && den >= EP_DEN_MIN && den < INFINITY && fabsf(c) < INFINITY) {
-            unsigned int qd[16];
-            hak_desc_load(pts1 + i, qd);
+            hak_desc_load(pts1 + i, qs.qd);
             auto scan = [&](int kbeg, int kend) {
                 for (int k = kbeg; k < kend; k++) {
-                    const float2 t = xy[k];
+                    const float2 t = view.xy[k];
                     const float e = (a * t.x + b * t.y) + c;
-                    if (fabsf(t.x) <= EP_L && fabsf(t.y) <= EP_L && (e * e) < r2den) {         // the exact gate
-                        const int j = idx[k];
-                        unsigned int td[16];
-                        hak_desc_load(pts2 + j, td);
-                        unsigned d = 0;
-#pragma unroll
-                        for (int w = 0; w < 16; w++) d = hak_bcnt_acc(qd[w] ^ td[w], d);
-                        hak_mkey_two_smallest(best, second, hak_mkey(d, (unsigned)j));
-                        if (cross) atomicMin(reinterpret_cast<unsigned*>(&rev[j].x), hak_mkey(d, (unsigned)i));
-                    }
+                    if (fabsf(t.x) <= EP_L && fabsf(t.y) <= EP_L && (e * e) < r2den)                // the exact gate
+                        gd_pass(qs, view, pts2, k, cross, i);
                 }
             };
             // major coordinate p (walked: y for rows), minor coordinate v = m p + q
@@ -128,29 +113,30 @@ __global__ __launch_bounds__(256) void k_epipolar_search(const hak_point* __rest
                 if (vlo > vhi) continue;
                 const int cv0 = gd_cell((float)vlo, ov, g.inv, nv), cv1 = gd_cell((float)vhi, ov, g.inv, nv);
                 if (rows)                                                     // cells cv0 .. cv1 of a row are consecutive in the sorted list
-                    scan(off[cp * g.nx + cv0], off[cp * g.nx + cv1 + 1]);
+                    scan(view.off[cp * g.nx + cv0], view.off[cp * g.nx + cv1 + 1]);
                 else
-                    for (int cv = cv0; cv <= cv1; cv++) scan(off[cv * g.nx + cp], off[cv * g.nx + cp + 1]);
+                    for (int cv = cv0; cv <= cv1; cv++) scan(view.off[cv * g.nx + cp], view.off[cv * g.nx + cp + 1]);
             }
         }
-        fwd[i] = hak_knn_record(best, second);
+        fwd[i] = hak_knn_record(qs.best, qs.second);
     }
 }
 
 // the forward search of npairs pairs into fwd ({j1, d1, d2, 0} per query) and, cross != 0, rev(j) into sc.rev ({i, d, 512, 0}).
-// With device-side counts n1_host / n2_host carry the capacity of the sets.  d_F: one record per pair on the device, or NULL:
-// h_F[9] (host) serves the only pair.
-void hak_launch_epipolar(hipStream_t st, const hak_point* pts1, const hak_point* pts2, const int* n1_dev, const int* n2_dev, int n1_host,
-                         int n2_host, long stride1, long stride2, int npairs, const hak_fundamental* d_F, const float* h_F, float radius,
-                         int cross, const HakGuidedScratch& sc, int4* fwd, long fwd_stride)
+// With device-side counts (pair k: n1_dev / n2_dev[k * count_step]) n1_host / n2_host carry the capacity of the sets.  d_F: one
+// record per pair on the device, or NULL: h_F[9] (host) serves the only pair.
+void hak_launch_epipolar(hipStream_t st, const hak_point* pts1, const hak_point* pts2, const int* n1_dev, const int* n2_dev, int count_step,
+                         int n1_host, int n2_host, long stride1, long stride2, int npairs, const hak_fundamental* d_F, const float* h_F,
+                         float radius, int cross, const HakGuidedScratch& sc, int4* fwd, long fwd_stride)
 {
     const double R = (double)radius * 1.0001 + 0.01;
     const float r2 = radius * radius;
     hak_fundamental fv{};
     if (!d_F)
         for (int k = 0; k < 9; k++) fv.F[k] = h_F[k];
-    hak_launch_guided_bin(st, pts2, n2_dev, n2_host, stride2, npairs, (float)R, sc);      // cells no smaller than the band's half-width
-    k_epipolar_search<<<dim3(hak_grid_x((n1_host + 255) / 256), npairs), 256, 0, st>>>(pts1, pts2, n1_dev, n1_host, stride1, stride2, 2, d_F,
-                                                                                        fv, R, r2, cross, sc, fwd, fwd_stride);
-    if (cross) hak_launch_guided_rev(st, n2_dev, n2_host, npairs, sc);
+    // (cells no smaller than the band's half-width)
+    gd_launch(st, pts2, n2_dev, n2_host, stride2, count_step, npairs, (float)R, cross, sc, n1_host, [&](dim3 grid) {
+        k_epipolar_search<<<grid, 256, 0, st>>>(pts1, pts2, n1_dev, n1_host, stride1, stride2, count_step, d_F, fv, R, r2, cross, sc, fwd,
+                                                fwd_stride);
+    });
 }

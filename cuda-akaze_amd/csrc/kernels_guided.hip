@@ -11,31 +11,21 @@
 //                    16 x (v_xor, v_bcnt) per passer; the two smallest packed keys (hak_mkey(d, j), hak_internal.h) give j1, d1, d2,
 //                    and an atomicMin of hak_mkey(d, i) on the train point's word gives rev(j) in the same pass
 //   k_guided_rev     reverse keys -> indices, the form k_knn2_finish reads
-// The bin and the reverse step are launchers of their own (hak_launch_guided_bin / _rev): the epipolar search of kernels_epipolar.hip
-// shares them, the scratch carve and the grid.
+// The bin and the reverse step are launchers of their own (hak_launch_guided_bin / _rev): the searches of kernels_epipolar.hip and
+// kernels_projected.hip share them, the scratch carve and the grid.  What a search does once its gate has passed, the walk of a
+// disc gate and the launch sequence are in gated_common.h, for all three.
 // The accept rule and the compaction are the 2-NN matcher's own finish kernels (kernels_match.hip), unchanged.
 //
 // Why the result does not depend on the binning.  The grid only decides WHICH candidates a query looks at; whether a candidate
 // counts is the exact gate, evaluated on the same float32 words the rule names.  So it is enough that every j with G(i, j) is
-// visited (the conservative window, below) -- and the order in which a cell lists its points (atomics) cannot show: the forward
-// result is the two smallest of a set of distinct keys, the reverse one an atomicMin, both order-free.
-//
-// The conservative window.  G(i, j) implies fl(dx dx) < r2 = fl(radius radius) (the other square is >= 0 and rounding is
-// monotone), hence dx dx < radius radius (rounding is monotone), hence |dx| < radius.  dx = fl(x2 - px) is within 2^-24 relative
-// of x2 - px (a float32 difference is exact where it is subnormal), so |x2 - px| < radius (1 + 2^-23) <= r' = fl(radius * 1.0001f).
-// x2 is a float32 and rounding is monotone, so fl(px - r') <= x2 <= fl(px + r').  The cell function of an axis,
-// cell(x) = clamp(floor(fl(fl(x - o) * inv)), 0, N - 1), is a composition of non-decreasing maps (inv > 0), so
-// cell(fl(px - r')) <= cell(x2) <= cell(fl(px + r')): the search walks exactly that range on each axis -- whatever the grid's
-// origin and cell side are, and wherever the points lie (points outside the box fall into border cells).  With a cell side of
-// at least r' that is at most 3 x 3 cells, up to rounding of the cell coordinate far from the origin (then a few more: the loop
-// bounds are the two cell numbers, not a constant).
-#include "hak_internal.h"
+// visited (the conservative window, beside gd_disc in gated_common.h) -- and the order in which a cell lists its points (atomics)
+// cannot show: the forward result is the two smallest of a set of distinct keys, the reverse one an atomicMin, both order-free.
+#include "gated_common.h"
 #include <cstddef>
 
 #define GD_THREADS 1024          // k_guided_bin's block
 #define GD_BOX 1048576.f         // |coordinate| beyond 2^20 does not stretch the box (such points sit in border cells)
 
-// (GD_N, GdGrid and gd_cell: hak_internal.h -- kernels_epipolar.hip searches the same grid)
 __global__ __launch_bounds__(GD_THREADS) void k_guided_bin(const hak_point* __restrict__ pts2_base, const int* __restrict__ n2_dev, int n2_host,
                                                             long stride2, int count_stride, float rp, HakGuidedScratch sc)
 {
@@ -47,10 +37,7 @@ __global__ __launch_bounds__(GD_THREADS) void k_guided_bin(const hak_point* __re
     const int cap = (int)sc.pts_cap;
     const int n2 = min(max(n2_dev ? n2_dev[pair * count_stride] : n2_host, 0), cap);
     const hak_point* pts2 = pts2_base + (long)pair * stride2;
-    int* idx = sc.idx + (long)pair * sc.pts_cap;
-    float2* xy = sc.xy + (long)pair * sc.pts_cap;
-    int* off = sc.off + (long)pair * (GD_N * GD_N + 1);
-    int4* rev = sc.rev + (long)pair * sc.rev_stride;
+    const GdLists l = gd_lists(sc, pair);
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
 
     // ---- bounding box of the finite train points
@@ -60,7 +47,7 @@ __global__ __launch_bounds__(GD_THREADS) void k_guided_bin(const hak_point* __re
         if (fabsf(x) <= GD_BOX && fabsf(y) <= GD_BOX) {               // (false for NaN and inf)
             x0 = fminf(x0, x); x1 = fmaxf(x1, x); y0 = fminf(y0, y); y1 = fmaxf(y1, y);
         }
-        rev[j] = hak_knn_none();                                      // .x: the reverse key, HAK_MKEY_EMPTY = no query gates this point
+        l.rev[j] = hak_knn_none();                                    // .x: the reverse key, HAK_MKEY_EMPTY = no query gates this point
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
@@ -85,7 +72,7 @@ __global__ __launch_bounds__(GD_THREADS) void k_guided_bin(const hak_point* __re
         g.nx = (int)fminf(floorf(ex * g.inv) + 1.f, (float)GD_N);
         g.ny = (int)fminf(floorf(ey * g.inv) + 1.f, (float)GD_N);
         sg = g;
-        *reinterpret_cast<GdGrid*>(sc.grid + (long)pair * 8) = g;
+        *gd_grid_slot(sc, pair) = g;
     }
     __syncthreads();
     const GdGrid g = sg;
@@ -112,10 +99,10 @@ __global__ __launch_bounds__(GD_THREADS) void k_guided_bin(const hak_point* __re
 #pragma unroll
     for (int k = 0; k < 4; k++) {
         const int c = 4 * threadIdx.x + k;
-        if (c < ncell) { off[c] = base; cnt[c] = base; }              // cnt becomes the cell's write cursor
+        if (c < ncell) { l.off[c] = base; cnt[c] = base; }            // cnt becomes the cell's write cursor
         base += v[k];
     }
-    if (threadIdx.x == 0) off[ncell] = n2;
+    if (threadIdx.x == 0) l.off[ncell] = n2;
     __syncthreads();
 
     // ---- scatter (the order inside a cell is arbitrary; see the file header)
@@ -123,12 +110,10 @@ __global__ __launch_bounds__(GD_THREADS) void k_guided_bin(const hak_point* __re
         const float x = pts2[j].x, y = pts2[j].y;
         const int c = gd_cell(y, g.oy, g.inv, g.ny) * g.nx + gd_cell(x, g.ox, g.inv, g.nx);
         const int pos = atomicAdd(&cnt[c], 1);
-        if (pos < cap) { idx[pos] = j; xy[pos] = make_float2(x, y); }   // (pos < n2 <= cap always)
+        if (pos < cap) { l.idx[pos] = j; l.xy[pos] = make_float2(x, y); }   // (pos < n2 <= cap always)
     }
 }
 
-// H of pair `pair`: the device record (batch) or the by-value copy (single call).  A pair has no model when its record says so
-// or any entry of H is non-finite.
 __global__ __launch_bounds__(256) void k_guided_search(const hak_point* __restrict__ pts1_base, const hak_point* __restrict__ pts2_base,
                                                         const int* __restrict__ n1_dev, int n1_host, long stride1, long stride2,
                                                         int count_stride, const hak_homography* __restrict__ d_H, hak_homography Hval,
@@ -139,16 +124,10 @@ __global__ __launch_bounds__(256) void k_guided_search(const hak_point* __restri
     const int n1 = n1_dev ? min(n1_dev[pair * count_stride], n1_host) : n1_host;     // (device counts: n1_host is the capacity)
     const hak_point* pts1 = pts1_base + (long)pair * stride1;
     const hak_point* pts2 = pts2_base + (long)pair * stride2;
-    const int* idx = sc.idx + (long)pair * sc.pts_cap;
-    const float2* xy = sc.xy + (long)pair * sc.pts_cap;
-    const int* off = sc.off + (long)pair * (GD_N * GD_N + 1);
-    int4* rev = sc.rev + (long)pair * sc.rev_stride;
     int4* fwd = fwd_base + (long)pair * fwd_stride;
-    const GdGrid g = *reinterpret_cast<const GdGrid*>(sc.grid + (long)pair * 8);
+    const GdView view = gd_view(sc, pair);
     const hak_homography hr = d_H ? d_H[pair] : Hval;
-    bool model = hr.hypothesis >= 0;
-#pragma unroll
-    for (int k = 0; k < 9; k++) model = model && fabsf(hr.H[k]) < INFINITY;     // (false for NaN)
+    const bool model = gd_model(hr.H, hr.hypothesis);
 
     for (int i = blockIdx.x * 256 + threadIdx.x; i < n1; i += gridDim.x * 256) {
         const float x = pts1[i].x, y = pts1[i].y;
@@ -157,33 +136,13 @@ __global__ __launch_bounds__(256) void k_guided_search(const hak_point* __restri
         const float u = (hr.H[0] * x + hr.H[1] * y) + hr.H[2];
         const float v = (hr.H[3] * x + hr.H[4] * y) + hr.H[5];
         const float px = u / wz, py = v / wz;
-        unsigned best = HAK_MKEY_EMPTY, second = HAK_MKEY_EMPTY;
-        // a non-finite projection is in no gate (every compare below would be false): it does not search
+        GdQuery q;
+        // a non-finite projection is in no gate (every compare of the walk would be false): it does not search
         if (model && wz > 0.f && fabsf(px) < INFINITY && fabsf(py) < INFINITY) {
-            unsigned int qd[16];
-            hak_desc_load(pts1 + i, qd);
-            const int cx0 = gd_cell(px - rp, g.ox, g.inv, g.nx), cx1 = gd_cell(px + rp, g.ox, g.inv, g.nx);
-            const int cy0 = gd_cell(py - rp, g.oy, g.inv, g.ny), cy1 = gd_cell(py + rp, g.oy, g.inv, g.ny);
-            for (int cy = cy0; cy <= cy1; cy++) {
-                // cells cx0 .. cx1 of a row are consecutive in the sorted list
-                const int kend = off[cy * g.nx + cx1 + 1];
-                for (int k = off[cy * g.nx + cx0]; k < kend; k++) {
-                    const float2 t = xy[k];
-                    const float dx = t.x - px, dy = t.y - py;
-                    if ((dx * dx) + (dy * dy) < r2) {                                  // the exact gate
-                        const int j = idx[k];
-                        unsigned int td[16];
-                        hak_desc_load(pts2 + j, td);
-                        unsigned d = 0;
-#pragma unroll
-                        for (int w = 0; w < 16; w++) d = hak_bcnt_acc(qd[w] ^ td[w], d);
-                        hak_mkey_two_smallest(best, second, hak_mkey(d, (unsigned)j));
-                        if (cross) atomicMin(reinterpret_cast<unsigned*>(&rev[j].x), hak_mkey(d, (unsigned)i));
-                    }
-                }
-            }
+            hak_desc_load(pts1 + i, q.qd);
+            gd_disc(q, view, pts2, px, py, rp, r2, cross, i);
         }
-        fwd[i] = hak_knn_record(best, second);
+        fwd[i] = hak_knn_record(q.best, q.second);
     }
 }
 
@@ -229,18 +188,18 @@ void hak_launch_guided_rev(hipStream_t st, const int* n2_dev, int n2_host, int n
 }
 
 // the forward search of npairs pairs into fwd ({j1, d1, d2, 0} per query) and, cross != 0, rev(j) into sc.rev ({i, d, 512, 0}).
-// With device-side counts n1_host / n2_host carry the capacity of the sets.  d_H: one record per pair on the device, or NULL:
-// h_H[9] (host) serves the only pair.
-void hak_launch_guided(hipStream_t st, const hak_point* pts1, const hak_point* pts2, const int* n1_dev, const int* n2_dev, int n1_host,
-                       int n2_host, long stride1, long stride2, int npairs, const hak_homography* d_H, const float* h_H, float radius,
-                       int cross, const HakGuidedScratch& sc, int4* fwd, long fwd_stride)
+// With device-side counts (pair k: n1_dev / n2_dev[k * count_step]) n1_host / n2_host carry the capacity of the sets.  d_H: one
+// record per pair on the device, or NULL: h_H[9] (host) serves the only pair.
+void hak_launch_guided(hipStream_t st, const hak_point* pts1, const hak_point* pts2, const int* n1_dev, const int* n2_dev, int count_step,
+                       int n1_host, int n2_host, long stride1, long stride2, int npairs, const hak_homography* d_H, const float* h_H,
+                       float radius, int cross, const HakGuidedScratch& sc, int4* fwd, long fwd_stride)
 {
     const float rp = radius * 1.0001f, r2 = radius * radius;
     hak_homography hv{};
     if (!d_H)
         for (int k = 0; k < 9; k++) hv.H[k] = h_H[k];
-    hak_launch_guided_bin(st, pts2, n2_dev, n2_host, stride2, npairs, rp, sc);
-    k_guided_search<<<dim3(hak_grid_x((n1_host + 255) / 256), npairs), 256, 0, st>>>(pts1, pts2, n1_dev, n1_host, stride1, stride2, 2, d_H, hv,
-                                                                                      rp, r2, cross, sc, fwd, fwd_stride);
-    if (cross) hak_launch_guided_rev(st, n2_dev, n2_host, npairs, sc);
+    gd_launch(st, pts2, n2_dev, n2_host, stride2, count_step, npairs, rp, cross, sc, n1_host, [&](dim3 grid) {
+        k_guided_search<<<grid, 256, 0, st>>>(pts1, pts2, n1_dev, n1_host, stride1, stride2, count_step, d_H, hv, rp, r2, cross, sc, fwd,
+                                              fwd_stride);
+    });
 }

@@ -13,9 +13,10 @@
 //   k_projected_finish  one block per list walks it in chunks of its block size, as k_link_gather compacts: hak_knn2_rule as it
 //                       stands, then an ordered compaction of the accepted landmarks into hak_corr3d records in ascending m.  No
 //                       atomics on the output, so the list does not depend on scheduling; it writes the count and nothing past it
-// The gate is the guided matcher's gate in (px, py), so the result does not depend on the binning for the reasons given in the
-// header of kernels_guided.hip, and its conservative-window argument carries over unchanged: the walk below is the same walk.
-#include "hak_internal.h"
+// The gate is the guided matcher's gate in (px, py) and the walk is the same function, gd_disc (gated_common.h, with its
+// conservative-window argument), so the result does not depend on the binning for the reasons given in the header of
+// kernels_guided.hip.
+#include "gated_common.h"
 #include "points_common.h"
 
 #define PJ_FINISH 1024           // k_projected_finish's block
@@ -44,18 +45,14 @@ __global__ __launch_bounds__(256) void k_projected_search(const hak_match_pair* 
     const float* xyz = xyz_base + 3 * ((long)pair * strideA);
     const hak_point* desc = desc_base + (long)pair * desc_stride;
     const hak_point* pts2 = pts2_base + (long)pair * stride2;
-    const int* idx = sc.idx + (long)pair * sc.pts_cap;
-    const float2* xy = sc.xy + (long)pair * sc.pts_cap;
-    const int* off = sc.off + (long)pair * (GD_N * GD_N + 1);
-    int4* rev = sc.rev + (long)pair * sc.rev_stride;
     int4* fwd = fwd_base + (long)pair * fwd_stride;
-    const GdGrid g = *reinterpret_cast<const GdGrid*>(sc.grid + (long)pair * 8);
+    const GdView view = gd_view(sc, pair);
     float M[12];
     const bool model = pt_view(views, kind, view_step, pair, cam.view, M);      // (block-uniform)
     const hak_intrinsics K = cam.K;
 
     for (int m = blockIdx.x * 256 + threadIdx.x; m < nA; m += gridDim.x * 256) {
-        unsigned best = HAK_MKEY_EMPTY, second = HAK_MKEY_EMPTY;
+        GdQuery q;
         const int e = A[m].train;
         if (model && e >= 0 && e < nD && (!mk || mk[m] != 0)) {
             const float X = xyz[3 * (long)m], Y = xyz[3 * (long)m + 1], Z = xyz[3 * (long)m + 2];
@@ -66,33 +63,13 @@ __global__ __launch_bounds__(256) void k_projected_search(const hak_match_pair* 
             const float zc = ((M[6] * X + M[7] * Y) + M[8] * Z) + M[11];
             const float px = (K.fx * (xc / zc)) + K.cx;
             const float py = (K.fy * (yc / zc)) + K.cy;
-            // a non-finite projection is in no gate (every compare below would be false): it does not search
+            // a non-finite projection is in no gate (every compare of the walk would be false): it does not search
             if (zc > 0.f && fabsf(px) < INFINITY && fabsf(py) < INFINITY) {
-                unsigned int qd[16];
-                hak_desc_load(desc + e, qd);
-                const int cx0 = gd_cell(px - rp, g.ox, g.inv, g.nx), cx1 = gd_cell(px + rp, g.ox, g.inv, g.nx);
-                const int cy0 = gd_cell(py - rp, g.oy, g.inv, g.ny), cy1 = gd_cell(py + rp, g.oy, g.inv, g.ny);
-                for (int cy = cy0; cy <= cy1; cy++) {
-                    // cells cx0 .. cx1 of a row are consecutive in the sorted list
-                    const int kend = off[cy * g.nx + cx1 + 1];
-                    for (int k = off[cy * g.nx + cx0]; k < kend; k++) {
-                        const float2 t = xy[k];
-                        const float dx = t.x - px, dy = t.y - py;
-                        if ((dx * dx) + (dy * dy) < r2) {                                  // the exact gate
-                            const int j = idx[k];
-                            unsigned int td[16];
-                            hak_desc_load(pts2 + j, td);
-                            unsigned d = 0;
-#pragma unroll
-                            for (int w = 0; w < 16; w++) d = hak_bcnt_acc(qd[w] ^ td[w], d);
-                            hak_mkey_two_smallest(best, second, hak_mkey(d, (unsigned)j));
-                            if (cross) atomicMin(reinterpret_cast<unsigned*>(&rev[j].x), hak_mkey(d, (unsigned)m));
-                        }
-                    }
-                }
+                hak_desc_load(desc + e, q.qd);
+                gd_disc(q, view, pts2, px, py, rp, r2, cross, m);
             }
         }
-        fwd[m] = hak_knn_record(best, second);
+        fwd[m] = hak_knn_record(q.best, q.second);
     }
 }
 
@@ -155,11 +132,11 @@ void hak_launch_projected(hipStream_t st, const hak_match_pair* A, long strideA,
     cam.K = K;
     for (int k = 0; k < 12; k++) cam.view[k] = h_view ? h_view[k] : 0.f;
     const int most = (int)(countsA ? capA : nA_host);                 // (device counts: the capacity of a list)
-    hak_launch_guided_bin(st, pts2, counts2, n2_host, stride2, npairs, rp, sc, step2);
-    k_projected_search<<<dim3(hak_grid_x((most + 255) / 256), npairs), 256, 0, st>>>(
-        A, strideA, countsA, stepA, nA_host, capA, masksA, xyzA, desc, desc_stride, desc_counts, desc_step, nD_host, capD, pts2, stride2,
-        views, h_view ? PT_VIEW_HOST : kind, view_step, cam, rp, r2, cross, sc, fwd, fwd_stride);
-    if (cross) hak_launch_guided_rev(st, counts2, n2_host, npairs, sc, step2);
+    gd_launch(st, pts2, counts2, n2_host, stride2, step2, npairs, rp, cross, sc, most, [&](dim3 grid) {
+        k_projected_search<<<grid, 256, 0, st>>>(A, strideA, countsA, stepA, nA_host, capA, masksA, xyzA, desc, desc_stride, desc_counts,
+                                                 desc_step, nD_host, capD, pts2, stride2, views, h_view ? PT_VIEW_HOST : kind, view_step,
+                                                 cam, rp, r2, cross, sc, fwd, fwd_stride);
+    });
     k_projected_finish<<<npairs, PJ_FINISH, 0, st>>>(countsA, stepA, nA_host, capA, xyzA, strideA, pts2, stride2, fwd, fwd_stride, sc.rev,
                                                      sc.rev_stride, ratio_num, ratio_den, cross, max_dist, out, out_stride, out_counts);
 }

@@ -51,6 +51,23 @@ namespace
         void xyz_to(float* h) const { if (d_xyz && hak_memcpy_d2h(h, d_xyz, (long)(sizeof(float) * 3 * (size_t)n))) fail("download"); }
         void fail(const char* step) const { die((std::string(name) + " " + step).c_str()); }
     };
+
+    // the call behind cuMatchGuided and cuMatchEpipolar: `entry` re-matches result1 against result2 under the nine floats of `model`;
+    // `name` is the wrapper's, for the messages
+    int match_gated(const char* name, decltype(&hak_match_guided) entry, akaze::AkazeData& result1, akaze::AkazeData& result2,
+                    const float model[9], hak_match_pair* matches, float radius, int ratio_num, int ratio_den, bool cross_check)
+    {
+        int count = 0;
+        hak_match_pair* d_out = nullptr;
+        const int cap = result1.num_pts > 0 ? result1.num_pts : 1;
+        if (matches && hipMalloc((void**)&d_out, sizeof(hak_match_pair) * (size_t)cap) != hipSuccess)
+            die((std::string(name) + " alloc").c_str());
+        if (entry(NULL, result1.d_data, result1.num_pts, result2.d_data, result2.num_pts, model, radius, ratio_num, ratio_den,
+                  cross_check ? 1 : 0, 0, result1.h_data, d_out, &count, matches))
+            die(name);
+        if (d_out) (void)hipFree(d_out);
+        return count;
+    }
 }
 
 namespace akaze
@@ -112,29 +129,13 @@ namespace akaze
     int cuMatchGuided(AkazeData& result1, AkazeData& result2, const float H[9], hak_match_pair* matches, float radius, int ratio_num,
                       int ratio_den, bool cross_check)
     {
-        int count = 0;
-        hak_match_pair* d_out = nullptr;
-        const int cap = result1.num_pts > 0 ? result1.num_pts : 1;
-        if (matches && hipMalloc((void**)&d_out, sizeof(hak_match_pair) * (size_t)cap) != hipSuccess) die("cuMatchGuided alloc");
-        if (hak_match_guided(NULL, result1.d_data, result1.num_pts, result2.d_data, result2.num_pts, H, radius, ratio_num, ratio_den,
-                             cross_check ? 1 : 0, 0, result1.h_data, d_out, &count, matches))
-            die("cuMatchGuided");
-        if (d_out) (void)hipFree(d_out);
-        return count;
+        return match_gated("cuMatchGuided", hak_match_guided, result1, result2, H, matches, radius, ratio_num, ratio_den, cross_check);
     }
 
     int cuMatchEpipolar(AkazeData& result1, AkazeData& result2, const float F[9], hak_match_pair* matches, float radius, int ratio_num,
                         int ratio_den, bool cross_check)
     {
-        int count = 0;
-        hak_match_pair* d_out = nullptr;
-        const int cap = result1.num_pts > 0 ? result1.num_pts : 1;
-        if (matches && hipMalloc((void**)&d_out, sizeof(hak_match_pair) * (size_t)cap) != hipSuccess) die("cuMatchEpipolar alloc");
-        if (hak_match_epipolar(NULL, result1.d_data, result1.num_pts, result2.d_data, result2.num_pts, F, radius, ratio_num, ratio_den,
-                               cross_check ? 1 : 0, 0, result1.h_data, d_out, &count, matches))
-            die("cuMatchEpipolar");
-        if (d_out) (void)hipFree(d_out);
-        return count;
+        return match_gated("cuMatchEpipolar", hak_match_epipolar, result1, result2, F, matches, radius, ratio_num, ratio_den, cross_check);
     }
 
     int cuFindHomography(const hak_match_pair* matches, int n, float H[9], unsigned char* inlier_mask, int iterations, float threshold,

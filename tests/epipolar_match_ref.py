@@ -1,10 +1,10 @@
 """The numpy statement of epipolar guided matching (include/hipakaze.h, hak_match_epipolar): float32 operations in the stated order,
-no FMA (numpy rounds every array operation to float32), the accept rule in Python integers.  The distance, the packed keys and the
-record layout are those of tests/guided_match_ref.py; only the gate differs.  The checker of tests/test_gpu_epipolar_match.py;
-tests/test_epipolar_match_cpu.py checks it against a plain double loop."""
+no FMA (numpy rounds every array operation to float32), the accept rule in Python integers.  The distance, the packed keys, the
+record layout and everything else behind the gate are those of tests/guided_match_ref.py (match_gated); only the gate differs.
+The checker of tests/test_gpu_epipolar_match.py; tests/test_epipolar_match_cpu.py checks it against a plain double loop."""
 import numpy as np
 
-from guided_match_ref import MATCH_PAIR_DTYPE, NONE, hamming
+from guided_match_ref import MATCH_PAIR_DTYPE, NONE, hamming, match_gated  # noqa: F401  (re-exported)
 
 L = np.float32(16384.0)
 DEN_MIN = np.float32(2.0 ** -100)
@@ -38,39 +38,4 @@ def match_epipolar(pts1, pts2, F, radius, ratio=(4, 5), cross_check=True, max_di
     """returns (out, pairs, why): out = a copy of pts1 with match / distance / match_x / match_y as the call writes them, pairs = the
     accepted matches in ascending query order, why[i] = 0 accepted, 1 J_i empty, 2 d1 >= max_dist, 3 ratio test, 4 cross-check alone.
     dist: hamming(pts1, pts2) when the caller has it.  model = False: a batch pair without a model (every query rejected)."""
-    n1, n2 = len(pts1), len(pts2)
-    max_dist = 96 if max_dist <= 0 else int(max_dist)
-    num, den = int(ratio[0]), int(ratio[1])
-    out = pts1.copy()
-    out["match"], out["distance"], out["match_x"], out["match_y"] = -1, -1, -1.0, -1.0
-    why = np.ones(n1, np.int32)
-    pairs = []
-    if n1 and n2 and model:
-        g = gate(pts1, pts2, F, radius)
-        d = (hamming(pts1, pts2) if dist is None else dist).astype(np.int64)
-        fkey = np.where(g, (d << 20) | np.arange(n2, dtype=np.int64)[None, :], NONE)
-        rkey = np.where(g, (d << 20) | np.arange(n1, dtype=np.int64)[:, None], NONE)
-        k1 = fkey.min(axis=1)
-        j1 = (k1 & 0xFFFFF).astype(np.int64)
-        rest = fkey.copy()
-        rest[np.arange(n1), j1] = NONE                                   # J_i \ {j1}
-        k2 = rest.min(axis=1)
-        rev = rkey.min(axis=0)
-        for i in range(n1):
-            if k1[i] == NONE:
-                continue
-            d1 = int(k1[i] >> 20)
-            d2 = 512 if k2[i] == NONE else int(k2[i] >> 20)
-            j = int(j1[i])
-            if not d1 < max_dist:
-                why[i] = 2
-            elif not d1 * den < d2 * num:
-                why[i] = 3
-            elif cross_check and int(rev[j] & 0xFFFFF) != i:
-                why[i] = 4
-            else:
-                why[i] = 0
-                out["match"][i], out["distance"][i] = j, d1
-                out["match_x"][i], out["match_y"][i] = pts2["x"][j], pts2["y"][j]
-                pairs.append((i, j, d1, d2, pts1["x"][i], pts1["y"][i], pts2["x"][j], pts2["y"][j]))
-    return out, np.array(pairs, MATCH_PAIR_DTYPE), why
+    return match_gated(pts1, pts2, lambda: gate(pts1, pts2, F, radius), ratio, cross_check, max_dist, dist, model)

@@ -37,34 +37,32 @@ def gate(pts1, pts2, H, radius):
         return (wz > 0)[:, None] & ((dx * dx) + (dy * dy) < r2)
 
 
-def match_guided(pts1, pts2, H, radius, ratio=(4, 5), cross_check=True, max_dist=0, dist=None, model=True):
-    """returns (out, pairs, why): out = a copy of pts1 with match / distance / match_x / match_y as the call writes them, pairs = the
-    accepted matches in ascending query order, why[i] = 0 accepted, 1 J_i empty, 2 d1 >= max_dist, 3 ratio test, 4 cross-check alone.
-    dist: hamming(pts1, pts2) when the caller has it.  model = False: a batch pair without a model (every query rejected)."""
-    n1, n2 = len(pts1), len(pts2)
+def keys(g, d):
+    """the packed keys of a gate matrix g (nq, n2) bool and a distance matrix d (nq, n2): forward keys d << 20 | j and reverse keys
+    d << 20 | i where g holds, NONE elsewhere -> (k1, k2, rev): per query the smallest and the second smallest forward key over J_i,
+    per train point the smallest reverse key over the queries that gate it"""
+    nq, n2 = g.shape
+    d = np.asarray(d).astype(np.int64) << 20
+    fkey = np.where(g, d | np.arange(n2, dtype=np.int64)[None, :], NONE)
+    rev = np.where(g, d | np.arange(nq, dtype=np.int64)[:, None], NONE).min(axis=0)
+    k1 = fkey.min(axis=1)
+    fkey[np.arange(nq), k1 & 0xFFFFF] = NONE                             # J_i \ {j1}
+    return k1, fkey.min(axis=1), rev
+
+
+def decide(found, nq, ratio=(4, 5), cross_check=True, max_dist=0):
+    """the accept decision from keys()'s result (None: nothing can be accepted) -> (why, acc): why[i] = 0 accepted, 1 J_i empty,
+    2 d1 >= max_dist, 3 ratio test, 4 cross-check alone; acc = the accepted (i, j1, d1, d2) in ascending i"""
     max_dist = 96 if max_dist <= 0 else int(max_dist)
     num, den = int(ratio[0]), int(ratio[1])
-    out = pts1.copy()
-    out["match"], out["distance"], out["match_x"], out["match_y"] = -1, -1, -1.0, -1.0
-    why = np.ones(n1, np.int32)
-    pairs = []
-    if n1 and n2 and model:
-        g = gate(pts1, pts2, H, radius)
-        d = (hamming(pts1, pts2) if dist is None else dist).astype(np.int64)
-        fkey = np.where(g, (d << 20) | np.arange(n2, dtype=np.int64)[None, :], NONE)
-        rkey = np.where(g, (d << 20) | np.arange(n1, dtype=np.int64)[:, None], NONE)
-        k1 = fkey.min(axis=1)
-        j1 = (k1 & 0xFFFFF).astype(np.int64)
-        rest = fkey.copy()
-        rest[np.arange(n1), j1] = NONE                                   # J_i \ {j1}
-        k2 = rest.min(axis=1)
-        rev = rkey.min(axis=0)
-        for i in range(n1):
-            if k1[i] == NONE:
-                continue
+    why = np.ones(nq, np.int32)
+    acc = []
+    if found is not None:
+        k1, k2, rev = found
+        for i in np.nonzero(k1 != NONE)[0]:
             d1 = int(k1[i] >> 20)
             d2 = 512 if k2[i] == NONE else int(k2[i] >> 20)
-            j = int(j1[i])
+            j = int(k1[i] & 0xFFFFF)
             if not d1 < max_dist:
                 why[i] = 2
             elif not d1 * den < d2 * num:
@@ -73,7 +71,27 @@ def match_guided(pts1, pts2, H, radius, ratio=(4, 5), cross_check=True, max_dist
                 why[i] = 4
             else:
                 why[i] = 0
-                out["match"][i], out["distance"][i] = j, d1
-                out["match_x"][i], out["match_y"][i] = pts2["x"][j], pts2["y"][j]
-                pairs.append((i, j, d1, d2, pts1["x"][i], pts1["y"][i], pts2["x"][j], pts2["y"][j]))
+                acc.append((int(i), j, d1, d2))
+    return why, acc
+
+
+def match_gated(pts1, pts2, gate_of, ratio, cross_check, max_dist, dist, model):
+    """match_guided / match_epipolar behind their gates: gate_of() gives the (n1, n2) gate matrix"""
+    n1, n2 = len(pts1), len(pts2)
+    out = pts1.copy()
+    out["match"], out["distance"], out["match_x"], out["match_y"] = -1, -1, -1.0, -1.0
+    found = keys(gate_of(), hamming(pts1, pts2) if dist is None else dist) if n1 and n2 and model else None
+    why, acc = decide(found, n1, ratio, cross_check, max_dist)
+    pairs = []
+    for i, j, d1, d2 in acc:
+        out["match"][i], out["distance"][i] = j, d1
+        out["match_x"][i], out["match_y"][i] = pts2["x"][j], pts2["y"][j]
+        pairs.append((i, j, d1, d2, pts1["x"][i], pts1["y"][i], pts2["x"][j], pts2["y"][j]))
     return out, np.array(pairs, MATCH_PAIR_DTYPE), why
+
+
+def match_guided(pts1, pts2, H, radius, ratio=(4, 5), cross_check=True, max_dist=0, dist=None, model=True):
+    """returns (out, pairs, why): out = a copy of pts1 with match / distance / match_x / match_y as the call writes them, pairs = the
+    accepted matches in ascending query order, why[i] = 0 accepted, 1 J_i empty, 2 d1 >= max_dist, 3 ratio test, 4 cross-check alone.
+    dist: hamming(pts1, pts2) when the caller has it.  model = False: a batch pair without a model (every query rejected)."""
+    return match_gated(pts1, pts2, lambda: gate(pts1, pts2, H, radius), ratio, cross_check, max_dist, dist, model)

@@ -5,7 +5,7 @@ tests/test_gpu_projected_match.py; tests/test_projected_match_cpu.py checks it a
 The checker only -- the product never calls it."""
 import numpy as np
 
-from guided_match_ref import NONE, hamming
+from guided_match_ref import decide, hamming, keys
 from pnp_ref import CORR3D_DTYPE
 from pose_ref import intrinsics
 from triangulate_ref import view
@@ -44,8 +44,6 @@ def gate(A, mask, xyz, n_desc, T, M, K, radius):
         return (eligible(A, mask, n_desc) & (zc > 0))[:, None] & ((dx * dx) + (dy * dy) < r2)
 
 
-
-
 def distances(A, mask, D, T):
     """step 4: (nA, n2) int32, d(m, j) for the eligible landmarks (0 elsewhere: such a row is in no gate)"""
     dist = np.zeros((len(A), len(T)), np.int32)
@@ -65,40 +63,16 @@ def search(A, mask, xyz, D, T, v, K, radius, dist=None):
     if not (nA and n2 and model):
         return None
     g = gate(A, mask, np.asarray(xyz, np.float32).reshape(nA, 3), len(D), T, M, K, radius)
-    d = (distances(A, mask, D, T) if dist is None else np.asarray(dist)).astype(np.int64) << 20
-    fkey = np.where(g, d | np.arange(n2, dtype=np.int64)[None, :], NONE)
-    rev = np.where(g, d | np.arange(nA, dtype=np.int64)[:, None], NONE).min(axis=0)
-    k1 = fkey.min(axis=1)
-    fkey[np.arange(nA), k1 & 0xFFFFF] = NONE                             # J_m \ {j1}
-    return k1, fkey.min(axis=1), rev
+    return keys(g, distances(A, mask, D, T) if dist is None else dist)
 
 
 def accept(found, xyz, T, ratio=(4, 5), cross_check=True, max_dist=0):
     """the accept rule and the output of step 6 from search()'s result -> (corr, why) as match_projected returns them"""
     xyz = np.asarray(xyz, np.float32).reshape(-1, 3)
-    nA = len(xyz)
-    max_dist = 96 if max_dist <= 0 else int(max_dist)
-    num, den = int(ratio[0]), int(ratio[1])
-    why = np.ones(nA, np.int32)
-    acc = []
-    if found is not None:
-        k1, k2, rev = found
-        for m in np.nonzero(k1 != NONE)[0]:
-            d1 = int(k1[m] >> 20)
-            d2 = 512 if k2[m] == NONE else int(k2[m] >> 20)
-            j = int(k1[m] & 0xFFFFF)
-            if not d1 < max_dist:
-                why[m] = 2
-            elif not d1 * den < d2 * num:
-                why[m] = 3
-            elif cross_check and int(rev[j] & 0xFFFFF) != m:
-                why[m] = 4
-            else:
-                why[m] = 0
-                acc.append((m, j))
+    why, acc = decide(found, len(xyz), ratio, cross_check, max_dist)
     out = np.zeros(len(acc), CORR3D_DTYPE)
     if acc:
-        ms, js = np.array(acc, np.int64).T
+        ms, js = np.array(acc, np.int64).T[:2]
         for k, f in enumerate(("X", "Y", "Z")):                         # the words, copied
             out[f].view(np.uint32)[:] = xyz[ms, k].view(np.uint32)
         out["u"], out["v"] = T["x"][js], T["y"][js]
