@@ -119,6 +119,8 @@ SYMBOLS = {
     "hak_refine_fundamental_batch": (C.c_int, [_vp, _vp, C.c_long, _vp, C.c_int, C.c_float, C.c_int, _vp, _vp]),
     "hak_recover_pose": (C.c_int, [_vp, _vp, C.c_int, _fp, _vp, _vp, C.c_float, C.c_float, _vp, _vp, _vp]),
     "hak_recover_pose_batch": (C.c_int, [_vp, _vp, C.c_long, _vp, C.c_int, _vp, _vp, _vp, C.c_float, C.c_float, _vp, _vp, _vp]),
+    "hak_refine_pose": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, C.c_float, C.c_float, C.c_int, _vp, _vp, _vp]),
+    "hak_refine_pose_batch": (C.c_int, [_vp, _vp, C.c_long, _vp, C.c_int, _vp, _vp, C.c_float, C.c_float, C.c_int, _vp, _vp, _vp]),
     "hak_link_tracks": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _ip, _vp]),
     "hak_link_tracks_batch": (C.c_int, [_vp, _vp, C.c_long, _vp, C.c_int, _vp, _vp, _vp, C.c_long, _vp, C.c_int, C.c_int, _vp, C.c_long, _vp]),
     "hak_solve_pnp": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, C.c_float, C.c_uint, _vp, _vp]),
@@ -749,6 +751,23 @@ def recoverPose(matches, F_or_record, K1, K2=None, threshold=1.0, max_depth=floa
     out = np.zeros((), POSE_DTYPE)
     check(lib.hak_recover_pose(ctx, d_m.data_ptr(), n, f.ctypes.data_as(_fp), k1.ctypes.data, k2.ctypes.data, float(threshold),
                                float(max_depth), d_mask.data_ptr(), d_xyz.data_ptr(), out.ctypes.data))
+    return (out,) + _out_host(n, d_mask, d_xyz)
+
+
+def refinePose(matches, K1, record, K2=None, threshold=1.0, max_depth=float("inf"), rounds=3, akazer=None):
+    """Calibrated Gauss-Newton refit of a relative pose over the matches that count under it, iterated up to `rounds` (1..8) times
+    (hipakaze.h hak_refine_pose), on the device.  `matches` as findHomography's; K1, K2, max_depth as recoverPose's; `record`: a
+    POSE_DTYPE record, recoverPose's or an earlier refit's (it is not modified).  Returns (record, mask uint8 (n,), xyz float32
+    (n, 3)) as recoverPose does, under the refitted pose: record["candidate"] == 4 when a refit was accepted, and
+    record["in_front"] is never below the input pose's count under its own F at `threshold`."""
+    ctx = _ctx_of(akazer)
+    d_m, n = _device_records(matches, MATCH_PAIR_DTYPE)
+    k1 = intrinsics(K1)
+    k2 = k1 if K2 is None else intrinsics(K2)
+    d_mask, d_xyz = _out_buffers(n, xyz=True)
+    out = np.array(record, POSE_DTYPE).reshape(())
+    check(lib.hak_refine_pose(ctx, d_m.data_ptr(), n, k1.ctypes.data, k2.ctypes.data, float(threshold), float(max_depth), int(rounds),
+                              d_mask.data_ptr(), d_xyz.data_ptr(), out.ctypes.data))
     return (out,) + _out_host(n, d_mask, d_xyz)
 
 

@@ -1,6 +1,6 @@
 // geom_common.h -- device arithmetic shared by the geometric-verification kernels (kernels_homography.hip, kernels_fundamental.hip,
-// kernels_fundrefit.hip, kernels_pose.hip, kernels_pnp.hip, kernels_pnprefit.hip, kernels_triangulate.hip): the wave sum whose
-// order the refits' rules fix,
+// kernels_fundrefit.hip, kernels_pose.hip, kernels_poserefit.hip, kernels_pnp.hip, kernels_pnprefit.hip,
+// kernels_triangulate.hip): the wave sum whose order the refits' rules fix,
 // the match-list record load and count clamp of all of them, the 3 x 3 product, the transfer-error test of the homography and the
 // Sampson test of the fundamental matrix, the real roots of a monic cubic by bracketing and bisection (step 5 of
 // hak_find_fundamental, also the critical points of hak_solve_pnp's quartic), and the 3 x 3 cyclic Jacobi of the refit's rule.

@@ -944,6 +944,30 @@ extern "C" int hak_recover_pose_batch(hak_ctx* c, const hak_match_pair* d_matche
     return 0;
 }
 
+// ----------------------------------------------------------- Gauss-Newton refit of a relative pose (kernels_poserefit.hip)
+extern "C" int hak_refine_pose(hak_ctx* c, const hak_match_pair* d_matches, int n, const hak_intrinsics* K1, const hak_intrinsics* K2,
+                               float threshold, float max_depth, int rounds, unsigned char* d_mask, float* d_xyz, hak_pose* h_inout)
+{
+    if (list_args(h_inout, d_matches, n, "d_matches must be 16-byte aligned")) return 1;
+    if (pose_args(K1, K2, threshold, max_depth) || refine_args(threshold, rounds)) return 1;
+    return record_single(c, c, h_inout, h_inout, "pose refit", [&](hipStream_t st, hak_pose* d_rec) {
+        hak_launch_pose_refit(st, d_matches, n > 0 ? n : 1, nullptr, n, 1, *K1, *K2, threshold, max_depth, rounds, d_rec, d_mask, d_xyz);
+    });
+}
+
+extern "C" int hak_refine_pose_batch(hak_ctx* c, const hak_match_pair* d_matches, long stride, const int* d_counts, int npairs,
+                                     const hak_intrinsics* K1, const hak_intrinsics* K2, float threshold, float max_depth, int rounds,
+                                     hak_pose* d_inout, unsigned char* d_masks, float* d_xyz)
+{
+    if (list_args_batch(c, d_matches, d_counts, d_inout, npairs, stride, "d_matches must be 16-byte aligned")) return 1;
+    if (pose_args(K1, K2, threshold, max_depth) || refine_args(threshold, rounds)) return 1;
+    order_after_null_stream(c, c->stream);
+    hak_launch_pose_refit(c->stream, d_matches, stride, d_counts, 0, npairs, *K1, *K2, threshold, max_depth, rounds, d_inout, d_masks,
+                          d_xyz);
+    if (hipGetLastError() != hipSuccess) return fail("pose refit launch failed");
+    return 0;
+}
+
 // ----------------------------------------------------------- track linking and RANSAC absolute pose (kernels_pnp.hip)
 extern "C" int hak_link_tracks(hak_ctx* c, const hak_match_pair* d_A, int nA, const unsigned char* d_maskA, const float* d_xyzA,
                                const hak_match_pair* d_B, int nB, int max_index, hak_corr3d* d_out, int* count, hak_corr3d* h_out)

@@ -809,6 +809,11 @@ void hak_launch_fundamental_refit(hipStream_t st, const hak_match_pair* matches,
 void hak_launch_pose(hipStream_t st, const hak_match_pair* matches, long stride, const int* counts, int n_host, int npairs,
                      const hak_fundamental* d_F, const float* h_F, const hak_intrinsics& K1, const hak_intrinsics& K2,
                      float threshold, float max_depth, hak_pose* out, unsigned char* masks, float* xyz);
+// Gauss-Newton refit of a relative pose (kernels_poserefit.hip): record k is read from and rewritten to inout[k]; masks and xyz as
+// hak_launch_pose writes them, under the refitted pose; no scratch.
+void hak_launch_pose_refit(hipStream_t st, const hak_match_pair* matches, long stride, const int* counts, int n_host, int npairs,
+                           const hak_intrinsics& K1, const hak_intrinsics& K2, float threshold, float max_depth, int rounds,
+                           hak_pose* inout, unsigned char* masks, float* xyz);
 // RANSAC absolute pose (kernels_pnp.hip): 49 model words per hypothesis
 long hak_pnp_words(int npairs, int iterations);
 void hak_launch_pnp(hipStream_t st, const hak_corr3d* corr, long stride, const int* counts, int n_host, int npairs,

@@ -90,19 +90,6 @@ __device__ bool po_decompose(const float F[9], const hak_intrinsics& K1, const h
     return true;
 }
 
-// step 5 of the rule for one match: the normalised points (x, y, 1) of image 1 and b of image 2 under (R, t); true = in front,
-// *z1 = the depth along the first camera's ray
-__device__ __forceinline__ bool po_front(const double R[9], const double t[3], double x, double y, const double b[3], double bb,
-                                         double md, double* z1)
-{
-    double a[3];
-#pragma unroll
-    for (int i = 0; i < 3; i++) a[i] = (R[3 * i] * x + R[3 * i + 1] * y) + R[3 * i + 2];
-    const pt_depths d = pt_two_rays(a, pt_dot(a, a), b, bb, t);
-    *z1 = d.z1;
-    return d.det > 0.0 && d.z1 > 0.0 && d.z1 < md && d.z2 > 0.0 && d.z2 < md;
-}
-
 __global__ __launch_bounds__(PO_BLOCK) void k_pose(const hak_match_pair* __restrict__ base, long stride,
                                                    const int* __restrict__ counts, int n_host,
                                                    const hak_fundamental* __restrict__ d_F, const PoseCameras cam, float t2,
@@ -149,10 +136,10 @@ __global__ __launch_bounds__(PO_BLOCK) void k_pose(const hak_match_pair* __restr
             const double b[3] = {k2.x(r.z), k2.y(r.w), 1.0};
             const double bb = pt_dot(b, b);
             double z;
-            c[0] += po_front(Ra, u3, x, y, b, bb, md, &z) ? 1 : 0;
-            c[1] += po_front(Ra, nu3, x, y, b, bb, md, &z) ? 1 : 0;
-            c[2] += po_front(Rb, u3, x, y, b, bb, md, &z) ? 1 : 0;
-            c[3] += po_front(Rb, nu3, x, y, b, bb, md, &z) ? 1 : 0;
+            c[0] += pt_front(Ra, u3, x, y, b, bb, md, &z) ? 1 : 0;
+            c[1] += pt_front(Ra, nu3, x, y, b, bb, md, &z) ? 1 : 0;
+            c[2] += pt_front(Rb, u3, x, y, b, bb, md, &z) ? 1 : 0;
+            c[3] += pt_front(Rb, nu3, x, y, b, bb, md, &z) ? 1 : 0;
             c[4]++;
         }
     pt_block_sum<5, PO_WAVES>(c, part);
@@ -178,7 +165,7 @@ __global__ __launch_bounds__(PO_BLOCK) void k_pose(const hak_match_pair* __restr
                     x = k1.x(r.x);
                     y = k1.y(r.y);
                     const double b[3] = {k2.x(r.z), k2.y(r.w), 1.0};
-                    front = po_front(R, t, x, y, b, pt_dot(b, b), md, &z);
+                    front = pt_front(R, t, x, y, b, pt_dot(b, b), md, &z);
                 }
             }
             o.store(i, front, (float)(z * x), (float)(z * y), (float)z);

@@ -1,6 +1,7 @@
-// points_common.h -- what the point kernels share (kernels_pose.hip, kernels_triangulate.hip; the view of a list also serves
-// kernels_projected.hip): the 3-vector dot product, the
-// least-squares two-ray solve of step 5 of hak_recover_pose (also the solve of hak_triangulate, include/hipakaze.h), the intrinsics
+// points_common.h -- what the point kernels share (kernels_pose.hip, kernels_poserefit.hip, kernels_triangulate.hip; the view of a
+// list also serves kernels_projected.hip): the 3-vector dot product, the
+// least-squares two-ray solve of step 5 of hak_recover_pose (also the solve of hak_triangulate, include/hipakaze.h) and that
+// step's front test, the intrinsics
 // widened to float64, the kernel argument of two cameras and a model kept on the host, the close of the per-lane integer counters
 // and the store of a match's mask byte and point.  The gates on the solve stay with the kernels: they differ.
 // Every file that includes it is built with -ffp-contract=off, so one source expression gives one rounding in both kernels.
@@ -20,6 +21,31 @@ __device__ __forceinline__ pt_depths pt_two_rays(const double a[3], double aa, c
     d.z1 = (ab * bw - bb * aw) / d.det;
     d.z2 = (aa * bw - ab * aw) / d.det;
     return d;
+}
+
+// step 5 of hak_recover_pose for one match (also the front test of hak_refine_pose): a = R (x, y, 1), the first image's ray in
+// the second camera's frame
+__device__ __forceinline__ void pt_rotate(const double R[9], double x, double y, double a[3])
+{
+#pragma unroll
+    for (int i = 0; i < 3; i++) a[i] = (R[3 * i] * x + R[3 * i + 1] * y) + R[3 * i + 2];
+}
+// ... and its gates on the rays a and b of the two images under the baseline t; true = in front, *z1 = the depth along the first
+// camera's ray
+__device__ __forceinline__ bool pt_front_rays(const double a[3], const double t[3], const double b[3], double bb, double md,
+                                              double* z1)
+{
+    const pt_depths d = pt_two_rays(a, pt_dot(a, a), b, bb, t);
+    *z1 = d.z1;
+    return d.det > 0.0 && d.z1 > 0.0 && d.z1 < md && d.z2 > 0.0 && d.z2 < md;
+}
+// both, for the normalised point (x, y, 1) of image 1 and b of image 2 under (R, t)
+__device__ __forceinline__ bool pt_front(const double R[9], const double t[3], double x, double y, const double b[3], double bb,
+                                         double md, double* z1)
+{
+    double a[3];
+    pt_rotate(R, x, y, a);
+    return pt_front_rays(a, t, b, bb, md, z1);
 }
 
 // a camera's intrinsics widened to float64; x, y: a pixel coordinate normalised

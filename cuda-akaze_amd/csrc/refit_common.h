@@ -1,6 +1,6 @@
-// refit_common.h -- the least-squares refit scaffold of the three estimators (kernels_homography.hip, kernels_fundrefit.hip,
-// kernels_pnprefit.hip): what is not an estimator's own algebra, stated once.  One wave per list; every lane ends with the same values,
-// so every exit is wave-uniform.  float64 sums in the one order the rules fix: lane l takes records i = l mod 64 in ascending i, then
+// refit_common.h -- the least-squares refit scaffold of the estimators (kernels_homography.hip, kernels_fundrefit.hip,
+// kernels_pnprefit.hip, kernels_poserefit.hip): what is not an estimator's own algebra, stated once.  One wave per list; every
+// lane ends with the same values, so every exit is wave-uniform.  float64 sums in the one order the rules fix: lane l takes records i = l mod 64 in ascending i, then
 // hg_wsum's xor butterfly.  Every loop over a system is fully unrolled (compile-time register indices; no LDS, no scratch).
 // A refit estimator E is a view of ransac_common.h that adds REFINED (the tag of a record that a round improved) and
 // round(list, n, cur, &cnt, cand) const: *cnt = the inliers of cur; true and cand = the refitted model, false when the round fails

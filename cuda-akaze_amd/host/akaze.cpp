@@ -184,6 +184,21 @@ namespace akaze
         return r.candidate < 0 ? -1 : r.in_front;
     }
 
+    int cuRefinePose(const hak_match_pair* matches, int n, const hak_intrinsics& K1, const hak_intrinsics& K2, float R[9], float t[3],
+                     unsigned char* front_mask, float threshold, float max_depth, int rounds)
+    {
+        DeviceList<hak_match_pair> l("cuRefinePose", matches, n, R && t, front_mask != nullptr);
+        hak_pose r{};
+        for (int k = 0; k < 9; k++) r.R[k] = R[k];
+        for (int k = 0; k < 3; k++) r.t[k] = t[k];
+        r.n = n;
+        if (hak_refine_pose(NULL, l.d, n, &K1, &K2, threshold, max_depth, rounds, l.d_mask, NULL, &r)) die(l.name);
+        l.mask_to(front_mask);
+        for (int k = 0; k < 9; k++) R[k] = r.R[k];
+        for (int k = 0; k < 3; k++) t[k] = r.t[k];
+        return r.candidate < 0 ? -1 : r.in_front;
+    }
+
     int cuTriangulate(const hak_match_pair* matches, int n, const float* RtA, const float* RtB, const hak_intrinsics& KA,
                       const hak_intrinsics& KB, float* xyz, unsigned char* mask, float threshold, float max_depth, float min_sin)
     {

@@ -170,6 +170,28 @@ int hak_recover_pose(hak_ctx*, const hak_match_pair* d, int n, const float* F, c
     }
     return 0;
 }
+// as hak_recover_pose's stub on the record handed in: a pose with t = 0 has no model; five matches or more are "refitted"
+int hak_refine_pose(hak_ctx*, const hak_match_pair* d, int n, const hak_intrinsics* K1, const hak_intrinsics* K2, float threshold,
+                    float max_depth, int rounds, unsigned char* mask, float* xyz, hak_pose* inout)
+{
+    if (!inout || !K1 || !K2 || (n > 0 && !d) || rounds < 1 || rounds > 8 || !(threshold > 0.f) || !(max_depth > 0.f) ||
+        K1->fx == 0.f || K2->fy == 0.f) {
+        g_err = "bad argument";
+        return 1;
+    }
+    const bool model = inout->candidate >= 0 && (inout->t[0] != 0.f || inout->t[1] != 0.f || inout->t[2] != 0.f);
+    inout->inliers = inout->in_front = 0;
+    inout->candidate = model ? (n >= 5 ? 4 : inout->candidate) : -1;
+    inout->n = n;
+    for (int i = 0; i < n; i++) {
+        const bool in = model && d[i].x1 == d[i].x1 && i % 3 == 0;
+        inout->inliers += in;
+        inout->in_front += in;
+        if (mask) mask[i] = in;
+        if (xyz) xyz[3 * i] = xyz[3 * i + 1] = xyz[3 * i + 2] = in ? 1.f : 0.f;
+    }
+    return 0;
+}
 // as hak_recover_pose's stub: every record and every entry of a host view read, every mask byte and xyz float written; "kept" are
 // the indices that are multiples of 3, their point is (tA0 + tB0, 0, 1)
 int hak_triangulate(hak_ctx*, const hak_match_pair* d, int n, const float* RtA, const float* RtB, const hak_intrinsics* KA,

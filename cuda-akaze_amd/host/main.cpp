@@ -3,7 +3,7 @@
 // `nrepeats` times and cuMatch once, and prints the same five result lines.
 //
 //   hipakaze_demo [device] [left.pgm right.pgm] [nrepeats] [--dump file] [--api-checks] [--pair] [--homography] [--retain-best N]
-//                 [--retain-grid G] [--guided R] [--fundamental] [--refine N] [--epipolar R] [--pose FX FY CX CY]
+//                 [--retain-grid G] [--guided R] [--fundamental] [--refine N] [--epipolar R] [--pose FX FY CX CY] [--pose-refine N]
 //
 // --dump file   writes the host-side results as raw 104-byte AkazePoint records:
 //               int32 n1, n2, then n1 + n2 records of the float path (image 1 after cuMatch),
@@ -31,6 +31,10 @@
 //               pinhole intrinsics, the same for both cameras (hak_recover_pose: 1 px, no depth limit), and prints R, the unit
 //               baseline direction t and the counts; with --dump, appends after the fundamental section the 64-byte hak_pose record,
 //               the n front-mask bytes and the 3 n float32 of the points
+// --pose-refine N  behind --pose (ignored without it) refits that pose with the calibration over the matches that count under it, up
+//               to N rounds of 1..8 (cuRefinePose: 1 px, no depth limit), and prints the refitted R, t and the count; with --dump,
+//               appends after the pose section the refitted R (9 float32), t (3 float32), the count (int32, -1 = no pose) and the n
+//               bytes of its front mask
 // --retain-best N  both AkazeData get capacity N (instead of 10000) and Akazer::setRetainBest(true): an image with more keypoints
 //               keeps its N strongest (hak_set_retain_best), in raster order, on the float and the FAST path alike
 // --retain-grid G  Akazer::setRetainGrid(G), G in 8..128: an image with more keypoints than the capacity (N of --retain-best, else
@@ -110,6 +114,7 @@ int main(int argc, char** argv)
     bool apiChecks = false, pairCalls = false, homography = false, fundamental = false;
     int retainBest = 0, retainGrid = 0, refine = 0;
     bool pose = false;
+    int poseRefine = 0;
     hak_intrinsics poseK{0.f, 0.f, 0.f, 0.f};
     float guided = 0.f, epipolar = 0.f;
     {   // strip the options; what is left are the reference demo's positional arguments (main.cpp:131-135)
@@ -122,6 +127,7 @@ int main(int argc, char** argv)
             else if (!strcmp(argv[i], "--fundamental")) fundamental = true;
             else if (!strcmp(argv[i], "--guided") && i + 1 < argc) { guided = (float)std::atof(argv[++i]); homography = true; }
             else if (!strcmp(argv[i], "--refine") && i + 1 < argc) { refine = std::atoi(argv[++i]); fundamental = true; }
+            else if (!strcmp(argv[i], "--pose-refine") && i + 1 < argc) poseRefine = std::atoi(argv[++i]);
             else if (!strcmp(argv[i], "--pose") && i + 4 < argc) {
                 poseK.fx = (float)std::atof(argv[i + 1]); poseK.fy = (float)std::atof(argv[i + 2]);
                 poseK.cx = (float)std::atof(argv[i + 3]); poseK.cy = (float)std::atof(argv[i + 4]);
@@ -272,6 +278,21 @@ int main(int argc, char** argv)
             std::cout << "  R [" << poseRec.R[3 * r] << ", " << poseRec.R[3 * r + 1] << ", " << poseRec.R[3 * r + 2] << "]" << std::endl;
         std::cout << "  t [" << poseRec.t[0] << ", " << poseRec.t[1] << ", " << poseRec.t[2] << "]" << std::endl;
     }
+    float refR[9], refT[3];
+    int refFront = -1;
+    std::vector<unsigned char> refMask(good.size(), 0);
+    if (pose && poseRefine > 0) {
+        for (int k = 0; k < 9; k++) refR[k] = poseRec.R[k];
+        for (int k = 0; k < 3; k++) refT[k] = poseRec.t[k];
+        float t8 = timer.read();
+        refFront = akaze::cuRefinePose(good.data(), ngood, poseK, poseK, refR, refT, refMask.data(), 1.f, INFINITY, poseRefine);
+        float t9 = timer.read();
+        std::cout << "Refit of the relative pose (calibrated Gauss-Newton, up to " << poseRefine << " rounds): " << refFront
+                  << " matches count under it  (" << t9 - t8 << " ms)" << std::endl;
+        for (int r = 0; r < 3; r++)
+            std::cout << "  R [" << refR[3 * r] << ", " << refR[3 * r + 1] << ", " << refR[3 * r + 2] << "]" << std::endl;
+        std::cout << "  t [" << refT[0] << ", " << refT[1] << ", " << refT[2] << "]" << std::endl;
+    }
     if (guided > 0.f) {
         std::vector<hak_match_pair> gm(good.size());
         float t8 = timer.read();
@@ -373,6 +394,12 @@ int main(int argc, char** argv)
             dump.write((const char*)&poseRec, sizeof(poseRec));
             dump.write((const char*)front.data(), (size_t)ngood);
             dump.write((const char*)xyz.data(), sizeof(float) * 3 * (size_t)ngood);
+            if (poseRefine > 0) {
+                dump.write((const char*)refR, sizeof(refR));
+                dump.write((const char*)refT, sizeof(refT));
+                dump.write((const char*)&refFront, sizeof(refFront));
+                dump.write((const char*)refMask.data(), (size_t)ngood);
+            }
         }
     }
 

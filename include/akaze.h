@@ -48,6 +48,14 @@ namespace akaze
                       float R[9], float t[3], unsigned char* front_mask = nullptr, float threshold = 1.f,
                       float max_depth = __builtin_inff());
 
+    // cuRefinePose (hak_refine_pose): calibrated Gauss-Newton refit of a relative pose over the matches that count under it (inliers
+    // of the pose's own F at `threshold` px, in front of both cameras), iterated up to `rounds` (1..8) times, on the device: R and t
+    // (cuRecoverPose's, when that found a pose) are replaced by the refitted pose when as many matches count under it, the optional
+    // front_mask (n bytes) gets those matches, and the return value is their count -- never fewer than the count under the given
+    // pose at that threshold -- or -1 when the given pose is none (non-finite, or t = 0 as cuRecoverPose leaves it without a pose).
+    int cuRefinePose(const hak_match_pair* matches, int n, const hak_intrinsics& K1, const hak_intrinsics& K2, float R[9], float t[3],
+                     unsigned char* front_mask = nullptr, float threshold = 1.f, float max_depth = __builtin_inff(), int rounds = 3);
+
     // build-side addition: a fourth view.  cuTriangulate (hak_triangulate) triangulates a host match list under two known views,
     // on the device: RtA, RtB are 12 floats {R row-major, t} with Xc = R X + t (cuRecoverPose's, cuSolvePnP's or cuRefinePnP's R
     // and t side by side), NULL = the identity.  xyz, when not NULL, gets 3 n floats (the midpoint of the two rays' common

@@ -393,7 +393,8 @@ int hak_refine_fundamental_batch(hak_ctx* ctx, const hak_match_pair* d_matches, 
  *      float32(z1)) for such a match and (0, 0, 0) otherwise (3 n floats).  in_front = 0 is still a pose: candidate = -1 only
  *      comes from steps 1-3.
  * Every value reduced across lanes is an integer count, so the result does not depend on the launch shape.
- * Limits: the pose comes from F and the intrinsics, not from a five-point essential-matrix RANSAC; no lens distortion, no skew;
+ * Limits: the pose comes from F and the intrinsics, not from a five-point essential-matrix RANSAC (hak_refine_pose refits it
+ * with the calibration afterwards); no lens distortion, no skew;
  * no bundle adjustment; depths are a linear two-ray solve, not a reprojection-error minimum.  A planar scene or a pure rotation
  * gives an F that does not determine the pose: the call returns whatever wins, and in_front / inliers is the caller's signal.
  * Refused with a non-zero status and a message before any device is touched: a threshold that is not finite or not > 0, a
@@ -406,7 +407,8 @@ typedef struct hak_pose {
     float t[3];              /* unit length: the baseline's direction, its scale is not observable */
     int   inliers;           /* Sampson inliers of F at this call's threshold */
     int   in_front;          /* of those, the matches in front of both cameras under (R, t) */
-    int   candidate;         /* 0..3: which of the four decompositions won; -1 = no pose (R = identity, t = 0) */
+    int   candidate;         /* 0..3: which of the four decompositions won; 4 = refitted by hak_refine_pose; -1 = no pose
+                              * (R = identity, t = 0) */
     int   n;                 /* matches considered */
 } hak_pose;                  /* 64 bytes */
 /* one list, synchronous; ctx may be NULL (default stream); F: 9 floats on the HOST, row-major as hak_fundamental.F; d_mask (device,
@@ -422,6 +424,68 @@ int hak_recover_pose(hak_ctx* ctx, const hak_match_pair* d_matches, int n, const
 int hak_recover_pose_batch(hak_ctx* ctx, const hak_match_pair* d_matches, long stride, const int* d_counts, int npairs,
                            const hak_fundamental* d_F, const hak_intrinsics* K1, const hak_intrinsics* K2,
                            float threshold, float max_depth, hak_pose* d_out, unsigned char* d_masks, float* d_xyz);
+
+/* ---- calibrated Gauss-Newton refit of the relative pose, iterated (build-side addition; the stage behind hak_recover_pose).
+ * hak_recover_pose decomposes an F that was fitted with seven degrees of freedom and without the calibration; the refit fits the
+ * five that remain once K1 and K2 are known -- rotation and baseline direction -- to the Sampson error in pixels of the matches
+ * that count under the pose, re-scores, and repeats from the larger set.  A pure function of (matches, input record, K1, K2,
+ * threshold, max_depth, rounds); tests/pose_refit_ref.py is its bit-exact numpy statement.  float64, no FMA, + - * / sqrt only,
+ * except where float32 is named; records are read as by hak_find_fundamental; dot, cross and M v as hak_recover_pose defines them.
+ *   1. No model: 1 <= rounds <= 8, t2 = threshold * threshold in float32.  A record with candidate < 0 or a non-finite entry of R
+ *      or t, or whose pose has no F by step 2, gives the no-pose record of step 1 of hak_recover_pose and an all-zero mask and xyz.
+ *   2. The F of a pose (R, t as float32, widened): column j of E = [t]x R is (t1 R[2][j] - t2 R[1][j], t2 R[0][j] - t0 R[2][j],
+ *      t0 R[1][j] - t1 R[0][j]).  G = E K1^-1 row by row: G[i][0] = E[i][0] / fx1, G[i][1] = E[i][1] / fy1,
+ *      G[i][2] = (E[i][2] - G[i][0] cx1) - G[i][1] cy1.  F = K2^-T G column by column: F[0][j] = G[0][j] / fx2,
+ *      F[1][j] = G[1][j] / fy2, F[2][j] = (G[2][j] - F[0][j] cx2) - F[1][j] cy2.  Every entry is divided by F's entry of largest
+ *      |value| (ties to the smallest index) and rounded to float32, as in step 6 of hak_find_fundamental; no model if that entry is
+ *      0 or non-finite.  A match COUNTS under a pose when it is an inlier of this F by step 7 of hak_find_fundamental at t2 and lies
+ *      in front by step 5 of hak_recover_pose under (R, t) widened from float32, with the same max_depth gates: the mask
+ *      hak_recover_pose writes, taken under the pose's own F.  cur = the input pose, cnt = the matches that count under it.
+ *   3. One round, over the matches that count under cur = (R, t): a = (x, y, 1) and b the normalised points of step 5 of
+ *      hak_recover_pose, q = R a, c = cross(t, q), e = dot(b, c), v = cross(b, t), u_j = (R[0][j] v0 + R[1][j] v1) + R[2][j] v2
+ *      (j = 0, 1); the Sampson denominator in pixels p0 = c0 / fx2, p1 = c1 / fy2, p2 = u0 / fx1, p3 = u1 / fy1,
+ *      s = sqrt((p0 p0 + p1 p1) + (p2 p2 + p3 p3)); the residual res = e / s.  The tangent basis of t: k = the index of the
+ *      smallest |t_k| (ties to the smallest index), nv = cross(t, e_k) written out as (0, t2, -t1), (-t2, 0, t0) or (t1, -t0, 0),
+ *      b1 = nv / sqrt(dot(nv, nv)), b2 = cross(t, b1).  Five unknowns (w0, w1, w2, d3, d4) under the left perturbation
+ *      R' = (I + [w]x) R and the tangent step t' = t + d3 b1 + d4 b2, with s held fixed: the Jacobian row is
+ *      w = [ jw0 / s, jw1 / s, jw2 / s, dot(h, b1) / s, dot(h, b2) / s ], jw = cross(q, v), h = cross(q, b).
+ *      The 15 sums N[p][q] += w[p] w[q], p <= q, mirrored afterwards, and the 5 sums g[p] += -(w[p] res), in the order of
+ *      hak_find_homography's refit (lane l of one wave takes the matches i = l (mod 64) in ascending i, the others skipped, every
+ *      partial sum from 0.0; then an xor butterfly over 32, 16, .., 1).  [N | g] (5 x 6) is solved as step 4 of hak_refine_pnp
+ *      solves its 6 x 7; the solution is d.  Update: R' = C R with C the Cayley map of 0.5 (d0, d1, d2) exactly as step 5 of
+ *      hak_refine_pnp; tn_i = (t_i + d3 b1_i) + d4 b2_i, len = sqrt(dot(tn, tn)), t' = tn / len; both rounded to float32; then
+ *      the F of (R', t') by step 2.  The round fails if fewer than 5 matches count, a pivot is 0 or non-finite, an entry of d,
+ *      len, R' or t' is non-finite, or (R', t') has no F.
+ *   4. Acceptance: cnt' = the matches that count under (R', t').  The round is accepted iff cnt' >= cnt; then cur = (R', t'),
+ *      cnt = cnt'.  At most `rounds` rounds are run; the first that fails or is not accepted ends the loop.
+ *   5. Output: R, t = cur; in_front = cnt; inliers = the inliers of cur's F alone at this call's threshold; n = the matches
+ *      considered; candidate = 4 if a round was accepted and the input's otherwise (4 is >= 0: every reader of a hak_pose view
+ *      takes a refitted record as a model).  The optional mask gets the matches that count under cur, the optional xyz
+ *      (float32(z1 x), float32(z1 y), float32(z1)) for them and zeros elsewhere, as step 6 of hak_recover_pose.
+ * in_front never falls below the input pose's count RECOMPUTED BY STEP 2 AT THIS CALL'S THRESHOLD.  That need not be the input
+ * record's in_front field, which hak_recover_pose counted under the F it was handed, not under the pose's own F; a refitted
+ * record's `inliers` changes its meaning in the same way (inliers of the pose's F, not of the F that was decomposed).  A
+ * refitted record may be passed in again, and at another threshold.
+ * Every value reduced across lanes outside the fixed-order float64 sums is an integer count.
+ * Limits: the Sampson denominator is frozen within a round; plain Gauss-Newton, one step per round, no damping and no robust
+ * kernel; R is re-rounded to float32 every round and not re-orthonormalised; no five-point RANSAC stands behind it, so the
+ * input pose must already be near.  A pure rotation or a planar scene makes the t-columns vanish or the system ill-conditioned,
+ * and nothing rescues it: the round fails or is rejected and the record comes back unchanged.
+ * Refused with a non-zero status and a message before any device is touched: what hak_recover_pose(_batch) refuses (with
+ * h_inout / d_inout in place of F / h_out / d_out / d_F), and rounds outside 1..8.  Device code: csrc/kernels_poserefit.hip. */
+/* one list, synchronous; ctx may be NULL (default stream; the call needs no scratch and allocates nothing: calls without a
+ * context share one device-resident record and take it in turn).  K1, K2 are host arguments.  *h_inout (host): in = a record of
+ * hak_recover_pose or of an earlier refit, out = the result; d_mask (device, n bytes) and d_xyz (device, 3 n floats) may each be
+ * NULL */
+int hak_refine_pose(hak_ctx* ctx, const hak_match_pair* d_matches, int n, const hak_intrinsics* K1, const hak_intrinsics* K2,
+                    float threshold, float max_depth, int rounds, unsigned char* d_mask, float* d_xyz, hak_pose* h_inout);
+/* batched, asynchronous on the context's stream, layouts exactly as hak_recover_pose_batch; d_inout[k] (device) is read and
+ * rewritten in place, d_masks / d_xyz (each unless NULL) are overwritten with the refitted pose's -- in a chain the buffers
+ * hak_recover_pose_batch wrote -- so .. -> hak_recover_pose_batch -> hak_refine_pose_batch -> hak_link_tracks_batch ->
+ * hak_solve_pnp_batch -> .. needs no host synchronisation and no allocation */
+int hak_refine_pose_batch(hak_ctx* ctx, const hak_match_pair* d_matches, long stride, const int* d_counts, int npairs,
+                          const hak_intrinsics* K1, const hak_intrinsics* K2, float threshold, float max_depth, int rounds,
+                          hak_pose* d_inout, unsigned char* d_masks, float* d_xyz);
 
 /* ---- a third view: track linking and RANSAC absolute pose (build-side addition; the stages behind hak_recover_pose).  A second
  * hak_recover_pose for the next image pair has a unit baseline of its own, unrelated to the first pair's, so two relative poses do
