@@ -167,6 +167,9 @@ SYMBOLS = {
 TEST_SYMBOLS = {
     "hak_debug_plane": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
     "hak_debug_kcontrast": (C.c_int, [_vp, C.c_int, _fp]),
+    "hak_debug_arena_layout": (C.c_int, [_vp, C.POINTER(C.c_long), C.c_int]),
+    "hak_debug_arena_read": (C.c_int, [_vp, C.c_int, _vp]),
+    "hak_debug_arena_write": (C.c_int, [_vp, C.c_int, _vp]),
     "hak_op_lowpass": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int]),
     "hak_op_down_smooth": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "hak_op_kcontrast": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_float, _fp, _fp, _ip]),
@@ -193,6 +196,10 @@ TEST_SYMBOLS = {
     "hak_op_fast_level_tile": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_long, C.c_int, C.c_int, C.c_int,
                                          C.c_int, C.c_int, _ip, _fp, C.c_int, _ip]),
     "hak_op_fast_hessian": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _ip]),
+    "hak_op_hessian_planes": (C.c_int, [_vp, _vp, _vp, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _ip]),
+    "hak_op_fast_hessian_planes": (C.c_int, [_vp, _vp, _vp, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _ip]),
+    "hak_op_fast_base_planes": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, _ip, _ip, _ip,
+                                          _ip]),
     "hak_op_hessian_batch": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _ip]),
     "hak_op_fast_hessian_batch": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _ip]),
     "hak_debug_set_plane": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
@@ -475,6 +482,33 @@ class Akazer:
         out = np.zeros((whp[1], whp[0]), np.float32)
         check(lib.hak_debug_plane(self.ctx, img, kind, octave, sublevel, out.ctypes.data))
         return out
+
+    def arena_layout(self):
+        """hak_debug_arena_layout: {"ms", "elements" (32-bit words per image), "batch", "octaves": [{"w", "h", "p", "smooth", "flow", "tmp",
+        "lt": [ms offsets], "dxy": [ms offsets]}]} -- the layout as the library holds it, offsets in elements from the image's first"""
+        n = lib.hak_debug_arena_layout(self.ctx, None, 0)
+        if n < 0:
+            check(1)
+        buf = (C.c_long * n)()
+        assert lib.hak_debug_arena_layout(self.ctx, buf, n) == n
+        noct, ms = int(buf[0]), int(buf[1])
+        per = 6 + 2 * ms
+        octs = []
+        for o in range(noct):
+            q = [int(v) for v in buf[4 + o * per:4 + (o + 1) * per]]
+            octs.append(dict(w=q[0], h=q[1], p=q[2], smooth=q[3], flow=q[4], tmp=q[5], lt=q[6:6 + ms], dxy=q[6 + ms:6 + 2 * ms]))
+        return dict(ms=ms, elements=int(buf[2]), batch=int(buf[3]), octaves=octs)
+
+    def arena_read(self, img=0):
+        """hak_debug_arena_read: the whole arena of batch image `img` as uint32 words"""
+        out = np.zeros(self.arena_layout()["elements"], np.uint32)
+        check(lib.hak_debug_arena_read(self.ctx, img, out.ctypes.data))
+        return out
+
+    def arena_write(self, words, img=0):
+        words = np.ascontiguousarray(words, np.uint32)
+        assert words.shape == (self.arena_layout()["elements"],), words.shape
+        check(lib.hak_debug_arena_write(self.ctx, img, words.ctypes.data))
 
     def set_plane(self, kind, octave, sublevel, plane, img=0):
         """hak_debug_set_plane: dense (h, w) float32 -> plane (0 Lt, 2 Lx, 3 Ly) of the level.  An int32 array (a plane of the FAST

@@ -40,6 +40,40 @@ extern "C" int hak_debug_plane(hak_ctx* c, int img, int kind, int o, int s, floa
     return rc;
 }
 
+// the context's arena as the library holds it (HakLayout): 4 + noct * (6 + 2 ms) words
+//   {noct, ms, elements per image, batch} and per octave {w, h, p, smooth, flow, tmp, Lt(o, 0 .. ms-1), dxy(o, 0 .. ms-1)} -- offsets
+// in elements from the image's first.  Returns the number of words (also when `out` is NULL or n too small: ask first), -1 on a bad call
+extern "C" int hak_debug_arena_layout(hak_ctx* c, long* out, int n)
+{
+    if (!c) { fail("null context"); return -1; }
+    const HakLayout& L = c->L;
+    const int per = 6 + 2 * L.ms, need = 4 + L.noct * per;
+    if (!out || n < need) return need;
+    out[0] = L.noct; out[1] = L.ms; out[2] = L.arena; out[3] = c->cfg.batch;
+    for (int o = 0; o < L.noct; o++) {
+        long* q = out + 4 + o * per;
+        q[0] = L.oct[o].w; q[1] = L.oct[o].h; q[2] = L.oct[o].p;
+        q[3] = L.smooth_off[o]; q[4] = L.flow_off[o]; q[5] = L.tmp_off[o];
+        for (int s = 0; s < L.ms; s++) { q[6 + s] = L.lt(o, s); q[6 + L.ms + s] = L.dxy(o, s); }
+    }
+    return need;
+}
+// the whole arena of batch image `img` to / from the host, as it lies (bits are copied: float and int32 planes alike)
+extern "C" int hak_debug_arena_read(hak_ctx* c, int img, float* h_dst)
+{
+    if (!c || !h_dst || img < 0 || img >= c->cfg.batch) return fail("bad arena read");
+    if (hak_sync(c)) return 1;
+    HIP_TRY(hipMemcpy(h_dst, c->arena + (long)img * c->L.arena, sizeof(float) * (size_t)c->L.arena, hipMemcpyDeviceToHost));
+    return 0;
+}
+extern "C" int hak_debug_arena_write(hak_ctx* c, int img, const float* h_src)
+{
+    if (!c || !h_src || img < 0 || img >= c->cfg.batch) return fail("bad arena write");
+    if (hak_sync(c)) return 1;
+    HIP_TRY(hipMemcpy(c->arena + (long)img * c->L.arena, h_src, sizeof(float) * (size_t)c->L.arena, hipMemcpyHostToDevice));
+    return 0;
+}
+
 extern "C" int hak_debug_kcontrast(hak_ctx* c, int img, float* kc)
 {
     if (!c || img < 0 || img >= c->cfg.batch) return fail("bad image index");
@@ -295,25 +329,23 @@ extern "C" int hak_op_fast_fed_cycle(const int* src, int head, int sw, int sh, i
                                      long stride, int w, int h, int p, int nimg, const int* kcontrast, const float* tau, int nsteps)
 { return fed_cycle_t("hak_op_fast_fed_cycle", src, head, sw, sh, sp, smooth, flow, dst, tmp, stride, w, h, p, nimg, kcontrast, tau, nsteps); }
 
-extern "C" int hak_op_fast_base(const unsigned char* img, int sp, int* lt, int w, int h, int p, float var_base, int radius, float per,
-                                int* kc, int* hmax, int* hist, int* route)
+// The octave-0 prologue on the caller's planes: Lt, the gradient scratch and the sigma = 1 plane lie in ONE allocation, as in the arena
+// (the streaming kernels address their output planes as 32-bit offsets from the lower one and decline planes that lie too far apart).
+// Routes 1 and 2 write d_lt and d_grad, route 3 d_lt and d_smooth; the third plane is not touched.
+extern "C" int hak_op_fast_base_planes(const unsigned char* img, int sp, int* Lt, int* grad, int* smooth, int w, int h, int p, float var_base,
+                                       int radius, float per, int* kc, int* hmax, int* hist, int* route)
 {
     if (radius < 1 || radius > 5) return fail("radius must be 1..5");
     if (p % 4) return fail("pitch must be a multiple of 4");
+    if (!Lt || !grad || !smooth) return fail("null plane");
     int taps1[8], tapsb[8];
     op_taps<int>(1.f, 2, taps1);
     op_taps<int>(var_base, radius, tapsb);
     const HakKnobs kn = hak_knobs_from_env();
-    // Lt, the gradient scratch and the sigma = 1 plane in ONE allocation, as in the arena: the streaming kernels address their
-    // output planes as 32-bit offsets from the lower one and decline planes that lie too far apart
-    const size_t plane = (size_t)h * p;
-    int* buf = nullptr;
-    HIP_TRY(hipMalloc((void**)&buf, sizeof(int) * 3 * plane));
     HakImgState* st = nullptr;
-    if (hipMalloc((void**)&st, sizeof(HakImgState)) != hipSuccess) { (void)hipFree(buf); return fail("state alloc"); }
+    HIP_TRY(hipMalloc((void**)&st, sizeof(HakImgState)));
     (void)hipMemset(st, 0, sizeof(HakImgState));
     hak_launch_reset_state(nullptr, st, 1);
-    int *Lt = buf, *grad = buf + plane, *smooth = buf + 2 * plane;
     const bool based = hak_launch_base_level(nullptr, img, 0, sp, Lt, grad, 0, w, h, p, 1, taps1, tapsb, radius, st, per, 1, kn);
     if (!based) {                                                                 // hak_sequence.hip build_level, akaze.cpp:589-623
         hak_launch_lowpass(nullptr, img, 0, sp, smooth, 0, w, h, p, 1, taps1, 2);
@@ -321,12 +353,24 @@ extern "C" int hak_op_fast_base(const unsigned char* img, int sp, int* lt, int w
         hak_launch_lowpass(nullptr, img, 0, sp, Lt, 0, w, h, p, 1, tapsb, radius);
     }
     // which kernel hak_launch_base_level took: the cover of launch_base_stream (kernels_base_stream.hip; its plane-distance clauses
-    // cannot trip on the single allocation above)
+    // do not trip on planes of one allocation)
     const bool streamed = radius >= 2 && radius <= 4 && (w & 3) == 0 && w >= 16 && h >= 16 && sp % 4 == 0 &&
                           reinterpret_cast<uintptr_t>(img) % 4 == 0 && hak_stream_pays(kn.base_stream, w, h, 1);
     if (route) *route = !based ? 3 : streamed ? 1 : 2;
-    int rc = op_state_result<int>("FAST contrast", st, w, h, kc, hmax, hist);
-    if (!rc && hipMemcpy(lt, Lt, sizeof(int) * plane, hipMemcpyDeviceToDevice) != hipSuccess) rc = fail("hak_op_fast_base: copy");
+    return op_state_result<int>("FAST contrast", st, w, h, kc, hmax, hist);
+}
+extern "C" int hak_op_fast_base(const unsigned char* img, int sp, int* lt, int w, int h, int p, float var_base, int radius, float per,
+                                int* kc, int* hmax, int* hist, int* route)
+{
+    if (radius < 1 || radius > 5) return fail("radius must be 1..5");
+    if (p % 4) return fail("pitch must be a multiple of 4");
+    const size_t plane = (size_t)h * p;
+    int* buf = nullptr;
+    HIP_TRY(hipMalloc((void**)&buf, sizeof(int) * 3 * plane));
+    int rc = hak_op_fast_base_planes(img, sp, buf, buf + plane, buf + 2 * plane, w, h, p, var_base, radius, per, kc, hmax, hist, route);
+    // (the w columns of every row: the pad columns of the caller's plane are not the operator's to write)
+    if (!rc && hipMemcpy2D(lt, sizeof(int) * p, buf, sizeof(int) * p, sizeof(int) * w, h, hipMemcpyDeviceToDevice) != hipSuccess)
+        rc = fail("hak_op_fast_base: copy");
     (void)hipFree(buf);
     return rc;
 }
@@ -351,67 +395,65 @@ extern "C" int hak_op_fast_level_tile(const int* src, int head, int sw, int sh, 
     return rc;
 }
 
-// Hessian of one level into the reference's three planes (the kernels write the derivatives interleaved, HakLayout).  The interleaved
-// derivatives and the determinant lie in ONE allocation (see hak_op_fast_base).  route: 1 streaming, 2 tile kernel, 3 unfused pair
+// Hessian of one level of `nimg` images on the caller's planes: the source, the interleaved {Lx, Ly} plane (2 h p elements) and the
+// determinant of image i lie `stride` elements behind image i-1's, all in ONE allocation (see hak_op_fast_base_planes).
+// route: 1 streaming, 2 tile kernel, 3 unfused pair
 template <typename V>
-static int hessian_t(const char* who, const V* s, V* lx, V* ly, V* det, int w, int h, int p, int step, int* route)
+static int hessian_planes_t(const char* who, const V* s, V* dxy, V* det, long stride, int w, int h, int p, int nimg, int step, int* route)
 {
-    if (op_fast<V> && step < 1) return fail("step < 1");
-    const size_t plane = (size_t)h * p;
-    V* buf = nullptr;
-    HIP_TRY(hipMalloc((void**)&buf, sizeof(V) * 3 * plane));
-    V *dxy = buf, *dt = buf + 2 * plane;
+    if (nimg < 1 || step < 1 || p % 4 || p < w || stride % 4) return fail(std::string(who) + ": nimg < 1, step < 1 or a bad pitch or stride");
+    if (!s || !dxy || !det) return fail(std::string(who) + ": null plane");
     const HakKnobs kn = hak_knobs_from_env();
     const V thr = 0;
-    const bool fused = hak_launch_hessian_level(nullptr, s, dxy, dt, true, 0, w, h, p, 1, step, nullptr, nullptr, nullptr, 0, 0, thr);
-    hak_launch_deinterleave(nullptr, reinterpret_cast<const float*>(dxy), reinterpret_cast<float*>(lx), reinterpret_cast<float*>(ly), w, h, p);
+    const bool fused = hak_launch_hessian_level(nullptr, s, dxy, det, true, stride, w, h, p, nimg, step, nullptr, nullptr, nullptr, 0, 0, thr);
     // launch_hessian_level_t (kernels_hessian.hip): streaming where it pays and covers, else the tile kernel up to dilation 4
-    if (route) *route = !fused ? 3 : (hak_stream_pays(kn.hess_stream, w, h, 1) && hak_hessian_stream_covers(w, h, step, false)) ? 1 : 2;
+    if (route) *route = !fused ? 3 : (hak_stream_pays(kn.hess_stream, w, h, nimg) && hak_hessian_stream_covers(w, h, step, false)) ? 1 : 2;
     int rc = op_sync(who);
     if (!rc && fused != (step <= 4)) rc = fail(std::string(who) + ": unexpected route");
-    if (!rc && hipMemcpy(det, dt, sizeof(V) * plane, hipMemcpyDeviceToDevice) != hipSuccess) rc = fail(std::string(who) + ": copy");
-    (void)hipFree(buf);
     return rc;
 }
-extern "C" int hak_op_hessian(const float* s, float* lx, float* ly, float* det, int w, int h, int p, int step)
-{ return hessian_t("hak_op_hessian", s, lx, ly, det, w, h, p, step, nullptr); }
-extern "C" int hak_op_fast_hessian(const int* s, int* lx, int* ly, int* det, int w, int h, int p, int step, int* route)
-{ return hessian_t("hak_op_fast_hessian", s, lx, ly, det, w, h, p, step, route); }
+extern "C" int hak_op_hessian_planes(const float* s, float* dxy, float* det, long stride, int w, int h, int p, int nimg, int step, int* route)
+{ return hessian_planes_t("hak_op_hessian_planes", s, dxy, det, stride, w, h, p, nimg, step, route); }
+extern "C" int hak_op_fast_hessian_planes(const int* s, int* dxy, int* det, long stride, int w, int h, int p, int nimg, int step, int* route)
+{ return hessian_planes_t("hak_op_fast_hessian_planes", s, dxy, det, stride, w, h, p, nimg, step, route); }
 
-// Hessian of one level on a batch, either element type (tests/test_gpu_strip_seams.py).  Per image the arena slot holds the interleaved
-// derivatives, the determinant and then the source plane: the last image's last source row ends the allocation, as an image's last
-// row ends the caller's buffer when its pitch is its width.
+// ... and into the reference's three dense planes (the kernels write the derivatives interleaved, HakLayout), on a batch of either
+// element type.  Per image the slot of the operator's own allocation holds the interleaved derivatives, the determinant and then the
+// source plane: the last image's last source row ends the allocation, as an image's last row ends the caller's buffer when its
+// pitch is its width (tests/test_gpu_strip_seams.py).
 template <typename V>
-static int hessian_batch_t(const char* who, const V* s, V* lx, V* ly, V* det, int w, int h, int p, int nimg, int step, int* route)
+static int hessian_batch_t(const char* who, const V* s, V* lx, V* ly, V* det, int w, int h, int p, int nimg, int step, int* route, bool any_step)
 {
     if (nimg < 1 || step < 1 || p % 4 || p < w) return fail(std::string(who) + ": nimg < 1, step < 1 or a bad pitch");
     const size_t plane = (size_t)h * p;
     const long stride = 4 * (long)plane;
     V* buf = nullptr;
     HIP_TRY(hipMalloc((void**)&buf, sizeof(V) * (size_t)stride * nimg));
-    int rc = 0;
+    int rc = 0, rt = 0;
     if (hipMemcpy2D(buf + 3 * plane, sizeof(V) * stride, s, sizeof(V) * plane, sizeof(V) * plane, nimg, hipMemcpyDeviceToDevice) != hipSuccess)
         rc = fail(std::string(who) + ": copy in");
-    const HakKnobs kn = hak_knobs_from_env();
-    const V thr = 0;
-    if (!rc && !hak_launch_hessian_level(nullptr, buf + 3 * plane, buf, buf + 2 * plane, true, stride, w, h, p, nimg, step, nullptr, nullptr,
-                                         nullptr, 0, 0, thr))
-        rc = fail(std::string(who) + ": the fused kernels do not cover this dilation");
+    if (!rc) rc = hessian_planes_t(who, buf + 3 * plane, buf, buf + 2 * plane, stride, w, h, p, nimg, step, &rt);
+    if (!rc && rt == 3 && !any_step) rc = fail(std::string(who) + ": the fused kernels do not cover this dilation");
+    if (route) *route = rt;
     for (int i = 0; i < nimg && !rc; i++)
         hak_launch_deinterleave(nullptr, reinterpret_cast<const float*>(buf + i * stride), reinterpret_cast<float*>(lx + i * plane),
                                 reinterpret_cast<float*>(ly + i * plane), w, h, p);
-    if (route) *route = (hak_stream_pays(kn.hess_stream, w, h, nimg) && hak_hessian_stream_covers(w, h, step, false)) ? 1 : 2;
-    const hipError_t e = hipDeviceSynchronize();
-    if (!rc && e != hipSuccess) rc = fail(std::string(who) + ": " + hipGetErrorString(e));
-    if (!rc && hipMemcpy2D(det, sizeof(V) * plane, buf + 2 * plane, sizeof(V) * stride, sizeof(V) * plane, nimg, hipMemcpyDeviceToDevice) != hipSuccess)
-        rc = fail(std::string(who) + ": copy out");
+    if (!rc) rc = op_sync(who);
+    // (the w columns of every row: the pad columns of the caller's planes are not the operator's to write)
+    for (int i = 0; i < nimg && !rc; i++)
+        if (hipMemcpy2D(det + i * plane, sizeof(V) * p, buf + i * stride + 2 * plane, sizeof(V) * p, sizeof(V) * w, h, hipMemcpyDeviceToDevice) != hipSuccess)
+            rc = fail(std::string(who) + ": copy out");
     (void)hipFree(buf);
     return rc;
 }
+extern "C" int hak_op_hessian(const float* s, float* lx, float* ly, float* det, int w, int h, int p, int step)
+{ return hessian_batch_t<float>("hak_op_hessian", s, lx, ly, det, w, h, p, 1, step, nullptr, true); }
+extern "C" int hak_op_fast_hessian(const int* s, int* lx, int* ly, int* det, int w, int h, int p, int step, int* route)
+{ return hessian_batch_t<int>("hak_op_fast_hessian", s, lx, ly, det, w, h, p, 1, step, route, true); }
 extern "C" int hak_op_hessian_batch(const float* s, float* lx, float* ly, float* det, int w, int h, int p, int nimg, int step, int* route)
-{ return hessian_batch_t<float>("hak_op_hessian_batch", s, lx, ly, det, w, h, p, nimg, step, route); }
+{ return hessian_batch_t<float>("hak_op_hessian_batch", s, lx, ly, det, w, h, p, nimg, step, route, false); }
 extern "C" int hak_op_fast_hessian_batch(const int* s, int* lx, int* ly, int* det, int w, int h, int p, int nimg, int step, int* route)
-{ return hessian_batch_t<int>("hak_op_fast_hessian_batch", s, lx, ly, det, w, h, p, nimg, step, route); }
+{ return hessian_batch_t<int>("hak_op_fast_hessian_batch", s, lx, ly, det, w, h, p, nimg, step, route, false); }
 
 // ---- detector tail / descriptors on hand-made inputs (include/hipakaze.h; tests/test_gpu_literal.py)
 static HakBatch tail_batch(hak_ctx* c)

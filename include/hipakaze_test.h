@@ -22,6 +22,17 @@ enum { HAK_PLANE_LT = 0, HAK_PLANE_DET = 1, HAK_PLANE_LX = 2, HAK_PLANE_LY = 3 }
 /* copy plane (kind, octave, sublevel) of batch image `img`, densely packed w x h, to host */
 int hak_debug_plane(hak_ctx* ctx, int img, int kind, int octave, int sublevel, float* h_dst);
 int hak_debug_kcontrast(hak_ctx* ctx, int img, float* kcontrast);
+/* the context's arena, for the write-contract test of the whole launch sequence (tests/test_gpu_plane_guard.py), which poisons the
+ * pad columns of every plane and looks at them afterwards.  hak_debug_arena_layout reports the layout as the library holds it, so
+ * that no test restates the pitch rule: 4 + noct * (6 + 2 ms) words
+ *   {noct, ms, elements per image, batch}, then per octave {w, h, p, smooth, flow, tmp, Lt(o, 0 .. ms-1), dxy(o, 0 .. ms-1)}
+ * with every plane as its offset in elements from the image's first; Lt, smooth, flow and tmp are h rows of p elements, dxy is the
+ * interleaved {Lx, Ly} plane, h rows of 2 p.  Returns the number of words, also when out is NULL or n is too small (ask first);
+ * -1 for a NULL context.  hak_debug_arena_read / _write copy the whole arena of batch image `img` (elements-per-image 32-bit words,
+ * float or int32 as the last call left them) after synchronising the context. */
+int hak_debug_arena_layout(hak_ctx* ctx, long* out, int n);
+int hak_debug_arena_read(hak_ctx* ctx, int img, float* h_dst);
+int hak_debug_arena_write(hak_ctx* ctx, int img, const float* h_src);
 
 /* ---- single-stage operators on caller-provided device planes (pitch p
  * elements, dense row-major), used by the per-kernel parity tests.  Each is
@@ -49,6 +60,14 @@ int hak_op_rcp_check(unsigned lo_bits, unsigned hi_bits, unsigned long long* mis
 int hak_op_smooth_flow(const float* d_src, float* d_smooth, float* d_flow, int w, int h, int p,
                        int diffusivity, float kcontrast);                                               /* hLowPass(var 1) + hFlow, akaze.cpp:403-404 */
 int hak_op_hessian(const float* d_src, float* d_lx, float* d_ly, float* d_det, int w, int h, int p, int step); /* hHessianDeterminant 2531 */
+/* the Hessian of one level on the CALLER's planes, as the kernels write them: d_dxy the interleaved {Lx, Ly} plane (h rows of 2 p
+ * elements, element (y, x) = {Lx, Ly} at 2 (y p + x)), d_det the determinant; the three planes of image i lie `stride` elements
+ * behind image i-1's and all of them in ONE allocation (the streaming kernel addresses d_det as a 32-bit offset from d_dxy).  Every
+ * dilation >= 1; *route (may be NULL): 1 streaming, 2 tile kernel, 3 the unfused pair above dilation 4.  hak_op_hessian and the batch
+ * forms below run this on an allocation of their own and copy the w columns of every row out (the caller's pad columns are left
+ * alone), so that nothing beside the kernels' planes can be seen; here the
+ * write-contract test sees every word around them (tests/test_gpu_plane_guard.py). */
+int hak_op_hessian_planes(const float* d_src, float* d_dxy, float* d_det, long stride, int w, int h, int p, int nimg, int step, int* route);
 
 /* ---- the same stage operators on the integer FAST path (namespace fastakaze, akazed.cu:2781-4367): int32 planes in 16.16 fixed
  * point, uint8 images for the two operators that read one.  Each drives the `int` overload of the launcher its float twin drives
@@ -67,6 +86,10 @@ int hak_op_fast_lowpass(const int* d_src, int* d_dst, int w, int h, int p, float
  * lattice maximum and histogram of its sigma = 1 low-pass, through the fused prologue the context would pick under the knobs */
 int hak_op_fast_base(const unsigned char* d_u8, int sp, int* d_lt, int w, int h, int p, float var_base, int radius, float per,
                      int* kcontrast, int* hmax, int* hist300, int* route);
+/* hak_op_fast_base on the CALLER's planes, all three in one allocation: routes 1 and 2 write d_lt and d_grad (the gradient magnitude of
+ * the sigma = 1 image, read back by the histogram pass), route 3 writes d_lt and d_smooth (the sigma = 1 image); the third is not touched */
+int hak_op_fast_base_planes(const unsigned char* d_u8, int sp, int* d_lt, int* d_grad, int* d_smooth, int w, int h, int p, float var_base,
+                            int radius, float per, int* kcontrast, int* hmax, int* hist300, int* route);
 int hak_op_fast_down_smooth(const int* d_src, int* d_dst, int* d_smooth, int sw, int sh, int sp, int dw, int dh, int dp);
 int hak_op_fast_kcontrast(const int* d_smooth, int w, int h, int p, float per, int* kcontrast, int* hmax, int* hist300);
 int hak_op_fast_flow(const int* d_src, int* d_dst, int w, int h, int p, int diffusivity, int kcontrast);
@@ -88,6 +111,8 @@ int hak_op_fast_hessian(const int* d_src, int* d_lx, int* d_ly, int* d_det, int 
  * outputs alike), through the fused kernel the knobs pick; *route as above (1 streaming, 2 tile).  Fails above dilation 4. */
 int hak_op_hessian_batch(const float* d_src, float* d_lx, float* d_ly, float* d_det, int w, int h, int p, int nimg, int step, int* route);
 int hak_op_fast_hessian_batch(const int* d_src, int* d_lx, int* d_ly, int* d_det, int w, int h, int p, int nimg, int step, int* route);
+/* hak_op_hessian_planes on int32 planes */
+int hak_op_fast_hessian_planes(const int* d_src, int* d_dxy, int* d_det, long stride, int w, int h, int p, int nimg, int step, int* route);
 
 /* ---- detector-tail and descriptor stages on hand-made inputs (tests/test_gpu_literal.py: micro-fixtures whose expected
  * output is derived by hand from the cited reference statements).  They drive the SAME launchers as the launch sequence, on
