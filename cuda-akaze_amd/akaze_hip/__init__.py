@@ -117,6 +117,8 @@ SYMBOLS = {
     "hak_find_fundamental_batch": (C.c_int, [_vp, _vp, C.c_long, _vp, C.c_int, C.c_int, C.c_float, C.c_uint, _vp, _vp]),
     "hak_refine_fundamental": (C.c_int, [_vp, _vp, C.c_int, C.c_float, C.c_int, _vp, _vp]),
     "hak_refine_fundamental_batch": (C.c_int, [_vp, _vp, C.c_long, _vp, C.c_int, C.c_float, C.c_int, _vp, _vp]),
+    "hak_find_essential": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, C.c_int, C.c_float, C.c_uint, _vp, _vp]),
+    "hak_find_essential_batch": (C.c_int, [_vp, _vp, C.c_long, _vp, C.c_int, _vp, _vp, C.c_int, C.c_float, C.c_uint, _vp, _vp]),
     "hak_recover_pose": (C.c_int, [_vp, _vp, C.c_int, _fp, _vp, _vp, C.c_float, C.c_float, _vp, _vp, _vp]),
     "hak_recover_pose_batch": (C.c_int, [_vp, _vp, C.c_long, _vp, C.c_int, _vp, _vp, _vp, C.c_float, C.c_float, _vp, _vp, _vp]),
     "hak_refine_pose": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, C.c_float, C.c_float, C.c_int, _vp, _vp, _vp]),
@@ -762,6 +764,22 @@ def intrinsics(K):
         return K.reshape(()).copy()
     K = np.asarray(K, np.float64)
     return np.array((K[0, 0], K[1, 1], K[0, 2], K[1, 2]) if K.shape == (3, 3) else tuple(K.reshape(4)), INTRINSICS_DTYPE)
+
+
+def findEssential(matches, K1, K2=None, iterations=1024, threshold=1.0, seed=0, akazer=None):
+    """Five-point RANSAC essential matrix over a match list under known intrinsics (hipakaze.h hak_find_essential), on the device.
+    `matches` as findHomography's; K1, K2 as recoverPose's.  Returns (record of FUNDAMENTAL_DTYPE, inlier mask as a uint8 numpy
+    array): record["F"] is K2^-T E K1^-1 scaled to largest |entry| 1, scored in pixels as findFundamental's, record["root"] is
+    16 + the root of the winner's degree-10 polynomial; recoverPose, refinePose and matchEpipolar take the record as it is."""
+    ctx = _ctx_of(akazer)
+    d_m, n = _device_records(matches, MATCH_PAIR_DTYPE)
+    k1 = intrinsics(K1)
+    k2 = k1 if K2 is None else intrinsics(K2)
+    d_mask, _ = _out_buffers(n)
+    out = np.zeros((), FUNDAMENTAL_DTYPE)
+    check(lib.hak_find_essential(ctx, d_m.data_ptr(), n, k1.ctypes.data, k2.ctypes.data, int(iterations), float(threshold),
+                                 int(seed) & 0xFFFFFFFF, d_mask.data_ptr(), out.ctypes.data))
+    return (out,) + _out_host(n, d_mask)
 
 
 def recoverPose(matches, F_or_record, K1, K2=None, threshold=1.0, max_depth=float("inf"), akazer=None):

@@ -944,6 +944,42 @@ extern "C" int hak_recover_pose_batch(hak_ctx* c, const hak_match_pair* d_matche
     return 0;
 }
 
+// ----------------------------------------------------------- five-point RANSAC essential matrix (kernels_essential.hip)
+static int essential_args(const hak_intrinsics* K1, const hak_intrinsics* K2, int iterations, float threshold)
+{
+    if (!K1 || !K2) return fail("null intrinsics");
+    return ransac_args(iterations, threshold, 0) || intrinsics_args(K1) || intrinsics_args(K2);
+}
+
+extern "C" int hak_find_essential(hak_ctx* c, const hak_match_pair* d_matches, int n, const hak_intrinsics* K1, const hak_intrinsics* K2,
+                                  int iterations, float threshold, unsigned seed, unsigned char* d_mask, hak_fundamental* h_out)
+{
+    if (list_args(h_out, d_matches, n, "d_matches must be 16-byte aligned") || essential_args(K1, K2, iterations, threshold)) return 1;
+    if (hak_device_count() == 0) return fail("no HIP device: libhipakaze has no CPU fallback");
+    RansacScratch s;
+    if (ransac_scratch(c, hak_essential_blocks(1, iterations), hak_essential_words(1, iterations), s)) return 1;
+    hipStream_t st = c ? c->stream : nullptr;
+    order_after_null_stream(c, st);
+    hak_launch_essential(st, d_matches, n > 0 ? n : 1, nullptr, n, 1, *K1, *K2, iterations, threshold, seed, s.models, s.slots,
+                         static_cast<hak_fundamental*>(s.rec), d_mask, 0);
+    return single_tail(0, st, "essential", "essential download", h_out, s.rec, sizeof(hak_fundamental), s.block);
+}
+
+extern "C" int hak_find_essential_batch(hak_ctx* c, const hak_match_pair* d_matches, long stride, const int* d_counts, int npairs,
+                                        const hak_intrinsics* K1, const hak_intrinsics* K2, int iterations, float threshold,
+                                        unsigned seed, hak_fundamental* d_out, unsigned char* d_masks)
+{
+    if (list_args_batch(c, d_matches, d_counts, d_out, npairs, stride, "d_matches must be 16-byte aligned")) return 1;
+    if (essential_args(K1, K2, iterations, threshold)) return 1;
+    RansacScratch s;
+    if (ransac_scratch(c, (long)npairs * hak_essential_blocks(npairs, iterations), hak_essential_words(npairs, iterations), s)) return 1;
+    order_after_null_stream(c, c->stream);
+    hak_launch_essential(c->stream, d_matches, stride, d_counts, 0, npairs, *K1, *K2, iterations, threshold, seed, s.models, s.slots,
+                         d_out, d_masks, stride);
+    if (hipGetLastError() != hipSuccess) return fail("essential launch failed");
+    return 0;
+}
+
 // ----------------------------------------------------------- Gauss-Newton refit of a relative pose (kernels_poserefit.hip)
 extern "C" int hak_refine_pose(hak_ctx* c, const hak_match_pair* d_matches, int n, const hak_intrinsics* K1, const hak_intrinsics* K2,
                                float threshold, float max_depth, int rounds, unsigned char* d_mask, float* d_xyz, hak_pose* h_inout)

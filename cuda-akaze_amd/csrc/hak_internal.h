@@ -796,6 +796,13 @@ long hak_fundamental_words(int npairs, int iterations);
 void hak_launch_fundamental(hipStream_t st, const hak_match_pair* matches, long stride, const int* counts, int n_host, int npairs,
                             int iterations, float threshold, unsigned seed, unsigned* models, unsigned long long* slots,
                             hak_fundamental* out, unsigned char* masks, long mask_stride);
+// five-point RANSAC essential matrix (kernels_essential.hip): each hypothesis is stored as three virtual hypotheses of four models,
+// 37 model words each (hak_essential_words), and scored in hak_essential_blocks = hak_homography_blocks(npairs, 3 * iterations) blocks
+long hak_essential_words(int npairs, int iterations);
+int hak_essential_blocks(int npairs, int iterations);
+void hak_launch_essential(hipStream_t st, const hak_match_pair* matches, long stride, const int* counts, int n_host, int npairs,
+                          const hak_intrinsics& K1, const hak_intrinsics& K2, int iterations, float threshold, unsigned seed,
+                          unsigned* models, unsigned long long* slots, hak_fundamental* out, unsigned char* masks, long mask_stride);
 // hak_shared_record(): the current device's one record of HAK_REC_BYTES (kernels_fundrefit.hip; NULL on failure) for the synchronous
 // one-list calls that own none: both refits without a context, hak_recover_pose and hak_triangulate always.  They take it in turn.
 #define HAK_REC_BYTES 64         // room for the largest record of an estimator or refit (hak_abs_pose)

@@ -160,6 +160,17 @@ namespace akaze
         return r.inliers;
     }
 
+    int cuFindEssential(const hak_match_pair* matches, int n, const hak_intrinsics& K1, const hak_intrinsics& K2, float F[9],
+                        unsigned char* inlier_mask, int iterations, float threshold, unsigned seed)
+    {
+        DeviceList<hak_match_pair> l("cuFindEssential", matches, n, F != nullptr, inlier_mask != nullptr);
+        hak_fundamental r;
+        if (hak_find_essential(NULL, l.d, n, &K1, &K2, iterations, threshold, seed, l.d_mask, &r)) die(l.name);
+        l.mask_to(inlier_mask);
+        for (int k = 0; k < 9; k++) F[k] = r.F[k];
+        return r.inliers;
+    }
+
     int cuRefineFundamental(const hak_match_pair* matches, int n, float F[9], unsigned char* inlier_mask, float threshold, int rounds)
     {
         DeviceList<hak_match_pair> l("cuRefineFundamental", matches, n, F != nullptr, inlier_mask != nullptr);

@@ -58,6 +58,12 @@ int main()
             REQUIRE(cuRefineFundamental(pairs.data(), np, F, mask.data()) == (np + 2) / 3 && mask[3] == 1 && mask[1] == 0 && F[7] == 1.f);
             const hak_intrinsics K{1500.f, 1500.f, 960.f, 540.f};      // pose over the host list: exact-size mask
             float R[9], t[3];
+            {                                                       // the calibrated estimator: exact-size list and mask
+                float E[9];
+                REQUIRE(cuFindEssential(pairs.data(), np, K, K, E, mask.data()) == (np + 2) / 3 && mask[3] == 1 && mask[1] == 0 && E[7] == 1.f);
+                REQUIRE(cuFindEssential(pairs.data(), 4, K, K, E, mask.data()) == 0 && E[7] == 0.f && mask[0] == 0);
+                REQUIRE(cuFindEssential(pairs.data(), np, K, K, E) == (np + 2) / 3 && cuFindEssential(NULL, 0, K, K, E) == 0);
+            }
             REQUIRE(cuRecoverPose(pairs.data(), np, F, K, K, R, t, mask.data()) == (np + 2) / 3 && mask[3] == 1 && mask[1] == 0 &&
                     R[4] == 1.f && t[0] == 1.f);
             REQUIRE(cuRecoverPose(pairs.data(), np, F, K, K, R, t) == (np + 2) / 3);

@@ -134,6 +134,22 @@ int hak_find_fundamental(hak_ctx*, const hak_match_pair* d, int n, int iteration
     }
     return 0;
 }
+// as hak_find_fundamental's stub from five records on, the intrinsics read: root = 16
+int hak_find_essential(hak_ctx*, const hak_match_pair* d, int n, const hak_intrinsics* K1, const hak_intrinsics* K2, int iterations,
+                       float threshold, unsigned, unsigned char* mask, hak_fundamental* out)
+{
+    if (!out || !K1 || !K2 || (n > 0 && !d) || iterations < 1 || !(threshold > 0.f) || K1->fx == 0.f || K2->fy == 0.f) {
+        g_err = "bad argument";
+        return 1;
+    }
+    *out = hak_fundamental{{0.f, 0.f, 0.f, 0.f, 0.f, n >= 5 ? -1.f : 0.f, 0.f, n >= 5 ? 1.f : 0.f, 0.f}, 0, n >= 5 ? 0 : -1, n >= 5 ? 16 : 0, n};
+    for (int i = 0; i < n; i++) {
+        const bool in = n >= 5 && d[i].x1 == d[i].x1 && i % 3 == 0;
+        out->inliers += in;
+        if (mask) mask[i] = in;
+    }
+    return 0;
+}
 // as hak_find_fundamental's stub: every record read, every mask byte written, the record rewritten in place with root = 3
 int hak_refine_fundamental(hak_ctx*, const hak_match_pair* d, int n, float threshold, int rounds, unsigned char* mask,
                            hak_fundamental* inout)

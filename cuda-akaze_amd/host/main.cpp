@@ -4,6 +4,7 @@
 //
 //   hipakaze_demo [device] [left.pgm right.pgm] [nrepeats] [--dump file] [--api-checks] [--pair] [--homography] [--retain-best N]
 //                 [--retain-grid G] [--guided R] [--fundamental] [--refine N] [--epipolar R] [--pose FX FY CX CY] [--pose-refine N]
+//                 [--essential FX FY CX CY]
 //
 // --dump file   writes the host-side results as raw 104-byte AkazePoint records:
 //               int32 n1, n2, then n1 + n2 records of the float path (image 1 after cuMatch),
@@ -35,6 +36,10 @@
 //               to N rounds of 1..8 (cuRefinePose: 1 px, no depth limit), and prints the refitted R, t and the count; with --dump,
 //               appends after the pose section the refitted R (9 float32), t (3 float32), the count (int32, -1 = no pose) and the n
 //               bytes of its front mask
+// --essential FX FY CX CY  takes the place of --fundamental in front of --pose / --pose-refine / --epipolar (and of the dump's
+//               fundamental section): estimates the essential matrix under these pinhole intrinsics, the same for both cameras
+//               (cuFindEssential: RANSAC, 1024 five-point hypotheses, Sampson distance < 1 px, seed 0) and prints F = K^-T E K^-1;
+//               --refine still refits it as a fundamental matrix, which gives up the essential constraints
 // --retain-best N  both AkazeData get capacity N (instead of 10000) and Akazer::setRetainBest(true): an image with more keypoints
 //               keeps its N strongest (hak_set_retain_best), in raster order, on the float and the FAST path alike
 // --retain-grid G  Akazer::setRetainGrid(G), G in 8..128: an image with more keypoints than the capacity (N of --retain-best, else
@@ -116,6 +121,8 @@ int main(int argc, char** argv)
     bool pose = false;
     int poseRefine = 0;
     hak_intrinsics poseK{0.f, 0.f, 0.f, 0.f};
+    bool essential = false;
+    hak_intrinsics essK{0.f, 0.f, 0.f, 0.f};
     float guided = 0.f, epipolar = 0.f;
     {   // strip the options; what is left are the reference demo's positional arguments (main.cpp:131-135)
         int n = 1;
@@ -133,6 +140,12 @@ int main(int argc, char** argv)
                 poseK.cx = (float)std::atof(argv[i + 3]); poseK.cy = (float)std::atof(argv[i + 4]);
                 i += 4;
                 pose = fundamental = true;
+            }
+            else if (!strcmp(argv[i], "--essential") && i + 4 < argc) {
+                essK.fx = (float)std::atof(argv[i + 1]); essK.fy = (float)std::atof(argv[i + 2]);
+                essK.cx = (float)std::atof(argv[i + 3]); essK.cy = (float)std::atof(argv[i + 4]);
+                i += 4;
+                essential = fundamental = true;
             }
             else if (!strcmp(argv[i], "--epipolar") && i + 1 < argc) { epipolar = (float)std::atof(argv[++i]); fundamental = true; }
             else if (!strcmp(argv[i], "--retain-best") && i + 1 < argc) retainBest = std::atoi(argv[++i]);
@@ -235,10 +248,12 @@ int main(int argc, char** argv)
     int nfinlier = 0;
     if (fundamental) {
         float t6 = timer.read();
-        nfinlier = akaze::cuFindFundamental(good.data(), ngood, fund, finlier.data());
+        nfinlier = essential ? akaze::cuFindEssential(good.data(), ngood, essK, essK, fund, finlier.data())
+                             : akaze::cuFindFundamental(good.data(), ngood, fund, finlier.data());
         float t7 = timer.read();
-        std::cout << "Fundamental matrix (RANSAC 1024 x 1 px Sampson, no refit): " << nfinlier << " inliers of " << ngood << "  ("
-                  << t7 - t6 << " ms)" << std::endl;
+        std::cout << (essential ? "Essential matrix as F (RANSAC 1024 five-point x 1 px Sampson): "
+                                : "Fundamental matrix (RANSAC 1024 x 1 px Sampson, no refit): ")
+                  << nfinlier << " inliers of " << ngood << "  (" << t7 - t6 << " ms)" << std::endl;
         for (int r = 0; r < 3; r++)
             std::cout << "  [" << fund[3 * r] << ", " << fund[3 * r + 1] << ", " << fund[3 * r + 2] << "]" << std::endl;
         if (refine > 0) {
@@ -313,8 +328,9 @@ int main(int argc, char** argv)
         std::cout << "Epipolar matches (radius " << epipolar << " px, ratio 0.8 + cross-check): " << nepi << " against " << ngood
                   << " of the 2-NN match  (" << t9 - t8 << " ms)" << std::endl;
         float fund2[9];
-        const int nfinlier2 = akaze::cuFindFundamental(em.data(), nepi, fund2);
-        std::cout << "Fundamental matrix of the epipolar matches: " << nfinlier2 << " inliers of " << nepi << " against " << nfinlier
+        const int nfinlier2 = essential ? akaze::cuFindEssential(em.data(), nepi, essK, essK, fund2)
+                                        : akaze::cuFindFundamental(em.data(), nepi, fund2);
+        std::cout << (essential ? "Essential matrix of the epipolar matches: " : "Fundamental matrix of the epipolar matches: ") << nfinlier2 << " inliers of " << nepi << " against " << nfinlier
                   << " of " << ngood << std::endl;
     }
 

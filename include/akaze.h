@@ -32,6 +32,13 @@ namespace akaze
     int cuFindFundamental(const hak_match_pair* matches, int n, float F[9], unsigned char* inlier_mask = nullptr, int iterations = 1024,
                           float threshold = 1.f, unsigned seed = 0);
 
+    // build-side addition: five-point RANSAC essential matrix over a host match list under the two cameras' pinhole intrinsics, on the
+    // device (hak_find_essential): writes F = K2^-T E K1^-1 as cuFindFundamental writes its F (all zero when there is no model) and,
+    // when inlier_mask is not NULL, n bytes (1 = Sampson distance below `threshold` px); returns the inlier count.  It takes
+    // cuFindFundamental's place in front of cuRecoverPose and cuRefinePose when the calibration is known.
+    int cuFindEssential(const hak_match_pair* matches, int n, const hak_intrinsics& K1, const hak_intrinsics& K2, float F[9],
+                        unsigned char* inlier_mask = nullptr, int iterations = 1024, float threshold = 1.f, unsigned seed = 0);
+
     // build-side addition: rank-2 least-squares refit of a fundamental matrix over its inliers among a host match list, iterated up to
     // `rounds` (1..8) times, on the device (hak_refine_fundamental): F (e.g. cuFindFundamental's; an all-zero F stays as it is) is
     // replaced by the refitted matrix when that scores at least as well at `threshold`, the optional inlier_mask (n bytes) gets the

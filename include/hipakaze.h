@@ -300,7 +300,8 @@ typedef struct hak_fundamental {
     float F[9];              /* row-major, (x2 y2 1) F (x1 y1 1)^T = 0; the entry of largest |value| is 1 */
     int   inliers;           /* inliers of F */
     int   hypothesis;        /* winning hypothesis, -1 = no model (F = 0, inliers = 0) */
-    int   root;              /* which real root of the winner's cubic (0..2); 3 = refitted by hak_refine_fundamental */
+    int   root;              /* which real root of the winner's cubic (0..2); 3 = refitted by hak_refine_fundamental;
+                              * 16 + r = root r (0..9) of the degree-10 polynomial of hak_find_essential */
     int   n;                 /* matches considered */
 } hak_fundamental;           /* 52 bytes, as hak_homography */
 /* one list, synchronous; ctx may be NULL (default stream; the call allocates its own scratch); result to *h_out (host) */
@@ -393,8 +394,8 @@ int hak_refine_fundamental_batch(hak_ctx* ctx, const hak_match_pair* d_matches, 
  *      float32(z1)) for such a match and (0, 0, 0) otherwise (3 n floats).  in_front = 0 is still a pose: candidate = -1 only
  *      comes from steps 1-3.
  * Every value reduced across lanes is an integer count, so the result does not depend on the launch shape.
- * Limits: the pose comes from F and the intrinsics, not from a five-point essential-matrix RANSAC (hak_refine_pose refits it
- * with the calibration afterwards); no lens distortion, no skew;
+ * Limits: the pose comes from whatever F it is handed (hak_find_essential below is the calibrated estimator, hak_refine_pose the
+ * calibrated refit); no lens distortion, no skew;
  * no bundle adjustment; depths are a linear two-ray solve, not a reprojection-error minimum.  A planar scene or a pure rotation
  * gives an F that does not determine the pose: the call returns whatever wins, and in_front / inliers is the caller's signal.
  * Refused with a non-zero status and a message before any device is touched: a threshold that is not finite or not > 0, a
@@ -468,8 +469,8 @@ int hak_recover_pose_batch(hak_ctx* ctx, const hak_match_pair* d_matches, long s
  * refitted record may be passed in again, and at another threshold.
  * Every value reduced across lanes outside the fixed-order float64 sums is an integer count.
  * Limits: the Sampson denominator is frozen within a round; plain Gauss-Newton, one step per round, no damping and no robust
- * kernel; R is re-rounded to float32 every round and not re-orthonormalised; no five-point RANSAC stands behind it, so the
- * input pose must already be near.  A pure rotation or a planar scene makes the t-columns vanish or the system ill-conditioned,
+ * kernel; R is re-rounded to float32 every round and not re-orthonormalised; the
+ * input pose must already be near (hak_find_essential or hak_find_fundamental + hak_recover_pose give the start).  A pure rotation or a planar scene makes the t-columns vanish or the system ill-conditioned,
  * and nothing rescues it: the round fails or is rejected and the record comes back unchanged.
  * Refused with a non-zero status and a message before any device is touched: what hak_recover_pose(_batch) refuses (with
  * h_inout / d_inout in place of F / h_out / d_out / d_F), and rounds outside 1..8.  Device code: csrc/kernels_poserefit.hip. */
@@ -486,6 +487,83 @@ int hak_refine_pose(hak_ctx* ctx, const hak_match_pair* d_matches, int n, const 
 int hak_refine_pose_batch(hak_ctx* ctx, const hak_match_pair* d_matches, long stride, const int* d_counts, int npairs,
                           const hak_intrinsics* K1, const hak_intrinsics* K2, float threshold, float max_depth, int rounds,
                           hak_pose* d_inout, unsigned char* d_masks, float* d_xyz);
+
+/* ---- five-point RANSAC essential matrix (build-side addition; the calibrated estimator next to hak_find_fundamental, for the
+ * caller who knows K1 and K2 before the first match).  It samples five points, not seven, enforces the two essential constraints
+ * and stays determined on a scene with a dominant plane (not on an exactly planar one: see the limits).  It writes a hak_fundamental record -- F = K2^-T E K1^-1 scaled so that its entry of largest
+ * |value| is 1 -- scored by the float32 Sampson test in pixels of hak_find_fundamental, so inlier counts and masks compare directly
+ * with the seven-point call at the same threshold, and hak_recover_pose(_batch), hak_refine_pose(_batch), hak_match_epipolar(_batch)
+ * and hak_refine_fundamental(_batch) take the record as it is.  hak_refine_fundamental is legal on it but gives up the essential
+ * constraints; the calibrated refit is hak_refine_pose.  A pure function of (matches, K1, K2, iterations, threshold, seed),
+ * whatever the launch shape; tests/essential_ref.py is its bit-exact numpy statement.  float64, no FMA, + - * / only; records are
+ * read as by hak_find_fundamental.  The rule is Nister's five-point solver:
+ *   1. Hypothesis h (0 <= h < iterations, 1 <= iterations <= 65536) draws as step 1 of hak_find_fundamental (32 draws) until it has
+ *      five distinct indices; it is degenerate with fewer (always when n < 5).
+ *   2. Bearings: x = (x1 - cx1) / fx1, y = (y1 - cy1) / fy1, u = (x2 - cx2) / fx2, v = (y2 - cy2) / fy2, everything widened to
+ *      float64 first.  Degenerate if one of them is non-finite.  No Hartley normalisation.
+ *   3. The 5 x 9 system has the row [u x, u y, u, v x, v y, v, x, y, 1] per point, in draw order.  Gaussian elimination with COMPLETE
+ *      pivoting, c = 0..4: the pivot is the largest |entry| of rows c..4 and columns c..8, scanned row by row with >, so ties go to
+ *      the smallest row, then the smallest column; degenerate if it is 0 or non-finite; rows c and the pivot's are exchanged, then
+ *      columns c and the pivot's (in all five rows; the column permutation is remembered); f = M[r][c] / M[c][c],
+ *      M[r][q] = M[r][q] - f M[c][q] for r > c, q > c.  Four null vectors X, Y, Z, W by back substitution with the identity on the
+ *      free positions 5..8: for vector k, f_(5+j) = (j == k), and for i = 4..0
+ *      f_i = ((-M[i][5+k]) - M[i][i+1] f_(i+1) - .. - M[i][4] f_4) / M[i][i]; position p belongs to entry perm[p] of E.  Then the
+ *      last free coordinate is mixed in: X' = X - 1.125 W, Y' = Y + 0.625 W, Z' = Z - 0.875 W (each entry v - a w with
+ *      a = 1.125, -0.625, 0.875), W' = W, and E = x X' + y Y' + z Z' + W'.  Without the mix, w = 1 normalises a coordinate that is
+ *      exactly zero on the true solution when R = I (E = [t]x has a zero diagonal): a stereo rig, a forward-moving camera.
+ *   4. The ten cubic constraints.  Polynomials over v = (x, y, z, 1): a linear one has 4 coefficients, a quadratic one 10 (the pairs
+ *      i <= j of variables in lexicographic order), a cubic one 20 (the triples likewise).  Products accumulate from 0.0:
+ *      linear * linear adds a_i b_j to the coefficient of v_i v_j for i = 0..3, j = 0..3 in that order; quadratic * linear adds A_a b_k
+ *      for a = 0..9, k = 0..3 in that order; a sum of products keeps accumulating into the same coefficients, a difference is taken
+ *      between two finished products.  Row 0 is det E = E00 c0 + E01 c1 + E02 c2 with c0 = E11 E22 - E12 E21,
+ *      c1 = E12 E20 - E10 E22, c2 = E10 E21 - E11 E20 (c_k * E0k, accumulated in k).  Row 1 + 3 i + j is entry (i, j) of
+ *      2 E E^T E - tr(E E^T) E as sum over k of A_ik * E_kj with L_ik = sum over l of E_il * E_kl, t = (L00 + L11) + L22,
+ *      A_ik = 2 L_ik - t for i = k and 2 L_ik otherwise.  The columns are then put in Nister's order
+ *      x^3 y^3 x^2y xy^2 x^2z x^2 y^2z y^2 xyz xy | xz^2 xz x yz^2 yz y z^3 z^2 z 1.  Gauss-Jordan on the left 10 x 10 block with fixed
+ *      pivot columns 0..9 and partial pivoting over rows, without moving a row: the pivot of column c is the largest |entry| among
+ *      the rows that hold no pivot yet (>, ties to the smallest row); degenerate if it is 0 or non-finite; v_q = M[p][q] / M[p][c]
+ *      for q > c replaces the pivot row p, every other row gets M[r][q] = M[r][q] - M[r][c] v_q.
+ *   5. With e, f, g, h, i, j the right halves of the rows that hold the pivots of x^2z, x^2, y^2z, y^2, xyz, xy: k = e - z f,
+ *      l = g - z h, m = i - z j, e.g. k_x(z) = e_x + (e_xz - f_x) z + (e_xz2 - f_xz) z^2 + (-f_xz2) z^3; B(z) has the rows k, l, m and
+ *      the columns (x, y, 1), of degree 3, 3 and 4.  Polynomial products out[i + j] += a[i] b[j] in ascending (i, j) from 0.0;
+ *      c0 = l_y m_1 - l_1 m_y, c1 = l_1 m_x - l_x m_1, c2 = l_x m_y - l_y m_x, det B = (k_x c0 + k_y c1) + k_1 c2: eleven
+ *      coefficients.  Degenerate if the leading one is 0 or any is non-finite.
+ *   6. Real roots by a derivative chain.  b_k = c_k / c_10, bound = 1 + max |b_k| (degenerate if a b_k or the bound is non-finite).
+ *      Level d = 1..10 is the (10 - d)-th derivative over (10 - d)!: a_j = C(j + 10 - d, 10 - d) b_(j + 10 - d), j = 0..d (b_10 = 1),
+ *      evaluated by Horner as ((a_d z + a_(d-1)) z + ..) + a_0.  It has d brackets between -bound, the d - 1 points of level d - 1
+ *      and bound.  A bracket holds a root iff (p(lo) < 0) != (p(hi) < 0); there, 64 bisections with the replacement rule of step 5 of
+ *      hak_find_fundamental, and the bracket's point is 0.5 (lo + hi); a bracket without a root passes its upper end on as its
+ *      point (a split of an interval on which the next level is monotonic, so no root of that level is lost or found twice).  The
+ *      roots of level 10 are numbered r = 0..9 in ascending bracket order, brackets without a root not counted.  A root of even
+ *      multiplicity is missed.
+ *   7. Per root z: (x, y, 1) is the cross product of two rows of B(z) divided by its third component, of the pair (0, 1), (0, 2) or
+ *      (1, 2) whose third component is largest in magnitude (>, ties to the first); the model is dropped if that component is 0 or
+ *      non-finite.  Then three Newton steps on B(z) (x, y, 1)^T = 0 in (x, y, z): residuals r_i = (a_i x + b_i y) + c_i, Jacobian rows
+ *      [a_i, b_i, (a_i' x + b_i' y) + c_i'] (the derivatives' coefficients are k a_k), the step by Cramer's rule with the determinant
+ *      of step 4 of hak_find_fundamental, columns replaced by r, subtracted.  (The expanded degree-10 polynomial loses digits on planar
+ *      scenes; B(z) itself does not.)  E_k = ((x X'_k + y Y'_k) + z Z'_k) + W_k; F = K2^-T (E K1^-1) with
+ *      K^-1 = [1/fx 0 -(cx/fx); 0 1/fy -(cy/fy); 0 0 1] and the products of step 6 of hak_find_fundamental; divided by its entry of
+ *      largest |value| (ties to the smallest index) and rounded to float32.  The model is dropped if that entry is 0 or anything
+ *      is non-finite.
+ *   8. Scored as step 7 of hak_find_fundamental.  The model with the most inliers wins, ties to the smallest h, then the smallest
+ *      root.
+ * Output: a hak_fundamental record with root = 16 + r; hypothesis = -1 means no model (F all zero, inliers = 0, root = 0, mask all
+ * zero).  Limits: roots of even multiplicity are missed; no lens distortion or skew; a pure rotation still leaves t undetermined;
+ * on an EXACTLY planar scene two essential matrices fit every point and tie on inliers, the smallest (h, root) of them wins, and
+ * in_front / inliers of the pose behind it is the caller's signal; no local optimisation inside the RANSAC loop (hak_refine_pose is the refit).
+ * Refused with a non-zero status and a message before any device is touched: what hak_find_fundamental(_batch) refuses, NULL K1 /
+ * K2, fx or fy not finite or 0, a non-finite cx or cy.  Device code: csrc/kernels_essential.hip (ten lanes per hypothesis; the
+ * scaffold of csrc/ransac_common.h over three virtual hypotheses of four models per hypothesis). */
+/* one list, synchronous; ctx may be NULL (default stream; the call allocates its own scratch); K1, K2 are host arguments; result to
+ * *h_out (host); d_mask (device, n bytes) may be NULL */
+int hak_find_essential(hak_ctx* ctx, const hak_match_pair* d_matches, int n, const hak_intrinsics* K1, const hak_intrinsics* K2,
+                       int iterations, float threshold, unsigned seed, unsigned char* d_mask, hak_fundamental* h_out);
+/* batched, asynchronous on the context's stream, layouts as hak_find_fundamental_batch; counts are read on the device; K1 and K2
+ * are host arguments, the same for every pair of the call, as in hak_recover_pose_batch.  detect batch -> hak_match_knn2_batch ->
+ * hak_find_essential_batch -> hak_recover_pose_batch -> hak_refine_pose_batch needs no host synchronisation */
+int hak_find_essential_batch(hak_ctx* ctx, const hak_match_pair* d_matches, long stride, const int* d_counts, int npairs,
+                             const hak_intrinsics* K1, const hak_intrinsics* K2, int iterations, float threshold, unsigned seed,
+                             hak_fundamental* d_out, unsigned char* d_masks);
 
 /* ---- a third view: track linking and RANSAC absolute pose (build-side addition; the stages behind hak_recover_pose).  A second
  * hak_recover_pose for the next image pair has a unit baseline of its own, unrelated to the first pair's, so two relative poses do

@@ -198,13 +198,15 @@ int hak_op_ransac_shape(int npairs, int iterations, int* hp, int* hblocks);
  *                   the kernel), LDS chunks per block pass (192 rows, a tail counts; k_match: tiles of 128; k_knn2: 0), blocks of the
  *                   2-NN finish for n1 queries (1 = one block per pair, else two passes of that many)} */
 int hak_op_match_shape(int search, int n1, int n2, int npairs, int device_counts, int capacity, int scratch, int* plan);
-/* hak_debug_ransac_scratch: what the last hak_find_homography / hak_find_fundamental / hak_solve_pnp call (single or batch) on `ctx`
+/* hak_debug_ransac_scratch: what the last hak_find_homography / hak_find_fundamental / hak_find_essential / hak_solve_pnp call (single or batch) on `ctx`
  * left in the context's RANSAC scratch, so that the tests (tests/ransac_trace.py) see every hypothesis and every score block and not
  * only the winner.  Synchronises the context's stream and launches nothing.
  *   h_models  npairs * words_per_hypothesis * iterations 32-bit words, as they lie: [pair][word][iterations], word NW r + q = word q of
  *             model r, the last word the mask of the models that exist (bit r = model r).  28 words per hypothesis for the fundamental
  *             matrix (3 models of 9), 49 for P3P (4 models of 12); 0 for the homography, which keeps no models: nothing is copied and
- *             h_models may be NULL.
+ *             h_models may be NULL.  hak_find_essential keeps hypothesis h as the three virtual hypotheses 3 h + g of four models each
+ *             (root r = model r mod 4 of virtual hypothesis 3 h + r / 4): 37 words per hypothesis, and `iterations` (here, in h_slots
+ *             and in hak_op_ransac_shape) is 3 x the call's, which both take up to 65536: calls of up to 21845 hypotheses.
  *   h_slots   npairs * hblocks triples of int32 {inliers, hypothesis, model}: the best of each score block, [pair][block], decoded
  *             from the block's key on the host; a block without a model gives {0, -1, 0}.
  * npairs, iterations and hblocks (hak_op_ransac_shape) are those of that call.  Refused with a message: a NULL context, a NULL
